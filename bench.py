@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mpixels/s of the per-pixel raymarch on the BASELINE.json workloads.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c5]
+  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c5] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W [--config …]
 
@@ -11,7 +11,7 @@ constants, power 8, 256 march steps, 12 fractal iterations — BASELINE.json con
 BASELINE.json configurations, loaded from the reference's own scenefiles (tests/golden/scenes/, input data) through the
 library's loader.  With N > 1 the frame is strong-scaled: rank r renders row tiles t ≡ r (mod N) (rm_render_tiles) and
 rank 0 gathers them with RCCL (dist.gather) and de-interleaves; the gather is inside the timed region.  Rank 0 prints
-ONE JSON line.
+ONE JSON line.  --dump-outputs DIR also writes the frame the last timed step produced as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -240,6 +240,28 @@ def cpu_baseline(t, s, W, H, rows, gpu_frame):
     return base, parity
 
 
+DUMP_WHOLE_MAX_BYTES = 48 << 20   # frames up to this size are written whole; larger ones as a sample (≤ 48 MB in all)
+DUMP_SAMPLE_PIXELS = 1 << 21      # 2^21 pixels x 16 B + their indices x 8 B = 48 MB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame the last timed step handed its caller (H x W x 4; the RGBA8 image of --gather rgba8 as its
+    0..255 values), in float32.  Up to DUMP_WHOLE_MAX_BYTES: DIR/frame.npy, the whole frame.  Larger: DIR/frame_sample.npy
+    (N x 4), the pixels at N flat indices y·W + x drawn without replacement with a fixed seed, and DIR/frame_sample_index.npy
+    (float64, exact), those indices in ascending order.  The same arguments give the same inputs and the same sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = frame.cpu().numpy().astype(np.float32, copy=False)
+    H, W, ch = a.shape
+    if a.nbytes <= DUMP_WHOLE_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), a)
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), a.reshape(H * W, ch)[idx])
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
+
+
 def timed_frames(r, L, fence, render, n):
     """n frames after one untimed frame; returns (wall ms per frame, HIP-event ms per launch)."""
     import ctypes as C
@@ -329,10 +351,15 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N > 1 code path (RCCL process group, pipelined gather, de-interleave) even with one rank: "
                          "a rehearsal of the multi-GPU path on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one produced to DIR as .npy (float32; a fixed, seeded "
+                         "sample of its pixels when it is over 48 MB), so that two builds can be compared output for output")
     args = ap.parse_args()
     cfg = args.config
     if args.steps is None:
         args.steps = {"c1": 200, "c2": 100, "c3": 100, "c4": 50, "c5": 20}[cfg]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.warmup is None:
         # c2: the launcher's own measurements of this picture — tile shape (8 frames), settling of the tile order (4), light split
         # (4) — are over after 16 frames
@@ -431,6 +458,8 @@ def main():
         dist.all_reduce(kmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     kernel_ms = float(kmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_frame)
 
     variants = {}
     if distributed and not args.no_variants and args.gather_root == "zero":

@@ -48,3 +48,30 @@ def test_flop_model_arithmetic():
     assert bench.flop_model(t, s, abi.RmCounters(0, 0, 0, 1, 0, 0))[0] == 50 + 3 * 50 + 4 * 400
     t, s, W, H, _ = bench.build_config("c4")
     assert bench.flop_model(t, s, abi.RmCounters(0, 0, 0, 0, 1, 1))[0] == bench.FLOP_PER_FBM9 + bench.FLOP_PER_FBMD8
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the limit is written whole; a larger one as the same seeded sample of pixels on every run,
+    with their flat indices, float32 / float64 and at most 64 MB in all (the 7680x4320 frame of c5 included)."""
+    import numpy as np
+    import torch
+    assert bench.DUMP_WHOLE_MAX_BYTES <= 64 << 20 and bench.DUMP_SAMPLE_PIXELS * (4 * 4 + 8) <= 64 << 20
+    assert bench.DUMP_SAMPLE_PIXELS * 4 * 4 <= bench.DUMP_WHOLE_MAX_BYTES  # every frame that is sampled has more pixels than the sample
+    frame = torch.arange(36 * 64 * 4, dtype=torch.float32).reshape(36, 64, 4)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    assert os.listdir(tmp_path / "whole") == ["frame.npy"]
+    whole = np.load(tmp_path / "whole" / "frame.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, frame.numpy())
+    bench.dump_outputs(str(tmp_path / "rgba8"), frame.to(torch.uint8))  # --gather rgba8: the 8-bit image as its 0..255 values
+    assert np.array_equal(np.load(tmp_path / "rgba8" / "frame.npy"), frame.to(torch.uint8).numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_WHOLE_MAX_BYTES", frame.numel() * 4 - 1)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame_sample.npy", "frame_sample_index.npy"]
+    sample, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    assert sample.dtype == np.float32 and sample.shape == (100, 4) and idx.dtype == np.float64 and idx.shape == (100,)
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 36 * 64
+    assert np.array_equal(sample, frame.numpy().reshape(-1, 4)[idx.astype(np.int64)])
+    for name in ("frame_sample.npy", "frame_sample_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))

@@ -153,14 +153,13 @@ def test_camera_against_independent_numpy_restatement():
         assert close(list(cam.invProjView), inv.T.reshape(-1), rel=1e-4, abs_=1e-3)
 
 
-REF_SCENES = "/root/reference/scenefiles"
+REF_SCENES = os.path.join(GOLD, "scenes")  # the reference's scenefiles with every image they and getCubeMapWithType name
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="the reference checkout (with its texture_store) is only in the build container")
 def test_every_textured_scenefile_loads_with_its_images():
-    """Container-only integration check: every scenefile of the reference that names a texture loads through the
-    product's loader AND its image files decode (PNG, JPEG, GIF) into the texture slots the renderer will index; one
-    of them is rendered by the oracle.  Also the three sky-box sets of getCubeMapWithType."""
+    """Integration check: every scenefile of the reference that names a texture loads through the product's loader AND
+    its image files decode (PNG, JPEG, GIF) into the texture slots the renderer will index; one of them is rendered by
+    the oracle.  Also the three sky-box sets of getCubeMapWithType."""
     import glob
     from raymarcher_amd import Scene, abi, lib
     from raymarcher_amd.render import load_image
