@@ -405,6 +405,11 @@ int rm_debug_ray_planes(const RmCamera *cam, float *out48);
  * ratio < 0.3).  lip: no object's distance value changes by more than lip per unit of world length (+inf with a fractal in
  * the table): the seed of the table walk's skip test.  A pure function of the object table and the globals; no GPU needed. */
 int rm_debug_cull_bounds(const RmObject *objs, int numObjects, const RmGlobals *g, float *out14);
+/* Tests: 1 if the launcher renders this table with the plain single-Mandelbulb kernel — one Mandelbulb whose invModel is 1
+ * on the diagonal and a zero of either sign elsewhere in the three rows the distance function reads, scaleFactor exactly 1,
+ * power 8, both Julia seed components zero — whose evaluations skip the object transform, the ·scaleFactor and the Julia
+ * select (same bits); 0 otherwise (another table, or the general Mandelbulb kernel); -1 on a null pointer.  No GPU needed. */
+int rm_debug_bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g);
 /* Tests: the kernels' cheap exact forms against the IEEE operations for every one of the 2^32 inputs, on the current device
  * (≈2 s).  mismatches5[0]: the reciprocal (v_rcp_f32 + one Newton step inside 2^-126 <= |y| < 2^126, the IEEE expansion
  * outside) vs 1.0f / y; [1]: the bare fast form over its range; [2]: the square root (v_sqrt_f32 + residual selection, the

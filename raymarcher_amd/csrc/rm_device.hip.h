@@ -62,6 +62,10 @@ struct Counters { unsigned long long evals, iters, shades, fbm9, fbmd8, shapes; 
 namespace rm {
 
 
+// The single-Mandelbulb class (the kernels' BULB template parameter; 0 = the table walk): any object transform, power and
+// Julia seed, or the plain form that SceneBlock::bulbPlain describes.
+constexpr int kBulbGeneral = 1, kBulbPlain = 2;
+
 // Everything a frame needs, in one constant block (uploaded once per launch by the launcher).
 struct EvalRecord {
   float m[12];  // invModel[0..2], [4..6], [8..10], [12..14]
@@ -98,6 +102,9 @@ struct SceneBlock {
   float cullR2Soft;  // larger ball for soft-shadow rays (0 = none): beyond it 8·d/t >= 1, so the penumbra min() is settled
   int32_t cullOk;
   int32_t cullOneOk;  // 1 = every object is a primitive (cube … rectangle): the march loops may take the single-object fast path
+  // 1 = the single-Mandelbulb class in its plain form (bulb_plain in rm_kernels.hip): invModel 1 on the diagonal and ±0
+  // elsewhere, scaleFactor exactly 1, power 8, no Julia seed.  The launcher then runs the kBulbPlain render kernel.
+  int32_t bulbPlain;
   float cullLip;  // Lipschitz bound of every object's distance value per unit of world length (+inf with a fractal in the table)
   float cullLo[3], cullHi[3];  // axis-aligned box with the same property (see scene_cull_ball); cullBoxOk = 0: none
   int32_t cullBoxOk;
@@ -222,14 +229,16 @@ RM_DEV float sdMandelBrot(const SceneBlock *sb, float px, float py) {
 enum BulbMode { BULB_GENERIC = 0, BULB_TRIG8 = 1, BULB_ALGEBRAIC8 = 2 };
 // TRAP = false drops the orbit trap altogether: shadow marches, normal taps and AO taps never read it (with the select
 // form the compiler removed it there by itself; the v_min_f32 form is inline asm, so it is spelled out).
-template <int COUNT, int MODE, bool TRAPMIN, bool TRAP>
+// NOJULIA: the launcher has found both juliaSeed components zero (SceneBlock::bulbPlain): frag:782's test is false, c = pos
+// without a per-lane select.
+template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false>
 RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
   // the power-8 instantiations are only entered with sb->g.power == 8.0f: the literal (an inline constant of the multiplies)
   // instead of a scalar-register operand, which halves a VALU instruction's issue rate (profiles/r03_c_valu_microbench.md)
   const float power = (MODE == BULB_GENERIC) ? sb->g.power : 8.0f;
   const float pexp = (power - 1.0f) / 2.0f;
   const int iters = sb->s.fractalIters;
-  const bool julia = len2(sb->g.juliaSeed[0], sb->g.juliaSeed[1]) != 0.0f;  // frag:782
+  const bool julia = !NOJULIA && len2(sb->g.juliaSeed[0], sb->g.juliaSeed[1]) != 0.0f;  // frag:782
   // angles are power·acos(·) ∈ [0, power·pi] and power·atan(·,·) ∈ [−power·pi, power·pi], always finite: for
   // |power| < 1e6 they stay inside the contract range of sin/cos and the range guard can be dropped
   const bool angleSafe = (MODE != BULB_GENERIC) || fabs_(power) < 1.0e6f;
@@ -238,15 +247,24 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
   float m = dot(w, w);
   V4 trap = v4(fabs_(w.x), fabs_(w.y), fabs_(w.z), m);
   float dz = 1.0f;
-  V3 c = julia ? v3(sb->g.juliaSeed[0], sb->g.juliaSeed[1], 0.0f) : pos;
+  const V3 c = NOJULIA ? pos : (julia ? v3(sb->g.juliaSeed[0], sb->g.juliaSeed[1], 0.0f) : pos);
   for (int i = 0; i < iters; i++) {
     if (COUNT) cnt.iters++;
-    // ONE range check per iteration for its square root and its two reciprocals (trigonometric forms): with
-    // 2^-96 <= m < inf the unscaled sqrt is exact and r = sqrt(m) lies in [2^-48, 2^64), inside the reciprocal's fast range;
-    // max(|w.x|, |w.z|) <= r, so it only needs its lower bound.  Any lane outside (the exact origin, a point on the y axis,
-    // non-finite input): the whole wave takes the individually guarded forms — the same bits either way.
-    const bool raw = (MODE != BULB_ALGEBRAIC8) &&
-                     __ballot(!(m >= 1.262177448e-29f) || !(m < __builtin_inff()) || !(max_(fabs_(w.x), fabs_(w.z)) >= 1.17549435e-38f)) == 0;
+    // ONE range check per iteration for its square root and its two reciprocals (trigonometric forms), built from
+    // mx = max(|w.x|, |w.z|) — atan2's divisor, computed once for both — and m < inf.  Every lane with 2^-48 <= mx, m < inf:
+    //  * m = fma(w.z, w.z, fma(w.y, w.y, w.x·w.x)) >= RN(mx²) >= 2^-96 (every term >= +0, rounding monotone, 2^-96 a float),
+    //    so the unscaled sqrt is exact (sqrt_noscale_) and r = sqrt(m) lies in [2^-48, 2^64): inside the fast range
+    //    [2^-126, 2^126) of the reciprocal of w.y / r;
+    //  * RN(w.x²) and RN(w.z²) are each <= m < inf, so mx < 2^64; with mx >= 2^-48 atan2's reciprocal is in range too and its
+    //    mx == 0 case cannot occur;
+    //  * m < inf also rejects NaN.
+    // These are exactly the preconditions of the fast forms, so on every wave where the RAW step runs it gives the guarded
+    // step's bits.  Any lane outside (the exact origin, a point on the y axis, non-finite input): the whole wave takes the
+    // individually guarded forms — the same bits either way.  Against the former test (m >= 2^-96, m < inf, mx >= 2^-126) the
+    // guarded step now also runs on waves with a lane whose 2^-126 <= mx < 2^-48 — an iterate within 3.6e-15 of the y axis
+    // that is not on it: the same bits, and no more often than such points occur.
+    const float mx = absmax_(w.x, w.z);
+    const bool raw = (MODE != BULB_ALGEBRAIC8) && __ballot(!(mx >= 3.5527136788e-15f) || !(m < __builtin_inff())) == 0;
     // the iteration's arithmetic, instantiated twice: RAW (unguarded fast forms) and guarded — a wave-uniform branch
     auto step = [&](auto rawTag) __attribute__((always_inline)) {
       constexpr bool RAW = decltype(rawTag)::value;
@@ -281,7 +299,7 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
         }
         dz = fma(power * pm, dz, 1.0f);       // frag:787
         float b = power * acos_(RAW ? w.y * rcp_raw_(r) : divr_(w.y, r));  // frag:790
-        float a = power * atan2_<RAW>(w.x, w.z);                            // frag:791
+        float a = power * atan2_mx_<RAW>(w.x, w.z, mx);                     // frag:791
         float sb_, cb_, sa_, ca_;
         if (angleSafe) { sincos_inrange_(b, sb_, cb_); sincos_inrange_(a, sa_, ca_); }  // wave-uniform
         else { sincos_(b, sb_, cb_); sincos_(a, sa_, ca_); }
@@ -299,11 +317,12 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
   resColor = v4(m, trap.y, trap.z, trap.w);
   return divr_((0.25f * log_(m)) * sqrt_fast_(m), dz);  // frag:802
 }
-template <int COUNT, bool TRAPMIN, bool TRAP>
+// PLAIN (SceneBlock::bulbPlain: power 8, no Julia seed): only the two power-8 forms, without the Julia select.
+template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false>
 RM_DEV float sdMandelBulb(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
-  if (sb->g.power == 8.0f) {  // wave-uniform
-    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP>(sb, pos, resColor, cnt);
-    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP>(sb, pos, resColor, cnt);
+  if (PLAIN || sb->g.power == 8.0f) {  // wave-uniform
+    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN>(sb, pos, resColor, cnt);
+    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN>(sb, pos, resColor, cnt);
   }
   return bulbIterate<COUNT, BULB_GENERIC, TRAPMIN, TRAP>(sb, pos, resColor, cnt);
 }
@@ -411,8 +430,9 @@ RM_DEV float sdMengerSponge(const SceneBlock *sb, V3 p, V4 &res) {
 }
 
 // ---- scene union (frag:1406-1430) ---------------------------------------------------------------------
-// BULB=true is the single-Mandelbulb scene class (numObjects == 1, type MANDELBULB): same arithmetic,
-// no table walk.
+// BULB != 0 is the single-Mandelbulb scene class (numObjects == 1, type MANDELBULB): same arithmetic, no table walk.
+// kBulbPlain is its common case, classified once per launch (SceneBlock::bulbPlain): the object transform, the ·scaleFactor
+// and the Julia select drop out of every evaluation.
 // SKIP (table-walk classes, march loops): an object whose bounding ball is farther from EVERY live lane's point than that
 // lane's current minimum cannot lower it (its value is >= (|p_object| − boundR)·scaleFactor, and the update below is a strict
 // <): the wave passes over it after the transform — 6 instructions and a wave-uniform branch instead of the shape's 20-50.
@@ -425,7 +445,7 @@ RM_DEV float sdMengerSponge(const SceneBlock *sb, V3 p, V4 &res) {
 // TRACK (with SKIP): also return in `second` a lower bound of every OTHER object's value at p — the runner-up of the minimum:
 // the values of the objects evaluated, and (|p_object|·(1 − ε) − boundR)·scaleFactor for the ones passed over.  The march
 // loops use it for the single-object fast path (sdSceneOne below).
-template <bool BULB, int COUNT, int TRAP, bool SKIP, bool TRACK>  // TRAP: 0 none, 1 the shader's, 2 the sponge's .z alone (mengerImpl)
+template <int BULB, int COUNT, int TRAP, bool SKIP, bool TRACK>  // TRAP: 0 none, 1 the shader's, 2 the sponge's .z alone (mengerImpl)
 RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub, float &second) {
   SceneMin res;
   if (TRACK) second = __builtin_inff();
@@ -443,9 +463,35 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
     for (int c = 0; c < 4; c++)
       for (int r = 0; r < 3; r++) M[c * 3 + r] = BULB ? sb->objs[0].invModel[c * 4 + r] : o.m[c * 3 + r];
     const float scaleFactor = BULB ? sb->objs[0].scaleFactor : o.scaleFactor;
-    V3 po = v3(fma(M[6], p.z, fma(M[3], p.y, fma(M[0], p.x, M[9]))),
-               fma(M[7], p.z, fma(M[4], p.y, fma(M[1], p.x, M[10]))),
-               fma(M[8], p.z, fma(M[5], p.y, fma(M[2], p.x, M[11]))));  // frag:1417
+    auto transform = [&]() __attribute__((always_inline)) {
+      return v3(fma(M[6], p.z, fma(M[3], p.y, fma(M[0], p.x, M[9]))),
+                fma(M[7], p.z, fma(M[4], p.y, fma(M[1], p.x, M[10]))),
+                fma(M[8], p.z, fma(M[5], p.y, fma(M[2], p.x, M[11]))));  // frag:1417
+    };
+    V3 po;
+    if (BULB == kBulbPlain) {
+      // invModel is 1 on the diagonal and a zero of either sign everywhere else (bulb_plain in rm_kernels.hip).  For finite p
+      // every product but the diagonal one is a zero and every sum exact, so the transform above returns p itself, except
+      // that a zero coordinate may come out as the other zero (a sum of zeros is −0 only if all of them are).  The bulb's
+      // value and trap do not see the sign of a zero in pos:
+      //  * y (w.y and c.y) is read only through acos_(w.y / r), which maps ±0 alike (x > 0 is false for both), |w.y| and
+      //    squares; when the iteration writes a zero into w.y again, the same holds;
+      //  * z (w.z, c.z): atan2_'s x argument enters as |x|, max / min of magnitudes and x < 0 (false for ±0); else |w.z| and
+      //    squares;
+      //  * x (w.x = c.x = pos.x): flipping the sign of the x component of both w and c mirrors the whole iteration exactly.
+      //    atan2_ is odd in its y argument (magnitudes, then the sign bit of y copied), power·a negates exactly, sincos_inrange_
+      //    is odd / even in bits (k = round-half-even(2a/pi) negates, r negates, k mod 4 parity and quadrant flips match),
+      //    so sin·(pr·…) and the fma with c.x negate exactly; cos, m, dz, r, the range guard and the trap read only even
+      //    quantities.  The algebraic form's complex squarings are odd in sx and even in cz the same way.  A NaN generated
+      //    on the way (inf·0) is the default NaN in both mirror images, and from there both run identically.
+      // So the value and the trap of pos = p equal those of the transformed point, as long as p is finite: the transform
+      // turns a non-finite coordinate anywhere into NaN in all three (+0·inf), which p does not.  dot(p, p) < inf holds
+      // exactly when all three coordinates are finite; a wave with any other lane takes the transform.
+      po = p;
+      if (__ballot(!(dot(p, p) < __builtin_inff())) != 0ull) po = transform();
+    } else {
+      po = transform();
+    }
     if (SKIP && !BULB) {
       const float lim = fma(ub, o.invScale, o.boundR), pp = dot(po, po);
       const bool far = (lim >= 0.0f) && (pp > (lim * lim) * 1.00003f);
@@ -473,12 +519,12 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
       case RM_DEATHSTAR: d = sdDeathStar(po, 0.5f, 0.35f, 0.5f); break;
       case RM_RECTANGLE: d = sdBox(po, 0.5f, 0.5f, 0.0f); break;
       case RM_MANDELBROT: d = sdMandelBrot(sb, po.x, po.y); break;
-      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0>(sb, po, res.trap, cnt); break;
+      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain>(sb, po, res.trap, cnt); break;
       case RM_MENGERSPONGE: d = sdMengerSponge<TRAP>(sb, po, res.trap); break;
       case RM_SIERPINSKI: d = sdSierpinski(po); break;
       default: continue;
     }
-    float cur = d * scaleFactor;  // frag:1419
+    float cur = (BULB == kBulbPlain) ? d : d * scaleFactor;  // frag:1419; bulbPlain: scaleFactor is exactly 1
     if (TRACK) {
       // the runner-up: the old minimum if cur replaces it, else cur; a NaN value (it never becomes the minimum) voids the bound
       const float other = (cur < res.d) ? res.d : ((cur >= res.d) ? cur : -__builtin_inff());
@@ -489,7 +535,7 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
   }
   return res;
 }
-template <bool BULB, int COUNT, int TRAP = 1, bool SKIP = false>
+template <int BULB, int COUNT, int TRAP = 1, bool SKIP = false>
 RM_DEV SceneMin sdScene(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
   float unused;
   return sdSceneImpl<BULB, COUNT, TRAP, SKIP, false>(sb, p, cnt, ub, unused);
@@ -534,7 +580,7 @@ RM_DEV float nextMinBound(float d, float lipLen, float depth) {
 
 // frag:1436-1444
 // ub: an upper bound of sdScene at p + any tap (the taps are 0.0005 from p), +inf = none; SKIP as in sdScene.
-template <bool BULB, int COUNT, bool SKIP = false>
+template <int BULB, int COUNT, bool SKIP = false>
 RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
   const float ex = (1.0f * 0.5773f) * 0.0005f, ey = (-1.0f * 0.5773f) * 0.0005f;
   float d[4];
@@ -622,7 +668,7 @@ RM_DEV float sceneCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end, float R
   return min_(end, tExit);
 }
 // ub0: an upper bound of sdScene at ro (+inf = none), for the first evaluation's skip test.
-template <bool BULB, int COUNT, bool SHADOW, bool CULL = false>
+template <int BULB, int COUNT, bool SHADOW, bool CULL = false>
 RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side, Counters &cnt, float ub0 = __builtin_inff()) {
   if (CULL && COUNT != 1) {
     const bool softRay = SHADOW && sb->s.enableSoftShadow != 0;  // wave-uniform
@@ -742,7 +788,7 @@ RM_DEV V3 bumpNormal(V3 normal, V3 pos) {  // frag:1679-1691, BUMP_SCALE 10, BUM
 // ---- shading --------------------------------------------------------------------------------------------
 // frag:1729-1740
 // ubPos: an upper bound of sdScene at pos (+inf = none); a tap lies h·|nor| from it.
-template <bool BULB, int COUNT, bool SKIP = false>
+template <int BULB, int COUNT, bool SKIP = false>
 RM_DEV float calcAO(const SceneBlock *sb, V3 pos, V3 nor, Counters &cnt, float ubPos = __builtin_inff()) {
   float occ = 0.0f, sca = 1.0f;
   const float lipN = SKIP ? (sb->cullLip * len(nor)) * 1.001f : 0.0f;
@@ -931,7 +977,7 @@ RM_DEV bool lightTerm(const RmLight &li, const LightGeom &g, const Material &mat
 // same sequence of evaluations as in march<…, SHADOW = true>: same origin, direction, cull end, step cap, hit test.
 // Returns the mask of lights whose ray hit.  (The schedule simulators, scripts/sim/, price this at ×0.95 of the
 // instructions of the per-light loop on the bench frame and ×0.87 on the 8K Menger frame.)
-template <bool BULB, int COUNT, bool CULLS>
+template <int BULB, int COUNT, bool CULLS>
 RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float far, Counters &cnt) {
   const int maxSteps = sb->s.maxSteps;
   if (maxSteps <= 0) return 0u;  // march() then evaluates nothing and reports a miss
@@ -976,7 +1022,7 @@ RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float fa
 // CULLS: end marches at the scene's bounds and pass over far objects in the table walk (off in the ENV instantiations, whose
 // register budget it would break).
 // SPLIT (table-walk kernels without samplers or secondary rays only): see LightSplit.
-template <bool BULB, int COUNT, bool RES, bool CULLS, int SPLIT = 0>
+template <int BULB, int COUNT, bool RES, bool CULLS, int SPLIT = 0>
 RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &mat, V3 N, V3 p, V3 rd, float far, Counters &cnt,
                    float ubPos = __builtin_inff(), LightSplit split = LightSplit{-1, nullptr, 0}) {
   constexpr bool SKIP = CULLS && !BULB && COUNT != 1;
@@ -1063,7 +1109,7 @@ RM_DEV V3 bulbTrapColor(float ty, float tz, float tw) {
 }
 
 // frag:2318-2375.  `objs` is the per-lane-indexable copy of the object table (LDS).
-template <bool BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0>
+template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0>
 RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, Hit &info, float side, float maxT,
                         V3 bg, Counters &cnt, LightSplit split = LightSplit{-1, nullptr, 0}) {
   RenderOut out;
@@ -1190,7 +1236,7 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // SEC = false compiles main's secondary rays out (reflection loop, refraction): the launcher picks it when the settings or the
 // materials rule them out for the whole frame, so that what render() hands over for them (hit point, normal, direction) is not
 // carried across the shadow marches — fewer registers spilled around the hot loops, the same pixels.
-template <bool BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
   float ndcx, ndcy;

@@ -86,7 +86,7 @@ static_assert(RM_TILE_W == 4 || RM_TILE_W == 8 || RM_TILE_W == 16, "tile width: 
 // grid: workgroups 0 … splitTiles·numLights − 1 are those tiles' partial workgroups (tile = tileOrder[b / numLights], light b mod
 // numLights: primary march, surface, THAT light's shadow march, its result to splitStore), the last of which to arrive finishes
 // the tile's pixels from the stored results (shadePixel's mode 2: no march); the rest render the other tiles whole.
-template <bool BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
 __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES) : (ENV ? (SEC ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES) : (BULB ? (SEC ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES) : (SEC ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES))))) void render_kernel(const SceneBlock *__restrict__ sb, RowMap map, int W, int H,
                                                       int nRows, float4 *__restrict__ out,
                                                       float4 *__restrict__ bright,
@@ -935,6 +935,22 @@ void scene_eval_records(SceneBlock *h) {
   }
 }
 
+// SceneBlock::bulbPlain: the single-Mandelbulb class whose evaluations can skip the object transform, the ·scaleFactor and
+// the Julia select (rm_device.hip.h, sdSceneImpl, has the argument).  Decided on the bits: the three rows of invModel that
+// sdScene reads hold exactly 1 on the diagonal and a zero of either sign everywhere else (the scenefile loader writes −0 in
+// some of them); scaleFactor is exactly 1; power is 8; both Julia seed components are zero, so frag:782's length is 0.
+int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {
+  if (numObjects != 1 || objs[0].type != RM_MANDELBULB) return 0;
+  auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+  for (int c = 0; c < 4; c++)
+    for (int r = 0; r < 3; r++) {
+      const uint32_t u = bits(objs[0].invModel[c * 4 + r]);
+      if (c == r ? (u != 0x3f800000u) : ((u & 0x7fffffffu) != 0u)) return 0;
+    }
+  if (bits(objs[0].scaleFactor) != 0x3f800000u || !(g->power == 8.0f)) return 0;
+  return (g->juliaSeed[0] == 0.0f && g->juliaSeed[1] == 0.0f) ? 1 : 0;
+}
+
 int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                 const RmGlobals *g, const RmSettings *s, hipStream_t stream, DeviceState &ds, Slot **slotOut,
                 const RmResources &res, const int32_t *tileOrder = nullptr, uint32_t *tileCost = nullptr,
@@ -955,6 +971,7 @@ int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const
   h->ltc1 = res.ltc1; h->ltc2 = res.ltc2;
   scene_cull_ball(h);
   ray_planes(h);
+  h->bulbPlain = bulb_plain(objs, numObjects, g);
   h->tileOrder = tileOrder; h->tileCost = tileCost; h->tileCount = tileCount;
   h->tileShift = tileShift;
   h->splitTiles = splitTiles; h->splitStore = splitStore;
@@ -1337,11 +1354,14 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
       else if (envFeatures) { if (count) RM_LAUNCH(false, 1, true, false); else if (secondary) RM_LAUNCH(false, 0, true, false); else RM_LAUNCH_NOSEC(false, true, false); }
       else { if (count) RM_LAUNCH(false, 1, false, true); else if (secondary) RM_LAUNCH(false, 0, false, true); else RM_LAUNCH_NOSEC(false, false, true); }
     } else if (bulb) {
-      if (count == 1) RM_LAUNCH(true, 1, false, false);
-      else if (count == 2) RM_LAUNCH(true, 2, false, false);
-      else if (count == 3) RM_LAUNCH(true, 3, false, false);
-      else if (secondary) RM_LAUNCH(true, 0, false, false);
-      else RM_LAUNCH_NOSEC(true, false, false);
+      // the counted launches keep the general form; the production ones take the plain form where the launcher found it
+      const bool plain = slot->host->bulbPlain != 0;
+      if (count == 1) RM_LAUNCH(kBulbGeneral, 1, false, false);
+      else if (count == 2) RM_LAUNCH(kBulbGeneral, 2, false, false);
+      else if (count == 3) RM_LAUNCH(kBulbGeneral, 3, false, false);
+      else if (secondary) { if (plain) RM_LAUNCH(kBulbPlain, 0, false, false); else RM_LAUNCH(kBulbGeneral, 0, false, false); }
+      else if (plain) RM_LAUNCH_NOSEC(kBulbPlain, false, false);
+      else RM_LAUNCH_NOSEC(kBulbGeneral, false, false);
     } else {
       if (count == 1) RM_LAUNCH(false, 1, false, false);
       else if (count == 2) RM_LAUNCH(false, 2, false, false);
@@ -1680,6 +1700,11 @@ int rm_debug_cull_bounds(const RmObject *objs, int numObjects, const RmGlobals *
   out14[4] = blk.cullR2; out14[5] = blk.cullR2Soft; out14[6] = (float)blk.cullBoxOk;
   out14[13] = blk.cullLip;
   return RM_OK;
+}
+int rm_debug_bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {
+  if ((!objs && numObjects > 0) || !g) { set_error("null pointer"); return -1; }
+  if (numObjects < 0 || numObjects > RM_MAX_OBJECTS) { set_error("numObjects out of range"); return -1; }
+  return bulb_plain(objs, numObjects, g);
 }
 int rm_debug_set_tile_order(const int32_t *d_order, uint32_t *d_cost, int tileCount) {
   DeviceState *ds;

@@ -197,24 +197,32 @@ RM_DEV float atan_p(float s) {
   return p;
 }
 // RAW = true: the caller has checked, for the whole wave, that max(|x|, |y|) lies in the reciprocal's fast range
-// (2^-126 <= · < 2^126): the bare v_rcp_f32 + Newton form, no guard of its own.  Same bits as RAW = false there.
+// (2^-126 <= · < 2^126): the bare v_rcp_f32 + Newton form, no guard of its own, and no mx == 0 case.  Same bits as RAW = false
+// there.  mx = max(|x|, |y|) comes from the caller (the Mandelbulb iteration's range guard reads the same value).
 template <bool RAW = false>
-RM_DEV float atan2_(float y, float x) {
+RM_DEV float atan2_mx_(float y, float x, float mx) {
   float ax = fabs_(x), ay = fabs_(y);
-  float mx, mn;  // the contract's max / min of the magnitudes, |·| folded into the instructions
-  asm("v_max_f32 %0, |%1|, |%2|" : "=v"(mx) : "v"(x), "v"(y));
+  float mn;  // the contract's min of the magnitudes, |·| folded into the instruction
   asm("v_min_f32 %0, |%1|, |%2|" : "=v"(mn) : "v"(x), "v"(y));
   float t = RAW ? mn * rcp_raw_(mx) : divr_(mn, mx);
   // contract: a NaN quotient (0·inf, inf·0, NaN operand) or one that overflows (denormal operands) is 1, and 0 if mx == 0.
   // mn <= mx, so any other quotient is <= 1 and v_min_f32(t, 1) — which ignores a NaN operand — is t itself.
   t = hwmin1_(t);
-  t = (mx == 0.0f) ? 0.0f : t;
+  if (!RAW) t = (mx == 0.0f) ? 0.0f : t;  // RAW: mx >= 2^-126
   float s = t * t;
   float a = fma(t * s, atan_p(s), t);
   a = (ay > ax) ? (kPio2 - a) : a;
   a = (x < 0.0f) ? (kPi - a) : a;
   return u2f((f2u(a) & 0x7fffffffu) | (f2u(y) & 0x80000000u));
 }
+// max(|x|, |y|) as the contract's max (v_max_f32 with |·| source modifiers)
+RM_DEV float absmax_(float x, float y) {
+  float mx;
+  asm("v_max_f32 %0, |%1|, |%2|" : "=v"(mx) : "v"(x), "v"(y));
+  return mx;
+}
+template <bool RAW = false>
+RM_DEV float atan2_(float y, float x) { return atan2_mx_<RAW>(y, x, absmax_(x, y)); }
 
 RM_DEV float log2_(float x) {
   uint32_t ux = f2u(x) - 0x3f3504f3u;
