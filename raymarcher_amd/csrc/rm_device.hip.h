@@ -122,9 +122,11 @@ struct SceneBlock {
   uint32_t *tileCost;
   int32_t tileCount;
   // "Light split" (rm_kernels.hip): the first splitTiles tiles of tileOrder — the heaviest of a settled picture — are rendered by
-  // numLights workgroups each, one shadow march per pixel apiece (results in splitStore: per tile 64 pixels × (numLights × (object
-  // bits, penumbra / distance) + the primary march's result, 6 words)), and finished by a second launch that reads them instead of
-  // marching.  0 / null otherwise.
+  // numLights workgroups each, one shadow march per pixel apiece, in the same launch as every other tile; the last of a tile's
+  // workgroups to arrive finishes the tile from the stored results instead of marching.  splitStore holds splitTiles arrival
+  // counters, padded to 64 words, then splitTiles·64·(2·numLights + 6) floats: per tile and pixel numLights × (object bits,
+  // penumbra / distance) and the primary march's result (6 words).  The launcher zeroes the counters before every split launch.
+  // 0 / null otherwise.
   int32_t splitTiles;
   float *splitStore;
   // Uniforms of sdMengerSponge's prologue (frag:1052-1053: ani = smoothstep(−0.2, 0.2, −cos(0.5·iTime)), off = 1.5·sin(0.01·iTime)),

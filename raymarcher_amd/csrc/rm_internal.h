@@ -54,6 +54,27 @@ __host__ __device__ inline void tile_owner(int t, int N, int K, int &shard, int 
   if (c < N * (K - 1)) { shard = c % N; local = q * (shard == 0 ? K - 1 : K) + c / N; }
   else { shard = c - N * (K - 1) + 1; local = q * K + (K - 1); }
 }
+// ---- the launcher's timed A/B tuners (tile shape, light split: rm_kernels.hip, Tuner) --------------------------------------
+// A tuner runs candidate 0 for two frames, then candidate 1 for two frames, `rounds` times over, and times the second frame of
+// each pair in timing slot 2·round + candidate.  After the schedule, and until every timing is in, it runs candidate 0: the
+// enqueue path never waits for the timings.
+struct TuneStep {
+  int candidate;
+  int slot;  // the timing slot this frame records, -1 for an untimed frame
+};
+inline TuneStep tune_schedule(int frame, int rounds) {
+  if (frame >= 4 * rounds) return {0, -1};
+  const int candidate = (frame >> 1) & 1;
+  return {candidate, (frame & 1) ? 2 * (frame >> 2) + candidate : -1};
+}
+// The decision from the times ms[slot] of slots 0 … 2·rounds − 1: candidate 1 only if every time could be read and its best
+// time is below 0.97 × candidate 0's best time (it must win by 3 %).
+inline int tune_decide(const float *ms, int rounds, bool allRead) {
+  float best[2] = {1e30f, 1e30f};
+  for (int k = 0; k < 2 * rounds; k++) best[k & 1] = ms[k] < best[k & 1] ? ms[k] : best[k & 1];
+  return (allRead && best[1] < 0.97f * best[0]) ? 1 : 0;
+}
+
 // a shard's local tile ordinal → global tile (increasing in j)
 __host__ __device__ inline int tile_of(int shard, int j, int N, int K) {
   if (K < 2 || N < 2) return j * N + shard;

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -412,6 +413,15 @@ struct TileOrderState {
   unsigned long long sceneKey = 0;  // hash of the scene + camera + row map of the frame that recorded the costs in `mem`
   int sorts = 0;                     // consecutive frames of that picture whose order came from measured costs
 };
+#define HIP_OK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) {                                                                       \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
+      return RM_ERR_DEVICE;                                                                       \
+    }                                                                                             \
+  } while (0)
+
 // "Tile shape": which of the two tile shapes a picture renders faster with is scene-dependent (upright objects: 4 wide × 16 tall
 // tiles straddle fewer vertical silhouettes, so whole waves agree on the table walk's shortcuts more often — C2 at 1080p 0.866 →
 // 0.792 ms — while reflections_complex.json loses 5 % that way; profiles/r04_m_tile_shape.txt).  So the launcher MEASURES, per
@@ -419,34 +429,74 @@ struct TileOrderState {
 // run 4×16 (frame 3 timed), frames 4-7 repeat that (clocks ramp up over a process's first frames: one round would favour the later
 // candidate), and from then on the shape with the smaller best time is used.  Same pixels whatever the shape.  Single-bulb class: 8×8
 // always (measured: 4×16 +5 %).  RM_TILE_SHAPE / rm_debug_set_tile_shape: 0 tune, 3 always 8×8, 2 always 4×16.
-struct ShapeTune {
-  unsigned long long key = 0;
-  int W = 0, nRows = 0;
-  int frame = 0;    // frames of this picture enqueued so far
-  int chosen = -1;  // the decided tile shift, -1 while measuring
-  hipEvent_t ev[4][2] = {};  // [timed launch k: candidate k & 1 (0 = 8×8, 1 = 4×16), round k >> 1][start, stop]
-  bool timed[4] = {false, false, false, false};
-  void drop() {
-    for (auto &c : ev) for (auto &e : c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (bool &t : timed) t = false;
-  }
-};
 // "Light split" (launch_render) helps frames that are bound by the life of their heaviest waves when those waves are shadow marches
 // (C2 at 1080p: −35 %) and costs others a few per cent (redundant primary marches, cache write-backs: 4K frames +3…+9 %,
 // depth_of_field.json +10 %; profiles/r04_s_light_split.md).  So it is MEASURED per stream and settled picture like the tile shape:
 // settled frames 0-1 plain (frame 1 timed), 2-3 split (frame 3 timed), then the split stays only if it won by 3 %; plain while the
-// timings are outstanding.  A decision is shared by the device's other streams.
-struct SplitTune {
-  unsigned long long key = 0;
-  int W = 0, nRows = 0, tileShift = 0, div = 0;
-  int frame = 0;    // settled frames of this picture enqueued so far
-  int chosen = -1;  // -1 measuring, 0 plain, 1 split
-  hipEvent_t ev[2][2] = {};  // [0 plain, 1 split][start, stop]
-  bool timed[2] = {false, false};
+// timings are outstanding.
+// Both are a Tuner: the schedule and the rule of rm_internal.h (tune_schedule, tune_decide) over `rounds` rounds (2 for the tile
+// shape, 1 for the light split), timed with HIP events around the render kernel alone.  A decision is published in the device's
+// map of that tuner, where the device's other streams adopt it.
+using TuneKey = std::tuple<unsigned long long, int, int, int, int>;  // picture, W, nRows and 0, 0 (tile shape) or tile shift, divisor (light split)
+using TuneDecisions = std::map<TuneKey, int>;  // decided candidate by key; cleared when it reaches 256 entries
+constexpr int kTuneSlots = 4;                  // 2 candidates × up to 2 rounds
+struct Tuner {
+  TuneKey key;
+  int frame = 0;    // frames of this key enqueued so far
+  int chosen = -1;  // the decided candidate, -1 while measuring
+  hipEvent_t ev[kTuneSlots][2] = {};  // [timing slot][start, stop]
+  bool timed[kTuneSlots] = {};
   void drop() {
     for (auto &p : ev) for (auto &e : p) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    timed[0] = timed[1] = false;
+    for (bool &t : timed) t = false;
   }
+  // This frame's candidate and timing slot.  A new key drops the old events and takes over a decision another stream of the
+  // device has published; the tuner decides once every slot was recorded and its stop event reports done.
+  TuneStep step(const TuneKey &k, int rounds, TuneDecisions &decided) {
+    if (key != k) {
+      drop();
+      key = k; frame = 0; chosen = -1;
+      const auto known = decided.find(k);
+      if (known != decided.end()) chosen = known->second;
+    }
+    if (chosen < 0 && frame >= 4 * rounds) {
+      bool ready = true;
+      for (int i = 0; i < 2 * rounds; i++) ready = ready && timed[i] && hipEventQuery(ev[i][1]) == hipSuccess;
+      if (ready) {
+        float ms[kTuneSlots] = {};
+        bool ok = true;
+        for (int i = 0; i < 2 * rounds; i++) ok = ok && hipEventElapsedTime(&ms[i], ev[i][0], ev[i][1]) == hipSuccess;
+        chosen = tune_decide(ms, rounds, ok);
+        drop();
+        if (decided.size() >= 256) decided.clear();
+        decided[k] = chosen;
+      }
+    }
+    (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error
+    const TuneStep t = chosen >= 0 ? TuneStep{chosen, -1} : tune_schedule(frame, rounds);
+    frame++;
+    return t;
+  }
+  // Events around a timed frame's render kernel.  A slot whose events cannot be created is never recorded (slot = -1): the tuner
+  // then stays undecided, on candidate 0, until its key changes.
+  int begin(int &slot, hipStream_t stream) {
+    if (slot < 0) return RM_OK;
+    if (hipEventCreate(&ev[slot][0]) == hipSuccess && hipEventCreate(&ev[slot][1]) == hipSuccess) HIP_OK(hipEventRecord(ev[slot][0], stream));
+    else slot = -1;
+    return RM_OK;
+  }
+  int end(int slot, hipStream_t stream) {
+    if (slot < 0) return RM_OK;
+    HIP_OK(hipEventRecord(ev[slot][1], stream));
+    timed[slot] = true;
+    return RM_OK;
+  }
+};
+// What the launcher remembers per stream: calls on different streams of one device may overlap on the GPU.
+struct StreamState {
+  TileOrderState tileOrder;  // what the stream's feedback costs belong to
+  Tuner shape, split;        // the tile-shape and light-split tuners
+  size_t wfDenied = 0;       // smallest wavefront workspace (bytes) that could not be had on the stream; 0: none was refused
 };
 struct TimedLaunch { hipEvent_t ev[5]; int n; };  // n = 2 (one stage) or 3 (tile-order sort + render kernel)
 struct DeviceState {
@@ -456,17 +506,13 @@ struct DeviceState {
   unsigned long long *dCounters = nullptr;  // 10 words: evals, iterations, hits, clock stamps (2), span pointer, shades, fbm9, fbmd8, shapes
   std::vector<TimedLaunch> timed;           // rm_set_timing / rm_get_timing, per device
   int numCUs = 0;
-  std::map<hipStream_t, TileOrderState> tileOrder;  // what the feedback costs of each stream belong to
-  std::map<hipStream_t, ShapeTune> shapeTune;  // the tile-shape tuner's state per stream
-  std::map<std::tuple<unsigned long long, int, int>, int> shapeChoice;  // decisions by (picture, W, rows): other streams adopt them
-  std::map<hipStream_t, size_t> wfDenied;  // smallest wavefront workspace (bytes) that could not be had on a stream
+  std::map<hipStream_t, StreamState> streams;
+  TuneDecisions shapeChoice, splitChoice;  // the tuners' decisions, adopted by the device's other streams
   const int32_t *dbgTileOrder = nullptr;  // rm_debug_set_tile_order (experiments): overrides the modes below
   uint32_t *dbgTileCost = nullptr;
   int dbgTileCount = 0;
   int lastPath = 0;  // rm_debug_last_path: the schedule of the most recent render launch on this device
   int lastSplit = 0; // rm_debug_last_split: tiles that launch rendered one light per workgroup (0: none)
-  std::map<hipStream_t, SplitTune> splitTune;  // the light split's tuner per stream
-  std::map<std::tuple<unsigned long long, int, int, int, int>, int> splitChoice;  // decisions by (picture, W, rows, tile shape, divisor)
 };
 std::atomic<int> g_tileOrderMode{-1};  // rm_set_tile_order: -1 = take RM_TILE_ORDER or the default
 constexpr int kDefaultTileOrder = 1;
@@ -477,14 +523,14 @@ std::atomic<bool> g_lightSplitForce{false};  // rm_debug_set_light_split with a 
 std::atomic<int> g_lightSplit{-1};  // rm_debug_set_light_split: -1 = the RM_LIGHT_SPLIT environment variable (default 256), 0 off, n: the heaviest 1/n of the tiles
 std::atomic<int> g_kernelPath{0};  // rm_set_kernel_path: 0 auto, 1 one lane per pixel, 5 wavefront pipeline
 
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
-      return RM_ERR_DEVICE;                                                                       \
-    }                                                                                             \
-  } while (0)
+// A knob for A/B runs (the defaults are the measured best), read once per process by its caller (a static): `def` if the variable
+// is unset, otherwise atoi of its text (0 when empty), clamped to [lo, hi].  Where an rm_* call sets the same thing (the g_* atomics
+// above), the call takes precedence.
+int env_int(const char *name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+  const char *e = std::getenv(name);
+  const int v = e ? std::atoi(e) : def;
+  return v < lo ? lo : (v > hi ? hi : v);
+}
 
 int new_slot(Slot *s) {
   HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&s->host), sizeof(SceneBlock), hipHostMallocDefault));
@@ -871,7 +917,7 @@ void scene_cull_ball(SceneBlock *h) {
     lo[k] -= m; hi[k] += m;
     boxOk = boxOk && std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k] && std::fabs(lo[k]) < 1e6 && std::fabs(hi[k]) < 1e6;
   }
-  static const bool boxOn = [] { const char *e = getenv("RM_CULL_BOX"); return !e || atoi(e) != 0; }();
+  static const bool boxOn = env_int("RM_CULL_BOX", 1) != 0;
   // Only where the box is much tighter than the ball (flat or elongated scenes: a floor slab, a row of objects): for a compact
   // scene — the lone Menger cube of C5: box / ball volume 0.39 — the three reciprocals per ray cost more than the 5 % of
   // evaluations they save (measured: 21.9 -> 22.3 ms), while directional_light_2.json (0.07) executes 16 % fewer evaluations.
@@ -1018,6 +1064,301 @@ bool wavefront_pays(const RmObject *objs, int numObjects, int bounces, size_t pi
   return bounces >= (skip_applies(objs, numObjects) ? 2 : 1) && pixels >= (size_t(1) << (tileShard ? 21 : 22));
 }
 
+// ---- launch_render's steps --------------------------------------------------------------------------------------------------
+// What decides which kernels a frame takes.
+struct FrameClass {
+  bool bulb, twoD, envFeatures, textured, secondary;
+  bool wfOk, wfSkip;  // the wavefront pipeline covers this frame; its kernels take the table walk's pass-over test
+  int wfBounces;      // its reflection generations
+};
+FrameClass classify_frame(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
+                          const RmSettings *s, int count) {
+  FrameClass fc{};
+  fc.bulb = numObjects == 1 && objs[0].type == RM_MANDELBULB;
+  fc.twoD = g->isTwoD != 0;
+  auto nonzero3 = [](const float *v) { return v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f; };
+  fc.envFeatures = (s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SKY_BACKGROUND | RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)) != 0;
+  // anything that reads a sampler or takes the area-light branches: object textures, sky box, emissive rectangles, area lights
+  fc.textured = s->enableSkyBox != 0;
+  for (int i = 0; i < numObjects; i++) fc.textured = fc.textured || objs[i].texLoc != -1 || objs[i].isEmissive;
+  for (int i = 0; i < numLights; i++) fc.textured = fc.textured || lights[i].type == RM_LIGHT_AREA;
+  // The wavefront pipeline (rm_wavefront.hip.h) covers the table-walk classes whose evaluations cost the same on every
+  // lane: no Mandelbulb / 2-D Mandelbrot in the table, no samplers or procedural layers, no refraction.
+  fc.wfOk = !fc.bulb && !count && !fc.envFeatures && !fc.textured && !fc.twoD && s->maxSteps >= 1 && s->numReflection <= kWfMaxBounces;
+  bool anyReflective = false, anyTransparent = false;
+  for (int i = 0; i < numObjects; i++) {
+    if (objs[i].type == RM_MANDELBULB || objs[i].type == RM_MANDELBROT) fc.wfOk = false;
+    if (s->enableRefraction && nonzero3(objs[i].cTransparent)) fc.wfOk = false;
+    anyReflective = anyReflective || nonzero3(objs[i].cReflective);
+    anyTransparent = anyTransparent || nonzero3(objs[i].cTransparent);
+  }
+  fc.wfBounces = (s->enableReflection && anyReflective) ? s->numReflection : 0;
+  // whether main's secondary rays (frag:2491-2570) can fire for any pixel of this frame: a reflective object with reflection on and
+  // at least one bounce, or a transparent one with refraction on — otherwise the plain instantiations compile them out (SEC = false)
+  fc.secondary = (s->enableReflection && anyReflective && s->numReflection > 0) || (s->enableRefraction && anyTransparent);
+  fc.wfSkip = skip_applies(objs, numObjects);
+  return fc;
+}
+
+// The wavefront pipeline's launch: whether this frame takes it, its persistent waves, chunk sizes and records.
+struct Wavefront {
+  bool on = false;
+  WfWs ws{};
+  int primaryWaves = 0, shadowWaves = 0, flush = 16;
+  uint32_t slotChunk = 0, maxChunk = 0, rayChunk = 0, pixelChunk = 0;
+};
+// Settled BEFORE anything else depends on `on`: if the workspace (≈(160 + 4·numLights) B per hit slot, grow-only per (device,
+// stream): 5.8 GB for an 8K frame) cannot be had, the auto-selected launch falls back to render_kernel — identical bits, no
+// workspace — and only an explicit path-5 request reports the failure.  A (device, stream) that was refused once is not asked
+// again for as much or more, so a frame sequence does not pay a failing allocation (and the stream synchronisation in front of
+// it) per frame.
+int setup_wavefront(DeviceState &ds, StreamState &ss, int dev, const FrameClass &fc, const RmObject *objs, int numObjects,
+                    int numLights, int W, int nRows, bool tileShard, int pathReq, hipStream_t stream, Wavefront *wf) {
+  wf->on = fc.wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(objs, numObjects, fc.wfBounces, (size_t)nRows * W, tileShard)));
+  if (!wf->on) return RM_OK;
+  static const int perSimd = env_int("RM_WF_WAVES_PER_SIMD", 0), envFlush = env_int("RM_WF_FLUSH", 0),
+                   envSlotChunk = env_int("RM_WF_SLOT_CHUNK", 0), envRayChunk = env_int("RM_WF_RAY_CHUNK", 0),
+                   envPixelChunk = env_int("RM_WF_PIXEL_CHUNK", 0), envMaxChunk = env_int("RM_WF_MAX_CHUNK", 0);
+  // chunk sizes are clamped so that slot and ray ids stay 32-bit
+  constexpr int kWfChunkMax = 4096;
+  auto clampChunk = [](int v) { return (uint32_t)(v > kWfChunkMax ? kWfChunkMax : v); };
+  wf->slotChunk = envSlotChunk >= 64 ? clampChunk(envSlotChunk) : kWfSlotChunk;  // >= 64: one trip's hits fit one fresh chunk
+  wf->maxChunk = envMaxChunk > 0 ? clampChunk(envMaxChunk) : 0u;  // 0: fixed chunks (guided chunks measured slower)
+  wf->rayChunk = envRayChunk > 0 ? clampChunk(envRayChunk) : wfRayChunk(1);
+  wf->pixelChunk = envPixelChunk > 0 ? clampChunk(envPixelChunk) : wfRayChunk(0);
+  wf->flush = envFlush > 0 && envFlush <= 64 ? envFlush : 16;
+  if (ds.numCUs == 0) {
+    hipDeviceProp_t prop;
+    HIP_OK(hipGetDeviceProperties(&prop, dev));
+    ds.numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  // persistent waves: as many as are resident at once (4 SIMDs per CU x the kernel's register budget)
+  auto waves = [&](int kind) { return ds.numCUs * 4 * (perSimd > 0 && perSimd < wfMarchWaves(kind) ? perSimd : wfMarchWaves(kind)); };
+  wf->primaryWaves = waves(0); wf->shadowWaves = waves(2);
+  const int marchWaves = wf->shadowWaves > wf->primaryWaves ? wf->shadowWaves : wf->primaryWaves;
+  // hit-slot capacity: every ray may hit, plus one partly used chunk of slots per persistent wave
+  const size_t cap = (size_t)nRows * W + (size_t)wf->slotChunk * marchWaves;
+  // 32-bit ids: hit slots x lights (shadow rays) and the striped cursors' padding (one chunk per stripe) stay below 2^32
+  const size_t chunkMax = wf->rayChunk > wf->pixelChunk ? wf->rayChunk : wf->pixelChunk;
+  const bool idsFit = (double)(cap + (size_t)kWfStripes * chunkMax) * (numLights > 0 ? numLights : 1) < 4.0e9;
+  int wst = RM_ERR_DEVICE;
+  const size_t wfBytes = wavefront_bytes(cap, numLights);
+  if (!idsFit) set_error("frame too large for the wavefront pipeline's 32-bit ray ids");
+  else if (ss.wfDenied != 0 && wfBytes >= ss.wfDenied) set_error("wavefront workspace was refused on this stream before");
+  else if ((wst = wavefront_workspace(cap, numLights, stream, &wf->ws)) != RM_OK) ss.wfDenied = wfBytes;
+  if (wst != RM_OK) {
+    if (pathReq == 5 && idsFit) return wst;  // an explicit request reports the workspace failure; a frame the ids cannot cover "does not apply"
+    wf->on = false;
+  }
+  return RM_OK;
+}
+
+// The picture this launch renders: everything that decides a pixel (FNV-1a over the caller's tables and the row map) — what the
+// tile-order feedback and the tuners key their measurements by.
+unsigned long long picture_key(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                               const RmGlobals *g, const RmSettings *s, const RowMap &map) {
+  unsigned long long key = 1469598103934665603ull;
+  auto mix = [&](const void *p, size_t nb) {
+    const unsigned char *b8 = static_cast<const unsigned char *>(p);
+    for (size_t k = 0; k < nb; k++) key = (key ^ b8[k]) * 1099511628211ull;
+  };
+  mix(cam, sizeof(*cam)); mix(g, sizeof(*g)); mix(s, sizeof(*s)); mix(&map, sizeof(map));
+  mix(objs, sizeof(RmObject) * (size_t)numObjects); mix(lights, sizeof(RmLight) * (size_t)numLights);
+  return key;
+}
+
+// Tile shape ("tile shape" above) as a tile shift: 8×8 unless the tuner is measuring or has chosen 4×16 for this picture on this
+// stream.  *timedSlot: the tuner's timing slot for this launch, -1 for none.
+int tile_shift(DeviceState &ds, StreamState &ss, const FrameClass &fc, bool wavefront, int count, int W, int nRows,
+               unsigned long long key, int *timedSlot) {
+  *timedSlot = -1;
+  static const int envShape = env_int("RM_TILE_SHAPE", 0);
+  const int shapeReq = g_tileShape.load() >= 0 ? g_tileShape.load() : envShape;
+  const bool bigFrame = (size_t)nRows * W >= (size_t)2048 * 64;
+  if ((shapeReq == 2 || shapeReq == 3) && count == 0) return shapeReq;  // the counted / stamped diagnostic builds keep 8×8 (their callers size per-wave arrays by it)
+  if (RM_TILE_W == 8 && !fc.bulb && !wavefront && !fc.twoD && count == 0 && bigFrame && !ds.dbgTileOrder && !ds.dbgTileCost) {
+    const TuneStep t = ss.shape.step(TuneKey(key, W, nRows, 0, 0), 2, ds.shapeChoice);  // candidate 0 = 8×8, 1 = 4×16
+    *timedSlot = t.slot;
+    return t.candidate ? 2 : 3;
+  }
+  return (RM_TILE_W == 8) ? 3 : (RM_TILE_W == 4 ? 2 : (RM_TILE_W == 16 ? 4 : 3));
+}
+
+// Tile order ("tile order" above): 0 raster order, 1 feedback — tiles start heaviest-first by the costs the previous frame of this
+// size on this stream recorded.  The plan of one frame, and its carve of the stream's tile-order workspace.
+struct TileOrderPlan {
+  bool ordered = false, byCost = false, byGeom = false, lastSort = false, settled = false;
+  bool combine = false;  // byGeom: the estimates take in the stale costs of the previous picture of this size
+  uint32_t *cost = nullptr, *hist = nullptr, *cost2 = nullptr;
+  int32_t *order = nullptr;
+  bool sorts() const { return (byCost || byGeom) && !settled; }  // the ordering launches run ahead of the render
+};
+int plan_tile_order(const DeviceState &ds, StreamState &ss, const FrameClass &fc, bool wavefront, int count, int numObjects, int W,
+                    int nRows, int nw, int tileShift, int tileCount, unsigned long long key, hipStream_t stream, TileOrderPlan *p) {
+  static const int envOrder = env_int("RM_TILE_ORDER", kDefaultTileOrder);
+  const int orderMode = g_tileOrderMode.load() >= 0 ? g_tileOrderMode.load() : envOrder;
+  // every class of the one-lane-per-pixel kernel (round 3: the layer and sampler kernels too — area light + point light 1080p
+  // 0.80 -> 0.59 ms, textured floor / sky box at 4K 2.5 -> 2.3 ms, terrain + cloud horizon view 4.31 -> 4.04 ms, sea unchanged).
+  // Small frames are not worth the two extra launches.
+  p->ordered = orderMode > 0 && !wavefront && !fc.twoD && count == 0 && tileCount >= 2048 && !ds.dbgTileOrder && !ds.dbgTileCost;
+  if (!p->ordered) return RM_OK;
+  void *mem = nullptr;
+  if (int st = stream_workspace(kWsTileOrder, stream, (size_t)tileCount * 12 + 256, &mem)) return st;
+  p->hist = static_cast<uint32_t *>(mem);
+  p->cost = p->hist + 64;
+  p->order = reinterpret_cast<int32_t *>(p->cost + tileCount);
+  p->cost2 = p->cost + 2 * (size_t)tileCount;  // a new picture's estimates (tile_geom_kernel), so that it can read its neighbours' stale costs
+  TileOrderState &ts = ss.tileOrder;
+  const TileOrderState now{tileCount, W, nRows, nw, tileShift, mem, key};
+  const bool haveCost = ts.tileCount == now.tileCount && ts.W == W && ts.nRows == nRows && ts.nw == nw && ts.tileShift == tileShift && ts.mem == mem;
+  if (!haveCost) HIP_OK(hipMemsetAsync(p->cost, 0, (size_t)tileCount * 4, stream));
+  const bool samePicture = haveCost && ts.sceneKey == key;
+  // A picture that repeats SETTLES: its first frames re-sort by the costs the frame before measured (each under a better order than
+  // the last); the kSettle-th such sort keeps its costs (they are the stale costs of whatever picture comes next) and from then on
+  // the same order is reused — no ordering launches (memset + two kernels, ≈25 µs a frame: 1 % of the 4K bulb frame, 8 % of its
+  // 1/8 shard) and no cost atomics in the render.  RM_TILE_ORDER_SETTLE=0: re-sort every frame (rounds 2-3).
+  static const int kSettle = env_int("RM_TILE_ORDER_SETTLE", 3, 0, 1000);
+  const int kSettleHold = kSettle + 1;
+  const int costSorts = samePicture ? ts.sorts + 1 : 0;  // this frame is the costSorts-th consecutive cost-ordered frame of its picture (0: not cost-ordered)
+  ts = now;
+  ts.sorts = costSorts > kSettleHold ? kSettleHold : costSorts;
+  // Which order this frame's tiles start in: the previous frame's measured costs when it was the same picture; otherwise — no
+  // history, or the scene / camera moved — the geometric classification (tile_geom_kernel), where the scene has per-object balls
+  // and no procedural layers (their cost is not where the objects are); otherwise raster order.
+  p->byCost = samePicture;
+  p->lastSort = p->byCost && kSettle > 0 && costSorts == kSettle;
+  p->settled = p->byCost && kSettle > 0 && costSorts > kSettle;
+  static const int geomMode = env_int("RM_TILE_ORDER_GEOMETRIC", 2);  // 0 off (raster), 1 geometry alone, 2 geometry + stale costs (measured best, default)
+  p->byGeom = !samePicture && geomMode != 0 && !fc.envFeatures && numObjects > 0;
+  p->combine = geomMode == 2 && haveCost;
+  return RM_OK;
+}
+
+// "Light split": a settled picture of the plain table-walk class (no secondary rays, samplers or layers) with several lights is
+// bound by the life of its heaviest waves, and those are whole tiles whose every pixel runs one long shadow march per light back to
+// back (C2: 26-40 evaluations of primary march, then three soft-shadow marches of 256 — profiles/r04_r_c2_chain_sim.txt).  The
+// first tileCount / kSplitDiv tiles of the settled order are therefore rendered by numLights workgroups each — every one repeats
+// the primary march and the surface point and marches ONE light, its result going to memory (the first one's primary result too)
+// — and the last of them to arrive finishes the tile from the stored results: surface point, AO and the light sum, no march.  The
+// same marches, the same sums in the same order: the same pixels.  Whether it pays is measured per picture (the tuner above).
+// RM_LIGHT_SPLIT=0: off; =n: the heaviest 1/n of the tiles.
+struct LightSplit {
+  int tiles = 0;        // the split tiles of this launch, 0: a plain launch
+  float *store = nullptr;
+  int timedSlot = -1;   // the tuner's timing slot for this launch
+};
+LightSplit plan_light_split(DeviceState &ds, StreamState &ss, const FrameClass &fc, const TileOrderPlan &to, int count, int nw,
+                            int numLights, int W, int nRows, int tileShift, int tileCount, bool shapeTimed,
+                            unsigned long long key, hipStream_t stream) {
+  LightSplit ls;
+  static const int envSplitDiv = env_int("RM_LIGHT_SPLIT", 256, 0);
+  const int kSplitDiv = g_lightSplit.load() >= 0 ? g_lightSplit.load() : envSplitDiv;  // rm_debug_set_light_split
+  if (!to.settled || kSplitDiv <= 0 || fc.bulb || fc.envFeatures || fc.textured || fc.secondary || count != 0 || nw != 1 ||
+      numLights < 2 || numLights > RM_MAX_LIGHTS || shapeTimed)
+    return ls;
+  int splitK = tileCount / kSplitDiv;
+  if (splitK > 0 && !g_lightSplitForce.load()) {  // measured, unless a test forces it (rm_debug_set_light_split)
+    const TuneStep t = ss.split.step(TuneKey(key, W, nRows, tileShift, kSplitDiv), 1, ds.splitChoice);  // candidate 0 = plain, 1 = split
+    ls.timedSlot = t.slot;
+    if (!t.candidate) splitK = 0;
+  }
+  if (splitK > 0) {
+    void *mem = nullptr;
+    // SceneBlock::splitStore: splitK arrival counters, padded to 64 words, then splitK·64·(2·numLights + 6) floats
+    if (stream_workspace(kWsLightSplit, stream, ((((size_t)splitK + 63) & ~(size_t)63) + (size_t)splitK * 64 * (2 * numLights + 6)) * sizeof(float), &mem) == RM_OK) {
+      ls.tiles = splitK;
+      ls.store = static_cast<float *>(mem);
+    }  // no memory for it: the plain launch
+  }
+  return ls;
+}
+
+// What every render launch of a frame shares.
+struct RenderLaunch {
+  SceneBlock *sb; RowMap map; int W, H, nRows; float4 *o, *b; unsigned long long *dc;  // the render kernels' arguments
+  hipStream_t stream; dim3 grid, block;
+};
+
+// This frame's launch order — from the previous frame's tile costs or from geometry — ahead of the render.
+int launch_tile_order(const TileOrderPlan &p, const RenderLaunch &r, int tileWpx, int tileH, int tileCount) {
+  static const int ringLog2 = env_int("RM_GEOM_RING_LOG2", 16, 5, 17), dilate = env_int("RM_GEOM_DILATE", 0, 0, 16);
+  const dim3 sgrid((tileCount + 255) / 256);
+  uint32_t *sortCost = p.cost;
+  if (p.byGeom) {  // estimates into their own array (the kernel reads the stale costs of a tile's neighbourhood), stale costs cleared after
+    hipLaunchKernelGGL(tile_geom_kernel, sgrid, dim3(256), 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, (int)r.grid.x, tileWpx, tileH,
+                       tileCount, p.cost, p.cost2, p.combine ? 1 : 0, (p.combine ? ringLog2 : 16), dilate);
+    HIP_OK(hipMemsetAsync(p.cost, 0, (size_t)tileCount * sizeof(uint32_t), r.stream));
+    sortCost = p.cost2;
+  }
+  HIP_OK(hipMemsetAsync(p.hist, 0, 2 * kOrderBuckets * sizeof(uint32_t), r.stream));
+  hipLaunchKernelGGL(tile_hist_kernel, sgrid, dim3(256), 0, r.stream, sortCost, tileCount, p.hist);
+  hipLaunchKernelGGL(tile_scatter_kernel, sgrid, dim3(256), 0, r.stream, sortCost, tileCount, p.hist, p.order, p.lastSort ? 1 : 0);
+  return RM_OK;
+}
+
+// The wavefront pipeline's generations: primary (gen 0) or bounce march, surface, shadow marches, lighting.
+template <bool SKIP>
+void launch_wavefront(const RenderLaunch &r, const Wavefront &wf, int bounces, int numLights, int numCUs) {
+  const dim3 pgrid(wf.primaryWaves), mgrid(wf.shadowWaves), mblock(64), dense(numCUs * 16), block(256);
+  for (int gen = 0; gen <= bounces; gen++) {
+    if (gen == 0) hipLaunchKernelGGL((wf_march_kernel<0, SKIP>), pgrid, mblock, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, wf.ws, gen, wf.flush, wf.pixelChunk, wf.maxChunk, wf.slotChunk);
+    else hipLaunchKernelGGL((wf_march_kernel<1, SKIP>), pgrid, mblock, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, wf.ws, gen, wf.flush, wf.rayChunk, wf.maxChunk, wf.slotChunk);
+    hipLaunchKernelGGL(wf_surface_kernel<SKIP>, dense, block, 0, r.stream, r.sb, r.map, r.W, r.H, wf.ws, gen);
+    if (numLights > 0) hipLaunchKernelGGL((wf_march_kernel<2, SKIP>), mgrid, mblock, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, wf.ws, gen, wf.flush, wf.rayChunk, wf.maxChunk, wf.slotChunk);
+    hipLaunchKernelGGL(wf_light_kernel, dense, block, 0, r.stream, r.sb, r.map, r.W, r.H, r.o, r.b, wf.ws, gen, bounces);
+  }
+}
+
+// render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>: the bulb class and the generic table walk, plain and counted, without
+// procedural layers or textures; the generic kernel with either or both.  Features a launch does not need are compiled out so the
+// common kernels keep their register budget.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+void launch_kernel(const RenderLaunch &r) {
+  hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
+}
+// a production launch: the secondary rays compiled in only where they can fire
+template <int BULB, bool ENV, bool TEX>
+void launch_production(bool secondary, const RenderLaunch &r) {
+  if (secondary) launch_kernel<BULB, 0, ENV, TEX>(r);
+  else launch_kernel<BULB, 0, ENV, TEX, false>(r);
+}
+// the counted (1: reference work, 2: executed work) and clock-stamped (3) launches
+template <int BULB>
+void launch_counted(int count, const RenderLaunch &r) {
+  if (count == 1) launch_kernel<BULB, 1, false, false>(r);
+  else if (count == 2) launch_kernel<BULB, 2, false, false>(r);
+  else launch_kernel<BULB, 3, false, false>(r);
+}
+// the layer / sampler kernels: their counting instantiations count the reference's work only (they have no shortcuts to count apart)
+template <bool ENV, bool TEX>
+void launch_layered(int count, bool secondary, const RenderLaunch &r) {
+  if (count) launch_kernel<0, 1, ENV, TEX>(r);
+  else launch_production<0, ENV, TEX>(secondary, r);
+}
+int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const LightSplit &ls, int numLights, int tileCount,
+                    const RenderLaunch &r) {
+  if (fc.envFeatures && fc.textured) launch_layered<true, true>(count, fc.secondary, r);
+  else if (fc.envFeatures) launch_layered<true, false>(count, fc.secondary, r);
+  else if (fc.textured) launch_layered<false, true>(count, fc.secondary, r);
+  else if (fc.bulb) {
+    // the counted launches keep the general form; the production ones take the plain form where the launcher found it
+    if (count) launch_counted<kBulbGeneral>(count, r);
+    else if (plainBulb) launch_production<kBulbPlain, false, false>(fc.secondary, r);
+    else launch_production<kBulbGeneral, false, false>(fc.secondary, r);
+  } else if (count) launch_counted<0>(count, r);
+  else if (!fc.secondary && ls.tiles > 0) {
+    // light split: the heavy tiles one light per workgroup first, every other tile behind them in the same grid; the last of a
+    // tile's workgroups to finish its march finishes the tile.  (A second launch for the finish cost 35-45 µs per frame —
+    // more than the split gains on throughput-bound frames; the same launch on a side stream gained nothing.)
+    HIP_OK(hipMemsetAsync(ls.store, 0, (size_t)ls.tiles * sizeof(uint32_t), r.stream));  // the tiles' arrival counters
+    RenderLaunch split = r;
+    split.grid = dim3((unsigned)(ls.tiles * numLights + tileCount - ls.tiles));
+    split.block = dim3(64);
+    launch_kernel<0, 0, false, false, false, 1>(split);
+  } else launch_production<0, false, false>(fc.secondary, r);
+  return RM_OK;
+}
+
 int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                   const RmGlobals *g, const RmSettings *s, int W, int H, RowMap map, int nRows, float *d_rgba,
                   float *d_bright, hipStream_t stream, int count, RmCounters *countersOut,
@@ -1034,245 +1375,38 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
   if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
   DeviceState &ds = g_dev[dev];
   std::lock_guard<std::mutex> lock(ds.mu);  // this device only; nothing below blocks on the GPU unless `count` asks for numbers back
-  const dim3 block(256);
-  const bool bulb = (numObjects == 1 && objs[0].type == RM_MANDELBULB);
-  auto nonzero3 = [](const float *v) { return v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f; };
+  StreamState &ss = ds.streams[stream];
   // Two schedules of the same per-ray arithmetic, identical bits: rm::render_kernel (one lane per pixel; every class, and the
   // counted variants) and, for table-walk classes with bounces, the wavefront pipeline.
-  static const int envPath = std::getenv("RM_KERNEL_PATH") ? std::atoi(std::getenv("RM_KERNEL_PATH")) : 0;
+  static const int envPath = env_int("RM_KERNEL_PATH", 0);
   const int pathReq = g_kernelPath.load() ? g_kernelPath.load() : envPath;  // 0 = the measured-fastest schedule of the scene's class
-  const bool envFeatures = (s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SKY_BACKGROUND | RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)) != 0;
-  // anything that reads a sampler or takes the area-light branches: object textures, sky box, emissive rectangles, area lights
-  bool textured = s->enableSkyBox != 0;
-  for (int i = 0; i < numObjects; i++) textured = textured || objs[i].texLoc != -1 || objs[i].isEmissive;
-  for (int i = 0; i < numLights; i++) textured = textured || lights[i].type == RM_LIGHT_AREA;
-  // The wavefront pipeline (rm_wavefront.hip.h) covers the table-walk classes whose evaluations cost the same on every
-  // lane: no Mandelbulb / 2-D Mandelbrot in the table, no samplers or procedural layers, no refraction.
-  bool wfOk = !bulb && !count && !envFeatures && !textured && !g->isTwoD && s->maxSteps >= 1 && s->numReflection <= kWfMaxBounces;
-  bool anyReflective = false;
-  for (int i = 0; i < numObjects; i++) {
-    if (objs[i].type == RM_MANDELBULB || objs[i].type == RM_MANDELBROT) wfOk = false;
-    if (s->enableRefraction && nonzero3(objs[i].cTransparent)) wfOk = false;
-    anyReflective = anyReflective || nonzero3(objs[i].cReflective);
-  }
-  const int wfBounces = (s->enableReflection && anyReflective) ? s->numReflection : 0;
-  // whether main's secondary rays (frag:2491-2570) can fire for any pixel of this frame: a reflective object with reflection on and
-  // at least one bounce, or a transparent one with refraction on — otherwise the plain instantiations compile them out (SEC = false)
-  bool anyTransparent = false;
-  for (int i = 0; i < numObjects; i++) anyTransparent = anyTransparent || nonzero3(objs[i].cTransparent);
-  const bool secondary = (s->enableReflection && anyReflective && s->numReflection > 0) || (s->enableRefraction && anyTransparent);
-  const bool wfSkip = skip_applies(objs, numObjects);
-  bool wavefront = wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(objs, numObjects, wfBounces, (size_t)nRows * W, map.numShards > 1)));
-  // The wavefront pipeline's knobs and records, settled BEFORE anything below depends on `wavefront`: if its workspace
-  // (≈(160 + 4·numLights) B per hit slot, grow-only per (device, stream): 5.8 GB for an 8K frame) cannot be had, the
-  // auto-selected launch falls back to render_kernel — identical bits, no workspace — and only an explicit path-5 request
-  // reports the failure.  A (device, stream) that was refused once is not asked again for as much or more, so a frame
-  // sequence does not pay a failing allocation (and the stream synchronisation in front of it) per frame.
-  // Tuning knobs for A/B runs (defaults are the measured best); chunk sizes are clamped so that slot and ray ids stay 32-bit.
-  auto envInt = [](const char *name) { const char *e = std::getenv(name); return e ? std::atoi(e) : 0; };
-  static const int wavesPerSimd = envInt("RM_WF_WAVES_PER_SIMD"), envFlush = envInt("RM_WF_FLUSH"), envSlotChunk = envInt("RM_WF_SLOT_CHUNK"),
-                   envRayChunk = envInt("RM_WF_RAY_CHUNK"), envPixelChunk = envInt("RM_WF_PIXEL_CHUNK"), envMaxChunk = envInt("RM_WF_MAX_CHUNK");
-  constexpr int kWfChunkMax = 4096;
-  auto clampChunk = [](int v) { return (uint32_t)(v > kWfChunkMax ? kWfChunkMax : v); };
-  const uint32_t slotChunk = envSlotChunk >= 64 ? clampChunk(envSlotChunk) : kWfSlotChunk;  // >= 64: one trip's hits fit one fresh chunk
-  const uint32_t maxChunk = envMaxChunk > 0 ? clampChunk(envMaxChunk) : 0u;  // 0: fixed chunks (guided chunks measured slower)
-  const uint32_t rayChunk = envRayChunk > 0 ? clampChunk(envRayChunk) : wfRayChunk(1), pixelChunk = envPixelChunk > 0 ? clampChunk(envPixelChunk) : wfRayChunk(0);
-  WfWs wfWs{};
-  int wfPrimaryWaves = 0, wfShadowWaves = 0;
-  if (wavefront) {
-    if (ds.numCUs == 0) {
-      hipDeviceProp_t prop;
-      HIP_OK(hipGetDeviceProperties(&prop, dev));
-      ds.numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    // persistent waves: as many as are resident at once (4 SIMDs per CU x the kernel's register budget)
-    auto waves = [&](int kind) { return ds.numCUs * 4 * (wavesPerSimd > 0 && wavesPerSimd < wfMarchWaves(kind) ? wavesPerSimd : wfMarchWaves(kind)); };
-    wfPrimaryWaves = waves(0); wfShadowWaves = waves(2);
-    const int marchWaves = wfShadowWaves > wfPrimaryWaves ? wfShadowWaves : wfPrimaryWaves;
-    // hit-slot capacity: every ray may hit, plus one partly used chunk of slots per persistent wave
-    const size_t cap = (size_t)nRows * W + (size_t)slotChunk * marchWaves;
-    // 32-bit ids: hit slots x lights (shadow rays) and the striped cursors' padding (one chunk per stripe) stay below 2^32
-    const size_t chunkMax = rayChunk > pixelChunk ? rayChunk : pixelChunk;
-    const bool idsFit = (double)(cap + (size_t)kWfStripes * chunkMax) * (numLights > 0 ? numLights : 1) < 4.0e9;
-    int wst = RM_ERR_DEVICE;
-    auto denied = ds.wfDenied.find(stream);
-    const size_t wfBytes = wavefront_bytes(cap, numLights);
-    if (!idsFit) set_error("frame too large for the wavefront pipeline's 32-bit ray ids");
-    else if (denied != ds.wfDenied.end() && wfBytes >= denied->second) set_error("wavefront workspace was refused on this stream before");
-    else if ((wst = wavefront_workspace(cap, numLights, stream, &wfWs)) != RM_OK) ds.wfDenied[stream] = wfBytes;
-    if (wst != RM_OK) {
-      if (pathReq == 5 && idsFit) return wst;  // an explicit request reports the workspace failure; a frame the ids cannot cover "does not apply"
-      wavefront = false;
-    }
-  }
+  const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, g, s, count);
+  Wavefront wf;
+  if ((st = setup_wavefront(ds, ss, dev, fc, objs, numObjects, numLights, W, nRows, map.numShards > 1, pathReq, stream, &wf)) != RM_OK) return st;
   // Waves (8×8 tiles, side by side) per workgroup.  A workgroup's registers and LDS come free only when its LAST wave
   // ends, and march lengths differ a lot between neighbouring tiles, so small workgroups keep more waves resident: one wave
   // per workgroup for every class (measured at the register budgets above: the 4K bulb frame 2.31 / 2.34 / 2.58 ms at
   // 1 / 2 / 4 waves, the 8K Menger frame 51.0 / 51.8 / 58.6 ms, bump + reflection at 4K 19.4 / 19.8 / 22.1 ms; at the
   // compiler's own budgets two waves were best for the bulb, profiles/r02_c_waves_per_block.md).  RM_WAVES_PER_BLOCK overrides.
-  static const int wpb = std::getenv("RM_WAVES_PER_BLOCK") ? std::atoi(std::getenv("RM_WAVES_PER_BLOCK")) : 0;
+  static const int wpb = env_int("RM_WAVES_PER_BLOCK", 0);
   const int nw = (wpb == 1 || wpb == 2 || wpb == 4) ? wpb : 1;
-  // the picture this launch renders: everything that decides a pixel (FNV-1a over the caller's tables and the row map) — what the
-  // tile-order feedback and the tile-shape tuner key their measurements by
-  unsigned long long key = 1469598103934665603ull;
-  {
-    auto mix = [&](const void *p, size_t nb) {
-      const unsigned char *b8 = static_cast<const unsigned char *>(p);
-      for (size_t k = 0; k < nb; k++) key = (key ^ b8[k]) * 1099511628211ull;
-    };
-    mix(cam, sizeof(*cam)); mix(g, sizeof(*g)); mix(s, sizeof(*s)); mix(&map, sizeof(map));
-    mix(objs, sizeof(RmObject) * (size_t)numObjects); mix(lights, sizeof(RmLight) * (size_t)numLights);
-  }
-  // Tile shape ("tile shape" above): 8×8 unless the tuner is measuring or has chosen 4×16 for this picture on this stream
-  static const int envShape = std::getenv("RM_TILE_SHAPE") ? std::atoi(std::getenv("RM_TILE_SHAPE")) : 0;
-  const int shapeReq = g_tileShape.load() >= 0 ? g_tileShape.load() : envShape;
-  const bool bigFrame = (size_t)nRows * W >= (size_t)2048 * 64;
-  int tileShift = (RM_TILE_W == 8) ? 3 : (RM_TILE_W == 4 ? 2 : (RM_TILE_W == 16 ? 4 : 3));
-  ShapeTune *tune = nullptr;  // non-null: this launch is one of the tuner's (frames 0-3 of a picture) or follows its choice
-  int tuneTimed = -1;         // 0..3: time this launch as the tuner's candidate (k & 1: 0 = 8×8, 1 = 4×16) of round k >> 1
-  if ((shapeReq == 2 || shapeReq == 3) && count == 0) tileShift = shapeReq;  // the counted / stamped diagnostic builds keep 8×8 (their callers size per-wave arrays by it)
-  else if (RM_TILE_W == 8 && !bulb && !wavefront && !g->isTwoD && count == 0 && bigFrame && !ds.dbgTileOrder && !ds.dbgTileCost) {
-    tune = &ds.shapeTune[stream];
-    if (tune->key != key || tune->W != W || tune->nRows != nRows) {
-      tune->drop();
-      tune->key = key; tune->W = W; tune->nRows = nRows; tune->frame = 0; tune->chosen = -1;
-      const auto known = ds.shapeChoice.find(std::make_tuple(key, W, nRows));  // another stream of this device measured this picture
-      if (known != ds.shapeChoice.end()) tune->chosen = known->second;
-    }
-    if (tune->chosen < 0 && tune->frame >= 8) {
-      bool ready = true;
-      for (int k = 0; k < 4; k++) ready = ready && tune->timed[k] && hipEventQuery(tune->ev[k][1]) == hipSuccess;
-      if (ready) {
-        float best[2] = {1e30f, 1e30f};
-        bool ok = true;
-        for (int k = 0; k < 4; k++) {
-          float ms = 0.0f;
-          ok = ok && hipEventElapsedTime(&ms, tune->ev[k][0], tune->ev[k][1]) == hipSuccess;
-          best[k & 1] = ms < best[k & 1] ? ms : best[k & 1];
-        }
-        tune->chosen = (ok && best[1] < 0.97f * best[0]) ? 2 : 3;  // 4×16 must win by 3 %
-        tune->drop();
-        if (ds.shapeChoice.size() >= 256) ds.shapeChoice.clear();
-        ds.shapeChoice[std::make_tuple(key, W, nRows)] = tune->chosen;
-      }
-    }
-    (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error
-    if (tune->chosen >= 0) tileShift = tune->chosen;
-    else {
-      // frames 0-1, 4-5: 8×8; 2-3, 6-7: 4×16; from frame 8 until the timings are in (a host that enqueues far ahead of the GPU): 8×8 —
-      // the enqueue path never waits for them
-      const int f = tune->frame;
-      tileShift = (f < 8 && ((f >> 1) & 1)) ? 2 : 3;
-      if (f < 8 && (f & 1)) tuneTimed = ((f >> 1) & 1) | ((f >> 2) << 1);  // candidate | round << 1
-    }
-    tune->frame++;
-  }
+  const unsigned long long key = picture_key(cam, objs, numObjects, lights, numLights, g, s, map);
+  int shapeSlot;
+  const int tileShift = tile_shift(ds, ss, fc, wf.on, count, W, nRows, key, &shapeSlot);
   const int tileW = 1 << tileShift, tileH = 64 >> tileShift;
   const dim3 rgrid((W + nw * tileW - 1) / (nw * tileW), (nRows + tileH - 1) / tileH), rblock(64 * nw);
-  // Tile order ("tile order" above): 0 raster order, 1 feedback — tiles start heaviest-first by the costs the previous frame
-  // of this size on this stream recorded.  Small frames are not worth the two extra launches.
-  static const int envOrder = std::getenv("RM_TILE_ORDER") ? std::atoi(std::getenv("RM_TILE_ORDER")) : kDefaultTileOrder;
-  const int orderMode = g_tileOrderMode.load() >= 0 ? g_tileOrderMode.load() : envOrder;
   const int tileCount = (int)(rgrid.x * rgrid.y);
-  // every class of the one-lane-per-pixel kernel (round 3: the layer and sampler kernels too — area light + point light 1080p
-  // 0.80 -> 0.59 ms, textured floor / sky box at 4K 2.5 -> 2.3 ms, terrain + cloud horizon view 4.31 -> 4.04 ms, sea unchanged)
-  const bool ordered = orderMode > 0 && !wavefront && !g->isTwoD && count == 0 &&
-                       tileCount >= 2048 && !ds.dbgTileOrder && !ds.dbgTileCost;
-  uint32_t *oCost = nullptr, *oHist = nullptr, *oCost2 = nullptr;
-  int32_t *oOrder = nullptr;
-  bool haveCost = false, samePicture = false;
-  // A picture that repeats SETTLES: its first frames re-sort by the costs the frame before measured (each under a better order than
-  // the last); the kSettle-th such sort keeps its costs (they are the stale costs of whatever picture comes next) and from then on
-  // the same order is reused — no ordering launches (memset + two kernels, ≈25 µs a frame: 1 % of the 4K bulb frame, 8 % of its
-  // 1/8 shard) and no cost atomics in the render.  RM_TILE_ORDER_SETTLE=0: re-sort every frame (rounds 2-3).
-  static const int kSettle = [] { const char *e = std::getenv("RM_TILE_ORDER_SETTLE"); const int v = e ? std::atoi(e) : 3; return v < 0 ? 0 : (v > 1000 ? 1000 : v); }();
-  const int kSettleHold = kSettle + 1;
-  int costSorts = 0;  // this frame is the costSorts-th consecutive cost-ordered frame of its picture (0: not cost-ordered)
-  if (ordered) {
-    void *mem = nullptr;
-    if ((st = stream_workspace(kWsTileOrder, stream, (size_t)tileCount * 12 + 256, &mem)) != RM_OK) return st;
-    oHist = static_cast<uint32_t *>(mem);
-    oCost = oHist + 64;
-    oOrder = reinterpret_cast<int32_t *>(oCost + tileCount);
-    oCost2 = oCost + 2 * (size_t)tileCount;  // a new picture's estimates (tile_geom_kernel), so that it can read its neighbours' stale costs
-    TileOrderState &ts = ds.tileOrder[stream];
-    const TileOrderState now{tileCount, W, nRows, nw, tileShift, mem, key};
-    haveCost = ts.tileCount == now.tileCount && ts.W == W && ts.nRows == nRows && ts.nw == nw && ts.tileShift == tileShift && ts.mem == mem;
-    if (!haveCost) HIP_OK(hipMemsetAsync(oCost, 0, (size_t)tileCount * 4, stream));
-    samePicture = haveCost && ts.sceneKey == key;
-    costSorts = samePicture ? ts.sorts + 1 : 0;
-    ts = now;
-    ts.sorts = costSorts > kSettleHold ? kSettleHold : costSorts;
-  }
-  // Which order this frame's tiles start in: the previous frame's measured costs when it was the same picture; otherwise — no
-  // history, or the scene / camera moved — the geometric classification (tile_geom_kernel), where the scene has per-object balls
-  // and no procedural layers (their cost is not where the objects are); otherwise raster order.
-  static const int geomMode = [] { const char *e = std::getenv("RM_TILE_ORDER_GEOMETRIC"); return e ? std::atoi(e) : 2; }();  // 0 off (raster), 1 geometry alone, 2 geometry + stale costs (measured best, default)
-  const bool geomOn = geomMode != 0;
-  static const int ringCombined = [] { const char *e = std::getenv("RM_GEOM_RING_LOG2"); const int v = e ? std::atoi(e) : 16; return v < 5 ? 5 : (v > 17 ? 17 : v); }();
-  static const int geomDilate = [] { const char *e = std::getenv("RM_GEOM_DILATE"); const int v = e ? std::atoi(e) : 0; return v < 0 ? 0 : (v > 16 ? 16 : v); }();
-  const bool byCost = ordered && samePicture;
-  const bool lastSort = byCost && kSettle > 0 && costSorts == kSettle, settled = byCost && kSettle > 0 && costSorts > kSettle;
-  bool byGeom = ordered && !samePicture && geomOn && !envFeatures && numObjects > 0;
-  // "Light split": a settled picture of the plain table-walk class (no secondary rays, samplers or layers) with several lights is
-  // bound by the life of its heaviest waves, and those are whole tiles whose every pixel runs one long shadow march per light back to
-  // back (C2: 26-40 evaluations of primary march, then three soft-shadow marches of 256 — profiles/r04_r_c2_chain_sim.txt).  The
-  // first tileCount / kSplitDiv tiles of the settled order are therefore rendered by numLights workgroups each — every one repeats
-  // the primary march and the surface point and marches ONE light, its result going to memory (the first one's primary result too)
-  // — and the last of them to arrive finishes the tile from the stored results: surface point, AO and the light sum, no march.  The
-  // same marches, the same sums in the same order: the same pixels.  Whether it pays is measured per picture (SplitTune above).
-  // RM_LIGHT_SPLIT=0: off; =n: the heaviest 1/n of the tiles.
-  static const int envSplitDiv = [] { const char *e = std::getenv("RM_LIGHT_SPLIT"); const int v = e ? std::atoi(e) : 256; return v < 0 ? 0 : v; }();
-  const int kSplitDiv = g_lightSplit.load() >= 0 ? g_lightSplit.load() : envSplitDiv;  // rm_debug_set_light_split
-  int splitK = 0, splitTimed = -1;  // splitTimed: 0 / 1 = time this launch as the tuner's plain / split candidate
-  float *splitStore = nullptr;
-  SplitTune *splitTune = nullptr;
-  if (settled && kSplitDiv > 0 && !bulb && !envFeatures && !textured && !secondary && count == 0 && nw == 1 && numLights >= 2 &&
-      numLights <= RM_MAX_LIGHTS && tuneTimed < 0) {
-    splitK = tileCount / kSplitDiv;
-    if (splitK > 0 && !g_lightSplitForce.load()) {  // measured, unless a test forces it (rm_debug_set_light_split)
-      splitTune = &ds.splitTune[stream];
-      SplitTune &tn = *splitTune;
-      if (tn.key != key || tn.W != W || tn.nRows != nRows || tn.tileShift != tileShift || tn.div != kSplitDiv) {
-        tn.drop();
-        tn.key = key; tn.W = W; tn.nRows = nRows; tn.tileShift = tileShift; tn.div = kSplitDiv; tn.frame = 0; tn.chosen = -1;
-        const auto known = ds.splitChoice.find(std::make_tuple(key, W, nRows, tileShift, kSplitDiv));
-        if (known != ds.splitChoice.end()) tn.chosen = known->second;
-      }
-      if (tn.chosen < 0 && tn.frame >= 4 && tn.timed[0] && tn.timed[1] && hipEventQuery(tn.ev[0][1]) == hipSuccess &&
-          hipEventQuery(tn.ev[1][1]) == hipSuccess) {
-        float plainMs = 0.0f, splitMs = 0.0f;
-        const bool ok = hipEventElapsedTime(&plainMs, tn.ev[0][0], tn.ev[0][1]) == hipSuccess &&
-                        hipEventElapsedTime(&splitMs, tn.ev[1][0], tn.ev[1][1]) == hipSuccess;
-        tn.chosen = (ok && splitMs < 0.97f * plainMs) ? 1 : 0;
-        tn.drop();
-        if (ds.splitChoice.size() >= 256) ds.splitChoice.clear();
-        ds.splitChoice[std::make_tuple(key, W, nRows, tileShift, kSplitDiv)] = tn.chosen;
-      }
-      (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error
-      bool useSplit = tn.chosen == 1;
-      if (tn.chosen < 0) {
-        const int f = tn.frame;
-        useSplit = f == 2 || f == 3;
-        if (f == 1 || f == 3) splitTimed = f >> 1;
-      }
-      tn.frame++;
-      if (!useSplit) splitK = 0;
-    }
-    if (splitK > 0) {
-      void *mem = nullptr;
-      if (stream_workspace(kWsLightSplit, stream, ((((size_t)splitK + 63) & ~(size_t)63) + (size_t)splitK * 64 * (2 * numLights + 6)) * sizeof(float), &mem) == RM_OK) splitStore = static_cast<float *>(mem);
-      else splitK = 0;  // no memory for it: the plain launch
-    }
-  }
+  TileOrderPlan to;
+  if ((st = plan_tile_order(ds, ss, fc, wf.on, count, numObjects, W, nRows, nw, tileShift, tileCount, key, stream, &to)) != RM_OK) return st;
+  const LightSplit ls = plan_light_split(ds, ss, fc, to, count, nw, numLights, W, nRows, tileShift, tileCount, shapeSlot >= 0, key, stream);
   Slot *slot;
   st = stage_scene(cam, objs, numObjects, lights, numLights, g, s, stream, ds, &slot, res,
-                   ordered ? ((byCost || byGeom) ? oOrder : nullptr) : ds.dbgTileOrder,
-                   ordered ? ((lastSort || settled) ? nullptr : oCost) : ds.dbgTileCost,
-                   ordered ? tileCount : ds.dbgTileCount, tileShift, splitK, splitStore);
+                   to.ordered ? ((to.byCost || to.byGeom) ? to.order : nullptr) : ds.dbgTileOrder,
+                   to.ordered ? ((to.lastSort || to.settled) ? nullptr : to.cost) : ds.dbgTileCost,
+                   to.ordered ? tileCount : ds.dbgTileCount, tileShift, ls.tiles, ls.store);
   if (st != RM_OK) return st;
-  if (byGeom && !slot->host->objBallOk) {  // an object without a bounding ball (Sierpinski, 2-D Mandelbrot as an object): raster order
-    byGeom = false;
+  if (to.byGeom && !slot->host->objBallOk) {  // an object without a bounding ball (Sierpinski, 2-D Mandelbrot as an object): raster order
+    to.byGeom = false;
     slot->host->tileOrder = nullptr;
     HIP_OK(hipMemcpyAsync(&slot->dev->tileOrder, &slot->host->tileOrder, sizeof(slot->host->tileOrder), hipMemcpyHostToDevice, stream));
   }
@@ -1281,6 +1415,7 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
     HIP_OK(hipMemsetAsync(dc, 0, 10 * sizeof(unsigned long long), stream));
     if (d_waveSpans) HIP_OK(hipMemcpyAsync(dc + 5, &d_waveSpans, sizeof(d_waveSpans), hipMemcpyHostToDevice, stream));
   }
+  // rm_set_timing: an event ahead of the launch, one after the ordering launches if they run, one after the render
   TimedLaunch tl{};
   const bool timing = g_timing.load();
   // the events of a launch that fails part-way are destroyed on the way out (kept = handed to ds.timed below)
@@ -1288,109 +1423,34 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
     TimedLaunch &t; bool kept = false;
     ~TimedGuard() { if (!kept) for (int i = 0; i < t.n; i++) (void)hipEventDestroy(t.ev[i]); }
   } timedGuard{tl};
-  auto stamp = [&](int i) -> int {
+  auto stamp = [&]() -> int {
     if (!timing) return RM_OK;
-    HIP_OK(hipEventCreate(&tl.ev[i]));
-    tl.n = i + 1;
-    HIP_OK(hipEventRecord(tl.ev[i], stream));
+    HIP_OK(hipEventCreate(&tl.ev[tl.n]));
+    tl.n++;
+    HIP_OK(hipEventRecord(tl.ev[tl.n - 1], stream));
     return RM_OK;
   };
-  float4 *o = reinterpret_cast<float4 *>(d_rgba), *b = reinterpret_cast<float4 *>(d_bright);
-  if (wavefront) {
-    const WfWs &ws = wfWs;
-    HIP_OK(hipMemsetAsync(ws.counters, 0, WF_STRIDE * (kWfMaxBounces + 2) * sizeof(uint32_t), stream));
-    const dim3 pgrid(wfPrimaryWaves), mgrid(wfShadowWaves), mblock(64), dense(ds.numCUs * 16);
-    const int thr = envFlush > 0 && envFlush <= 64 ? envFlush : 16;
-    if ((st = stamp(0)) != RM_OK) return st;
-    for (int gen = 0; gen <= wfBounces; gen++) {
-      if (wfSkip) {
-        if (gen == 0) hipLaunchKernelGGL((wf_march_kernel<0, true>), pgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, pixelChunk, maxChunk, slotChunk);
-        else hipLaunchKernelGGL((wf_march_kernel<1, true>), pgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, rayChunk, maxChunk, slotChunk);
-        hipLaunchKernelGGL(wf_surface_kernel<true>, dense, block, 0, stream, slot->dev, map, W, H, ws, gen);
-        if (numLights > 0) hipLaunchKernelGGL((wf_march_kernel<2, true>), mgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, rayChunk, maxChunk, slotChunk);
-      } else {
-        if (gen == 0) hipLaunchKernelGGL((wf_march_kernel<0, false>), pgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, pixelChunk, maxChunk, slotChunk);
-        else hipLaunchKernelGGL((wf_march_kernel<1, false>), pgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, rayChunk, maxChunk, slotChunk);
-        hipLaunchKernelGGL(wf_surface_kernel<false>, dense, block, 0, stream, slot->dev, map, W, H, ws, gen);
-        if (numLights > 0) hipLaunchKernelGGL((wf_march_kernel<2, false>), mgrid, mblock, 0, stream, slot->dev, map, W, H, nRows, o, b, ws, gen, thr, rayChunk, maxChunk, slotChunk);
-      }
-      hipLaunchKernelGGL(wf_light_kernel, dense, block, 0, stream, slot->dev, map, W, H, o, b, ws, gen, wfBounces);
-    }
-    if ((st = stamp(1)) != RM_OK) return st;
+  const RenderLaunch r{slot->dev, map, W, H, nRows, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), dc, stream, rgrid, rblock};
+  if (wf.on) {
+    HIP_OK(hipMemsetAsync(wf.ws.counters, 0, WF_STRIDE * (kWfMaxBounces + 2) * sizeof(uint32_t), stream));
+    if ((st = stamp()) != RM_OK) return st;
+    if (fc.wfSkip) launch_wavefront<true>(r, wf, fc.wfBounces, numLights, ds.numCUs);
+    else launch_wavefront<false>(r, wf, fc.wfBounces, numLights, ds.numCUs);
   } else {
-    if ((st = stamp(0)) != RM_OK) return st;
-    // instantiations <BULB, COUNT, ENV, TEX>: the bulb class and the generic table walk, plain and counted, without
-    // procedural layers or textures; the generic kernel with either or both.  Features a launch does not need are
-    // compiled out so the common kernels keep their register budget.
-    if ((byCost || byGeom) && !settled) {  // this frame's launch order — from the previous frame's tile costs or from geometry — ahead of the render
-      const dim3 sgrid((tileCount + 255) / 256);
-      uint32_t *sortCost = oCost;
-      if (byGeom) {  // estimates into their own array (the kernel reads the stale costs of a tile's neighbourhood), stale costs cleared after
-        hipLaunchKernelGGL(tile_geom_kernel, sgrid, dim3(256), 0, stream, slot->dev, map, W, H, nRows, (int)rgrid.x, nw * tileW, tileH, tileCount, oCost, oCost2,
-                           (geomMode == 2 && haveCost) ? 1 : 0, ((geomMode == 2 && haveCost) ? ringCombined : 16), geomDilate);
-        HIP_OK(hipMemsetAsync(oCost, 0, (size_t)tileCount * sizeof(uint32_t), stream));
-        sortCost = oCost2;
-      }
-      HIP_OK(hipMemsetAsync(oHist, 0, 2 * kOrderBuckets * sizeof(uint32_t), stream));
-      hipLaunchKernelGGL(tile_hist_kernel, sgrid, dim3(256), 0, stream, sortCost, tileCount, oHist);
-      hipLaunchKernelGGL(tile_scatter_kernel, sgrid, dim3(256), 0, stream, sortCost, tileCount, oHist, oOrder, lastSort ? 1 : 0);
-      if ((st = stamp(1)) != RM_OK) return st;  // stage 0 = the ordering launches, stage 1 = the render
+    if ((st = stamp()) != RM_OK) return st;
+    if (to.sorts()) {
+      if ((st = launch_tile_order(to, r, nw * tileW, tileH, tileCount)) != RM_OK) return st;
+      if ((st = stamp()) != RM_OK) return st;  // stage 0 = the ordering launches, stage 1 = the render
     }
-    if (splitTimed >= 0 && splitTune) {
-      if (hipEventCreate(&splitTune->ev[splitTimed][0]) == hipSuccess && hipEventCreate(&splitTune->ev[splitTimed][1]) == hipSuccess)
-        HIP_OK(hipEventRecord(splitTune->ev[splitTimed][0], stream));
-      else splitTimed = -1;
-    }
-    if (tuneTimed >= 0 && tune) {  // the tuner's timed launch of this candidate shape: events around the render kernel alone
-      if (hipEventCreate(&tune->ev[tuneTimed][0]) == hipSuccess && hipEventCreate(&tune->ev[tuneTimed][1]) == hipSuccess)
-        HIP_OK(hipEventRecord(tune->ev[tuneTimed][0], stream));
-      else tuneTimed = -1;
-    }
-#define RM_LAUNCH(B, C, E, T) hipLaunchKernelGGL((render_kernel<B, C, E, T>), rgrid, rblock, 0, stream, slot->dev, map, W, H, nRows, o, b, dc)
-    if (envFeatures || textured) {
-      // counting instantiations of the layer / sampler kernels: the reference's work only (they have no shortcuts to count apart)
-#define RM_LAUNCH_NOSEC(B, E, T) hipLaunchKernelGGL((render_kernel<B, 0, E, T, false>), rgrid, rblock, 0, stream, slot->dev, map, W, H, nRows, o, b, dc)
-      if (envFeatures && textured) { if (count) RM_LAUNCH(false, 1, true, true); else if (secondary) RM_LAUNCH(false, 0, true, true); else RM_LAUNCH_NOSEC(false, true, true); }
-      else if (envFeatures) { if (count) RM_LAUNCH(false, 1, true, false); else if (secondary) RM_LAUNCH(false, 0, true, false); else RM_LAUNCH_NOSEC(false, true, false); }
-      else { if (count) RM_LAUNCH(false, 1, false, true); else if (secondary) RM_LAUNCH(false, 0, false, true); else RM_LAUNCH_NOSEC(false, false, true); }
-    } else if (bulb) {
-      // the counted launches keep the general form; the production ones take the plain form where the launcher found it
-      const bool plain = slot->host->bulbPlain != 0;
-      if (count == 1) RM_LAUNCH(kBulbGeneral, 1, false, false);
-      else if (count == 2) RM_LAUNCH(kBulbGeneral, 2, false, false);
-      else if (count == 3) RM_LAUNCH(kBulbGeneral, 3, false, false);
-      else if (secondary) { if (plain) RM_LAUNCH(kBulbPlain, 0, false, false); else RM_LAUNCH(kBulbGeneral, 0, false, false); }
-      else if (plain) RM_LAUNCH_NOSEC(kBulbPlain, false, false);
-      else RM_LAUNCH_NOSEC(kBulbGeneral, false, false);
-    } else {
-      if (count == 1) RM_LAUNCH(false, 1, false, false);
-      else if (count == 2) RM_LAUNCH(false, 2, false, false);
-      else if (count == 3) RM_LAUNCH(false, 3, false, false);
-      else if (secondary) RM_LAUNCH(false, 0, false, false);
-      else if (splitK > 0) {
-        // light split: the heavy tiles one light per workgroup first, every other tile behind them in the same grid; the last of a
-        // tile's workgroups to finish its march finishes the tile.  (A second launch for the finish cost 35-45 µs per frame —
-        // more than the split gains on throughput-bound frames; the same launch on a side stream gained nothing.)
-        HIP_OK(hipMemsetAsync(splitStore, 0, (size_t)splitK * sizeof(uint32_t), stream));  // the tiles' arrival counters
-        hipLaunchKernelGGL((render_kernel<false, 0, false, false, false, 1>), dim3((unsigned)(splitK * numLights + tileCount - splitK)), dim3(64), 0, stream,
-                           slot->dev, map, W, H, nRows, o, b, dc);
-      } else RM_LAUNCH_NOSEC(false, false, false);
-    }
-#undef RM_LAUNCH
-#undef RM_LAUNCH_NOSEC
-    if (tuneTimed >= 0 && tune) {
-      HIP_OK(hipEventRecord(tune->ev[tuneTimed][1], stream));
-      tune->timed[tuneTimed] = true;
-    }
-    if (splitTimed >= 0 && splitTune) {
-      HIP_OK(hipEventRecord(splitTune->ev[splitTimed][1], stream));
-      splitTune->timed[splitTimed] = true;
-    }
-    if ((st = stamp(((byCost || byGeom) && !settled) ? 2 : 1)) != RM_OK) return st;
+    int splitSlot = ls.timedSlot;
+    if ((st = ss.split.begin(splitSlot, stream)) != RM_OK || (st = ss.shape.begin(shapeSlot, stream)) != RM_OK) return st;
+    if ((st = dispatch_render(fc, count, slot->host->bulbPlain != 0, ls, numLights, tileCount, r)) != RM_OK) return st;
+    if ((st = ss.shape.end(shapeSlot, stream)) != RM_OK || (st = ss.split.end(splitSlot, stream)) != RM_OK) return st;
   }
+  if ((st = stamp()) != RM_OK) return st;
   HIP_OK(hipGetLastError());
-  ds.lastPath = wavefront ? 5 : 1;
-  ds.lastSplit = wavefront ? 0 : splitK;
+  ds.lastPath = wf.on ? 5 : 1;
+  ds.lastSplit = wf.on ? 0 : ls.tiles;
   if (timing) { ds.timed.push_back(tl); timedGuard.kept = true; }
   HIP_OK(hipEventRecord(slot->done, stream));
   if (count) {
@@ -1414,6 +1474,13 @@ int current_device_state(DeviceState **out) {
   *out = &g_dev[dev];
   return RM_OK;
 }
+// the row map of the rows [rowBegin, rowEnd) of an H-row frame (rm_render*, rm_render_counted*)
+int row_range(int H, int rowBegin, int rowEnd, RowMap *map, int *nRows) {
+  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
+  *nRows = rowEnd - rowBegin;
+  *map = RowMap{rowBegin, *nRows > 0 ? *nRows : 1, 0, 1, 0};
+  return RM_OK;
+}
 }  // namespace
 }  // namespace rm
 
@@ -1434,31 +1501,23 @@ int rm_set_device(int device) {
 int rm_render(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
               const RmGlobals *g, const RmSettings *s, int W, int H, int rowBegin, int rowEnd, float *d_rgba,
               float *d_bright, void *stream) {
-  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
-  int n = rowEnd - rowBegin;
-  RowMap map{rowBegin, n > 0 ? n : 1, 0, 1, 0};
-  return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright,
-                       static_cast<hipStream_t>(stream), 0, nullptr);
+  return rm_render_res(cam, objs, numObjects, lights, numLights, g, s, nullptr, W, H, rowBegin, rowEnd, d_rgba, d_bright, stream);
 }
 
 int rm_render_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                  const RmGlobals *g, const RmSettings *s, const RmTexture *textures, int numTextures, int W, int H,
                  int rowBegin, int rowEnd, float *d_rgba, float *d_bright, void *stream) {
-  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
-  int n = rowEnd - rowBegin;
-  RowMap map{rowBegin, n > 0 ? n : 1, 0, 1, 0};
   RmResources res{};
   res.textures = textures; res.numTextures = numTextures;
-  return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright,
-                       static_cast<hipStream_t>(stream), 0, nullptr, res);
+  return rm_render_res(cam, objs, numObjects, lights, numLights, g, s, &res, W, H, rowBegin, rowEnd, d_rgba, d_bright, stream);
 }
 
 int rm_render_res(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                   const RmGlobals *g, const RmSettings *s, const RmResources *res, int W, int H, int rowBegin, int rowEnd,
                   float *d_rgba, float *d_bright, void *stream) {
-  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
-  int n = rowEnd - rowBegin;
-  RowMap map{rowBegin, n > 0 ? n : 1, 0, 1, 0};
+  RowMap map;
+  int n;
+  if (int st = row_range(H, rowBegin, rowEnd, &map, &n)) return st;
   return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright,
                        static_cast<hipStream_t>(stream), 0, nullptr, res ? *res : kNoResources);
 }
@@ -1466,19 +1525,16 @@ int rm_render_res(const RmCamera *cam, const RmObject *objs, int numObjects, con
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                          const RmGlobals *g, const RmSettings *s, int W, int H, int rowBegin, int rowEnd, float *d_rgba,
                          float *d_bright, int mode, RmCounters *out) {
-  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
-  if (mode != RM_COUNT_REFERENCE && mode != RM_COUNT_EXECUTED) { set_error("bad counting mode"); return RM_ERR_INVALID_ARGUMENT; }
-  int n = rowEnd - rowBegin;
-  RowMap map{rowBegin, n > 0 ? n : 1, 0, 1, 0};
-  return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright, nullptr, mode, out);
+  return rm_render_counted_res(cam, objs, numObjects, lights, numLights, g, s, nullptr, W, H, rowBegin, rowEnd, d_rgba, d_bright,
+                               mode, out);
 }
 int rm_render_counted_res(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                           const RmGlobals *g, const RmSettings *s, const RmResources *res, int W, int H, int rowBegin, int rowEnd,
                           float *d_rgba, float *d_bright, int mode, RmCounters *out) {
-  if (rowBegin < 0 || rowEnd > H || rowBegin > rowEnd) { set_error("rows out of range"); return RM_ERR_INVALID_ARGUMENT; }
+  RowMap map;
+  int n;
+  if (int st = row_range(H, rowBegin, rowEnd, &map, &n)) return st;
   if (mode != RM_COUNT_REFERENCE && mode != RM_COUNT_EXECUTED) { set_error("bad counting mode"); return RM_ERR_INVALID_ARGUMENT; }
-  int n = rowEnd - rowBegin;
-  RowMap map{rowBegin, n > 0 ? n : 1, 0, 1, 0};
   return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright, nullptr, mode, out,
                        res ? *res : kNoResources);
 }
@@ -1510,13 +1566,8 @@ int rm_render_clocked(const RmCamera *cam, const RmObject *objs, int numObjects,
 int rm_render_tiles(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                     const RmGlobals *g, const RmSettings *s, int W, int H, int tileRows, int shard, int numShards,
                     float *d_rgba, float *d_bright, void *stream) {
-  if (tileRows <= 0 || numShards <= 0 || shard < 0 || shard >= numShards) {
-    set_error("bad tile partition");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  RowMap map{0, tileRows, shard, numShards, root_relief()};
-  return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, shard_rows(H, tileRows, shard, numShards, root_relief()),
-                       d_rgba, d_bright, static_cast<hipStream_t>(stream), 0, nullptr);
+  return rm_render_tiles_res(cam, objs, numObjects, lights, numLights, g, s, nullptr, W, H, tileRows, shard, numShards, d_rgba,
+                             d_bright, stream);
 }
 
 int rm_render_tiles_res(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
@@ -1750,7 +1801,7 @@ int rm_set_workspace_limit(unsigned long long bytes) {
   g_wsLimit.store(bytes == ~0ull ? ~0ull - 1 : bytes);
   for (DeviceState &ds : g_dev) {  // what was refused under the old limit may be asked for again
     std::lock_guard<std::mutex> lock(ds.mu);
-    ds.wfDenied.clear();
+    for (auto &kv : ds.streams) kv.second.wfDenied = 0;
   }
   return RM_OK;
 }
@@ -1760,14 +1811,10 @@ int rm_release_workspaces(unsigned long long *freedBytes) {
   std::lock_guard<std::mutex> lock(ds->mu);  // no launch is being enqueued on this device meanwhile
   size_t freed = 0;
   if (int st = release_workspaces(&freed)) return st;
-  ds->tileOrder.clear();  // the feedback costs lived in the buffers just freed
-  for (auto &kv : ds->shapeTune) kv.second.drop();
-  ds->shapeTune.clear();
+  for (auto &kv : ds->streams) { kv.second.shape.drop(); kv.second.split.drop(); }
+  ds->streams.clear();  // with the tile-order state: the feedback costs lived in the buffers just freed
   ds->shapeChoice.clear();
-  for (auto &kv : ds->splitTune) kv.second.drop();
-  ds->splitTune.clear();
   ds->splitChoice.clear();
-  ds->wfDenied.clear();
   if (freedBytes) *freedBytes = freed;
   return RM_OK;
 }
