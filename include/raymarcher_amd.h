@@ -34,11 +34,13 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 4
+#define RM_ABI_VERSION 5
 
 /* Capacity limits — src/realtime.h:17-27 (MAX_NUM_LIGHTS 10, MAX_NUM_SHAPES 30). */
 #define RM_MAX_LIGHTS 10
 #define RM_MAX_OBJECTS 30
+/* Frames of one rm_render_batch call. */
+#define RM_MAX_BATCH_FRAMES 1024
 
 /* Primitive type tags — src/utils/scenedata.h:18-33 == frag:53-68. */
 enum {
@@ -222,6 +224,27 @@ int rm_render_res(const RmCamera *cam, const RmObject *objs, int numObjects, con
                   int rowEnd, float *d_rgba, float *d_bright, void *stream);
 
 /*
+ * rm_render_batch — numFrames whole W×H frames of ONE scene in one kernel launch (no reference counterpart; the reference
+ * renders a sequence one draw call per frame, src/realtime.cpp:235-281): turntables, animation export, thumbnails, multi-view
+ * sets, and frames too small to fill the GPU on their own.  Frame f has its own camera cams[f] and its own globals — globals[f]
+ * when numGlobals == numFrames, globals[0] for every frame when numGlobals == 1 — (iTime, power, Julia seed, 2-D mode); the
+ * object, light, settings and resource tables (res may be NULL) are shared.  Frame f is written to d_rgba + f·H·W·4, rows
+ * bottom-up exactly as rm_render writes a whole frame; d_bright the same or NULL.  Every frame is bit-identical to rm_render of
+ * the same camera and globals.  Asynchronous on `stream`; host arrays are copied before return.
+ * numFrames == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT: numFrames < 0, numGlobals neither 1 nor numFrames, null
+ * cams / globals, W or H <= 0; RM_ERR_CAPACITY: numFrames > RM_MAX_BATCH_FRAMES; the tables, resources and device pointers are
+ * checked as rm_render_res checks them.
+ * Schedule: the frames share one launch of the one-lane-per-pixel kernel (rm_debug_last_path() = 6) in raster tile order, 8×8
+ * tiles unless rm_debug_set_tile_shape / RM_TILE_SHAPE pins a shape, no light split; a batch neither reads nor changes the
+ * per-stream tuner and tile-order state of single-frame renders.  A frame that rm_render would give the wavefront pipeline
+ * (path 5) is rendered as rm_render renders it, after the batched launch, in frame order on the same stream.  The scene blocks
+ * of a batch (≈9.7 KB per frame, pinned on the host and on the device) live in a ring of up to 4 grow-only slots per device.
+ */
+int rm_render_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                    int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W,
+                    int H, float *d_rgba, float *d_bright, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -335,6 +358,7 @@ int rm_get_timing(double *avgKernelMs, int *launches);
 /* Same, split by role, both averaged over ALL the launches (total = stage 0 + stage 1): stage 1 = the render (the one-lane-per-pixel
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
+ * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own).
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -359,7 +383,8 @@ int rm_set_kernel_path(int path);
  * that needs one allocates it again, and the next frame on each stream runs in raster tile order. */
 int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
-/* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error. */
+/* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
+ * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel (not a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -1238,7 +1238,9 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // SEC = false compiles main's secondary rays out (reflection loop, refraction): the launcher picks it when the settings or the
 // materials rule them out for the whole frame, so that what render() hands over for them (hit point, normal, direction) is not
 // carried across the shadow marches — fewer registers spilled around the hot loops, the same pixels.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+// BATCH changes no code: it gives the batched render kernels (rm_render_batch) instantiations of their own, so that each
+// single-frame kernel stays the only caller of its shadePixel and compiles exactly as it does without the batched ones.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
   float ndcx, ndcy;

@@ -87,12 +87,16 @@ static_assert(RM_TILE_W == 4 || RM_TILE_W == 8 || RM_TILE_W == 16, "tile width: 
 // grid: workgroups 0 … splitTiles·numLights − 1 are those tiles' partial workgroups (tile = tileOrder[b / numLights], light b mod
 // numLights: primary march, surface, THAT light's shadow march, its result to splitStore), the last of which to arrive finishes
 // the tile's pixels from the stored results (shadePixel's mode 2: no march); the rest render the other tiles whole.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+// BATCH (rm_render_batch, production kernels only): a (tilesX, tilesY, numFrames) grid over numFrames whole frames — frame
+// blockIdx.z reads SceneBlock sb[blockIdx.z] and writes nRows·W pixels from out + blockIdx.z·nRows·W (and bright likewise).
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
 __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES) : (ENV ? (SEC ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES) : (BULB ? (SEC ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES) : (SEC ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES))))) void render_kernel(const SceneBlock *__restrict__ sb, RowMap map, int W, int H,
                                                       int nRows, float4 *__restrict__ out,
                                                       float4 *__restrict__ bright,
                                                       unsigned long long *__restrict__ counters) {
   constexpr int CM = (COUNT == 3) ? 0 : COUNT;  // counting mode of the device code
+  static_assert(!BATCH || (COUNT == 0 && SPLIT == 0), "batched launches are production launches");
+  if (BATCH) sb += blockIdx.z;  // wave-uniform: the frame's own scene block
   unsigned long long t0 = 0, r0 = 0;
   if (COUNT == 3) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
   // LDS copy of the object table for per-lane (divergent) material lookups; the single-bulb class reads one entry.
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVE
   V4 col, br;
   Counters cnt{0, 0, 0, 0, 0, 0};
   bool hit;
-  shadePixel<BULB, CM, ENV, TEX, SEC, SPLIT>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
+  shadePixel<BULB, CM, ENV, TEX, SEC, SPLIT, BATCH>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
   if (SPLIT == 1 && split.part >= 0) {
     // A partial workgroup: its results are in memory.  The LAST of the tile's numLights workgroups to get here finishes the tile —
     // surface point, AO and the light sum from the stored results, no march (shadePixel in mode 2) — the others are done.  Release /
@@ -155,6 +159,11 @@ __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVE
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // only the finisher invalidates its view before it reads the others' records
     split.part = -1;
     shadePixel<BULB, CM, ENV, TEX, SEC, 2>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
+  }
+  if (BATCH) {
+    const size_t f = (size_t)blockIdx.z * (size_t)nRows * (size_t)W;
+    out += f;
+    if (bright) bright += f;
   }
   const size_t o = (size_t)r * W + x;
   out[o] = make_float4(col.x, col.y, col.z, col.w);
@@ -194,9 +203,15 @@ __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVE
 
 // sdMengerSponge's uniform prologue (frag:1052-1053), once per launch, with the device's own rm_math (bit-exactness with the
 // oracle needs the contract's sin / cos / smoothstep, which only the device and the oracle implement).
-__global__ void scene_prep_kernel(SceneBlock *sb) {
+RM_DEV void menger_uniforms(SceneBlock *sb) {
   sb->mengerAni = smoothstep_(-0.2f, 0.2f, -cos_(0.5f * sb->g.iTime));
   sb->mengerOff = 1.5f * sin_(0.01f * sb->g.iTime);
+}
+__global__ void scene_prep_kernel(SceneBlock *sb) { menger_uniforms(sb); }
+// the same for every frame of a batch (rm_render_batch): one thread per scene block, each with its own iTime
+__global__ void scene_prep_batch_kernel(SceneBlock *sb, int n) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < n) menger_uniforms(sb + f);
 }
 
 // ---- tile order ------------------------------------------------------------------------------------------
@@ -499,10 +514,19 @@ struct StreamState {
   size_t wfDenied = 0;       // smallest wavefront workspace (bytes) that could not be had on the stream; 0: none was refused
 };
 struct TimedLaunch { hipEvent_t ev[5]; int n; };  // n = 2 (one stage) or 3 (tile-order sort + render kernel)
+// The scene blocks of one batch (rm_render_batch): `cap` SceneBlocks, contiguous, pinned on the host and on the device.
+struct BatchSlot {
+  SceneBlock *host = nullptr, *dev = nullptr;
+  int cap = 0;
+  hipEvent_t done = nullptr;
+  bool used = false;
+};
 struct DeviceState {
   std::mutex mu;                 // guards everything below; held for the host-side enqueue of ONE launch on this device
   std::vector<Slot> slots;       // ring of scene-table slots; grows (to kSlotsMax) instead of waiting for a busy slot
   size_t next = 0;
+  std::vector<BatchSlot> batchSlots;  // the same for batches (acquire_batch_slot), to kBatchSlotsMax
+  size_t batchNext = 0;
   unsigned long long *dCounters = nullptr;  // 10 words: evals, iterations, hits, clock stamps (2), span pointer, shades, fbm9, fbmd8, shapes
   std::vector<TimedLaunch> timed;           // rm_set_timing / rm_get_timing, per device
   int numCUs = 0;
@@ -585,6 +609,57 @@ int acquire_slot(DeviceState &ds, Slot **out) {
   ds.next = (ds.next + 1) % ds.slots.size();
   s->used = true;
   *out = s;
+  return RM_OK;
+}
+
+// The batch ring (rm_render_batch) keeps the single-frame ring's rules: a slot is written only after the event recorded behind
+// its last launch has fired (the pinned blocks of a batch whose upload may still be in flight are never overwritten); a busy
+// slot gets a fresh one in front of it instead of a wait, up to kBatchSlotsMax slots, and only then the enqueue waits for the
+// oldest.  Slots are grow-only: a batch larger than the idle slot it lands on replaces that slot's buffers by ones of the next
+// power of two >= numFrames (16 … RM_MAX_BATCH_FRAMES blocks, 9.7 KB each) — at most six times per slot over a process, and
+// those frees may wait for the device.  Caller holds ds.mu.
+constexpr int kBatchSlotsMax = 4;
+void free_batch_slot(BatchSlot &b) {
+  if (b.host) (void)hipHostFree(b.host);
+  if (b.dev) (void)hipFree(b.dev);
+  if (b.done) (void)hipEventDestroy(b.done);
+  b = BatchSlot{};
+}
+int acquire_batch_slot(DeviceState &ds, int n, BatchSlot **out) {
+  if (ds.batchSlots.empty()) { ds.batchSlots.resize(1); ds.batchNext = 0; }
+  BatchSlot *b = &ds.batchSlots[ds.batchNext];
+  if (b->used) {
+    const hipError_t q = hipEventQuery(b->done);
+    if (q == hipErrorNotReady) {
+      if ((int)ds.batchSlots.size() < kBatchSlotsMax) {
+        ds.batchSlots.insert(ds.batchSlots.begin() + (long)ds.batchNext, BatchSlot{});  // in front of the busy one: ring order
+        b = &ds.batchSlots[ds.batchNext];
+      } else {
+        HIP_OK(hipEventSynchronize(b->done));
+      }
+    } else if (q != hipSuccess) {
+      set_error(std::string("hipEventQuery: ") + hipGetErrorString(q));
+      return RM_ERR_DEVICE;
+    }
+  }
+  if (b->cap < n) {  // idle (never used, or its last launch has finished): grow
+    int cap = 16;
+    while (cap < n) cap *= 2;
+    free_batch_slot(*b);
+    const size_t bytes = (size_t)cap * sizeof(SceneBlock);
+    if (hipHostMalloc(reinterpret_cast<void **>(&b->host), bytes, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&b->dev), bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      free_batch_slot(*b);  // an empty slot (cap 0): the next batch that lands on it tries again
+      set_error("allocation of " + std::to_string(bytes) + " bytes of batch scene blocks failed");
+      return RM_ERR_DEVICE;
+    }
+    b->cap = cap;
+  }
+  ds.batchNext = (ds.batchNext + 1) % ds.batchSlots.size();
+  b->used = true;
+  *out = b;
   return RM_OK;
 }
 
@@ -997,14 +1072,10 @@ int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {
   return (g->juliaSeed[0] == 0.0f && g->juliaSeed[1] == 0.0f) ? 1 : 0;
 }
 
-int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
-                const RmGlobals *g, const RmSettings *s, hipStream_t stream, DeviceState &ds, Slot **slotOut,
-                const RmResources &res, const int32_t *tileOrder = nullptr, uint32_t *tileCost = nullptr,
-                int tileCount = 0, int tileShift = 3, int splitTiles = 0, float *splitStore = nullptr) {  // caller holds ds.mu
-  Slot *slot;
-  int st = acquire_slot(ds, &slot);
-  if (st != RM_OK) return st;
-  SceneBlock *h = slot->host;
+// Everything of a frame's SceneBlock that the caller's tables decide (the launch fields — tile order, light split, Menger
+// uniforms — are the stager's).
+void fill_scene(SceneBlock *h, const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                const RmGlobals *g, const RmSettings *s, const RmResources &res) {
   h->cam = *cam; h->g = *g; h->s = *s;
   h->numObjects = numObjects; h->numLights = numLights;
   for (int i = 0; i < numObjects; i++) h->objs[i] = objs[i];
@@ -1018,6 +1089,17 @@ int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const
   scene_cull_ball(h);
   ray_planes(h);
   h->bulbPlain = bulb_plain(objs, numObjects, g);
+}
+
+int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                const RmGlobals *g, const RmSettings *s, hipStream_t stream, DeviceState &ds, Slot **slotOut,
+                const RmResources &res, const int32_t *tileOrder = nullptr, uint32_t *tileCost = nullptr,
+                int tileCount = 0, int tileShift = 3, int splitTiles = 0, float *splitStore = nullptr) {  // caller holds ds.mu
+  Slot *slot;
+  int st = acquire_slot(ds, &slot);
+  if (st != RM_OK) return st;
+  SceneBlock *h = slot->host;
+  fill_scene(h, cam, objs, numObjects, lights, numLights, g, s, res);
   h->tileOrder = tileOrder; h->tileCost = tileCost; h->tileCount = tileCount;
   h->tileShift = tileShift;
   h->splitTiles = splitTiles; h->splitStore = splitStore;
@@ -1169,11 +1251,16 @@ unsigned long long picture_key(const RmCamera *cam, const RmObject *objs, int nu
 
 // Tile shape ("tile shape" above) as a tile shift: 8×8 unless the tuner is measuring or has chosen 4×16 for this picture on this
 // stream.  *timedSlot: the tuner's timing slot for this launch, -1 for none.
+constexpr int kDefaultTileShift = (RM_TILE_W == 8) ? 3 : (RM_TILE_W == 4 ? 2 : (RM_TILE_W == 16 ? 4 : 3));
+// rm_debug_set_tile_shape / RM_TILE_SHAPE: 0 tune, 2 pinned to 4×16, 3 pinned to 8×8
+int tile_shape_request() {
+  static const int envShape = env_int("RM_TILE_SHAPE", 0);
+  return g_tileShape.load() >= 0 ? g_tileShape.load() : envShape;
+}
 int tile_shift(DeviceState &ds, StreamState &ss, const FrameClass &fc, bool wavefront, int count, int W, int nRows,
                unsigned long long key, int *timedSlot) {
   *timedSlot = -1;
-  static const int envShape = env_int("RM_TILE_SHAPE", 0);
-  const int shapeReq = g_tileShape.load() >= 0 ? g_tileShape.load() : envShape;
+  const int shapeReq = tile_shape_request();
   const bool bigFrame = (size_t)nRows * W >= (size_t)2048 * 64;
   if ((shapeReq == 2 || shapeReq == 3) && count == 0) return shapeReq;  // the counted / stamped diagnostic builds keep 8×8 (their callers size per-wave arrays by it)
   if (RM_TILE_W == 8 && !fc.bulb && !wavefront && !fc.twoD && count == 0 && bigFrame && !ds.dbgTileOrder && !ds.dbgTileCost) {
@@ -1181,7 +1268,7 @@ int tile_shift(DeviceState &ds, StreamState &ss, const FrameClass &fc, bool wave
     *timedSlot = t.slot;
     return t.candidate ? 2 : 3;
   }
-  return (RM_TILE_W == 8) ? 3 : (RM_TILE_W == 4 ? 2 : (RM_TILE_W == 16 ? 4 : 3));
+  return kDefaultTileShift;
 }
 
 // Tile order ("tile order" above): 0 raster order, 1 feedback — tiles start heaviest-first by the costs the previous frame of this
@@ -1312,15 +1399,15 @@ void launch_wavefront(const RenderLaunch &r, const Wavefront &wf, int bounces, i
 // render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>: the bulb class and the generic table walk, plain and counted, without
 // procedural layers or textures; the generic kernel with either or both.  Features a launch does not need are compiled out so the
 // common kernels keep their register budget.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
 void launch_kernel(const RenderLaunch &r) {
-  hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
+  hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT, BATCH>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
 }
 // a production launch: the secondary rays compiled in only where they can fire
-template <int BULB, bool ENV, bool TEX>
+template <int BULB, bool ENV, bool TEX, bool BATCH = false>
 void launch_production(bool secondary, const RenderLaunch &r) {
-  if (secondary) launch_kernel<BULB, 0, ENV, TEX>(r);
-  else launch_kernel<BULB, 0, ENV, TEX, false>(r);
+  if (secondary) launch_kernel<BULB, 0, ENV, TEX, true, 0, BATCH>(r);
+  else launch_kernel<BULB, 0, ENV, TEX, false, 0, BATCH>(r);
 }
 // the counted (1: reference work, 2: executed work) and clock-stamped (3) launches
 template <int BULB>
@@ -1359,6 +1446,27 @@ int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const Light
   return RM_OK;
 }
 
+// the batched production kernels (rm_render_batch): one class for every frame of the launch
+void dispatch_batch(const FrameClass &fc, bool plainBulb, const RenderLaunch &r) {
+  if (fc.envFeatures && fc.textured) launch_production<0, true, true, true>(fc.secondary, r);
+  else if (fc.envFeatures) launch_production<0, true, false, true>(fc.secondary, r);
+  else if (fc.textured) launch_production<0, false, true, true>(fc.secondary, r);
+  else if (fc.bulb && plainBulb) launch_production<kBulbPlain, false, false, true>(fc.secondary, r);
+  else if (fc.bulb) launch_production<kBulbGeneral, false, false, true>(fc.secondary, r);
+  else launch_production<0, false, false, true>(fc.secondary, r);
+}
+
+// rm_set_kernel_path / RM_KERNEL_PATH: 0 = the measured-fastest schedule of the scene's class
+int kernel_path_request() {
+  static const int envPath = env_int("RM_KERNEL_PATH", 0);
+  return g_kernelPath.load() ? g_kernelPath.load() : envPath;
+}
+// RM_WAVES_PER_BLOCK: 1 (default), 2 or 4 waves per workgroup (launch_render has the measurements)
+int waves_per_block() {
+  static const int wpb = env_int("RM_WAVES_PER_BLOCK", 0);
+  return (wpb == 1 || wpb == 2 || wpb == 4) ? wpb : 1;
+}
+
 int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                   const RmGlobals *g, const RmSettings *s, int W, int H, RowMap map, int nRows, float *d_rgba,
                   float *d_bright, hipStream_t stream, int count, RmCounters *countersOut,
@@ -1378,8 +1486,7 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
   StreamState &ss = ds.streams[stream];
   // Two schedules of the same per-ray arithmetic, identical bits: rm::render_kernel (one lane per pixel; every class, and the
   // counted variants) and, for table-walk classes with bounces, the wavefront pipeline.
-  static const int envPath = env_int("RM_KERNEL_PATH", 0);
-  const int pathReq = g_kernelPath.load() ? g_kernelPath.load() : envPath;  // 0 = the measured-fastest schedule of the scene's class
+  const int pathReq = kernel_path_request();
   const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, g, s, count);
   Wavefront wf;
   if ((st = setup_wavefront(ds, ss, dev, fc, objs, numObjects, numLights, W, nRows, map.numShards > 1, pathReq, stream, &wf)) != RM_OK) return st;
@@ -1388,8 +1495,7 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
   // per workgroup for every class (measured at the register budgets above: the 4K bulb frame 2.31 / 2.34 / 2.58 ms at
   // 1 / 2 / 4 waves, the 8K Menger frame 51.0 / 51.8 / 58.6 ms, bump + reflection at 4K 19.4 / 19.8 / 22.1 ms; at the
   // compiler's own budgets two waves were best for the bulb, profiles/r02_c_waves_per_block.md).  RM_WAVES_PER_BLOCK overrides.
-  static const int wpb = env_int("RM_WAVES_PER_BLOCK", 0);
-  const int nw = (wpb == 1 || wpb == 2 || wpb == 4) ? wpb : 1;
+  const int nw = waves_per_block();
   const unsigned long long key = picture_key(cam, objs, numObjects, lights, numLights, g, s, map);
   int shapeSlot;
   const int tileShift = tile_shift(ds, ss, fc, wf.on, count, W, nRows, key, &shapeSlot);
@@ -1481,6 +1587,121 @@ int row_range(int H, int rowBegin, int rowEnd, RowMap *map, int *nRows) {
   *map = RowMap{rowBegin, *nRows > 0 ? *nRows : 1, 0, 1, 0};
   return RM_OK;
 }
+
+// ---- batches: numFrames whole frames of one scene, each with its own camera and globals, in one launch -----------------------
+// Every batched frame renders with the one-lane-per-pixel kernel in raster tile order (no tile-order history, no light split), 8×8
+// tiles unless a shape is pinned: a batch reads and changes none of the per-stream state (tuners, tile order), so a host that
+// interleaves batches with repeated single frames sees those tune as before.  The frames overlap on the chip as frames in flight
+// on several streams do — the tail of frame f under the full waves of frame f + 1 — without streams or per-call host overhead.
+// A frame that would take the wavefront pipeline on its own (path 5, chosen or requested) is rendered through launch_render
+// instead, after the batched launch, in frame order on the same stream.
+int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
+                 const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H, float *d_rgba,
+                 float *d_bright, hipStream_t stream) {
+  // every argument check ahead of the first HIP call (as launch_render's)
+  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (numFrames == 0) return RM_OK;
+  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
+  if (st != RM_OK) return st;
+  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
+  const size_t frame = (size_t)H * W * 4;  // floats per frame
+  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
+  // which frames the single-frame launcher would give the wavefront pipeline (launch_render, setup_wavefront): only the 2-D mode,
+  // a per-frame global, can tell frames apart
+  const int pathReq = kernel_path_request();
+  std::vector<char> alone(numFrames, 0);
+  bool anyBatched = false, plainBulb = true;
+  for (int f = 0; f < numFrames; f++) {
+    const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(f), s, 0);
+    alone[f] = fc.wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(objs, numObjects, fc.wfBounces, (size_t)H * W, false)));
+    if (!alone[f]) {
+      anyBatched = true;
+      plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
+    }
+  }
+  if (anyBatched) {
+    int dev = 0;
+    HIP_OK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
+    DeviceState &ds = g_dev[dev];
+    std::lock_guard<std::mutex> lock(ds.mu);  // nothing below waits for the GPU but acquire_batch_slot at its bounds
+    BatchSlot *b;
+    if ((st = acquire_batch_slot(ds, numFrames, &b)) != RM_OK) return st;
+    const int pinned = tile_shape_request();
+    const int tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
+    // the shared parts once (frame 0's block), then per frame its camera, globals and what they decide
+    SceneBlock *h0 = b->host;
+    fill_scene(h0, &cams[0], objs, numObjects, lights, numLights, globalsOf(0), s, res);
+    h0->tileOrder = nullptr; h0->tileCost = nullptr; h0->tileCount = 0;
+    h0->tileShift = tileShift;
+    h0->splitTiles = 0; h0->splitStore = nullptr;
+    h0->mengerAni = 0.0f; h0->mengerOff = 0.0f;
+    bool bulbInTable = false, menger = false;
+    for (int i = 0; i < numObjects; i++) {
+      bulbInTable = bulbInTable || objs[i].type == RM_MANDELBULB;  // the only type whose cull bounds read the globals
+      menger = menger || objs[i].type == RM_MENGERSPONGE;
+    }
+    for (int f = 1; f < numFrames; f++) {
+      SceneBlock *h = b->host + f;
+      *h = *h0;
+      h->cam = cams[f];
+      h->g = *globalsOf(f);
+      if (bulbInTable && numGlobals > 1) scene_cull_ball(h);
+      ray_planes(h);
+      h->bulbPlain = bulb_plain(objs, numObjects, &h->g);
+    }
+    HIP_OK(hipMemcpyAsync(b->dev, b->host, (size_t)numFrames * sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
+    if (menger) {  // per frame, its own iTime; stream-ordered between the upload and the render
+      hipLaunchKernelGGL(scene_prep_batch_kernel, dim3((numFrames + 63) / 64), dim3(64), 0, stream, b->dev, numFrames);
+      HIP_OK(hipGetLastError());
+    }
+    const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
+    const int nw = waves_per_block(), tileW = 1 << tileShift, tileH = 64 >> tileShift;
+    TimedLaunch tl{};
+    const bool timing = g_timing.load();
+    struct TimedGuard {
+      TimedLaunch &t; bool kept = false;
+      ~TimedGuard() { if (!kept) for (int i = 0; i < t.n; i++) (void)hipEventDestroy(t.ev[i]); }
+    } timedGuard{tl};
+    auto stamp = [&]() -> int {
+      if (!timing) return RM_OK;
+      HIP_OK(hipEventCreate(&tl.ev[tl.n]));
+      tl.n++;
+      HIP_OK(hipEventRecord(tl.ev[tl.n - 1], stream));
+      return RM_OK;
+    };
+    if ((st = stamp()) != RM_OK) return st;
+    // one launch per run of consecutive batched frames (one run unless wavefront frames sit between them)
+    for (int f0 = 0; f0 < numFrames;) {
+      if (alone[f0]) { f0++; continue; }
+      int f1 = f0;
+      while (f1 < numFrames && !alone[f1]) f1++;
+      const RowMap map{0, H, 0, 1, 0};
+      const dim3 grid((W + nw * tileW - 1) / (nw * tileW), (H + tileH - 1) / tileH, (unsigned)(f1 - f0));
+      const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba + f0 * frame),
+                           d_bright ? reinterpret_cast<float4 *>(d_bright + f0 * frame) : nullptr, nullptr, stream, grid, dim3(64 * nw)};
+      dispatch_batch(fc, plainBulb, r);
+      f0 = f1;
+    }
+    if ((st = stamp()) != RM_OK) return st;
+    HIP_OK(hipGetLastError());
+    ds.lastPath = 6;
+    ds.lastSplit = 0;
+    if (timing) { ds.timed.push_back(tl); timedGuard.kept = true; }
+    HIP_OK(hipEventRecord(b->done, stream));
+  }
+  const RowMap whole{0, H, 0, 1, 0};
+  for (int f = 0; f < numFrames; f++)
+    if (alone[f] && (st = launch_render(&cams[f], objs, numObjects, lights, numLights, globalsOf(f), s, W, H, whole, H, d_rgba + f * frame,
+                                        d_bright ? d_bright + f * frame : nullptr, stream, 0, nullptr, res)) != RM_OK)
+      return st;
+  return RM_OK;
+}
 }  // namespace
 }  // namespace rm
 
@@ -1520,6 +1741,13 @@ int rm_render_res(const RmCamera *cam, const RmObject *objs, int numObjects, con
   if (int st = row_range(H, rowBegin, rowEnd, &map, &n)) return st;
   return launch_render(cam, objs, numObjects, lights, numLights, g, s, W, H, map, n, d_rgba, d_bright,
                        static_cast<hipStream_t>(stream), 0, nullptr, res ? *res : kNoResources);
+}
+
+int rm_render_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
+                    const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W, int H, float *d_rgba,
+                    float *d_bright, void *stream) {
+  return launch_batch(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
+                      d_rgba, d_bright, static_cast<hipStream_t>(stream));
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
@@ -1812,6 +2040,8 @@ int rm_release_workspaces(unsigned long long *freedBytes) {
   size_t freed = 0;
   if (int st = release_workspaces(&freed)) return st;
   for (auto &kv : ds->streams) { kv.second.shape.drop(); kv.second.split.drop(); }
+  for (auto &b : ds->batchSlots) { freed += (size_t)b.cap * sizeof(SceneBlock); free_batch_slot(b); }  // the device has drained
+  ds->batchSlots.clear();
   ds->streams.clear();  // with the tile-order state: the feedback costs lived in the buffers just freed
   ds->shapeChoice.clear();
   ds->splitChoice.clear();

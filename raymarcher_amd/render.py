@@ -146,6 +146,22 @@ class Scene:
         return SceneTables(cam, objs, no, lights, nl, g, tex_list)
 
 
+def batch_arrays(cameras, globals_):
+    """The ctypes arrays of rm_render_batch: (RmCamera * N, RmGlobals * 1 or N).  globals_ is one RmGlobals (shared by every
+    frame) or a sequence of N; raises ValueError on any other length or element type."""
+    cameras = list(cameras)
+    if not all(isinstance(c, abi.RmCamera) for c in cameras):
+        raise ValueError("cameras must be RmCamera structs (build_camera(...)[0])")
+    if len(cameras) > abi.RM_MAX_BATCH_FRAMES:
+        raise ValueError(f"{len(cameras)} cameras: at most RM_MAX_BATCH_FRAMES = {abi.RM_MAX_BATCH_FRAMES} frames per batch")
+    globs = [globals_] if isinstance(globals_, abi.RmGlobals) else list(globals_)
+    if not all(isinstance(g, abi.RmGlobals) for g in globs):
+        raise ValueError("globals_ must be an RmGlobals or a sequence of them")
+    if len(globs) != len(cameras) and len(globs) != 1:
+        raise ValueError(f"{len(globs)} globals for {len(cameras)} cameras: pass one, or one per camera")
+    return (abi.RmCamera * max(len(cameras), 1))(*cameras), (abi.RmGlobals * len(globs))(*globs)
+
+
 class Renderer:
     """Launches the HIP raymarch on one GPU; outputs are torch tensors on that device."""
 
@@ -218,6 +234,25 @@ class Renderer:
         res, _keep = self._resources(tables)
         check(lib().rm_render_res(*tables.args(settings), C.byref(res), W, H, row_begin, row_end, C.c_void_p(out.data_ptr()),
                                   C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
+        return (out, br) if bright else out
+
+    def render_batch(self, tables, settings, W, H, cameras, globals_=None, bright=False, out=None):
+        """rm_render_batch: N whole frames of the scene in `tables`, frame i seen through cameras[i] (RmCamera, as build_camera
+        returns them) → float32 tensor (N, H, W, 4), row 0 = bottom.  globals_: None (tables.globals_ for every frame), one
+        RmGlobals for every frame, or a sequence of N of them."""
+        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
+        n = len(cameras)
+        shape = (n, H, W, 4)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != self.torch.float32 or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+        t = self.torch
+        if out is None:
+            out = t.empty(shape, dtype=t.float32, device=self.device)
+        br = t.empty_like(out) if bright else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_render_batch(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
+                                    C.byref(settings), C.byref(res), W, H, C.c_void_p(out.data_ptr()),
+                                    C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
