@@ -978,7 +978,8 @@ RM_DEV bool lightTerm(const RmLight &li, const LightGeom &g, const Material &mat
 // wants a march — one evaluation per trip; a lane whose ray ends starts its next one in the same trip.  Each ray is the very
 // same sequence of evaluations as in march<…, SHADOW = true>: same origin, direction, cull end, step cap, hit test.
 // Returns the mask of lights whose ray hit.  (The schedule simulators, scripts/sim/, price this at ×0.95 of the
-// instructions of the per-light loop on the bench frame and ×0.87 on the 8K Menger frame.)
+// instructions of the per-light loop on the bench frame and ×0.87 on the 8K Menger frame.)  It balances the rays within a lane
+// only: the primary rays of the bulb kernels without layers or textures pool them across the wave instead (shadowPool).
 template <int BULB, int COUNT, bool CULLS>
 RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float far, Counters &cnt) {
   const int maxSteps = sb->s.maxSteps;
@@ -1019,6 +1020,27 @@ RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float fa
   return hitMask;
 }
 
+// Hard shadows from directional lights only (wave-uniform): the frames whose shadow marches the queue or the pool may schedule.
+RM_DEV bool hardDirectionalOnly(const SceneBlock *sb) {
+  const int nl = sb->numLights;
+  bool ok = sb->s.enableSoftShadow == 0 && nl > 0;
+  for (int i = 0; i < nl; i++) ok = ok && sb->lights[i].type == RM_LIGHT_DIRECTIONAL;
+  return ok;
+}
+// getPhong's light sum over hard shadows, given the mask of lights whose shadow ray hit (bit i = light i): the shadow queue's and
+// the shadow pool's (renderPooled).  `total` holds the ambient term.
+RM_DEV V3 hardLightSum(const SceneBlock *sb, const Material &mat, V3 N, V3 p, V3 V, float far, float ks, uint32_t hitMask,
+                       V3 total) {
+  const int nl = sb->numLights;
+  for (int i = 0; i < nl; i++) {
+    const RmLight &li = sb->lights[i];
+    const LightGeom g = lightSetup(li, p, far);
+    V3 cur;
+    if (lightTerm(li, g, mat, N, V, ks, ((hitMask >> i) & 1u) ? 0 : -1, 1.0f, false, cur)) total = add(total, cur);
+  }
+  return total;
+}
+
 // frag:1842-1933 with getDiffuse's untextured path (frag:1749-1752) and getSpecular (frag:1787-1792)
 // RES = true adds the area-light branch (frag:1884-1905); `objs` is only read there.
 // CULLS: end marches at the scene's bounds and pass over far objects in the table walk (off in the ENV instantiations, whose
@@ -1042,10 +1064,9 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
   if (BULB && !RES && COUNT != 1) {
     // hard shadows from directional lights only (wave-uniform test): the shadow marches run as a per-lane queue.  Single-bulb
     // class only: measured 2.46 → 2.37 ms on the 4K bulb frame, but 60 → 63 ms on the 8K Menger frame, whose evaluations are
-    // too cheap to pay for the ray set-up inside the loop
-    bool queue = !soft && nl > 0;
-    for (int i = 0; i < nl; i++) queue = queue && sb->lights[i].type == RM_LIGHT_DIRECTIONAL;
-    if (queue) {
+    // too cheap to pay for the ray set-up inside the loop.  (The primary rays of the bulb kernels without layers or textures
+    // take these pixels to the wave's shadow pool instead, renderPooled; their secondary rays come here.)
+    if (hardDirectionalOnly(sb)) {
       uint32_t need = 0u;
       for (int i = 0; i < nl; i++) {
         const RmLight &li = sb->lights[i];
@@ -1053,13 +1074,7 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
         if (!(dot(N, L) <= 0.005f)) need |= 1u << i;  // a light that N·L drops is not marched (see below)
       }
       const uint32_t hitMask = shadowQueue<BULB, COUNT, CULLS>(sb, so, need, far, cnt);
-      for (int i = 0; i < nl; i++) {
-        const RmLight &li = sb->lights[i];
-        const LightGeom g = lightSetup(li, p, far);
-        V3 cur;
-        if (lightTerm(li, g, mat, N, V, ks, ((hitMask >> i) & 1u) ? 0 : -1, 1.0f, false, cur)) total = add(total, cur);
-      }
-      return total;
+      return hardLightSum(sb, mat, N, p, V, far, ks, hitMask, total);
     }
   }
   for (int i = 0; i < nl; i++) {
@@ -1110,8 +1125,164 @@ RM_DEV V3 bulbTrapColor(float ty, float tz, float tw) {
   return scale(c, 0.5f);
 }
 
+// ---- the wave's shadow pool (bulb class, hard shadows, directional lights) ---------------------------------------------
+// shadowQueue balances a pixel's rays within its lane only, and it runs inside render()'s hit branch: a wave pays for its
+// busiest lane while the background lanes, the lanes whose lights N·L dropped and the lanes done early idle.  Here the rays of
+// all the wave's pixels go into ONE list and every lane of the wave marches them: a lane whose ray ends, or that has none,
+// takes the next unclaimed ray of any pixel, and the hit bit goes back to the pixel that owns the ray.  The list is
+// light-major (light 0's rays of every pixel, then light 1's, …): listed pixel-major, the first pixels' rays would start first
+// and the others' long rays would be left for the tail (an offline schedule simulation prices that above the queue).  Each ray is still the
+// very same sequence of evaluations as in march<…, SHADOW = true> — only the lane that computes it changes, and sdScene's
+// per-lane result does not depend on the other lanes (its wave-uniform choices are bit-neutral).
+//
+// Every lane of the wave that renders a pixel calls it, converged.  pend: the lights whose ray is still to march from `so`
+// (0 for a lane without one); dStart: the depth at which they resume — |sdScene(so)| after the shared first step (renderPooled),
+// their second evaluation, or −1: from the start.  Returns the mask of this lane's pending lights whose ray hit.
+// LDS: per wave (at most 4 per workgroup) a list of 64·RM_MAX_LIGHTS 16-bit entries (lane | light << 6) and the hit masks,
+// 16 bits per lane: 5.6 KB per workgroup.
+constexpr int kPoolWaves = 4, kPoolList = 64 * RM_MAX_LIGHTS;
+static_assert(RM_MAX_LIGHTS <= 16, "a pool entry holds the light in 10 bits, a hit mask 16 lights");
+template <int BULB, int COUNT>
+RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dStart, float far, Counters &cnt) {
+  __shared__ uint16_t s_list[kPoolWaves][kPoolList];
+  __shared__ uint32_t s_hits[kPoolWaves][32];
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)__lane_id();
+  uint16_t *list = s_list[wave];
+  uint32_t *hitw = s_hits[wave];
+  hitw[lane >> 1] = 0u;  // every lane zeroes the word that holds its mask (its pair partner may too)
+  // the list, light by light: offset = the earlier lights' rays + this lane's rank among the lanes that march this light
+  const int nl = sb->numLights;
+  uint32_t n = 0u;  // wave-uniform
+  for (int i = 0; i < nl; i++) {
+    const bool mine = ((pend >> i) & 1u) != 0u;
+    const uint64_t m = __ballot(mine);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (mine) list[n + rank] = (uint16_t)(lane | (i << 6));
+    n += (uint32_t)__popcll(m);
+  }
+  __builtin_amdgcn_wave_barrier();
+  const int maxSteps = sb->s.maxSteps;
+  int cur = -1, own = 0, step = 0;  // the light and the owner lane of this lane's ray (cur = −1: none)
+  V3 o = so, L = v3(0.0f, 0.0f, 0.0f);
+  float depth = 0.0f, end = 0.0f;
+  uint32_t next = 0u;  // wave-uniform: the first unclaimed entry
+  for (;;) {
+    const uint64_t idle = __ballot(cur < 0);
+    if (idle != 0ull && next < n) {  // wave-uniform: hand out the next rays in list order, one per idle lane
+      const uint32_t k = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+      next += (uint32_t)__popcll(idle);
+      const bool take = cur < 0 && k < n;
+      uint32_t e = 0u;
+      if (take) e = list[k];
+      // the owner's origin and resume depth, read by every lane (a permute reads only active lanes)
+      const int src = (int)(e & 63u);
+      const V3 os = v3(__shfl(so.x, src), __shfl(so.y, src), __shfl(so.z, src));
+      const float ds = __shfl(dStart, src);
+      if (take) {
+        cur = (int)(e >> 6);
+        own = src;
+        o = os;
+        const RmLight &li = sb->lights[cur];  // per-lane index: a vector load, once per ray
+        L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));  // lightSetup's direction of a directional light
+        end = bulbCullEnd(sb, o, L, far);
+        const bool resume = !(ds < 0.0f);  // after the shared first step (a NaN |d0| resumes too, as march() would go on)
+        depth = resume ? ds : 0.0f;
+        step = resume ? 1 : 0;
+        if (resume && 0.0f > end) cur = -1;  // the first step's `depth > end` (depth 0) ended the ray: a miss
+      }
+    }
+    if (cur >= 0) {
+      const SceneMin c = sdScene<BULB, COUNT, false>(sb, madd(L, depth, o), cnt);
+      const bool hit = fabs_(c.d) < kSurfaceDist;
+      bool fin = hit || depth > end;
+      if (!fin) {
+        depth = depth + fabs_(c.d);
+        step++;
+        fin = step >= maxSteps;  // the loop of march() runs out: a miss
+      }
+      if (fin) {
+        if (hit) atomicOr(&hitw[own >> 1], 1u << (((own & 1) << 4) + cur));
+        cur = -1;
+      }
+    }
+    if (__ballot(cur >= 0) == 0ull && next >= n) break;
+  }
+  __builtin_amdgcn_wave_barrier();
+  return (hitw[lane >> 1] >> ((lane & 1) << 4)) & 0xffffu;
+}
+
+// render() from its primary march on, with the shadow pool: the bulb class, hard shadows from directional lights only.  Every
+// lane of the wave that renders a pixel calls it, hit or not — the pool needs them all.  Three phases, the pixels of render()
+// with getPhong's queue: (a) the hit lanes compute the surface (normal, bump, AO, the lights to march) and the shared first
+// step; (b) the whole wave marches the shadow rays; (c) the hit lanes sum the lights.  The shared first step: a pixel's
+// rays all start at `so` with depth 0, so their first evaluation sdScene(madd(L, 0, so)) = sdScene(so) is one value — unless
+// a component of `so` is −0, whose sign madd then takes from L (such a pixel, and any frame with a non-finite light direction,
+// marches from the start).
+template <int BULB, int COUNT>
+RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, const MarchRes &res, Hit &info,
+                              float maxT, V3 bg, Counters &cnt) {
+  const bool surf = res.obj != -1;
+  const int nl = sb->numLights;
+  V3 p = v3(0.0f, 0.0f, 0.0f), N = p, so = p;
+  float ao = 1.0f, dStart = -1.0f;
+  uint32_t pend = 0u, hits = 0u;
+  if (surf) {
+    if (COUNT) cnt.shades++;
+    p = madd(rd, res.d, ro);
+    N = getNormal<BULB, COUNT>(sb, p, cnt);
+    if (sb->s.features & RM_FEAT_PERLIN_BUMP) N = bumpNormal(N, p);
+    if (sb->s.enableAmbientOcclusion) ao = calcAO<BULB, COUNT>(sb, p, N, cnt);
+    so = shadowOrigin(p, N);
+    bool shared = f2u(so.x) != 0x80000000u && f2u(so.y) != 0x80000000u && f2u(so.z) != 0x80000000u;
+    uint32_t need = 0u;
+    for (int i = 0; i < nl; i++) {
+      const RmLight &li = sb->lights[i];
+      const V3 L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
+      shared = shared && (fabs_(L.x) + fabs_(L.y) + fabs_(L.z) <= 2.0f);  // false for a NaN / inf direction
+      if (!(dot(N, L) <= 0.005f)) need |= 1u << i;  // a light that N·L drops is not marched (getPhong)
+    }
+    const int maxSteps = sb->s.maxSteps;
+    if (need != 0u && maxSteps > 0) {  // maxSteps <= 0: march() evaluates nothing and reports a miss
+      if (!shared) {
+        pend = need;
+      } else {
+        const float d0 = fabs_(sdScene<BULB, COUNT, false>(sb, so, cnt).d);
+        if (d0 < kSurfaceDist) hits = need;                 // every ray hits on its first evaluation
+        else if (maxSteps > 1) { pend = need; dStart = d0; }  // else every ray's loop runs out after it: a miss
+      }
+    }
+  }
+  const uint32_t hitMask = hits | shadowPool<BULB, COUNT>(sb, so, pend, dStart, maxT, cnt);
+  RenderOut out;
+  if (!surf) {
+    out.col = bg;
+    out.isEnv = 1;
+    out.d = maxT;
+    return out;
+  }
+  out.isEnv = 0;
+  out.d = res.d;
+  const RmObject &o = objs[0];
+  Material mat;
+  mat.amb = v3(o.cAmbient[0], o.cAmbient[1], o.cAmbient[2]);
+  mat.dif = getDiffuse<false>(sb, o, p);
+  mat.spec = v3(o.cSpecular[0], o.cSpecular[1], o.cSpecular[2]);
+  mat.shininess = o.shininess;
+  const float ka = sb->g.ka, ks = sb->g.ks;
+  const V3 total = v3((mat.amb.x * ka) * ao, (mat.amb.y * ka) * ao, (mat.amb.z * ka) * ao);
+  // lightSetup reads the point for point and spot lights only: not keeping p live across the pool frees three registers
+  const V3 ph = hardLightSum(sb, mat, N, v3(0.0f, 0.0f, 0.0f), normalize(neg(rd)), maxT, ks, hitMask, total);
+  const V3 c = bulbTrapColor(res.trap.y, res.trap.z, res.trap.w);
+  out.col = v3(c.x * (ph.x * 8.0f), c.y * (ph.y * 8.0f), c.z * (ph.z * 8.0f));
+  info.p = p; info.n = N; info.rd = rd; info.obj = res.obj;
+  return out;
+}
+
 // frag:2318-2375.  `objs` is the per-lane-indexable copy of the object table (LDS).
-template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0>
+// POOL (bulb kernels without procedural layers or textures, not counting the reference's work; the primary call of shadePixel,
+// which every lane of the wave that renders a pixel reaches): renderPooled takes the frames whose shadow rays the pool may
+// schedule.  The secondary rays' render() calls are divergent and keep getPhong's queue.
+template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false>
 RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, Hit &info, float side, float maxT,
                         V3 bg, Counters &cnt, LightSplit split = LightSplit{-1, nullptr, 0}) {
   RenderOut out;
@@ -1130,6 +1301,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
       q[0] = __int_as_float(res.obj); q[1] = res.d; q[2] = res.trap.x; q[3] = res.trap.y; q[4] = res.trap.z; q[5] = res.trap.w;
     }
   }
+  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
   if (res.obj == -1) {
     out.col = (TEX && sb->s.enableSkyBox) ? sampleCube(sb->skybox, rd) : bg;  // frag:2325-2327
     out.isEnv = 1;
@@ -1261,7 +1433,8 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
   const float iTime = sb->g.iTime;
 
   Hit info;
-  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
+  constexpr bool POOL = BULB && !ENV && !TEX && COUNT != 1 && SPLIT == 0;  // the shadow pool (renderPooled)
+  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
   EnvOut e;
   e.terrainHit = false; e.cloudHit = false; e.seaHit = false;
   if (env) e = envLayers(feat, sb->noise, iTime, W, ro, rd, ri.d, bg, cnt);  // frag:2444-2456
