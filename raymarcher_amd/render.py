@@ -175,6 +175,16 @@ class Renderer:
         torch.cuda.set_device(self.device)
         check(lib().rm_set_device(device))
 
+    def _out(self, a, shape, dtype, name="out"):
+        """A fresh tensor of `shape` and `dtype` on this device, or the caller's `a` once it is checked to be exactly that (the
+        kernels write every element of it and nothing past it)."""
+        t = self.torch
+        if a is None:
+            return t.empty(shape, dtype=dtype, device=self.device)
+        if tuple(a.shape) != tuple(shape) or a.dtype != dtype or not a.is_contiguous() or a.device != self.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
+        return a
+
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -223,32 +233,32 @@ class Renderer:
                 setattr(res, name, dev.data_ptr())
         return res, keep
 
-    def render(self, tables, settings, W, H, row_begin=0, row_end=None, bright=False, out=None):
-        """rm_render: rows [row_begin,row_end) → float32 tensor (rows, W, 4), row 0 = bottom."""
+    def render(self, tables, settings, W, H, row_begin=0, row_end=None, bright=False, out=None, out_bright=None):
+        """rm_render: rows [row_begin,row_end) → float32 tensor (rows, W, 4), row 0 = bottom.  out / out_bright: the caller's
+        buffers for the frame and (implying bright=True) its BrightColor."""
         t = self.torch
         row_end = H if row_end is None else row_end
-        n = row_end - row_begin
-        if out is None:
-            out = t.empty((max(n, 0), W, 4), dtype=t.float32, device=self.device)
-        br = t.empty_like(out) if bright else None
+        shape = (max(row_end - row_begin, 0), W, 4)
+        out = self._out(out, shape, t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
         res, _keep = self._resources(tables)
         check(lib().rm_render_res(*tables.args(settings), C.byref(res), W, H, row_begin, row_end, C.c_void_p(out.data_ptr()),
                                   C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
-    def render_batch(self, tables, settings, W, H, cameras, globals_=None, bright=False, out=None):
+    def render_batch(self, tables, settings, W, H, cameras, globals_=None, bright=False, out=None, out_bright=None):
         """rm_render_batch: N whole frames of the scene in `tables`, frame i seen through cameras[i] (RmCamera, as build_camera
         returns them) → float32 tensor (N, H, W, 4), row 0 = bottom.  globals_: None (tables.globals_ for every frame), one
-        RmGlobals for every frame, or a sequence of N of them."""
+        RmGlobals for every frame, or a sequence of N of them.  out / out_bright: the caller's buffers (out_bright implies
+        bright=True)."""
         cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
         n = len(cameras)
         shape = (n, H, W, 4)
-        if out is not None and (tuple(out.shape) != shape or out.dtype != self.torch.float32 or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
         t = self.torch
-        if out is None:
-            out = t.empty(shape, dtype=t.float32, device=self.device)
-        br = t.empty_like(out) if bright else None
+        out = self._out(out, shape, t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
         res, _keep = self._resources(tables)
         check(lib().rm_render_batch(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
                                     C.byref(settings), C.byref(res), W, H, C.c_void_p(out.data_ptr()),
@@ -285,16 +295,15 @@ class Renderer:
         """rm_render_tiles: this shard's interleaved row tiles, packed → (rm_shard_rows, W, 4)."""
         t = self.torch
         n = lib().rm_shard_rows(H, tile_rows, shard, num_shards)
-        if out is None:
-            out = t.empty((max(n, 0), W, 4), dtype=t.float32, device=self.device)
+        out = self._out(out, (max(n, 0), W, 4), t.float32)
         res, _keep = self._resources(tables)
         check(lib().rm_render_tiles_res(*tables.args(settings), C.byref(res), W, H, tile_rows, shard, num_shards,
                                         C.c_void_p(out.data_ptr()), None, self._stream()))
         return out
 
-    def deinterleave(self, gathered, W, H, tile_rows, num_shards, shard_stride_rows=0):
+    def deinterleave(self, gathered, W, H, tile_rows, num_shards, shard_stride_rows=0, out=None):
         t = self.torch
-        frame = t.empty((H, W, 4), dtype=t.float32, device=self.device)
+        frame = self._out(out, (H, W, 4), t.float32)
         check(lib().rm_deinterleave(C.c_void_p(gathered.data_ptr()), C.c_void_p(frame.data_ptr()), W, H, tile_rows,
                                     num_shards, shard_stride_rows, self._stream()))
         return frame
@@ -303,33 +312,32 @@ class Renderer:
         """rm_tiles_to_rgba8: a shard's packed float4 rows → RGBA8, same rows (clamp → ×255 → round, no flip)."""
         t = self.torch
         rows, W = tiles.shape[0], tiles.shape[1]
-        if out is None:
-            out = t.empty((rows, W, 4), dtype=t.uint8, device=self.device)
+        out = self._out(out, (rows, W, 4), t.uint8)
         check(lib().rm_tiles_to_rgba8(C.c_void_p(tiles.data_ptr()), C.c_void_p(out.data_ptr()), W, rows, self._stream()))
         return out
 
-    def deinterleave_rgba8(self, gathered8, W, H, tile_rows, num_shards, shard_stride_rows=0, flip=True):
+    def deinterleave_rgba8(self, gathered8, W, H, tile_rows, num_shards, shard_stride_rows=0, flip=True, out=None):
         """rm_deinterleave_rgba8: gathered RGBA8 slots → the frame's image (flip: row 0 = top, as to_rgba8 writes it)."""
         t = self.torch
-        img = t.empty((H, W, 4), dtype=t.uint8, device=self.device)
+        img = self._out(out, (H, W, 4), t.uint8)
         check(lib().rm_deinterleave_rgba8(C.c_void_p(gathered8.data_ptr()), C.c_void_p(img.data_ptr()), W, H, tile_rows, num_shards,
                                           shard_stride_rows, 1 if flip else 0, self._stream()))
         return img
 
-    def post_process(self, frame, bright, post):
+    def post_process(self, frame, bright, post, out=None):
         """rm_post_process: bloom / HDR / gamma / FXAA (applyLightEffects + applyFXAA, realtimerender.cpp:78-165)."""
         t = self.torch
         H, W = frame.shape[0], frame.shape[1]
-        out = t.empty((H, W, 4), dtype=t.float32, device=self.device)
+        out = self._out(out, (H, W, 4), t.float32)
         check(lib().rm_post_process(C.c_void_p(frame.data_ptr()), C.c_void_p(bright.data_ptr()) if bright is not None else None,
                                     C.c_void_p(out.data_ptr()), W, H, C.byref(post), self._stream()))
         return out
 
-    def to_rgba8(self, frame):
+    def to_rgba8(self, frame, out=None):
         """Clamp/quantise + vertical flip (saveViewportImage, realtime.cpp:284-350) → uint8 (H, W, 4)."""
         t = self.torch
         H, W = frame.shape[0], frame.shape[1]
-        out = t.empty((H, W, 4), dtype=t.uint8, device=self.device)
+        out = self._out(out, (H, W, 4), t.uint8)
         check(lib().rm_frame_to_rgba8(C.c_void_p(frame.data_ptr()), C.c_void_p(out.data_ptr()), W, H, self._stream()))
         return out
 
@@ -337,18 +345,18 @@ class Renderer:
         img = self.to_rgba8(frame).cpu().contiguous()
         check(lib().rm_write_png(str(path).encode(), C.c_void_p(img.data_ptr()), img.shape[1], img.shape[0]))
 
-    def probe_math(self, fn, x, y=None, z=None):
+    def probe_math(self, fn, x, y=None, z=None, out=None):
         t = self.torch
-        out = t.empty_like(x)
+        out = t.empty_like(x) if out is None else self._out(out, x.shape, x.dtype)
         check(lib().rm_probe_math(fn, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
                                   C.c_void_p(z.data_ptr()) if z is not None else None, C.c_void_p(out.data_ptr()),
                                   x.numel(), self._stream()))
         return out
 
-    def probe_sdscene(self, tables, settings, pts):
+    def probe_sdscene(self, tables, settings, pts, out=None):
         t = self.torch
         n = pts.shape[0]
-        out = t.empty((n, 4), dtype=t.float32, device=self.device)
+        out = self._out(out, (n, 4), t.float32)
         check(lib().rm_probe_sdscene(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings),
                                      C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()), n, self._stream()))
         return out

@@ -340,3 +340,104 @@ def random_tablewalk_objects(rng, max_objects=30, materials=True):
         objs.append(make_object(ty, model=M, scale_factor=float(sf), **material()))
         models.append((M, sc))
     return objs
+
+
+# ------------------------------------------------------------------ guarded, poisoned output buffers (write coverage)
+FLOAT_POISON = 0x7FA5A5A5      # a signalling NaN with a fixed payload: GPU arithmetic only ever produces quiet NaNs
+U8_POISONS = (0xA5, 0x5A)      # a byte poison can be a real value: uint8 outputs are produced twice, once under each
+
+
+def _i32(v):
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+class Guarded:
+    """One device allocation: a guard band, the payload, a guard band, all filled with `poison` (see guarded)."""
+
+    def __init__(self, shape, dtype, poison, device):
+        import torch
+        self.shape, self.dtype, self.poison = tuple(int(d) for d in shape), dtype, poison
+        item = torch.empty((), dtype=dtype).element_size()
+        row = item * (self.shape[-2] * self.shape[-1] if len(self.shape) >= 2 else 1)
+        self.nbytes = item * int(np.prod(self.shape, dtype=np.int64))
+        self.guard = max(4096, -(-row // 256) * 256)  # >= one output row, >= 4 KB, a multiple of 256 bytes
+        tail = self.guard + (-self.nbytes) % 256  # the back guard starts right at the payload's end
+        self.buf = torch.empty(self.guard + self.nbytes + tail, dtype=torch.uint8, device=device)
+        if item == 1:
+            self.buf.fill_(poison)
+        else:
+            self.buf.view(torch.int32).fill_(_i32(poison))  # through an integer view: a float fill would lose the NaN's payload
+        self.payload = self.buf[self.guard:self.guard + self.nbytes].view(dtype).view(self.shape)
+
+    def _unwritten(self, region):
+        """Mask of the words (bytes for uint8) of a region of buf that still hold the poison."""
+        import torch
+        return region == self.poison if self.dtype.itemsize == 1 else region.view(torch.int32) == _i32(self.poison)
+
+    def check(self):
+        """Both guards still hold the poison bit for bit, and (float payloads) no payload word still holds it; a uint8 payload can
+        hold its poison legitimately: see guarded_u8.  Synchronises through the comparisons."""
+        end = self.guard + self.nbytes
+        for name, lo, hi in (("front", 0, self.guard), ("back", end, self.buf.numel())):
+            kept = self._unwritten(self.buf[lo:hi])
+            if not bool(kept.all()):
+                w = int((~kept).nonzero()[0, 0]) * (hi - lo) // kept.numel()  # byte offset in the guard
+                off = f"{self.guard - w} bytes before the payload" if name == "front" else f"{w} bytes past its end"
+                raise AssertionError(f"{name} guard written: {int((~kept).sum())} of {kept.numel()} guard words changed, "
+                                     f"the first {off}")
+        if self.dtype.itemsize == 1:
+            return
+        left = self._unwritten(self.buf[self.guard:end])
+        if bool(left.any()):
+            i = int(left.nonzero()[0, 0]) * 4 // self.dtype.itemsize
+            where = tuple(int(v) for v in np.unravel_index(i, self.shape))
+            raise AssertionError(f"{int(left.sum())} of {left.numel()} payload words never written; the first at {where} "
+                                 f"(row, column, channel) of {self.shape}")
+
+
+def guarded(shape, dtype=None, poison=FLOAT_POISON, device="cuda"):
+    """A freshly poisoned output between two guard bands → (payload view, check).  check() asserts that both guards still hold
+    the poison and that no payload word does (the names of the first offending element or guard byte are in the message)."""
+    import torch
+    g = Guarded(shape, torch.float32 if dtype is None else dtype, poison, device)
+    return g.payload, g.check
+
+
+def guarded_u8(shape, produce, device="cuda"):
+    """Produce a uint8 output twice, into buffers poisoned with 0xA5 and with 0x5A: `produce(out)` writes `out`.  Both results
+    equal and both guards intact → the result (a byte the launch never wrote would differ between the two)."""
+    import torch
+    got = []
+    for p in U8_POISONS:
+        out, check = guarded(shape, torch.uint8, p, device)
+        produce(out)
+        check()
+        got.append(out)
+    bad = got[0] != got[1]
+    if bool(bad.any()):
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{int(bad.sum())} of {bad.numel()} bytes differ under the two poisons (never written); the first at {i}")
+    return got[0]
+
+
+def render_guarded(renderer, tables, settings, W, H, row_begin=0, row_end=None, bright=False):
+    """Renderer.render into freshly poisoned, guarded buffers (and the bright one too with bright=True), checked before it
+    returns: a pixel the launch never wrote, or a write past either end of the rows, fails here."""
+    row_end = H if row_end is None else row_end
+    out, c1 = guarded((row_end - row_begin, W, 4), device=renderer.device)
+    br, c2 = guarded((row_end - row_begin, W, 4), device=renderer.device) if bright else (None, None)
+    renderer.render(tables, settings, W, H, row_begin, row_end, bright=bright, out=out, out_bright=br)
+    c1()
+    if bright:
+        c2()
+        return out, br
+    return out
+
+
+def render_tiles_guarded(renderer, tables, settings, W, H, tile_rows, shard, num_shards):
+    """Renderer.render_tiles into a freshly poisoned, guarded buffer of exactly the shard's rows, checked before it returns."""
+    from raymarcher_amd import lib
+    out, check = guarded((lib().rm_shard_rows(H, tile_rows, shard, num_shards), W, 4), device=renderer.device)
+    renderer.render_tiles(tables, settings, W, H, tile_rows, shard, num_shards, out=out)
+    check()
+    return out

@@ -178,7 +178,7 @@ def test_each_frame_equals_rm_render_including_bright(renderer):
     for f in range(4):
         tf = tables_of((cams[f], t.objects, t.num_objects, t.lights, t.num_lights, globs[f]))
         for _ in range(3):  # a new picture, then repeats of it (cost-ordered tiles)
-            o1, b1 = renderer.render(tf, s, W, H, bright=True)
+            o1, b1 = h.render_guarded(renderer, tf, s, W, H, bright=True)
             assert P._ieq(o1, out[f]) and P._ieq(b1, br[f]), f"frame {f}"
     # numGlobals = 1 equals N identical explicit entries
     one = renderer.render_batch(t, s, W, H, cams, globals_=globs[0]).clone()

@@ -1044,7 +1044,7 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
     def frames(seq, **kw):
         outs = []
         for scene, s in seq:
-            outs.append(renderer.render(tables_of(scene), s, W, H, **kw).clone())
+            outs.append(h.render_guarded(renderer, tables_of(scene), s, W, H, **kw).clone())
         return outs
 
     prim = all_primitives_scene(W, H)
@@ -1073,22 +1073,22 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
         scene = (h.make_camera((0, 1.2, 6), (0, -0.2, -1), (0, 1, 0), 45.0, W, H2),) + prim[1:]
         t = tables_of(scene)
         L.rm_set_tile_order(0)
-        full = renderer.render(t, s0, W, H2).clone()
+        full = h.render_guarded(renderer, t, s0, W, H2).clone()
         L.rm_set_tile_order(1)
         for _ in range(2):
-            assert _ieq(renderer.render(t, s0, W, H2), full)
-            assert _ieq(renderer.render(t, s0, W, H2, row_begin=200, row_end=904), full[200:904])
-            mine = renderer.render_tiles(t, s0, W, H2, 8, 1, 2)
+            assert _ieq(h.render_guarded(renderer, t, s0, W, H2), full)
+            assert _ieq(h.render_guarded(renderer, t, s0, W, H2, row_begin=200, row_end=904), full[200:904])
+            mine = h.render_tiles_guarded(renderer, t, s0, W, H2, 8, 1, 2)
             rows = [L.rm_shard_row_to_frame(H2, 8, 1, 2, i) for i in range(mine.shape[0])]
             assert _ieq(mine, full[torch.tensor(rows, device=full.device)])
         # a picture that repeats settles (the fourth cost-ordered frame on reuses the third's order: no ordering launches, no cost
         # atomics); the picture after a settled one is ordered by geometry + the costs the last sort kept
         settle = [(bulb, sb)] * 7 + [(prim, s0)] + [(bulb, sb)] * 6 + [(moved, s0)] * 14 + [(prim, s0), (moved, s0)]
         L.rm_set_tile_order(0)
-        want = {id(sc): renderer.render(tables_of(sc), st, W, H).clone() for sc, st in ((bulb, sb), (prim, s0), (moved, s0))}
+        want = {id(sc): h.render_guarded(renderer, tables_of(sc), st, W, H).clone() for sc, st in ((bulb, sb), (prim, s0), (moved, s0))}
         L.rm_set_tile_order(1)
         for k, (sc, st) in enumerate(settle):
-            assert _ieq(renderer.render(tables_of(sc), st, W, H), want[id(sc)]), f"frame {k} of the settling sequence"
+            assert _ieq(h.render_guarded(renderer, tables_of(sc), st, W, H), want[id(sc)]), f"frame {k} of the settling sequence"
     finally:
         L.rm_set_tile_order(-1)
 
@@ -1117,18 +1117,18 @@ def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, 
     try:
         assert L.rm_debug_set_tile_shape(shape) == 0
         assert L.rm_debug_set_light_split(32) == 0  # the heaviest 1/32 of the tiles (default 1/256)
-        first = renderer.render(t, s, W, H).clone()
+        first = h.render_guarded(renderer, t, s, W, H).clone()
         assert_bit_equal(first.cpu().numpy(), h.oracle_render(scene, s, W, H), "first frame vs oracle")
         assert L.rm_debug_last_split() == 0
         split = 0
         for k in range(8):
-            assert _ieq(renderer.render(t, s, W, H), first), f"repeat {k + 1} differs"
+            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"repeat {k + 1} differs"
             split = max(split, L.rm_debug_last_split())
         tiles = (-(-W // 8)) * (-(-H // 8)) if shape == 3 else (-(-W // 4)) * (-(-H // 16))
         assert split == tiles // 32, "the settled picture was not split"
         # a row range is another picture: it settles and splits on its own
         for k in range(7):
-            assert _ieq(renderer.render(t, s, W, H, row_begin=40, row_end=364), first[40:364]), f"row range, frame {k}"
+            assert _ieq(h.render_guarded(renderer, t, s, W, H, row_begin=40, row_end=364), first[40:364]), f"row range, frame {k}"
         assert L.rm_debug_last_split() > 0
         # a frame whose pixels can spawn secondary rays is not eligible
         prim2 = all_primitives_scene(W, H)
@@ -1136,23 +1136,23 @@ def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, 
             prim2[1][3].cReflective[c] = 0.4
         t2 = tables_of((prim2[0], prim2[1], prim2[2], lights, 4, prim2[5]))
         s2 = abi.default_settings(maxSteps=96, enableSoftShadow=soft, enableAmbientOcclusion=ao, enableReflection=1)
-        ref2 = renderer.render(t2, s2, W, H).clone()
+        ref2 = h.render_guarded(renderer, t2, s2, W, H).clone()
         for k in range(6):
-            assert _ieq(renderer.render(t2, s2, W, H), ref2)
+            assert _ieq(h.render_guarded(renderer, t2, s2, W, H), ref2)
         assert L.rm_debug_last_split() == 0
         # every tile split — 200 frames of it: the tiles' workgroups hand their results over through memory inside one launch
         # (release / acquire around a per-tile arrival counter), and whichever of them arrives last finishes the tile
         assert L.rm_debug_set_light_split(1) == 0
         for k in range(200):
-            assert _ieq(renderer.render(t, s, W, H), first), f"all tiles split, frame {k}"
+            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"all tiles split, frame {k}"
         assert L.rm_debug_last_split() == tiles
         assert L.rm_debug_set_light_split(0) == 0
-        assert _ieq(renderer.render(t, s, W, H), first) and L.rm_debug_last_split() == 0
+        assert _ieq(h.render_guarded(renderer, t, s, W, H), first) and L.rm_debug_last_split() == 0
         # the default: the launcher measures (two plain frames, two split, then the better) — whatever it decides, the same frame
         assert L.rm_debug_set_light_split(-1) == 0
         seen = set()
         for k in range(20):
-            assert _ieq(renderer.render(t, s, W, H), first), f"measured mode, frame {k}"
+            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"measured mode, frame {k}"
             seen.add(L.rm_debug_last_split())
         assert seen <= {0, tiles // 256} and tiles // 256 in seen  # its two split frames ran
     finally:
@@ -1173,22 +1173,22 @@ def test_tile_shape_tuner_never_changes_a_pixel(renderer):
     s = abi.default_settings(maxSteps=96, enableSoftShadow=1)
     try:
         assert L.rm_debug_set_tile_shape(3) == 0
-        ref = renderer.render(t, s, W, H).clone()
+        ref = h.render_guarded(renderer, t, s, W, H).clone()
         assert_bit_equal(ref.cpu().numpy(), h.oracle_render(scene, s, W, H), "8×8 tiles vs oracle")
         assert L.rm_debug_set_tile_shape(2) == 0
         for _ in range(2):
-            assert _ieq(renderer.render(t, s, W, H), ref)
-        assert _ieq(renderer.render(t, s, W, H, row_begin=33, row_end=377), ref[33:377])
-        mine = renderer.render_tiles(t, s, W, H, 8, 1, 3)
+            assert _ieq(h.render_guarded(renderer, t, s, W, H), ref)
+        assert _ieq(h.render_guarded(renderer, t, s, W, H, row_begin=33, row_end=377), ref[33:377])
+        mine = h.render_tiles_guarded(renderer, t, s, W, H, 8, 1, 3)
         rows = [L.rm_shard_row_to_frame(H, 8, 1, 3, i) for i in range(mine.shape[0])]
         assert _ieq(mine, ref[torch.tensor(rows, device=ref.device)])
         assert L.rm_debug_set_tile_shape(0) == 0
         for k in range(14):  # the tuner's eight frames, its decision, and frames after it
-            assert _ieq(renderer.render(t, s, W, H), ref), f"frame {k} of the tuned sequence differs"
+            assert _ieq(h.render_guarded(renderer, t, s, W, H), ref), f"frame {k} of the tuned sequence differs"
         moved = (h.make_camera((0.5, 2.0, 6.5), (-0.1, -0.3, -1), (0, 1, 0), 45.0, W, H),) + scene[1:]
         want = h.oracle_render(moved, s, W, H)
         for k in range(3):  # a new picture restarts the measurement
-            assert_bit_equal(renderer.render(tables_of(moved), s, W, H).cpu().numpy(), want, f"moved camera, frame {k}")
+            assert_bit_equal(h.render_guarded(renderer, tables_of(moved), s, W, H).cpu().numpy(), want, f"moved camera, frame {k}")
         assert L.rm_debug_set_tile_shape(5) == abi.RM_ERR_INVALID_ARGUMENT
     finally:
         L.rm_debug_set_tile_shape(-1)
@@ -1428,7 +1428,7 @@ def test_random_scenes_bit_exact(renderer):
         assert_bit_equal(br.cpu().numpy(), ref_b, f"random scene {i} bright")
         if (W // 8) * (H // 8) >= 2048:
             for rep in range(3):
-                assert _ieq(renderer.render(t, s, W, H), out), f"random scene {i}: repeat {rep + 1} differs"
+                assert _ieq(h.render_guarded(renderer, t, s, W, H), out), f"random scene {i}: repeat {rep + 1} differs"
         kinds |= {scene[1][k].type for k in range(scene[2])}
     assert len(kinds) >= 10
 

@@ -162,10 +162,14 @@ def test_wavefront_row_ranges_tiles_and_streams(renderer):
         streams = [torch.cuda.Stream(device=renderer.device) for _ in range(2)]
         outs = []
         for st in streams * 2:
-            with torch.cuda.stream(st):
-                outs.append(renderer.render(t, s, W, H))
+            with torch.cuda.stream(st):  # poisoned on the stream that renders into it
+                out, check = h.guarded((H, W, 4), device=renderer.device)
+                renderer.render(t, s, W, H, out=out)
+            outs.append((out, check))
         torch.cuda.synchronize()
-        assert all(tg._ieq(o, full) for o in outs)
+        for _, check in outs:
+            check()
+        assert all(tg._ieq(o, full) for o, _ in outs)
     finally:
         lib().rm_set_kernel_path(0)
 
