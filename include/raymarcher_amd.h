@@ -448,6 +448,14 @@ int rm_debug_check_math(unsigned long long *mismatches5);
  * d_out: H·W·4 bytes, row 0 = top.
  */
 int rm_frame_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, void *stream);
+/*
+ * rm_frames_to_rgba8 — rm_frame_to_rgba8 of numFrames frames in one launch.  Frame f is read from d_rgba + f·H·W·4 floats (rows
+ * bottom-up, as rm_render_batch and rm_post_process_batch write it) and written to d_out + f·H·W·4 bytes, flipped within itself
+ * (row 0 = the frame's top); every frame is bit-identical to rm_frame_to_rgba8 of that frame.  numFrames == 0: RM_OK, nothing
+ * written.  RM_ERR_INVALID_ARGUMENT: numFrames < 0, null d_rgba / d_out, W or H <= 0, a pointer that is not device memory;
+ * RM_ERR_CAPACITY: numFrames > RM_MAX_BATCH_FRAMES.
+ */
+int rm_frames_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, int numFrames, void *stream);
 
 /* ---- post passes (src/realtimerender.cpp:78-165; resources/blur.frag, hdr.frag, fxaa.frag) ------------------ */
 /* Settings surface — src/settings.h:37-41. */
@@ -462,10 +470,27 @@ typedef struct RmPostSettings {
  * bright / ping-pong targets are RGBA16F (values are rounded to binary16 between passes), the FXAA source is
  * RGBA8 sampled with GL_LINEAR / GL_REPEAT.  d_frag, d_bright (may be NULL without bloom) and d_out are H·W
  * float4, row 0 = bottom; d_out receives the colour the 8-bit default framebuffer would quantise
- * (rm_frame_to_rgba8 does that).  Uses a grow-only per-device workspace of 24 B/pixel.
+ * (rm_frame_to_rgba8 does that).  Uses a grow-only per-stream workspace of 20 B/pixel.
  */
 int rm_post_process(const float *d_frag, const float *d_bright, float *d_out, int W, int H, const RmPostSettings *ps,
                     void *stream);
+/*
+ * rm_post_process_batch — rm_post_process of numFrames frames (an exported sequence: rm_render_batch's output feeds straight
+ * in).  Frame f sits at + f·H·W·4 floats in d_frag, d_bright and d_out, rows bottom-up.  ps holds numPost entries: numPost == 1
+ * applies ps[0] to every frame, numPost == numFrames gives frame f ps[f].  The four enable flags must be the same in every
+ * entry; exposure may differ per frame (an exposure fade).  Every output frame is bit-identical to rm_post_process of that frame
+ * with its settings.  d_out == d_frag (the whole batch in place) is allowed, any other overlap is undefined; d_bright may be
+ * NULL without bloom.  Asynchronous on `stream`; ps is copied before return.
+ * The frames go through the passes in chunks of k = min(64, numFrames, max(1, cap / (20·W·H))) frames, one launch per pass
+ * and chunk, with the chunk's images in the stream's post workspace (20 B/pixel/frame); cap is the rm_set_workspace_limit
+ * value when one is set, 256 MiB otherwise.  A single frame that exceeds a set limit fails with RM_ERR_DEVICE as in
+ * rm_post_process.
+ * numFrames == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT: numFrames < 0, numPost neither 1 nor numFrames, the enable
+ * flags differ between entries of ps, null d_frag / d_out / ps, bloom without d_bright, W or H <= 0, a pointer that is not
+ * device memory; RM_ERR_CAPACITY: numFrames > RM_MAX_BATCH_FRAMES.  All but the last are checked before any HIP call.
+ */
+int rm_post_process_batch(const float *d_frag, const float *d_bright, float *d_out, int W, int H, int numFrames,
+                          const RmPostSettings *ps, int numPost, void *stream);
 
 /* ---- math spec probes (tests only: evaluate the device implementation of one rm_math function
  *      element-wise so it can be compared bit-for-bit with the oracle) ---------------------------- */

@@ -32,6 +32,8 @@ int require_device_pointers(std::initializer_list<std::pair<const char *, const 
 enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 #endif
+// The largest single workspace buffer stream_workspace may allocate, 0 = no limit (rm_set_workspace_limit).
+unsigned long long workspace_limit();
 
 // Baseline JPEG → RGBA8, top row first (rm_jpeg.cpp).
 int jpeg_decode(const std::vector<uint8_t> &file, std::vector<uint8_t> &rgba, int &W, int &H);

@@ -365,13 +365,15 @@ __global__ void probe_sdscene_kernel(const SceneBlock *__restrict__ sb, const fl
   out[4 * i + 3] = m.trap.z;
 }
 
-// clamp → ×255 → round-half-up, vertical flip (src/realtime.cpp:337-338 + GL's RGBA8 conversion).
+// clamp → ×255 → round-half-up, vertical flip (src/realtime.cpp:337-338 + GL's RGBA8 conversion).  blockIdx.z = frame: each
+// frame is flipped within itself.
 __global__ void to_rgba8_kernel(const float4 *__restrict__ in, uchar4 *__restrict__ out, int W, int H) {
   int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W) return;
-  float4 c = in[(size_t)y * W + x];
+  const size_t base = (size_t)blockIdx.z * W * H;
+  float4 c = in[base + (size_t)y * W + x];
   auto q = [](float v) { v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); return (unsigned char)(v * 255.0f + 0.5f); };
-  out[(size_t)(H - 1 - y) * W + x] = make_uchar4(q(c.x), q(c.y), q(c.z), q(c.w));
+  out[base + (size_t)(H - 1 - y) * W + x] = make_uchar4(q(c.x), q(c.y), q(c.z), q(c.w));
 }
 
 // packed tiles → RGBA8, rows as they are (the multi-GPU shard's share of to_rgba8_kernel's conversion)
@@ -1857,6 +1859,20 @@ int rm_frame_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, void *s
   if (!d_rgba || !d_out || W <= 0 || H <= 0) { set_error("bad frame arguments"); return RM_ERR_INVALID_ARGUMENT; }
   if (int st = require_device_pointers({{"d_rgba", d_rgba}, {"d_out", d_out}})) return st;
   dim3 grid((W + 255) / 256, H), block(256);
+  hipLaunchKernelGGL(to_rgba8_kernel, grid, block, 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<uchar4 *>(d_out), W, H);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+
+int rm_frames_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, int numFrames, void *stream) {
+  // every argument check ahead of the first HIP call (as rm_render_batch's)
+  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (numFrames == 0) return RM_OK;
+  if (!d_rgba || !d_out || W <= 0 || H <= 0) { set_error("bad frame arguments"); return RM_ERR_INVALID_ARGUMENT; }
+  if (int st = require_device_pointers({{"d_rgba", d_rgba}, {"d_out", d_out}})) return st;
+  dim3 grid((W + 255) / 256, H, numFrames), block(256);
   hipLaunchKernelGGL(to_rgba8_kernel, grid, block, 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<uchar4 *>(d_out), W, H);
   HIP_OK(hipGetLastError());

@@ -7,6 +7,10 @@
 // FXAA neighbourhood hit L1/L2), nowhere near the raymarch's cost.  Intermediate images use the reference's storage
 // formats — binary16 for the HDR / bright / ping-pong targets, 8-bit for the FXAA source — so values are rounded
 // exactly where the reference's framebuffers round them, and the result is bit-reproducible against the oracle.
+//
+// Every pass takes a frame dimension (blockIdx.z, or blockIdx.y for the 1-D passes): a launch covers the frames of a chunk,
+// each at its own base offset, and every clamp or wrap stays inside its frame.  rm_post_process is the one-frame case of the
+// launches rm_post_process_batch makes.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -28,6 +32,10 @@ __device__ __forceinline__ unsigned char to8(float v) {
   return (unsigned char)(int)fma(v, 255.0f, 0.5f);
 }
 __device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// Frames per post launch, and their exposures, passed by value (a 256-byte kernel argument: no upload, no ring).
+constexpr int kPostChunk = 64;
+struct Exposures { float e[kPostChunk]; };
 
 // blur.frag:9-31, CLAMP_TO_EDGE, taps on texel centres
 __global__ void blur_kernel(const half4 *__restrict__ src, half4 *__restrict__ dst, int W, int H, int horizontal) {
@@ -68,9 +76,11 @@ __global__ __launch_bounds__(256) void blur_pair_kernel(const void *__restrict__
   __shared__ half4 s_h[SH][kBlurTW];
   const float w[5] = {0.2270270270f, 0.1945945946f, 0.1216216216f, 0.0540540541f, 0.0162162162f};
   const int x0 = blockIdx.x * kBlurTW, y0 = blockIdx.y * kBlurTH;
+  const size_t base = (size_t)blockIdx.z * W * H;  // this block's frame
+  dst += base;
   {  // every load of the thread is issued before the first LDS write waits for one (a load-wait-write loop is latency-bound)
     using Texel = typename std::conditional<F32SRC, float4, half4>::type;
-    const Texel *src = static_cast<const Texel *>(srcv);
+    const Texel *src = static_cast<const Texel *>(srcv) + base;
     Texel t[kPer];
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
@@ -122,11 +132,13 @@ __global__ __launch_bounds__(256) void blur_pair_kernel(const void *__restrict__
 }
 
 // hdr.frag:13-35 without bloom (with it: light_bloom_kernel).  Writes either the float frame (no FXAA afterwards) or the RGBA8 FXAA
-// source.
+// source.  Grid: (blocks of one frame of n pixels, frames).
 __global__ void light_kernel(const float4 *__restrict__ frag, float4 *__restrict__ outF, uchar4 *__restrict__ out8, int n, int hdr,
-                             float exposure) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+                             Exposures ex) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const size_t i = (size_t)blockIdx.y * n + p;
+  const float exposure = ex.e[blockIdx.y];
   float4 f = frag[i];
   const float c[3] = {q16(f.x), q16(f.y), q16(f.z)};
   float r[3];
@@ -141,15 +153,17 @@ __global__ void light_kernel(const float4 *__restrict__ frag, float4 *__restrict
 // have held — and composites.  Saves the 8 B/pixel written and re-read between the two and a pass whose nine taps per pixel
 // came through L1.
 __global__ __launch_bounds__(256) void light_bloom_kernel(const float4 *__restrict__ frag, const half4 *__restrict__ src, float4 *__restrict__ outF,
-                                                          uchar4 *__restrict__ out8, int W, int H, float exposure) {
+                                                          uchar4 *__restrict__ out8, int W, int H, Exposures ex) {
   __shared__ half4 s_row[256 + 2 * kBlurR];
   const float w[5] = {0.2270270270f, 0.1945945946f, 0.1216216216f, 0.0540540541f, 0.0162162162f};
   const int x0 = blockIdx.x * 256, y = blockIdx.y, x = x0 + threadIdx.x;
-  const half4 *row = src + (size_t)y * W;
+  const size_t base = (size_t)blockIdx.z * W * H;  // this block's frame
+  const float exposure = ex.e[blockIdx.z];
+  const half4 *row = src + base + (size_t)y * W;
   s_row[threadIdx.x] = row[clampi(x0 - kBlurR + (int)threadIdx.x, W)];
   if (threadIdx.x < 2 * kBlurR) s_row[256 + threadIdx.x] = row[clampi(x0 - kBlurR + 256 + (int)threadIdx.x, W)];
   float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (x < W) f = frag[(size_t)y * W + x];
+  if (x < W) f = frag[base + (size_t)y * W + x];
   __syncthreads();
   if (x >= W) return;
   const int lx = threadIdx.x + kBlurR;
@@ -166,14 +180,16 @@ __global__ __launch_bounds__(256) void light_bloom_kernel(const float4 *__restri
   float o[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) o[k] = 1.0f - exp_((-c[k]) * exposure);
-  const size_t i = (size_t)y * W + x;
+  const size_t i = base + (size_t)y * W + x;
   if (out8) out8[i] = make_uchar4(to8(o[0]), to8(o[1]), to8(o[2]), 255);
   else outF[i] = make_float4(o[0], o[1], o[2], 1.0f);
 }
 
+// grid: (blocks of one frame of n pixels, frames)
 __global__ void quant8_kernel(const float4 *__restrict__ frag, uchar4 *__restrict__ out8, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const size_t i = (size_t)blockIdx.y * n + p;
   float4 f = frag[i];
   out8[i] = make_uchar4(to8(f.x), to8(f.y), to8(f.z), 255);
 }
@@ -203,6 +219,11 @@ __global__ void fxaa_kernel(const uchar4 *__restrict__ img, float4 *__restrict__
   __syncthreads();
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= W || y >= H) return;
+  {  // this block's frame: the GL_REPEAT wrap of fetch8 stays inside it
+    const size_t base = (size_t)blockIdx.z * W * H;
+    img += base;
+    out += base;
+  }
   const float quality[12] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.5f, 2.0f, 2.0f, 2.0f, 2.0f, 4.0f, 8.0f};
   const float invW = 1.0f / (float)W, invH = 1.0f / (float)H;
   const float tu = ((float)x + 0.5f) / (float)W, tv = ((float)y + 0.5f) / (float)H;
@@ -291,51 +312,102 @@ using namespace rm;
     }                                                                                              \
   } while (0)
 
+namespace {
+
+// Frames per chunk of a batch: each frame of a chunk needs 20 B/pixel of the stream's post workspace (two binary16 ping-pong
+// images and the 8-bit FXAA source), and the chunk's workspace stays under the workspace limit, or under kPostDefaultCap when no
+// limit is set.  At least one frame: a frame that alone exceeds a set limit fails in stream_workspace.
+constexpr size_t kPostBytesPerPixel = 8 + 8 + 4;
+constexpr unsigned long long kPostDefaultCap = 256ull << 20;
+int post_chunk_frames(int numFrames, size_t n) {
+  const unsigned long long limit = workspace_limit(), cap = limit ? limit : kPostDefaultCap;
+  const unsigned long long fit = cap / (kPostBytesPerPixel * n);
+  int k = numFrames < kPostChunk ? numFrames : kPostChunk;
+  if (fit < (unsigned long long)k) k = fit < 1 ? 1 : (int)fit;
+  return k;
+}
+
+// numFrames (>= 1) frames at frame stride n = W·H pixels through the passes `ps[0]`'s flags select, in chunks of
+// post_chunk_frames; frame f takes its exposure from ps[numPost == 1 ? 0 : f].  The arguments are checked by the caller.
+int post_frames(const float *d_frag, const float *d_bright, float *d_out, int W, int H, int numFrames, const RmPostSettings *ps,
+                int numPost, hipStream_t st) {
+  const size_t n = (size_t)W * H;
+  const int chunk = post_chunk_frames(numFrames, n);
+  // ping-pong + 8-bit staging images of THIS stream: post-processing frames on two streams never shares them
+  void *wsMem = nullptr;
+  if (int rc = stream_workspace(kWsPost, st, (size_t)chunk * n * kPostBytesPerPixel, &wsMem)) return rc;
+  half4 *pa = static_cast<half4 *>(wsMem), *pb = pa + chunk * n;
+  uchar4 *stage8 = reinterpret_cast<uchar4 *>(pb + chunk * n);
+  const RmPostSettings &flags = ps[0];
+  const bool light = flags.enableHDR || flags.enableGammaCorrection || flags.enableBloom;
+  if (!light && !flags.enableFXAA) {
+    if (d_out != d_frag) HIP_OK(hipMemcpyAsync(d_out, d_frag, (size_t)numFrames * n * 16, hipMemcpyDeviceToDevice, st));
+    return RM_OK;
+  }
+  static const int fbw = std::getenv("RM_FXAA_BLOCK_W") ? std::atoi(std::getenv("RM_FXAA_BLOCK_W")) : 16;
+  // 16 × 16 pixels per block (measured at 4K: 256×1 0.269 ms, 64×4 0.263, 32×8 0.257, 16×16 0.252 — the pass is bound by its divergent
+  // edge searches and bilinear fetches, not by cache lines)
+  const int bw = (fbw == 256 || fbw == 64 || fbw == 32 || fbw == 16) ? fbw : 16, bh = 256 / bw;
+  const dim3 blk(256);
+  for (int f0 = 0; f0 < numFrames; f0 += chunk) {
+    const int k = numFrames - f0 < chunk ? numFrames - f0 : chunk;
+    const size_t off = (size_t)f0 * n;  // pixels before the chunk's first frame
+    const float4 *frag = reinterpret_cast<const float4 *>(d_frag) + off;
+    float4 *out = reinterpret_cast<float4 *>(d_out) + off;
+    Exposures ex{};
+    for (int j = 0; j < k; j++) ex.e[j] = ps[numPost == 1 ? 0 : f0 + j].exposure;
+    const dim3 lin((unsigned)((n + 255) / 256), k), grid2((W + 255) / 256, H, k);
+    if (light) {
+      if (flags.enableBloom) {  // applyBloom: 10 passes H,V,H,…; the composite reads the buffer pass 9 wrote
+        half4 *src = pa, *dst = pb;
+        const dim3 tiles((W + kBlurTW - 1) / kBlurTW, (H + kBlurTH - 1) / kBlurTH, k);
+        const float4 *bright = reinterpret_cast<const float4 *>(d_bright) + off;
+        // passes 1-8 as four horizontal+vertical pairs through LDS; the first reads the float BrightColor plane directly
+        hipLaunchKernelGGL(blur_pair_kernel<true>, tiles, blk, 0, st, static_cast<const void *>(bright), src, W, H);
+        for (int i = 1; i < 4; i++) {
+          hipLaunchKernelGGL(blur_pair_kernel<false>, tiles, blk, 0, st, static_cast<const void *>(src), dst, W, H);
+          half4 *t = src; src = dst; dst = t;
+        }
+        // pass 9 (horizontal), the one composited, inside the composite
+        hipLaunchKernelGGL(light_bloom_kernel, grid2, blk, 0, st, frag, src, out, flags.enableFXAA ? stage8 : nullptr, W, H, ex);
+      } else {
+        hipLaunchKernelGGL(light_kernel, lin, blk, 0, st, frag, out, flags.enableFXAA ? stage8 : nullptr, (int)n, flags.enableHDR, ex);
+      }
+    } else {
+      hipLaunchKernelGGL(quant8_kernel, lin, blk, 0, st, frag, stage8, (int)n);
+    }
+    if (flags.enableFXAA)
+      hipLaunchKernelGGL(fxaa_kernel, dim3((W + bw - 1) / bw, (H + bh - 1) / bh, k), dim3(bw, bh), 0, st, stage8, out, W, H);
+    HIP_OK(hipGetLastError());
+  }
+  return RM_OK;
+}
+
+}  // namespace
+
 extern "C" int rm_post_process(const float *d_frag, const float *d_bright, float *d_out, int W, int H,
                                const RmPostSettings *ps, void *stream) {
   if (!d_frag || !d_out || !ps || W <= 0 || H <= 0) { set_error("bad post-process arguments"); return RM_ERR_INVALID_ARGUMENT; }
   if (ps->enableBloom && !d_bright) { set_error("bloom needs the BrightColor plane"); return RM_ERR_INVALID_ARGUMENT; }
   if (int rc = require_device_pointers({{"d_frag", d_frag}, {"d_bright", d_bright}, {"d_out", d_out}})) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t n = (size_t)W * H;
-  // ping-pong + 8-bit staging images of THIS stream: post-processing two frames on two streams never shares them
-  void *wsMem = nullptr;
-  if (int rc = stream_workspace(kWsPost, st, n * (8 + 8 + 4), &wsMem)) return rc;
-  half4 *pa = static_cast<half4 *>(wsMem), *pb = pa + n;
-  uchar4 *stage8 = reinterpret_cast<uchar4 *>(pb + n);
-  const float4 *frag = reinterpret_cast<const float4 *>(d_frag);
-  float4 *out = reinterpret_cast<float4 *>(d_out);
-  const dim3 lin((unsigned)((n + 255) / 256)), blk(256), grid2((W + 255) / 256, H);
-  const bool light = ps->enableHDR || ps->enableGammaCorrection || ps->enableBloom;
-  if (!light && !ps->enableFXAA) {
-    if (d_out != d_frag) HIP_OK(hipMemcpyAsync(d_out, d_frag, n * 16, hipMemcpyDeviceToDevice, st));
-    return RM_OK;
-  }
-  if (light) {
-    if (ps->enableBloom) {  // applyBloom: 10 passes H,V,H,…; the composite reads the buffer pass 9 wrote
-      half4 *src = pa, *dst = pb;
-      const dim3 tiles((W + kBlurTW - 1) / kBlurTW, (H + kBlurTH - 1) / kBlurTH);
-      // passes 1-8 as four horizontal+vertical pairs through LDS; the first reads the float BrightColor plane directly
-      hipLaunchKernelGGL(blur_pair_kernel<true>, tiles, blk, 0, st, static_cast<const void *>(d_bright), src, W, H);
-      for (int i = 1; i < 4; i++) {
-        hipLaunchKernelGGL(blur_pair_kernel<false>, tiles, blk, 0, st, static_cast<const void *>(src), dst, W, H);
-        half4 *t = src; src = dst; dst = t;
-      }
-      // pass 9 (horizontal), the one composited, inside the composite
-      hipLaunchKernelGGL(light_bloom_kernel, grid2, blk, 0, st, frag, src, out, ps->enableFXAA ? stage8 : nullptr, W, H, ps->exposure);
-    } else {
-      hipLaunchKernelGGL(light_kernel, lin, blk, 0, st, frag, out, ps->enableFXAA ? stage8 : nullptr, (int)n, ps->enableHDR, ps->exposure);
+  return post_frames(d_frag, d_bright, d_out, W, H, 1, ps, 1, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rm_post_process_batch(const float *d_frag, const float *d_bright, float *d_out, int W, int H, int numFrames,
+                                     const RmPostSettings *ps, int numPost, void *stream) {
+  // every argument check ahead of the first HIP call (as rm_render_batch's)
+  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (numFrames == 0) return RM_OK;
+  if (numPost != 1 && numPost != numFrames) { set_error("numPost must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!d_frag || !d_out || !ps || W <= 0 || H <= 0) { set_error("bad post-process arguments"); return RM_ERR_INVALID_ARGUMENT; }
+  for (int f = 1; f < numPost; f++)
+    if (ps[f].enableFXAA != ps[0].enableFXAA || ps[f].enableGammaCorrection != ps[0].enableGammaCorrection ||
+        ps[f].enableHDR != ps[0].enableHDR || ps[f].enableBloom != ps[0].enableBloom) {
+      set_error("the enable flags of ps[" + std::to_string(f) + "] differ from ps[0]'s (only exposure may change per frame)");
+      return RM_ERR_INVALID_ARGUMENT;
     }
-  } else {
-    hipLaunchKernelGGL(quant8_kernel, lin, blk, 0, st, frag, stage8, (int)n);
-  }
-  if (ps->enableFXAA) {
-    static const int fbw = std::getenv("RM_FXAA_BLOCK_W") ? std::atoi(std::getenv("RM_FXAA_BLOCK_W")) : 16;
-    // 16 × 16 pixels per block (measured at 4K: 256×1 0.269 ms, 64×4 0.263, 32×8 0.257, 16×16 0.252 — the pass is bound by its divergent
-    // edge searches and bilinear fetches, not by cache lines)
-    const int bw = (fbw == 256 || fbw == 64 || fbw == 32 || fbw == 16) ? fbw : 16, bh = 256 / bw;
-    hipLaunchKernelGGL(fxaa_kernel, dim3((W + bw - 1) / bw, (H + bh - 1) / bh), dim3(bw, bh), 0, st, stage8, out, W, H);
-  }
-  HIP_OK(hipGetLastError());
-  return RM_OK;
+  if (ps[0].enableBloom && !d_bright) { set_error("bloom needs the BrightColor plane"); return RM_ERR_INVALID_ARGUMENT; }
+  if (int rc = require_device_pointers({{"d_frag", d_frag}, {"d_bright", d_bright}, {"d_out", d_out}})) return rc;
+  return post_frames(d_frag, d_bright, d_out, W, H, numFrames, ps, numPost, static_cast<hipStream_t>(stream));
 }

@@ -162,6 +162,35 @@ def batch_arrays(cameras, globals_):
     return (abi.RmCamera * max(len(cameras), 1))(*cameras), (abi.RmGlobals * len(globs))(*globs)
 
 
+def post_array(post, n):
+    """The ctypes array of rm_post_process_batch: RmPostSettings * 1 or N.  post is one RmPostSettings (every frame) or a sequence
+    of n; the enable flags must be the same in every entry (only exposure may differ).  Raises ValueError otherwise."""
+    posts = [post] if isinstance(post, abi.RmPostSettings) else list(post)
+    if not all(isinstance(p, abi.RmPostSettings) for p in posts):
+        raise ValueError("post must be an RmPostSettings or a sequence of them")
+    if len(posts) != n and len(posts) != 1:
+        raise ValueError(f"{len(posts)} post settings for {n} frames: pass one, or one per frame")
+    if len({(p.enableFXAA, p.enableGammaCorrection, p.enableHDR, p.enableBloom) for p in posts}) > 1:
+        raise ValueError("the enable flags must be the same for every frame; only exposure may differ")
+    return (abi.RmPostSettings * len(posts))(*posts)
+
+
+def save_png_sequence(images8, pattern):
+    """Write the (N, H, W, 4) uint8 images (top row first, as to_rgba8_batch / render_sequence return them) with rm_write_png,
+    image i to pattern.format(i), e.g. pattern="frame_{:04d}.png".  Returns the paths written."""
+    import numpy as np
+    imgs = images8.cpu().numpy() if hasattr(images8, "cpu") else np.asarray(images8)
+    if imgs.ndim != 4 or imgs.shape[-1] != 4 or imgs.dtype != np.uint8:
+        raise ValueError("images8 must be uint8 of shape (N, H, W, 4)")
+    paths = []
+    for i, img in enumerate(imgs):
+        img = np.ascontiguousarray(img)
+        path = pattern.format(i)
+        check(lib().rm_write_png(str(path).encode(), C.c_void_p(img.ctypes.data), img.shape[1], img.shape[0]))
+        paths.append(path)
+    return paths
+
+
 class Renderer:
     """Launches the HIP raymarch on one GPU; outputs are torch tensors on that device."""
 
@@ -340,6 +369,56 @@ class Renderer:
         out = self._out(out, (H, W, 4), t.uint8)
         check(lib().rm_frame_to_rgba8(C.c_void_p(frame.data_ptr()), C.c_void_p(out.data_ptr()), W, H, self._stream()))
         return out
+
+    def _frames(self, frames, name):
+        """(N, H, W) of a batch of frames (N, H, W, 4); ValueError for anything else.  Type and device: _out."""
+        if not isinstance(frames, self.torch.Tensor) or frames.dim() != 4 or frames.shape[-1] != 4:
+            raise ValueError(f"{name} must be a tensor of shape (N, H, W, 4)")
+        n, H, W = (int(d) for d in frames.shape[:3])
+        if n > abi.RM_MAX_BATCH_FRAMES:
+            raise ValueError(f"{n} frames: at most RM_MAX_BATCH_FRAMES = {abi.RM_MAX_BATCH_FRAMES} frames per batch")
+        return n, H, W
+
+    def post_process_batch(self, frames, brights, post, out=None):
+        """rm_post_process_batch: post_process of every frame of (N, H, W, 4) float32 `frames` (row 0 = bottom), brights the
+        matching BrightColor planes (None without bloom).  post: one RmPostSettings for every frame, or a sequence of N with the
+        same enable flags (the exposure may differ).  out may be `frames` itself (in place)."""
+        t = self.torch
+        n, H, W = self._frames(frames, "frames")
+        ps = post_array(post, n)
+        self._out(frames, (n, H, W, 4), t.float32, "frames")
+        if brights is not None:
+            self._out(brights, (n, H, W, 4), t.float32, "brights")
+        elif ps[0].enableBloom:
+            raise ValueError("bloom needs the BrightColor planes (brights)")
+        out = self._out(out, (n, H, W, 4), t.float32)
+        check(lib().rm_post_process_batch(C.c_void_p(frames.data_ptr()), C.c_void_p(brights.data_ptr()) if brights is not None else None,
+                                          C.c_void_p(out.data_ptr()), W, H, n, ps, len(ps), self._stream()))
+        return out
+
+    def to_rgba8_batch(self, frames, out=None):
+        """rm_frames_to_rgba8: to_rgba8 of every frame of (N, H, W, 4) float32 `frames` → uint8 (N, H, W, 4), each image's top
+        row first."""
+        t = self.torch
+        n, H, W = self._frames(frames, "frames")
+        self._out(frames, (n, H, W, 4), t.float32, "frames")
+        out = self._out(out, (n, H, W, 4), t.uint8)
+        check(lib().rm_frames_to_rgba8(C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()), W, H, n, self._stream()))
+        return out
+
+    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None):
+        """The finished images of an exported sequence: render_batch (with the BrightColor planes only when bloom is on), then
+        post_process_batch in place (skipped for post=None), then to_rgba8_batch → uint8 (N, H, W, 4), each image's top row
+        first.  post: one RmPostSettings or a sequence of N (see post_process_batch)."""
+        ps = post_array(post, len(cameras)) if post is not None else None
+        bloom = ps is not None and bool(ps[0].enableBloom)
+        frames = self.render_batch(tables, settings, W, H, cameras, globals_, bright=bloom)
+        brights = None
+        if bloom:
+            frames, brights = frames
+        if ps is not None:
+            self.post_process_batch(frames, brights, post, out=frames)
+        return self.to_rgba8_batch(frames)
 
     def save_png(self, frame, path):
         img = self.to_rgba8(frame).cpu().contiguous()
