@@ -506,6 +506,24 @@ int rm_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, 
 /* Evaluate sdScene (frag:1406-1430) at n world-space points: d_out[4n] = (minD, minObjIdx, trap.y, trap.z). */
 int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
                      const float *d_pts, float *d_out, int n, void *stream);
+/* Evaluate one of the production instantiations of the scene evaluator at n world-space points (tests only).
+ * bulbClass: 0 the table walk, 1 the single-Mandelbulb class in its general form, 2 in its plain form; count: the work-counter
+ * mode (0, 1, 2); trap: 0 none, 1 the shader's orbit trap, 2 the sponge's .z alone; skip / track: the table walk's pass-over
+ * test and its runner-up bound; one >= 0: the march's single-object fast path on object `one` (a primitive) instead of the walk.
+ * Only the combinations that production kernels instantiate are accepted:
+ *   table walk:  trap 0 / 1 with skip = track = 0, and with skip = track = 1 when count != 1; trap 0 with skip = 1, track = 0
+ *                when count != 1; trap 2 with count 0, track 0, skip 0 / 1;
+ *   bulbClass 1: trap 0 / 1, count 0 / 1 / 2, skip = track = 0;   bulbClass 2: trap 0 / 1, count 0, skip = track = 0;
+ *   one >= 0:    table walk, count 0 / 2, trap 0 / 1, skip = track = 1 (the march's instantiations that it stands in for).
+ * A bulb class needs a table of one Mandelbulb (bulbClass 2 also one that the plain form accepts); `one` must name a primitive.
+ * Anything else returns RM_ERR_INVALID_ARGUMENT before any HIP call.
+ * d_ub: per point, the upper bound of the minimum handed to the evaluation (only read with skip); NULL = +inf.
+ * d_out[8n] = (d, idx, trap.x, trap.y, trap.z, trap.w, second (+inf without track), shapes evaluated (0 with count 0)).
+ * Point i runs on lane i % 64 of wave i / 64 (the evaluator's wave-uniform choices see exactly those 64 points; the last wave
+ * may be partial). */
+int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, int bulbClass,
+                             int count, int trap, int skip, int track, int one, const float *d_pts, const float *d_ub,
+                             float *d_out, int n, void *stream);
 
 /* ---- host side kept from the reference: scenefile loader, camera, Settings -------------------- */
 /* Settings surface — src/settings.h:19-55 (render-relevant fields only). */

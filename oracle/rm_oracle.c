@@ -1699,6 +1699,19 @@ int rmo_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, 
   }
   return RM_OK;
 }
+/* the same evaluation with the whole orbit trap: out[6n] = (minD, minObjIdx, trap.x, trap.y, trap.z, trap.w) */
+int rmo_probe_sdscene_trap4(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                            const float *pts, float *out, int n) {
+  Ctx c;
+  c.cam = NULL; c.objs = objs; c.numObjects = numObjects; c.lights = NULL; c.numLights = 0;
+  c.g = *g; c.s = *s; c.nEval = c.nIter = c.nHit = 0; c.tex = NULL; c.numTex = 0;
+  for (int i = 0; i < n; i++) {
+    SceneMin m = sdScene(&c, V3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
+    float *o = out + 6 * i;
+    o[0] = m.minD; o[1] = (float)m.minObjIdx; o[2] = m.trap.x; o[3] = m.trap.y; o[4] = m.trap.z; o[5] = m.trap.w;
+  }
+  return RM_OK;
+}
 
 /* procedural-layer probes: kind 0 cloudsFbm → (value, gradient), 1 cloudsMap → (density, gra.y, nnd, 0),
  * 2 sdTerrain(p.xz) → (height, slope flag, 0, 0) */

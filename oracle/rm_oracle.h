@@ -27,6 +27,9 @@ int rmo_post_process(const float *frag, const float *bright, float *out, int W, 
 int rmo_probe_math(int fn, const float *x, const float *y, const float *z, float *out, int n);
 int rmo_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
                       const float *pts, float *out, int n);
+/* Same with the whole orbit trap: out[6n] = (minD, minObjIdx, trap.x, trap.y, trap.z, trap.w). */
+int rmo_probe_sdscene_trap4(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                            const float *pts, float *out, int n);
 int rmo_probe_env(int kind, float iTime, const float *pts, float *out, int n);
 int rmo_probe_env2(int kind, float iTime, const RmTexture *noise, const float *pts, float *out, int n);
 uint32_t rmo_const_bits(int which);

@@ -487,8 +487,9 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
       //    quantities.  The algebraic form's complex squarings are odd in sx and even in cz the same way.  A NaN generated
       //    on the way (inf·0) is the default NaN in both mirror images, and from there both run identically.
       // So the value and the trap of pos = p equal those of the transformed point, as long as p is finite: the transform
-      // turns a non-finite coordinate anywhere into NaN in all three (+0·inf), which p does not.  dot(p, p) < inf holds
-      // exactly when all three coordinates are finite; a wave with any other lane takes the transform.
+      // turns a non-finite coordinate anywhere into NaN in all three (+0·inf), which p does not.  dot(p, p) < inf implies
+      // that all three coordinates are finite, but not conversely: a finite p with |p| above ~1.8e19 overflows it too.  A wave
+      // with any lane that fails the test takes the transform, which is always exact, so the test may be conservative.
       po = p;
       if (__ballot(!(dot(p, p) < __builtin_inff())) != 0ull) po = transform();
     } else {

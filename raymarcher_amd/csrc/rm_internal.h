@@ -31,6 +31,11 @@ int require_device_pointers(std::initializer_list<std::pair<const char *, const 
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
 enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
+// The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
+// this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).
+bool sdscene_variant_exists(int bulbClass, int count, int trap, int skip, int track, bool one);
+int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, int skip, int track, int one, const float *d_pts,
+                           const float *d_ub, float *d_out, int n, hipStream_t stream);
 #endif
 // The largest single workspace buffer stream_workspace may allocate, 0 = no limit (rm_set_workspace_limit).
 unsigned long long workspace_limit();

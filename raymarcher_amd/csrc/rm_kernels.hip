@@ -2096,4 +2096,32 @@ int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, c
   return RM_OK;
 }
 
+int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, int bulbClass,
+                             int count, int trap, int skip, int track, int one, const float *d_pts, const float *d_ub,
+                             float *d_out, int n, void *stream) {
+  RmCamera cam{};
+  int st = validate_scene(&cam, objs, numObjects, nullptr, 0, g, s, kNoResources);
+  if (st != RM_OK) return st;
+  auto bad = [](const char *msg) { set_error(msg); return (int)RM_ERR_INVALID_ARGUMENT; };
+  if (!sdscene_variant_exists(bulbClass, count, trap, skip, track, one >= 0))
+    return bad("no production kernel instantiates this sdScene variant");
+  if (bulbClass != 0 && (numObjects != 1 || objs[0].type != RM_MANDELBULB)) return bad("a bulb class needs a table of one Mandelbulb");
+  if (bulbClass == kBulbPlain && !bulb_plain(objs, numObjects, g)) return bad("the plain bulb form does not apply to this table");
+  if (one < -1 || one >= numObjects || (one >= 0 && !(objs[one].type >= RM_CUBE && objs[one].type <= RM_RECTANGLE)))
+    return bad("`one` must name a primitive of the table");
+  if (!d_pts || !d_out || n < 0) return bad("bad probe arguments");
+  if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_ub", d_ub}, {"d_out", d_out}})) return st2;
+  if (n == 0) return RM_OK;
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  Slot *slot;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  st = stage_scene(&cam, objs, numObjects, nullptr, 0, g, s, hs, *ds, &slot, kNoResources);
+  if (st != RM_OK) return st;
+  st = launch_sdscene_variant(slot->dev, bulbClass, count, trap, skip, track, one, d_pts, d_ub, d_out, n, hs);
+  HIP_OK(hipEventRecord(slot->done, hs));
+  return st;
+}
+
 }  // extern "C"

@@ -439,3 +439,21 @@ class Renderer:
         check(lib().rm_probe_sdscene(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings),
                                      C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()), n, self._stream()))
         return out
+
+    def probe_sdscene_variant(self, tables, settings, pts, bulb_class=0, count=0, trap=1, skip=0, track=0, one=-1, ub=None,
+                              out=None):
+        """One production instantiation of the scene evaluator at the (n, 3) points `pts` (include/raymarcher_amd.h,
+        rm_probe_sdscene_variant; point i runs on lane i % 64 of wave i / 64).  ub: (n,) upper bounds of the minimum or None
+        (+inf).  Returns (n, 8): d, idx, trap.x, trap.y, trap.z, trap.w, second, shapes evaluated."""
+        t = self.torch
+        n = pts.shape[0]
+        if tuple(pts.shape) != (n, 3) or pts.dtype != t.float32 or not pts.is_contiguous() or pts.device != self.device:
+            raise ValueError(f"pts must be a contiguous float32 tensor of shape (n, 3) on {self.device}")
+        if ub is not None and (tuple(ub.shape) != (n,) or ub.dtype != t.float32 or not ub.is_contiguous() or ub.device != self.device):
+            raise ValueError(f"ub must be a contiguous float32 tensor of shape ({n},) on {self.device}")
+        out = self._out(out, (n, 8), t.float32)
+        check(lib().rm_probe_sdscene_variant(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings),
+                                             bulb_class, count, trap, skip, track, one, C.c_void_p(pts.data_ptr()),
+                                             C.c_void_p(ub.data_ptr()) if ub is not None else None,
+                                             C.c_void_p(out.data_ptr()), n, self._stream()))
+        return out
