@@ -379,8 +379,9 @@ int rm_set_kernel_path(int path);
  * workspace exceeds the limit or the device cannot allocate it, a launch that chose the pipeline by itself (kernel path 0)
  * renders with rm::render_kernel instead — identical pixels, no workspace — and remembers the refusal for that stream; only
  * an explicit rm_set_kernel_path(5) reports RM_ERR_DEVICE.  An allocation failure never leaves HIP's error state set.
- * rm_release_workspaces drains the current device and frees all of its buffers (freedBytes may be NULL); the next launch
- * that needs one allocates it again, and the next frame on each stream runs in raster tile order. */
+ * rm_release_workspaces drains the current device and frees all of its buffers (freedBytes may be NULL); a render launch or
+ * post pass that another thread is enqueuing on the device at the time finishes its enqueue first.  The next launch that
+ * needs a buffer allocates it again, and the next frame on each stream runs in raster tile order. */
 int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a

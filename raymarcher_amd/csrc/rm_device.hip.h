@@ -130,8 +130,8 @@ struct SceneBlock {
   int32_t splitTiles;
   float *splitStore;
   // Uniforms of sdMengerSponge's prologue (frag:1052-1053: ani = smoothstep(−0.2, 0.2, −cos(0.5·iTime)), off = 1.5·sin(0.01·iTime)),
-  // evaluated ONCE per launch by scene_prep_kernel with the contract's own sin / cos instead of once per evaluation per lane
-  // (≈45 of the ≈230 vector instructions of a 5-level evaluation); only read when the table holds a Menger sponge.
+  // evaluated ONCE per frame of a launch by scene_prep_batch_kernel with the contract's own sin / cos instead of once per evaluation
+  // per lane (≈45 of the ≈230 vector instructions of a 5-level evaluation); only read when the table holds a Menger sponge.
   float mengerAni, mengerOff;
 };
 
@@ -362,7 +362,7 @@ template <int TRAP, int LEVELS, bool STILL>
 RM_DEV float mengerImpl(const SceneBlock *sb, V3 p, V4 &res) {
   float d = sdBox(p, 1.0f, 1.0f, 1.0f);
   float ty = 1.0f, tz = 0.0f;
-  const float ani = sb->mengerAni, off = sb->mengerOff;  // scene_prep_kernel (rm_kernels.hip): the prologue's uniforms
+  const float ani = sb->mengerAni, off = sb->mengerOff;  // scene_prep_batch_kernel (rm_kernels.hip): the prologue's uniforms
   const int levels = LEVELS > 0 ? LEVELS : sb->s.mengerLevels;
   const bool still = STILL || ani == 0.0f;  // wave-uniform (scalar loads)
   // one level (frag:1057-1069); hs = 0.5·s = 0.5·3^m and the divisor 3^(m+1) as compile-time constants (DIVC > 0)

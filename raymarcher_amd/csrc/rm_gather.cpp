@@ -61,14 +61,6 @@ int load_rccl() {
   return RM_OK;
 }
 
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
-      return RM_ERR_DEVICE;                                                                       \
-    }                                                                                             \
-  } while (0)
 #define NCCL_OK(expr)                                                                             \
   do {                                                                                            \
     ncclResult_t r_ = (expr);                                                                     \

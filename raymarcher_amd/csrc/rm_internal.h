@@ -1,6 +1,7 @@
 // rm_internal.h — helpers shared by the launcher (rm_kernels.hip) and the host side (rm_host.cpp).
 #pragma once
 #include <initializer_list>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -26,6 +27,18 @@ bool device_accessible(const void *p);
 int require_device_pointers(std::initializer_list<std::pair<const char *, const void *>> ptrs);
 
 #ifdef __HIPCC__
+// Evaluates a HIP call; on failure records "<call>: <HIP's text>" and returns RM_ERR_DEVICE from the enclosing function.
+#define HIP_OK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) {                                                                       \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
+      return RM_ERR_DEVICE;                                                                       \
+    }                                                                                             \
+  } while (0)
+// Takes the launcher's lock of the current device (rm_kernels.hip).  Whoever enqueues work on a buffer of stream_workspace
+// holds it from that call to its last launch: rm_release_workspaces takes it too, so it never frees a buffer in use.
+int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
 // different streams of one device may run concurrently on the GPU and therefore never share scratch.  Growing
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.

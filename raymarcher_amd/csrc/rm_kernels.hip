@@ -207,8 +207,7 @@ RM_DEV void menger_uniforms(SceneBlock *sb) {
   sb->mengerAni = smoothstep_(-0.2f, 0.2f, -cos_(0.5f * sb->g.iTime));
   sb->mengerOff = 1.5f * sin_(0.01f * sb->g.iTime);
 }
-__global__ void scene_prep_kernel(SceneBlock *sb) { menger_uniforms(sb); }
-// the same for every frame of a batch (rm_render_batch): one thread per scene block, each with its own iTime
+// one thread per scene block of the launch (one frame, or every frame of a batch), each with its own iTime
 __global__ void scene_prep_batch_kernel(SceneBlock *sb, int n) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f < n) menger_uniforms(sb + f);
@@ -417,28 +416,12 @@ __global__ void deinterleave_kernel(const float4 *__restrict__ in, float4 *__res
 // is held across a blocking HIP call on the launch path.  Scratch memory is per (device, stream): two calls on different
 // streams of one device may overlap on the GPU, so they must not share ping-pong buffers or hit lists.
 namespace {
-constexpr int kSlotsInit = 8, kSlotsMax = 64;
-struct Slot {
-  SceneBlock *host = nullptr;  // pinned
-  SceneBlock *dev = nullptr;
-  hipEvent_t done = nullptr;
-  bool used = false;
-};
 struct TileOrderState {
   int tileCount = 0, W = 0, nRows = 0, nw = 0, tileShift = 3;
   void *mem = nullptr;
   unsigned long long sceneKey = 0;  // hash of the scene + camera + row map of the frame that recorded the costs in `mem`
   int sorts = 0;                     // consecutive frames of that picture whose order came from measured costs
 };
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
-      return RM_ERR_DEVICE;                                                                       \
-    }                                                                                             \
-  } while (0)
-
 // "Tile shape": which of the two tile shapes a picture renders faster with is scene-dependent (upright objects: 4 wide × 16 tall
 // tiles straddle fewer vertical silhouettes, so whole waves agree on the table walk's shortcuts more often — C2 at 1080p 0.866 →
 // 0.792 ms — while reflections_complex.json loses 5 % that way; profiles/r04_m_tile_shape.txt).  So the launcher MEASURES, per
@@ -516,19 +499,23 @@ struct StreamState {
   size_t wfDenied = 0;       // smallest wavefront workspace (bytes) that could not be had on the stream; 0: none was refused
 };
 struct TimedLaunch { hipEvent_t ev[5]; int n; };  // n = 2 (one stage) or 3 (tile-order sort + render kernel)
-// The scene blocks of one batch (rm_render_batch): `cap` SceneBlocks, contiguous, pinned on the host and on the device.
-struct BatchSlot {
+// The scene blocks of one launch: `cap` SceneBlocks, contiguous, pinned on the host and on the device.
+struct Slot {
   SceneBlock *host = nullptr, *dev = nullptr;
   int cap = 0;
-  hipEvent_t done = nullptr;
+  hipEvent_t done = nullptr;  // recorded behind the slot's last launch
   bool used = false;
+};
+// A ring of slots (acquire_slot): at most maxSlots, each of at least minCap blocks once allocated.
+struct Ring {
+  int maxSlots, minCap;
+  std::vector<Slot> slots;
+  size_t next = 0;
 };
 struct DeviceState {
   std::mutex mu;                 // guards everything below; held for the host-side enqueue of ONE launch on this device
-  std::vector<Slot> slots;       // ring of scene-table slots; grows (to kSlotsMax) instead of waiting for a busy slot
-  size_t next = 0;
-  std::vector<BatchSlot> batchSlots;  // the same for batches (acquire_batch_slot), to kBatchSlotsMax
-  size_t batchNext = 0;
+  Ring frames{64, 1};            // single frames and probes: up to 64 slots of one block
+  Ring batches{4, 16};           // rm_render_batch: up to 4 slots of 16 … RM_MAX_BATCH_FRAMES blocks
   unsigned long long *dCounters = nullptr;  // 10 words: evals, iterations, hits, clock stamps (2), span pointer, shades, fbm9, fbmd8, shapes
   std::vector<TimedLaunch> timed;           // rm_set_timing / rm_get_timing, per device
   int numCUs = 0;
@@ -558,48 +545,37 @@ int env_int(const char *name, int def, int lo = INT_MIN, int hi = INT_MAX) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
-int new_slot(Slot *s) {
-  HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&s->host), sizeof(SceneBlock), hipHostMallocDefault));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&s->dev), sizeof(SceneBlock)));
-  HIP_OK(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+// the device the calling thread has current
+int current_device_state(DeviceState **out) {
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
+  *out = &g_dev[dev];
   return RM_OK;
 }
-// Caller holds ds.mu.  Returns a slot whose previous launch (if any) has finished: the next slot of the ring if its event
-// has fired, otherwise a fresh one — the enqueue path never blocks on the GPU while it holds the device lock.  Only when
-// kSlotsMax launches are in flight does it wait (hipEventSynchronize on the oldest), which bounds pinned memory.
-int acquire_slot(DeviceState &ds, Slot **out) {
-  if (ds.slots.empty()) {
-    // built aside and swapped in only when every allocation has succeeded: a failure part-way (out of memory on the first
-    // call) leaves the device state empty, so the next call tries again instead of handing out half-made slots
-    std::vector<Slot> fresh(kSlotsInit);
-    unsigned long long *counters = nullptr;
-    int st = RM_OK;
-    for (auto &s : fresh)
-      if ((st = new_slot(&s)) != RM_OK) break;
-    if (st == RM_OK && hipMalloc(reinterpret_cast<void **>(&counters), 10 * sizeof(unsigned long long)) != hipSuccess) {
-      set_error("hipMalloc of the counter block failed");
-      st = RM_ERR_DEVICE;
-    }
-    if (st != RM_OK) {
-      for (auto &s : fresh) {
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
-        if (s.done) (void)hipEventDestroy(s.done);
-      }
-      return st;
-    }
-    ds.slots.swap(fresh);
-    ds.dCounters = counters;
-  }
-  Slot *s = &ds.slots[ds.next];
+
+void free_slot(Slot &s) {
+  if (s.host) (void)hipHostFree(s.host);
+  if (s.dev) (void)hipFree(s.dev);
+  if (s.done) (void)hipEventDestroy(s.done);
+  s = Slot{};
+}
+// Caller holds the device's lock.  Returns a slot of at least n blocks whose last launch (if any) has finished, so that its pinned
+// blocks, whose upload may still be in flight, are never overwritten.  The next slot of the ring if its event has fired; otherwise
+// a fresh slot in front of it (ring order) while the ring is below its maximum, so the enqueue path does not block on the GPU
+// while it holds the device lock; only at the maximum does it wait for that slot (hipEventSynchronize), which bounds pinned
+// memory.  Slots are grow-only: an idle slot of fewer than n blocks is reallocated to the next power of two >= max(n, minCap)
+// (a batch slot at most six times over a process; those frees may wait for the device).  A failed allocation leaves an empty
+// slot (cap 0), which the next launch that lands on it tries again.
+int acquire_slot(Ring &ring, int n, Slot **out) {
+  if (ring.slots.empty()) { ring.slots.resize(1); ring.next = 0; }
+  Slot *s = &ring.slots[ring.next];
   if (s->used) {
     const hipError_t q = hipEventQuery(s->done);
     if (q == hipErrorNotReady) {
-      if ((int)ds.slots.size() < kSlotsMax) {
-        ds.slots.insert(ds.slots.begin() + (long)ds.next, Slot{});  // a fresh slot in front of the busy one keeps ring order
-        s = &ds.slots[ds.next];
-        int st = new_slot(s);
-        if (st != RM_OK) { ds.slots.erase(ds.slots.begin() + (long)ds.next); return st; }
+      if ((int)ring.slots.size() < ring.maxSlots) {
+        ring.slots.insert(ring.slots.begin() + (long)ring.next, Slot{});
+        s = &ring.slots[ring.next];
       } else {
         HIP_OK(hipEventSynchronize(s->done));
       }
@@ -608,60 +584,24 @@ int acquire_slot(DeviceState &ds, Slot **out) {
       return RM_ERR_DEVICE;
     }
   }
-  ds.next = (ds.next + 1) % ds.slots.size();
+  if (s->cap < n) {
+    int cap = ring.minCap;
+    while (cap < n) cap *= 2;
+    free_slot(*s);
+    const size_t bytes = (size_t)cap * sizeof(SceneBlock);
+    if (hipHostMalloc(reinterpret_cast<void **>(&s->host), bytes, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s->dev), bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      free_slot(*s);
+      set_error("allocation of " + std::to_string(bytes) + " bytes of scene blocks failed");
+      return RM_ERR_DEVICE;
+    }
+    s->cap = cap;
+  }
+  ring.next = (ring.next + 1) % ring.slots.size();
   s->used = true;
   *out = s;
-  return RM_OK;
-}
-
-// The batch ring (rm_render_batch) keeps the single-frame ring's rules: a slot is written only after the event recorded behind
-// its last launch has fired (the pinned blocks of a batch whose upload may still be in flight are never overwritten); a busy
-// slot gets a fresh one in front of it instead of a wait, up to kBatchSlotsMax slots, and only then the enqueue waits for the
-// oldest.  Slots are grow-only: a batch larger than the idle slot it lands on replaces that slot's buffers by ones of the next
-// power of two >= numFrames (16 … RM_MAX_BATCH_FRAMES blocks, 9.7 KB each) — at most six times per slot over a process, and
-// those frees may wait for the device.  Caller holds ds.mu.
-constexpr int kBatchSlotsMax = 4;
-void free_batch_slot(BatchSlot &b) {
-  if (b.host) (void)hipHostFree(b.host);
-  if (b.dev) (void)hipFree(b.dev);
-  if (b.done) (void)hipEventDestroy(b.done);
-  b = BatchSlot{};
-}
-int acquire_batch_slot(DeviceState &ds, int n, BatchSlot **out) {
-  if (ds.batchSlots.empty()) { ds.batchSlots.resize(1); ds.batchNext = 0; }
-  BatchSlot *b = &ds.batchSlots[ds.batchNext];
-  if (b->used) {
-    const hipError_t q = hipEventQuery(b->done);
-    if (q == hipErrorNotReady) {
-      if ((int)ds.batchSlots.size() < kBatchSlotsMax) {
-        ds.batchSlots.insert(ds.batchSlots.begin() + (long)ds.batchNext, BatchSlot{});  // in front of the busy one: ring order
-        b = &ds.batchSlots[ds.batchNext];
-      } else {
-        HIP_OK(hipEventSynchronize(b->done));
-      }
-    } else if (q != hipSuccess) {
-      set_error(std::string("hipEventQuery: ") + hipGetErrorString(q));
-      return RM_ERR_DEVICE;
-    }
-  }
-  if (b->cap < n) {  // idle (never used, or its last launch has finished): grow
-    int cap = 16;
-    while (cap < n) cap *= 2;
-    free_batch_slot(*b);
-    const size_t bytes = (size_t)cap * sizeof(SceneBlock);
-    if (hipHostMalloc(reinterpret_cast<void **>(&b->host), bytes, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&b->dev), bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      free_batch_slot(*b);  // an empty slot (cap 0): the next batch that lands on it tries again
-      set_error("allocation of " + std::to_string(bytes) + " bytes of batch scene blocks failed");
-      return RM_ERR_DEVICE;
-    }
-    b->cap = cap;
-  }
-  ds.batchNext = (ds.batchNext + 1) % ds.batchSlots.size();
-  b->used = true;
-  *out = b;
   return RM_OK;
 }
 
@@ -684,6 +624,13 @@ unsigned long long workspace_limit() {
   return v;
 }
 
+int lock_current_device(std::unique_lock<std::mutex> &lock) {
+  DeviceState *ds;
+  if (int st = current_device_state(&ds)) return st;
+  lock = std::unique_lock<std::mutex>(ds->mu);
+  return RM_OK;
+}
+
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out) {
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
@@ -691,7 +638,7 @@ int stream_workspace(int tag, hipStream_t stream, size_t need, void **out) {
   {
     std::lock_guard<std::mutex> lock(g_wsMu);
     b = &g_ws[WsKey{dev, stream, tag}];  // std::map nodes are stable: the pointer outlives the lock
-  }
+  }  // and the caller holds the device's launcher lock, which release_workspaces' caller takes before it erases the node
   // only work enqueued on `stream` uses this buffer, and one host thread enqueues on a stream at a time
   if (b->bytes < need) {
     const unsigned long long limit = workspace_limit();
@@ -722,12 +669,10 @@ int release_workspaces(size_t *freedOut) {
   size_t freed = 0;
   std::lock_guard<std::mutex> lock(g_wsMu);
   for (auto it = g_ws.begin(); it != g_ws.end();) {
-    if (it->first.dev == dev) {
-      if (it->second.mem) { HIP_OK(hipFree(it->second.mem)); freed += it->second.bytes; }
-      it = g_ws.erase(it);
-    } else {
-      ++it;
-    }
+    if (it->first.dev != dev) { ++it; continue; }
+    const WsBuf b = it->second;
+    it = g_ws.erase(it);  // before the free: a failure leaves no entry that points at freed memory
+    if (b.mem) { HIP_OK(hipFree(b.mem)); freed += b.bytes; }
   }
   if (freedOut) *freedOut = freed;
   return RM_OK;
@@ -1074,11 +1019,13 @@ int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {
   return (g->juliaSeed[0] == 0.0f && g->juliaSeed[1] == 0.0f) ? 1 : 0;
 }
 
-// Everything of a frame's SceneBlock that the caller's tables decide (the launch fields — tile order, light split, Menger
-// uniforms — are the stager's).
-void fill_scene(SceneBlock *h, const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
-                const RmGlobals *g, const RmSettings *s, const RmResources &res) {
-  h->cam = *cam; h->g = *g; h->s = *s;
+// The fill step of a launch: everything of the SceneBlocks of frames 0 … n−1 of one scene that the caller's tables decide (the
+// launch fields are upload_frames').  Block 0 from the tables; every other frame a copy of it with its own camera and globals
+// (globals[numGlobals == 1 ? 0 : f]) and what they decide: the ray planes, the plain-bulb flag and, where the globals differ per
+// frame and the table holds a Mandelbulb (the only type whose cull bounds read them), the cull bounds.
+void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs,
+                 int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res) {
+  h->cam = cams[0]; h->g = globals[0]; h->s = *s;
   h->numObjects = numObjects; h->numLights = numLights;
   for (int i = 0; i < numObjects; i++) h->objs[i] = objs[i];
   scene_eval_records(h);
@@ -1090,30 +1037,46 @@ void fill_scene(SceneBlock *h, const RmCamera *cam, const RmObject *objs, int nu
   h->ltc1 = res.ltc1; h->ltc2 = res.ltc2;
   scene_cull_ball(h);
   ray_planes(h);
-  h->bulbPlain = bulb_plain(objs, numObjects, g);
+  h->bulbPlain = bulb_plain(objs, numObjects, &globals[0]);
+  bool bulbInTable = false;
+  for (int i = 0; i < numObjects; i++) bulbInTable = bulbInTable || objs[i].type == RM_MANDELBULB;
+  for (int f = 1; f < n; f++) {
+    SceneBlock *b = h + f;
+    *b = *h;
+    b->cam = cams[f];
+    b->g = globals[numGlobals == 1 ? 0 : f];
+    if (bulbInTable && numGlobals > 1) scene_cull_ball(b);
+    ray_planes(b);
+    b->bulbPlain = bulb_plain(objs, numObjects, &b->g);
+  }
 }
 
-int stage_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
-                const RmGlobals *g, const RmSettings *s, hipStream_t stream, DeviceState &ds, Slot **slotOut,
-                const RmResources &res, const int32_t *tileOrder = nullptr, uint32_t *tileCost = nullptr,
-                int tileCount = 0, int tileShift = 3, int splitTiles = 0, float *splitStore = nullptr) {  // caller holds ds.mu
-  Slot *slot;
-  int st = acquire_slot(ds, &slot);
-  if (st != RM_OK) return st;
-  SceneBlock *h = slot->host;
-  fill_scene(h, cam, objs, numObjects, lights, numLights, g, s, res);
-  h->tileOrder = tileOrder; h->tileCost = tileCost; h->tileCount = tileCount;
-  h->tileShift = tileShift;
-  h->splitTiles = splitTiles; h->splitStore = splitStore;
-  h->mengerAni = 0.0f; h->mengerOff = 0.0f;
-  HIP_OK(hipMemcpyAsync(slot->dev, h, sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
+// The fields of a SceneBlock that the launch decides, the same in every block of the launch (the defaults: raster order, no
+// cost feedback, 8×8 tiles, no light split).
+struct LaunchFields {
+  const int32_t *tileOrder = nullptr;
+  uint32_t *tileCost = nullptr;
+  int tileCount = 0, tileShift = 3, splitTiles = 0;
+  float *splitStore = nullptr;
+};
+// The upload step: the launch fields into the slot's first n blocks, one copy of them to the device and, when the table holds a
+// Menger sponge, each frame's sponge uniforms computed on the device — stream-ordered between the upload and the kernels that
+// read the blocks.
+int upload_frames(const Slot &slot, int n, const LaunchFields &lf, hipStream_t stream) {
+  for (int f = 0; f < n; f++) {
+    SceneBlock *h = slot.host + f;
+    h->tileOrder = lf.tileOrder; h->tileCost = lf.tileCost; h->tileCount = lf.tileCount;
+    h->tileShift = lf.tileShift;
+    h->splitTiles = lf.splitTiles; h->splitStore = lf.splitStore;
+    h->mengerAni = 0.0f; h->mengerOff = 0.0f;
+  }
+  HIP_OK(hipMemcpyAsync(slot.dev, slot.host, (size_t)n * sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
   bool menger = false;
-  for (int i = 0; i < numObjects; i++) menger = menger || objs[i].type == RM_MENGERSPONGE;
-  if (menger) {  // stream-ordered between the upload and the kernels that read the block
-    hipLaunchKernelGGL(scene_prep_kernel, dim3(1), dim3(1), 0, stream, slot->dev);
+  for (int i = 0; i < slot.host->numObjects; i++) menger = menger || slot.host->objs[i].type == RM_MENGERSPONGE;
+  if (menger) {
+    hipLaunchKernelGGL(scene_prep_batch_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, slot.dev, n);
     HIP_OK(hipGetLastError());
   }
-  *slotOut = slot;
   return RM_OK;
 }
 
@@ -1196,7 +1159,7 @@ struct Wavefront {
 // workspace — and only an explicit path-5 request reports the failure.  A (device, stream) that was refused once is not asked
 // again for as much or more, so a frame sequence does not pay a failing allocation (and the stream synchronisation in front of
 // it) per frame.
-int setup_wavefront(DeviceState &ds, StreamState &ss, int dev, const FrameClass &fc, const RmObject *objs, int numObjects,
+int setup_wavefront(DeviceState &ds, StreamState &ss, const FrameClass &fc, const RmObject *objs, int numObjects,
                     int numLights, int W, int nRows, bool tileShard, int pathReq, hipStream_t stream, Wavefront *wf) {
   wf->on = fc.wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(objs, numObjects, fc.wfBounces, (size_t)nRows * W, tileShard)));
   if (!wf->on) return RM_OK;
@@ -1212,7 +1175,9 @@ int setup_wavefront(DeviceState &ds, StreamState &ss, int dev, const FrameClass 
   wf->pixelChunk = envPixelChunk > 0 ? clampChunk(envPixelChunk) : wfRayChunk(0);
   wf->flush = envFlush > 0 && envFlush <= 64 ? envFlush : 16;
   if (ds.numCUs == 0) {
+    int dev = 0;
     hipDeviceProp_t prop;
+    HIP_OK(hipGetDevice(&dev));
     HIP_OK(hipGetDeviceProperties(&prop, dev));
     ds.numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
@@ -1419,21 +1384,24 @@ void launch_counted(int count, const RenderLaunch &r) {
   else launch_kernel<BULB, 3, false, false>(r);
 }
 // the layer / sampler kernels: their counting instantiations count the reference's work only (they have no shortcuts to count apart)
-template <bool ENV, bool TEX>
+template <bool ENV, bool TEX, bool BATCH>
 void launch_layered(int count, bool secondary, const RenderLaunch &r) {
   if (count) launch_kernel<0, 1, ENV, TEX>(r);
-  else launch_production<0, ENV, TEX>(secondary, r);
+  else launch_production<0, ENV, TEX, BATCH>(secondary, r);
 }
+// BATCH: the batched production kernels (rm_render_batch, one class for every frame of the launch), which a batch reaches with
+// count = 0 and no light split; the counted and split kernels exist for single frames only.
+template <bool BATCH = false>
 int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const LightSplit &ls, int numLights, int tileCount,
                     const RenderLaunch &r) {
-  if (fc.envFeatures && fc.textured) launch_layered<true, true>(count, fc.secondary, r);
-  else if (fc.envFeatures) launch_layered<true, false>(count, fc.secondary, r);
-  else if (fc.textured) launch_layered<false, true>(count, fc.secondary, r);
+  if (fc.envFeatures && fc.textured) launch_layered<true, true, BATCH>(count, fc.secondary, r);
+  else if (fc.envFeatures) launch_layered<true, false, BATCH>(count, fc.secondary, r);
+  else if (fc.textured) launch_layered<false, true, BATCH>(count, fc.secondary, r);
   else if (fc.bulb) {
     // the counted launches keep the general form; the production ones take the plain form where the launcher found it
     if (count) launch_counted<kBulbGeneral>(count, r);
-    else if (plainBulb) launch_production<kBulbPlain, false, false>(fc.secondary, r);
-    else launch_production<kBulbGeneral, false, false>(fc.secondary, r);
+    else if (plainBulb) launch_production<kBulbPlain, false, false, BATCH>(fc.secondary, r);
+    else launch_production<kBulbGeneral, false, false, BATCH>(fc.secondary, r);
   } else if (count) launch_counted<0>(count, r);
   else if (!fc.secondary && ls.tiles > 0) {
     // light split: the heavy tiles one light per workgroup first, every other tile behind them in the same grid; the last of a
@@ -1444,18 +1412,8 @@ int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const Light
     split.grid = dim3((unsigned)(ls.tiles * numLights + tileCount - ls.tiles));
     split.block = dim3(64);
     launch_kernel<0, 0, false, false, false, 1>(split);
-  } else launch_production<0, false, false>(fc.secondary, r);
+  } else launch_production<0, false, false, BATCH>(fc.secondary, r);
   return RM_OK;
-}
-
-// the batched production kernels (rm_render_batch): one class for every frame of the launch
-void dispatch_batch(const FrameClass &fc, bool plainBulb, const RenderLaunch &r) {
-  if (fc.envFeatures && fc.textured) launch_production<0, true, true, true>(fc.secondary, r);
-  else if (fc.envFeatures) launch_production<0, true, false, true>(fc.secondary, r);
-  else if (fc.textured) launch_production<0, false, true, true>(fc.secondary, r);
-  else if (fc.bulb && plainBulb) launch_production<kBulbPlain, false, false, true>(fc.secondary, r);
-  else if (fc.bulb) launch_production<kBulbGeneral, false, false, true>(fc.secondary, r);
-  else launch_production<0, false, false, true>(fc.secondary, r);
 }
 
 // rm_set_kernel_path / RM_KERNEL_PATH: 0 = the measured-fastest schedule of the scene's class
@@ -1469,6 +1427,26 @@ int waves_per_block() {
   return (wpb == 1 || wpb == 2 || wpb == 4) ? wpb : 1;
 }
 
+// rm_set_timing: the events of one launch — one ahead of it, one after the ordering launches if they run, one after the render.
+// keep() hands them to the device's list; a launch that fails part-way destroys them on the way out.
+struct LaunchTimer {
+  TimedLaunch t{};
+  hipStream_t stream;
+  bool on = g_timing.load(), kept = false;
+  explicit LaunchTimer(hipStream_t s) : stream(s) {}
+  ~LaunchTimer() { if (!kept) for (int i = 0; i < t.n; i++) (void)hipEventDestroy(t.ev[i]); }
+  int stamp() {
+    if (!on) return RM_OK;
+    HIP_OK(hipEventCreate(&t.ev[t.n]));
+    t.n++;
+    HIP_OK(hipEventRecord(t.ev[t.n - 1], stream));
+    return RM_OK;
+  }
+  void keep(DeviceState &ds) {
+    if (on) { ds.timed.push_back(t); kept = true; }
+  }
+};
+
 int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                   const RmGlobals *g, const RmSettings *s, int W, int H, RowMap map, int nRows, float *d_rgba,
                   float *d_bright, hipStream_t stream, int count, RmCounters *countersOut,
@@ -1480,18 +1458,24 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
   if (nRows == 0) return RM_OK;  // empty row range: nothing to write, a null buffer is fine
   if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
   if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
-  int dev = 0;
-  HIP_OK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
-  DeviceState &ds = g_dev[dev];
+  DeviceState *pds;
+  if ((st = current_device_state(&pds)) != RM_OK) return st;
+  DeviceState &ds = *pds;
   std::lock_guard<std::mutex> lock(ds.mu);  // this device only; nothing below blocks on the GPU unless `count` asks for numbers back
+  // the counter block (DeviceState::dCounters) that every render launch passes to its kernel, allocated once per device
+  if (!ds.dCounters && hipMalloc(reinterpret_cast<void **>(&ds.dCounters), 10 * sizeof(unsigned long long)) != hipSuccess) {
+    (void)hipGetLastError();
+    ds.dCounters = nullptr;
+    set_error("hipMalloc of the counter block failed");
+    return RM_ERR_DEVICE;
+  }
   StreamState &ss = ds.streams[stream];
   // Two schedules of the same per-ray arithmetic, identical bits: rm::render_kernel (one lane per pixel; every class, and the
   // counted variants) and, for table-walk classes with bounces, the wavefront pipeline.
   const int pathReq = kernel_path_request();
   const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, g, s, count);
   Wavefront wf;
-  if ((st = setup_wavefront(ds, ss, dev, fc, objs, numObjects, numLights, W, nRows, map.numShards > 1, pathReq, stream, &wf)) != RM_OK) return st;
+  if ((st = setup_wavefront(ds, ss, fc, objs, numObjects, numLights, W, nRows, map.numShards > 1, pathReq, stream, &wf)) != RM_OK) return st;
   // Waves (8×8 tiles, side by side) per workgroup.  A workgroup's registers and LDS come free only when its LAST wave
   // ends, and march lengths differ a lot between neighbouring tiles, so small workgroups keep more waves resident: one wave
   // per workgroup for every class (measured at the register budgets above: the 4K bulb frame 2.31 / 2.34 / 2.58 ms at
@@ -1508,58 +1492,44 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
   if ((st = plan_tile_order(ds, ss, fc, wf.on, count, numObjects, W, nRows, nw, tileShift, tileCount, key, stream, &to)) != RM_OK) return st;
   const LightSplit ls = plan_light_split(ds, ss, fc, to, count, nw, numLights, W, nRows, tileShift, tileCount, shapeSlot >= 0, key, stream);
   Slot *slot;
-  st = stage_scene(cam, objs, numObjects, lights, numLights, g, s, stream, ds, &slot, res,
-                   to.ordered ? ((to.byCost || to.byGeom) ? to.order : nullptr) : ds.dbgTileOrder,
-                   to.ordered ? ((to.lastSort || to.settled) ? nullptr : to.cost) : ds.dbgTileCost,
-                   to.ordered ? tileCount : ds.dbgTileCount, tileShift, ls.tiles, ls.store);
-  if (st != RM_OK) return st;
-  if (to.byGeom && !slot->host->objBallOk) {  // an object without a bounding ball (Sierpinski, 2-D Mandelbrot as an object): raster order
-    to.byGeom = false;
-    slot->host->tileOrder = nullptr;
-    HIP_OK(hipMemcpyAsync(&slot->dev->tileOrder, &slot->host->tileOrder, sizeof(slot->host->tileOrder), hipMemcpyHostToDevice, stream));
-  }
+  if ((st = acquire_slot(ds.frames, 1, &slot)) != RM_OK) return st;
+  fill_frames(slot->host, 1, cam, g, 1, objs, numObjects, lights, numLights, s, res);
+  if (to.byGeom && !slot->host->objBallOk) to.byGeom = false;  // an object without a bounding ball (Sierpinski, 2-D Mandelbrot as an object): raster order
+  LaunchFields lf;
+  lf.tileOrder = to.ordered ? ((to.byCost || to.byGeom) ? to.order : nullptr) : ds.dbgTileOrder;
+  lf.tileCost = to.ordered ? ((to.lastSort || to.settled) ? nullptr : to.cost) : ds.dbgTileCost;
+  lf.tileCount = to.ordered ? tileCount : ds.dbgTileCount;
+  lf.tileShift = tileShift;
+  lf.splitTiles = ls.tiles; lf.splitStore = ls.store;
+  if ((st = upload_frames(*slot, 1, lf, stream)) != RM_OK) return st;
   unsigned long long *dc = ds.dCounters;
   if (count) {
     HIP_OK(hipMemsetAsync(dc, 0, 10 * sizeof(unsigned long long), stream));
     if (d_waveSpans) HIP_OK(hipMemcpyAsync(dc + 5, &d_waveSpans, sizeof(d_waveSpans), hipMemcpyHostToDevice, stream));
   }
-  // rm_set_timing: an event ahead of the launch, one after the ordering launches if they run, one after the render
-  TimedLaunch tl{};
-  const bool timing = g_timing.load();
-  // the events of a launch that fails part-way are destroyed on the way out (kept = handed to ds.timed below)
-  struct TimedGuard {
-    TimedLaunch &t; bool kept = false;
-    ~TimedGuard() { if (!kept) for (int i = 0; i < t.n; i++) (void)hipEventDestroy(t.ev[i]); }
-  } timedGuard{tl};
-  auto stamp = [&]() -> int {
-    if (!timing) return RM_OK;
-    HIP_OK(hipEventCreate(&tl.ev[tl.n]));
-    tl.n++;
-    HIP_OK(hipEventRecord(tl.ev[tl.n - 1], stream));
-    return RM_OK;
-  };
+  LaunchTimer timer(stream);
   const RenderLaunch r{slot->dev, map, W, H, nRows, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), dc, stream, rgrid, rblock};
   if (wf.on) {
     HIP_OK(hipMemsetAsync(wf.ws.counters, 0, WF_STRIDE * (kWfMaxBounces + 2) * sizeof(uint32_t), stream));
-    if ((st = stamp()) != RM_OK) return st;
+    if ((st = timer.stamp()) != RM_OK) return st;
     if (fc.wfSkip) launch_wavefront<true>(r, wf, fc.wfBounces, numLights, ds.numCUs);
     else launch_wavefront<false>(r, wf, fc.wfBounces, numLights, ds.numCUs);
   } else {
-    if ((st = stamp()) != RM_OK) return st;
+    if ((st = timer.stamp()) != RM_OK) return st;
     if (to.sorts()) {
       if ((st = launch_tile_order(to, r, nw * tileW, tileH, tileCount)) != RM_OK) return st;
-      if ((st = stamp()) != RM_OK) return st;  // stage 0 = the ordering launches, stage 1 = the render
+      if ((st = timer.stamp()) != RM_OK) return st;  // stage 0 = the ordering launches, stage 1 = the render
     }
     int splitSlot = ls.timedSlot;
     if ((st = ss.split.begin(splitSlot, stream)) != RM_OK || (st = ss.shape.begin(shapeSlot, stream)) != RM_OK) return st;
     if ((st = dispatch_render(fc, count, slot->host->bulbPlain != 0, ls, numLights, tileCount, r)) != RM_OK) return st;
     if ((st = ss.shape.end(shapeSlot, stream)) != RM_OK || (st = ss.split.end(splitSlot, stream)) != RM_OK) return st;
   }
-  if ((st = stamp()) != RM_OK) return st;
+  if ((st = timer.stamp()) != RM_OK) return st;
   HIP_OK(hipGetLastError());
   ds.lastPath = wf.on ? 5 : 1;
   ds.lastSplit = wf.on ? 0 : ls.tiles;
-  if (timing) { ds.timed.push_back(tl); timedGuard.kept = true; }
+  timer.keep(ds);
   HIP_OK(hipEventRecord(slot->done, stream));
   if (count) {
     unsigned long long hc[10];
@@ -1572,14 +1542,6 @@ int launch_render(const RmCamera *cam, const RmObject *objs, int numObjects, con
     }
     if (clockMHz) *clockMHz = hc[4] ? 100.0 * (double)hc[3] / (double)hc[4] : 0.0;
   }
-  return RM_OK;
-}
-// the device the calling thread has current
-int current_device_state(DeviceState **out) {
-  int dev = 0;
-  HIP_OK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
-  *out = &g_dev[dev];
   return RM_OK;
 }
 // the row map of the rows [rowBegin, rowEnd) of an H-row frame (rm_render*, rm_render_counted*)
@@ -1627,57 +1589,20 @@ int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals,
     }
   }
   if (anyBatched) {
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { set_error("device index out of range"); return RM_ERR_DEVICE; }
-    DeviceState &ds = g_dev[dev];
-    std::lock_guard<std::mutex> lock(ds.mu);  // nothing below waits for the GPU but acquire_batch_slot at its bounds
-    BatchSlot *b;
-    if ((st = acquire_batch_slot(ds, numFrames, &b)) != RM_OK) return st;
+    DeviceState *ds;
+    if ((st = current_device_state(&ds)) != RM_OK) return st;
+    std::lock_guard<std::mutex> lock(ds->mu);  // nothing below waits for the GPU but acquire_slot at the ring's bounds
+    Slot *b;
+    if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
+    fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
     const int pinned = tile_shape_request();
-    const int tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
-    // the shared parts once (frame 0's block), then per frame its camera, globals and what they decide
-    SceneBlock *h0 = b->host;
-    fill_scene(h0, &cams[0], objs, numObjects, lights, numLights, globalsOf(0), s, res);
-    h0->tileOrder = nullptr; h0->tileCost = nullptr; h0->tileCount = 0;
-    h0->tileShift = tileShift;
-    h0->splitTiles = 0; h0->splitStore = nullptr;
-    h0->mengerAni = 0.0f; h0->mengerOff = 0.0f;
-    bool bulbInTable = false, menger = false;
-    for (int i = 0; i < numObjects; i++) {
-      bulbInTable = bulbInTable || objs[i].type == RM_MANDELBULB;  // the only type whose cull bounds read the globals
-      menger = menger || objs[i].type == RM_MENGERSPONGE;
-    }
-    for (int f = 1; f < numFrames; f++) {
-      SceneBlock *h = b->host + f;
-      *h = *h0;
-      h->cam = cams[f];
-      h->g = *globalsOf(f);
-      if (bulbInTable && numGlobals > 1) scene_cull_ball(h);
-      ray_planes(h);
-      h->bulbPlain = bulb_plain(objs, numObjects, &h->g);
-    }
-    HIP_OK(hipMemcpyAsync(b->dev, b->host, (size_t)numFrames * sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
-    if (menger) {  // per frame, its own iTime; stream-ordered between the upload and the render
-      hipLaunchKernelGGL(scene_prep_batch_kernel, dim3((numFrames + 63) / 64), dim3(64), 0, stream, b->dev, numFrames);
-      HIP_OK(hipGetLastError());
-    }
+    LaunchFields lf;
+    lf.tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
+    if ((st = upload_frames(*b, numFrames, lf, stream)) != RM_OK) return st;
     const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
-    const int nw = waves_per_block(), tileW = 1 << tileShift, tileH = 64 >> tileShift;
-    TimedLaunch tl{};
-    const bool timing = g_timing.load();
-    struct TimedGuard {
-      TimedLaunch &t; bool kept = false;
-      ~TimedGuard() { if (!kept) for (int i = 0; i < t.n; i++) (void)hipEventDestroy(t.ev[i]); }
-    } timedGuard{tl};
-    auto stamp = [&]() -> int {
-      if (!timing) return RM_OK;
-      HIP_OK(hipEventCreate(&tl.ev[tl.n]));
-      tl.n++;
-      HIP_OK(hipEventRecord(tl.ev[tl.n - 1], stream));
-      return RM_OK;
-    };
-    if ((st = stamp()) != RM_OK) return st;
+    const int nw = waves_per_block(), tileW = 1 << lf.tileShift, tileH = 64 >> lf.tileShift;
+    LaunchTimer timer(stream);
+    if ((st = timer.stamp()) != RM_OK) return st;
     // one launch per run of consecutive batched frames (one run unless wavefront frames sit between them)
     for (int f0 = 0; f0 < numFrames;) {
       if (alone[f0]) { f0++; continue; }
@@ -1687,14 +1612,14 @@ int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals,
       const dim3 grid((W + nw * tileW - 1) / (nw * tileW), (H + tileH - 1) / tileH, (unsigned)(f1 - f0));
       const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba + f0 * frame),
                            d_bright ? reinterpret_cast<float4 *>(d_bright + f0 * frame) : nullptr, nullptr, stream, grid, dim3(64 * nw)};
-      dispatch_batch(fc, plainBulb, r);
+      dispatch_render<true>(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
       f0 = f1;
     }
-    if ((st = stamp()) != RM_OK) return st;
+    if ((st = timer.stamp()) != RM_OK) return st;
     HIP_OK(hipGetLastError());
-    ds.lastPath = 6;
-    ds.lastSplit = 0;
-    if (timing) { ds.timed.push_back(tl); timedGuard.kept = true; }
+    ds->lastPath = 6;
+    ds->lastSplit = 0;
+    timer.keep(*ds);
     HIP_OK(hipEventRecord(b->done, stream));
   }
   const RowMap whole{0, H, 0, 1, 0};
@@ -1703,6 +1628,23 @@ int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals,
                                         d_bright ? d_bright + f * frame : nullptr, stream, 0, nullptr, res)) != RM_OK)
       return st;
   return RM_OK;
+}
+
+// The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
+// device's block) behind it.
+template <class Launch>
+int probe_scene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, hipStream_t stream, Launch launch) {
+  DeviceState *ds;
+  if (int st = current_device_state(&ds)) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  Slot *slot;
+  if (int st = acquire_slot(ds->frames, 1, &slot)) return st;
+  const RmCamera cam{};
+  fill_frames(slot->host, 1, &cam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
+  if (int st = upload_frames(*slot, 1, LaunchFields{}, stream)) return st;
+  const int st = launch(slot->dev);
+  HIP_OK(hipEventRecord(slot->done, stream));
+  return st;
 }
 }  // namespace
 }  // namespace rm
@@ -1856,13 +1798,7 @@ int rm_deinterleave_rgba8(const uint8_t *d_gathered8, uint8_t *d_frame8, int W, 
 }
 
 int rm_frame_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, void *stream) {
-  if (!d_rgba || !d_out || W <= 0 || H <= 0) { set_error("bad frame arguments"); return RM_ERR_INVALID_ARGUMENT; }
-  if (int st = require_device_pointers({{"d_rgba", d_rgba}, {"d_out", d_out}})) return st;
-  dim3 grid((W + 255) / 256, H), block(256);
-  hipLaunchKernelGGL(to_rgba8_kernel, grid, block, 0, static_cast<hipStream_t>(stream),
-                     reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<uchar4 *>(d_out), W, H);
-  HIP_OK(hipGetLastError());
-  return RM_OK;
+  return rm_frames_to_rgba8(d_rgba, d_out, W, H, 1, stream);
 }
 
 int rm_frames_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, int numFrames, void *stream) {
@@ -2056,8 +1992,8 @@ int rm_release_workspaces(unsigned long long *freedBytes) {
   size_t freed = 0;
   if (int st = release_workspaces(&freed)) return st;
   for (auto &kv : ds->streams) { kv.second.shape.drop(); kv.second.split.drop(); }
-  for (auto &b : ds->batchSlots) { freed += (size_t)b.cap * sizeof(SceneBlock); free_batch_slot(b); }  // the device has drained
-  ds->batchSlots.clear();
+  for (Slot &b : ds->batches.slots) { freed += (size_t)b.cap * sizeof(SceneBlock); free_slot(b); }  // the device has drained
+  ds->batches.slots.clear();
   ds->streams.clear();  // with the tile-order state: the feedback costs lived in the buffers just freed
   ds->shapeChoice.clear();
   ds->splitChoice.clear();
@@ -2083,17 +2019,12 @@ int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, c
   if (!d_pts || !d_out || n < 0) { set_error("bad probe arguments"); return RM_ERR_INVALID_ARGUMENT; }
   if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st2;
   if (n == 0) return RM_OK;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
-  Slot *slot;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  st = stage_scene(&cam, objs, numObjects, nullptr, 0, g, s, hs, *ds, &slot, kNoResources);
-  if (st != RM_OK) return st;
-  hipLaunchKernelGGL(probe_sdscene_kernel, dim3((n + 255) / 256), dim3(256), 0, hs, slot->dev, d_pts, d_out, n);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(slot->done, hs));
-  return RM_OK;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) -> int {
+    hipLaunchKernelGGL(probe_sdscene_kernel, dim3((n + 255) / 256), dim3(256), 0, hs, sb, d_pts, d_out, n);
+    HIP_OK(hipGetLastError());
+    return RM_OK;
+  });
 }
 
 int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, int bulbClass,
@@ -2112,16 +2043,10 @@ int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGloba
   if (!d_pts || !d_out || n < 0) return bad("bad probe arguments");
   if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_ub", d_ub}, {"d_out", d_out}})) return st2;
   if (n == 0) return RM_OK;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
-  Slot *slot;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  st = stage_scene(&cam, objs, numObjects, nullptr, 0, g, s, hs, *ds, &slot, kNoResources);
-  if (st != RM_OK) return st;
-  st = launch_sdscene_variant(slot->dev, bulbClass, count, trap, skip, track, one, d_pts, d_ub, d_out, n, hs);
-  HIP_OK(hipEventRecord(slot->done, hs));
-  return st;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) {
+    return launch_sdscene_variant(sb, bulbClass, count, trap, skip, track, one, d_pts, d_ub, d_out, n, hs);
+  });
 }
 
 }  // extern "C"

@@ -303,15 +303,6 @@ __global__ void fxaa_kernel(const uchar4 *__restrict__ img, float4 *__restrict__
 
 using namespace rm;
 
-#define HIP_OK(expr)                                                                               \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) {                                                                        \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                                \
-      return RM_ERR_DEVICE;                                                                        \
-    }                                                                                              \
-  } while (0)
-
 namespace {
 
 // Frames per chunk of a batch: each frame of a chunk needs 20 B/pixel of the stream's post workspace (two binary16 ping-pong
@@ -333,7 +324,10 @@ int post_frames(const float *d_frag, const float *d_bright, float *d_out, int W,
                 int numPost, hipStream_t st) {
   const size_t n = (size_t)W * H;
   const int chunk = post_chunk_frames(numFrames, n);
-  // ping-pong + 8-bit staging images of THIS stream: post-processing frames on two streams never shares them
+  // ping-pong + 8-bit staging images of THIS stream: post-processing frames on two streams never shares them; the device's
+  // launcher lock keeps rm_release_workspaces from freeing them until the last pass is enqueued
+  std::unique_lock<std::mutex> lock;
+  if (int rc = lock_current_device(lock)) return rc;
   void *wsMem = nullptr;
   if (int rc = stream_workspace(kWsPost, st, (size_t)chunk * n * kPostBytesPerPixel, &wsMem)) return rc;
   half4 *pa = static_cast<half4 *>(wsMem), *pb = pa + chunk * n;

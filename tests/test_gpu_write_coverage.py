@@ -417,15 +417,16 @@ def test_frames_in_flight_on_three_streams(renderer):
         tg.assert_bit_equal(out.cpu().numpy(), want[name], f"{name}, frame {k}")
 
 
-# The two launch rings (acquire_slot, acquire_batch_slot) only grow, once per process: their cases run in a fresh child process,
+# Both launch rings of acquire_slot (single frames, batches) only grow, once per process: their cases run in a fresh child process,
 # and every launch is queued behind a gate — torch.cuda._sleep spinning the stream for GATE_CYCLES GPU clock cycles (tens of
 # milliseconds at least) — so that all of them are still in flight when the host has queued the last one.
 GATE_CYCLES = 50_000_000
 
 
 def ring_growth_case(renderer):
-    """One heavy frame behind the gate, then 14 small frames on the same stream: more launches in flight than the scene-block
-    ring's kSlotsInit = 8 slots, so acquire_slot grows the ring while its slots are busy.  Every frame is its own picture's."""
+    """One heavy frame behind the gate, then 14 small frames on the same stream: 15 launches in flight, so acquire_slot grows the
+    frames ring (it starts empty, a fresh slot in front of each busy one) while its slots are busy.  Every frame is its own
+    picture's."""
     import torch
     W, H = 1280, 720
     heavy = h.scene_mandelbulb(W, H)
@@ -452,7 +453,7 @@ def ring_growth_case(renderer):
 
 
 def batch_slot_case(renderer):
-    """Six batches behind the gate on one stream: the first four fill the batch ring (kBatchSlotsMax = 4, each busy slot gets a
+    """Six batches behind the gate on one stream: the first four fill the batch ring (at most 4 slots, each busy slot gets a
     fresh one in front of it), the fifth and sixth find every slot busy and wait for the oldest (hipEventSynchronize).  Then a
     40-frame batch, larger than the 16 scene blocks every slot of this process holds: the idle slot it lands on grows.  Every
     batch into its own guarded buffers."""
