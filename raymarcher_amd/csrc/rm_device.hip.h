@@ -133,6 +133,8 @@ struct SceneBlock {
   // evaluated ONCE per frame of a launch by scene_prep_batch_kernel with the contract's own sin / cos instead of once per evaluation
   // per lane (≈45 of the ≈230 vector instructions of a 5-level evaluation); only read when the table holds a Menger sponge.
   float mengerAni, mengerOff;
+  // The block's index in its slot (upload_frames): a production render kernel writes its frame from out + frame·nRows·W.
+  int32_t frame;
 };
 
 // Which frame row a launch's local row r is: a plain row range (numShards = 1) or the row tiles of one shard of a multi-GPU
@@ -1411,9 +1413,7 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // SEC = false compiles main's secondary rays out (reflection loop, refraction): the launcher picks it when the settings or the
 // materials rule them out for the whole frame, so that what render() hands over for them (hit point, normal, direction) is not
 // carried across the shadow marches — fewer registers spilled around the hot loops, the same pixels.
-// BATCH changes no code: it gives the batched render kernels (rm_render_batch) instantiations of their own, so that each
-// single-frame kernel stays the only caller of its shadePixel and compiles exactly as it does without the batched ones.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
   float ndcx, ndcy;

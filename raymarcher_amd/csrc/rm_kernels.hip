@@ -83,20 +83,28 @@ static_assert(RM_TILE_W == 4 || RM_TILE_W == 8 || RM_TILE_W == 16, "tile width: 
 #ifndef RM_TEX_WAVES
 #define RM_TEX_WAVES 6
 #endif
+// the register budget of a kernel class: the second launch bound of render_kernel
+constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
+  if (tex) return sec ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES;
+  if (env) return sec ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES;
+  if (bulb) return sec ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES;
+  return sec ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES;
+}
 // SPLIT ("light split", launch_render): 1 = the launch of a frame whose heaviest tiles are rendered one light per workgroup — a 1-D
 // grid: workgroups 0 … splitTiles·numLights − 1 are those tiles' partial workgroups (tile = tileOrder[b / numLights], light b mod
 // numLights: primary march, surface, THAT light's shadow march, its result to splitStore), the last of which to arrive finishes
 // the tile's pixels from the stored results (shadePixel's mode 2: no march); the rest render the other tiles whole.
-// BATCH (rm_render_batch, production kernels only): a (tilesX, tilesY, numFrames) grid over numFrames whole frames — frame
-// blockIdx.z reads SceneBlock sb[blockIdx.z] and writes nRows·W pixels from out + blockIdx.z·nRows·W (and bright likewise).
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
-__global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES) : (ENV ? (SEC ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES) : (BULB ? (SEC ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES) : (SEC ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES))))) void render_kernel(const SceneBlock *__restrict__ sb, RowMap map, int W, int H,
-                                                      int nRows, float4 *__restrict__ out,
-                                                      float4 *__restrict__ bright,
-                                                      unsigned long long *__restrict__ counters) {
+// The production kernels (COUNT = 0, no SPLIT) render a (tilesX, tilesY, numFrames) grid over numFrames whole frames — frame
+// blockIdx.z reads SceneBlock sb[blockIdx.z] and writes nRows·W pixels from out + sb->frame·nRows·W (and bright likewise; the
+// block's own index, so that blockIdx.z is not live across the kernel).  A single frame (launch_render) is a grid of one frame;
+// rm_render_batch launches the same kernels over many.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+__global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render_kernel(
+    const SceneBlock *__restrict__ sb, RowMap map, int W, int H, int nRows, float4 *__restrict__ out, float4 *__restrict__ bright,
+    unsigned long long *__restrict__ counters) {
   constexpr int CM = (COUNT == 3) ? 0 : COUNT;  // counting mode of the device code
-  static_assert(!BATCH || (COUNT == 0 && SPLIT == 0), "batched launches are production launches");
-  if (BATCH) sb += blockIdx.z;  // wave-uniform: the frame's own scene block
+  constexpr bool FRAMES = COUNT == 0 && SPLIT == 0;  // the production kernels: frame blockIdx.z of the grid
+  if (FRAMES) sb += blockIdx.z;  // wave-uniform: the frame's own scene block
   unsigned long long t0 = 0, r0 = 0;
   if (COUNT == 3) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
   // LDS copy of the object table for per-lane (divergent) material lookups; the single-bulb class reads one entry.
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVE
   V4 col, br;
   Counters cnt{0, 0, 0, 0, 0, 0};
   bool hit;
-  shadePixel<BULB, CM, ENV, TEX, SEC, SPLIT, BATCH>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
+  shadePixel<BULB, CM, ENV, TEX, SEC, SPLIT>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
   if (SPLIT == 1 && split.part >= 0) {
     // A partial workgroup: its results are in memory.  The LAST of the tile's numLights workgroups to get here finishes the tile —
     // surface point, AO and the light sum from the stored results, no march (shadePixel in mode 2) — the others are done.  Release /
@@ -160,8 +168,8 @@ __global__ __launch_bounds__(256, (TEX ? (SEC ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVE
     split.part = -1;
     shadePixel<BULB, CM, ENV, TEX, SEC, 2>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
   }
-  if (BATCH) {
-    const size_t f = (size_t)blockIdx.z * (size_t)nRows * (size_t)W;
+  if (FRAMES) {
+    const size_t f = (size_t)sb->frame * (size_t)nRows * (size_t)W;
     out += f;
     if (bright) bright += f;
   }
@@ -1069,6 +1077,7 @@ int upload_frames(const Slot &slot, int n, const LaunchFields &lf, hipStream_t s
     h->tileShift = lf.tileShift;
     h->splitTiles = lf.splitTiles; h->splitStore = lf.splitStore;
     h->mengerAni = 0.0f; h->mengerOff = 0.0f;
+    h->frame = f;
   }
   HIP_OK(hipMemcpyAsync(slot.dev, slot.host, (size_t)n * sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
   bool menger = false;
@@ -1366,15 +1375,15 @@ void launch_wavefront(const RenderLaunch &r, const Wavefront &wf, int bounces, i
 // render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>: the bulb class and the generic table walk, plain and counted, without
 // procedural layers or textures; the generic kernel with either or both.  Features a launch does not need are compiled out so the
 // common kernels keep their register budget.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool BATCH = false>
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
 void launch_kernel(const RenderLaunch &r) {
-  hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT, BATCH>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
+  hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
 }
 // a production launch: the secondary rays compiled in only where they can fire
-template <int BULB, bool ENV, bool TEX, bool BATCH = false>
+template <int BULB, bool ENV, bool TEX>
 void launch_production(bool secondary, const RenderLaunch &r) {
-  if (secondary) launch_kernel<BULB, 0, ENV, TEX, true, 0, BATCH>(r);
-  else launch_kernel<BULB, 0, ENV, TEX, false, 0, BATCH>(r);
+  if (secondary) launch_kernel<BULB, 0, ENV, TEX, true>(r);
+  else launch_kernel<BULB, 0, ENV, TEX, false>(r);
 }
 // the counted (1: reference work, 2: executed work) and clock-stamped (3) launches
 template <int BULB>
@@ -1384,24 +1393,23 @@ void launch_counted(int count, const RenderLaunch &r) {
   else launch_kernel<BULB, 3, false, false>(r);
 }
 // the layer / sampler kernels: their counting instantiations count the reference's work only (they have no shortcuts to count apart)
-template <bool ENV, bool TEX, bool BATCH>
+template <bool ENV, bool TEX>
 void launch_layered(int count, bool secondary, const RenderLaunch &r) {
   if (count) launch_kernel<0, 1, ENV, TEX>(r);
-  else launch_production<0, ENV, TEX, BATCH>(secondary, r);
+  else launch_production<0, ENV, TEX>(secondary, r);
 }
-// BATCH: the batched production kernels (rm_render_batch, one class for every frame of the launch), which a batch reaches with
-// count = 0 and no light split; the counted and split kernels exist for single frames only.
-template <bool BATCH = false>
+// A batch (rm_render_batch, one class for every frame of the launch) comes with count = 0 and no light split, so it reaches only
+// the production kernels; the counted and split kernels render single frames.
 int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const LightSplit &ls, int numLights, int tileCount,
                     const RenderLaunch &r) {
-  if (fc.envFeatures && fc.textured) launch_layered<true, true, BATCH>(count, fc.secondary, r);
-  else if (fc.envFeatures) launch_layered<true, false, BATCH>(count, fc.secondary, r);
-  else if (fc.textured) launch_layered<false, true, BATCH>(count, fc.secondary, r);
+  if (fc.envFeatures && fc.textured) launch_layered<true, true>(count, fc.secondary, r);
+  else if (fc.envFeatures) launch_layered<true, false>(count, fc.secondary, r);
+  else if (fc.textured) launch_layered<false, true>(count, fc.secondary, r);
   else if (fc.bulb) {
     // the counted launches keep the general form; the production ones take the plain form where the launcher found it
     if (count) launch_counted<kBulbGeneral>(count, r);
-    else if (plainBulb) launch_production<kBulbPlain, false, false, BATCH>(fc.secondary, r);
-    else launch_production<kBulbGeneral, false, false, BATCH>(fc.secondary, r);
+    else if (plainBulb) launch_production<kBulbPlain, false, false>(fc.secondary, r);
+    else launch_production<kBulbGeneral, false, false>(fc.secondary, r);
   } else if (count) launch_counted<0>(count, r);
   else if (!fc.secondary && ls.tiles > 0) {
     // light split: the heavy tiles one light per workgroup first, every other tile behind them in the same grid; the last of a
@@ -1412,7 +1420,7 @@ int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const Light
     split.grid = dim3((unsigned)(ls.tiles * numLights + tileCount - ls.tiles));
     split.block = dim3(64);
     launch_kernel<0, 0, false, false, false, 1>(split);
-  } else launch_production<0, false, false, BATCH>(fc.secondary, r);
+  } else launch_production<0, false, false>(fc.secondary, r);
   return RM_OK;
 }
 
@@ -1610,9 +1618,9 @@ int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals,
       while (f1 < numFrames && !alone[f1]) f1++;
       const RowMap map{0, H, 0, 1, 0};
       const dim3 grid((W + nw * tileW - 1) / (nw * tileW), (H + tileH - 1) / tileH, (unsigned)(f1 - f0));
-      const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba + f0 * frame),
-                           d_bright ? reinterpret_cast<float4 *>(d_bright + f0 * frame) : nullptr, nullptr, stream, grid, dim3(64 * nw)};
-      dispatch_render<true>(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
+      const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), nullptr,
+                           stream, grid, dim3(64 * nw)};
+      dispatch_render(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
       f0 = f1;
     }
     if ((st = timer.stamp()) != RM_OK) return st;
