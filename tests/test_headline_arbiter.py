@@ -106,8 +106,9 @@ TABLE_SCENES = ['cubemap/beach', 'lighting/depth_of_field', 'lighting/directiona
 def test_tables_of_primitives_against_the_independent_arbiter(name):
     """C2's class (round 4, late), transcribed independently (arbiter_numpy.render_frame_table): sdScene over a table, all nine
     primitives of sdMatch, softshadow's penumbra factor (UB1), calcAO and getPhong with directional, point and spot lights — on the
-    GEOMETRY AND LIGHTS of every scenefile of the reference that holds nothing else (38 of its 52; their textures switched off: the
-    samplers are not transcribed), soft shadows + ambient occlusion on, C2's own `directional_light_2.json` also with hard shadows.
+    GEOMETRY AND LIGHTS of every scenefile of the reference that holds nothing else (38 of its 52; their textures switched off here:
+    the textured frames, sky box and area lights are held by tests/test_resource_arbiter.py), soft shadows + ambient occlusion on,
+    C2's own `directional_light_2.json` also with hard shadows.
     The two binary64 transcriptions agree to 1e-6 on EVERY pixel (measured ≤ 5.1e-7); the binary32 oracle is within the north star's
     1e-3 of them on ≥ 99.9 % of the pixels (measured ≥ 99.98 %: one or two silhouette pixels in six of the scenes)."""
     t = Scene(path=os.path.join(GOLD, "scenes", name + ".json")).tables(W, H, load_textures=False)
