@@ -245,6 +245,32 @@ int rm_render_batch(const RmCamera *cams, const RmGlobals *globals, int numGloba
                     int H, float *d_rgba, float *d_bright, void *stream);
 
 /*
+ * rm_render_supersampled — rm_render_batch with ss × ss samples per pixel, resolved inside the render kernel (no reference
+ * counterpart: the reference's only anti-aliasing is FXAA, a blur over the finished 8-bit image).  The shape and every rule of
+ * rm_render_batch — one scene, cams[f] and globals[f] (or globals[0]) per frame, numFrames == 1 for a still, numFrames·H·W float4
+ * per output with rows bottom-up, d_bright may be NULL, asynchronous on `stream`, host arrays copied before return — plus `ss`,
+ * the samples per pixel along each axis: 1, 2 or 4.  ss == 1 is rm_render_batch, exactly.
+ * Definition of a pixel.  Let S be the frame rm_render_res writes for the same camera, globals, tables and settings at
+ * ss·W × ss·H: sample (i, j) of output pixel (X, Y) is pixel (ss·X + i, ss·Y + j) of S.  fragColor and BrightColor, all four
+ * channels, are reduced over the pixel's ss × ss block of S by a fixed tree of binary32 round-to-nearest adds (denormals kept),
+ * one level of which is: x pairs first, a(x, y) = S(2x, y) + S(2x + 1, y), then y pairs, b(x, y) = a(x, 2y) + a(x, 2y + 1).
+ * ss = 2 applies one level, ss = 4 applies the level twice (to S, then to its result); the sum is then multiplied by
+ * 1.0f / (ss·ss) (0.25f or 0.0625f).  In NumPy, on float32 arrays: a = S[:, 0::2] + S[:, 1::2]; b = a[0::2] + a[1::2], repeated
+ * for ss = 4, then b * np.float32(1 / ss**2).  The result is defined bit for bit; no ss·W × ss·H image exists in memory.
+ * RM_ERR_INVALID_ARGUMENT: ss not 1, 2 or 4; ss·W or ss·H above INT_MAX / 8, or more samples than one launch can index (more
+ * than 65535 rows of 8×8 sample tiles, or more than INT_MAX tiles per frame); everything rm_render_batch refuses, with its codes
+ * (numFrames > RM_MAX_BATCH_FRAMES: RM_ERR_CAPACITY; numFrames == 0: RM_OK).  All of these are checked before any HIP call.
+ * Schedule: ONE launch of the supersampling kernel over every frame (rm_debug_last_path() = 7, rm_debug_last_split() = 0), 8×8
+ * sample tiles in raster order: no wavefront pipeline (rm_set_kernel_path is not consulted), no light split, no tile-shape pin, no
+ * library workspace; it uses the batch ring of scene blocks (one block per frame, not per sample) and neither reads nor changes
+ * the per-stream tuner and tile-order state of single-frame renders.  With rm_set_timing(1) it counts as one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_render_supersampled(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                           int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res,
+                           int W, int H, int ss, float *d_rgba, float *d_bright, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -358,7 +384,8 @@ int rm_get_timing(double *avgKernelMs, int *launches);
 /* Same, split by role, both averaged over ALL the launches (total = stage 0 + stage 1): stage 1 = the render (the one-lane-per-pixel
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
- * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own).
+ * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
+ * launch of rm_render_supersampled.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -385,7 +412,8 @@ int rm_set_kernel_path(int path);
 int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
- * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel (not a value rm_set_kernel_path takes). */
+ * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
+ * with ss > 1 (neither is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -49,7 +49,47 @@ int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 bool sdscene_variant_exists(int bulbClass, int count, int trap, int skip, int track, bool one);
 int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, int skip, int track, int one, const float *d_pts,
                            const float *d_ub, float *d_out, int n, hipStream_t stream);
+// The supersampling kernels (rm_supersample.hip, rm_render_supersampled): the launch of render_ss_kernel<bulbClass, env, tex, sec>
+// over the staged SceneBlocks `sb` (device pointer; one per frame of grid.z), W × H output pixels of ss × ss samples each.  A
+// translation unit of its own, so that the code objects of rm_kernels.hip do not depend on it.
+int launch_render_ss(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
+                     float *d_rgba, float *d_bright, hipStream_t stream);
 #endif
+// ---- register budgets of the render kernels (rm_kernels.hip has the measurements; -DRM_*_WAVES=n overrides) --------------------
+#ifndef RM_GENERIC_WAVES
+#define RM_GENERIC_WAVES 6
+#endif
+#ifndef RM_BULB_WAVES
+#define RM_BULB_WAVES 5
+#endif
+// the instantiations without main's secondary rays (SEC = false: no reflection / refraction anywhere in the frame) need far fewer
+// registers — the bulb kernel 90 without a single spill — and take their own budgets (profiles/r04_d_secondary_rays.md)
+#ifndef RM_BULB_NOSEC_WAVES
+#define RM_BULB_NOSEC_WAVES 6
+#endif
+#ifndef RM_GENERIC_NOSEC_WAVES
+#define RM_GENERIC_NOSEC_WAVES 6
+#endif
+#ifndef RM_ENV_NOSEC_WAVES
+#define RM_ENV_NOSEC_WAVES 6
+#endif
+#ifndef RM_TEX_NOSEC_WAVES
+#define RM_TEX_NOSEC_WAVES 6
+#endif
+#ifndef RM_ENV_WAVES
+#define RM_ENV_WAVES 6
+#endif
+#ifndef RM_TEX_WAVES
+#define RM_TEX_WAVES 6
+#endif
+// the register budget of a kernel class: the second launch bound of render_kernel
+constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
+  if (tex) return sec ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES;
+  if (env) return sec ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES;
+  if (bulb) return sec ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES;
+  return sec ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES;
+}
+
 // The largest single workspace buffer stream_workspace may allocate, 0 = no limit (rm_set_workspace_limit).
 unsigned long long workspace_limit();
 

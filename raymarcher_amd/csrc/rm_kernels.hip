@@ -57,39 +57,7 @@ static_assert(RM_TILE_W == 4 || RM_TILE_W == 8 || RM_TILE_W == 16, "tile width: 
 // scene gains 26 %, bump + reflection 28 %, textured / sky-box scenes 83-90 %, the 8K Menger frame 18 %, the terrain and
 // sea frames 5-7 %, the headline bulb frame 2.3 % (5 waves; its hot loops stay spill-free).  Re-tuned on the final code: 6 / 5 / 6 / 6.  Frames too small to fill the
 // chip (256x256, 1080p tails) lose 1-2 %.  -DRM_*_WAVES=n overrides, for the experiment script scripts/gpu_variants.sh.
-#ifndef RM_GENERIC_WAVES
-#define RM_GENERIC_WAVES 6
-#endif
-#ifndef RM_BULB_WAVES
-#define RM_BULB_WAVES 5
-#endif
-// the instantiations without main's secondary rays (SEC = false: no reflection / refraction anywhere in the frame) need far fewer
-// registers — the bulb kernel 90 without a single spill — and take their own budgets (profiles/r04_d_secondary_rays.md)
-#ifndef RM_BULB_NOSEC_WAVES
-#define RM_BULB_NOSEC_WAVES 6
-#endif
-#ifndef RM_GENERIC_NOSEC_WAVES
-#define RM_GENERIC_NOSEC_WAVES 6
-#endif
-#ifndef RM_ENV_NOSEC_WAVES
-#define RM_ENV_NOSEC_WAVES 6
-#endif
-#ifndef RM_TEX_NOSEC_WAVES
-#define RM_TEX_NOSEC_WAVES 6
-#endif
-#ifndef RM_ENV_WAVES
-#define RM_ENV_WAVES 6
-#endif
-#ifndef RM_TEX_WAVES
-#define RM_TEX_WAVES 6
-#endif
-// the register budget of a kernel class: the second launch bound of render_kernel
-constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
-  if (tex) return sec ? RM_TEX_WAVES : RM_TEX_NOSEC_WAVES;
-  if (env) return sec ? RM_ENV_WAVES : RM_ENV_NOSEC_WAVES;
-  if (bulb) return sec ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES;
-  return sec ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES;
-}
+// The budgets themselves (RM_*_WAVES, render_waves) are in rm_internal.h: the supersampling kernels of rm_supersample.hip take the same.
 // SPLIT ("light split", launch_render): 1 = the launch of a frame whose heaviest tiles are rendered one light per workgroup — a 1-D
 // grid: workgroups 0 … splitTiles·numLights − 1 are those tiles' partial workgroups (tile = tileOrder[b / numLights], light b mod
 // numLights: primary march, surface, THAT light's shadow march, its result to splitStore), the last of which to arrive finishes
@@ -1638,6 +1606,58 @@ int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals,
   return RM_OK;
 }
 
+// ---- supersampled frames: ss × ss samples per pixel, resolved in the wave (render_ss_kernel) -----------------------------------
+// rm_render_supersampled.  A batch's shape and staging (the batch ring, fill_frames, upload_frames: one scene block per frame, not
+// per sample), ONE launch over (tilesX, tilesY, numFrames) 8×8 sample tiles in raster order for every frame: no wavefront pipeline,
+// no light split, no tile-shape pin, no tuner or tile-order state read or written, no library workspace.
+int launch_supersampled(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                        int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H,
+                        int ss, float *d_rgba, float *d_bright, hipStream_t stream) {
+  // every argument check ahead of the first HIP call (as launch_batch's)
+  if (ss != 1 && ss != 2 && ss != 4) { set_error("ss (samples per pixel along each axis) must be 1, 2 or 4"); return RM_ERR_INVALID_ARGUMENT; }
+  if (ss == 1) return launch_batch(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res, W, H, d_rgba, d_bright, stream);
+  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (numFrames == 0) return RM_OK;
+  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W > INT_MAX / 8 / ss || H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
+  // the kernel's sample coordinates are 32-bit and come from blockIdx: a grid's y extent is at most 65535 tiles, and the tiles of
+  // one frame stay countable in an int (as render_kernel's)
+  const int nw = waves_per_block();
+  const long long tilesX = ((long long)ss * W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * H + 7) / 8;
+  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
+  if (st != RM_OK) return st;
+  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
+  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
+  bool plainBulb = true;
+  for (int f = 0; f < numFrames; f++) plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);  // nothing below waits for the GPU but acquire_slot at the ring's bounds
+  Slot *b;
+  if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
+  fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
+  if ((st = upload_frames(*b, numFrames, LaunchFields{}, stream)) != RM_OK) return st;
+  const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
+  LaunchTimer timer(stream);
+  if ((st = timer.stamp()) != RM_OK) return st;
+  const dim3 grid((unsigned)tilesX, (unsigned)tilesY, (unsigned)numFrames), block(64 * nw);
+  // the class set of launch_production and nothing more; the kernels are a translation unit of their own (rm_supersample.hip)
+  const int bulbClass = (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
+  if ((st = launch_render_ss(b->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, grid, block, W, H, ss, d_rgba, d_bright, stream)) != RM_OK) return st;
+  if ((st = timer.stamp()) != RM_OK) return st;
+  HIP_OK(hipGetLastError());
+  ds->lastPath = 7;
+  ds->lastSplit = 0;
+  timer.keep(*ds);
+  HIP_OK(hipEventRecord(b->done, stream));
+  return RM_OK;
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1700,6 +1720,13 @@ int rm_render_batch(const RmCamera *cams, const RmGlobals *globals, int numGloba
                     float *d_bright, void *stream) {
   return launch_batch(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
                       d_rgba, d_bright, static_cast<hipStream_t>(stream));
+}
+
+int rm_render_supersampled(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                           int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W,
+                           int H, int ss, float *d_rgba, float *d_bright, void *stream) {
+  return launch_supersampled(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
+                             W, H, ss, d_rgba, d_bright, static_cast<hipStream_t>(stream));
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

@@ -1,0 +1,97 @@
+// rm_supersample.hip — the kernels of rm_render_supersampled (gfx950 only): the per-pixel raymarch of rm_kernels.hip with ss × ss
+// samples per output pixel, resolved inside the wave.  The launcher (argument checks, staging, schedule) is launch_supersampled in
+// rm_kernels.hip; the kernels live here so that adding them leaves the code objects of the existing kernels as they were.
+#include <hip/hip_runtime.h>
+
+#include "rm_device.hip.h"
+#include "rm_internal.h"
+
+namespace rm {
+
+// The value of lane (lane ^ MASK) for the four masks of the resolve, without LDS traffic where DPP reaches: ^ 1 and ^ 2 are quad
+// permutes, ^ 8 is a rotation by 8 within a row of 16 lanes, ^ 16 a ds_swizzle in bit-mask mode (and 0x1f, or 0, xor 0x10).  The
+// source lane must be active (render_ss_kernel's invariant on edge lanes).
+template <int MASK>
+RM_DEV float xorLane(float f) {
+  static_assert(MASK == 1 || MASK == 2 || MASK == 8 || MASK == 16, "lane masks of the 8×8 tile's butterfly");
+  const int u = __float_as_int(f);
+  if (MASK == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, u, 0xB1, 0xF, 0xF, true));   // quad_perm:[1,0,3,2]
+  if (MASK == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, u, 0x4E, 0xF, 0xF, true));   // quad_perm:[2,3,0,1]
+  if (MASK == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, u, 0x128, 0xF, 0xF, true));  // row_ror:8
+  return __int_as_float(__builtin_amdgcn_ds_swizzle(u, 0x401F));
+}
+// One level of the tree on the eight channels: x pairs, S(2x, y) + S(2x + 1, y), then y pairs, a(x, 2y) + a(x, 2y + 1).
+template <int LEVEL>
+RM_DEV void reduceLevel(float (&v)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) v[k] += xorLane<LEVEL>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 8; k++) v[k] += xorLane<8 * LEVEL>(v[k]);
+}
+
+// rm_render_supersampled: ss × ss samples per output pixel (ss = 2 or 4), resolved inside the wave that rendered them.  Sample
+// (x, y) is pixel (x, y) of the ss·W × ss·H frame of the same camera — the unchanged shadePixel — and a wave's tile is always 8×8
+// samples, lane = ly·8 + lx, i.e. 4×4 (ss = 2) or 2×2 (ss = 4) whole output pixels: the resolve needs no memory and no second
+// kernel.  The reduction is the fixed tree of the header (x pairs, then y pairs, once or twice, then · 1 / ss²) as a butterfly:
+// the binary32 add is commutative, so after `v += xorLane<1>(v)` both lanes of an x pair hold the same bits, after
+// `v += xorLane<8>(v)` all four lanes of a 2×2 block do, and lane ^ 2, lane ^ 16 repeat that one level up.  Production only
+// (no counters, no light split), raster tile order straight from blockIdx: the launch fields of the scene block are not read.
+template <int BULB, bool ENV, bool TEX, bool SEC>
+__global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render_ss_kernel(
+    const SceneBlock *__restrict__ sb, int W, int H, int ss, float4 *__restrict__ out, float4 *__restrict__ bright) {
+  sb += blockIdx.z;  // wave-uniform: the frame's own scene block
+  __shared__ RmObject s_objs[BULB ? 1 : RM_MAX_OBJECTS];
+  {
+    const int nd = sb->numObjects * (int)(sizeof(RmObject) / 4);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sb->objs);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(s_objs);
+    for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
+  }
+  if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int sW = W * ss, sH = H * ss;  // the sample frame
+  const int x = ((int)blockIdx.x * (int)(blockDim.x >> 6) + wave) * 8 + (lane & 7);
+  const int y = (int)blockIdx.y * 8 + (lane >> 3);
+  // Edge lanes leave before the cross-lane reads below, which is safe because of this invariant: ss divides 8 and tile origins are
+  // multiples of 8, so an output pixel's ss × ss lanes lie in one wave, and sW, sH are multiples of ss, so those lanes are either
+  // all inside the sample frame or all past its edge.  Every lane that stays reads only lanes of its own block, all of which stay.
+  if (x >= sW || y >= sH) return;
+  V4 col, br;
+  Counters cnt{0, 0, 0, 0, 0, 0};
+  bool hit;
+  shadePixel<BULB, 0, ENV, TEX, SEC, 0>(sb, s_objs, x, y, sW, sH, col, br, cnt, hit);
+  float v[8] = {col.x, col.y, col.z, col.w, br.x, br.y, br.z, br.w};
+  reduceLevel<1>(v);               // lanes ^ 1, ^ 8: the 2×2 blocks of S
+  if (ss == 4) reduceLevel<2>(v);  // wave-uniform; lanes ^ 2, ^ 16: the 2×2 blocks of the first level's result
+  if ((x & (ss - 1)) | (y & (ss - 1))) return;  // one lane per output pixel stores
+  const float scale = ss == 2 ? 0.25f : 0.0625f;
+  const size_t o = ((size_t)sb->frame * (size_t)H + (size_t)(y / ss)) * (size_t)W + (size_t)(x / ss);
+  out[o] = make_float4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale);
+  if (bright) bright[o] = make_float4(v[4] * scale, v[5] * scale, v[6] * scale, v[7] * scale);
+}
+
+namespace {
+template <int BULB, bool ENV, bool TEX>
+void launch_ss(bool sec, dim3 grid, dim3 block, hipStream_t stream, const SceneBlock *sb, int W, int H, int ss, float4 *o, float4 *b) {
+  if (sec) hipLaunchKernelGGL((render_ss_kernel<BULB, ENV, TEX, true>), grid, block, 0, stream, sb, W, H, ss, o, b);
+  else hipLaunchKernelGGL((render_ss_kernel<BULB, ENV, TEX, false>), grid, block, 0, stream, sb, W, H, ss, o, b);
+}
+}  // namespace
+
+// The class set of launch_production (rm_kernels.hip) and nothing more: the secondary rays compiled in only where they can fire.
+int launch_render_ss(const void *sbv, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
+                     float *d_rgba, float *d_bright, hipStream_t stream) {
+  const SceneBlock *sb = static_cast<const SceneBlock *>(sbv);
+  float4 *o = reinterpret_cast<float4 *>(d_rgba), *b = reinterpret_cast<float4 *>(d_bright);
+  if (env && tex) launch_ss<0, true, true>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  else if (env) launch_ss<0, true, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  else if (tex) launch_ss<0, false, true>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  else if (bulbClass == kBulbPlain) launch_ss<kBulbPlain, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  else if (bulbClass == kBulbGeneral) launch_ss<kBulbGeneral, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  else launch_ss<0, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+
+}  // namespace rm

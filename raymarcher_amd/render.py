@@ -294,6 +294,25 @@ class Renderer:
                                     C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
+    def render_supersampled(self, tables, settings, W, H, cameras, ss, globals_=None, bright=False, out=None, out_bright=None):
+        """rm_render_supersampled: render_batch with ss × ss samples per pixel (ss = 1, 2 or 4), resolved inside the kernel by the
+        fixed reduction tree of include/raymarcher_amd.h → float32 tensor (N, H, W, 4), row 0 = bottom.  Every other argument as
+        render_batch's; ss = 1 is render_batch."""
+        if ss not in (1, 2, 4):
+            raise ValueError(f"ss = {ss!r}: the samples per pixel along each axis are 1, 2 or 4")
+        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
+        n = len(cameras)
+        shape = (n, H, W, 4)
+        t = self.torch
+        out = self._out(out, shape, t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_render_supersampled(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights,
+                                           tables.num_lights, C.byref(settings), C.byref(res), W, H, ss, C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
+        return (out, br) if bright else out
+
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
         what the production kernel really executes (RM_COUNT_EXECUTED; plain scene classes only)."""
@@ -406,13 +425,17 @@ class Renderer:
         check(lib().rm_frames_to_rgba8(C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()), W, H, n, self._stream()))
         return out
 
-    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None):
+    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1):
         """The finished images of an exported sequence: render_batch (with the BrightColor planes only when bloom is on), then
         post_process_batch in place (skipped for post=None), then to_rgba8_batch → uint8 (N, H, W, 4), each image's top row
-        first.  post: one RmPostSettings or a sequence of N (see post_process_batch)."""
+        first.  post: one RmPostSettings or a sequence of N (see post_process_batch).  supersample = 2 or 4: the render step is
+        render_supersampled with that many samples per pixel along each axis (bloom then sees the resolved BrightColor)."""
         ps = post_array(post, len(cameras)) if post is not None else None
         bloom = ps is not None and bool(ps[0].enableBloom)
-        frames = self.render_batch(tables, settings, W, H, cameras, globals_, bright=bloom)
+        if supersample == 1:
+            frames = self.render_batch(tables, settings, W, H, cameras, globals_, bright=bloom)
+        else:
+            frames = self.render_supersampled(tables, settings, W, H, cameras, supersample, globals_, bright=bloom)
         brights = None
         if bloom:
             frames, brights = frames
