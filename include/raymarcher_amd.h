@@ -271,6 +271,45 @@ int rm_render_supersampled(const RmCamera *cams, const RmGlobals *globals, int n
                            int W, int H, int ss, float *d_rgba, float *d_bright, void *stream);
 
 /*
+ * rm_render_adaptive — rm_render_supersampled for the pixels that show contrast, rm_render_batch for the rest (no reference
+ * counterpart).  The shape and every rule of rm_render_supersampled — one scene, cams[f] and globals[f] (or globals[0]) per frame,
+ * numFrames·H·W float4 per output with rows bottom-up, d_bright may be NULL, asynchronous on `stream`, host arrays copied before
+ * return, ss = 1, 2 or 4 — plus a threshold and two optional outputs.
+ * Definition of a pixel.  For frame f let F, Fb be the fragColor / BrightColor that rm_render_batch writes for it at W×H, and R,
+ * Rb what rm_render_supersampled writes for it at the same W×H and ss (for ss = 1: R = F).  M(X, Y) is true iff for some
+ * 4-neighbour N of (X, Y) inside the frame (left, right, below, above; border pixels have fewer) and some channel c of r, g, b of
+ * fragColor: not (|F(X,Y).c − F(N).c| <= threshold), the subtraction one binary32 round-to-nearest operation, denormals kept.
+ * Written with "not <=" so that a NaN difference flags the pixel.  Alpha and BrightColor are not looked at.  The relation is
+ * symmetric: both pixels of a contrasting pair are flagged.  Then out(X, Y) = M ? R : F and bright(X, Y) = M ? Rb : Fb, all four
+ * channels, bit for bit.  In NumPy on the float32 frame, c = F[..., :3]: dx = (~(abs(c[:, 1:] − c[:, :-1]) <= thr)).any(-1), the
+ * same for rows, and each of dx, dy OR-ed into both pixels it separates.
+ * d_mask (NULL, or numFrames·H·W bytes, frame-major, rows bottom-up) receives 1 where M, 0 elsewhere; d_refined (NULL, or
+ * numFrames 32-bit words) receives the number of flagged pixels of each frame.  Both are device-accessible memory.
+ * threshold: any value but NaN.  +inf flags nothing (unless a difference is NaN): the output is rm_render_batch's.  A negative
+ * value flags every pixel of a frame larger than 1×1: the output is rm_render_supersampled's.  A 1×1 frame has no neighbour and is
+ * never flagged.  The result does not depend on the order in which flagged pixels are refined.
+ * RM_ERR_INVALID_ARGUMENT: threshold NaN; more than INT_MAX pixels per frame; everything rm_render_supersampled refuses, with its
+ * codes (ss not 1, 2 or 4, the size limits — for ss = 1 too —, numFrames < 0, null arrays, numGlobals; numFrames >
+ * RM_MAX_BATCH_FRAMES: RM_ERR_CAPACITY; numFrames == 0: RM_OK); d_mask or d_refined not device-accessible.  All of these but the
+ * device-pointer checks are made before any HIP call.
+ * Schedule: rm_debug_last_path() = 8, rm_debug_last_split() = 0.  Per chunk of frames three steps on `stream`: the
+ * one-lane-per-pixel kernel as rm_render_batch launches it (raster order, 8×8 tiles) into the outputs, a classify kernel (mask,
+ * lists of flagged pixels, counts), and for ss > 1 a refine kernel that supersamples the listed pixels and overwrites them.  No
+ * wavefront pipeline (rm_set_kernel_path is not consulted), no light split, no tile-shape pin, no tile order; the per-stream tuner
+ * and tile-order state of single-frame renders is neither read nor changed.  One slot of the batch ring holds the scene blocks of
+ * the whole call.  No host synchronisation and no read-back inside the call: the number of flagged pixels stays on the device.
+ * Workspace: per (device, stream) a grow-only list of 4 B per pixel of a chunk and a block of counters; frames go through the
+ * three steps in chunks of k = min(numFrames, max(1, cap / (4·W·H))) frames, cap = the rm_set_workspace_limit value when set, else
+ * 256 MiB (the rule of rm_post_process_batch).  A single frame over a set limit: RM_ERR_DEVICE.  rm_release_workspaces frees it.
+ * With rm_set_timing(1) the whole call counts as one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_render_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                       int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W,
+                       int H, int ss, float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined,
+                       void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -385,7 +424,7 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled.
+ * launch of rm_render_supersampled, and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -399,7 +438,8 @@ int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches)
  * frame incl. frames without tile-order history — profiles/r04_b_bulb_paths.md — and removed in round 4; the numbers are refused.) */
 int rm_set_kernel_path(int path);
 /* Scratch memory the library owns.  Everything the schedules need beyond the caller's frame lives in grow-only buffers per
- * (device, stream): 8 B per tile for the tile-order feedback, the post passes' ping-pong images, and — by far the largest —
+ * (device, stream): 8 B per tile for the tile-order feedback, the post passes' ping-pong images, the lists of rm_render_adaptive
+ * (4 B per pixel of a chunk of frames), and — by far the largest —
  * the wavefront pipeline's ray / hit / path records, ≈(160 + 4·numLights) bytes per pixel of the launch (5.8 GB for a
  * 7680×4320 frame, once per stream that renders such frames).  rm_set_workspace_limit caps the size of any ONE such buffer
  * (0 = no limit, the default; the environment variable RM_WF_MAX_WORKSPACE_BYTES sets the initial value).  When the wavefront
@@ -413,7 +453,7 @@ int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
- * with ss > 1 (neither is a value rm_set_kernel_path takes). */
+ * with ss > 1, 8 = a call of rm_render_adaptive (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

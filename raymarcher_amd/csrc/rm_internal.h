@@ -42,7 +42,7 @@ int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
 // different streams of one device may run concurrently on the GPU and therefore never share scratch.  Growing
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
-enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5 };
+enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 // The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
 // this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).
@@ -54,6 +54,14 @@ int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, i
 // translation unit of its own, so that the code objects of rm_kernels.hip do not depend on it.
 int launch_render_ss(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
                      float *d_rgba, float *d_bright, hipStream_t stream);
+// The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
+// test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
+// counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the
+// supersampling kernel of the class over those lists, grid.z = the chunk's frames, `sb` the chunk's first scene block.
+int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, int frames, int wavesPerBlock, float threshold,
+                             uint8_t *d_mask, uint32_t *d_list, uint32_t *d_counts, hipStream_t stream);
+int launch_adaptive_refine(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
+                           const uint32_t *d_list, const uint32_t *d_counts, float *d_rgba, float *d_bright, hipStream_t stream);
 #endif
 // ---- register budgets of the render kernels (rm_kernels.hip has the measurements; -DRM_*_WAVES=n overrides) --------------------
 #ifndef RM_GENERIC_WAVES

@@ -1658,6 +1658,88 @@ int launch_supersampled(const RmCamera *cams, const RmGlobals *globals, int numG
   return RM_OK;
 }
 
+// ---- adaptive supersampling: the 1-sample frame everywhere, ss × ss samples where it shows contrast ----------------------------
+// rm_render_adaptive (the header has the definition).  A batch's staging (one slot of the batch ring for the whole call), then per
+// chunk of frames, all on the caller's stream: (1) the one-lane-per-pixel kernel as launch_batch launches it (raster order, 8×8
+// tiles, grid.z = frames) straight into the outputs — so an unflagged pixel is rm_render_batch's by construction —, (2) the
+// classify kernel: mask, per-frame lists of flagged pixels and their counts into the stream's workspace, (3) for ss > 1 the refine
+// kernel over the lists, which overwrites the flagged pixels.  The host never learns the counts: the refine grid is fixed — at most
+// kRefineWaves waves per chunk, about three times what the chip holds, each striding over its frame's list — and workgroups past
+// the end of a list leave at once.  No wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state.
+constexpr unsigned long long kAdaptiveDefaultCap = 256ull << 20;  // of list per chunk when no workspace limit is set (as the post passes')
+constexpr int kRefineWaves = 16384;
+int launch_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
+                    const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H, int ss,
+                    float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined, hipStream_t stream) {
+  // every argument check ahead of the first HIP call (launch_supersampled's, in its order, and the threshold)
+  if (ss != 1 && ss != 2 && ss != 4) { set_error("ss (samples per pixel along each axis) must be 1, 2 or 4"); return RM_ERR_INVALID_ARGUMENT; }
+  if (threshold != threshold) { set_error("threshold is NaN"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (numFrames == 0) return RM_OK;
+  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W > INT_MAX / 8 / ss || H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
+  const int nw = waves_per_block();
+  const long long tilesX = ((long long)ss * W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * H + 7) / 8;
+  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((long long)W * H > INT_MAX) { set_error("more pixels per frame than a list entry can index"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
+  if (st != RM_OK) return st;
+  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
+  if ((st = require_device_pointers({{"d_mask", d_mask}, {"d_refined", d_refined}})) != RM_OK) return st;
+  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
+  bool plainBulb = true;
+  for (int f = 0; f < numFrames; f++) plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);  // held to the last launch: the workspace is in use until then (rm_release_workspaces)
+  // frames per chunk: 4 B of list per pixel under the workspace limit (a single frame above a set limit fails in stream_workspace)
+  const size_t px = (size_t)W * (size_t)H;
+  const unsigned long long limit = workspace_limit(), fit = (limit ? limit : kAdaptiveDefaultCap) / (4ull * px);
+  const int chunk = fit < (unsigned long long)numFrames ? (fit < 1 ? 1 : (int)fit) : numFrames;
+  void *listMem, *countMem;
+  if ((st = stream_workspace(kWsAdaptive, stream, (size_t)chunk * px * sizeof(uint32_t), &listMem)) != RM_OK) return st;
+  if ((st = stream_workspace(kWsAdaptiveCounts, stream, RM_MAX_BATCH_FRAMES * sizeof(uint32_t), &countMem)) != RM_OK) return st;
+  uint32_t *list = static_cast<uint32_t *>(listMem), *counts = static_cast<uint32_t *>(countMem);
+  Slot *b;
+  if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
+  fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
+  if ((st = upload_frames(*b, numFrames, LaunchFields{}, stream)) != RM_OK) return st;
+  const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
+  const int bulbClass = (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
+  LaunchTimer timer(stream);
+  if ((st = timer.stamp()) != RM_OK) return st;
+  for (int f0 = 0; f0 < numFrames; f0 += chunk) {
+    const int k = numFrames - f0 < chunk ? numFrames - f0 : chunk;
+    const RowMap map{0, H, 0, 1, 0};
+    const dim3 grid((W + nw * 8 - 1) / (nw * 8), (H + 7) / 8, (unsigned)k), block(64 * nw);
+    const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), nullptr,
+                         stream, grid, block};
+    dispatch_render(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemsetAsync(counts, 0, (size_t)k * sizeof(uint32_t), stream));
+    if ((st = launch_adaptive_classify(d_rgba, W, H, f0, k, nw, threshold, d_mask, list, counts, stream)) != RM_OK) return st;
+    if (d_refined) HIP_OK(hipMemcpyAsync(d_refined + f0, counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    if (ss > 1) {
+      // a frame's grid slice: enough waves for every pixel of it, at most the chunk's share of kRefineWaves
+      const size_t perWave = 64 / (size_t)(ss * ss), want = (px + perWave * nw - 1) / (perWave * nw);
+      const size_t most = (size_t)(kRefineWaves / nw / k > 0 ? kRefineWaves / nw / k : 1);
+      const dim3 rgrid((unsigned)(want < most ? want : most), 1, (unsigned)k);
+      if ((st = launch_adaptive_refine(b->dev + f0, bulbClass, fc.envFeatures, fc.textured, fc.secondary, rgrid, block, W, H, ss, list, counts,
+                                       d_rgba, d_bright, stream)) != RM_OK) return st;
+    }
+  }
+  if ((st = timer.stamp()) != RM_OK) return st;
+  ds->lastPath = 8;
+  ds->lastSplit = 0;
+  timer.keep(*ds);
+  HIP_OK(hipEventRecord(b->done, stream));
+  return RM_OK;
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1727,6 +1809,13 @@ int rm_render_supersampled(const RmCamera *cams, const RmGlobals *globals, int n
                            int H, int ss, float *d_rgba, float *d_bright, void *stream) {
   return launch_supersampled(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
                              W, H, ss, d_rgba, d_bright, static_cast<hipStream_t>(stream));
+}
+
+int rm_render_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                       int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W, int H,
+                       int ss, float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined, void *stream) {
+  return launch_adaptive(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
+                         ss, threshold, d_rgba, d_bright, d_mask, d_refined, static_cast<hipStream_t>(stream));
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

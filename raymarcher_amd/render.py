@@ -313,6 +313,36 @@ class Renderer:
                                            C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
+    def render_adaptive(self, tables, settings, W, H, cameras, ss, threshold, globals_=None, bright=False, out=None, out_bright=None,
+                        mask=False, counts=False):
+        """rm_render_adaptive: render_batch's frames with the pixels that differ from a 4-neighbour by more than `threshold` in r, g
+        or b replaced by render_supersampled's (the definition is in include/raymarcher_amd.h) → float32 tensor (N, H, W, 4), row 0
+        = bottom; with bright, mask (uint8 (N, H, W), 1 = refined) or counts (int32 (N,), refined pixels per frame, left on the
+        device) a tuple (frames[, bright][, mask][, counts]).  mask / counts: True, or the caller's buffer of that shape and
+        type.  Every other argument as render_supersampled's."""
+        if ss not in (1, 2, 4):
+            raise ValueError(f"ss = {ss!r}: the samples per pixel along each axis are 1, 2 or 4")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
+        n = len(cameras)
+        shape = (n, H, W, 4)
+        t = self.torch
+        out = self._out(out, shape, t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
+        want_mask, want_counts = mask is not False and mask is not None, counts is not False and counts is not None
+        m = self._out(None if mask is True else mask, (n, H, W), t.uint8, "mask") if want_mask else None
+        cnt = self._out(None if counts is True else counts, (n,), t.int32, "counts") if want_counts else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_render_adaptive(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
+                                       C.byref(settings), C.byref(res), W, H, ss, threshold, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(br.data_ptr()) if bright else None, C.c_void_p(m.data_ptr()) if want_mask else None,
+                                       C.c_void_p(cnt.data_ptr()) if want_counts else None, self._stream()))
+        extra = [x for x in (br, m, cnt) if x is not None]
+        return (out, *extra) if extra else out
+
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
         what the production kernel really executes (RM_COUNT_EXECUTED; plain scene classes only)."""
@@ -425,14 +455,18 @@ class Renderer:
         check(lib().rm_frames_to_rgba8(C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()), W, H, n, self._stream()))
         return out
 
-    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1):
+    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1, adaptive=None):
         """The finished images of an exported sequence: render_batch (with the BrightColor planes only when bloom is on), then
         post_process_batch in place (skipped for post=None), then to_rgba8_batch → uint8 (N, H, W, 4), each image's top row
         first.  post: one RmPostSettings or a sequence of N (see post_process_batch).  supersample = 2 or 4: the render step is
-        render_supersampled with that many samples per pixel along each axis (bloom then sees the resolved BrightColor)."""
+        render_supersampled with that many samples per pixel along each axis (bloom then sees the resolved BrightColor).
+        adaptive = t: the render step is render_adaptive(…, supersample, t) — those samples only where the 1-sample frame shows
+        contrast above t."""
         ps = post_array(post, len(cameras)) if post is not None else None
         bloom = ps is not None and bool(ps[0].enableBloom)
-        if supersample == 1:
+        if adaptive is not None:
+            frames = self.render_adaptive(tables, settings, W, H, cameras, supersample, adaptive, globals_, bright=bloom)
+        elif supersample == 1:
             frames = self.render_batch(tables, settings, W, H, cameras, globals_, bright=bloom)
         else:
             frames = self.render_supersampled(tables, settings, W, H, cameras, supersample, globals_, bright=bloom)
