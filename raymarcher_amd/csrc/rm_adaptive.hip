@@ -101,15 +101,6 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void adapti
   }
 }
 
-namespace {
-template <int BULB, bool ENV, bool TEX>
-void launch_refine(bool sec, dim3 grid, dim3 block, hipStream_t stream, const SceneBlock *sb, int W, int H, int ss, const uint32_t *list,
-                   const uint32_t *counts, float4 *o, float4 *b) {
-  if (sec) hipLaunchKernelGGL((adaptive_refine_kernel<BULB, ENV, TEX, true>), grid, block, 0, stream, sb, W, H, ss, list, counts, o, b);
-  else hipLaunchKernelGGL((adaptive_refine_kernel<BULB, ENV, TEX, false>), grid, block, 0, stream, sb, W, H, ss, list, counts, o, b);
-}
-}  // namespace
-
 int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, int frames, int wavesPerBlock, float threshold,
                              uint8_t *d_mask, uint32_t *d_list, uint32_t *d_counts, hipStream_t stream) {
   const dim3 grid((unsigned)((W + wavesPerBlock * 8 - 1) / (wavesPerBlock * 8)), (unsigned)((H + 7) / 8), (unsigned)frames);
@@ -119,17 +110,15 @@ int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, int fram
   return RM_OK;
 }
 
-// The class set of launch_render_ss (rm_supersample.hip), the same twelve instantiations.
+// The production classes (dispatch_class, rm_internal.h): render_ss_kernel's.
 int launch_adaptive_refine(const void *sbv, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
                            const uint32_t *d_list, const uint32_t *d_counts, float *d_rgba, float *d_bright, hipStream_t stream) {
   const SceneBlock *sb = static_cast<const SceneBlock *>(sbv);
   float4 *o = reinterpret_cast<float4 *>(d_rgba), *b = reinterpret_cast<float4 *>(d_bright);
-  if (env && tex) launch_refine<0, true, true>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
-  else if (env) launch_refine<0, true, false>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
-  else if (tex) launch_refine<0, false, true>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
-  else if (bulbClass == kBulbPlain) launch_refine<kBulbPlain, false, false>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
-  else if (bulbClass == kBulbGeneral) launch_refine<kBulbGeneral, false, false>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
-  else launch_refine<0, false, false>(sec, grid, block, stream, sb, W, H, ss, d_list, d_counts, o, b);
+  dispatch_class(bulbClass, env, tex, sec, [&](auto c) {
+    using K = decltype(c);
+    hipLaunchKernelGGL((adaptive_refine_kernel<K::bulb, K::env, K::tex, K::sec>), grid, block, 0, stream, sb, W, H, ss, d_list, d_counts, o, b);
+  });
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

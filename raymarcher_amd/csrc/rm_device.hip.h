@@ -61,11 +61,6 @@ struct Counters { unsigned long long evals, iters, shades, fbm9, fbmd8, shapes; 
 #include "rm_env.hip.h"
 namespace rm {
 
-
-// The single-Mandelbulb class (the kernels' BULB template parameter; 0 = the table walk): any object transform, power and
-// Julia seed, or the plain form that SceneBlock::bulbPlain describes.
-constexpr int kBulbGeneral = 1, kBulbPlain = 2;
-
 // Everything a frame needs, in one constant block (uploaded once per launch by the launcher).
 struct EvalRecord {
   float m[12];  // invModel[0..2], [4..6], [8..10], [12..14]

@@ -97,6 +97,26 @@ constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
   if (bulb) return sec ? RM_BULB_WAVES : RM_BULB_NOSEC_WAVES;
   return sec ? RM_GENERIC_WAVES : RM_GENERIC_NOSEC_WAVES;
 }
+// The single-Mandelbulb class (the kernels' BULB template parameter; 0 = the table walk): any object transform, power and
+// Julia seed, or the plain form that SceneBlock::bulbPlain describes.
+constexpr int kBulbGeneral = 1, kBulbPlain = 2;
+// The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel and adaptive_refine_kernel
+// are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
+// then the plain table walk, each with main's secondary rays compiled in only where they can fire (sec).
+template <int BULB, bool ENV, bool TEX, bool SEC>
+struct KernelClass { static constexpr int bulb = BULB; static constexpr bool env = ENV, tex = TEX, sec = SEC; };
+// Calls f(KernelClass<…>{}) for the class of a launch: `f` is a generic lambda that launches its kernel with the tag's members as
+// template arguments, so a kernel has exactly the instantiations of this ladder.
+template <class F>
+void dispatch_class(int bulbClass, bool env, bool tex, bool sec, F &&f) {
+  auto either = [&](auto on, auto off) { if (sec) f(on); else f(off); };
+  if (env && tex) either(KernelClass<0, true, true, true>{}, KernelClass<0, true, true, false>{});
+  else if (env) either(KernelClass<0, true, false, true>{}, KernelClass<0, true, false, false>{});
+  else if (tex) either(KernelClass<0, false, true, true>{}, KernelClass<0, false, true, false>{});
+  else if (bulbClass == kBulbPlain) either(KernelClass<kBulbPlain, false, false, true>{}, KernelClass<kBulbPlain, false, false, false>{});
+  else if (bulbClass == kBulbGeneral) either(KernelClass<kBulbGeneral, false, false, true>{}, KernelClass<kBulbGeneral, false, false, false>{});
+  else either(KernelClass<0, false, false, true>{}, KernelClass<0, false, false, false>{});
+}
 
 // The largest single workspace buffer stream_workspace may allocate, 0 = no limit (rm_set_workspace_limit).
 unsigned long long workspace_limit();

@@ -1347,12 +1347,6 @@ template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 
 void launch_kernel(const RenderLaunch &r) {
   hipLaunchKernelGGL((render_kernel<BULB, COUNT, ENV, TEX, SEC, SPLIT>), r.grid, r.block, 0, r.stream, r.sb, r.map, r.W, r.H, r.nRows, r.o, r.b, r.dc);
 }
-// a production launch: the secondary rays compiled in only where they can fire
-template <int BULB, bool ENV, bool TEX>
-void launch_production(bool secondary, const RenderLaunch &r) {
-  if (secondary) launch_kernel<BULB, 0, ENV, TEX, true>(r);
-  else launch_kernel<BULB, 0, ENV, TEX, false>(r);
-}
 // the counted (1: reference work, 2: executed work) and clock-stamped (3) launches
 template <int BULB>
 void launch_counted(int count, const RenderLaunch &r) {
@@ -1360,26 +1354,24 @@ void launch_counted(int count, const RenderLaunch &r) {
   else if (count == 2) launch_kernel<BULB, 2, false, false>(r);
   else launch_kernel<BULB, 3, false, false>(r);
 }
-// the layer / sampler kernels: their counting instantiations count the reference's work only (they have no shortcuts to count apart)
-template <bool ENV, bool TEX>
-void launch_layered(int count, bool secondary, const RenderLaunch &r) {
-  if (count) launch_kernel<0, 1, ENV, TEX>(r);
-  else launch_production<0, ENV, TEX>(secondary, r);
+// The BULB argument of a frame's production kernels (dispatch_class): the bulb class only without layers and samplers, its plain
+// form where the launcher found it.
+int bulb_class(const FrameClass &fc, bool plainBulb) {
+  return (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
 }
 // A batch (rm_render_batch, one class for every frame of the launch) comes with count = 0 and no light split, so it reaches only
 // the production kernels; the counted and split kernels render single frames.
 int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const LightSplit &ls, int numLights, int tileCount,
                     const RenderLaunch &r) {
-  if (fc.envFeatures && fc.textured) launch_layered<true, true>(count, fc.secondary, r);
-  else if (fc.envFeatures) launch_layered<true, false>(count, fc.secondary, r);
-  else if (fc.textured) launch_layered<false, true>(count, fc.secondary, r);
-  else if (fc.bulb) {
-    // the counted launches keep the general form; the production ones take the plain form where the launcher found it
-    if (count) launch_counted<kBulbGeneral>(count, r);
-    else if (plainBulb) launch_production<kBulbPlain, false, false>(fc.secondary, r);
-    else launch_production<kBulbGeneral, false, false>(fc.secondary, r);
-  } else if (count) launch_counted<0>(count, r);
-  else if (!fc.secondary && ls.tiles > 0) {
+  const int bulbClass = bulb_class(fc, plainBulb);
+  if (count) {
+    // the layer / sampler kernels count the reference's work only (they have no shortcuts to count apart); the bulb keeps the general form
+    if (fc.envFeatures && fc.textured) launch_kernel<0, 1, true, true>(r);
+    else if (fc.envFeatures) launch_kernel<0, 1, true, false>(r);
+    else if (fc.textured) launch_kernel<0, 1, false, true>(r);
+    else if (fc.bulb) launch_counted<kBulbGeneral>(count, r);
+    else launch_counted<0>(count, r);
+  } else if (!bulbClass && !fc.envFeatures && !fc.textured && !fc.secondary && ls.tiles > 0) {
     // light split: the heavy tiles one light per workgroup first, every other tile behind them in the same grid; the last of a
     // tile's workgroups to finish its march finishes the tile.  (A second launch for the finish cost 35-45 µs per frame —
     // more than the split gains on throughput-bound frames; the same launch on a side stream gained nothing.)
@@ -1388,7 +1380,12 @@ int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const Light
     split.grid = dim3((unsigned)(ls.tiles * numLights + tileCount - ls.tiles));
     split.block = dim3(64);
     launch_kernel<0, 0, false, false, false, 1>(split);
-  } else launch_production<0, false, false>(fc.secondary, r);
+  } else {
+    dispatch_class(bulbClass, fc.envFeatures, fc.textured, fc.secondary, [&](auto c) {
+      using K = decltype(c);
+      launch_kernel<K::bulb, 0, K::env, K::tex, K::sec>(r);
+    });
+  }
   return RM_OK;
 }
 
@@ -1528,216 +1525,206 @@ int row_range(int H, int rowBegin, int rowEnd, RowMap *map, int *nRows) {
   return RM_OK;
 }
 
-// ---- batches: numFrames whole frames of one scene, each with its own camera and globals, in one launch -----------------------
+// ---- multi-frame calls: numFrames whole frames of one scene, each with its own camera and globals -----------------------------
+// What rm_render_batch, rm_render_supersampled and rm_render_adaptive are all called with.
+struct FrameCall {
+  const RmCamera *cams; const RmGlobals *globals; int numGlobals, numFrames;
+  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
+  const RmSettings *s; const RmResources &res;
+  int W, H; float *d_rgba, *d_bright; hipStream_t stream;
+  const RmGlobals *globalsOf(int f) const { return &globals[numGlobals == 1 ? 0 : f]; }
+};
+// The argument checks the three entry points share, every one ahead of the first HIP call (as launch_render's); an input that
+// fails several reports the first of this order.  numFrames = 0 passes: nothing to write, the caller returns RM_OK.  sampled: the
+// call renders an ss·W × ss·H sample frame (rm_render_supersampled; rm_render_adaptive, which checks it for ss = 1 too), whose
+// coordinates and tiles must fit the kernels' indices.  sizeCheck: the entry point's own check of the frame size, between those
+// and the scene's.
+int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(const FrameCall &) = nullptr) {
+  if (c.numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (c.numFrames == 0) return RM_OK;
+  if (c.numGlobals != 1 && c.numGlobals != c.numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!c.cams || !c.globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.W <= 0 || c.H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
+  if (sampled) {
+    if (c.W > INT_MAX / 8 / ss || c.H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
+    // the kernel's sample coordinates are 32-bit and come from blockIdx: a grid's y extent is at most 65535 tiles, and the tiles of
+    // one frame stay countable in an int (as render_kernel's)
+    const int nw = waves_per_block();
+    const long long tilesX = ((long long)ss * c.W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * c.H + 7) / 8;
+    if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
+  }
+  int st = sizeCheck ? sizeCheck(c) : RM_OK;
+  if (st != RM_OK) return st;
+  if ((st = validate_scene(&c.cams[0], c.objs, c.numObjects, c.lights, c.numLights, &c.globals[0], c.s, c.res)) != RM_OK) return st;
+  if (!c.d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  return check_device_pointers(c.res, c.d_rgba, c.d_bright);
+}
+
+// What the staging step hands a multi-frame launcher.
+struct StagedFrames {
+  Slot *slot = nullptr;   // of the batch ring: one scene block per frame (not per sample), filled and uploaded
+  FrameClass fc{};        // shared by every frame
+  bool plainBulb = true;  // the plain bulb form only where every frame has it
+  int bulbClass = 0;      // bulb_class of the two
+  LaunchTimer timer;      // stamped once, ahead of the caller's launches
+  explicit StagedFrames(hipStream_t stream) : timer(stream) {}
+};
+// The staging step.  The caller holds the device's lock, from here to finish_frames at least; nothing here waits for the GPU but
+// acquire_slot at the ring's bounds.  tileShift: the tile shape of the launch (LaunchFields).  alone (or null): the frames that
+// are not part of the launch (launch_batch), which have no say in plainBulb.
+int stage_frames(DeviceState &ds, const FrameCall &c, int tileShift, const char *alone, StagedFrames *sf) {
+  for (int f = 0; f < c.numFrames; f++)
+    if (!alone || !alone[f]) sf->plainBulb = sf->plainBulb && bulb_plain(c.objs, c.numObjects, c.globalsOf(f));
+  int st = acquire_slot(ds.batches, c.numFrames, &sf->slot);
+  if (st != RM_OK) return st;
+  fill_frames(sf->slot->host, c.numFrames, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+  LaunchFields lf;
+  lf.tileShift = tileShift;
+  if ((st = upload_frames(*sf->slot, c.numFrames, lf, c.stream)) != RM_OK) return st;
+  sf->fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.globalsOf(0), c.s, 0);
+  sf->bulbClass = bulb_class(sf->fc, sf->plainBulb);
+  return sf->timer.stamp();
+}
+// One launch of the one-lane-per-pixel kernel of the class over frames f0 … f0 + k − 1 of the staged slot (grid.z = k), straight
+// into the call's outputs: raster order, tiles 2^tileShift pixels wide (the shift the slot was staged with).
+int launch_frames(const FrameCall &c, const StagedFrames &sf, int f0, int k, int tileShift) {
+  const int nw = waves_per_block(), tileW = 1 << tileShift, tileH = 64 >> tileShift;
+  const RowMap map{0, c.H, 0, 1, 0};
+  const dim3 grid((c.W + nw * tileW - 1) / (nw * tileW), (c.H + tileH - 1) / tileH, (unsigned)k);
+  const RenderLaunch r{sf.slot->dev + f0, map, c.W, c.H, c.H, reinterpret_cast<float4 *>(c.d_rgba), reinterpret_cast<float4 *>(c.d_bright),
+                       nullptr, c.stream, grid, dim3(64 * nw)};
+  return dispatch_render(sf.fc, 0, sf.plainBulb, LightSplit{}, c.numLights, 0, r);
+}
+// The finishing step, behind the caller's last launch: the timing's end, rm_debug_last_path / rm_debug_last_split and the slot's event.
+int finish_frames(DeviceState &ds, StagedFrames &sf, int path, hipStream_t stream) {
+  if (int st = sf.timer.stamp()) return st;
+  HIP_OK(hipGetLastError());
+  ds.lastPath = path;
+  ds.lastSplit = 0;
+  sf.timer.keep(ds);
+  HIP_OK(hipEventRecord(sf.slot->done, stream));
+  return RM_OK;
+}
+constexpr int kTiles8x8 = 3;  // the tile shift of the launches that take no shape pin
+
+// ---- batches: rm_render_batch ------------------------------------------------------------------------------------------------
 // Every batched frame renders with the one-lane-per-pixel kernel in raster tile order (no tile-order history, no light split), 8×8
 // tiles unless a shape is pinned: a batch reads and changes none of the per-stream state (tuners, tile order), so a host that
 // interleaves batches with repeated single frames sees those tune as before.  The frames overlap on the chip as frames in flight
 // on several streams do — the tail of frame f under the full waves of frame f + 1 — without streams or per-call host overhead.
 // A frame that would take the wavefront pipeline on its own (path 5, chosen or requested) is rendered through launch_render
 // instead, after the batched launch, in frame order on the same stream.
-int launch_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
-                 const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H, float *d_rgba,
-                 float *d_bright, hipStream_t stream) {
-  // every argument check ahead of the first HIP call (as launch_render's)
-  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
-  if (numFrames == 0) return RM_OK;
-  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
-  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
-  if (st != RM_OK) return st;
-  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
-  const size_t frame = (size_t)H * W * 4;  // floats per frame
-  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
+int launch_batch(const FrameCall &c) {
+  int st = check_frames(c, 1, false);
+  if (st != RM_OK || c.numFrames == 0) return st;
   // which frames the single-frame launcher would give the wavefront pipeline (launch_render, setup_wavefront): only the 2-D mode,
   // a per-frame global, can tell frames apart
   const int pathReq = kernel_path_request();
-  std::vector<char> alone(numFrames, 0);
-  bool anyBatched = false, plainBulb = true;
-  for (int f = 0; f < numFrames; f++) {
-    const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(f), s, 0);
-    alone[f] = fc.wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(objs, numObjects, fc.wfBounces, (size_t)H * W, false)));
-    if (!alone[f]) {
-      anyBatched = true;
-      plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
-    }
+  std::vector<char> alone(c.numFrames, 0);
+  bool anyBatched = false;
+  for (int f = 0; f < c.numFrames; f++) {
+    const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.globalsOf(f), c.s, 0);
+    alone[f] = fc.wfOk && (pathReq == 5 || (pathReq == 0 && wavefront_pays(c.objs, c.numObjects, fc.wfBounces, (size_t)c.H * c.W, false)));
+    anyBatched = anyBatched || !alone[f];
   }
   if (anyBatched) {
     DeviceState *ds;
     if ((st = current_device_state(&ds)) != RM_OK) return st;
-    std::lock_guard<std::mutex> lock(ds->mu);  // nothing below waits for the GPU but acquire_slot at the ring's bounds
-    Slot *b;
-    if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
-    fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
-    const int pinned = tile_shape_request();
-    LaunchFields lf;
-    lf.tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
-    if ((st = upload_frames(*b, numFrames, lf, stream)) != RM_OK) return st;
-    const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
-    const int nw = waves_per_block(), tileW = 1 << lf.tileShift, tileH = 64 >> lf.tileShift;
-    LaunchTimer timer(stream);
-    if ((st = timer.stamp()) != RM_OK) return st;
+    std::lock_guard<std::mutex> lock(ds->mu);
+    const int pinned = tile_shape_request(), tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
+    StagedFrames sf(c.stream);
+    if ((st = stage_frames(*ds, c, tileShift, alone.data(), &sf)) != RM_OK) return st;
     // one launch per run of consecutive batched frames (one run unless wavefront frames sit between them)
-    for (int f0 = 0; f0 < numFrames;) {
+    for (int f0 = 0; f0 < c.numFrames;) {
       if (alone[f0]) { f0++; continue; }
       int f1 = f0;
-      while (f1 < numFrames && !alone[f1]) f1++;
-      const RowMap map{0, H, 0, 1, 0};
-      const dim3 grid((W + nw * tileW - 1) / (nw * tileW), (H + tileH - 1) / tileH, (unsigned)(f1 - f0));
-      const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), nullptr,
-                           stream, grid, dim3(64 * nw)};
-      dispatch_render(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
+      while (f1 < c.numFrames && !alone[f1]) f1++;
+      if ((st = launch_frames(c, sf, f0, f1 - f0, tileShift)) != RM_OK) return st;
       f0 = f1;
     }
-    if ((st = timer.stamp()) != RM_OK) return st;
-    HIP_OK(hipGetLastError());
-    ds->lastPath = 6;
-    ds->lastSplit = 0;
-    timer.keep(*ds);
-    HIP_OK(hipEventRecord(b->done, stream));
+    if ((st = finish_frames(*ds, sf, 6, c.stream)) != RM_OK) return st;
   }
-  const RowMap whole{0, H, 0, 1, 0};
-  for (int f = 0; f < numFrames; f++)
-    if (alone[f] && (st = launch_render(&cams[f], objs, numObjects, lights, numLights, globalsOf(f), s, W, H, whole, H, d_rgba + f * frame,
-                                        d_bright ? d_bright + f * frame : nullptr, stream, 0, nullptr, res)) != RM_OK)
+  const size_t frame = (size_t)c.H * c.W * 4;  // floats per frame
+  const RowMap whole{0, c.H, 0, 1, 0};
+  for (int f = 0; f < c.numFrames; f++)
+    if (alone[f] && (st = launch_render(&c.cams[f], c.objs, c.numObjects, c.lights, c.numLights, c.globalsOf(f), c.s, c.W, c.H, whole, c.H,
+                                        c.d_rgba + f * frame, c.d_bright ? c.d_bright + f * frame : nullptr, c.stream, 0, nullptr, c.res)) != RM_OK)
       return st;
   return RM_OK;
 }
 
 // ---- supersampled frames: ss × ss samples per pixel, resolved in the wave (render_ss_kernel) -----------------------------------
-// rm_render_supersampled.  A batch's shape and staging (the batch ring, fill_frames, upload_frames: one scene block per frame, not
-// per sample), ONE launch over (tilesX, tilesY, numFrames) 8×8 sample tiles in raster order for every frame: no wavefront pipeline,
-// no light split, no tile-shape pin, no tuner or tile-order state read or written, no library workspace.
-int launch_supersampled(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
-                        int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H,
-                        int ss, float *d_rgba, float *d_bright, hipStream_t stream) {
-  // every argument check ahead of the first HIP call (as launch_batch's)
+// rm_render_supersampled.  A batch's staging, then ONE launch over (tilesX, tilesY, numFrames) 8×8 sample tiles in raster order for
+// every frame: no wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state read or written, no library
+// workspace.  The kernels are a translation unit of their own (rm_supersample.hip).
+int launch_supersampled(const FrameCall &c, int ss) {
   if (ss != 1 && ss != 2 && ss != 4) { set_error("ss (samples per pixel along each axis) must be 1, 2 or 4"); return RM_ERR_INVALID_ARGUMENT; }
-  if (ss == 1) return launch_batch(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res, W, H, d_rgba, d_bright, stream);
-  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
-  if (numFrames == 0) return RM_OK;
-  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
-  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
-  if (W > INT_MAX / 8 / ss || H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
-  // the kernel's sample coordinates are 32-bit and come from blockIdx: a grid's y extent is at most 65535 tiles, and the tiles of
-  // one frame stay countable in an int (as render_kernel's)
-  const int nw = waves_per_block();
-  const long long tilesX = ((long long)ss * W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * H + 7) / 8;
-  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
-  if (st != RM_OK) return st;
-  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
-  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
-  bool plainBulb = true;
-  for (int f = 0; f < numFrames; f++) plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
+  if (ss == 1) return launch_batch(c);
+  int st = check_frames(c, ss, true);
+  if (st != RM_OK || c.numFrames == 0) return st;
   DeviceState *ds;
   if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);  // nothing below waits for the GPU but acquire_slot at the ring's bounds
-  Slot *b;
-  if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
-  fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
-  if ((st = upload_frames(*b, numFrames, LaunchFields{}, stream)) != RM_OK) return st;
-  const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
-  LaunchTimer timer(stream);
-  if ((st = timer.stamp()) != RM_OK) return st;
-  const dim3 grid((unsigned)tilesX, (unsigned)tilesY, (unsigned)numFrames), block(64 * nw);
-  // the class set of launch_production and nothing more; the kernels are a translation unit of their own (rm_supersample.hip)
-  const int bulbClass = (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
-  if ((st = launch_render_ss(b->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, grid, block, W, H, ss, d_rgba, d_bright, stream)) != RM_OK) return st;
-  if ((st = timer.stamp()) != RM_OK) return st;
-  HIP_OK(hipGetLastError());
-  ds->lastPath = 7;
-  ds->lastSplit = 0;
-  timer.keep(*ds);
-  HIP_OK(hipEventRecord(b->done, stream));
-  return RM_OK;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  const int nw = waves_per_block();
+  const dim3 grid((unsigned)((ss * c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((ss * c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
+  if ((st = launch_render_ss(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, grid, block, c.W, c.H, ss,
+                             c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
+  return finish_frames(*ds, sf, 7, c.stream);
 }
 
 // ---- adaptive supersampling: the 1-sample frame everywhere, ss × ss samples where it shows contrast ----------------------------
 // rm_render_adaptive (the header has the definition).  A batch's staging (one slot of the batch ring for the whole call), then per
-// chunk of frames, all on the caller's stream: (1) the one-lane-per-pixel kernel as launch_batch launches it (raster order, 8×8
-// tiles, grid.z = frames) straight into the outputs — so an unflagged pixel is rm_render_batch's by construction —, (2) the
-// classify kernel: mask, per-frame lists of flagged pixels and their counts into the stream's workspace, (3) for ss > 1 the refine
-// kernel over the lists, which overwrites the flagged pixels.  The host never learns the counts: the refine grid is fixed — at most
-// kRefineWaves waves per chunk, about three times what the chip holds, each striding over its frame's list — and workgroups past
-// the end of a list leave at once.  No wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state.
+// chunk of frames, all on the caller's stream: (1) launch_frames, the one-lane-per-pixel launch of launch_batch (8×8 tiles always)
+// straight into the outputs — so an unflagged pixel is rm_render_batch's by construction —, (2) the classify kernel: mask,
+// per-frame lists of flagged pixels and their counts into the stream's workspace, (3) for ss > 1 the refine kernel over the lists,
+// which overwrites the flagged pixels.  The host never learns the counts: the refine grid is fixed — at most kRefineWaves waves per
+// chunk, about three times what the chip holds, each striding over its frame's list — and workgroups past the end of a list leave
+// at once.  No wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state.
 constexpr unsigned long long kAdaptiveDefaultCap = 256ull << 20;  // of list per chunk when no workspace limit is set (as the post passes')
 constexpr int kRefineWaves = 16384;
-int launch_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
-                    const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res, int W, int H, int ss,
-                    float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined, hipStream_t stream) {
-  // every argument check ahead of the first HIP call (launch_supersampled's, in its order, and the threshold)
+int launch_adaptive(const FrameCall &c, int ss, float threshold, uint8_t *d_mask, uint32_t *d_refined) {
   if (ss != 1 && ss != 2 && ss != 4) { set_error("ss (samples per pixel along each axis) must be 1, 2 or 4"); return RM_ERR_INVALID_ARGUMENT; }
   if (threshold != threshold) { set_error("threshold is NaN"); return RM_ERR_INVALID_ARGUMENT; }
-  if (numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
-  if (numFrames == 0) return RM_OK;
-  if (numGlobals != 1 && numGlobals != numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!cams || !globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
-  if (W <= 0 || H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
-  if (W > INT_MAX / 8 / ss || H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
-  const int nw = waves_per_block();
-  const long long tilesX = ((long long)ss * W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * H + 7) / 8;
-  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((long long)W * H > INT_MAX) { set_error("more pixels per frame than a list entry can index"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = validate_scene(&cams[0], objs, numObjects, lights, numLights, &globals[0], s, res);
-  if (st != RM_OK) return st;
-  if (!d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = check_device_pointers(res, d_rgba, d_bright)) != RM_OK) return st;
+  int st = check_frames(c, ss, true, [](const FrameCall &call) {
+    if ((long long)call.W * call.H > INT_MAX) { set_error("more pixels per frame than a list entry can index"); return (int)RM_ERR_INVALID_ARGUMENT; }
+    return (int)RM_OK;
+  });
+  if (st != RM_OK || c.numFrames == 0) return st;
   if ((st = require_device_pointers({{"d_mask", d_mask}, {"d_refined", d_refined}})) != RM_OK) return st;
-  auto globalsOf = [&](int f) { return &globals[numGlobals == 1 ? 0 : f]; };
-  bool plainBulb = true;
-  for (int f = 0; f < numFrames; f++) plainBulb = plainBulb && bulb_plain(objs, numObjects, globalsOf(f));  // the plain form only where every frame has it
   DeviceState *ds;
   if ((st = current_device_state(&ds)) != RM_OK) return st;
   std::lock_guard<std::mutex> lock(ds->mu);  // held to the last launch: the workspace is in use until then (rm_release_workspaces)
   // frames per chunk: 4 B of list per pixel under the workspace limit (a single frame above a set limit fails in stream_workspace)
-  const size_t px = (size_t)W * (size_t)H;
+  const size_t px = (size_t)c.W * (size_t)c.H;
   const unsigned long long limit = workspace_limit(), fit = (limit ? limit : kAdaptiveDefaultCap) / (4ull * px);
-  const int chunk = fit < (unsigned long long)numFrames ? (fit < 1 ? 1 : (int)fit) : numFrames;
+  const int chunk = fit < (unsigned long long)c.numFrames ? (fit < 1 ? 1 : (int)fit) : c.numFrames;
   void *listMem, *countMem;
-  if ((st = stream_workspace(kWsAdaptive, stream, (size_t)chunk * px * sizeof(uint32_t), &listMem)) != RM_OK) return st;
-  if ((st = stream_workspace(kWsAdaptiveCounts, stream, RM_MAX_BATCH_FRAMES * sizeof(uint32_t), &countMem)) != RM_OK) return st;
+  if ((st = stream_workspace(kWsAdaptive, c.stream, (size_t)chunk * px * sizeof(uint32_t), &listMem)) != RM_OK) return st;
+  if ((st = stream_workspace(kWsAdaptiveCounts, c.stream, RM_MAX_BATCH_FRAMES * sizeof(uint32_t), &countMem)) != RM_OK) return st;
   uint32_t *list = static_cast<uint32_t *>(listMem), *counts = static_cast<uint32_t *>(countMem);
-  Slot *b;
-  if ((st = acquire_slot(ds->batches, numFrames, &b)) != RM_OK) return st;
-  fill_frames(b->host, numFrames, cams, globals, numGlobals, objs, numObjects, lights, numLights, s, res);
-  if ((st = upload_frames(*b, numFrames, LaunchFields{}, stream)) != RM_OK) return st;
-  const FrameClass fc = classify_frame(objs, numObjects, lights, numLights, globalsOf(0), s, 0);  // shared by every frame
-  const int bulbClass = (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
-  LaunchTimer timer(stream);
-  if ((st = timer.stamp()) != RM_OK) return st;
-  for (int f0 = 0; f0 < numFrames; f0 += chunk) {
-    const int k = numFrames - f0 < chunk ? numFrames - f0 : chunk;
-    const RowMap map{0, H, 0, 1, 0};
-    const dim3 grid((W + nw * 8 - 1) / (nw * 8), (H + 7) / 8, (unsigned)k), block(64 * nw);
-    const RenderLaunch r{b->dev + f0, map, W, H, H, reinterpret_cast<float4 *>(d_rgba), reinterpret_cast<float4 *>(d_bright), nullptr,
-                         stream, grid, block};
-    dispatch_render(fc, 0, plainBulb, LightSplit{}, numLights, 0, r);
+  StagedFrames sf(c.stream);
+  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  const int nw = waves_per_block();
+  for (int f0 = 0; f0 < c.numFrames; f0 += chunk) {
+    const int k = c.numFrames - f0 < chunk ? c.numFrames - f0 : chunk;
+    if ((st = launch_frames(c, sf, f0, k, kTiles8x8)) != RM_OK) return st;
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemsetAsync(counts, 0, (size_t)k * sizeof(uint32_t), stream));
-    if ((st = launch_adaptive_classify(d_rgba, W, H, f0, k, nw, threshold, d_mask, list, counts, stream)) != RM_OK) return st;
-    if (d_refined) HIP_OK(hipMemcpyAsync(d_refined + f0, counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    HIP_OK(hipMemsetAsync(counts, 0, (size_t)k * sizeof(uint32_t), c.stream));
+    if ((st = launch_adaptive_classify(c.d_rgba, c.W, c.H, f0, k, nw, threshold, d_mask, list, counts, c.stream)) != RM_OK) return st;
+    if (d_refined) HIP_OK(hipMemcpyAsync(d_refined + f0, counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.stream));
     if (ss > 1) {
       // a frame's grid slice: enough waves for every pixel of it, at most the chunk's share of kRefineWaves
       const size_t perWave = 64 / (size_t)(ss * ss), want = (px + perWave * nw - 1) / (perWave * nw);
       const size_t most = (size_t)(kRefineWaves / nw / k > 0 ? kRefineWaves / nw / k : 1);
       const dim3 rgrid((unsigned)(want < most ? want : most), 1, (unsigned)k);
-      if ((st = launch_adaptive_refine(b->dev + f0, bulbClass, fc.envFeatures, fc.textured, fc.secondary, rgrid, block, W, H, ss, list, counts,
-                                       d_rgba, d_bright, stream)) != RM_OK) return st;
+      if ((st = launch_adaptive_refine(sf.slot->dev + f0, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, rgrid, dim3(64 * nw),
+                                       c.W, c.H, ss, list, counts, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
     }
   }
-  if ((st = timer.stamp()) != RM_OK) return st;
-  ds->lastPath = 8;
-  ds->lastSplit = 0;
-  timer.keep(*ds);
-  HIP_OK(hipEventRecord(b->done, stream));
-  return RM_OK;
+  return finish_frames(*ds, sf, 8, c.stream);
 }
 
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
@@ -1800,22 +1787,22 @@ int rm_render_res(const RmCamera *cam, const RmObject *objs, int numObjects, con
 int rm_render_batch(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
                     const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W, int H, float *d_rgba,
                     float *d_bright, void *stream) {
-  return launch_batch(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
-                      d_rgba, d_bright, static_cast<hipStream_t>(stream));
+  return launch_batch(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
+                                d_rgba, d_bright, static_cast<hipStream_t>(stream)});
 }
 
 int rm_render_supersampled(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
                            int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W,
                            int H, int ss, float *d_rgba, float *d_bright, void *stream) {
-  return launch_supersampled(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
-                             W, H, ss, d_rgba, d_bright, static_cast<hipStream_t>(stream));
+  return launch_supersampled(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s,
+                                       res ? *res : kNoResources, W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream)}, ss);
 }
 
 int rm_render_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
                        int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources *res, int W, int H,
                        int ss, float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined, void *stream) {
-  return launch_adaptive(cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources, W, H,
-                         ss, threshold, d_rgba, d_bright, d_mask, d_refined, static_cast<hipStream_t>(stream));
+  return launch_adaptive(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
+                                   W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream)}, ss, threshold, d_mask, d_refined);
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

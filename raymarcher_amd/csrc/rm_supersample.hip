@@ -51,25 +51,15 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
   if (bright) bright[o] = make_float4(v[4] * scale, v[5] * scale, v[6] * scale, v[7] * scale);
 }
 
-namespace {
-template <int BULB, bool ENV, bool TEX>
-void launch_ss(bool sec, dim3 grid, dim3 block, hipStream_t stream, const SceneBlock *sb, int W, int H, int ss, float4 *o, float4 *b) {
-  if (sec) hipLaunchKernelGGL((render_ss_kernel<BULB, ENV, TEX, true>), grid, block, 0, stream, sb, W, H, ss, o, b);
-  else hipLaunchKernelGGL((render_ss_kernel<BULB, ENV, TEX, false>), grid, block, 0, stream, sb, W, H, ss, o, b);
-}
-}  // namespace
-
-// The class set of launch_production (rm_kernels.hip) and nothing more: the secondary rays compiled in only where they can fire.
+// The production classes (dispatch_class, rm_internal.h) and nothing more.
 int launch_render_ss(const void *sbv, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
                      float *d_rgba, float *d_bright, hipStream_t stream) {
   const SceneBlock *sb = static_cast<const SceneBlock *>(sbv);
   float4 *o = reinterpret_cast<float4 *>(d_rgba), *b = reinterpret_cast<float4 *>(d_bright);
-  if (env && tex) launch_ss<0, true, true>(sec, grid, block, stream, sb, W, H, ss, o, b);
-  else if (env) launch_ss<0, true, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
-  else if (tex) launch_ss<0, false, true>(sec, grid, block, stream, sb, W, H, ss, o, b);
-  else if (bulbClass == kBulbPlain) launch_ss<kBulbPlain, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
-  else if (bulbClass == kBulbGeneral) launch_ss<kBulbGeneral, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
-  else launch_ss<0, false, false>(sec, grid, block, stream, sb, W, H, ss, o, b);
+  dispatch_class(bulbClass, env, tex, sec, [&](auto c) {
+    using K = decltype(c);
+    hipLaunchKernelGGL((render_ss_kernel<K::bulb, K::env, K::tex, K::sec>), grid, block, 0, stream, sb, W, H, ss, o, b);
+  });
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

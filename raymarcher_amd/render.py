@@ -276,11 +276,10 @@ class Renderer:
                                   C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
-    def render_batch(self, tables, settings, W, H, cameras, globals_=None, bright=False, out=None, out_bright=None):
-        """rm_render_batch: N whole frames of the scene in `tables`, frame i seen through cameras[i] (RmCamera, as build_camera
-        returns them) → float32 tensor (N, H, W, 4), row 0 = bottom.  globals_: None (tables.globals_ for every frame), one
-        RmGlobals for every frame, or a sequence of N of them.  out / out_bright: the caller's buffers (out_bright implies
-        bright=True)."""
+    def _render_frames(self, entry, tables, settings, W, H, cameras, globals_, bright, out, out_bright, mid=(), extra=None):
+        """What render_batch, render_supersampled and render_adaptive share: the batch arrays, the checked or fresh (N, H, W, 4)
+        outputs, the resources, the call of lib().<entry> and the return value.  mid: the entry point's arguments between H and
+        d_rgba.  extra(n): its optional outputs after d_bright, tensors or None, which join the returned tuple."""
         cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
         n = len(cameras)
         shape = (n, H, W, 4)
@@ -288,11 +287,20 @@ class Renderer:
         out = self._out(out, shape, t.float32)
         bright = bright or out_bright is not None
         br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
+        more = extra(n) if extra else ()
         res, _keep = self._resources(tables)
-        check(lib().rm_render_batch(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
-                                    C.byref(settings), C.byref(res), W, H, C.c_void_p(out.data_ptr()),
-                                    C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
-        return (out, br) if bright else out
+        ptrs = [C.c_void_p(a.data_ptr()) if a is not None else None for a in (out, br, *more)]
+        check(getattr(lib(), entry)(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
+                                    C.byref(settings), C.byref(res), W, H, *mid, *ptrs, self._stream()))
+        rest = [x for x in (br, *more) if x is not None]
+        return (out, *rest) if rest else out
+
+    def render_batch(self, tables, settings, W, H, cameras, globals_=None, bright=False, out=None, out_bright=None):
+        """rm_render_batch: N whole frames of the scene in `tables`, frame i seen through cameras[i] (RmCamera, as build_camera
+        returns them) → float32 tensor (N, H, W, 4), row 0 = bottom.  globals_: None (tables.globals_ for every frame), one
+        RmGlobals for every frame, or a sequence of N of them.  out / out_bright: the caller's buffers (out_bright implies
+        bright=True)."""
+        return self._render_frames("rm_render_batch", tables, settings, W, H, cameras, globals_, bright, out, out_bright)
 
     def render_supersampled(self, tables, settings, W, H, cameras, ss, globals_=None, bright=False, out=None, out_bright=None):
         """rm_render_supersampled: render_batch with ss × ss samples per pixel (ss = 1, 2 or 4), resolved inside the kernel by the
@@ -300,18 +308,7 @@ class Renderer:
         render_batch's; ss = 1 is render_batch."""
         if ss not in (1, 2, 4):
             raise ValueError(f"ss = {ss!r}: the samples per pixel along each axis are 1, 2 or 4")
-        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
-        n = len(cameras)
-        shape = (n, H, W, 4)
-        t = self.torch
-        out = self._out(out, shape, t.float32)
-        bright = bright or out_bright is not None
-        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
-        res, _keep = self._resources(tables)
-        check(lib().rm_render_supersampled(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights,
-                                           tables.num_lights, C.byref(settings), C.byref(res), W, H, ss, C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
-        return (out, br) if bright else out
+        return self._render_frames("rm_render_supersampled", tables, settings, W, H, cameras, globals_, bright, out, out_bright, mid=(ss,))
 
     def render_adaptive(self, tables, settings, W, H, cameras, ss, threshold, globals_=None, bright=False, out=None, out_bright=None,
                         mask=False, counts=False):
@@ -325,23 +322,16 @@ class Renderer:
         threshold = float(threshold)
         if threshold != threshold:
             raise ValueError("threshold is NaN")
-        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
-        n = len(cameras)
-        shape = (n, H, W, 4)
-        t = self.torch
-        out = self._out(out, shape, t.float32)
-        bright = bright or out_bright is not None
-        br = self._out(out_bright, shape, t.float32, "out_bright") if bright else None
-        want_mask, want_counts = mask is not False and mask is not None, counts is not False and counts is not None
-        m = self._out(None if mask is True else mask, (n, H, W), t.uint8, "mask") if want_mask else None
-        cnt = self._out(None if counts is True else counts, (n,), t.int32, "counts") if want_counts else None
-        res, _keep = self._resources(tables)
-        check(lib().rm_render_adaptive(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
-                                       C.byref(settings), C.byref(res), W, H, ss, threshold, C.c_void_p(out.data_ptr()),
-                                       C.c_void_p(br.data_ptr()) if bright else None, C.c_void_p(m.data_ptr()) if want_mask else None,
-                                       C.c_void_p(cnt.data_ptr()) if want_counts else None, self._stream()))
-        extra = [x for x in (br, m, cnt) if x is not None]
-        return (out, *extra) if extra else out
+
+        def extra(n):
+            t = self.torch
+            want_mask, want_counts = mask is not False and mask is not None, counts is not False and counts is not None
+            m = self._out(None if mask is True else mask, (n, H, W), t.uint8, "mask") if want_mask else None
+            cnt = self._out(None if counts is True else counts, (n,), t.int32, "counts") if want_counts else None
+            return m, cnt
+
+        return self._render_frames("rm_render_adaptive", tables, settings, W, H, cameras, globals_, bright, out, out_bright,
+                                   mid=(ss, threshold), extra=extra)
 
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or

@@ -113,6 +113,39 @@ def test_sample_frames_too_large_are_refused_before_any_hip_call():
         assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=INT_MAX // 8 // ss, H=32768, ss=ss, out=fake)), ss
 
 
+def test_shared_argument_errors_report_in_precedence_order():
+    """An input that violates several checks reports the earliest one.  The walk starts from a call that fails every check and
+    mends them one at a time, in the order the entry point has checked them since it exists (statuses and words written down from
+    the library before the multi-frame launchers shared one checking function)."""
+    L = lib()
+    cams, globs, scene = _batch(3)
+    objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
+    many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
+    for ss in (2, 4):
+        a = dict(cams=None, globs=None, ng=2, n=-1, objs=many, no=abi.RM_MAX_OBJECTS + 1, W=0, H=0, ss=3, out=None)
+        walk = [
+            (dict(), abi.RM_ERR_INVALID_ARGUMENT, "ss (samples per pixel"),
+            (dict(ss=ss), abi.RM_ERR_INVALID_ARGUMENT, "negative numFrames"),
+            (dict(n=abi.RM_MAX_BATCH_FRAMES + 1), abi.RM_ERR_CAPACITY, "RM_MAX_BATCH_FRAMES"),
+            (dict(n=0), abi.RM_OK, None),  # nothing to write: whatever else is wrong
+            (dict(n=3), abi.RM_ERR_INVALID_ARGUMENT, "numGlobals"),
+            (dict(ng=3), abi.RM_ERR_INVALID_ARGUMENT, "null cameras or globals"),
+            (dict(cams=cams), abi.RM_ERR_INVALID_ARGUMENT, "null cameras or globals"),
+            (dict(globs=globs), abi.RM_ERR_INVALID_ARGUMENT, "bad frame size"),
+            (dict(W=INT_MAX // 8 // ss + 1), abi.RM_ERR_INVALID_ARGUMENT, "bad frame size"),  # H = 0 still
+            (dict(H=65536 * 8 // ss), abi.RM_ERR_INVALID_ARGUMENT, "INT_MAX / 8"),             # too wide and too many tiles
+            (dict(W=8), abi.RM_ERR_INVALID_ARGUMENT, "too many samples"),
+            (dict(W=32, H=24), abi.RM_ERR_CAPACITY, "RM_MAX_OBJECTS"),
+            (dict(objs=objs, no=no), abi.RM_ERR_INVALID_ARGUMENT, "null output"),
+        ]
+        for step, (mend, status, word) in enumerate(walk):
+            a.update(mend)
+            got = call(a["cams"], a["globs"], a["ng"], a["n"], a["objs"], a["no"], lights, nl, W=a["W"], H=a["H"], ss=a["ss"], out=a["out"])
+            assert got == status, (ss, step, mend, got, L.rm_last_error().decode())
+            if word is not None:
+                assert word in L.rm_last_error().decode(), (ss, step, mend, L.rm_last_error().decode())
+
+
 def test_python_wrapper_checks_ss_and_lengths():
     from raymarcher_amd.render import Renderer, SceneTables
     W, H = 32, 24
