@@ -41,6 +41,8 @@ extern "C" {
 #define RM_MAX_OBJECTS 30
 /* Frames of one rm_render_batch call. */
 #define RM_MAX_BATCH_FRAMES 1024
+/* Sub-frames (lens samples, shutter times) of one output frame of rm_render_accumulated. */
+#define RM_MAX_SUBFRAMES 64
 
 /* Primitive type tags — src/utils/scenedata.h:18-33 == frag:53-68. */
 enum {
@@ -310,6 +312,38 @@ int rm_render_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGl
                        void *stream);
 
 /*
+ * rm_render_accumulated — the mean of subFrames renders per output frame, taken inside the render kernel: depth of field (the
+ * cameras of rm_camera_lens_samples), motion blur (globals with iTime across the shutter interval), or both (no reference
+ * counterpart: the reference's scenefiles carry aperture and focalLength, and no shader reads them).  The shape and every rule of
+ * rm_render_batch — one scene, numFrames·H·W float4 per output with rows bottom-up, d_bright may be NULL, asynchronous on `stream`,
+ * host arrays copied before return — with subFrames cameras per output frame: cams holds numFrames·subFrames of them, sub-frame j
+ * of output frame f is cams[f·subFrames + j], and numGlobals is 1 (globals[0] for every sub-frame) or numFrames·subFrames with the
+ * same indexing.
+ * Definition of a pixel.  Let S_j be the frame rm_render_batch writes for sub-frame j of f.  With n = subFrames: acc = S_0, then
+ * acc = acc + S_j for j = 1 … n − 1 in that order, each add one binary32 round-to-nearest add, denormals kept, all four channels,
+ * fragColor and BrightColor alike; then out = acc · c, c the binary32 value of 1.0f / (float)n (one IEEE division, then one
+ * multiply).  In NumPy on float32 arrays: acc = S[0].copy(); for j in 1 … n − 1: acc = acc + S[j];
+ * out = acc * (np.float32(1) / np.float32(n)).  The order is sequential on purpose: a wave loops over the sub-frames with one
+ * wave-uniform scene block at a time and one running sum per channel.  subFrames == 1 is rm_render_batch, exactly (c = 1).  The
+ * result is defined bit for bit, and no subFrames-sized image exists in device memory: the caller's numFrames outputs are all the
+ * pixels there are, where rm_render_batch of every sub-frame plus a reduction needs 32 B per pixel per sub-frame with d_bright
+ * (4.2 GB for a 3840×2160 still of 16 lens samples).
+ * RM_ERR_INVALID_ARGUMENT: subFrames < 1 or > RM_MAX_SUBFRAMES; numGlobals neither 1 nor numFrames·subFrames; W or H above
+ * INT_MAX / 8, or more 8×8 tiles than one launch can index (more than 65535 rows of them, or more than INT_MAX per frame);
+ * RM_ERR_CAPACITY: numFrames·subFrames > RM_MAX_BATCH_FRAMES (one scene block is staged per sub-frame); numFrames == 0: RM_OK;
+ * everything rm_render_batch refuses, with its codes.  All of these are checked before any HIP call.
+ * Schedule: ONE launch of the accumulating kernel over every output frame (rm_debug_last_path() = 9, rm_debug_last_split() = 0), 8×8
+ * tiles in raster order: no wavefront pipeline (rm_set_kernel_path is not consulted), no light split, no tile-shape pin, no tile
+ * order, no library workspace; it uses the batch ring of scene blocks (one block per sub-frame — the only memory that grows with
+ * subFrames, ≈9.7 KB each) and neither reads nor changes the per-stream tuner and tile-order state of single-frame renders.  With
+ * rm_set_timing(1) it counts as one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_render_accumulated(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, int subFrames,
+                          const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmSettings *s,
+                          const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -424,7 +458,7 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled, and so does a whole call of rm_render_adaptive.
+ * launch of rm_render_supersampled or rm_render_accumulated, and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -453,7 +487,8 @@ int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
- * with ss > 1, 8 = a call of rm_render_adaptive (none of them is a value rm_set_kernel_path takes). */
+ * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated (none of them is a value
+ * rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups
@@ -613,6 +648,17 @@ typedef struct RmCameraData {
 } RmCameraData;
 int rm_camera_build(const RmCameraData *cd, int W, int H, float nearPlane, float farPlane,
                     float view[16], float proj[16], RmCamera *out);
+/* The n cameras of a thin lens, for rm_render_accumulated (no reference counterpart).  out[0] is rm_camera_build(cd, …) exactly: the
+ * pinhole at the lens centre.  out[k], k >= 1, is rm_camera_build of a copy of cd whose pos is shifted on the lens disc by
+ * lensRadius · r_k · (cos θ_k · right + sin θ_k · trueUp), r_k = sqrt(k / (n − 1)), θ_k = k · π(3 − √5) (the golden-angle spiral:
+ * equal areas per sample, the last on the rim), and whose look points from the shifted position at the focus point
+ * pos + focusDistance · normalize(look); right and trueUp are the camera's own axes (u and v of camera.cpp:8-34).  Everything up to
+ * the shifted pos and look is computed in double and rounded once to float.  A point at focusDistance along the view direction
+ * projects to the same pixel in every sample; everything nearer or farther spreads over a disc.  A sample whose shift rounds to nothing
+ * (lensRadius = 0: every one) is out[0] bit for bit.  Both lengths are in world units.  RM_ERR_INVALID_ARGUMENT: n < 1, lensRadius negative or not finite, focusDistance not
+ * positive or not finite, null cd / out, and what rm_camera_build refuses. */
+int rm_camera_lens_samples(const RmCameraData *cd, int W, int H, float nearPlane, float farPlane, float lensRadius,
+                           float focusDistance, int n, RmCamera *out);
 
 /* Opaque parsed scene — SceneParser::parse (src/utils/sceneparser.cpp:117-133) +
  * RayMarchScene::initScene (src/raymarch/raymarchscene.cpp:104-134). */
@@ -627,6 +673,11 @@ const RmObject *rm_scene_objects(const RmScene *scene);
 const RmLight *rm_scene_lights(const RmScene *scene);
 int rm_scene_globals(const RmScene *scene, const RmHostSettings *hs, RmGlobals *out);
 int rm_scene_camera_data(const RmScene *scene, RmCameraData *out);
+/* The scenefile's cameraData.aperture and cameraData.focalLength (scenedata.h:117-118, "Only applicable for depth of field"), 0 for
+ * a field the file does not have.  The reference parses both and gives them no meaning — no shader reads them; this library reads
+ * aperture as the radius of the lens and focalLength as the distance to the plane in focus, both in world units: the lensRadius and
+ * focusDistance of rm_camera_lens_samples. */
+int rm_scene_camera_lens(const RmScene *scene, float *aperture, float *focalLength);
 /* Texture file referenced by object i, or NULL; load it with rm_image_load(path, 1, …) into RmResources.textures[texLoc]. */
 const char *rm_scene_object_texture(const RmScene *scene, int i);
 

@@ -39,6 +39,9 @@ SIGNATURES = {
     "rm_render_adaptive": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, C.c_int, _P(abi.RmObject), C.c_int,
                                      _P(abi.RmLight), C.c_int, _P(abi.RmSettings), _P(abi.RmResources), C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_render_accumulated": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, C.c_int, C.c_int, _P(abi.RmObject), C.c_int,
+                                        _P(abi.RmLight), C.c_int, _P(abi.RmSettings), _P(abi.RmResources), C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
     "rm_skybox_face_path": (C.c_char_p, [C.c_int, C.c_int]),
@@ -97,6 +100,8 @@ SIGNATURES = {
     "rm_host_settings_default": (None, [_P(abi.RmHostSettings)]),
     "rm_camera_build": (C.c_int, [_P(abi.RmCameraData), C.c_int, C.c_int, C.c_float, C.c_float, _P(C.c_float),
                                   _P(C.c_float), _P(abi.RmCamera)]),
+    "rm_camera_lens_samples": (C.c_int, [_P(abi.RmCameraData), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                         _P(abi.RmCamera)]),
     "rm_scene_load": (C.c_int, [C.c_char_p, _P(C.c_void_p)]),
     "rm_scene_load_string": (C.c_int, [C.c_char_p, _P(C.c_void_p)]),
     "rm_scene_free": (None, [C.c_void_p]),
@@ -106,6 +111,7 @@ SIGNATURES = {
     "rm_scene_lights": (_P(abi.RmLight), [C.c_void_p]),
     "rm_scene_globals": (C.c_int, [C.c_void_p, _P(abi.RmHostSettings), _P(abi.RmGlobals)]),
     "rm_scene_camera_data": (C.c_int, [C.c_void_p, _P(abi.RmCameraData)]),
+    "rm_scene_camera_lens": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
     "rm_scene_object_texture": (C.c_char_p, [C.c_void_p, C.c_int]),
     "rm_write_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "rm_abi_sizeof": (C.c_int, [C.c_int]),

@@ -10,6 +10,7 @@ RM_COUNT_REFERENCE, RM_COUNT_EXECUTED = 1, 2
 RM_MAX_LIGHTS = 10
 RM_MAX_OBJECTS = 30
 RM_MAX_BATCH_FRAMES = 1024  # frames of one rm_render_batch call
+RM_MAX_SUBFRAMES = 64  # sub-frames of one output frame of rm_render_accumulated
 
 (RM_CUBE, RM_CONE, RM_CYLINDER, RM_SPHERE, RM_OCTAHEDRON, RM_TORUS, RM_CAPSULE, RM_DEATHSTAR, RM_RECTANGLE,
  RM_MANDELBROT, RM_MANDELBULB, RM_MENGERSPONGE, RM_SIERPINSKI, RM_CUSTOM) = range(14)

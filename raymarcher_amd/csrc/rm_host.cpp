@@ -140,6 +140,40 @@ int rm_camera_build(const RmCameraData *cd, int W, int H, float nearPlane, float
   return RM_OK;
 }
 
+// The thin lens of rm_render_accumulated: sample 0 the pinhole, the others on the golden-angle spiral over the lens disc, every one
+// looking at the focus point.  The camera's axes as rm_camera_build forms them (w = −normalize(look), v = normalize(up − (up·w)w),
+// u = v × w), here in double; each sample's pos and look are rounded to float once and handed to rm_camera_build.
+int rm_camera_lens_samples(const RmCameraData *cd, int W, int H, float nearPlane, float farPlane, float lensRadius,
+                           float focusDistance, int n, RmCamera *out) {
+  if (!cd || !out) { set_error("null argument"); return RM_ERR_INVALID_ARGUMENT; }
+  if (n < 1) { set_error("lens samples: n must be at least 1"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!std::isfinite(lensRadius) || lensRadius < 0.0f) { set_error("lens radius must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!std::isfinite(focusDistance) || !(focusDistance > 0.0f)) { set_error("focus distance must be finite and positive"); return RM_ERR_INVALID_ARGUMENT; }
+  if (int st = rm_camera_build(cd, W, H, nearPlane, farPlane, nullptr, nullptr, &out[0])) return st;  // incl. the checks of look and up
+  const double l[3] = {cd->look[0], cd->look[1], cd->look[2]}, up[3] = {cd->up[0], cd->up[1], cd->up[2]};
+  const double ll = std::sqrt(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+  const double w[3] = {-l[0] / ll, -l[1] / ll, -l[2] / ll};
+  const double duw = up[0] * w[0] + up[1] * w[1] + up[2] * w[2];
+  double v[3] = {up[0] - duw * w[0], up[1] - duw * w[1], up[2] - duw * w[2]};
+  const double vl = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  for (double &c : v) c /= vl;
+  const double u[3] = {v[1] * w[2] - w[1] * v[2], v[2] * w[0] - w[2] * v[0], v[0] * w[1] - w[0] * v[1]};
+  const double kGoldenAngle = 3.14159265358979323846 * (3.0 - std::sqrt(5.0));
+  for (int k = 1; k < n; k++) {
+    const double r = (double)lensRadius * std::sqrt((double)k / (double)(n - 1)), th = (double)k * kGoldenAngle;
+    RmCameraData s = *cd;
+    for (int i = 0; i < 3; i++) {
+      s.pos[i] = (float)((double)cd->pos[i] + r * (std::cos(th) * u[i] + std::sin(th) * v[i]));
+      // from the position the sample really has (the rounded one) at the focus point
+      s.look[i] = (float)(((double)cd->pos[i] - (double)focusDistance * w[i]) - (double)s.pos[i]);
+    }
+    // a shift that rounds to nothing (lensRadius = 0 above all) is the pinhole itself, look vector and all: bit-equal to out[0]
+    if (s.pos[0] == cd->pos[0] && s.pos[1] == cd->pos[1] && s.pos[2] == cd->pos[2]) { out[k] = out[0]; continue; }
+    if (int st = rm_camera_build(&s, W, H, nearPlane, farPlane, nullptr, nullptr, &out[k])) return st;
+  }
+  return RM_OK;
+}
+
 int rm_shard_rows(int H, int tileRows, int shard, int numShards) {
   if (H <= 0 || tileRows <= 0 || numShards <= 0 || shard < 0 || shard >= numShards) return -1;
   return shard_rows(H, tileRows, shard, numShards, root_relief());

@@ -54,6 +54,11 @@ int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, i
 // translation unit of its own, so that the code objects of rm_kernels.hip do not depend on it.
 int launch_render_ss(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
                      float *d_rgba, float *d_bright, hipStream_t stream);
+// The accumulating kernels (rm_accumulate.hip, rm_render_accumulated; a translation unit of its own for the same reason): the
+// launch of render_acc_kernel<bulbClass, env, tex, sec> over the staged SceneBlocks `sb` — n per frame of grid.z, frame f's at
+// sb[f·n] … sb[f·n + n − 1] — into W × H output pixels per frame: their sum in index order, times 1.0f / n.
+int launch_render_acc(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int n,
+                      float *d_rgba, float *d_bright, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the
@@ -100,8 +105,8 @@ constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
 // The single-Mandelbulb class (the kernels' BULB template parameter; 0 = the table walk): any object transform, power and
 // Julia seed, or the plain form that SceneBlock::bulbPlain describes.
 constexpr int kBulbGeneral = 1, kBulbPlain = 2;
-// The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel and adaptive_refine_kernel
-// are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
+// The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel, adaptive_refine_kernel and
+// render_acc_kernel are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
 // then the plain table walk, each with main's secondary rays compiled in only where they can fire (sec).
 template <int BULB, bool ENV, bool TEX, bool SEC>
 struct KernelClass { static constexpr int bulb = BULB; static constexpr bool env = ENV, tex = TEX, sec = SEC; };

@@ -1526,24 +1526,35 @@ int row_range(int H, int rowBegin, int rowEnd, RowMap *map, int *nRows) {
 }
 
 // ---- multi-frame calls: numFrames whole frames of one scene, each with its own camera and globals -----------------------------
-// What rm_render_batch, rm_render_supersampled and rm_render_adaptive are all called with.
+// What rm_render_batch, rm_render_supersampled, rm_render_adaptive and rm_render_accumulated are all called with.  subFrames
+// (rm_render_accumulated; 1 everywhere else): an output frame is made of that many cameras and globals, each staged as a scene
+// block of its own — blocks() of them, block f·subFrames + j for sub-frame j of frame f — and globalsOf counts blocks.
 struct FrameCall {
   const RmCamera *cams; const RmGlobals *globals; int numGlobals, numFrames;
   const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
   const RmSettings *s; const RmResources &res;
   int W, H; float *d_rgba, *d_bright; hipStream_t stream;
-  const RmGlobals *globalsOf(int f) const { return &globals[numGlobals == 1 ? 0 : f]; }
+  int subFrames = 1;
+  long long blocks() const { return (long long)numFrames * subFrames; }
+  const RmGlobals *globalsOf(int b) const { return &globals[numGlobals == 1 ? 0 : b]; }
 };
-// The argument checks the three entry points share, every one ahead of the first HIP call (as launch_render's); an input that
+// The argument checks the four entry points share, every one ahead of the first HIP call (as launch_render's); an input that
 // fails several reports the first of this order.  numFrames = 0 passes: nothing to write, the caller returns RM_OK.  sampled: the
 // call renders an ss·W × ss·H sample frame (rm_render_supersampled; rm_render_adaptive, which checks it for ss = 1 too), whose
 // coordinates and tiles must fit the kernels' indices.  sizeCheck: the entry point's own check of the frame size, between those
 // and the scene's.
 int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(const FrameCall &) = nullptr) {
   if (c.numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  // one scene block per sub-frame: the cap counts blocks
+  if (c.blocks() > RM_MAX_BATCH_FRAMES) {
+    set_error(c.subFrames == 1 ? "numFrames exceeds RM_MAX_BATCH_FRAMES" : "numFrames·subFrames exceeds RM_MAX_BATCH_FRAMES");
+    return RM_ERR_CAPACITY;
+  }
   if (c.numFrames == 0) return RM_OK;
-  if (c.numGlobals != 1 && c.numGlobals != c.numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numGlobals != 1 && c.numGlobals != c.blocks()) {
+    set_error(c.subFrames == 1 ? "numGlobals must be 1 or numFrames" : "numGlobals must be 1 or numFrames·subFrames");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
   if (!c.cams || !c.globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
   if (c.W <= 0 || c.H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
   if (sampled) {
@@ -1563,9 +1574,9 @@ int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(cons
 
 // What the staging step hands a multi-frame launcher.
 struct StagedFrames {
-  Slot *slot = nullptr;   // of the batch ring: one scene block per frame (not per sample), filled and uploaded
+  Slot *slot = nullptr;   // of the batch ring: one scene block per frame (not per sample) and sub-frame, filled and uploaded
   FrameClass fc{};        // shared by every frame
-  bool plainBulb = true;  // the plain bulb form only where every frame has it
+  bool plainBulb = true;  // the plain bulb form only where every frame (and sub-frame) has it
   int bulbClass = 0;      // bulb_class of the two
   LaunchTimer timer;      // stamped once, ahead of the caller's launches
   explicit StagedFrames(hipStream_t stream) : timer(stream) {}
@@ -1574,14 +1585,15 @@ struct StagedFrames {
 // acquire_slot at the ring's bounds.  tileShift: the tile shape of the launch (LaunchFields).  alone (or null): the frames that
 // are not part of the launch (launch_batch), which have no say in plainBulb.
 int stage_frames(DeviceState &ds, const FrameCall &c, int tileShift, const char *alone, StagedFrames *sf) {
-  for (int f = 0; f < c.numFrames; f++)
+  const int blocks = (int)c.blocks();  // = numFrames but for rm_render_accumulated (which passes no `alone`)
+  for (int f = 0; f < blocks; f++)
     if (!alone || !alone[f]) sf->plainBulb = sf->plainBulb && bulb_plain(c.objs, c.numObjects, c.globalsOf(f));
-  int st = acquire_slot(ds.batches, c.numFrames, &sf->slot);
+  int st = acquire_slot(ds.batches, blocks, &sf->slot);
   if (st != RM_OK) return st;
-  fill_frames(sf->slot->host, c.numFrames, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+  fill_frames(sf->slot->host, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
   LaunchFields lf;
   lf.tileShift = tileShift;
-  if ((st = upload_frames(*sf->slot, c.numFrames, lf, c.stream)) != RM_OK) return st;
+  if ((st = upload_frames(*sf->slot, blocks, lf, c.stream)) != RM_OK) return st;
   sf->fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.globalsOf(0), c.s, 0);
   sf->bulbClass = bulb_class(sf->fc, sf->plainBulb);
   return sf->timer.stamp();
@@ -1727,6 +1739,29 @@ int launch_adaptive(const FrameCall &c, int ss, float threshold, uint8_t *d_mask
   return finish_frames(*ds, sf, 8, c.stream);
 }
 
+// ---- accumulated frames: the mean of subFrames renders per output frame, summed in the lane (render_acc_kernel) -----------------
+// rm_render_accumulated (the header has the definition).  A batch's staging with one scene block per SUB-frame — numFrames·subFrames
+// of them in one slot of the batch ring, which is all that grows with subFrames: "one block per sub-frame" also leaves room for
+// per-sub-frame object tables later — then ONE launch over (tilesX, tilesY, numFrames) 8×8 tiles in raster order whose lanes walk
+// their frame's blocks: no wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state read or written, no
+// library workspace.  The kernels are a translation unit of their own (rm_accumulate.hip).  subFrames = 1 takes the same launch:
+// the sum of one frame is that frame and the scale is 1, so the bits are rm_render_batch's.
+int launch_accumulated(const FrameCall &c) {
+  if (c.subFrames < 1 || c.subFrames > RM_MAX_SUBFRAMES) { set_error("subFrames must be 1 … RM_MAX_SUBFRAMES"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = check_frames(c, 1, true);  // the frame's coordinates and tiles come from blockIdx, as a sample frame's do
+  if (st != RM_OK || c.numFrames == 0) return st;
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  const int nw = waves_per_block();
+  const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
+  if ((st = launch_render_acc(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, grid, block, c.W, c.H,
+                              c.subFrames, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
+  return finish_frames(*ds, sf, 9, c.stream);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1803,6 +1838,13 @@ int rm_render_adaptive(const RmCamera *cams, const RmGlobals *globals, int numGl
                        int ss, float threshold, float *d_rgba, float *d_bright, uint8_t *d_mask, uint32_t *d_refined, void *stream) {
   return launch_adaptive(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
                                    W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream)}, ss, threshold, d_mask, d_refined);
+}
+
+int rm_render_accumulated(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, int subFrames,
+                          const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmSettings *s,
+                          const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream) {
+  return launch_accumulated(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
+                                      W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream), subFrames});
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

@@ -213,6 +213,7 @@ struct RmScene {
   std::vector<std::string> textures;  // per object ("" if none)
   float ka = 0, kd = 0, ks = 0, kt = 0;
   RmCameraData cam{};
+  float aperture = 0, focalLength = 0;  // cameraData's lens fields, 0 where the file has none (rm_scene_camera_lens)
 };
 
 namespace rm {
@@ -285,9 +286,15 @@ struct Reader {
     double ha;
     if (!num(c, "heightAngle", &ha, "cameraData")) return false;
     cd.heightAngle = (float)(ha * kPi / 180.0);
-    double dummy;
-    if (c.has("aperture") && !num(c, "aperture", &dummy, "cameraData")) return false;
-    if (c.has("focalLength") && !num(c, "focalLength", &dummy, "cameraData")) return false;
+    double lens;
+    if (c.has("aperture")) {
+      if (!num(c, "aperture", &lens, "cameraData")) return false;
+      sc.aperture = (float)lens;
+    }
+    if (c.has("focalLength")) {
+      if (!num(c, "focalLength", &lens, "cameraData")) return false;
+      sc.focalLength = (float)lens;
+    }
     if (c.has("look")) {
       if (!vec(c, "look", 3, cd.look, "cameraData")) return false;
       cd.look[3] = 0.0f;
@@ -629,6 +636,12 @@ int rm_scene_globals(const RmScene *scene, const RmHostSettings *hs, RmGlobals *
 int rm_scene_camera_data(const RmScene *scene, RmCameraData *out) {
   if (!scene || !out) { set_error("null argument"); return RM_ERR_INVALID_ARGUMENT; }
   *out = scene->cam;
+  return RM_OK;
+}
+int rm_scene_camera_lens(const RmScene *scene, float *aperture, float *focalLength) {
+  if (!scene || !aperture || !focalLength) { set_error("null argument"); return RM_ERR_INVALID_ARGUMENT; }
+  *aperture = scene->aperture;
+  *focalLength = scene->focalLength;
   return RM_OK;
 }
 const char *rm_scene_object_texture(const RmScene *scene, int i) {

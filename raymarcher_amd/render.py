@@ -106,6 +106,13 @@ class Scene:
         check(lib().rm_scene_camera_data(self._h, C.byref(cd)))
         return cd
 
+    def lens(self):
+        """rm_scene_camera_lens: the scenefile's (aperture, focalLength), which this library reads as the lens radius and the
+        focus distance of lens_cameras, in world units; 0.0 for a field the file does not have."""
+        a, f = C.c_float(), C.c_float()
+        check(lib().rm_scene_camera_lens(self._h, C.byref(a), C.byref(f)))
+        return a.value, f.value
+
     def texture_of(self, i):
         t = lib().rm_scene_object_texture(self._h, i)
         return t.decode() if t else None
@@ -144,6 +151,40 @@ class Scene:
                     textures[objs[i].texLoc] = np.array([[[0, 0, 0, 255]]], dtype=np.uint8)
         tex_list = [textures[k] for k in sorted(textures)] if textures else None
         return SceneTables(cam, objs, no, lights, nl, g, tex_list)
+
+
+def lens_cameras(camera_data, W, H, radius, focus, n, near=0.1, far=100.0):
+    """rm_camera_lens_samples: the n cameras of a thin lens of `radius` focused at distance `focus` along the view direction of
+    `camera_data` (an RmCameraData, e.g. Scene.camera_data()) → a list of n RmCamera for Renderer.render_accumulated.  The first
+    is the pinhole camera itself."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n = {n}: a lens needs at least one sample")
+    out = (abi.RmCamera * n)()
+    check(lib().rm_camera_lens_samples(C.byref(camera_data), W, H, near, far, radius, focus, n, out))
+    cams = []
+    for c in out:  # copies that own their memory, not views into the array
+        cam = abi.RmCamera()
+        C.memmove(C.byref(cam), C.byref(c), C.sizeof(abi.RmCamera))
+        cams.append(cam)
+    return cams
+
+
+def shutter_globals(globals_, t_open, t_close, n):
+    """n copies of the RmGlobals `globals_` with iTime at the midpoints of the n equal parts of the shutter interval
+    [t_open, t_close] — t_open + (j + 0.5)·(t_close − t_open) / n, computed in float64 and rounded once — for
+    Renderer.render_accumulated."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n = {n}: a shutter interval needs at least one sample")
+    t_open, t_close = float(t_open), float(t_close)
+    out = []
+    for j in range(n):
+        g = abi.RmGlobals()
+        C.memmove(C.byref(g), C.byref(globals_), C.sizeof(abi.RmGlobals))
+        g.iTime = t_open + (j + 0.5) * (t_close - t_open) / n  # the c_float field rounds the float64 value once
+        out.append(g)
+    return out
 
 
 def batch_arrays(cameras, globals_):
@@ -276,12 +317,15 @@ class Renderer:
                                   C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
-    def _render_frames(self, entry, tables, settings, W, H, cameras, globals_, bright, out, out_bright, mid=(), extra=None):
-        """What render_batch, render_supersampled and render_adaptive share: the batch arrays, the checked or fresh (N, H, W, 4)
-        outputs, the resources, the call of lib().<entry> and the return value.  mid: the entry point's arguments between H and
-        d_rgba.  extra(n): its optional outputs after d_bright, tensors or None, which join the returned tuple."""
+    def _render_frames(self, entry, tables, settings, W, H, cameras, globals_, bright, out, out_bright, mid=(), extra=None,
+                       sub_frames=None):
+        """What render_batch, render_supersampled, render_adaptive and render_accumulated share: the batch arrays, the checked or
+        fresh (N, H, W, 4) outputs, the resources, the call of lib().<entry> and the return value.  mid: the entry point's arguments
+        between H and d_rgba.  extra(n): its optional outputs after d_bright, tensors or None, which join the returned tuple.
+        sub_frames (render_accumulated): that many cameras per output frame, passed behind numFrames."""
         cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
-        n = len(cameras)
+        n = len(cameras) if sub_frames is None else len(cameras) // sub_frames
+        counts = (n,) if sub_frames is None else (n, sub_frames)
         shape = (n, H, W, 4)
         t = self.torch
         out = self._out(out, shape, t.float32)
@@ -290,7 +334,7 @@ class Renderer:
         more = extra(n) if extra else ()
         res, _keep = self._resources(tables)
         ptrs = [C.c_void_p(a.data_ptr()) if a is not None else None for a in (out, br, *more)]
-        check(getattr(lib(), entry)(cams, globs, len(globs), n, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
+        check(getattr(lib(), entry)(cams, globs, len(globs), *counts, tables.objects, tables.num_objects, tables.lights, tables.num_lights,
                                     C.byref(settings), C.byref(res), W, H, *mid, *ptrs, self._stream()))
         rest = [x for x in (br, *more) if x is not None]
         return (out, *rest) if rest else out
@@ -332,6 +376,19 @@ class Renderer:
 
         return self._render_frames("rm_render_adaptive", tables, settings, W, H, cameras, globals_, bright, out, out_bright,
                                    mid=(ss, threshold), extra=extra)
+
+    def render_accumulated(self, tables, settings, W, H, cameras, sub_frames, globals_=None, bright=False, out=None, out_bright=None):
+        """rm_render_accumulated: N = len(cameras) / sub_frames frames, frame f the mean of render_batch's frames for
+        cameras[f·sub_frames : (f + 1)·sub_frames] — summed in that order inside the kernel, then · 1 / sub_frames; the definition is
+        in include/raymarcher_amd.h — → float32 tensor (N, H, W, 4), row 0 = bottom.  Depth of field: lens_cameras(...); motion
+        blur: globals_=shutter_globals(...).  globals_: None (tables.globals_ for every sub-frame), one RmGlobals, or one per
+        camera.  Every other argument as render_batch's; sub_frames = 1 is render_batch."""
+        if not isinstance(sub_frames, int) or isinstance(sub_frames, bool) or not 1 <= sub_frames <= abi.RM_MAX_SUBFRAMES:
+            raise ValueError(f"sub_frames = {sub_frames!r}: an integer from 1 to RM_MAX_SUBFRAMES = {abi.RM_MAX_SUBFRAMES}")
+        if len(cameras) % sub_frames:
+            raise ValueError(f"{len(cameras)} cameras are not a whole number of frames of {sub_frames} sub-frames")
+        return self._render_frames("rm_render_accumulated", tables, settings, W, H, cameras, globals_, bright, out, out_bright,
+                                   sub_frames=sub_frames)
 
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
@@ -445,16 +502,23 @@ class Renderer:
         check(lib().rm_frames_to_rgba8(C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()), W, H, n, self._stream()))
         return out
 
-    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1, adaptive=None):
+    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1, adaptive=None, accumulate=None):
         """The finished images of an exported sequence: render_batch (with the BrightColor planes only when bloom is on), then
         post_process_batch in place (skipped for post=None), then to_rgba8_batch → uint8 (N, H, W, 4), each image's top row
         first.  post: one RmPostSettings or a sequence of N (see post_process_batch).  supersample = 2 or 4: the render step is
         render_supersampled with that many samples per pixel along each axis (bloom then sees the resolved BrightColor).
         adaptive = t: the render step is render_adaptive(…, supersample, t) — those samples only where the 1-sample frame shows
-        contrast above t."""
-        ps = post_array(post, len(cameras)) if post is not None else None
+        contrast above t.  accumulate = n: the render step is render_accumulated(…, n) — len(cameras) / n images, each the mean of n
+        consecutive cameras (and globals); not together with supersample > 1 or adaptive."""
+        if accumulate is not None and (supersample != 1 or adaptive is not None):
+            raise ValueError("accumulate cannot be combined with supersample > 1 or adaptive")
+        if accumulate is not None and (not isinstance(accumulate, int) or accumulate < 1 or len(cameras) % accumulate):
+            raise ValueError(f"accumulate = {accumulate!r}: a positive integer that divides the {len(cameras)} cameras")
+        ps = post_array(post, len(cameras) // (accumulate or 1)) if post is not None else None
         bloom = ps is not None and bool(ps[0].enableBloom)
-        if adaptive is not None:
+        if accumulate is not None:
+            frames = self.render_accumulated(tables, settings, W, H, cameras, accumulate, globals_, bright=bloom)
+        elif adaptive is not None:
             frames = self.render_adaptive(tables, settings, W, H, cameras, supersample, adaptive, globals_, bright=bloom)
         elif supersample == 1:
             frames = self.render_batch(tables, settings, W, H, cameras, globals_, bright=bloom)
