@@ -1,6 +1,6 @@
 // rm_accumulate.hip — the kernels of rm_render_accumulated (gfx950 only): the per-pixel raymarch of rm_kernels.hip over the n
 // sub-frames (lens samples, shutter times) of an output frame, summed in the lane that rendered them.  The launcher (argument
-// checks, staging, schedule) is launch_accumulated in rm_kernels.hip; the kernels live here so that adding them leaves the code
+// checks, staging, schedule) is launch_accumulated in rm_launcher.hip; the kernels live here so that adding them leaves the code
 // objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // rm_adaptive.hip — the kernels of rm_render_adaptive (gfx950 only): the contrast test over a finished 1-sample frame and the
 // supersampling of the pixels it flags.  The launcher (argument checks, staging, chunks, schedule) is launch_adaptive in
-// rm_kernels.hip; the kernels live here so that adding them leaves the code objects of the existing kernels as they were.
+// rm_launcher.hip; the kernels live here so that adding them leaves the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 
 #include "rm_device.hip.h"

@@ -1,4 +1,4 @@
-// rm_internal.h — helpers shared by the launcher (rm_kernels.hip) and the host side (rm_host.cpp).
+// rm_internal.h — helpers shared by the launcher (rm_launcher.hip), the kernels' translation units and the host side (rm_host.cpp).
 #pragma once
 #include <initializer_list>
 #include <mutex>
@@ -36,7 +36,7 @@ int require_device_pointers(std::initializer_list<std::pair<const char *, const 
       return RM_ERR_DEVICE;                                                                       \
     }                                                                                             \
   } while (0)
-// Takes the launcher's lock of the current device (rm_kernels.hip).  Whoever enqueues work on a buffer of stream_workspace
+// Takes the launcher's lock of the current device (rm_launcher.hip).  Whoever enqueues work on a buffer of stream_workspace
 // holds it from that call to its last launch: rm_release_workspaces takes it too, so it never frees a buffer in use.
 int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
@@ -49,6 +49,28 @@ int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 bool sdscene_variant_exists(int bulbClass, int count, int trap, int skip, int track, bool one);
 int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, int skip, int track, int one, const float *d_pts,
                            const float *d_ub, float *d_out, int n, hipStream_t stream);
+// The other test-only probes of rm_probe.hip: rm_probe_math's kernel, the plain sdScene probe on a staged SceneBlock and the
+// 2^32-input checker of the cheap exact forms (rm_debug_check_math; `d_out5` zeroed by the caller, default stream).
+int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, float *d_out, int n, hipStream_t stream);
+int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream);
+void launch_check_math(unsigned long long *d_out5);
+// The kernels of rm_kernels.hip, as the launcher calls them (the structs are rm_launch.h's, FrameClass rm_frame.h's).  Scene prep:
+// the sponge uniforms of the n staged blocks.  Tile order: the ordering launches of a plan, ahead of the render.  Wavefront: the
+// pipeline's generations (skip: its kernels take the table walk's pass-over test).  dispatch_render: the one-lane-per-pixel kernel
+// of the frame's class — counted, light-split or production — over r's grid.  Then the conversion kernels of the entry points
+// named after them, arguments already checked.
+struct SceneBlock; struct RenderLaunch; struct TileOrderPlan; struct SplitPlan; struct Wavefront; struct FrameClass;
+int launch_scene_prep(SceneBlock *sb, int n, hipStream_t stream);
+int launch_tile_order(const TileOrderPlan &p, const RenderLaunch &r, int tileWpx, int tileH, int tileCount);
+void launch_wavefront(bool skip, const RenderLaunch &r, const Wavefront &wf, int bounces, int numLights, int numCUs);
+int dispatch_render(const FrameClass &fc, int count, bool plainBulb, const SplitPlan &ls, int numLights, int tileCount,
+                    const RenderLaunch &r);
+int launch_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, int numFrames, hipStream_t stream);
+int launch_tiles_to_rgba8(const float *d_tiles, uint8_t *d_tiles8, size_t n, hipStream_t stream);
+int launch_deinterleave(const float *d_gathered, float *d_frame, int W, int H, int tileRows, int numShards, int shardStrideRows,
+                        int relief, hipStream_t stream);
+int launch_deinterleave_rgba8(const uint8_t *d_gathered8, uint8_t *d_frame8, int W, int H, int tileRows, int numShards,
+                              int shardStrideRows, int flip, int relief, hipStream_t stream);
 // The supersampling kernels (rm_supersample.hip, rm_render_supersampled): the launch of render_ss_kernel<bulbClass, env, tex, sec>
 // over the staged SceneBlocks `sb` (device pointer; one per frame of grid.z), W × H output pixels of ss × ss samples each.  A
 // translation unit of its own, so that the code objects of rm_kernels.hip do not depend on it.
@@ -147,7 +169,7 @@ __host__ __device__ inline void tile_owner(int t, int N, int K, int &shard, int 
   if (c < N * (K - 1)) { shard = c % N; local = q * (shard == 0 ? K - 1 : K) + c / N; }
   else { shard = c - N * (K - 1) + 1; local = q * K + (K - 1); }
 }
-// ---- the launcher's timed A/B tuners (tile shape, light split: rm_kernels.hip, Tuner) --------------------------------------
+// ---- the launcher's timed A/B tuners (tile shape, light split: rm_launcher.hip, Tuner) --------------------------------------
 // A tuner runs candidate 0 for two frames, then candidate 1 for two frames, `rounds` times over, and times the second frame of
 // each pair in timing slot 2·round + candidate.  After the schedule, and until every timing is in, it runs candidate 0: the
 // enqueue path never waits for the timings.

@@ -1,0 +1,60 @@
+// rm_launch.h — what the launcher (rm_launcher.hip) hands the launch functions of the kernels (rm_kernels.hip; declared in
+// rm_internal.h): the arguments every render launch of a frame shares and the plans of its tile order, light split and
+// wavefront pipeline.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rm_scene_block.h"
+#include "rm_wavefront.h"
+
+namespace rm {
+
+// What every render launch of a frame shares.
+struct RenderLaunch {
+  SceneBlock *sb; RowMap map; int W, H, nRows; float4 *o, *b; unsigned long long *dc;  // the render kernels' arguments
+  hipStream_t stream; dim3 grid, block;
+};
+
+// Tile order ("tile order" in rm_kernels.hip): 0 raster order, 1 feedback — tiles start heaviest-first by the costs the previous frame of this
+// size on this stream recorded.  The plan of one frame, and its carve of the stream's tile-order workspace.
+struct TileOrderPlan {
+  bool ordered = false, byCost = false, byGeom = false, lastSort = false, settled = false;
+  bool combine = false;  // byGeom: the estimates take in the stale costs of the previous picture of this size
+  int ringLog2 = 16, dilate = 0;  // byGeom: tile_geom_kernel's cost of a silhouette tile and its reach into the stale costs (RM_GEOM_*)
+  uint32_t *cost = nullptr, *hist = nullptr, *cost2 = nullptr;
+  int32_t *order = nullptr;
+  bool sorts() const { return (byCost || byGeom) && !settled; }  // the ordering launches run ahead of the render
+};
+
+// The light split of one launch (plan_light_split in rm_launcher.hip has the reasoning).
+struct SplitPlan {
+  int tiles = 0;        // the split tiles of this launch, 0: a plain launch
+  float *store = nullptr;
+  int timedSlot = -1;   // the tuner's timing slot for this launch
+};
+
+// The wavefront pipeline's records (rm_wavefront.hip.h), carved out of the stream's workspace by the launcher.
+struct WfWs {
+  uint32_t *counters;  // [WF_STRIDE·g + …]: source cursor, hit slots reserved, shadow-ray cursor, rays appended for g + 1
+  float4 *rayO[2];     // rays of generation g >= 1 live in buffer g & 1: (origin, path id bits) …
+  float4 *rayD[2];     // … (direction, unused)
+  int4 *hit;           // per hit slot: (src = pixel index (g = 0) or ray index; < 0 = hole, bits of res.d, object, bits of trap.z)
+  float4 *surfP;       // (p, ambient occlusion)
+  float4 *surfN;       // (bumped normal, unused)
+  float *shadow;       // [light·cap + hit slot]: penumbra factor of a ray that missed, kWfShadowHit of one that hit
+  int2 *pathPix;       // paths are indexed by the generation-0 hit slot: (pixel index, object of the primary hit)
+  float4 *pathA;       // (phong.xyz, refl.w)
+  float4 *pathB;       // (refl.xyz, fil.x)
+  float2 *pathC;       // (fil.y, fil.z)
+  uint32_t cap;        // hit-slot capacity
+};
+
+// The wavefront pipeline's launch: whether this frame takes it, its persistent waves, chunk sizes and records.
+struct Wavefront {
+  bool on = false;
+  WfWs ws{};
+  int primaryWaves = 0, shadowWaves = 0, flush = 16;
+  uint32_t slotChunk = 0, maxChunk = 0, rayChunk = 0, pixelChunk = 0;
+};
+
+}  // namespace rm

@@ -1,9 +1,12 @@
-// rm_probe.hip — test-only device probe of the scene evaluator's production instantiations (rm_probe_sdscene_variant).
+// rm_probe.hip — the test-only device probes: the scene evaluator's production instantiations (rm_probe_sdscene_variant), the
+// plain evaluator (rm_probe_sdscene), the rm_math built-ins (rm_probe_math) and the 2^32-input checker of the cheap exact forms
+// (rm_debug_check_math).
 //
-// Kept out of rm_kernels.hip so that the production translation unit's compile time and code stay as they are.  The kernels
+// Kept out of rm_kernels.hip so that the production translation unit's compile time and code stay as they are.  The variant kernels
 // below call the very template functions the render kernels call (sdSceneImpl, sdSceneOne in rm_device.hip.h) with the same
-// template arguments; the launcher (rm_kernels.hip) validates the request and stages the production SceneBlock, then hands it
+// template arguments; the launcher (rm_launcher.hip) validates the request and stages the production SceneBlock, then hands it
 // to launch_sdscene_variant.
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -12,6 +15,47 @@
 #include "rm_internal.h"
 
 namespace rm {
+
+__global__ void probe_math_kernel(int fn, const float *x, const float *y, const float *z, float *out, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a = x[i], b = y ? y[i] : 0.0f, c = z ? z[i] : 0.0f, r = 0.0f;
+  switch (fn) {
+    case RM_FN_SIN: r = sin_(a); break;
+    case RM_FN_COS: r = cos_(a); break;
+    case RM_FN_ACOS: r = acos_(a); break;
+    case RM_FN_ATAN2: r = atan2_(a, b); break;
+    case RM_FN_LOG2: r = log2_(a); break;
+    case RM_FN_EXP2: r = exp2_(a); break;
+    case RM_FN_POW: r = pow_(a, b); break;
+    case RM_FN_SQRT: r = sqrt_(a); break;
+    case RM_FN_DIV: r = a / b; break;
+    case RM_FN_PNOISE3: r = pnoise(v3(a, b, c)); break;
+    case RM_FN_ASIN: r = asin_(a); break;
+    case RM_FN_Q16: r = __half2float(__float2half_rn(a)); break;
+    case RM_FN_SQRT_FAST: r = sqrt_fast_(a); break;
+    case RM_FN_DIVR: r = divr_(a, b); break;
+    case RM_FN_RCP: r = rcp_(a); break;
+    case RM_FN_SMOOTHSTEP: r = smoothstep_(a, b, c); break;
+    case RM_FN_MIN: r = min_(a, b); break;
+    case RM_FN_MAX: r = max_(a, b); break;
+    case RM_FN_FRACT: r = fract_(a); break;
+    case RM_FN_MEDIAN_ABS: r = __builtin_amdgcn_fmed3f(fabs_(a), fabs_(b), fabs_(c)); break;
+  }
+  out[i] = r;
+}
+
+__global__ void probe_sdscene_kernel(const SceneBlock *__restrict__ sb, const float *pts, float *out, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Counters cnt{0, 0, 0, 0, 0, 0};
+  SceneMin m = sdScene<false, 0>(sb, v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), cnt);
+  out[4 * i] = m.d;
+  out[4 * i + 1] = (float)m.idx;
+  out[4 * i + 2] = m.trap.y;
+  out[4 * i + 3] = m.trap.z;
+}
+
 namespace {
 
 // One lane per point, one 64-lane workgroup per wave: point i runs on lane i % 64 of wave i / 64, so every wave-uniform
@@ -98,4 +142,51 @@ int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, i
   return RM_OK;
 }
 
+int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, float *d_out, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_math_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, d_x, d_y, d_z, d_out, n);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_sdscene_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const SceneBlock *>(sb), d_pts, d_out, n);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+
 }  // namespace rm
+
+using namespace rm;
+
+// The cheap exact forms against the IEEE operations for EVERY binary32 input (NaN = NaN): out[0] = inputs where rcp_(y) !=
+// 1.0f / y, out[1] = inputs of the fast range 2^-126 <= |y| < 2^126 where the bare v_rcp_f32 + Newton form differs, out[2] =
+// inputs where sqrt_fast_(x) != sqrtf(x), out[3] = inputs of sqrt_noscale_'s domain (±0, |x| >= 2^-96, ±inf, NaN)
+// where it differs from sqrtf(x), out[4] = inputs where fract_(x) (v_fract_f32) != x − floor(x) kept below 1.  All must be 0.
+extern "C" __global__ void check_math_kernel(unsigned long long *out) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  unsigned long long bad = 0, badFast = 0, badSqrt = 0, badNoscale = 0, badFract = 0;
+  for (uint64_t u = tid; u < (1ull << 32); u += stride) {
+    const float y = u2f((uint32_t)u), ref = 1.0f / y, got = rcp_(y);
+    if (f2u(got) != f2u(ref) && !(got != got && ref != ref)) bad++;
+    const float ay = fabs_(y);
+    if (ay >= 1.17549435e-38f && ay < 8.50705917e37f) {
+      const float r = __builtin_amdgcn_rcpf(y), f = rm::fma(rm::fma(-y, r, 1.0f), r, r);
+      if (f2u(f) != f2u(ref)) badFast++;
+    }
+    const float fd = y - __builtin_floorf(y), fref = (fd >= 1.0f) ? 0.99999994f : fd, fg = fract_(y);
+    if (f2u(fg) != f2u(fref) && !(fg != fg && fref != fref)) badFract++;
+    const float sref = sqrt_(y), sf = sqrt_fast_(y);
+    if (f2u(sf) != f2u(sref) && !(sf != sf && sref != sref)) badSqrt++;
+    if (!(ay > 0.0f && ay < 1.262177448e-29f)) {
+      const float sn = sqrt_noscale_(y);
+      if (f2u(sn) != f2u(sref) && !(sn != sn && sref != sref)) badNoscale++;
+
+    }
+  }
+  if (bad) atomicAdd(&out[0], bad);
+  if (badFast) atomicAdd(&out[1], badFast);
+  if (badSqrt) atomicAdd(&out[2], badSqrt);
+  if (badNoscale) atomicAdd(&out[3], badNoscale);
+  if (badFract) atomicAdd(&out[4], badFract);
+}
+
+void rm::launch_check_math(unsigned long long *d_out5) { check_math_kernel<<<4096, 256>>>(d_out5); }

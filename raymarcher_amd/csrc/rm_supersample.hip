@@ -1,6 +1,6 @@
 // rm_supersample.hip — the kernels of rm_render_supersampled (gfx950 only): the per-pixel raymarch of rm_kernels.hip with ss × ss
 // samples per output pixel, resolved inside the wave.  The launcher (argument checks, staging, schedule) is launch_supersampled in
-// rm_kernels.hip; the kernels live here so that adding them leaves the code objects of the existing kernels as they were.
+// rm_launcher.hip; the kernels live here so that adding them leaves the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 
 #include "rm_device.hip.h"

@@ -26,6 +26,7 @@
 // lights), refraction, scenes with a Mandelbulb or the 2-D Mandelbrot (data-dependent evaluation cost), counting modes.
 #pragma once
 #include "rm_device.hip.h"
+#include "rm_launch.h"
 
 namespace rm {
 
@@ -63,24 +64,7 @@ RM_DEV uint32_t blockAppend(bool want, uint32_t *counter, uint32_t *ldsScratch /
   return slot;
 }
 
-constexpr int kWfMaxBounces = 7;
 constexpr uint32_t kWfShadowHit = 0x7fc00001u;  // shadow result of a ray that hit: a NaN (no penumbra factor is one)
-enum { WF_SRC = 0, WF_HITS = 1, WF_SHADOW = 2, WF_NEXT = 3, WF_STRIDE = 8 };  // counters of one generation
-
-struct WfWs {
-  uint32_t *counters;  // [WF_STRIDE·g + …]: source cursor, hit slots reserved, shadow-ray cursor, rays appended for g + 1
-  float4 *rayO[2];     // rays of generation g >= 1 live in buffer g & 1: (origin, path id bits) …
-  float4 *rayD[2];     // … (direction, unused)
-  int4 *hit;           // per hit slot: (src = pixel index (g = 0) or ray index; < 0 = hole, bits of res.d, object, bits of trap.z)
-  float4 *surfP;       // (p, ambient occlusion)
-  float4 *surfN;       // (bumped normal, unused)
-  float *shadow;       // [light·cap + hit slot]: penumbra factor of a ray that missed, kWfShadowHit of one that hit
-  int2 *pathPix;       // paths are indexed by the generation-0 hit slot: (pixel index, object of the primary hit)
-  float4 *pathA;       // (phong.xyz, refl.w)
-  float4 *pathB;       // (refl.xyz, fil.x)
-  float2 *pathC;       // (fil.y, fil.z)
-  uint32_t cap;        // hit-slot capacity
-};
 
 // frag:2572-2574 with refr = 0: fragColor = phong + refl + refr, bright pass (frag:1938-1946)
 RM_DEV void wfStorePixel(float4 *__restrict__ out, float4 *__restrict__ bright, int pix, V3 phong, V4 refl) {
@@ -116,32 +100,6 @@ RM_DEV void wfLightRay(const RmLight &li, V3 p, float far, V3 &L, float &maxT) {
     maxT = len(toL);
   }
 }
-
-// Register budgets (waves per SIMD) of the march kernels: the shadow kernel fits 64 VGPRs; the primary / bounce kernels carry
-// the ray set-up of their refill path (primaryRay's IEEE divisions) and spill 15 / 5 registers at that budget.
-#ifndef RM_WF_MARCH_WAVES
-#define RM_WF_MARCH_WAVES 8
-#endif
-#ifndef RM_WF_PRIMARY_WAVES
-#define RM_WF_PRIMARY_WAVES 6
-#endif
-constexpr int wfMarchWaves(int kind) { return kind == 2 ? RM_WF_MARCH_WAVES : RM_WF_PRIMARY_WAVES; }
-// Cursor granularity.  One device counter sustains ≈88 atomics per µs (measured in round 1): with 64-slot hit chunks the 20 M
-// primary hits of the 8K Menger frame were 311 k atomics ≈ 3.5 ms of a 5.0 ms kernel (the bounce kernels likewise), so hit
-// slots, rays and pixels are reserved 256 at a time (a wave's unused remainder becomes holes; 64 was atomic-bound, 1024 and
-// guided chunks measured slower: profiles/r03_b_wavefront.md).
-#ifndef RM_WF_SLOT_CHUNK
-#define RM_WF_SLOT_CHUNK 256
-#endif
-#ifndef RM_WF_RAY_CHUNK
-#define RM_WF_RAY_CHUNK 256
-#endif
-#ifndef RM_WF_PIXEL_CHUNK
-#define RM_WF_PIXEL_CHUNK 256
-#endif
-constexpr uint32_t kWfSlotChunk = RM_WF_SLOT_CHUNK;
-constexpr uint32_t kWfStripes = 64;  // power of two
-constexpr uint32_t wfRayChunk(int kind) { return kind == 0 ? RM_WF_PIXEL_CHUNK : RM_WF_RAY_CHUNK; }
 
 // KIND 0: primary rays from the tile-major pixel cursor; 1: bounce rays of generation `gen` from the ray queue;
 // 2: shadow rays of generation `gen`, ray id = light·(hit slots) + hit slot.

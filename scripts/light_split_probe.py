@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the light split (rm_kernels.hip: the heaviest tiles of a settled picture one light per workgroup) on the reference's
+"""A/B of the light split (rm_launcher.hip: the heaviest tiles of a settled picture one light per workgroup) on the reference's
 lighting scenefiles with several lights: kernel ms of the settled frame with the split off / forced at 1/256 of the tiles / left to
 the launcher's own measurement (the default), hard and soft shadows, 1080p and 4K.  GPU box only.   python scripts/light_split_probe.py [out.md]"""
 import ctypes as C

@@ -290,7 +290,7 @@ def rotation(axis, angle):
 
 def random_tablewalk_objects(rng, max_objects=30, materials=True):
     """A random all-primitive table drawn WIDE — what the pass-over test, the runner-up tracking and the ball ∩ box culls of the
-    table walk (rm_device.hip.h sdSceneImpl / march, rm_kernels.hip scene_cull_ball) must survive without changing a bit:
+    table walk (rm_device.hip.h sdSceneImpl / march, rm_frame.cpp scene_cull_ball) must survive without changing a bit:
     arbitrary-axis rotations, shear, anisotropy 0.2–5, a scaleFactor that is deliberately NOT the smallest scale (the ABI accepts
     any: the distance values are then not 1-Lipschitz, which the launcher's `lip` must account for), objects inside objects,
     coincident copies (ties: the lower index wins), tables of up to 30.  Returns a list of RmObject."""

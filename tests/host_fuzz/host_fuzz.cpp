@@ -3,7 +3,9 @@
 // under a sanitizer on this pool — and driven over (1) every scenefile and image of tests/golden/scenes and (2) seeded random
 // mutations of them (truncations, byte flips, spliced ranges, structural JSON tokens).  Any out-of-bounds access, overflow or
 // leak aborts the run; a mutated input may of course be REJECTED (RM_ERR_*), it must not crash.  (3) the row-tile partition of the
-// multi-GPU path: every frame row in exactly one (shard, local row) for random heights, tile sizes and shard counts.
+// multi-GPU path: every frame row in exactly one (shard, local row) for random heights, tile sizes and shard counts.  (4) the scene
+// prep of a launch (rm_frame.cpp) for every scenefile that loads, pristine or mutated: validate_scene with default settings and
+// no resources and, where it passes, fill_frames — cull ball and box, per-object balls, ray planes, the plain-bulb flag.
 // Usage: host_fuzz <scenes dir> <tmp dir> <iterations> <seed>
 #include <dirent.h>
 #include <sys/stat.h>
@@ -13,14 +15,16 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "../../include/raymarcher_amd.h"
+#include "../../raymarcher_amd/csrc/rm_frame.h"
 #include "../../raymarcher_amd/csrc/rm_internal.h"
 
-// the two helpers the launcher (rm_kernels.hip) defines for the host files
+// the two helpers the launcher (rm_launcher.hip) defines for the host files
 namespace rm {
 static thread_local std::string t_err;
 bool device_accessible(const void *) { return false; }
@@ -56,9 +60,9 @@ static int touch_scene(RmScene *sc) {
   b = reinterpret_cast<const uint8_t *>(l);
   for (size_t i = 0; i < sizeof(RmLight) * (size_t)nl; i++) g_sum += b[i];
   RmCameraData cd;
+  RmCamera cam{};
   if (rm_scene_camera_data(sc, &cd) == RM_OK) {
     float view[16], proj[16];
-    RmCamera cam;
     if (rm_camera_build(&cd, 640, 360, 0.1f, 100.0f, view, proj, &cam) == RM_OK) {
       const uint8_t *c = reinterpret_cast<const uint8_t *>(&cam);
       for (size_t i = 0; i < sizeof(cam); i++) g_sum += c[i];
@@ -66,8 +70,20 @@ static int touch_scene(RmScene *sc) {
   }
   RmHostSettings hs;
   rm_host_settings_default(&hs);
-  RmGlobals g;
+  RmGlobals g{};
   rm_scene_globals(sc, &hs, &g);
+  // the launch's scene prep: what a render of these tables would check and stage
+  RmSettings st;
+  rm_settings_default(&st);
+  const RmResources none{};
+  if (rm::validate_scene(&cam, o, no, l, nl, &g, &st, none) == RM_OK) {
+    auto blk = std::make_unique<rm::SceneBlock>();
+    rm::fill_frames(blk.get(), 1, &cam, &g, 1, o, no, l, nl, &st, none);
+    const auto fold = [](const void *p, size_t n) { const uint8_t *q = static_cast<const uint8_t *>(p); for (size_t i = 0; i < n; i++) g_sum += q[i]; };
+    g_sum += (uint64_t)(blk->cullOk + 2 * blk->cullBoxOk + 4 * blk->objBallOk + 8 * blk->bulbPlain);
+    fold(&blk->cullR2, sizeof(blk->cullR2));
+    fold(blk->rayPlane, sizeof(blk->rayPlane));
+  }
   for (int i = 0; i < no; i++) { const char *t = rm_scene_object_texture(sc, i); if (t) g_sum += strlen(t); }
   return no + nl;
 }

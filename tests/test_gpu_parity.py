@@ -1096,7 +1096,7 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
 @pytest.mark.parametrize("soft,ao,shape", [(1, 1, 3), (0, 0, 3), (1, 0, 2)])
 def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, ao, shape):
     """A settled picture of the plain table-walk class with several lights renders its heaviest tiles one light per workgroup; the
-    last of a tile's workgroups to arrive finishes it from the stored results (rm_kernels.hip, "light split"; forced here — by
+    last of a tile's workgroups to arrive finishes it from the stored results (rm_launcher.hip, "light split"; forced here — by
     default the launcher measures per picture whether it pays).  Every frame of the sequence —
     new picture, cost-ordered repeats, settled and split — is the first frame, which is the oracle's; lights of every plain kind,
     one of them facing away from most of the scene (dropped by N·L on many pixels), soft and hard shadows, both tile shapes, a
@@ -1162,7 +1162,7 @@ def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, 
 
 def test_tile_shape_tuner_never_changes_a_pixel(renderer):
     """The launcher measures, per stream and picture, whether 8×8 or 4 wide × 16 tall pixel tiles are faster (frames 0-7 of a
-    picture alternate the two shapes in pairs, then the choice sticks; rm_kernels.hip "tile shape").  Every frame of such a
+    picture alternate the two shapes in pairs, then the choice sticks; rm_launcher.hip "tile shape").  Every frame of such a
     sequence — and the frame with either shape forced, whole, as a row range and as a shard — is the same frame, the oracle's."""
     import torch
     from raymarcher_amd import lib

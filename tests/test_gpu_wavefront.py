@@ -194,7 +194,7 @@ def test_wavefront_workspace_refused_falls_back_to_the_pixel_kernel(renderer):
     """The auto-selected pipeline needs ≈175 B of grow-only scratch per pixel (per device and stream).  When that buffer may
     not be had — rm_set_workspace_limit here; a failing hipMalloc takes the same branch — a launch that chose the pipeline by
     itself renders with rm::render_kernel instead (identical bits, no workspace); only an explicit rm_set_kernel_path(5)
-    reports the failure, and HIP's error state stays clean either way (rm_kernels.hip launch_render / stream_workspace)."""
+    reports the failure, and HIP's error state stays clean either way (rm_launcher.hip launch_render / stream_workspace)."""
     import ctypes as C
     import torch
     from raymarcher_amd import Scene, lib

@@ -20,7 +20,7 @@ def harness(tmp_path_factory):
     out = tmp_path_factory.mktemp("host_fuzz") / "host_fuzz"
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-o", str(out), os.path.join(ROOT, "tests", "host_fuzz", "host_fuzz.cpp")]
-    cmd += [os.path.join(CSRC, f) for f in ("rm_host.cpp", "rm_scene.cpp", "rm_jpeg.cpp", "rm_gif.cpp")] + ["-lz"]
+    cmd += [os.path.join(CSRC, f) for f in ("rm_host.cpp", "rm_scene.cpp", "rm_jpeg.cpp", "rm_gif.cpp", "rm_frame.cpp")] + ["-lz"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0 and ("cannot find -lasan" in r.stderr or "cannot find -lubsan" in r.stderr):
         pytest.skip("sanitizer runtimes not installed")
