@@ -549,7 +549,8 @@ int rm_debug_check_math(unsigned long long *mismatches5);
 /*
  * rm_frame_to_rgba8 — clamp→×255→round and vertical flip, the read-back of
  * Realtime::saveViewportImage (src/realtime.cpp:284-350).  d_rgba: H·W float4 (row 0 = bottom);
- * d_out: H·W·4 bytes, row 0 = top.
+ * d_out: H·W·4 bytes, row 0 = top.  A NaN is stored as 0, as anything not greater than 0 is; +inf as 255 (rm_frames_to_rgba8
+ * and rm_tiles_to_rgba8 convert the same way).
  */
 int rm_frame_to_rgba8(const float *d_rgba, uint8_t *d_out, int W, int H, void *stream);
 /*
@@ -574,7 +575,8 @@ typedef struct RmPostSettings {
  * bright / ping-pong targets are RGBA16F (values are rounded to binary16 between passes), the FXAA source is
  * RGBA8 sampled with GL_LINEAR / GL_REPEAT.  d_frag, d_bright (may be NULL without bloom) and d_out are H·W
  * float4, row 0 = bottom; d_out receives the colour the 8-bit default framebuffer would quantise
- * (rm_frame_to_rgba8 does that).  Uses a grow-only per-stream workspace of 20 B/pixel.
+ * (rm_frame_to_rgba8 does that).  Uses a grow-only per-stream workspace of 20 B/pixel.  Non-finite and negative inputs have
+ * defined results: a NaN that reaches the 8-bit FXAA source is stored as 0.
  */
 int rm_post_process(const float *d_frag, const float *d_bright, float *d_out, int W, int H, const RmPostSettings *ps,
                     void *stream);

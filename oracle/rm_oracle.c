@@ -1404,9 +1404,10 @@ done:
 #include <immintrin.h>
 /* storage in an RGBA16F target: round to binary16 (nearest even) and back */
 static inline float q16(float v) { return _cvtsh_ss(_cvtss_sh(v, _MM_FROUND_TO_NEAREST_INT | _MM_FROUND_NO_EXC)); }
-/* storage in an RGBA8 target: clamp, ×255, round half up, /255 */
+/* storage in an RGBA8 target: clamp, ×255, round half up, /255.  A NaN is stored as 0 (UB12): "not greater than 0" takes it,
+ * so the float → int conversion (undefined for a NaN) never sees one. */
 static inline float q8(float v) {
-  v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+  v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
   return (float)(int)rm_fma(v, 255.0f, 0.5f) / 255.0f;
 }
 static inline int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }

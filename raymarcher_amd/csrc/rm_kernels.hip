@@ -276,7 +276,7 @@ __global__ void to_rgba8_kernel(const float4 *__restrict__ in, uchar4 *__restric
   if (x >= W) return;
   const size_t base = (size_t)blockIdx.z * W * H;
   float4 c = in[base + (size_t)y * W + x];
-  auto q = [](float v) { v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); return (unsigned char)(v * 255.0f + 0.5f); };
+  auto q = [](float v) { v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); return (unsigned char)(v * 255.0f + 0.5f); };  // NaN → 0 (UB12)
   out[base + (size_t)(H - 1 - y) * W + x] = make_uchar4(q(c.x), q(c.y), q(c.z), q(c.w));
 }
 
@@ -285,7 +285,7 @@ __global__ void tiles_to_rgba8_kernel(const float4 *__restrict__ in, uchar4 *__r
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 c = in[i];
-  auto q = [](float v) { v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); return (unsigned char)(v * 255.0f + 0.5f); };
+  auto q = [](float v) { v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); return (unsigned char)(v * 255.0f + 0.5f); };  // NaN → 0 (UB12)
   out[i] = make_uchar4(q(c.x), q(c.y), q(c.z), q(c.w));
 }
 // gathered RGBA8 slots → frame rows (flip: row 0 of the output is the top of the image, as rm_frame_to_rgba8 writes it)

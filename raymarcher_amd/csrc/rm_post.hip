@@ -27,8 +27,9 @@ namespace {
 struct alignas(8) half4 { __half x, y, z, w; };  // 8-byte aligned: one 64-bit global / LDS access per texel
 
 __device__ __forceinline__ float q16(float v) { return __half2float(__float2half_rn(v)); }
+// A NaN stored to an 8-bit target is 0 (UB12): "not greater than 0" takes it, so the conversion below never sees one.
 __device__ __forceinline__ unsigned char to8(float v) {
-  v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+  v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
   return (unsigned char)(int)fma(v, 255.0f, 0.5f);
 }
 __device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }

@@ -617,7 +617,8 @@ def test_post_passes_bit_exact(renderer, name):
     if name != "none":
         assert np.abs(got[..., :3] - frag.cpu().numpy()[..., :3]).max() > 0.01
     img = renderer.to_rgba8(renderer.post_process(frag, bright, post)).cpu().numpy()
-    exp = (np.clip(ref[::-1], 0, 1) * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
+    clamped = np.where(ref[::-1] > 0, np.minimum(ref[::-1], np.float32(1.0)), np.float32(0.0))  # "not greater than 0" → 0: a NaN is stored as 0
+    exp = (clamped * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
     assert (img == exp).all()
 
 
