@@ -344,6 +344,42 @@ int rm_render_accumulated(const RmCamera *cams, const RmGlobals *globals, int nu
                           const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream);
 
 /*
+ * rm_render_animated — rm_render_accumulated where every sub-frame may have an object table and a light table of its own: objects and
+ * lights that move, appear or change material from frame to frame (animation export in one launch) and during the shutter interval
+ * (motion blur of what moves, not only of what iTime drives) — no reference counterpart.  The shape and every rule of
+ * rm_render_accumulated — numFrames·H·W float4 per output with rows bottom-up, d_bright may be NULL, asynchronous on `stream`, host
+ * arrays copied before return — with blocks = numFrames·subFrames and block b = f·subFrames + j for sub-frame j of output frame f:
+ * cams holds `blocks` cameras; numGlobals, numObjectTables and numLightTables are each 1 (entry 0 for every block) or `blocks`;
+ * object table b is objs + b·numObjects, light table b is lights + b·numLights.  numObjects and numLights are the same for every
+ * block; everything inside an entry may differ between blocks (type, transform, materials, texLoc, emissive flag, light kind).
+ * Settings and resources are shared.  rm_object_translated moves an object; a light moves by writing its pos / dir / points.
+ * Definition of a pixel.  Let S_b be the frame rm_render_res writes for block b's camera, globals, object table and light table.
+ * Output frame f is the rm_render_accumulated reduction of S_{f·n} … S_{f·n + n − 1}, n = subFrames: acc = S_{f·n}, then
+ * acc = acc + S_{f·n + j} for j = 1 … n − 1 in that order, each add one binary32 round-to-nearest add, denormals kept, all four
+ * channels, fragColor and BrightColor alike; then out = acc · c, c the binary32 value of 1.0f / (float)n.  subFrames == 1 gives
+ * frame f = S_f.  The result is defined bit for bit.  numObjectTables == numLightTables == 1 is rm_render_accumulated, exactly
+ * (for subFrames == 1: rm_render_batch), and one table repeated `blocks` times gives the same bits as passing it once.
+ * RM_ERR_INVALID_ARGUMENT: numObjectTables or numLightTables neither 1 nor numFrames·subFrames; null objs / lights where the count
+ * needs them; everything rm_render_accumulated refuses, with its codes (subFrames < 1 or > RM_MAX_SUBFRAMES, numGlobals, the size
+ * limits; numFrames·subFrames > RM_MAX_BATCH_FRAMES: RM_ERR_CAPACITY; numFrames == 0: RM_OK).  The tables of EVERY block are checked
+ * as rm_render_res checks them (a CUSTOM object, a texLoc without its texture, an area light without the LTC tables in any block:
+ * RM_ERR_UNSUPPORTED); the error text names the block.  All of these are checked before any HIP call.
+ * Schedule: ONE launch (rm_debug_last_path() = 10, rm_debug_last_split() = 0), 8×8 tiles in raster order, of the kernel class the
+ * most general block needs — samplers if any block reads one, secondary rays if any block can fire them, the single-Mandelbulb
+ * classes only if every block is a lone Mandelbulb (its plain form only if every block has it); the classes are specialisations
+ * with identical pixels.  subFrames == 1 launches the one-lane-per-pixel kernel over the blocks; subFrames > 1 the animated kernel,
+ * whose workgroups stage the object table again (two barriers) only ahead of a sub-frame whose table differs from the one before it:
+ * shared object tables (depth of field, moving lights) pay nothing beyond rm_render_accumulated.  No wavefront pipeline
+ * (rm_set_kernel_path is not consulted), no light split, no tile-shape pin, no tile order, no library workspace; it uses one slot of
+ * the batch ring of scene blocks (one block per sub-frame, ≈9.7 KB each) and neither reads nor changes the per-stream tuner and
+ * tile-order state of single-frame renders.  With rm_set_timing(1) it counts as one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_render_animated(const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs, int numObjects,
+                       int numObjectTables, const RmLight *lights, int numLights, int numLightTables, int numFrames, int subFrames,
+                       const RmSettings *s, const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -458,7 +494,7 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled or rm_render_accumulated, and so does a whole call of rm_render_adaptive.
+ * launch of rm_render_supersampled, rm_render_accumulated or rm_render_animated, and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -487,8 +523,8 @@ int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
- * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated (none of them is a value
- * rm_set_kernel_path takes). */
+ * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated (none of them is a
+ * value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups
@@ -661,6 +697,11 @@ int rm_camera_build(const RmCameraData *cd, int W, int H, float nearPlane, float
  * positive or not finite, null cd / out, and what rm_camera_build refuses. */
 int rm_camera_lens_samples(const RmCameraData *cd, int W, int H, float nearPlane, float farPlane, float lensRadius,
                            float focusDistance, int n, RmCamera *out);
+/* An object moved by t in world space, for the object tables of rm_render_animated (no reference counterpart): *out is *in with
+ * invModel' = invModel · T(−t), T the translation matrix — the fourth column becomes −t[0]·col0 − t[1]·col1 − t[2]·col2 + col3,
+ * computed in double and rounded once to float; every other field is copied.  t = 0 returns *in bit for bit.  in and out may be the
+ * same object.  RM_ERR_INVALID_ARGUMENT: a null pointer or a t that is not finite. */
+int rm_object_translated(const RmObject *in, const float t[3], RmObject *out);
 
 /* Opaque parsed scene — SceneParser::parse (src/utils/sceneparser.cpp:117-133) +
  * RayMarchScene::initScene (src/raymarch/raymarchscene.cpp:104-134). */

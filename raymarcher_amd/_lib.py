@@ -42,6 +42,9 @@ SIGNATURES = {
     "rm_render_accumulated": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, C.c_int, C.c_int, _P(abi.RmObject), C.c_int,
                                         _P(abi.RmLight), C.c_int, _P(abi.RmSettings), _P(abi.RmResources), C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_render_animated": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, _P(abi.RmObject), C.c_int, C.c_int, _P(abi.RmLight),
+                                     C.c_int, C.c_int, C.c_int, C.c_int, _P(abi.RmSettings), _P(abi.RmResources), C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
     "rm_skybox_face_path": (C.c_char_p, [C.c_int, C.c_int]),
@@ -102,6 +105,7 @@ SIGNATURES = {
                                   _P(C.c_float), _P(abi.RmCamera)]),
     "rm_camera_lens_samples": (C.c_int, [_P(abi.RmCameraData), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                          _P(abi.RmCamera)]),
+    "rm_object_translated": (C.c_int, [_P(abi.RmObject), _P(C.c_float), _P(abi.RmObject)]),
     "rm_scene_load": (C.c_int, [C.c_char_p, _P(C.c_void_p)]),
     "rm_scene_load_string": (C.c_int, [C.c_char_p, _P(C.c_void_p)]),
     "rm_scene_free": (None, [C.c_void_p]),

@@ -347,6 +347,44 @@ void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *gl
   }
 }
 
+// The fill step of rm_render_animated: fill_frames where every block may have an object table and a light table of its own
+// (objs + b·numObjects when numObjectTables > 1, table 0 otherwise; the lights likewise).  Nothing is taken over from block 0 but
+// what a call shares (settings, resources, the counts): the table copies, the evaluation records, the cull ball and box with
+// cullLip, cullOneOk and objBall, the ray planes and the plain-bulb flag all come from the block's own tables, camera and globals.
+// With both counts 1 every block holds what fill_frames gives it.  restage (or null): bit b set where block b's object table
+// differs, byte for byte, from block b − 1's (never for b = 0) — what render_anim_kernel stages anew.
+void fill_frames_animated(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs,
+                          int numObjects, int numObjectTables, const RmLight *lights, int numLights, int numLightTables,
+                          const RmSettings *s, const RmResources &res, RestageBits *restage) {
+  const size_t tableBytes = sizeof(RmObject) * (size_t)numObjects;
+  if (restage) std::memset(restage, 0, sizeof(*restage));
+  for (int f = 0; f < n; f++) {
+    SceneBlock *b = h + f;
+    const RmObject *o = objs + (numObjectTables == 1 ? 0 : (size_t)f * (size_t)numObjects);
+    const RmLight *l = lights + (numLightTables == 1 ? 0 : (size_t)f * (size_t)numLights);
+    const RmGlobals *g = &globals[numGlobals == 1 ? 0 : f];
+    if (f == 0) {
+      fill_frames(b, 1, cams, g, 1, o, numObjects, l, numLights, s, res);
+      continue;
+    }
+    const RmObject *prev = objs + (numObjectTables == 1 ? 0 : (size_t)(f - 1) * (size_t)numObjects);
+    const bool sameObjs = o == prev || tableBytes == 0 || std::memcmp(o, prev, tableBytes) == 0;
+    *b = *(b - 1);  // the shared part, and the previous block's tables where this block's are the same
+    b->cam = cams[f];
+    b->g = *g;
+    if (!sameObjs) {
+      for (int i = 0; i < numObjects; i++) b->objs[i] = o[i];
+      scene_eval_records(b);
+      if (restage) restage->set(f);
+    }
+    for (int i = 0; i < numLights; i++) b->lights[i] = l[i];
+    // the cull bounds read the table and, for a Mandelbulb, the globals: recomputed whenever either may differ from the previous block's
+    if (!sameObjs || numGlobals > 1) scene_cull_ball(b);
+    ray_planes(b);
+    b->bulbPlain = bulb_plain(o, numObjects, g);
+  }
+}
+
 // Whether the wavefront pipeline is expected to beat the one-lane-per-pixel kernel on this scene (measured).
 // Measured (profiles/r03_b_wavefront.md): with reflection bounces the regrouping wins from 4K frames up (8K Menger frame
 // with two bounces 39.0 -> 24.4 ms, the same scene at 4K 12.0 -> 9.2 ms, reflections_complex.json at 4K with two bounces

@@ -21,6 +21,9 @@ void scene_eval_records(SceneBlock *h);
 int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g);
 void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs,
                  int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res);
+void fill_frames_animated(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs,
+                          int numObjects, int numObjectTables, const RmLight *lights, int numLights, int numLightTables,
+                          const RmSettings *s, const RmResources &res, RestageBits *restage);
 
 bool skip_applies(const RmObject *objs, int numObjects);
 bool all_primitives(const RmObject *objs, int numObjects);

@@ -174,6 +174,19 @@ int rm_camera_lens_samples(const RmCameraData *cd, int W, int H, float nearPlane
   return RM_OK;
 }
 
+int rm_object_translated(const RmObject *in, const float t[3], RmObject *out) {
+  if (!in || !t || !out) { set_error("null argument"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2])) { set_error("translation must be finite"); return RM_ERR_INVALID_ARGUMENT; }
+  RmObject o = *in;
+  if (t[0] != 0.0f || t[1] != 0.0f || t[2] != 0.0f) {  // t = 0: the object itself, signed zeros and all
+    const float *M = in->invModel;  // column-major: row r of column c is M[4·c + r]
+    for (int r = 0; r < 4; r++)
+      o.invModel[12 + r] = (float)((((double)M[r] * -(double)t[0] + (double)M[4 + r] * -(double)t[1]) + (double)M[8 + r] * -(double)t[2]) + (double)M[12 + r]);
+  }
+  *out = o;
+  return RM_OK;
+}
+
 int rm_shard_rows(int H, int tileRows, int shard, int numShards) {
   if (H <= 0 || tileRows <= 0 || numShards <= 0 || shard < 0 || shard >= numShards) return -1;
   return shard_rows(H, tileRows, shard, numShards, root_relief());

@@ -81,6 +81,12 @@ int launch_render_ss(const void *sb, int bulbClass, bool env, bool tex, bool sec
 // sb[f·n] … sb[f·n + n − 1] — into W × H output pixels per frame: their sum in index order, times 1.0f / n.
 int launch_render_acc(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int n,
                       float *d_rgba, float *d_bright, hipStream_t stream);
+// The animated kernels (rm_animate.hip, rm_render_animated with subFrames > 1; a translation unit of its own for the same reason):
+// launch_render_acc's launch where every block has its own object and light table; `restage` says before which blocks a workgroup
+// stages the object table anew (RestageBits, rm_scene_block.h).
+struct RestageBits;
+int launch_render_anim(const void *sb, const RestageBits &restage, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block,
+                       int W, int H, int n, float *d_rgba, float *d_bright, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

@@ -359,8 +359,8 @@ struct LaunchFields {
 };
 // The upload step: the launch fields into the slot's first n blocks, one copy of them to the device and, when the table holds a
 // Menger sponge, each frame's sponge uniforms computed on the device — stream-ordered between the upload and the kernels that
-// read the blocks.
-int upload_frames(const Slot &slot, int n, const LaunchFields &lf, hipStream_t stream) {
+// read the blocks.  mengerAnywhere (rm_render_animated, whose blocks have tables of their own): a block other than the first holds one.
+int upload_frames(const Slot &slot, int n, const LaunchFields &lf, hipStream_t stream, bool mengerAnywhere = false) {
   for (int f = 0; f < n; f++) {
     SceneBlock *h = slot.host + f;
     h->tileOrder = lf.tileOrder; h->tileCost = lf.tileCost; h->tileCount = lf.tileCount;
@@ -370,7 +370,7 @@ int upload_frames(const Slot &slot, int n, const LaunchFields &lf, hipStream_t s
     h->frame = f;
   }
   HIP_OK(hipMemcpyAsync(slot.dev, slot.host, (size_t)n * sizeof(SceneBlock), hipMemcpyHostToDevice, stream));
-  bool menger = false;
+  bool menger = mengerAnywhere;
   for (int i = 0; i < slot.host->numObjects; i++) menger = menger || slot.host->objs[i].type == RM_MENGERSPONGE;
   if (menger) {
     if (int st = launch_scene_prep(slot.dev, n, stream)) return st;
@@ -664,8 +664,11 @@ struct FrameCall {
   const RmSettings *s; const RmResources &res;
   int W, H; float *d_rgba, *d_bright; hipStream_t stream;
   int subFrames = 1;
+  int numObjectTables = 1, numLightTables = 1;  // rm_render_animated: 1 (table 0 for every block) or blocks()
   long long blocks() const { return (long long)numFrames * subFrames; }
   const RmGlobals *globalsOf(int b) const { return &globals[numGlobals == 1 ? 0 : b]; }
+  const RmObject *objsOf(int b) const { return objs + (numObjectTables == 1 ? 0 : (size_t)b * (size_t)numObjects); }
+  const RmLight *lightsOf(int b) const { return lights + (numLightTables == 1 ? 0 : (size_t)b * (size_t)numLights); }
 };
 // The argument checks the four entry points share, every one ahead of the first HIP call (as launch_render's); an input that
 // fails several reports the first of this order.  numFrames = 0 passes: nothing to write, the caller returns RM_OK.  sampled: the
@@ -891,6 +894,78 @@ int launch_accumulated(const FrameCall &c) {
   return finish_frames(*ds, sf, 9, c.stream);
 }
 
+// ---- animated frames: object and light tables per block (rm_render_animated) ---------------------------------------------------
+// rm_render_animated (the header has the definition): rm_render_accumulated's call where numObjectTables / numLightTables say
+// whether every block brings an object / light table of its own.  The table counts and validate_scene of EVERY block (the error
+// text names the block) run as check_frames' size check, ahead of its pointer checks and of any HIP call.  Staging is
+// fill_frames_animated into one slot of the batch ring, one block per sub-frame, with the sponge prologue when any block holds a
+// sponge.  The class of the call is the most general one any block needs: textured / secondary if any block is, the bulb classes
+// only if every block is a lone Mandelbulb, the plain form only if every block has it.  subFrames = 1: the production
+// render_kernel of that class over the blocks (launch_frames, 8×8 tiles); subFrames > 1: render_anim_kernel (rm_animate.hip), which
+// stages the object table again where the restage bits say it changed.  One launch either way, path 10: no wavefront pipeline,
+// light split, tile-shape pin, tile order or library workspace, no tuner or tile-order state read or written.
+int check_animated_tables(const FrameCall &c) {
+  const long long blocks = c.blocks();
+  if (c.numObjectTables != 1 && c.numObjectTables != blocks) {
+    set_error("numObjectTables must be 1 or numFrames·subFrames");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (c.numLightTables != 1 && c.numLightTables != blocks) {
+    set_error("numLightTables must be 1 or numFrames·subFrames");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  // block 0 first: it also checks the counts that index the later tables (and the pointers they are taken from)
+  for (int b = 0; b < (int)blocks; b++) {
+    if (b > 0 && c.numObjectTables == 1 && c.numLightTables == 1) break;  // validate_scene reads nothing else per block
+    const int st = validate_scene(&c.cams[b], c.objsOf(b), c.numObjects, c.lightsOf(b), c.numLights, c.globalsOf(b), c.s, c.res);
+    if (st != RM_OK) {
+      if (blocks > 1) set_error("block " + std::to_string(b) + ": " + rm_last_error());
+      return st;
+    }
+  }
+  return RM_OK;
+}
+int launch_animated(const FrameCall &c) {
+  if (c.subFrames < 1 || c.subFrames > RM_MAX_SUBFRAMES) { set_error("subFrames must be 1 … RM_MAX_SUBFRAMES"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = check_frames(c, 1, true, check_animated_tables);
+  if (st != RM_OK || c.numFrames == 0) return st;
+  const int blocks = (int)c.blocks();
+  // the class of the call and what the upload needs to know, from every block's own tables
+  FrameClass fc = classify_frame(c.objsOf(0), c.numObjects, c.lightsOf(0), c.numLights, c.globalsOf(0), c.s, 0);
+  bool plainBulb = true, menger = false;
+  for (int b = 0; b < blocks; b++) {
+    plainBulb = plainBulb && bulb_plain(c.objsOf(b), c.numObjects, c.globalsOf(b));
+    if (b == 0 || (c.numObjectTables == 1 && c.numLightTables == 1)) continue;
+    const FrameClass fb = classify_frame(c.objsOf(b), c.numObjects, c.lightsOf(b), c.numLights, c.globalsOf(b), c.s, 0);
+    fc.bulb = fc.bulb && fb.bulb;
+    fc.textured = fc.textured || fb.textured;
+    fc.secondary = fc.secondary || fb.secondary;
+    for (int i = 0; i < c.numObjects; i++) menger = menger || c.objsOf(b)[i].type == RM_MENGERSPONGE;
+  }
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  sf.fc = fc;
+  sf.plainBulb = plainBulb;
+  sf.bulbClass = bulb_class(fc, plainBulb);
+  if ((st = acquire_slot(ds->batches, blocks, &sf.slot)) != RM_OK) return st;
+  RestageBits restage;
+  fill_frames_animated(sf.slot->host, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.numObjectTables, c.lights,
+                       c.numLights, c.numLightTables, c.s, c.res, &restage);
+  if ((st = upload_frames(*sf.slot, blocks, LaunchFields{}, c.stream, menger)) != RM_OK) return st;
+  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if (c.subFrames == 1) {
+    if ((st = launch_frames(c, sf, 0, c.numFrames, kTiles8x8)) != RM_OK) return st;
+  } else {
+    const int nw = waves_per_block();
+    const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
+    if ((st = launch_render_anim(sf.slot->dev, restage, sf.bulbClass, fc.envFeatures, fc.textured, fc.secondary, grid, block, c.W, c.H,
+                                 c.subFrames, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
+  }
+  return finish_frames(*ds, sf, 10, c.stream);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -974,6 +1049,15 @@ int rm_render_accumulated(const RmCamera *cams, const RmGlobals *globals, int nu
                           const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream) {
   return launch_accumulated(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
                                       W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream), subFrames});
+}
+
+int rm_render_animated(const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs, int numObjects,
+                       int numObjectTables, const RmLight *lights, int numLights, int numLightTables, int numFrames, int subFrames,
+                       const RmSettings *s, const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream) {
+  FrameCall c{cams, globals, numGlobals, numFrames, objs, numObjects, lights, numLights, s, res ? *res : kNoResources,
+              W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream), subFrames};
+  c.numObjectTables = numObjectTables; c.numLightTables = numLightTables;
+  return launch_animated(c);
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

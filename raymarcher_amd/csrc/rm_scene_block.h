@@ -90,5 +90,12 @@ struct RowMap {
 };
 static_assert(sizeof(SceneBlock) == 9664, "host and device agree on the block's layout");
 
+// rm_render_animated: one bit per scene block of a call, beside the blocks (a kernel argument of render_anim_kernel, rm_animate.hip).
+// Bit b set: block b's object table differs from block b − 1's, so a workgroup that walks from one to the other stages it anew.
+struct RestageBits {
+  uint32_t w[RM_MAX_BATCH_FRAMES / 32];
+  void set(int b) { w[b >> 5] |= 1u << (b & 31); }
+};
+
 }  // namespace rm
 #endif  // RM_SCENE_BLOCK_H

@@ -187,6 +187,45 @@ def shutter_globals(globals_, t_open, t_close, n):
     return out
 
 
+def translated_objects(objs, index, offsets):
+    """The stacked object tables of Renderer.render_animated for one moving object: table b is a copy of `objs` (a sequence or
+    ctypes array of RmObject) whose entry `index` is moved by offsets[b] = (x, y, z) in world space through rm_object_translated
+    → a ctypes array RmObject * (len(offsets)·len(objs)), table b at [b·len(objs) : (b + 1)·len(objs)].  Pass it as `objects`."""
+    objs = list(objs)
+    offsets = [tuple(float(v) for v in t) for t in offsets]
+    if not objs or not all(isinstance(o, abi.RmObject) for o in objs):
+        raise ValueError("objs must be a non-empty sequence of RmObject structs")
+    if not isinstance(index, int) or isinstance(index, bool) or not 0 <= index < len(objs):
+        raise ValueError(f"index = {index!r}: an entry of the {len(objs)}-object table")
+    if not offsets or any(len(t) != 3 for t in offsets):
+        raise ValueError("offsets must be a non-empty sequence of (x, y, z)")
+    n = len(objs)
+    out = (abi.RmObject * (len(offsets) * n))()
+    for b, t in enumerate(offsets):
+        for i, o in enumerate(objs):
+            C.memmove(C.byref(out[b * n + i]), C.byref(o), C.sizeof(abi.RmObject))
+        check(lib().rm_object_translated(C.byref(objs[index]), (C.c_float * 3)(*t), C.byref(out[b * n + index])))
+    return out
+
+
+def _stacked_tables(tables, what, struct, count, blocks):
+    """The (array, number of tables) arguments of rm_render_animated for `tables` = None (one table: the scene's own, `count`
+    entries) or the caller's per-block tables: a flat ctypes array / sequence of blocks·count structs, or a sequence of `blocks`
+    sequences of `count` structs."""
+    if tables is None:
+        return None, 1
+    rows = list(tables)
+    if rows and not isinstance(rows[0], struct):
+        if len(rows) != blocks or any(len(r) != count for r in rows):
+            raise ValueError(f"{what} must have shape (blocks, {count}) = ({blocks}, {count})")
+        rows = [e for r in rows for e in r]
+    if len(rows) != blocks * count or not all(isinstance(e, struct) for e in rows):
+        raise ValueError(f"{what} must hold blocks·count = {blocks}·{count} {struct.__name__} structs, one table per block")
+    if isinstance(tables, C.Array) and tables._type_ is struct:
+        return tables, blocks
+    return (struct * max(len(rows), 1))(*rows), blocks
+
+
 def batch_arrays(cameras, globals_):
     """The ctypes arrays of rm_render_batch: (RmCamera * N, RmGlobals * 1 or N).  globals_ is one RmGlobals (shared by every
     frame) or a sequence of N; raises ValueError on any other length or element type."""
@@ -390,6 +429,33 @@ class Renderer:
         return self._render_frames("rm_render_accumulated", tables, settings, W, H, cameras, globals_, bright, out, out_bright,
                                    sub_frames=sub_frames)
 
+    def render_animated(self, tables, settings, W, H, cameras, sub_frames=1, objects=None, lights=None, globals_=None, bright=False,
+                        out=None, out_bright=None):
+        """rm_render_animated: render_accumulated where every camera (block) may have an object table and a light table of its own
+        → float32 tensor (len(cameras) / sub_frames, H, W, 4), row 0 = bottom.  objects / lights: None (tables.objects /
+        tables.lights for every block) or the per-block tables, shape (blocks, tables.num_objects) / (blocks, tables.num_lights) of
+        RmObject / RmLight — nested sequences or one flat ctypes array, e.g. translated_objects(...).  Every other argument as
+        render_accumulated's; the definition is in include/raymarcher_amd.h."""
+        if not isinstance(sub_frames, int) or isinstance(sub_frames, bool) or not 1 <= sub_frames <= abi.RM_MAX_SUBFRAMES:
+            raise ValueError(f"sub_frames = {sub_frames!r}: an integer from 1 to RM_MAX_SUBFRAMES = {abi.RM_MAX_SUBFRAMES}")
+        if len(cameras) % sub_frames:
+            raise ValueError(f"{len(cameras)} cameras are not a whole number of frames of {sub_frames} sub-frames")
+        cams, globs = batch_arrays(cameras, tables.globals_ if globals_ is None else globals_)
+        blocks = len(cameras)
+        objs, n_obj_tables = _stacked_tables(objects, "objects", abi.RmObject, tables.num_objects, blocks)
+        lts, n_light_tables = _stacked_tables(lights, "lights", abi.RmLight, tables.num_lights, blocks)
+        n = blocks // sub_frames
+        t = self.torch
+        out = self._out(out, (n, H, W, 4), t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, (n, H, W, 4), t.float32, "out_bright") if bright else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_render_animated(cams, globs, len(globs), tables.objects if objs is None else objs, tables.num_objects, n_obj_tables,
+                                       tables.lights if lts is None else lts, tables.num_lights, n_light_tables, n, sub_frames,
+                                       C.byref(settings), C.byref(res), W, H, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
+        return (out, br) if bright else out
+
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
         what the production kernel really executes (RM_COUNT_EXECUTED; plain scene classes only)."""
@@ -502,21 +568,29 @@ class Renderer:
         check(lib().rm_frames_to_rgba8(C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()), W, H, n, self._stream()))
         return out
 
-    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1, adaptive=None, accumulate=None):
+    def render_sequence(self, tables, settings, W, H, cameras, globals_=None, post=None, supersample=1, adaptive=None, accumulate=None,
+                        *, objects=None, lights=None):
         """The finished images of an exported sequence: render_batch (with the BrightColor planes only when bloom is on), then
         post_process_batch in place (skipped for post=None), then to_rgba8_batch → uint8 (N, H, W, 4), each image's top row
         first.  post: one RmPostSettings or a sequence of N (see post_process_batch).  supersample = 2 or 4: the render step is
         render_supersampled with that many samples per pixel along each axis (bloom then sees the resolved BrightColor).
         adaptive = t: the render step is render_adaptive(…, supersample, t) — those samples only where the 1-sample frame shows
         contrast above t.  accumulate = n: the render step is render_accumulated(…, n) — len(cameras) / n images, each the mean of n
-        consecutive cameras (and globals); not together with supersample > 1 or adaptive."""
+        consecutive cameras (and globals); not together with supersample > 1 or adaptive.  objects / lights: per-camera object /
+        light tables (render_animated's arguments) — the render step is then render_animated(…, accumulate or 1, objects, lights);
+        not together with supersample > 1 or adaptive either."""
+        animated = objects is not None or lights is not None
+        if animated and (supersample != 1 or adaptive is not None):
+            raise ValueError("objects / lights cannot be combined with supersample > 1 or adaptive")
         if accumulate is not None and (supersample != 1 or adaptive is not None):
             raise ValueError("accumulate cannot be combined with supersample > 1 or adaptive")
         if accumulate is not None and (not isinstance(accumulate, int) or accumulate < 1 or len(cameras) % accumulate):
             raise ValueError(f"accumulate = {accumulate!r}: a positive integer that divides the {len(cameras)} cameras")
         ps = post_array(post, len(cameras) // (accumulate or 1)) if post is not None else None
         bloom = ps is not None and bool(ps[0].enableBloom)
-        if accumulate is not None:
+        if animated:
+            frames = self.render_animated(tables, settings, W, H, cameras, accumulate or 1, objects, lights, globals_, bright=bloom)
+        elif accumulate is not None:
             frames = self.render_accumulated(tables, settings, W, H, cameras, accumulate, globals_, bright=bloom)
         elif adaptive is not None:
             frames = self.render_adaptive(tables, settings, W, H, cameras, supersample, adaptive, globals_, bright=bloom)
