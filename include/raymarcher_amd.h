@@ -380,6 +380,42 @@ int rm_render_animated(const RmCamera *cams, const RmGlobals *globals, int numGl
                        const RmSettings *s, const RmResources *res, int W, int H, float *d_rgba, float *d_bright, void *stream);
 
 /*
+ * rm_render_gbuffer — what the primary ray of every pixel HIT instead of the colour shading makes of it: surface normal, depth,
+ * object index and, optionally, the surface point (no reference counterpart: the shader keeps these in locals).  For compositing
+ * and depth-aware post effects, denoiser and edge guides, picking and masks, and a cheap geometry-only preview.  The call shape is
+ * rm_render_batch's without lights and resources: numFrames whole W×H frames of ONE object table in one launch, frame f with its own
+ * camera cams[f] and globals (globals[f] when numGlobals == numFrames, globals[0] when numGlobals == 1).  Frame f starts at f·W·H
+ * elements of each output; rows bottom-up.  Asynchronous on `stream`; host arrays are copied before return.
+ * Definition, bit for bit.  The G-buffer of a frame is the RayMarchRes / IntersectionInfo of main's first render call
+ * (frag:2388-2392, 2443, 2318-2337, 1453-1484, 1436-1444, 1679-1691).  For pixel (x, y): ro, rd = the primary ray of rm_render —
+ * the varyings interpolated from the ray planes, the divisions by w, normalize; far = cam->initialFar;
+ * res = raymarch(ro, rd, far, OUTSIDE) with the call's maxSteps.  Hit (res.intersectObj != -1): objectId = res.intersectObj — the
+ * march's index, so the emissive rectangle of an area light reports its own index, not the −1 that `info` keeps —; depth = res.d,
+ * the distance along the normalised rd from ro on the near plane (not a view-space z); p = rd·res.d + ro in render's fused form;
+ * n = getNormal(p), then bumpNormal(n, p, 10, 2) when RM_FEAT_PERLIN_BUMP is set: the normal render hands getPhong.  Miss:
+ * objectId = −1, depth = far (RenderInfo.d of a miss, frag:2328, not the march's ray depth), n = (0, 0, 0), p = (0, 0, 0).
+ * d_normalDepth: float4 (n.x, n.y, n.z, depth) per pixel; d_objectId: int32 per pixel; d_position: float4 (p.x, p.y, p.z,
+ * hit ? 1 : 0) per pixel, or NULL: nothing is written for it and the other two outputs are the same bits.
+ * Of RmSettings the call reads maxSteps, the bounds of the fractals' loops (fractalIters, mengerLevels, the power-8 form) and
+ * RM_FEAT_PERLIN_BUMP.  Lights, textures, sky box, LTC tables, shadows, ambient occlusion, reflection and refraction play no part:
+ * a texLoc or enableSkyBox without its sampler is not an error here.
+ * numFrames == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT: numFrames < 0, numGlobals neither 1 nor numFrames, null cams /
+ * globals, W or H <= 0 or above INT_MAX / 8 or more tiles than one launch can index, null s or objs, a negative loop bound, a null
+ * d_normalDepth / d_objectId, an output that is not device memory; RM_ERR_CAPACITY: numFrames > RM_MAX_BATCH_FRAMES, numObjects >
+ * RM_MAX_OBJECTS; RM_ERR_UNSUPPORTED, rather than a G-buffer that would lie: RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA in the
+ * settings (a layer may cover the object table), isTwoD in any frame's globals (the error text names the frame), a CUSTOM object.
+ * All of these are checked, in this order, before any HIP call.
+ * Schedule: ONE launch of the G-buffer kernel of the table's march class (rm_debug_last_path() = 11, rm_debug_last_split() = 0), 8×8
+ * tiles in raster order: no wavefront pipeline (rm_set_kernel_path is not consulted), no light split, no tile-shape pin, no tile
+ * order, no library workspace; it uses one slot of the batch ring of scene blocks and neither reads nor changes the per-stream tuner
+ * and tile-order state of single-frame renders.  With rm_set_timing(1) it counts as one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs,
+                      int numObjects, const RmSettings *s, int W, int H, float *d_normalDepth, int32_t *d_objectId,
+                      float *d_position, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -494,7 +530,8 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled, rm_render_accumulated or rm_render_animated, and so does a whole call of rm_render_adaptive.
+ * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated or rm_render_gbuffer, and so does a whole call of
+ * rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -523,8 +560,8 @@ int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
- * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated (none of them is a
- * value rm_set_kernel_path takes). */
+ * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
+ * of rm_render_gbuffer (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

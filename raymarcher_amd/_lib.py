@@ -45,6 +45,8 @@ SIGNATURES = {
     "rm_render_animated": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, _P(abi.RmObject), C.c_int, C.c_int, _P(abi.RmLight),
                                      C.c_int, C.c_int, C.c_int, C.c_int, _P(abi.RmSettings), _P(abi.RmResources), C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_render_gbuffer": (C.c_int, [_P(abi.RmCamera), _P(abi.RmGlobals), C.c_int, C.c_int, _P(abi.RmObject), C.c_int, _P(abi.RmSettings),
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
     "rm_skybox_face_path": (C.c_char_p, [C.c_int, C.c_int]),

@@ -87,6 +87,11 @@ int launch_render_acc(const void *sb, int bulbClass, bool env, bool tex, bool se
 struct RestageBits;
 int launch_render_anim(const void *sb, const RestageBits &restage, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block,
                        int W, int H, int n, float *d_rgba, float *d_bright, hipStream_t stream);
+// The G-buffer kernels (rm_gbuffer.hip, rm_render_gbuffer; a translation unit of its own for the same reason): the launch of
+// gbuffer_kernel<bulbClass> over the staged SceneBlocks `sb` (one per frame of grid.z) — normal and depth, object index and, when
+// d_position is not null, the surface point of every pixel's primary hit, W·H elements per frame.
+int launch_gbuffer_kernel(const void *sb, int bulbClass, dim3 grid, dim3 block, int W, int H, float *d_normalDepth, int32_t *d_objectId,
+                          float *d_position, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

@@ -966,6 +966,84 @@ int launch_animated(const FrameCall &c) {
   return finish_frames(*ds, sf, 10, c.stream);
 }
 
+// ---- G-buffers: what the primary ray hit (rm_render_gbuffer) -------------------------------------------------------------------
+// rm_render_gbuffer (the header has the definition): rm_render_batch's call shape without lights and resources, three outputs
+// instead of colour.  GBufferCall stands beside FrameCall, which carries both; its checks run in check_frames' order, every one
+// ahead of the first HIP call: numFrames, the cap, numFrames == 0, numGlobals, null cameras or globals, the frame size (the
+// coordinates and tiles come from blockIdx, as a sample frame's), then the scene — settings and table pointers, the layers and
+// the 2-D mode the G-buffer does not describe, the table's limits and types — then the outputs.  A texLoc, a sky box or an area
+// light's rectangle without its sampler is no error: nothing here reads one.
+// Staging is a batch's: one slot of the batch ring, fill_frames with no lights and no resources (one scene block per frame: cull
+// data, ray planes, bulbPlain), upload_frames with the default launch fields (and the sponge prologue when the table holds one).
+// Then ONE launch of gbuffer_kernel (rm_gbuffer.hip) over (tilesX, tilesY, numFrames) 8×8 tiles in raster order, path 11: no
+// wavefront pipeline, light split, tile-shape pin, tile order, tuner state or library workspace.
+struct GBufferCall {
+  const RmCamera *cams; const RmGlobals *globals; int numGlobals, numFrames;
+  const RmObject *objs; int numObjects; const RmSettings *s;
+  int W, H; float *d_normalDepth; int32_t *d_objectId; float *d_position; hipStream_t stream;
+  const RmGlobals *globalsOf(int f) const { return &globals[numGlobals == 1 ? 0 : f]; }
+};
+int check_gbuffer(const GBufferCall &c) {
+  if (c.numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
+  if (c.numFrames == 0) return RM_OK;
+  if (c.numGlobals != 1 && c.numGlobals != c.numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!c.cams || !c.globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.W <= 0 || c.H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.W > INT_MAX / 8 || c.H > INT_MAX / 8) { set_error("W or H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
+  const int nw = waves_per_block();
+  const long long tilesX = ((long long)c.W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)c.H + 7) / 8;
+  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many tiles for one launch"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!c.s || (c.numObjects > 0 && !c.objs) || c.numObjects < 0) {
+    set_error("null scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
+    set_error("rm_render_gbuffer describes the object table: TERRAIN / CLOUD / SEA may cover it");
+    return RM_ERR_UNSUPPORTED;
+  }
+  for (int f = 0; f < c.numFrames; f++)
+    if (c.globalsOf(f)->isTwoD) {
+      set_error("frame " + std::to_string(f) + ": the 2-D mode (isTwoD) marches no ray, it has no G-buffer");
+      return RM_ERR_UNSUPPORTED;
+    }
+  if (c.numObjects > RM_MAX_OBJECTS) { set_error("scene exceeds RM_MAX_OBJECTS"); return RM_ERR_CAPACITY; }
+  if (c.s->maxSteps < 0 || c.s->fractalIters < 0 || c.s->mengerLevels < 0) {
+    set_error("negative loop bound in RmSettings");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  for (int i = 0; i < c.numObjects; i++)
+    if (c.objs[i].type < 0 || c.objs[i].type >= RM_CUSTOM) {
+      set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
+      return RM_ERR_UNSUPPORTED;
+    }
+  if (!c.d_normalDepth || !c.d_objectId) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  return require_device_pointers({{"d_normalDepth", c.d_normalDepth}, {"d_objectId", c.d_objectId}, {"d_position", c.d_position}});
+}
+int launch_gbuffer(const GBufferCall &c) {
+  int st = check_gbuffer(c);
+  if (st != RM_OK || c.numFrames == 0) return st;
+  const int n = c.numFrames;
+  // the march class of the call, as bulb_class: a lone Mandelbulb, its plain form only if every frame has it
+  bool plainBulb = true;
+  for (int f = 0; f < n; f++) plainBulb = plainBulb && bulb_plain(c.objs, c.numObjects, c.globalsOf(f));
+  const bool bulb = c.numObjects == 1 && c.objs[0].type == RM_MANDELBULB;
+  const int bulbClass = bulb ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  if ((st = acquire_slot(ds->batches, n, &sf.slot)) != RM_OK) return st;
+  fill_frames(sf.slot->host, n, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
+  if ((st = upload_frames(*sf.slot, n, LaunchFields{}, c.stream)) != RM_OK) return st;
+  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  const int nw = waves_per_block();
+  const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)n), block(64 * nw);
+  if ((st = launch_gbuffer_kernel(sf.slot->dev, bulbClass, grid, block, c.W, c.H, c.d_normalDepth, c.d_objectId, c.d_position,
+                                  c.stream)) != RM_OK) return st;
+  return finish_frames(*ds, sf, 11, c.stream);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1058,6 +1136,12 @@ int rm_render_animated(const RmCamera *cams, const RmGlobals *globals, int numGl
               W, H, d_rgba, d_bright, static_cast<hipStream_t>(stream), subFrames};
   c.numObjectTables = numObjectTables; c.numLightTables = numLightTables;
   return launch_animated(c);
+}
+
+int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
+                      const RmSettings *s, int W, int H, float *d_normalDepth, int32_t *d_objectId, float *d_position, void *stream) {
+  return launch_gbuffer(GBufferCall{cams, globals, numGlobals, numFrames, objs, numObjects, s, W, H, d_normalDepth, d_objectId, d_position,
+                                    static_cast<hipStream_t>(stream)});
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

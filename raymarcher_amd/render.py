@@ -456,6 +456,26 @@ class Renderer:
                                        C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
         return (out, br) if bright else out
 
+    def render_gbuffer(self, tables, settings, W, H, cameras=None, globals_=None, position=False, out_normal_depth=None,
+                       out_object_id=None, out_position=None):
+        """rm_render_gbuffer: what the primary ray of every pixel hit, N frames in one launch → (normal_depth, object_id[, position]):
+        float32 (N, H, W, 4) = (n.x, n.y, n.z, depth along the ray), int32 (N, H, W) = the object's index in tables.objects (−1: a
+        miss, with depth = the camera's initialFar and a zero normal) and, with position, float32 (N, H, W, 4) = (p.x, p.y, p.z,
+        1 for a hit / 0).  Row 0 = bottom.  cameras: None (the scene's own camera, N = 1) or a sequence of RmCamera; globals_ as
+        render_batch's.  Lights, textures and the shading settings play no part; the definition is in include/raymarcher_amd.h.
+        out_*: the caller's buffers (out_position implies position=True)."""
+        t = self.torch
+        cams, globs = batch_arrays([tables.camera] if cameras is None else cameras, tables.globals_ if globals_ is None else globals_)
+        n = 1 if cameras is None else len(cameras)
+        nd = self._out(out_normal_depth, (n, H, W, 4), t.float32, "out_normal_depth")
+        ids = self._out(out_object_id, (n, H, W), t.int32, "out_object_id")
+        position = position or out_position is not None
+        pos = self._out(out_position, (n, H, W, 4), t.float32, "out_position") if position else None
+        check(lib().rm_render_gbuffer(cams, globs, len(globs), n, tables.objects, tables.num_objects, C.byref(settings), W, H,
+                                      C.c_void_p(nd.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                      C.c_void_p(pos.data_ptr()) if position else None, self._stream()))
+        return (nd, ids, pos) if position else (nd, ids)
+
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
         what the production kernel really executes (RM_COUNT_EXECUTED; plain scene classes only)."""

@@ -1,0 +1,67 @@
+"""The specification of rm_render_gbuffer for the tests: tests/gbuffer_spec/rm_gbuffer_spec.c, which includes the oracle's source and
+restates the head of its render() with the oracle's own static functions, built on demand with gcc and oracle/Makefile's flags into
+tests/gbuffer_spec/_build/ and loaded with ctypes.  Nothing under oracle/ is touched."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import helpers as h
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SPEC_DIR = os.path.join(HERE, "gbuffer_spec")
+SPEC_SRC = os.path.join(SPEC_DIR, "rm_gbuffer_spec.c")
+SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_gbuffer_spec.so")
+# oracle/Makefile's CFLAGS (-ffp-contract=off: the numeric contract fuses only where rm_fma() is written)
+CFLAGS = ["-O3", "-std=c99", "-fPIC", "-mfma", "-mavx2", "-mf16c", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
+          "-Wextra", "-Wno-unused-function"]
+_SPEC = None
+
+
+def spec():
+    """ctypes handle of the spec library, rebuilt when a source it is made of is newer."""
+    global _SPEC
+    if _SPEC is None:
+        deps = [SPEC_SRC] + [os.path.join(h.ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
+               [os.path.join(h.ROOT, "include", "raymarcher_amd.h")]
+        if not os.path.exists(SPEC_SO) or os.path.getmtime(SPEC_SO) < max(os.path.getmtime(d) for d in deps):
+            os.makedirs(os.path.dirname(SPEC_SO), exist_ok=True)
+            tmp = f"{SPEC_SO}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
+            subprocess.check_call([os.environ.get("CC", "gcc")] + CFLAGS + ["-shared", "-o", tmp, SPEC_SRC, "-lm"])
+            os.replace(tmp, SPEC_SO)
+        lib = C.CDLL(SPEC_SO)
+        lib.rmo_spec_gbuffer.restype = C.c_int
+        lib.rmo_spec_gbuffer.argtypes = [C.POINTER(h.abi.RmCamera), C.POINTER(h.abi.RmObject), C.c_int, C.POINTER(h.abi.RmGlobals),
+                                         C.POINTER(h.abi.RmSettings), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_float)]
+        _SPEC = lib
+    return _SPEC
+
+
+def spec_gbuffer(cam, objs, num_objects, g, s, W, H, position=True):
+    """The G-buffer of one frame by the specification → (normal_depth (H, W, 4) float32, object_id (H, W) int32, position (H, W, 4)
+    float32 or None), row 0 at the bottom."""
+    nd = np.empty((H, W, 4), dtype=np.float32)
+    ids = np.empty((H, W), dtype=np.int32)
+    pos = np.empty((H, W, 4), dtype=np.float32) if position else None
+    st = spec().rmo_spec_gbuffer(C.byref(cam), objs, num_objects, C.byref(g), C.byref(s), W, H, h.fptr(nd),
+                                 ids.ctypes.data_as(C.POINTER(C.c_int32)), h.fptr(pos) if position else None)
+    assert st == 0, f"spec status {st}"
+    return nd, ids, pos
+
+
+def primary_rays(cam, W, H):
+    """(ro, rd) of every pixel centre in float64 from the camera's inverse projection-view matrix, (H, W, 3) each, row 0 at the
+    bottom — an independent statement of frag:2388-2392 for the analytic checks (evaluated per pixel, not from the corners)."""
+    M = np.array(cam.invProjView[:], dtype=np.float64).reshape(4, 4).T  # column-major storage
+    x = (np.arange(W) + 0.5) / W * 2.0 - 1.0
+    y = (np.arange(H) + 0.5) / H * 2.0 - 1.0
+    X, Y = np.meshgrid(x, y)
+
+    def unproject(z):
+        p = np.stack([X, Y, np.full_like(X, z), np.ones_like(X)], axis=-1) @ M.T
+        return p[..., :3] / p[..., 3:4]
+    ro, far = unproject(-1.0), unproject(1.0)
+    rd = far - ro
+    return ro, rd / np.linalg.norm(rd, axis=-1, keepdims=True)
