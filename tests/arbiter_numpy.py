@@ -918,3 +918,77 @@ def render_frame_table(tables, settings, W, H, resources=None, diag=False, jitte
             "lum": np.where(is_env, np.inf, np.abs(lum - 1.0)).reshape(H, W)}
     info.update({k: v.reshape(H, W) for k, v in mg.items()})
     return out.reshape(H, W, 4), (~is_env).reshape(H, W), info
+
+
+# ---------------------------------------------------------------------------------------------- the G-buffer (rm_render_gbuffer)
+def gbuffer_frame(tables, settings, W, H, shift=0.0, wobble=None):
+    """What the primary ray of every pixel hits, from the definition in include/raymarcher_amd.h (rm_render_gbuffer) and the shader
+    text: main's first render() call up to the normal it hands getPhong (frag:2388-2392, 2443, 2318-2337) → float64 (normal (H, W, 3),
+    depth (H, W), object_id (H, W), position (H, W, 4), geom_margin (H, W)), row 0 = bottom.
+    The primary ray of a pixel is computed at that pixel from invProjView (raymarch.vert:13-25 at the pixel centre; nothing is
+    interpolated from corners).  A table of one Mandelbulb or one Menger sponge marches through `raymarch` with Bulb / Menger, any
+    other table (Table's primitives and the Sierpinski; an empty one too) through `_march`, both to initialFar with the call's
+    maxSteps.  A hit: object_id is the march's index (an emissive rectangle reports ITSELF: nothing here reads isEmissive), depth =
+    rayDepth − minD, p = ro + rd·depth, n = get_normal(p), then bump_normal(n, p) when RM_FEAT_PERLIN_BUMP is set; position = (p, 1).
+    A miss: n = (0, 0, 0), depth = initialFar, object_id = −1, position = (0, 0, 0, 0).
+    geom_margin: min over the march's evaluations of | |d| − SURFACE_DIST | — how far the nearest stopping test was from flipping
+    (`raymarch` keeps no margin, so the fractals' comes from a second pass through `_march`, which must reproduce hit and depth).
+    shift: evaluate the normal at p + rd·shift instead of p (depth and position stay those of p) — how much of a normal's error
+    a hit point that is off by one stopping step along the ray explains.
+    wobble=(δ, tol) appends a bool (H, W), `unstable`: the same march started δ further along the ray, or δ nearer, hits another
+    object (or none), or ends — hit or miss, the depth the march reports — more than tol from where this one ends.  The march is the iteration t ← t + d(t).  About a surface crossed at
+    angle θ, where d' = −k·cos θ, its derivative is 1 − k·cos θ; k = 1 for a true distance, but the ABI accepts any scaleFactor, and
+    with one above the smallest scale of the model (or a sheared model) k·cos θ can exceed 2.  Then the iteration is no contraction:
+    the ray bounces about the surface, every step multiplies a rounding difference, and where — or whether, within maxSteps — it
+    lands inside SURFACE_DIST is decided by the last bit of the first step.  geom_margin, the distance of THIS trajectory's stopping
+    tests from flipping, does not see that; with δ one binary32 ulp of the depth, such a pixel is defined by its binary32
+    evaluation alone."""
+    assert not tables.globals_.isTwoD
+    assert not settings.features & (RM_FEAT_CLOUD | RM_FEAT_TERRAIN | RM_FEAT_SEA)
+    gl, n_obj = tables.globals_, tables.num_objects
+    far = float(tables.camera.initialFar)
+    inv_pv = np.array(list(tables.camera.invProjView), np.float64).reshape(4, 4).T  # column-major storage
+    ys, xs = np.mgrid[0:H, 0:W]
+    ndc = np.stack([(xs.ravel() + 0.5) / W * 2.0 - 1.0, (ys.ravel() + 0.5) / H * 2.0 - 1.0], -1)
+    near = np.concatenate([ndc, np.full((len(ndc), 1), -1.0), np.ones((len(ndc), 1))], -1) @ inv_pv.T
+    farc = np.concatenate([ndc, np.ones((len(ndc), 1)), np.ones((len(ndc), 1))], -1) @ inv_pv.T
+    ro = near[:, :3] / near[:, 3:]                      # setScene, frag:2388-2392
+    rd = _normalize(farc[:, :3] / farc[:, 3:] - ro)
+
+    def inv_model(o):
+        return np.array(list(o.invModel), np.float64).reshape(4, 4).T
+    fractal = n_obj == 1 and tables.objects[0].type in (RM_MANDELBULB, RM_MENGERSPONGE)
+    if fractal:
+        o = tables.objects[0]
+        if o.type == RM_MANDELBULB:
+            sd = Bulb(inv_model(o), o.scaleFactor, gl.power, settings.fractalIters, (gl.juliaSeed[0], gl.juliaSeed[1]))
+        else:
+            sd = Menger(inv_model(o), o.scaleFactor, settings.mengerLevels, gl.iTime)
+        hit, depth, _trap = raymarch(sd, ro, rd, far, settings.maxSteps)
+        hit2, depth2, _obj, margin = _march(sd, ro, rd, far, settings.maxSteps)
+        assert (hit2 == hit).all() and (depth2[hit] == depth[hit]).all()
+        obj = np.where(hit, 0, -1)
+    else:
+        sd = Table([(tables.objects[i].type, inv_model(tables.objects[i]), tables.objects[i].scaleFactor) for i in range(n_obj)])
+        hit, depth, obj, margin = _march(sd, ro, rd, far, settings.maxSteps)
+    n = len(ro)
+    N, P, D = np.zeros((n, 3)), np.zeros((n, 4)), np.full(n, far)
+    if hit.any():
+        p = ro[hit] + rd[hit] * depth[hit, None]         # frag:2333
+        q = p + rd[hit] * shift
+        pn = get_normal(sd, q)
+        if settings.features & RM_FEAT_PERLIN_BUMP:      # frag:2334-2336
+            pn = bump_normal(pn, q)
+        N[hit], D[hit] = pn, depth[hit]
+        P[hit, :3], P[hit, 3] = p, 1.0
+    res = (N.reshape(H, W, 3), D.reshape(H, W), np.where(hit, obj, -1).astype(np.float64).reshape(H, W), P.reshape(H, W, 4),
+           margin.reshape(H, W))
+    if wobble is None:
+        return res
+    unstable = np.zeros(n, bool)
+    for dt in (wobble[0], -wobble[0]):
+        hit_w, depth_w, obj_w, _m = _march(sd, ro + rd * dt, rd, far, settings.maxSteps)
+        if fractal:
+            obj_w = np.zeros(n, int)   # the fractal classes carry their trap where a table carries the index
+        unstable |= (hit_w != hit) | (hit & (np.where(hit_w, obj_w, -1) != np.where(hit, obj, -1))) | (np.abs(depth_w + dt - depth) > wobble[1])
+    return res + (unstable.reshape(H, W),)

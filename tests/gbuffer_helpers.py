@@ -1,6 +1,7 @@
 """The specification of rm_render_gbuffer for the tests: tests/gbuffer_spec/rm_gbuffer_spec.c, which includes the oracle's source and
 restates the head of its render() with the oracle's own static functions, built on demand with gcc and oracle/Makefile's flags into
-tests/gbuffer_spec/_build/ and loaded with ctypes.  Nothing under oracle/ is touched."""
+tests/gbuffer_spec/_build/ and loaded with ctypes.  Nothing under oracle/ is touched.  Also the scenes that more than one G-buffer test
+module renders."""
 import ctypes as C
 import os
 import subprocess
@@ -8,6 +9,7 @@ import subprocess
 import numpy as np
 
 import helpers as h
+from raymarcher_amd import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SPEC_DIR = os.path.join(HERE, "gbuffer_spec")
@@ -17,6 +19,22 @@ SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_gbuffer_spec.so")
 CFLAGS = ["-O3", "-std=c99", "-fPIC", "-mfma", "-mavx2", "-mf16c", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
           "-Wextra", "-Wno-unused-function"]
 _SPEC = None
+SCENES = os.path.join(HERE, "golden", "scenes")
+
+
+def directional_light_2(W, H):
+    """lighting/directional_light_2.json through the library's loader, as the scene tuple the tests pass around."""
+    from raymarcher_amd import Scene
+    t = Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).tables(W, H)
+    return t.camera, t.objects, t.num_objects, t.lights, t.num_lights, t.globals_
+
+
+def moved_bulb_scene(W, H):
+    """helpers.scene_mandelbulb with the bulb translated and rotated: the general Mandelbulb class."""
+    scene = h.scene_mandelbulb(W, H)
+    model = h.translate(0.15, -0.1, 0.2) @ h.rotation((0.3, 1.0, -0.2), 0.7)
+    objs = (abi.RmObject * 1)(h.make_object(abi.RM_MANDELBULB, model=model))
+    return (scene[0], objs, 1) + tuple(scene[3:])
 
 
 def spec():

@@ -17,7 +17,6 @@ from raymarcher_amd._lib import LIB_PATH, SIGNATURES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-SCENES = os.path.join(ROOT, "tests", "golden", "scenes")
 INT_MAX = 2 ** 31 - 1
 SURFACE_DIST = 1e-3  # frag:32
 
@@ -149,16 +148,10 @@ def test_object_validation_and_outputs():
 
 
 # ---------------------------------------------------------------- the specification, on the CPU
-def _directional_light_2(W, H):
-    from raymarcher_amd import Scene
-    t = Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).tables(W, H)
-    return t.camera, t.objects, t.num_objects, t.lights, t.num_lights, t.globals_
-
-
 @pytest.mark.parametrize("name", ["directional_light_2", "mandelbulb"])
 def test_spec_hits_what_the_oracle_hits(name):
     W, H = 64, 36
-    scene = _directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
+    scene = G.directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
     s = abi.default_settings()
     _, cnt = h.oracle_render(scene, s, W, H, counters=True)
     nd, ids, pos = G.spec_gbuffer(scene[0], scene[1], scene[2], scene[5], s, W, H)
