@@ -150,7 +150,8 @@ enum BulbMode { BULB_GENERIC = 0, BULB_TRIG8 = 1, BULB_ALGEBRAIC8 = 2 };
 // form the compiler removed it there by itself; the v_min_f32 form is inline asm, so it is spelled out).
 // NOJULIA: the launcher has found both juliaSeed components zero (SceneBlock::bulbPlain): frag:782's test is false, c = pos
 // without a per-lane select.
-template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false>
+// FUSE (the single-bulb classes): one range guard for the estimate's logarithm, square root and reciprocal (see the return).
+template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false, bool FUSE = false>
 RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
   // the power-8 instantiations are only entered with sb->g.power == 8.0f: the literal (an inline constant of the multiplies)
   // instead of a scalar-register operand, which halves a VALU instruction's issue rate (profiles/r03_c_valu_microbench.md)
@@ -234,16 +235,31 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
     if (m > 2.0f) break;  // frag:798 (FRACTALS_BAILOUT)
   }
   resColor = v4(m, trap.y, trap.z, trap.w);
+  // ONE range check for the estimate's logarithm, square root and reciprocal, as the iteration has one for its own: the three
+  // guarded forms below each test their operand (log2_'s underflow select, sqrt_fast_'s and rcp_'s ballots).  With
+  //  * m >= 2^-96: the domain of the unscaled square root (sqrt_noscale_, correct for +inf too), and above 2^-126, where log2_'s
+  //    select passes (log2_raw_ is what it passes to, +inf included); m == 0 would do for the root but not for the logarithm;
+  //  * 2^-126 <= dz < 2^126: the reciprocal's fast range (rcp_raw_).  The power-8 forms have dz = fma(8·pm, dz, 1) with
+  //    pm = m³·√m >= +0, inf or NaN from dz = 1 on: dz >= 1, inf or NaN, so the lower compare is not needed (the generic
+  //    power, whose dz has no known sign, is not instantiated with FUSE).  dz reaches 2^126 and then inf once a point stays inside for many iterations;
+  //  * a NaN m or dz fails its compare (they are written so that NaN fails)
+  // on every lane of the wave, the bare forms give the guarded forms' bits, in the same order of operations.  Any lane outside
+  // (the origin, |p| near 1e-20, an interior point after dozens of iterations, non-finite input): the whole wave takes the
+  // guarded forms, the same bits either way.  Both ordinary exits — bailout with 2 < m < inf, `iters` reached with m <= 2,
+  // and then m well above 2^-96 for any point that is not the origin's own orbit — pass.
+  static_assert(!FUSE || MODE != BULB_GENERIC, "the generic power's dz has no known sign: it keeps the guarded forms");
+  if (FUSE && __ballot(!(m >= 1.262177448e-29f) || !(dz < 8.50705917e37f)) == 0ull)
+    return ((0.25f * (log2_raw_(m) * kLn2)) * sqrt_noscale_(m)) * rcp_raw_(dz);
   return divr_((0.25f * log_(m)) * sqrt_fast_(m), dz);  // frag:802
 }
 // PLAIN (SceneBlock::bulbPlain: power 8, no Julia seed): only the two power-8 forms, without the Julia select.
-template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false>
+template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false, bool FUSE = false>
 RM_DEV float sdMandelBulb(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
   if (PLAIN || sb->g.power == 8.0f) {  // wave-uniform
-    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN>(sb, pos, resColor, cnt);
-    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN>(sb, pos, resColor, cnt);
+    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN, FUSE>(sb, pos, resColor, cnt);
+    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN, FUSE>(sb, pos, resColor, cnt);
   }
-  return bulbIterate<COUNT, BULB_GENERIC, TRAPMIN, TRAP>(sb, pos, resColor, cnt);
+  return bulbIterate<COUNT, BULB_GENERIC, TRAPMIN, TRAP>(sb, pos, resColor, cnt);  // the generic power keeps the guarded forms
 }
 
 // frag:808-827
@@ -439,7 +455,7 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
       case RM_DEATHSTAR: d = sdDeathStar(po, 0.5f, 0.35f, 0.5f); break;
       case RM_RECTANGLE: d = sdBox(po, 0.5f, 0.5f, 0.0f); break;
       case RM_MANDELBROT: d = sdMandelBrot(sb, po.x, po.y); break;
-      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain>(sb, po, res.trap, cnt); break;
+      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain, BULB != 0>(sb, po, res.trap, cnt); break;
       case RM_MENGERSPONGE: d = sdMengerSponge<TRAP>(sb, po, res.trap); break;
       case RM_SIERPINSKI: d = sdSierpinski(po); break;
       default: continue;
@@ -527,7 +543,8 @@ RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __buil
 // SHADOW=false: returns obj, d = rayDepth − minD on a hit, rayDepth on a miss (contract UB2).
 // SHADOW=true : returns obj, d = penumbra factor res (contract UB1), k = 8, start depth 0.
 //
-// CULL (single-Mandelbulb class only; never in the counted variant, whose counters are the reference's work): a march
+// CULL (single-Mandelbulb class only; never in the reference-counted variant, COUNT == 1, whose counters are the reference's
+// work; the executed-counted and clocked variants follow production): a march
 // whose miss distance nobody reads — primary / secondary rays of render(), hard-shadow rays — may stop as soon as the ray
 // has left a ball |p_object| <= R for good, because it can no longer hit.  For power 8 and |p| = ρ the first iteration
 // gives |w| >= ρ^8 − max(ρ, |seed|), the loop bails out (|w|² > 2) and the estimate is
@@ -536,10 +553,17 @@ RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __buil
 //            hit threshold; the set {estimate < 0.001} lies inside the ball;
 //   R = 2.1  (|seed| <= 2,    scaleFactor >= 0.01): |w| >= 254, estimate >= 0.68.
 // The march therefore ends at min(end, t_exit) with the same obj = −1 it would have reached some evaluations later at
-// t > far.  Rays that never enter the ball stop after their first evaluation.  Soft-shadow rays also read the penumbra
+// t > far.  Hard rays that never enter the ball evaluate nothing, and a hard ray that has left it ends before its next
+// evaluation (march()'s PRE form); where the end is `far`, rays stop after the first evaluation past it.  Soft-shadow rays also read the penumbra
 // factor min(8·d/t); they use the launcher's larger ball (sceneCullEnd with cullR2Soft), which accounts for anisotropic
 // object scales.
-RM_DEV float bulbCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end) {
+// own: whether the value returned is the cull's own t_exit (it won the min against `end`), on a lane whose ray provably is
+// outside the ball at every t > t_exit — the precondition of ending a march BEFORE an evaluation (see march()).  False
+// wherever `end` comes back untouched (cull off, a <= 0, a NaN t_exit), and for an origin inside the ball (c <= 0) unless
+// t_exit > 0: there sqrt(disc) >= |b| (disc = RN(b² + |a·c|) >= RN(b²), whose correctly rounded root is |b|), so t_exit >= 1e-3
+// by its margin — short of an underflowing b², which the test rules out instead of arguing about.
+RM_DEV float bulbCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end, bool &own) {
+  own = false;
   const RmObject &o = sb->objs[0];
   const float jx = sb->g.juliaSeed[0], jy = sb->g.juliaSeed[1];
   const float seed2 = fma(jx, jx, jy * jy);
@@ -558,7 +582,12 @@ RM_DEV float bulbCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end) {
   tExit = fma(tExit, 1.0001f, 1.0e-3f);
   if (c > 0.0f && (b >= 0.0f || disc < 0.0f)) tExit = -1.0f;  // outside and never entering
   if (!(a > 0.0f)) return end;
+  own = (tExit <= end) && (c > 0.0f || tExit > 0.0f);  // false for a NaN tExit
   return min_(end, tExit);  // a NaN tExit leaves `end` untouched
+}
+RM_DEV float bulbCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end) {
+  bool own;
+  return bulbCullEnd(sb, ro, rd, end, own);
 }
 // The same idea for any scene: the launcher bounds every object by a world-space ball (exact SDFs are >= the distance
 // to their object's ball; the bound includes a margin δ with minScale·δ >> the hit threshold), and a march whose miss
@@ -590,9 +619,10 @@ RM_DEV float sceneCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end, float R
 // ub0: an upper bound of sdScene at ro (+inf = none), for the first evaluation's skip test.
 template <int BULB, int COUNT, bool SHADOW, bool CULL = false>
 RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side, Counters &cnt, float ub0 = __builtin_inff()) {
+  bool own = false;  // this lane's `end` is the bulb cull's own t_exit (bulbCullEnd)
   if (CULL && COUNT != 1) {
     const bool softRay = SHADOW && sb->s.enableSoftShadow != 0;  // wave-uniform
-    if (BULB && !softRay) end = bulbCullEnd(sb, ro, rd, end);
+    if (BULB && !softRay) end = bulbCullEnd(sb, ro, rd, end, own);
     else if (softRay) end = sceneCullEnd<false>(sb, ro, rd, end, sb->cullR2Soft);
     else end = sceneCullEnd<true>(sb, ro, rd, end, sb->cullR2);
   }
@@ -610,6 +640,42 @@ RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side,
   // step).  While it stays above ub for every live lane, and the lanes agree on the nearest object, no other object can be
   // the minimum at the next point — strictly — so sdScene there IS that object's value: one record, one shape, no table walk.
   float second = -__builtin_inff();
+  // PRE (bulb cull, hard rays): the `depth > end` test runs BEFORE the evaluation instead of after it — the same compare, moved —
+  // and a lane past its end leaves as the miss it would be one evaluation later, without that evaluation (a step, the
+  // transform guard, a full iteration, the log / sqrt / reciprocal epilogue), and without any when the ray never enters the ball
+  // (t_exit = −1 < depth 0).  Why no bit changes: on a lane with `own` (bulbCullEnd) end = t_exit = 1.0001·t + 1e-3 with t the
+  // far root of the ray against the ball in object space (or −1: no root, origin outside), so depth > end puts the point outside
+  // the ball, by a margin far above the rounding of madd, of the transform and of the quadratic.  Outside the ball the estimate
+  // cannot be a hit (comment above bulbCullEnd): R = 1.15 is used only with scaleFactor >= 0.05 and |seed|² <= 1.2996, where
+  // estimate·scaleFactor >= 0.0277·0.05 = 1.39× the threshold; R = 2.1 with scaleFactor >= 0.01 and |seed|² <= 4, where it is
+  // >= 0.68·0.01 = 6.8×; an estimate that overflows to inf or NaN is no hit either.  So the evaluation skipped would have
+  // failed |d| < kSurfaceDist and then taken `depth > end`: obj = −1 and d = depth, what is returned below — depth is the same
+  // (not advanced since), hit is false (c is the previous evaluation's, which did not hit, or the initial 1e6), and the trap of a
+  // miss is read by nobody (render, renderPooled and the G-buffer read it only with obj != −1).  An origin inside the ball
+  // (c <= 0) has own only with t_exit > 0 = its first depth: it never skips its first evaluation.  A non-finite ray has a NaN
+  // t_exit: own is false.  A lane whose end is `far` (far < t_exit, the cull off) must keep the reference's order — beyond far
+  // it does evaluate, and a hit there counts — so the form is chosen once per march: PRE only when every lane of the wave owns
+  // its end, else the loop as it was (below, untouched), for all lanes.
+  if constexpr (BULB != 0 && CULL && COUNT != 1) {
+    static_assert(!SKIP, "the bulb classes have no single-object fast path");
+    // the body of the loop below without its SKIP parts, in both orders of the `depth > end` test
+    auto bulbLoop = [&](auto preTag) __attribute__((always_inline)) {
+      constexpr bool PRE = decltype(preTag)::value;
+      for (int i = 0; i < steps; i++) {
+        if (PRE && depth > end) break;
+        c = sdSceneImpl<BULB, COUNT, !SHADOW, false, false>(sb, madd(rd, depth, ro), cnt, ub, second);
+        if (fabs_(c.d) < kSurfaceDist || (!PRE && depth > end)) break;
+        if (SHADOW) {
+          if (soft) pen = min_(pen, divr_(8.0f * c.d, depth));
+          depth = depth + fabs_(c.d);
+        } else {
+          depth = fma(c.d, side, depth);
+        }
+      }
+    };
+    if (__ballot(!own) == 0ull) bulbLoop(std::true_type{});  // wave-uniform; own is false on soft rays
+    else bulbLoop(std::false_type{});
+  } else
   for (int i = 0; i < steps; i++) {
     const V3 p = madd(rd, depth, ro);
     bool one = false;
@@ -1084,6 +1150,13 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
   V3 o = so, L = v3(0.0f, 0.0f, 0.0f);
   float depth = 0.0f, end = 0.0f;
   uint32_t next = 0u;  // wave-uniform: the first unclaimed entry
+  // march()'s PRE form, here: while every ray handed out so far owns its end (bulbCullEnd: end is the cull's t_exit, beyond
+  // which the ray cannot hit — the argument is in march()), `depth > end` is tested right after the step instead of after the
+  // next evaluation, so a ray past its end finishes without that evaluation and its lane takes the next entry one trip earlier.
+  // The compare is the same one, moved; the choice is a scalar branch.  Once a ray is handed out whose end is `far` — beyond
+  // which the reference does evaluate, and a hit counts — the wave keeps the former order for the rest of the call: a ray in
+  // flight in the PRE form has depth <= end (or NaN) before each evaluation, a state the former order marches identically.
+  bool pre = true;  // wave-uniform
   for (;;) {
     const uint64_t idle = __ballot(cur < 0);
     if (idle != 0ull && next < n) {  // wave-uniform: hand out the next rays in list order, one per idle lane
@@ -1096,27 +1169,43 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
       const int src = (int)(e & 63u);
       const V3 os = v3(__shfl(so.x, src), __shfl(so.y, src), __shfl(so.z, src));
       const float ds = __shfl(dStart, src);
+      bool endOwn = true;  // a lane that takes nothing does not vote
       if (take) {
         cur = (int)(e >> 6);
         own = src;
         o = os;
         const RmLight &li = sb->lights[cur];  // per-lane index: a vector load, once per ray
         L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));  // lightSetup's direction of a directional light
-        end = bulbCullEnd(sb, o, L, far);
+        end = bulbCullEnd(sb, o, L, far, endOwn);
         const bool resume = !(ds < 0.0f);  // after the shared first step (a NaN |d0| resumes too, as march() would go on)
         depth = resume ? ds : 0.0f;
         step = resume ? 1 : 0;
-        if (resume && 0.0f > end) cur = -1;  // the first step's `depth > end` (depth 0) ended the ray: a miss
+        // a miss before the ray's next evaluation: the first step's `depth > end` (depth 0) ended it, or it owns its end and
+        // starts past it (never entering the ball: t_exit = −1; or the shared first step already went past t_exit).  Such a
+        // lane idles for this trip and takes its next entry in the next one: a shadow ray starts on the surface, inside the
+        // ball, so this is the rare case, and handing out in a loop would put a scalar loop into every trip for it
+        if ((resume && 0.0f > end) || (endOwn && depth > end)) cur = -1;
       }
+      pre = pre && __ballot(!endOwn) == 0ull;
     }
     if (cur >= 0) {
       const SceneMin c = sdScene<BULB, COUNT, false>(sb, madd(L, depth, o), cnt);
       const bool hit = fabs_(c.d) < kSurfaceDist;
-      bool fin = hit || depth > end;
-      if (!fin) {
-        depth = depth + fabs_(c.d);
-        step++;
-        fin = step >= maxSteps;  // the loop of march() runs out: a miss
+      bool fin;
+      if (pre) {  // scalar branch
+        fin = hit;
+        if (!fin) {
+          depth = depth + fabs_(c.d);
+          step++;
+          fin = step >= maxSteps || depth > end;  // the loop of march() runs out, or the ray has left the ball: a miss
+        }
+      } else {
+        fin = hit || depth > end;
+        if (!fin) {
+          depth = depth + fabs_(c.d);
+          step++;
+          fin = step >= maxSteps;  // the loop of march() runs out: a miss
+        }
       }
       if (fin) {
         if (hit) atomicOr(&hitw[own >> 1], 1u << (((own & 1) << 4) + cur));

@@ -240,6 +240,23 @@ RM_DEV float log2_(float x) {
   float r = fma(f, l, (float)e);
   return (x >= 1.17549435e-38f) ? r : -__builtin_inff();
 }
+// log2_ of x >= 2^-126 (+inf included) without the underflow select: for a caller that has done the range check itself
+// (bulbIterate's fused guard).  A copy, so that log2_ and every caller of it compile as they did.
+RM_DEV float log2_raw_(float x) {
+  uint32_t ux = f2u(x) - 0x3f3504f3u;
+  int32_t e = (int32_t)ux >> 23;
+  float m = u2f((ux & 0x007fffffu) + 0x3f3504f3u);
+  float f = m - 1.0f;
+  float l = fma(f, 1.258333027e-01f, -2.072679251e-01f);
+  l = fma(f, l, 2.157161385e-01f);
+  l = fma(f, l, -2.389451116e-01f);
+  l = fma(f, l, 2.879162133e-01f);
+  l = fma(f, l, -3.607036769e-01f);
+  l = fma(f, l, 4.809106290e-01f);
+  l = fma(f, l, -7.213473320e-01f);
+  l = fma(f, l, 1.442695022e+00f);
+  return fma(f, l, (float)e);
+}
 RM_DEV float exp2_(float x) {
   float n = __builtin_rintf(x);
   float f = x - n;
