@@ -185,7 +185,8 @@ void rm_settings_default(RmSettings *s);
 /* ---- library / device ---------------------------------------------------------------------- */
 int rm_abi_version(void);
 /* sizeof() of ABI struct `which` as compiled into the library (0 RmObject, 1 RmLight, 2 RmCamera, 3 RmGlobals,
- * 4 RmSettings, 5 RmCounters, 6 RmHostSettings, 7 RmCameraData, 8 RmTexture, 9 RmPostSettings, 10 RmResources; -1 otherwise) so bindings can verify layout. */
+ * 4 RmSettings, 5 RmCounters, 6 RmHostSettings, 7 RmCameraData, 8 RmTexture, 9 RmPostSettings, 10 RmResources, 11 RmRay, 12 RmRayHit; -1 otherwise) so bindings can verify
+ * layout. */
 int rm_abi_sizeof(int which);
 const char *rm_status_string(int status);
 /* Thread-local text of the last failure in this thread ("" if none). */
@@ -416,6 +417,59 @@ int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlo
                       float *d_position, void *stream);
 
 /*
+ * rm_trace_rays — what ARBITRARY rays hit: the closest hit of each ray, or the renderer's own shadow march along it (no reference
+ * counterpart: the shader only traces the rays it makes itself).  For picking the object under the mouse, keeping a fly-through
+ * camera out of the scene, finding the distance to focus rm_camera_lens_samples at, and line-of-sight / soft-visibility tests
+ * between two points.  d_rays: numRays RmRay in device memory; d_hits: numRays RmRayHit in device memory (both 16-byte aligned);
+ * the object table, g and s are host memory, copied before return.  Asynchronous on `stream`.
+ * Definition, bit for bit.  dir is used as given, NOT normalised: t is in units of |dir|, and a ray that copies primaryRay's ro
+ * and rd (rm_camera_rays) reproduces rm_render_gbuffer exactly.
+ * RM_TRACE_CLOSEST: res = raymarch(origin, dir, tMax, OUTSIDE) (frag:1453-1484) with the call's maxSteps.  Hit (res.intersectObj !=
+ * -1): objectId = res.intersectObj — the march's index, an emissive rectangle reports its own —; t = res.d; position = dir·t +
+ * origin in render's fused form (frag:2318-2337); normal = getNormal(position) (frag:1436-1444), then bumpNormal(normal, position,
+ * 10, 2) (frag:1679-1691) when RM_FEAT_PERLIN_BUMP is set.  With RM_TRACE_NO_NORMAL normal and position are stored as zeros and no
+ * tap is evaluated; objectId and t are the same bits.  Miss: objectId = −1, t = tMax as given (not the march's ray depth — the
+ * choice of rm_render_gbuffer's depth = far), normal and position zeros.
+ * RM_TRACE_OCCLUSION: r = softshadow(origin, dir, 0, tMax, 8) (frag:1703-1725), lightTerm's shadow march.  objectId =
+ * r.intersectObj (−1: nothing in the way), t = r.d = the penumbra factor, tracked whatever s->enableSoftShadow says; normal and
+ * position zeros.  What lightTerm reads as visibility is objectId == −1 ? t : 0.
+ * Invalid ray: a non-finite component of origin or dir, dir all zeros, tMax NaN or negative (+inf is valid).  It stores objectId =
+ * RM_RAY_INVALID, t = 0 and zeros, and evaluates nothing.  Rays are device data: the host cannot refuse them.  `reserved` is not
+ * read.
+ * Of RmSettings the call reads maxSteps, the bounds of the fractals' loops (fractalIters, mengerLevels, the power-8 form) and
+ * RM_FEAT_PERLIN_BUMP; of RmGlobals power, juliaSeed and iTime.  Lights, samplers and cameras play no part.  The result of a ray
+ * does not depend on which other rays share its call.
+ * numRays == 0: RM_OK, nothing read or written.  RM_ERR_INVALID_ARGUMENT: numRays < 0 (every non-negative int fits one launch),
+ * null g or s, a null table with numObjects > 0 or numObjects < 0, mode bits other than the three below or RM_TRACE_NO_NORMAL
+ * together with RM_TRACE_OCCLUSION, a negative loop bound, null or misaligned d_rays / d_hits, an array that is not device memory;
+ * RM_ERR_CAPACITY: numObjects > RM_MAX_OBJECTS; RM_ERR_UNSUPPORTED: RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA in the settings
+ * (rays through the layers are not defined here), g->isTwoD, a CUSTOM or unknown object type.  All of these but the device-memory
+ * check of the two arrays are made, in this order, before any HIP call.
+ * Schedule: ONE launch, one lane per ray, of the trace kernel of the table's march class (rm_debug_last_path() = 12,
+ * rm_debug_last_split() = 0); it uses one slot of the batch ring of scene blocks and neither reads nor changes the per-stream tuner
+ * and tile-order state of single-frame renders, and no library workspace.  With rm_set_timing(1) it counts as one launch, all
+ * stage 1.  Rays that share a wave (64 consecutive rays) and go different ways cost what the longest of them costs: a caller with
+ * many rays does well to keep neighbours together (for a camera's rays, 8×8 pixel tiles).
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmRay { float origin[3]; float tMax; float dir[3]; int32_t reserved; } RmRay;            /* 32 bytes */
+typedef struct RmRayHit { float normal[3]; float t; float position[3]; int32_t objectId; } RmRayHit;   /* 32 bytes */
+#define RM_TRACE_CLOSEST 0u   /* nearest hit, with normal and position */
+#define RM_TRACE_NO_NORMAL 1u /* flag on CLOSEST: id and t only, normal and position stored as zeros */
+#define RM_TRACE_OCCLUSION 2u /* the renderer's own shadow march: occluder id and penumbra factor */
+#define RM_RAY_INVALID (-2)
+int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                  unsigned mode, RmRayHit *d_hits, void *stream);
+/*
+ * rm_camera_rays — the primary rays of pixels of a W×H frame of `cam`, on the host (no HIP call, no GPU): origin and dir are bit
+ * for bit the ro and rd of rm_render and rm_render_gbuffer for that pixel (the ray planes of raymarch.vert:23-24 interpolated to
+ * the pixel centre, the divisions by w, normalize: frag:2388-2392), tMax = cam->initialFar, reserved = 0.  xy: n pairs (x, y), y =
+ * 0 the bottom row; or NULL, then n must be W·H and the rays come out row-major, row 0 at the bottom.  RM_ERR_INVALID_ARGUMENT: a
+ * null cam or out, W or H <= 0, n < 0, n != W·H without xy, a pixel outside the frame (nothing is written then).
+ */
+int rm_camera_rays(const RmCamera *cam, int W, int H, const int32_t *xy, int n, RmRay *out);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -530,8 +584,8 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated or rm_render_gbuffer, and so does a whole call of
- * rm_render_adaptive.
+ * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer or rm_trace_rays, and so does a
+ * whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -561,7 +615,7 @@ int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
- * of rm_render_gbuffer (none of them is a value rm_set_kernel_path takes). */
+ * of rm_render_gbuffer, 12 = a launch of rm_trace_rays (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -110,6 +110,18 @@ class RmCameraData(C.Structure):
     _fields_ = [("pos", f32 * 4), ("look", f32 * 4), ("up", f32 * 4), ("heightAngle", f32)]
 
 
+class RmRay(C.Structure):
+    _fields_ = [("origin", f32 * 3), ("tMax", f32), ("dir", f32 * 3), ("reserved", i32)]
+
+
+class RmRayHit(C.Structure):
+    _fields_ = [("normal", f32 * 3), ("t", f32), ("position", f32 * 3), ("objectId", i32)]
+
+
+RM_TRACE_CLOSEST, RM_TRACE_NO_NORMAL, RM_TRACE_OCCLUSION = 0, 1, 2  # mode of rm_trace_rays; NO_NORMAL is a flag on CLOSEST
+RM_RAY_INVALID = -2  # RmRayHit.objectId of an invalid ray
+
+
 def default_settings(**over):
     """RmSettings with the reference's constants (frag:28,29,45,1056; frag:9,15)."""
     s = RmSettings(0, 0, 0, 0, 0, 256, 20, 4, 1, RM_FEAT_REFERENCE_DEFAULT)

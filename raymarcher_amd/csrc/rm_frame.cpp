@@ -259,8 +259,8 @@ void scene_cull_ball(SceneBlock *h) {
 // triangle: P0, P1 − P0, P2 − P0 with P0 = (sg, sg), P1 = (−sg, sg), P2 = (sg, −sg), sg = −1 below the TL-BR diagonal and
 // +1 above it.  invProjView·(x, y, z, 1) = ((M0·x + M1·y) + M2·z) + M3, fused — the oracle's mat4_mul_v4, on the host's
 // binary32 FMA (the same bits on any IEEE machine).
-void ray_planes(SceneBlock *h) {
-  const float *M = h->cam.invProjView;
+namespace {
+void ray_planes_of(const float *M, float rayPlane[2][2][3][4]) {
   auto corner = [&](float x, float y, float z, float out[4]) {
     for (int c = 0; c < 4; c++) out[c] = std::fmaf(M[12 + c], 1.0f, std::fmaf(M[8 + c], z, std::fmaf(M[4 + c], y, M[c] * x)));
   };
@@ -271,13 +271,15 @@ void ray_planes(SceneBlock *h) {
       float p0[4], p1[4], p2[4];
       corner(sg, sg, z, p0); corner(-sg, sg, z, p1); corner(sg, -sg, z, p2);
       for (int c = 0; c < 4; c++) {
-        h->rayPlane[tri][k][0][c] = p0[c];
-        h->rayPlane[tri][k][1][c] = p1[c] - p0[c];
-        h->rayPlane[tri][k][2][c] = p2[c] - p0[c];
+        rayPlane[tri][k][0][c] = p0[c];
+        rayPlane[tri][k][1][c] = p1[c] - p0[c];
+        rayPlane[tri][k][2][c] = p2[c] - p0[c];
       }
     }
   }
 }
+}  // namespace
+void ray_planes(SceneBlock *h) { ray_planes_of(h->cam.invProjView, h->rayPlane); }
 
 // What an evaluation reads of an object (SceneBlock::evalRec), incl. the bound of the table walk's pass-over test, from h->objs.
 void scene_eval_records(SceneBlock *h) {
@@ -509,6 +511,45 @@ int rm_debug_bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g
   if ((!objs && numObjects > 0) || !g) { set_error("null pointer"); return -1; }
   if (numObjects < 0 || numObjects > RM_MAX_OBJECTS) { set_error("numObjects out of range"); return -1; }
   return bulb_plain(objs, numObjects, g);
+}
+
+// rm_camera_rays (the header has the definition): the host restatement of ray_planes + the device's primaryRay (rm_device.hip.h:
+// quadCoord, the two fused interpolations, the divisions by w, normalize = v · (1 / len)) with the same operations in the same
+// order — binary32 fmaf, correctly rounded divide and square root, nothing contracted (-ffp-contract=off) — so the same bits.
+int rm_camera_rays(const RmCamera *cam, int W, int H, const int32_t *xy, int n, RmRay *out) {
+  if (!cam || !out) { set_error("null camera or output"); return RM_ERR_INVALID_ARGUMENT; }
+  if (W <= 0 || H <= 0 || n < 0) { set_error("bad frame size or count"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!xy && (long long)n != (long long)W * H) { set_error("without a pixel list n must be W·H"); return RM_ERR_INVALID_ARGUMENT; }
+  if (xy)
+    for (int i = 0; i < n; i++)
+      if (xy[2 * i] < 0 || xy[2 * i] >= W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= H) {
+        set_error("pixel " + std::to_string(i) + " lies outside the frame");
+        return RM_ERR_INVALID_ARGUMENT;
+      }
+  float P[2][2][3][4];
+  ray_planes_of(cam->invProjView, P);
+  for (int i = 0; i < n; i++) {
+    const int px = xy ? xy[2 * i] : i % W, py = xy ? xy[2 * i + 1] : i / W;
+    const float tx = ((float)px + 0.5f) / (float)W, ty = ((float)py + 0.5f) / (float)H;
+    const int upper = (tx + ty) > 1.0f;
+    const float I = upper ? 1.0f - tx : tx, J = upper ? 1.0f - ty : ty;
+    float nc[4], fc[4];
+    for (int k = 0; k < 4; k++) {
+      nc[k] = std::fmaf(J, P[upper][0][2][k], std::fmaf(I, P[upper][0][1][k], P[upper][0][0][k]));
+      fc[k] = std::fmaf(J, P[upper][1][2][k], std::fmaf(I, P[upper][1][1][k], P[upper][1][0][k]));
+    }
+    RmRay &r = out[i];
+    float d[3];
+    for (int k = 0; k < 3; k++) {
+      r.origin[k] = nc[k] / nc[3];
+      d[k] = fc[k] / fc[3] - r.origin[k];
+    }
+    const float inv = 1.0f / std::sqrt(std::fmaf(d[2], d[2], std::fmaf(d[1], d[1], d[0] * d[0])));
+    for (int k = 0; k < 3; k++) r.dir[k] = d[k] * inv;
+    r.tMax = cam->initialFar;
+    r.reserved = 0;
+  }
+  return RM_OK;
 }
 
 }  // extern "C"

@@ -92,6 +92,11 @@ int launch_render_anim(const void *sb, const RestageBits &restage, int bulbClass
 // d_position is not null, the surface point of every pixel's primary hit, W·H elements per frame.
 int launch_gbuffer_kernel(const void *sb, int bulbClass, dim3 grid, dim3 block, int W, int H, float *d_normalDepth, int32_t *d_objectId,
                           float *d_position, hipStream_t stream);
+// The trace kernels (rm_trace.hip, rm_trace_rays; a translation unit of its own for the same reason): the launch of
+// trace_kernel<bulbClass, closest / occlusion> over the ONE staged SceneBlock `sb`, one lane per ray — numRays RmRay from d_rays,
+// numRays RmRayHit into d_hits.  noNormal (closest only): the surface point and the normal are left out, zeros stored.
+int launch_trace_kernel(const void *sb, int bulbClass, bool occlusion, bool noNormal, const void *d_rays, int numRays, void *d_hits,
+                        hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

@@ -1044,6 +1044,82 @@ int launch_gbuffer(const GBufferCall &c) {
   return finish_frames(*ds, sf, 11, c.stream);
 }
 
+// ---- rays from memory: closest hits and occlusion (rm_trace_rays) -----------------------------------------------------------------
+// rm_trace_rays (the header has the definition): the caller's rays against ONE object table.  TraceCall stands beside GBufferCall;
+// its checks run in check_gbuffer's order, every one but the last ahead of the first HIP call: numRays (negative; zero is RM_OK;
+// every int fits one grid of 256-lane workgroups), the scene pointers, the mode bits, the layers and the 2-D mode a ray is not
+// defined through, the table's limits and types, the arrays (null, alignment of the float4 accesses), then whether they are
+// device memory.
+// Staging is a one-frame batch's: one slot of the batch ring, fill_frames with a zeroed camera, no lights and no resources — the
+// evaluation records, the cull ball and box with cullLip and cullOneOk, bulbPlain — upload_frames with the default launch fields
+// (and the sponge prologue when the table holds one).  rayPlane and cam are staged (zeros) and never read.  The occlusion mode
+// stages two fields of its own: s.enableSoftShadow = 1, so that march<…, SHADOW> tracks the penumbra factor whatever the caller's
+// settings say, and cullR2Soft = 0.  scene_cull_ball derives that larger ball for shadow rays that start on a surface, inside the
+// cull ball, where t <= ρ + R; a caller's ray may start anywhere, so with it a far origin would settle the factor too early.
+// Without it a soft march ends at tMax, as the reference's does.  (The hard bounds — ball, box, the bulb's own ball — argue about
+// points, not origins, and hold for any ray.)
+// Then ONE launch of trace_kernel (rm_trace.hip), path 12: no tuner, tile-order or workspace state is read or changed.
+struct TraceCall {
+  const RmRay *d_rays; int numRays;
+  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s;
+  unsigned mode; RmRayHit *d_hits; hipStream_t stream;
+};
+int check_trace(const TraceCall &c) {
+  if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numRays == 0) return RM_OK;
+  static_assert(((long long)INT_MAX + 255) / 256 <= INT_MAX, "every int numRays fits one grid of 256-lane workgroups");
+  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || c.numObjects < 0) {
+    set_error("null scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (c.mode & ~(RM_TRACE_NO_NORMAL | RM_TRACE_OCCLUSION)) { set_error("unknown mode bits"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((c.mode & RM_TRACE_NO_NORMAL) && (c.mode & RM_TRACE_OCCLUSION)) {
+    set_error("RM_TRACE_NO_NORMAL is a flag on RM_TRACE_CLOSEST: occlusion stores no normal anyway");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
+    set_error("rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+    return RM_ERR_UNSUPPORTED;
+  }
+  if (c.g->isTwoD) { set_error("the 2-D mode (isTwoD) marches no ray"); return RM_ERR_UNSUPPORTED; }
+  if (c.numObjects > RM_MAX_OBJECTS) { set_error("scene exceeds RM_MAX_OBJECTS"); return RM_ERR_CAPACITY; }
+  if (c.s->maxSteps < 0 || c.s->fractalIters < 0 || c.s->mengerLevels < 0) {
+    set_error("negative loop bound in RmSettings");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  for (int i = 0; i < c.numObjects; i++)
+    if (c.objs[i].type < 0 || c.objs[i].type >= RM_CUSTOM) {
+      set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
+      return RM_ERR_UNSUPPORTED;
+    }
+  if (!c.d_rays || !c.d_hits) { set_error("null d_rays or d_hits"); return RM_ERR_INVALID_ARGUMENT; }
+  if (((uintptr_t)c.d_rays | (uintptr_t)c.d_hits) & 15u) { set_error("d_rays and d_hits must be 16-byte aligned"); return RM_ERR_INVALID_ARGUMENT; }
+  return require_device_pointers({{"d_rays", c.d_rays}, {"d_hits", c.d_hits}});
+}
+int launch_trace(const TraceCall &c) {
+  int st = check_trace(c);
+  if (st != RM_OK || c.numRays == 0) return st;
+  const bool occlusion = (c.mode & RM_TRACE_OCCLUSION) != 0;
+  // the march class of the call, as launch_gbuffer's
+  const bool bulb = c.numObjects == 1 && c.objs[0].type == RM_MANDELBULB;
+  const int bulbClass = bulb ? (bulb_plain(c.objs, c.numObjects, c.g) ? kBulbPlain : kBulbGeneral) : 0;
+  RmSettings s = *c.s;
+  if (occlusion) s.enableSoftShadow = 1;
+  const RmCamera noCam{};
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  if ((st = acquire_slot(ds->batches, 1, &sf.slot)) != RM_OK) return st;
+  fill_frames(sf.slot->host, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, &s, kNoResources);
+  if (occlusion) sf.slot->host->cullR2Soft = 0.0f;
+  if ((st = upload_frames(*sf.slot, 1, LaunchFields{}, c.stream)) != RM_OK) return st;
+  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if ((st = launch_trace_kernel(sf.slot->dev, bulbClass, occlusion, (c.mode & RM_TRACE_NO_NORMAL) != 0, c.d_rays, c.numRays, c.d_hits,
+                                c.stream)) != RM_OK) return st;
+  return finish_frames(*ds, sf, 12, c.stream);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1142,6 +1218,11 @@ int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlo
                       const RmSettings *s, int W, int H, float *d_normalDepth, int32_t *d_objectId, float *d_position, void *stream) {
   return launch_gbuffer(GBufferCall{cams, globals, numGlobals, numFrames, objs, numObjects, s, W, H, d_normalDepth, d_objectId, d_position,
                                     static_cast<hipStream_t>(stream)});
+}
+
+int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                  unsigned mode, RmRayHit *d_hits, void *stream) {
+  return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream)});
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

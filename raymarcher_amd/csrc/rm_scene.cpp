@@ -662,6 +662,8 @@ int rm_abi_sizeof(int which) {
     case 8: return (int)sizeof(RmTexture);
     case 9: return (int)sizeof(RmPostSettings);
     case 10: return (int)sizeof(RmResources);
+    case 11: return (int)sizeof(RmRay);
+    case 12: return (int)sizeof(RmRayHit);
     default: return -1;
   }
 }

@@ -187,6 +187,23 @@ def shutter_globals(globals_, t_open, t_close, n):
     return out
 
 
+def camera_rays(camera, W, H, pixels=None):
+    """rm_camera_rays: the primary rays of `camera` (an RmCamera) for a W×H frame → float32 (n, 8) numpy array, one RmRay per row:
+    (origin.xyz, tMax = the camera's initialFar, dir.xyz, 0).  pixels: None (every pixel, row-major, row 0 at the bottom, n = W·H)
+    or n pairs (x, y).  Origin and dir are bit for bit what rm_render and rm_render_gbuffer use for that pixel, so
+    Renderer.trace_rays on them gives the G-buffer's values.  A host function: it needs no GPU."""
+    import numpy as np
+    if pixels is None:
+        xy, n = None, int(W) * int(H)
+    else:
+        xy = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        n = len(xy)
+    out = np.zeros((n, 8), dtype=np.float32)
+    check(lib().rm_camera_rays(C.byref(camera), W, H, xy.ctypes.data_as(C.POINTER(C.c_int32)) if xy is not None else None, n,
+                               C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def translated_objects(objs, index, offsets):
     """The stacked object tables of Renderer.render_animated for one moving object: table b is a copy of `objs` (a sequence or
     ctypes array of RmObject) whose entry `index` is moved by offsets[b] = (x, y, z) in world space through rm_object_translated
@@ -475,6 +492,38 @@ class Renderer:
                                       C.c_void_p(nd.data_ptr()), C.c_void_p(ids.data_ptr()),
                                       C.c_void_p(pos.data_ptr()) if position else None, self._stream()))
         return (nd, ids, pos) if position else (nd, ids)
+
+    def trace_rays(self, tables, settings, rays, mode="closest", normals=True, out=None):
+        """rm_trace_rays: what arbitrary rays hit, one lane per ray in one launch → (normal, t, position, object_id): float32 (n, 3),
+        float32 (n), float32 (n, 3) and int32 (n), views of ONE float32 (n, 8) device tensor of RmRayHit rows (`out`, if given).
+        rays: float32 (n, 8) rows of RmRay (origin.xyz, tMax, dir.xyz, unused) — a numpy array, which is uploaded, or a tensor on
+        this device; dir is used as given, so t is in units of |dir|.  mode "closest": object_id = the object's index in
+        tables.objects (−1: a miss, with t = tMax and zeros; abi.RM_RAY_INVALID: a non-finite or zero ray), t, the surface point
+        and its normal; normals=False leaves the point and the normal out (zeros).  mode "occlusion": the renderer's shadow march:
+        object_id = the occluder (−1: none), t = the penumbra factor; visibility is t where object_id == −1, else 0.  Lights,
+        textures, the camera and the shading settings play no part; the definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        if mode not in ("closest", "occlusion"):
+            raise ValueError(f"mode = {mode!r}: 'closest' or 'occlusion'")
+        if not t.is_tensor(rays):
+            import numpy as np
+            rays = t.from_numpy(np.ascontiguousarray(rays, dtype=np.float32)).to(self.device)
+        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != t.float32 or not rays.is_contiguous() or rays.device != self.device:
+            raise ValueError(f"rays must be a contiguous float32 tensor of shape (n, 8) on {self.device}")
+        n = rays.shape[0]
+        hits = self._out(out, (n, 8), t.float32)
+        bits = abi.RM_TRACE_OCCLUSION if mode == "occlusion" else (abi.RM_TRACE_CLOSEST if normals else abi.RM_TRACE_NO_NORMAL)
+        check(lib().rm_trace_rays(C.c_void_p(rays.data_ptr()), n, tables.objects, tables.num_objects, C.byref(tables.globals_),
+                                  C.byref(settings), bits, C.c_void_p(hits.data_ptr()), self._stream()))
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def pick(self, tables, settings, W, H, x, y, camera=None):
+        """What lies under pixel (x, y) of a W×H frame (y = 0 the bottom row) → (object_id, position, normal, t): an int (−1: nothing),
+        two tuples of three floats and a float, through camera_rays and trace_rays — the values rm_render_gbuffer has for that
+        pixel.  camera: None (the scene's own) or an RmCamera.  It waits for the result."""
+        ray = camera_rays(tables.camera if camera is None else camera, W, H, [(x, y)])
+        normal, t, position, object_id = self.trace_rays(tables, settings, ray)
+        return (int(object_id[0]), tuple(position[0].tolist()), tuple(normal[0].tolist()), float(t[0]))
 
     def render_counted(self, tables, settings, W, H, mode=abi.RM_COUNT_REFERENCE):
         """rm_render_counted_res: the frame plus its work counters — the reference's work (mode RM_COUNT_REFERENCE) or
