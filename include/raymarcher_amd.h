@@ -468,6 +468,42 @@ int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int nu
  * null cam or out, W or H <= 0, n < 0, n != W·H without xy, a pixel outside the frame (nothing is written then).
  */
 int rm_camera_rays(const RmCamera *cam, int W, int H, const int32_t *xy, int n, RmRay *out);
+/*
+ * rm_shade_rays — the renderer's full COLOUR for arbitrary rays: the shader's whole main, from the background colour to BrightColor,
+ * for rays from device memory (no reference counterpart: the shader only shades the rays of its one pinhole camera).  For 360°
+ * panoramas and fisheyes, the faces of an environment probe, stereo pairs, and the colour along a handful of rays (a mirror preview,
+ * a light probe).  d_rays: numRays RmRay in device memory; d_rgba and d_bright (may be NULL): numRays float4 each in device memory
+ * (all three 16-byte aligned); the tables, g, s and res (may be NULL) are host memory, copied before return.  Asynchronous on
+ * `stream`.
+ * Definition, bit for bit.  The colour of ray i is what main computes for a pixel whose primary ray is ro = origin, rd = dir, with
+ * far = the call's `far`: the background colour for rd (frag:2405-2419: sky, night sky, white, dark, later bits overriding earlier
+ * ones); render(ro, rd, OUTSIDE, far, bg) (frag:2443, 2318-2375), the sky box on a miss; the reflection loop (frag:2491-2524) and the
+ * refraction pair (frag:2526-2570); fragColor = phong + refl + refr with its alpha 1 + bounces (frag:2572); bright = BrightColor of
+ * it (frag:1938-1946), (0, 0, 0, 1) for a ray that hit nothing.  dir is used as given, NOT normalised, which is rm_trace_rays'
+ * rule: a ray that copies primaryRay's ro and rd (rm_camera_rays) reproduces rm_render's pixel in every bit, colour and bright.  The
+ * shader's Phong (the view vector, the specular term) assumes a unit rd: pass unit directions unless a scaled one is meant.
+ * `far` is ONE value per call, as the shader has one per frame; RmRay.tMax is NOT read (nor is `reserved`).  Every device function
+ * reads far as uniform over the wave, and the bulb class marches a pixel's shadow rays on whichever lane is idle.
+ * Invalid ray: a non-finite component of origin or dir, or dir all zeros.  It stores (0, 0, 0, 0) in both outputs and evaluates
+ * nothing; a valid ray's alpha is >= 1, so alpha 0 marks it.  Rays are device data: the host cannot refuse them.  The result of a ray
+ * does not depend on which other rays share its call.
+ * numRays == 0: RM_OK, nothing read or written.  Otherwise, in this order and all but the last before any HIP call:
+ * RM_ERR_INVALID_ARGUMENT: numRays < 0, null g or s, a null table with a positive count or a negative count, far NaN, negative or
+ * infinite; RM_ERR_UNSUPPORTED: RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA (rays through the layers are not defined here),
+ * g->isTwoD; then rm_render_res's checks of the scene with its statuses: a bad texture table, RM_ERR_CAPACITY beyond RM_MAX_OBJECTS /
+ * RM_MAX_LIGHTS / RM_MAX_TEXTURES, a negative loop bound, RM_ERR_UNSUPPORTED for a night sky, sky box, texLoc or area light without
+ * its sampler and for a CUSTOM or unknown object or light type; RM_ERR_INVALID_ARGUMENT: null or misaligned d_rays / d_rgba, a
+ * misaligned d_bright; an array or a sampler's pixels that are not device memory.
+ * Schedule: ONE launch, one lane per ray, of the shade kernel of the scene's class (the twelve classes of the render kernels;
+ * rm_debug_last_path() = 13, rm_debug_last_split() = 0); it uses one slot of the batch ring of scene blocks and neither reads nor
+ * changes the per-stream tuner and tile-order state of single-frame renders, and no library workspace: no wavefront pipeline, no
+ * light split.  With rm_set_timing(1) it counts as one launch, all stage 1.  Rays that share a wave (64 consecutive rays) and go
+ * different ways cost what the longest of them costs: keep neighbours together (for an image, 8×8 pixel tiles).
+ * Added without a change of RM_ABI_VERSION (a new symbol and nothing else): bindings detect it by symbol lookup.
+ */
+int rm_shade_rays(const RmRay *d_rays, int numRays, float far, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                  const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */, float *d_rgba,
+                  float *d_bright /* may be NULL */, void *stream);
 
 /*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
@@ -584,8 +620,8 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer or rm_trace_rays, and so does a
- * whole call of rm_render_adaptive.
+ * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer, rm_trace_rays or rm_shade_rays,
+ * and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -615,7 +651,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
- * of rm_render_gbuffer, 12 = a launch of rm_trace_rays (none of them is a value rm_set_kernel_path takes). */
+ * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays (none of them is a value rm_set_kernel_path
+ * takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -120,6 +120,7 @@ class RmRayHit(C.Structure):
 
 RM_TRACE_CLOSEST, RM_TRACE_NO_NORMAL, RM_TRACE_OCCLUSION = 0, 1, 2  # mode of rm_trace_rays; NO_NORMAL is a flag on CLOSEST
 RM_RAY_INVALID = -2  # RmRayHit.objectId of an invalid ray
+RM_PATH_TRACE_RAYS, RM_PATH_SHADE_RAYS = 12, 13  # rm_debug_last_path() behind a launch of rm_trace_rays / rm_shade_rays
 
 
 def default_settings(**over):

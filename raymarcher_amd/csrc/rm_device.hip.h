@@ -1417,20 +1417,29 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // SEC = false compiles main's secondary rays out (reflection loop, refraction): the launcher picks it when the settings or the
 // materials rule them out for the whole frame, so that what render() hands over for them (hit point, normal, direction) is not
 // carried across the shadow marches — fewer registers spilled around the hot loops, the same pixels.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+// ONE body serves pixels and rays.  RAY = false (every render kernel): the pixel part — the pixel's coordinates, the 2-D mode,
+// primaryRay — in front of the ray part, main from the background colour (frag:2405) to BrightColor.  RAY = true (shadeRay below,
+// shade_rays_kernel in rm_shade.hip): the pixel part is compiled out and the ray part runs for the caller's (*rayO, *rayD) — rd used
+// as given, the shader's Phong assumes it unit — with far = sb->cam.initialFar; px, py and H are not read, and W only by envLayers'
+// sea normal (frag:2444-2456), unread without the layers.  The ray part reads nothing else of the camera and nothing of the pixel.
+// The pixel form is written so that its instantiations compile to what they did before the ray form existed: the code objects of
+// the render kernels are byte-identical.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
-                       V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
+                       V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0},
+                       const V3 *rayO = nullptr, const V3 *rayD = nullptr) {
   float ndcx, ndcy;
-  pixelNdc(px, py, W, H, ndcx, ndcy);
+  if (!RAY) pixelNdc(px, py, W, H, ndcx, ndcy);
   bright = v4(0.0f, 0.0f, 0.0f, 1.0f);
   hitFlag = false;
-  if (sb->g.isTwoD) {  // frag:2431, 2377-2380
+  if (!RAY && sb->g.isTwoD) {  // frag:2431, 2377-2380
     float s = sdMandelBrot(sb, ndcx, ndcy);
     fragColor = v4(pow_(s, 0.9f), pow_(s, 1.1f), pow_(s, 1.4f), 1.0f);
     return;
   }
   V3 ro, rd;
-  primaryRay(sb, px, py, W, H, ro, rd);
+  if (RAY) { ro = *rayO; rd = *rayD; }
+  else primaryRay(sb, px, py, W, H, ro, rd);
   const V3 bg = ENV ? backgroundColor(sb, rd) : backgroundColor(sb);
   const uint32_t feat = sb->s.features;
   const bool env = ENV && (feat & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) != 0;
@@ -1515,6 +1524,12 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
   V3 c = v3(fragColor.x, fragColor.y, fragColor.z);
   float brightness = dot(c, v3(0.2126f, 0.7152f, 0.0722f));  // frag:1938-1946
   if (brightness > 1.0f) bright = v4(c.x, c.y, c.z, 1.0f);
+}
+// The ray part alone: the colour, bright value and hit flag of the ray (ro, rd), for rays that do not come from a pixel.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+RM_DEV void shadeRay(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, int W, V4 &fragColor, V4 &bright, Counters &cnt,
+                     bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
+  shadePixel<BULB, COUNT, ENV, TEX, SEC, SPLIT, true>(sb, objs, 0, 0, W, 1, fragColor, bright, cnt, hitFlag, split, &ro, &rd);
 }
 
 }  // namespace rm

@@ -97,6 +97,11 @@ int launch_gbuffer_kernel(const void *sb, int bulbClass, dim3 grid, dim3 block, 
 // numRays RmRayHit into d_hits.  noNormal (closest only): the surface point and the normal are left out, zeros stored.
 int launch_trace_kernel(const void *sb, int bulbClass, bool occlusion, bool noNormal, const void *d_rays, int numRays, void *d_hits,
                         hipStream_t stream);
+// The shade kernels (rm_shade.hip, rm_shade_rays; a translation unit of its own for the same reason): the launch of
+// shade_rays_kernel<bulbClass, env, tex, sec> over the ONE staged SceneBlock `sb`, one lane per ray — numRays RmRay from d_rays,
+// numRays float4 of colour into d_rgba and, when d_bright is not null, of bright values into d_bright.
+int launch_shade_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const void *d_rays, int numRays, float *d_rgba,
+                        float *d_bright, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the
@@ -143,8 +148,8 @@ constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
 // The single-Mandelbulb class (the kernels' BULB template parameter; 0 = the table walk): any object transform, power and
 // Julia seed, or the plain form that SceneBlock::bulbPlain describes.
 constexpr int kBulbGeneral = 1, kBulbPlain = 2;
-// The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel, adaptive_refine_kernel and
-// render_acc_kernel are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
+// The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel, adaptive_refine_kernel,
+// render_acc_kernel and shade_rays_kernel are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
 // then the plain table walk, each with main's secondary rays compiled in only where they can fire (sec).
 template <int BULB, bool ENV, bool TEX, bool SEC>
 struct KernelClass { static constexpr int bulb = BULB; static constexpr bool env = ENV, tex = TEX, sec = SEC; };

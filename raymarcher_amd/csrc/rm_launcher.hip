@@ -1120,6 +1120,67 @@ int launch_trace(const TraceCall &c) {
   return finish_frames(*ds, sf, 12, c.stream);
 }
 
+// ---- rays from memory: the full colour (rm_shade_rays) ----------------------------------------------------------------------------
+// rm_shade_rays (the header has the definition): the shader's whole main for the caller's rays against ONE scene.  ShadeCall stands
+// beside TraceCall; its checks run in check_trace's order, every one but the last ahead of the first HIP call: numRays (negative;
+// zero is RM_OK), the scene pointers and counts, far, the layers and the 2-D mode a ray is not defined through, then what
+// validate_scene checks of a frame — the limits, the loop bounds, the samplers a feature, an object or a light reads, the types,
+// with rm_render_res's statuses and texts — the arrays (null, alignment of the float4 accesses), and whether they, and the
+// resources' pixels, are device memory.
+// Staging is a one-frame batch's: one slot of the batch ring, fill_frames with the caller's lights and resources and a camera that
+// is zeros but for initialFar = far — the one far every device function reads, wave-uniform (a per-ray far would change which lane
+// of the shadow pool ends a pooled ray where) — upload_frames with the default launch fields (and the sponge prologue when the table
+// holds one).  rayPlane and the rest of cam are staged and never read.  The class is the frame's (classify_frame, bulb_class with
+// the plain form where bulb_plain finds it).  Then ONE launch of shade_rays_kernel (rm_shade.hip), path 13: no wavefront
+// pipeline, no light split, no tuner, tile-order or workspace state is read or changed.
+struct ShadeCall {
+  const RmRay *d_rays; int numRays; float far;
+  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
+  const RmGlobals *g; const RmSettings *s; const RmResources &res;
+  float *d_rgba, *d_bright; hipStream_t stream;
+};
+int check_shade(const ShadeCall &c, const RmCamera &cam) {
+  if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numRays == 0) return RM_OK;
+  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.numLights > 0 && !c.lights) || c.numObjects < 0 || c.numLights < 0) {
+    set_error("null scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (!(c.far >= 0.0f) || c.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
+    set_error("rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+    return RM_ERR_UNSUPPORTED;
+  }
+  if (c.g->isTwoD) { set_error("the 2-D mode (isTwoD) marches no ray"); return RM_ERR_UNSUPPORTED; }
+  if (int st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) return st;
+  if (!c.d_rays || !c.d_rgba) { set_error("null d_rays or d_rgba"); return RM_ERR_INVALID_ARGUMENT; }
+  if (((uintptr_t)c.d_rays | (uintptr_t)c.d_rgba | (uintptr_t)c.d_bright) & 15u) {
+    set_error("d_rays, d_rgba and d_bright must be 16-byte aligned");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (int st = require_device_pointers({{"d_rays", c.d_rays}})) return st;
+  return check_device_pointers(c.res, c.d_rgba, c.d_bright);
+}
+int launch_shade(const ShadeCall &c) {
+  RmCamera cam{};
+  cam.initialFar = c.far;
+  int st = check_shade(c, cam);
+  if (st != RM_OK || c.numRays == 0) return st;
+  const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
+  const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  DeviceState *ds;
+  if ((st = current_device_state(&ds)) != RM_OK) return st;
+  std::lock_guard<std::mutex> lock(ds->mu);
+  StagedFrames sf(c.stream);
+  if ((st = acquire_slot(ds->batches, 1, &sf.slot)) != RM_OK) return st;
+  fill_frames(sf.slot->host, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+  if ((st = upload_frames(*sf.slot, 1, LaunchFields{}, c.stream)) != RM_OK) return st;
+  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if ((st = launch_shade_kernel(sf.slot->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba,
+                                c.d_bright, c.stream)) != RM_OK) return st;
+  return finish_frames(*ds, sf, 13, c.stream);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
 // device's block) behind it.
 template <class Launch>
@@ -1223,6 +1284,12 @@ int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlo
 int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
                   unsigned mode, RmRayHit *d_hits, void *stream) {
   return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream)});
+}
+
+int rm_shade_rays(const RmRay *d_rays, int numRays, float far, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                  const RmGlobals *g, const RmSettings *s, const RmResources *res, float *d_rgba, float *d_bright, void *stream) {
+  return launch_shade(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba, d_bright,
+                                static_cast<hipStream_t>(stream)});
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
