@@ -32,9 +32,8 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
   }
   if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
   __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int x = ((int)blockIdx.x * (int)(blockDim.x >> 6) + wave) * 8 + (lane & 7);
-  const int y = (int)blockIdx.y * 8 + (lane >> 3);
+  int x, y;
+  tilePixel8x8(x, y);
   if (x >= W || y >= H) return;
   float acc[8] = {-0.0f, -0.0f, -0.0f, -0.0f, -0.0f, -0.0f, -0.0f, -0.0f};
 #pragma clang loop unroll(disable)

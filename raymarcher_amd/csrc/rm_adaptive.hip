@@ -69,14 +69,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void adapti
   sb += blockIdx.z;  // wave-uniform: the frame's own scene block
   list += (size_t)blockIdx.z * (size_t)W * (size_t)H;
   __shared__ RmObject s_objs[BULB ? 1 : RM_MAX_OBJECTS];
-  {
-    const int nd = sb->numObjects * (int)(sizeof(RmObject) / 4);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sb->objs);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(s_objs);
-    for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-  }
-  if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
-  __syncthreads();
+  stageWorkgroup<ENV, TEX>(sb, s_objs);
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t lx = lane & 7u, ly = lane >> 3;
   const uint32_t sub = ss == 2 ? (ly >> 1) * 4u + (lx >> 1) : (ly >> 2) * 2u + (lx >> 2);
@@ -101,11 +94,10 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void adapti
   }
 }
 
-int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, int frames, int wavesPerBlock, float threshold,
-                             uint8_t *d_mask, uint32_t *d_list, uint32_t *d_counts, hipStream_t stream) {
-  const dim3 grid((unsigned)((W + wavesPerBlock * 8 - 1) / (wavesPerBlock * 8)), (unsigned)((H + 7) / 8), (unsigned)frames);
-  hipLaunchKernelGGL(adaptive_classify_kernel, grid, dim3(64 * wavesPerBlock), 0, stream, reinterpret_cast<const float4 *>(d_rgba), W,
-                     H, f0, threshold, d_mask, d_list, d_counts);
+int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, dim3 grid, dim3 block, float threshold, uint8_t *d_mask,
+                             uint32_t *d_list, uint32_t *d_counts, hipStream_t stream) {
+  hipLaunchKernelGGL(adaptive_classify_kernel, grid, block, 0, stream, reinterpret_cast<const float4 *>(d_rgba), W, H, f0, threshold,
+                     d_mask, d_list, d_counts);
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

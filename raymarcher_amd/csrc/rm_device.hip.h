@@ -1532,4 +1532,29 @@ RM_DEV void shadeRay(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, i
   shadePixel<BULB, COUNT, ENV, TEX, SEC, SPLIT, true>(sb, objs, 0, 0, W, 1, fragColor, bright, cnt, hitFlag, split, &ro, &rd);
 }
 
+// The workgroup prologue of a kernel that shades: the object table into the kernel's own s_objs, its LDS copy for per-lane
+// (divergent) material lookups (declared there: an LDS variable's symbol carries the name of the function that declares it; the
+// single-bulb class reads one entry), the byte→unorm table for the launches that read samplers (wave-uniform condition; ends with
+// a barrier), then the barrier behind which every wave may read both.  render_ss_kernel, adaptive_refine_kernel and
+// shade_rays_kernel call it.  render_kernel, render_acc_kernel and render_anim_kernel keep the same statements in their bodies:
+// through the call their code objects came out different, and a change of theirs is a change to re-measure.
+template <bool ENV, bool TEX>
+RM_DEV void stageWorkgroup(const SceneBlock *sb, RmObject *s_objs) {
+  const int nd = sb->numObjects * (int)(sizeof(RmObject) / 4);
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(sb->objs);
+  uint32_t *dst = reinterpret_cast<uint32_t *>(s_objs);
+  for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
+  if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
+  __syncthreads();
+}
+// The pixel of this lane where a wave is an 8×8 tile, lane = ly·8 + lx, a workgroup's waves lie side by side and the tiles are
+// in raster order straight from blockIdx (render_kernel has the general mapping: tile order and tile shift).  render_ss_kernel,
+// render_acc_kernel and gbuffer_kernel call it; render_anim_kernel and adaptive_classify_kernel keep the expressions, for the
+// same reason.
+RM_DEV void tilePixel8x8(int &x, int &y) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  x = ((int)blockIdx.x * (int)(blockDim.x >> 6) + wave) * 8 + (lane & 7);
+  y = (int)blockIdx.y * 8 + (lane >> 3);
+}
+
 }  // namespace rm

@@ -28,6 +28,23 @@ namespace {
 bool tex_ok(const RmTexture &t) { return t.pixels && t.width > 0 && t.height > 0; }
 }  // namespace
 
+// object i's type is one the kernels evaluate
+static int check_object_type(const RmObject *objs, int i) {
+  if (objs[i].type >= 0 && objs[i].type < RM_CUSTOM) return RM_OK;
+  set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
+  return RM_ERR_UNSUPPORTED;
+}
+int check_object_table(const RmObject *objs, int numObjects, const RmSettings *s) {
+  if (numObjects > RM_MAX_OBJECTS) { set_error("scene exceeds RM_MAX_OBJECTS"); return RM_ERR_CAPACITY; }
+  if (s->maxSteps < 0 || s->fractalIters < 0 || s->mengerLevels < 0) {
+    set_error("negative loop bound in RmSettings");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  for (int i = 0; i < numObjects; i++)
+    if (int st = check_object_type(objs, i)) return st;
+  return RM_OK;
+}
+
 int validate_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                    const RmGlobals *g, const RmSettings *s, const RmResources &res) {
   const RmTexture *tex = res.textures;
@@ -58,10 +75,7 @@ int validate_scene(const RmCamera *cam, const RmObject *objs, int numObjects, co
       }
   }
   for (int i = 0; i < numObjects; i++) {
-    if (objs[i].type < 0 || objs[i].type >= RM_CUSTOM) {
-      set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
-      return RM_ERR_UNSUPPORTED;
-    }
+    if (int st = check_object_type(objs, i)) return st;
     if (objs[i].texLoc != -1) {
       const int t = objs[i].texLoc, ty = objs[i].type;
       if (t < 0 || t >= numTex) {
@@ -451,6 +465,10 @@ FrameClass classify_frame(const RmObject *objs, int numObjects, const RmLight *l
 // form where the launcher found it.
 int bulb_class(const FrameClass &fc, bool plainBulb) {
   return (fc.bulb && !fc.envFeatures && !fc.textured) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
+}
+// The same for the calls that march a bare object table (no layers, no samplers): the bulb class of a lone Mandelbulb.
+int table_bulb_class(const RmObject *objs, int numObjects, bool plainBulb) {
+  return (numObjects == 1 && objs[0].type == RM_MANDELBULB) ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
 }
 
 // The picture this launch renders: everything that decides a pixel (FNV-1a over the caller's tables and the row map) — what the

@@ -14,6 +14,9 @@ int env_int(const char *name, int def, int lo = INT_MIN, int hi = INT_MAX);
 // RM_OK, or the status of the first check the scene fails with its text in rm_last_error.
 int validate_scene(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                    const RmGlobals *g, const RmSettings *s, const RmResources &res);
+// The same for a bare object table whose pointers and count are checked (rm_render_gbuffer, rm_trace_rays): the capacity, the
+// loop bounds of the march and the types.
+int check_object_table(const RmObject *objs, int numObjects, const RmSettings *s);
 double sigma_max3(const double m[3][3]);
 void scene_cull_ball(SceneBlock *h);
 void ray_planes(SceneBlock *h);
@@ -38,6 +41,7 @@ struct FrameClass {
 FrameClass classify_frame(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
                           const RmSettings *s, int count);
 int bulb_class(const FrameClass &fc, bool plainBulb);
+int table_bulb_class(const RmObject *objs, int numObjects, bool plainBulb);
 
 unsigned long long picture_key(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                                const RmGlobals *g, const RmSettings *s, const RowMap &map);

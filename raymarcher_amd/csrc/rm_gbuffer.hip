@@ -38,9 +38,8 @@ __global__ __launch_bounds__(256, gbuffer_waves(BULB)) void gbuffer_kernel(
     const SceneBlock *__restrict__ sb, int W, int H, float4 *__restrict__ normalDepth, int32_t *__restrict__ objectId,
     float4 *__restrict__ position) {
   sb += blockIdx.z;  // wave-uniform: the frame's own scene block
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int x = ((int)blockIdx.x * (int)(blockDim.x >> 6) + wave) * 8 + (lane & 7);
-  const int y = (int)blockIdx.y * 8 + (lane >> 3);
+  int x, y;
+  tilePixel8x8(x, y);
   if (x >= W || y >= H) return;
   V3 ro, rd;
   primaryRay(sb, x, y, W, H, ro, rd);

@@ -103,11 +103,11 @@ int launch_trace_kernel(const void *sb, int bulbClass, bool occlusion, bool noNo
 int launch_shade_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const void *d_rays, int numRays, float *d_rgba,
                         float *d_bright, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
-// test over frames f0 … f0 + frames − 1 of d_rgba, into d_mask (may be null; whole-batch pointer) and the chunk's lists and
+// test over frames f0 … f0 + grid.z − 1 of d_rgba (grid: their 8×8 tiles), into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the
 // supersampling kernel of the class over those lists, grid.z = the chunk's frames, `sb` the chunk's first scene block.
-int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, int frames, int wavesPerBlock, float threshold,
-                             uint8_t *d_mask, uint32_t *d_list, uint32_t *d_counts, hipStream_t stream);
+int launch_adaptive_classify(const float *d_rgba, int W, int H, int f0, dim3 grid, dim3 block, float threshold, uint8_t *d_mask,
+                             uint32_t *d_list, uint32_t *d_counts, hipStream_t stream);
 int launch_adaptive_refine(const void *sb, int bulbClass, bool env, bool tex, bool sec, dim3 grid, dim3 block, int W, int H, int ss,
                            const uint32_t *d_list, const uint32_t *d_counts, float *d_rgba, float *d_bright, hipStream_t stream);
 #endif
@@ -149,8 +149,9 @@ constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
 // Julia seed, or the plain form that SceneBlock::bulbPlain describes.
 constexpr int kBulbGeneral = 1, kBulbPlain = 2;
 // The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel, adaptive_refine_kernel,
-// render_acc_kernel and shade_rays_kernel are instantiated with.  Layers and samplers (env, tex: the table walk, whatever the table holds) first, then the bulb class,
-// then the plain table walk, each with main's secondary rays compiled in only where they can fire (sec).
+// render_acc_kernel, render_anim_kernel and shade_rays_kernel are instantiated with.  Layers and samplers (env, tex: the table walk,
+// whatever the table holds) first, then the bulb class, then the plain table walk, each with main's secondary rays compiled in
+// only where they can fire (sec).
 template <int BULB, bool ENV, bool TEX, bool SEC>
 struct KernelClass { static constexpr int bulb = BULB; static constexpr bool env = ENV, tex = TEX, sec = SEC; };
 // Calls f(KernelClass<…>{}) for the class of a launch: `f` is a generic lambda that launches its kernel with the tag's members as

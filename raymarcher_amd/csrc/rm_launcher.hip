@@ -670,12 +670,28 @@ struct FrameCall {
   const RmObject *objsOf(int b) const { return objs + (numObjectTables == 1 ? 0 : (size_t)b * (size_t)numObjects); }
   const RmLight *lightsOf(int b) const { return lights + (numLightTables == 1 ? 0 : (size_t)b * (size_t)numLights); }
 };
-// The argument checks the four entry points share, every one ahead of the first HIP call (as launch_render's); an input that
-// fails several reports the first of this order.  numFrames = 0 passes: nothing to write, the caller returns RM_OK.  sampled: the
-// call renders an ss·W × ss·H sample frame (rm_render_supersampled; rm_render_adaptive, which checks it for ss = 1 too), whose
-// coordinates and tiles must fit the kernels' indices.  sizeCheck: the entry point's own check of the frame size, between those
-// and the scene's.
-int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(const FrameCall &) = nullptr) {
+// The launch of a one-lane-per-pixel kernel over `frames` frames of W × H pixels at ss samples per axis: waves_per_block() waves
+// side by side in a workgroup, each on a tile of 2^tileShift × (64 >> tileShift) samples, the tiles of a frame in grid.x and
+// grid.y and the frame in grid.z.
+constexpr int kTiles8x8 = 3;  // the tile shift of the launches that take no shape pin
+struct TileGrid { dim3 grid, block; };
+TileGrid tile_grid(int W, int H, int frames, int ss = 1, int tileShift = kTiles8x8) {
+  const long long nw = waves_per_block(), tileW = 1 << tileShift, tileH = 64 >> tileShift;
+  return {dim3((unsigned)(((long long)ss * W + nw * tileW - 1) / (nw * tileW)), (unsigned)(((long long)ss * H + tileH - 1) / tileH),
+               (unsigned)frames), dim3((unsigned)(64 * nw))};
+}
+// Its limits, for a frame whose ss·W and ss·H are at most INT_MAX / 8: the kernels' coordinates are 32-bit and come from blockIdx,
+// a grid's y extent is at most 65535 tiles, and the tiles of one frame stay countable in an int (as render_kernel's).
+bool tiles_fit(int W, int H, int ss) {
+  const dim3 g = tile_grid(W, H, 1, ss).grid;
+  return g.y <= 65535 && (long long)g.x * g.y <= INT_MAX;
+}
+
+// The head of every multi-frame call's argument checks, ahead of the first HIP call (as launch_render's); an input that fails
+// several reports the first of this order.  numFrames = 0 passes: nothing to write, the caller returns RM_OK.  coordText (or
+// null: launch_batch, whose kernel takes its tiles from the scene block's fields) and tilesText: the entry point's own texts where
+// the call renders an ss·W × ss·H sample frame whose coordinates and tiles must fit the kernels' indices.
+int check_frame_head(const FrameCall &c, int ss, const char *coordText, const char *tilesText) {
   if (c.numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
   // one scene block per sub-frame: the cap counts blocks
   if (c.blocks() > RM_MAX_BATCH_FRAMES) {
@@ -689,68 +705,99 @@ int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(cons
   }
   if (!c.cams || !c.globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
   if (c.W <= 0 || c.H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
-  if (sampled) {
-    if (c.W > INT_MAX / 8 / ss || c.H > INT_MAX / 8 / ss) { set_error("ss·W or ss·H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
-    // the kernel's sample coordinates are 32-bit and come from blockIdx: a grid's y extent is at most 65535 tiles, and the tiles of
-    // one frame stay countable in an int (as render_kernel's)
-    const int nw = waves_per_block();
-    const long long tilesX = ((long long)ss * c.W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)ss * c.H + 7) / 8;
-    if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many samples for one supersampled launch"); return RM_ERR_INVALID_ARGUMENT; }
+  if (coordText) {
+    if (c.W > INT_MAX / 8 / ss || c.H > INT_MAX / 8 / ss) { set_error(coordText); return RM_ERR_INVALID_ARGUMENT; }
+    if (!tiles_fit(c.W, c.H, ss)) { set_error(tilesText); return RM_ERR_INVALID_ARGUMENT; }
   }
-  int st = sizeCheck ? sizeCheck(c) : RM_OK;
-  if (st != RM_OK) return st;
+  return RM_OK;
+}
+// The argument checks of the entry points that render colour: the head, then sizeCheck, the entry point's own check of the frame
+// size, then the scene and the outputs.  sampled: rm_render_supersampled and the calls that, like it, take their coordinates
+// from blockIdx (rm_render_adaptive for ss = 1 too).
+int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(const FrameCall &) = nullptr) {
+  int st = check_frame_head(c, ss, sampled ? "ss·W or ss·H exceeds INT_MAX / 8" : nullptr, "too many samples for one supersampled launch");
+  if (st != RM_OK || c.numFrames == 0) return st;
+  if (sizeCheck && (st = sizeCheck(c)) != RM_OK) return st;
   if ((st = validate_scene(&c.cams[0], c.objs, c.numObjects, c.lights, c.numLights, &c.globals[0], c.s, c.res)) != RM_OK) return st;
   if (!c.d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
   return check_device_pointers(c.res, c.d_rgba, c.d_bright);
 }
+// The refusals of the entry points that are defined by the object table alone, each with the entry point's own text: the layers
+// that may cover the table, and the 2-D mode, which marches no ray.
+int refuse_layers(const RmSettings *s, const char *text) {
+  if (!(s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA))) return RM_OK;
+  set_error(text);
+  return RM_ERR_UNSUPPORTED;
+}
+int refuse_two_d(const RmGlobals *g, const char *text) {
+  if (!g->isTwoD) return RM_OK;
+  set_error(text);
+  return RM_ERR_UNSUPPORTED;
+}
 
-// What the staging step hands a multi-frame launcher.
+// What the staging step hands a launcher, and what holds the device's lock for it: from lock_device (or stage_blocks) until the
+// object goes, behind finish_frames.
 struct StagedFrames {
-  Slot *slot = nullptr;   // of the batch ring: one scene block per frame (not per sample) and sub-frame, filled and uploaded
+  DeviceState *ds = nullptr;
+  std::unique_lock<std::mutex> lock;  // ds->mu
+  Slot *slot = nullptr;   // one scene block per frame (not per sample) and sub-frame, filled and uploaded
   FrameClass fc{};        // shared by every frame
   bool plainBulb = true;  // the plain bulb form only where every frame (and sub-frame) has it
   int bulbClass = 0;      // bulb_class of the two
   LaunchTimer timer;      // stamped once, ahead of the caller's launches
   explicit StagedFrames(hipStream_t stream) : timer(stream) {}
+  // The current device's state and its lock, for a caller that needs them ahead of the staging (launch_adaptive's workspaces).
+  int lock_device() {
+    if (int st = current_device_state(&ds)) return st;
+    lock = std::unique_lock<std::mutex>(ds->mu);
+    return RM_OK;
+  }
 };
-// The staging step.  The caller holds the device's lock, from here to finish_frames at least; nothing here waits for the GPU but
-// acquire_slot at the ring's bounds.  tileShift: the tile shape of the launch (LaunchFields).  alone (or null): the frames that
-// are not part of the launch (launch_batch), which have no say in plainBulb.
-int stage_frames(DeviceState &ds, const FrameCall &c, int tileShift, const char *alone, StagedFrames *sf) {
+// The staging step of every launch but launch_render's own, between the argument checks and the first kernel: the device and its
+// lock, a slot of n blocks of `ring` (nothing here waits for the GPU but acquire_slot at the ring's bounds), the caller's fill of
+// the slot's pinned blocks, the upload with the launch fields (and the sponge prologue, upload_frames), the timing's start.
+template <class Fill>
+int stage_blocks(StagedFrames *sf, Ring DeviceState::*ring, int n, const LaunchFields &lf, bool mengerAnywhere, Fill fill) {
+  int st = sf->ds ? RM_OK : sf->lock_device();
+  if (st != RM_OK || (st = acquire_slot(sf->ds->*ring, n, &sf->slot)) != RM_OK) return st;
+  fill(sf->slot->host);
+  if ((st = upload_frames(*sf->slot, n, lf, sf->timer.stream, mengerAnywhere)) != RM_OK) return st;
+  return sf->timer.stamp();
+}
+// A FrameCall's staging: stage_blocks on the batch ring with fill_frames, and the class of the call.  tileShift: the tile shape
+// of the launch (LaunchFields).  alone (or null): the frames that are not part of the launch (launch_batch), which have no say
+// in plainBulb.
+int stage_frames(const FrameCall &c, int tileShift, const char *alone, StagedFrames *sf) {
   const int blocks = (int)c.blocks();  // = numFrames but for rm_render_accumulated (which passes no `alone`)
   for (int f = 0; f < blocks; f++)
     if (!alone || !alone[f]) sf->plainBulb = sf->plainBulb && bulb_plain(c.objs, c.numObjects, c.globalsOf(f));
-  int st = acquire_slot(ds.batches, blocks, &sf->slot);
-  if (st != RM_OK) return st;
-  fill_frames(sf->slot->host, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
-  LaunchFields lf;
-  lf.tileShift = tileShift;
-  if ((st = upload_frames(*sf->slot, blocks, lf, c.stream)) != RM_OK) return st;
   sf->fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.globalsOf(0), c.s, 0);
   sf->bulbClass = bulb_class(sf->fc, sf->plainBulb);
-  return sf->timer.stamp();
+  LaunchFields lf;
+  lf.tileShift = tileShift;
+  return stage_blocks(sf, &DeviceState::batches, blocks, lf, false, [&](SceneBlock *h) {
+    fill_frames(h, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+  });
 }
 // One launch of the one-lane-per-pixel kernel of the class over frames f0 … f0 + k − 1 of the staged slot (grid.z = k), straight
 // into the call's outputs: raster order, tiles 2^tileShift pixels wide (the shift the slot was staged with).
 int launch_frames(const FrameCall &c, const StagedFrames &sf, int f0, int k, int tileShift) {
-  const int nw = waves_per_block(), tileW = 1 << tileShift, tileH = 64 >> tileShift;
   const RowMap map{0, c.H, 0, 1, 0};
-  const dim3 grid((c.W + nw * tileW - 1) / (nw * tileW), (c.H + tileH - 1) / tileH, (unsigned)k);
+  const TileGrid t = tile_grid(c.W, c.H, k, 1, tileShift);
   const RenderLaunch r{sf.slot->dev + f0, map, c.W, c.H, c.H, reinterpret_cast<float4 *>(c.d_rgba), reinterpret_cast<float4 *>(c.d_bright),
-                       nullptr, c.stream, grid, dim3(64 * nw)};
+                       nullptr, c.stream, t.grid, t.block};
   return dispatch_render(sf.fc, 0, sf.plainBulb, SplitPlan{}, c.numLights, 0, r);
 }
 // The finishing step, behind the caller's last launch: the timing's end, rm_debug_last_path / rm_debug_last_split and the slot's event.
-int finish_frames(DeviceState &ds, StagedFrames &sf, int path, hipStream_t stream) {
+int finish_frames(StagedFrames &sf, int path) {
   if (int st = sf.timer.stamp()) return st;
   HIP_OK(hipGetLastError());
-  ds.lastPath = path;
-  ds.lastSplit = 0;
-  sf.timer.keep(ds);
-  HIP_OK(hipEventRecord(sf.slot->done, stream));
+  sf.ds->lastPath = path;
+  sf.ds->lastSplit = 0;
+  sf.timer.keep(*sf.ds);
+  HIP_OK(hipEventRecord(sf.slot->done, sf.timer.stream));
   return RM_OK;
 }
-constexpr int kTiles8x8 = 3;  // the tile shift of the launches that take no shape pin
 
 // ---- batches: rm_render_batch ------------------------------------------------------------------------------------------------
 // Every batched frame renders with the one-lane-per-pixel kernel in raster tile order (no tile-order history, no light split), 8×8
@@ -773,12 +820,9 @@ int launch_batch(const FrameCall &c) {
     anyBatched = anyBatched || !alone[f];
   }
   if (anyBatched) {
-    DeviceState *ds;
-    if ((st = current_device_state(&ds)) != RM_OK) return st;
-    std::lock_guard<std::mutex> lock(ds->mu);
     const int pinned = tile_shape_request(), tileShift = (pinned == 2 || pinned == 3) ? pinned : kDefaultTileShift;
-    StagedFrames sf(c.stream);
-    if ((st = stage_frames(*ds, c, tileShift, alone.data(), &sf)) != RM_OK) return st;
+    StagedFrames sf(c.stream);  // and the device's lock, to the end of this block: launch_render below takes it itself
+    if ((st = stage_frames(c, tileShift, alone.data(), &sf)) != RM_OK) return st;
     // one launch per run of consecutive batched frames (one run unless wavefront frames sit between them)
     for (int f0 = 0; f0 < c.numFrames;) {
       if (alone[f0]) { f0++; continue; }
@@ -787,7 +831,7 @@ int launch_batch(const FrameCall &c) {
       if ((st = launch_frames(c, sf, f0, f1 - f0, tileShift)) != RM_OK) return st;
       f0 = f1;
     }
-    if ((st = finish_frames(*ds, sf, 6, c.stream)) != RM_OK) return st;
+    if ((st = finish_frames(sf, 6)) != RM_OK) return st;
   }
   const size_t frame = (size_t)c.H * c.W * 4;  // floats per frame
   const RowMap whole{0, c.H, 0, 1, 0};
@@ -799,7 +843,7 @@ int launch_batch(const FrameCall &c) {
 }
 
 // ---- supersampled frames: ss × ss samples per pixel, resolved in the wave (render_ss_kernel) -----------------------------------
-// rm_render_supersampled.  A batch's staging, then ONE launch over (tilesX, tilesY, numFrames) 8×8 sample tiles in raster order for
+// rm_render_supersampled.  stage_frames, then ONE launch over (tilesX, tilesY, numFrames) 8×8 sample tiles in raster order for
 // every frame: no wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state read or written, no library
 // workspace.  The kernels are a translation unit of their own (rm_supersample.hip).
 int launch_supersampled(const FrameCall &c, int ss) {
@@ -807,20 +851,16 @@ int launch_supersampled(const FrameCall &c, int ss) {
   if (ss == 1) return launch_batch(c);
   int st = check_frames(c, ss, true);
   if (st != RM_OK || c.numFrames == 0) return st;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
-  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
-  const int nw = waves_per_block();
-  const dim3 grid((unsigned)((ss * c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((ss * c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
-  if ((st = launch_render_ss(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, grid, block, c.W, c.H, ss,
+  if ((st = stage_frames(c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  const TileGrid t = tile_grid(c.W, c.H, c.numFrames, ss);
+  if ((st = launch_render_ss(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, t.grid, t.block, c.W, c.H, ss,
                              c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
-  return finish_frames(*ds, sf, 7, c.stream);
+  return finish_frames(sf, 7);
 }
 
 // ---- adaptive supersampling: the 1-sample frame everywhere, ss × ss samples where it shows contrast ----------------------------
-// rm_render_adaptive (the header has the definition).  A batch's staging (one slot of the batch ring for the whole call), then per
+// rm_render_adaptive (the header has the definition).  stage_frames (one slot of the batch ring for the whole call), then per
 // chunk of frames, all on the caller's stream: (1) launch_frames, the one-lane-per-pixel launch of launch_batch (8×8 tiles always)
 // straight into the outputs — so an unflagged pixel is rm_render_batch's by construction —, (2) the classify kernel: mask,
 // per-frame lists of flagged pixels and their counts into the stream's workspace, (3) for ss > 1 the refine kernel over the lists,
@@ -838,9 +878,8 @@ int launch_adaptive(const FrameCall &c, int ss, float threshold, uint8_t *d_mask
   });
   if (st != RM_OK || c.numFrames == 0) return st;
   if ((st = require_device_pointers({{"d_mask", d_mask}, {"d_refined", d_refined}})) != RM_OK) return st;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);  // held to the last launch: the workspace is in use until then (rm_release_workspaces)
+  StagedFrames sf(c.stream);
+  if ((st = sf.lock_device()) != RM_OK) return st;  // ahead of the workspaces, which are in use until the last launch (rm_release_workspaces)
   // frames per chunk: 4 B of list per pixel under the workspace limit (a single frame above a set limit fails in stream_workspace)
   const size_t px = (size_t)c.W * (size_t)c.H;
   const unsigned long long limit = workspace_limit(), fit = (limit ? limit : kAdaptiveDefaultCap) / (4ull * px);
@@ -849,15 +888,15 @@ int launch_adaptive(const FrameCall &c, int ss, float threshold, uint8_t *d_mask
   if ((st = stream_workspace(kWsAdaptive, c.stream, (size_t)chunk * px * sizeof(uint32_t), &listMem)) != RM_OK) return st;
   if ((st = stream_workspace(kWsAdaptiveCounts, c.stream, RM_MAX_BATCH_FRAMES * sizeof(uint32_t), &countMem)) != RM_OK) return st;
   uint32_t *list = static_cast<uint32_t *>(listMem), *counts = static_cast<uint32_t *>(countMem);
-  StagedFrames sf(c.stream);
-  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  if ((st = stage_frames(c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
   const int nw = waves_per_block();
   for (int f0 = 0; f0 < c.numFrames; f0 += chunk) {
     const int k = c.numFrames - f0 < chunk ? c.numFrames - f0 : chunk;
     if ((st = launch_frames(c, sf, f0, k, kTiles8x8)) != RM_OK) return st;
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemsetAsync(counts, 0, (size_t)k * sizeof(uint32_t), c.stream));
-    if ((st = launch_adaptive_classify(c.d_rgba, c.W, c.H, f0, k, nw, threshold, d_mask, list, counts, c.stream)) != RM_OK) return st;
+    const TileGrid t = tile_grid(c.W, c.H, k);
+    if ((st = launch_adaptive_classify(c.d_rgba, c.W, c.H, f0, t.grid, t.block, threshold, d_mask, list, counts, c.stream)) != RM_OK) return st;
     if (d_refined) HIP_OK(hipMemcpyAsync(d_refined + f0, counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.stream));
     if (ss > 1) {
       // a frame's grid slice: enough waves for every pixel of it, at most the chunk's share of kRefineWaves
@@ -868,11 +907,11 @@ int launch_adaptive(const FrameCall &c, int ss, float threshold, uint8_t *d_mask
                                        c.W, c.H, ss, list, counts, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
     }
   }
-  return finish_frames(*ds, sf, 8, c.stream);
+  return finish_frames(sf, 8);
 }
 
 // ---- accumulated frames: the mean of subFrames renders per output frame, summed in the lane (render_acc_kernel) -----------------
-// rm_render_accumulated (the header has the definition).  A batch's staging with one scene block per SUB-frame — numFrames·subFrames
+// rm_render_accumulated (the header has the definition).  stage_frames with one scene block per SUB-frame — numFrames·subFrames
 // of them in one slot of the batch ring, which is all that grows with subFrames: "one block per sub-frame" also leaves room for
 // per-sub-frame object tables later — then ONE launch over (tilesX, tilesY, numFrames) 8×8 tiles in raster order whose lanes walk
 // their frame's blocks: no wavefront pipeline, no light split, no tile-shape pin, no tuner or tile-order state read or written, no
@@ -882,24 +921,19 @@ int launch_accumulated(const FrameCall &c) {
   if (c.subFrames < 1 || c.subFrames > RM_MAX_SUBFRAMES) { set_error("subFrames must be 1 … RM_MAX_SUBFRAMES"); return RM_ERR_INVALID_ARGUMENT; }
   int st = check_frames(c, 1, true);  // the frame's coordinates and tiles come from blockIdx, as a sample frame's do
   if (st != RM_OK || c.numFrames == 0) return st;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
-  if ((st = stage_frames(*ds, c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
-  const int nw = waves_per_block();
-  const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
-  if ((st = launch_render_acc(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, grid, block, c.W, c.H,
+  if ((st = stage_frames(c, kTiles8x8, nullptr, &sf)) != RM_OK) return st;
+  const TileGrid t = tile_grid(c.W, c.H, c.numFrames);
+  if ((st = launch_render_acc(sf.slot->dev, sf.bulbClass, sf.fc.envFeatures, sf.fc.textured, sf.fc.secondary, t.grid, t.block, c.W, c.H,
                               c.subFrames, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
-  return finish_frames(*ds, sf, 9, c.stream);
+  return finish_frames(sf, 9);
 }
 
 // ---- animated frames: object and light tables per block (rm_render_animated) ---------------------------------------------------
 // rm_render_animated (the header has the definition): rm_render_accumulated's call where numObjectTables / numLightTables say
 // whether every block brings an object / light table of its own.  The table counts and validate_scene of EVERY block (the error
 // text names the block) run as check_frames' size check, ahead of its pointer checks and of any HIP call.  Staging is
-// fill_frames_animated into one slot of the batch ring, one block per sub-frame, with the sponge prologue when any block holds a
-// sponge.  The class of the call is the most general one any block needs: textured / secondary if any block is, the bulb classes
+// stage_blocks with fill_frames_animated, one block per sub-frame, with the sponge prologue when any block holds a sponge.  The class of the call is the most general one any block needs: textured / secondary if any block is, the bulb classes
 // only if every block is a lone Mandelbulb, the plain form only if every block has it.  subFrames = 1: the production
 // render_kernel of that class over the blocks (launch_frames, 8×8 tiles); subFrames > 1: render_anim_kernel (rm_animate.hip), which
 // stages the object table again where the restage bits say it changed.  One launch either way, path 10: no wavefront pipeline,
@@ -942,117 +976,75 @@ int launch_animated(const FrameCall &c) {
     fc.secondary = fc.secondary || fb.secondary;
     for (int i = 0; i < c.numObjects; i++) menger = menger || c.objsOf(b)[i].type == RM_MENGERSPONGE;
   }
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
   sf.fc = fc;
   sf.plainBulb = plainBulb;
   sf.bulbClass = bulb_class(fc, plainBulb);
-  if ((st = acquire_slot(ds->batches, blocks, &sf.slot)) != RM_OK) return st;
   RestageBits restage;
-  fill_frames_animated(sf.slot->host, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.numObjectTables, c.lights,
-                       c.numLights, c.numLightTables, c.s, c.res, &restage);
-  if ((st = upload_frames(*sf.slot, blocks, LaunchFields{}, c.stream, menger)) != RM_OK) return st;
-  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if ((st = stage_blocks(&sf, &DeviceState::batches, blocks, LaunchFields{}, menger, [&](SceneBlock *h) {
+        fill_frames_animated(h, blocks, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, c.numObjectTables, c.lights, c.numLights,
+                             c.numLightTables, c.s, c.res, &restage);
+      })) != RM_OK) return st;
   if (c.subFrames == 1) {
     if ((st = launch_frames(c, sf, 0, c.numFrames, kTiles8x8)) != RM_OK) return st;
   } else {
-    const int nw = waves_per_block();
-    const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)c.numFrames), block(64 * nw);
-    if ((st = launch_render_anim(sf.slot->dev, restage, sf.bulbClass, fc.envFeatures, fc.textured, fc.secondary, grid, block, c.W, c.H,
+    const TileGrid t = tile_grid(c.W, c.H, c.numFrames);
+    if ((st = launch_render_anim(sf.slot->dev, restage, sf.bulbClass, fc.envFeatures, fc.textured, fc.secondary, t.grid, t.block, c.W, c.H,
                                  c.subFrames, c.d_rgba, c.d_bright, c.stream)) != RM_OK) return st;
   }
-  return finish_frames(*ds, sf, 10, c.stream);
+  return finish_frames(sf, 10);
 }
 
 // ---- G-buffers: what the primary ray hit (rm_render_gbuffer) -------------------------------------------------------------------
-// rm_render_gbuffer (the header has the definition): rm_render_batch's call shape without lights and resources, three outputs
-// instead of colour.  GBufferCall stands beside FrameCall, which carries both; its checks run in check_frames' order, every one
-// ahead of the first HIP call: numFrames, the cap, numFrames == 0, numGlobals, null cameras or globals, the frame size (the
-// coordinates and tiles come from blockIdx, as a sample frame's), then the scene — settings and table pointers, the layers and
-// the 2-D mode the G-buffer does not describe, the table's limits and types — then the outputs.  A texLoc, a sky box or an area
-// light's rectangle without its sampler is no error: nothing here reads one.
-// Staging is a batch's: one slot of the batch ring, fill_frames with no lights and no resources (one scene block per frame: cull
-// data, ray planes, bulbPlain), upload_frames with the default launch fields (and the sponge prologue when the table holds one).
-// Then ONE launch of gbuffer_kernel (rm_gbuffer.hip) over (tilesX, tilesY, numFrames) 8×8 tiles in raster order, path 11: no
-// wavefront pipeline, light split, tile-shape pin, tile order, tuner state or library workspace.
-struct GBufferCall {
-  const RmCamera *cams; const RmGlobals *globals; int numGlobals, numFrames;
-  const RmObject *objs; int numObjects; const RmSettings *s;
-  int W, H; float *d_normalDepth; int32_t *d_objectId; float *d_position; hipStream_t stream;
-  const RmGlobals *globalsOf(int f) const { return &globals[numGlobals == 1 ? 0 : f]; }
-};
-int check_gbuffer(const GBufferCall &c) {
-  if (c.numFrames < 0) { set_error("negative numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.numFrames > RM_MAX_BATCH_FRAMES) { set_error("numFrames exceeds RM_MAX_BATCH_FRAMES"); return RM_ERR_CAPACITY; }
-  if (c.numFrames == 0) return RM_OK;
-  if (c.numGlobals != 1 && c.numGlobals != c.numFrames) { set_error("numGlobals must be 1 or numFrames"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!c.cams || !c.globals) { set_error("null cameras or globals"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.W <= 0 || c.H <= 0) { set_error("bad frame size"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.W > INT_MAX / 8 || c.H > INT_MAX / 8) { set_error("W or H exceeds INT_MAX / 8"); return RM_ERR_INVALID_ARGUMENT; }
-  const int nw = waves_per_block();
-  const long long tilesX = ((long long)c.W + nw * 8 - 1) / (nw * 8), tilesY = ((long long)c.H + 7) / 8;
-  if (tilesY > 65535 || tilesX * tilesY > INT_MAX) { set_error("too many tiles for one launch"); return RM_ERR_INVALID_ARGUMENT; }
+// rm_render_gbuffer (the header has the definition): rm_render_batch's call shape without lights and resources — a FrameCall
+// that has none — and three outputs instead of colour.  Its checks run in check_frames' order, every one ahead of the first HIP
+// call: check_frame_head (the coordinates and tiles come from blockIdx, as a sample frame's), then the scene — settings and
+// table pointers, the layers and the 2-D mode the G-buffer does not describe, the table's limits and types — then the outputs.
+// A texLoc, a sky box or an area light's rectangle without its sampler is no error: nothing here reads one.
+// Staging is stage_blocks with fill_frames (one scene block per frame: cull data, ray planes, bulbPlain).  Then ONE launch of
+// gbuffer_kernel (rm_gbuffer.hip) over (tilesX, tilesY, numFrames) 8×8 tiles in raster order, path 11: no wavefront pipeline,
+// light split, tile-shape pin, tile order, tuner state or library workspace.
+int check_gbuffer(const FrameCall &c, const float *d_normalDepth, const int32_t *d_objectId, const float *d_position) {
+  int st = check_frame_head(c, 1, "W or H exceeds INT_MAX / 8", "too many tiles for one launch");
+  if (st != RM_OK || c.numFrames == 0) return st;
   if (!c.s || (c.numObjects > 0 && !c.objs) || c.numObjects < 0) {
     set_error("null scene pointer or negative count");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
-    set_error("rm_render_gbuffer describes the object table: TERRAIN / CLOUD / SEA may cover it");
-    return RM_ERR_UNSUPPORTED;
-  }
+  if ((st = refuse_layers(c.s, "rm_render_gbuffer describes the object table: TERRAIN / CLOUD / SEA may cover it")) != RM_OK) return st;
   for (int f = 0; f < c.numFrames; f++)
-    if (c.globalsOf(f)->isTwoD) {
-      set_error("frame " + std::to_string(f) + ": the 2-D mode (isTwoD) marches no ray, it has no G-buffer");
-      return RM_ERR_UNSUPPORTED;
+    if ((st = refuse_two_d(c.globalsOf(f), "the 2-D mode (isTwoD) marches no ray, it has no G-buffer")) != RM_OK) {
+      set_error("frame " + std::to_string(f) + ": " + rm_last_error());
+      return st;
     }
-  if (c.numObjects > RM_MAX_OBJECTS) { set_error("scene exceeds RM_MAX_OBJECTS"); return RM_ERR_CAPACITY; }
-  if (c.s->maxSteps < 0 || c.s->fractalIters < 0 || c.s->mengerLevels < 0) {
-    set_error("negative loop bound in RmSettings");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  for (int i = 0; i < c.numObjects; i++)
-    if (c.objs[i].type < 0 || c.objs[i].type >= RM_CUSTOM) {
-      set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
-      return RM_ERR_UNSUPPORTED;
-    }
-  if (!c.d_normalDepth || !c.d_objectId) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
-  return require_device_pointers({{"d_normalDepth", c.d_normalDepth}, {"d_objectId", c.d_objectId}, {"d_position", c.d_position}});
+  if ((st = check_object_table(c.objs, c.numObjects, c.s)) != RM_OK) return st;
+  if (!d_normalDepth || !d_objectId) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
+  return require_device_pointers({{"d_normalDepth", d_normalDepth}, {"d_objectId", d_objectId}, {"d_position", d_position}});
 }
-int launch_gbuffer(const GBufferCall &c) {
-  int st = check_gbuffer(c);
+int launch_gbuffer(const FrameCall &c, float *d_normalDepth, int32_t *d_objectId, float *d_position) {
+  int st = check_gbuffer(c, d_normalDepth, d_objectId, d_position);
   if (st != RM_OK || c.numFrames == 0) return st;
   const int n = c.numFrames;
-  // the march class of the call, as bulb_class: a lone Mandelbulb, its plain form only if every frame has it
+  // the march class of the call: a lone Mandelbulb, its plain form only if every frame has it
   bool plainBulb = true;
   for (int f = 0; f < n; f++) plainBulb = plainBulb && bulb_plain(c.objs, c.numObjects, c.globalsOf(f));
-  const bool bulb = c.numObjects == 1 && c.objs[0].type == RM_MANDELBULB;
-  const int bulbClass = bulb ? (plainBulb ? kBulbPlain : kBulbGeneral) : 0;
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
-  if ((st = acquire_slot(ds->batches, n, &sf.slot)) != RM_OK) return st;
-  fill_frames(sf.slot->host, n, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
-  if ((st = upload_frames(*sf.slot, n, LaunchFields{}, c.stream)) != RM_OK) return st;
-  if ((st = sf.timer.stamp()) != RM_OK) return st;
-  const int nw = waves_per_block();
-  const dim3 grid((unsigned)((c.W + nw * 8 - 1) / (nw * 8)), (unsigned)((c.H + 7) / 8), (unsigned)n), block(64 * nw);
-  if ((st = launch_gbuffer_kernel(sf.slot->dev, bulbClass, grid, block, c.W, c.H, c.d_normalDepth, c.d_objectId, c.d_position,
-                                  c.stream)) != RM_OK) return st;
-  return finish_frames(*ds, sf, 11, c.stream);
+  if ((st = stage_blocks(&sf, &DeviceState::batches, n, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, n, c.cams, c.globals, c.numGlobals, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
+      })) != RM_OK) return st;
+  const TileGrid t = tile_grid(c.W, c.H, n);
+  if ((st = launch_gbuffer_kernel(sf.slot->dev, table_bulb_class(c.objs, c.numObjects, plainBulb), t.grid, t.block, c.W, c.H, d_normalDepth,
+                                  d_objectId, d_position, c.stream)) != RM_OK) return st;
+  return finish_frames(sf, 11);
 }
 
 // ---- rays from memory: closest hits and occlusion (rm_trace_rays) -----------------------------------------------------------------
-// rm_trace_rays (the header has the definition): the caller's rays against ONE object table.  TraceCall stands beside GBufferCall;
-// its checks run in check_gbuffer's order, every one but the last ahead of the first HIP call: numRays (negative; zero is RM_OK;
-// every int fits one grid of 256-lane workgroups), the scene pointers, the mode bits, the layers and the 2-D mode a ray is not
-// defined through, the table's limits and types, the arrays (null, alignment of the float4 accesses), then whether they are
-// device memory.
-// Staging is a one-frame batch's: one slot of the batch ring, fill_frames with a zeroed camera, no lights and no resources — the
-// evaluation records, the cull ball and box with cullLip and cullOneOk, bulbPlain — upload_frames with the default launch fields
-// (and the sponge prologue when the table holds one).  rayPlane and cam are staged (zeros) and never read.  The occlusion mode
+// rm_trace_rays (the header has the definition): the caller's rays against ONE object table.  Its checks run in check_gbuffer's
+// order, every one but the last ahead of the first HIP call: numRays (negative; zero is RM_OK; every int fits one grid of
+// 256-lane workgroups), the scene pointers, the mode bits, the layers and the 2-D mode a ray is not defined through, the
+// table's limits and types, the arrays (null, alignment of the float4 accesses), then whether they are device memory.
+// Staging is stage_blocks of one block, filled with a zeroed camera, no lights and no resources — the evaluation records, the
+// cull ball and box with cullLip and cullOneOk, bulbPlain.  rayPlane and cam are staged (zeros) and never read.  The occlusion mode
 // stages two fields of its own: s.enableSoftShadow = 1, so that march<…, SHADOW> tracks the penumbra factor whatever the caller's
 // settings say, and cullR2Soft = 0.  scene_cull_ball derives that larger ball for shadow rays that start on a surface, inside the
 // cull ball, where t <= ρ + R; a caller's ray may start anywhere, so with it a far origin would settle the factor too early.
@@ -1077,21 +1069,9 @@ int check_trace(const TraceCall &c) {
     set_error("RM_TRACE_NO_NORMAL is a flag on RM_TRACE_CLOSEST: occlusion stores no normal anyway");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
-    set_error("rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
-    return RM_ERR_UNSUPPORTED;
-  }
-  if (c.g->isTwoD) { set_error("the 2-D mode (isTwoD) marches no ray"); return RM_ERR_UNSUPPORTED; }
-  if (c.numObjects > RM_MAX_OBJECTS) { set_error("scene exceeds RM_MAX_OBJECTS"); return RM_ERR_CAPACITY; }
-  if (c.s->maxSteps < 0 || c.s->fractalIters < 0 || c.s->mengerLevels < 0) {
-    set_error("negative loop bound in RmSettings");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  for (int i = 0; i < c.numObjects; i++)
-    if (c.objs[i].type < 0 || c.objs[i].type >= RM_CUSTOM) {
-      set_error("object " + std::to_string(i) + ": CUSTOM / unknown type (the reference's sdCUSTOM returns an unset value)");
-      return RM_ERR_UNSUPPORTED;
-    }
+  int st = refuse_layers(c.s, "rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
+  if ((st = check_object_table(c.objs, c.numObjects, c.s)) != RM_OK) return st;
   if (!c.d_rays || !c.d_hits) { set_error("null d_rays or d_hits"); return RM_ERR_INVALID_ARGUMENT; }
   if (((uintptr_t)c.d_rays | (uintptr_t)c.d_hits) & 15u) { set_error("d_rays and d_hits must be 16-byte aligned"); return RM_ERR_INVALID_ARGUMENT; }
   return require_device_pointers({{"d_rays", c.d_rays}, {"d_hits", c.d_hits}});
@@ -1100,24 +1080,18 @@ int launch_trace(const TraceCall &c) {
   int st = check_trace(c);
   if (st != RM_OK || c.numRays == 0) return st;
   const bool occlusion = (c.mode & RM_TRACE_OCCLUSION) != 0;
-  // the march class of the call, as launch_gbuffer's
-  const bool bulb = c.numObjects == 1 && c.objs[0].type == RM_MANDELBULB;
-  const int bulbClass = bulb ? (bulb_plain(c.objs, c.numObjects, c.g) ? kBulbPlain : kBulbGeneral) : 0;
+  const int bulbClass = table_bulb_class(c.objs, c.numObjects, bulb_plain(c.objs, c.numObjects, c.g) != 0);
   RmSettings s = *c.s;
   if (occlusion) s.enableSoftShadow = 1;
   const RmCamera noCam{};
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
-  if ((st = acquire_slot(ds->batches, 1, &sf.slot)) != RM_OK) return st;
-  fill_frames(sf.slot->host, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, &s, kNoResources);
-  if (occlusion) sf.slot->host->cullR2Soft = 0.0f;
-  if ((st = upload_frames(*sf.slot, 1, LaunchFields{}, c.stream)) != RM_OK) return st;
-  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, &s, kNoResources);
+        if (occlusion) h->cullR2Soft = 0.0f;
+      })) != RM_OK) return st;
   if ((st = launch_trace_kernel(sf.slot->dev, bulbClass, occlusion, (c.mode & RM_TRACE_NO_NORMAL) != 0, c.d_rays, c.numRays, c.d_hits,
                                 c.stream)) != RM_OK) return st;
-  return finish_frames(*ds, sf, 12, c.stream);
+  return finish_frames(sf, 12);
 }
 
 // ---- rays from memory: the full colour (rm_shade_rays) ----------------------------------------------------------------------------
@@ -1127,12 +1101,11 @@ int launch_trace(const TraceCall &c) {
 // validate_scene checks of a frame — the limits, the loop bounds, the samplers a feature, an object or a light reads, the types,
 // with rm_render_res's statuses and texts — the arrays (null, alignment of the float4 accesses), and whether they, and the
 // resources' pixels, are device memory.
-// Staging is a one-frame batch's: one slot of the batch ring, fill_frames with the caller's lights and resources and a camera that
-// is zeros but for initialFar = far — the one far every device function reads, wave-uniform (a per-ray far would change which lane
-// of the shadow pool ends a pooled ray where) — upload_frames with the default launch fields (and the sponge prologue when the table
-// holds one).  rayPlane and the rest of cam are staged and never read.  The class is the frame's (classify_frame, bulb_class with
-// the plain form where bulb_plain finds it).  Then ONE launch of shade_rays_kernel (rm_shade.hip), path 13: no wavefront
-// pipeline, no light split, no tuner, tile-order or workspace state is read or changed.
+// Staging is stage_blocks of one block, filled with the caller's lights and resources and a camera that is zeros but for
+// initialFar = far — the one far every device function reads, wave-uniform (a per-ray far would change which lane of the shadow
+// pool ends a pooled ray where).  rayPlane and the rest of cam are staged and never read.  The class is the frame's
+// (classify_frame, bulb_class with the plain form where bulb_plain finds it).  Then ONE launch of shade_rays_kernel
+// (rm_shade.hip), path 13: no wavefront pipeline, no light split, no tuner, tile-order or workspace state is read or changed.
 struct ShadeCall {
   const RmRay *d_rays; int numRays; float far;
   const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
@@ -1147,18 +1120,15 @@ int check_shade(const ShadeCall &c, const RmCamera &cam) {
     return RM_ERR_INVALID_ARGUMENT;
   }
   if (!(c.far >= 0.0f) || c.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)) {
-    set_error("rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
-    return RM_ERR_UNSUPPORTED;
-  }
-  if (c.g->isTwoD) { set_error("the 2-D mode (isTwoD) marches no ray"); return RM_ERR_UNSUPPORTED; }
-  if (int st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) return st;
+  int st = refuse_layers(c.s, "rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
+  if ((st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) != RM_OK) return st;
   if (!c.d_rays || !c.d_rgba) { set_error("null d_rays or d_rgba"); return RM_ERR_INVALID_ARGUMENT; }
   if (((uintptr_t)c.d_rays | (uintptr_t)c.d_rgba | (uintptr_t)c.d_bright) & 15u) {
     set_error("d_rays, d_rgba and d_bright must be 16-byte aligned");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  if (int st = require_device_pointers({{"d_rays", c.d_rays}})) return st;
+  if ((st = require_device_pointers({{"d_rays", c.d_rays}})) != RM_OK) return st;
   return check_device_pointers(c.res, c.d_rgba, c.d_bright);
 }
 int launch_shade(const ShadeCall &c) {
@@ -1168,33 +1138,27 @@ int launch_shade(const ShadeCall &c) {
   if (st != RM_OK || c.numRays == 0) return st;
   const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
   const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
-  DeviceState *ds;
-  if ((st = current_device_state(&ds)) != RM_OK) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
   StagedFrames sf(c.stream);
-  if ((st = acquire_slot(ds->batches, 1, &sf.slot)) != RM_OK) return st;
-  fill_frames(sf.slot->host, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
-  if ((st = upload_frames(*sf.slot, 1, LaunchFields{}, c.stream)) != RM_OK) return st;
-  if ((st = sf.timer.stamp()) != RM_OK) return st;
+  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+      })) != RM_OK) return st;
   if ((st = launch_shade_kernel(sf.slot->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba,
                                 c.d_bright, c.stream)) != RM_OK) return st;
-  return finish_frames(*ds, sf, 13, c.stream);
+  return finish_frames(sf, 13);
 }
 
-// The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights), then launch(the
-// device's block) behind it.
+// The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
+// single frames, then launch(the device's block) behind it.
 template <class Launch>
 int probe_scene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, hipStream_t stream, Launch launch) {
-  DeviceState *ds;
-  if (int st = current_device_state(&ds)) return st;
-  std::lock_guard<std::mutex> lock(ds->mu);
-  Slot *slot;
-  if (int st = acquire_slot(ds->frames, 1, &slot)) return st;
+  StagedFrames sf(stream);
+  sf.timer.on = false;  // a probe is no timed launch: only the slot's event follows it
   const RmCamera cam{};
-  fill_frames(slot->host, 1, &cam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
-  if (int st = upload_frames(*slot, 1, LaunchFields{}, stream)) return st;
-  const int st = launch(slot->dev);
-  HIP_OK(hipEventRecord(slot->done, stream));
+  if (int st = stage_blocks(&sf, &DeviceState::frames, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, &cam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
+      })) return st;
+  const int st = launch(sf.slot->dev);
+  HIP_OK(hipEventRecord(sf.slot->done, stream));
   return st;
 }
 }  // namespace
@@ -1277,8 +1241,8 @@ int rm_render_animated(const RmCamera *cams, const RmGlobals *globals, int numGl
 
 int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlobals, int numFrames, const RmObject *objs, int numObjects,
                       const RmSettings *s, int W, int H, float *d_normalDepth, int32_t *d_objectId, float *d_position, void *stream) {
-  return launch_gbuffer(GBufferCall{cams, globals, numGlobals, numFrames, objs, numObjects, s, W, H, d_normalDepth, d_objectId, d_position,
-                                    static_cast<hipStream_t>(stream)});
+  return launch_gbuffer(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, nullptr, 0, s, kNoResources, W, H, nullptr, nullptr,
+                                  static_cast<hipStream_t>(stream)}, d_normalDepth, d_objectId, d_position);
 }
 
 int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,

@@ -66,14 +66,7 @@ __global__ __launch_bounds__(256, shade_waves(BULB, ENV, TEX, SEC)) void shade_r
     const SceneBlock *__restrict__ sb, const float4 *__restrict__ rays, int numRays, float4 *__restrict__ out,
     float4 *__restrict__ bright) {
   __shared__ RmObject s_objs[BULB ? 1 : RM_MAX_OBJECTS];
-  {
-    const int nd = sb->numObjects * (int)(sizeof(RmObject) / 4);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sb->objs);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(s_objs);
-    for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-  }
-  if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
-  __syncthreads();
+  stageWorkgroup<ENV, TEX>(sb, s_objs);
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned)numRays) return;
   const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];

@@ -21,18 +21,10 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
     const SceneBlock *__restrict__ sb, int W, int H, int ss, float4 *__restrict__ out, float4 *__restrict__ bright) {
   sb += blockIdx.z;  // wave-uniform: the frame's own scene block
   __shared__ RmObject s_objs[BULB ? 1 : RM_MAX_OBJECTS];
-  {
-    const int nd = sb->numObjects * (int)(sizeof(RmObject) / 4);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(sb->objs);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(s_objs);
-    for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
-  }
-  if (TEX || (ENV && (sb->s.features & (RM_FEAT_NIGHTSKY_BACKGROUND | RM_FEAT_SEA)))) initUnormTable();
-  __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  stageWorkgroup<ENV, TEX>(sb, s_objs);
   const int sW = W * ss, sH = H * ss;  // the sample frame
-  const int x = ((int)blockIdx.x * (int)(blockDim.x >> 6) + wave) * 8 + (lane & 7);
-  const int y = (int)blockIdx.y * 8 + (lane >> 3);
+  int x, y;
+  tilePixel8x8(x, y);
   // Edge lanes leave before the cross-lane reads below, which is safe because of this invariant: ss divides 8 and tile origins are
   // multiples of 8, so an output pixel's ss × ss lanes lie in one wave, and sW, sH are multiples of ss, so those lanes are either
   // all inside the sample frame or all past its edge.  Every lane that stays reads only lanes of its own block, all of which stay.
