@@ -794,6 +794,14 @@ int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, c
 int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, int bulbClass,
                              int count, int trap, int skip, int track, int one, const float *d_pts, const float *d_ub,
                              float *d_out, int n, void *stream);
+/* The four Perlin samples behind bumpNormal(n, p, 10, 2) at n world-space points, from the device function the production
+ * kernels call for them (tests only).  d_pts[3n]: the positions; d_out[4n] = (nv, g0, g1, g2) with ps = 10 · p, nv = pnoise(ps)
+ * and gk = pnoise(ps + 0.1 · e_k) − nv: the values before bumpNormal's normalize(n + 2 · g).  The function shares the noise
+ * lattice of the base sample with an offset sample when every lane of the wave stays in its cell on that axis, and the result
+ * is the same bits either way.  Point i runs on lane i % 64 of wave i / 64 (that choice sees exactly those 64 points; the last
+ * wave may be partial).  n == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT: n < 0, a null pointer or one that is not
+ * device memory. */
+int rm_probe_bump(const float *d_pts, float *d_out, int n, void *stream);
 
 /* ---- host side kept from the reference: scenefile loader, camera, Settings -------------------- */
 /* Settings surface — src/settings.h:19-55 (render-relevant fields only). */

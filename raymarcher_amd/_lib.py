@@ -107,6 +107,7 @@ SIGNATURES = {
     "rm_probe_sdscene_variant": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p]),
+    "rm_probe_bump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rm_host_settings_default": (None, [_P(abi.RmHostSettings)]),
     "rm_camera_build": (C.c_int, [_P(abi.RmCameraData), C.c_int, C.c_int, C.c_float, C.c_float, _P(C.c_float),
                                   _P(C.c_float), _P(abi.RmCamera)]),

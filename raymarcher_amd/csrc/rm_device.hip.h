@@ -771,6 +771,80 @@ RM_DEV V3 bumpNormal(V3 normal, V3 pos) {  // frag:1679-1691, BUMP_SCALE 10, BUM
   return normalize(madd(v3(g[0], g[1], g[2]), 2.0f, normal));
 }
 
+// The lattice-sharing form of bumpNormal's four samples.  Everything pnoise computes before its dot products — the cell, the 14
+// hashes, the eight gradients with their normalisation — depends on floor(p) alone, and the three offset samples move one
+// coordinate by a tenth of a cell: they almost always lie in the base sample's cell and would rebuild the same eight gradients.
+// pgradn is pcorner's gradient (pgrad, taylorInvSqrt, scale) without its dot; pcell is the rest of pnoise from the gradients on:
+// the eight dots in pcorner's operand order, the seven mixes in pnoise's nesting, the 2.2f.  Same inputs and same operations in
+// the same order give the same bits, so pcell of the base cell's gradients with a sample's own fractions is pnoise of that sample
+// whenever the sample lies in the base cell.
+RM_DEV V3 pgradn(float ixyz) {
+  float gx, gy, gz;
+  pgrad(ixyz, gx, gy, gz);
+  V3 g = v3(gx, gy, gz);
+  return scale(g, taylorInvSqrt(dot(g, g)));
+}
+RM_DEV float pcell(const V3 (&g)[8], float f0x, float f0y, float f0z, float fx, float fy, float fz) {
+  float f1x = f0x - 1.0f, f1y = f0y - 1.0f, f1z = f0z - 1.0f;
+  float n000 = dot(g[0], v3(f0x, f0y, f0z)), n100 = dot(g[1], v3(f1x, f0y, f0z));
+  float n010 = dot(g[2], v3(f0x, f1y, f0z)), n110 = dot(g[3], v3(f1x, f1y, f0z));
+  float n001 = dot(g[4], v3(f0x, f0y, f1z)), n101 = dot(g[5], v3(f1x, f0y, f1z));
+  float n011 = dot(g[6], v3(f0x, f1y, f1z)), n111 = dot(g[7], v3(f1x, f1y, f1z));
+  float nzx = mix_(n000, n001, fz), nzy = mix_(n100, n101, fz), nzz = mix_(n010, n011, fz), nzw = mix_(n110, n111, fz);
+  float nyx = mix_(nzx, nzz, fy), nyy = mix_(nzy, nzw, fy);
+  return 2.2f * mix_(nyx, nyy, fx);
+}
+// nv = pnoise(ps) and g[k] = pnoise(ps + 0.1·e_k) − nv for ps = 10·pos, bit for bit what bumpNormal forms.  Sample k is taken
+// from the base cell's gradients when floor(ps_k + 0.1f) == floor(ps_k) — the float32 sum bumpNormal forms, the unwrapped floors —
+// on every calling lane of the wave (one __ballot per sample) and ps is finite there: then i0 and i1 of the sample are the base
+// sample's, so are its hashes and gradients, and only the fraction of coordinate k and its fade differ.  (The other two
+// coordinates reach pnoise as ps + 0.0f, which differs from ps only for −0, and neither mod_(floor_(·), 256) nor fract_ tells
+// −0 from +0.)  A non-finite ps is never taken that way: floor(inf + 0.1f) == floor(inf) says nothing about a cell.  A sample that
+// any lane of the wave cannot take so goes through pnoise itself for all of them, behind a scalar branch; the bits are the same
+// either way, so which lanes share a wave changes the cost and never the value.
+RM_DEV void bumpGradient(V3 pos, float &nv, float (&g)[3]) {
+  V3 ps = scale(pos, 10.0f);
+  float flx = floor_(ps.x), fly = floor_(ps.y), flz = floor_(ps.z);
+  float f0x = fract_(ps.x), f0y = fract_(ps.y), f0z = fract_(ps.z);
+  V3 G[8];
+  {
+    float i1x = mod_(flx + 1.0f, 256.0f), i1y = mod_(fly + 1.0f, 256.0f), i1z = mod_(flz + 1.0f, 256.0f);
+    float i0x = mod_(flx, 256.0f), i0y = mod_(fly, 256.0f), i0z = mod_(flz, 256.0f);
+    float px0 = permute(i0x), px1 = permute(i1x);
+    float ixy00 = permute(px0 + i0y), ixy10 = permute(px1 + i0y);
+    float ixy01 = permute(px0 + i1y), ixy11 = permute(px1 + i1y);
+    G[0] = pgradn(permute(ixy00 + i0z)); G[1] = pgradn(permute(ixy10 + i0z));
+    G[2] = pgradn(permute(ixy01 + i0z)); G[3] = pgradn(permute(ixy11 + i0z));
+    G[4] = pgradn(permute(ixy00 + i1z)); G[5] = pgradn(permute(ixy10 + i1z));
+    G[6] = pgradn(permute(ixy01 + i1z)); G[7] = pgradn(permute(ixy11 + i1z));
+  }
+  float fx = fade(f0x), fy = fade(f0y), fz = fade(f0z);
+  nv = pcell(G, f0x, f0y, f0z, fx, fy, fz);
+  const bool finite = (fabs_(ps.x) + fabs_(ps.y)) + fabs_(ps.z) < __builtin_inff();  // false for NaN; an overflowing sum only falls back
+  const float qx = ps.x + 0.1f, qy = ps.y + 0.1f, qz = ps.z + 0.1f;
+  uint32_t full = 0u;  // wave-uniform: the samples that go through pnoise
+  if (__ballot(!(finite && floor_(qx) == flx)) == 0ull) { float f = fract_(qx); g[0] = pcell(G, f, f0y, f0z, fade(f), fy, fz) - nv; }
+  else full |= 1u;
+  if (__ballot(!(finite && floor_(qy) == fly)) == 0ull) { float f = fract_(qy); g[1] = pcell(G, f0x, f, f0z, fx, fade(f), fz) - nv; }
+  else full |= 2u;
+  if (__ballot(!(finite && floor_(qz) == flz)) == 0ull) { float f = fract_(qz); g[2] = pcell(G, f0x, f0y, f, fx, fy, fade(f)) - nv; }
+  else full |= 4u;
+#pragma unroll 1
+  for (int k = 0; k < 3 && full != 0u; k++) {
+    if (!((full >> k) & 1u)) continue;
+    float v = pnoise(v3(ps.x + ((k == 0) ? 0.1f : 0.0f), ps.y + ((k == 1) ? 0.1f : 0.0f),
+                        ps.z + ((k == 2) ? 0.1f : 0.0f))) - nv;
+    g[0] = (k == 0) ? v : g[0];
+    g[1] = (k == 1) ? v : g[1];
+    g[2] = (k == 2) ? v : g[2];
+  }
+}
+RM_DEV V3 bumpNormalShared(V3 normal, V3 pos) {  // bumpNormal with bumpGradient's samples: the same bits
+  float nv, g[3];
+  bumpGradient(pos, nv, g);
+  return normalize(madd(v3(g[0], g[1], g[2]), 2.0f, normal));
+}
+
 // ---- shading --------------------------------------------------------------------------------------------
 // frag:1729-1740
 // ubPos: an upper bound of sdScene at pos (+inf = none); a tap lies h·|nor| from it.
@@ -1225,7 +1299,10 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
 // rays all start at `so` with depth 0, so their first evaluation sdScene(madd(L, 0, so)) = sdScene(so) is one value — unless
 // a component of `so` is −0, whose sign madd then takes from L (such a pixel, and any frame with a non-finite light direction,
 // marches from the start).
-template <int BULB, int COUNT>
+// SHARE: the bump's four noise samples from one lattice (bumpNormalShared) instead of four pnoise calls: the same bits; chosen per
+// kernel by the compiler's register report (shadePixel's SHARE: the kernels that hold several samples' or frames' state live
+// across this function spill more with the eight gradients and keep bumpNormal).
+template <int BULB, int COUNT, bool SHARE>
 RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, const MarchRes &res, Hit &info,
                               float maxT, V3 bg, Counters &cnt) {
   const bool surf = res.obj != -1;
@@ -1237,7 +1314,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
     if (COUNT) cnt.shades++;
     p = madd(rd, res.d, ro);
     N = getNormal<BULB, COUNT>(sb, p, cnt);
-    if (sb->s.features & RM_FEAT_PERLIN_BUMP) N = bumpNormal(N, p);
+    if (sb->s.features & RM_FEAT_PERLIN_BUMP) N = SHARE ? bumpNormalShared(N, p) : bumpNormal(N, p);
     if (sb->s.enableAmbientOcclusion) ao = calcAO<BULB, COUNT>(sb, p, N, cnt);
     so = shadowOrigin(p, N);
     bool shared = f2u(so.x) != 0x80000000u && f2u(so.y) != 0x80000000u && f2u(so.z) != 0x80000000u;
@@ -1289,7 +1366,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
 // POOL (bulb kernels without procedural layers or textures, not counting the reference's work; the primary call of shadePixel,
 // which every lane of the wave that renders a pixel reaches): renderPooled takes the frames whose shadow rays the pool may
 // schedule.  The secondary rays' render() calls are divergent and keep getPhong's queue.
-template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false>
+template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false, bool SHARE = false>
 RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, Hit &info, float side, float maxT,
                         V3 bg, Counters &cnt, LightSplit split = LightSplit{-1, nullptr, 0}) {
   RenderOut out;
@@ -1308,7 +1385,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
       q[0] = __int_as_float(res.obj); q[1] = res.d; q[2] = res.trap.x; q[3] = res.trap.y; q[4] = res.trap.z; q[5] = res.trap.w;
     }
   }
-  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
+  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT, SHARE>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
   if (res.obj == -1) {
     out.col = (TEX && sb->s.enableSkyBox) ? sampleCube(sb->skybox, rd) : bg;  // frag:2325-2327
     out.isEnv = 1;
@@ -1424,7 +1501,8 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // sea normal (frag:2444-2456), unread without the layers.  The ray part reads nothing else of the camera and nothing of the pixel.
 // The pixel form is written so that its instantiations compile to what they did before the ray form existed: the code objects of
 // the render kernels are byte-identical.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false>
+// SHARE = false keeps bumpNormal in the pooled surface phase (renderPooled): render_adaptive, render_acc and render_anim kernels.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false, bool SHARE = true>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0},
                        const V3 *rayO = nullptr, const V3 *rayD = nullptr) {
@@ -1448,7 +1526,7 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
 
   Hit info;
   constexpr bool POOL = BULB && !ENV && !TEX && COUNT != 1 && SPLIT == 0;  // the shadow pool (renderPooled)
-  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
+  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL, SHARE>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
   EnvOut e;
   e.terrainHit = false; e.cloudHit = false; e.seaHit = false;
   if (env) e = envLayers(feat, sb->noise, iTime, W, ro, rd, ri.d, bg, cnt);  // frag:2444-2456

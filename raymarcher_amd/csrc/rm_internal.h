@@ -53,6 +53,7 @@ int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, i
 // 2^32-input checker of the cheap exact forms (rm_debug_check_math; `d_out5` zeroed by the caller, default stream).
 int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, float *d_out, int n, hipStream_t stream);
 int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream);
+int launch_probe_bump(const float *d_pts, float *d_out, int n, hipStream_t stream);  // rm_probe_bump's kernel: bumpGradient
 void launch_check_math(unsigned long long *d_out5);
 // The kernels of rm_kernels.hip, as the launcher calls them (the structs are rm_launch.h's, FrameClass rm_frame.h's).  Scene prep:
 // the sponge uniforms of the n staged blocks.  Tile order: the ordering launches of a plan, ahead of the render.  Wavefront: the

@@ -1491,6 +1491,13 @@ int rm_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, 
   return launch_probe_math(fn, d_x, d_y, d_z, d_out, n, static_cast<hipStream_t>(stream));
 }
 
+int rm_probe_bump(const float *d_pts, float *d_out, int n, void *stream) {
+  if (!d_pts || !d_out || n < 0) { set_error("bad probe arguments"); return RM_ERR_INVALID_ARGUMENT; }
+  if (int st = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st;
+  if (n == 0) return RM_OK;
+  return launch_probe_bump(d_pts, d_out, n, static_cast<hipStream_t>(stream));
+}
+
 int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float *d_pts,
                      float *d_out, int n, void *stream) {
   RmCamera cam{};

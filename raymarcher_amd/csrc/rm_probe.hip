@@ -1,6 +1,6 @@
 // rm_probe.hip — the test-only device probes: the scene evaluator's production instantiations (rm_probe_sdscene_variant), the
-// plain evaluator (rm_probe_sdscene), the rm_math built-ins (rm_probe_math) and the 2^32-input checker of the cheap exact forms
-// (rm_debug_check_math).
+// plain evaluator (rm_probe_sdscene), the rm_math built-ins (rm_probe_math), the bump gradient's four noise samples (rm_probe_bump)
+// and the 2^32-input checker of the cheap exact forms (rm_debug_check_math).
 //
 // Kept out of rm_kernels.hip so that the production translation unit's compile time and code stay as they are.  The variant kernels
 // below call the very template functions the render kernels call (sdSceneImpl, sdSceneOne in rm_device.hip.h) with the same
@@ -54,6 +54,20 @@ __global__ void probe_sdscene_kernel(const SceneBlock *__restrict__ sb, const fl
   out[4 * i + 1] = (float)m.idx;
   out[4 * i + 2] = m.trap.y;
   out[4 * i + 3] = m.trap.z;
+}
+
+// bumpGradient, the function behind bumpNormalShared, on the lanes the caller chose: point i on lane i % 64 of wave i / 64 (one
+// 64-lane workgroup per wave, lanes past n leave before the call), so its per-sample ballots see exactly those 64 points.
+__global__ void __launch_bounds__(64) probe_bump_kernel(const float *pts, float *out, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  float nv, g[3];
+  bumpGradient(v3(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]), nv, g);
+  float *o = out + 4 * (size_t)i;
+  o[0] = nv;
+  o[1] = g[0];
+  o[2] = g[1];
+  o[3] = g[2];
 }
 
 namespace {
@@ -149,6 +163,11 @@ int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d
 }
 int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream) {
   hipLaunchKernelGGL(probe_sdscene_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const SceneBlock *>(sb), d_pts, d_out, n);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+int launch_probe_bump(const float *d_pts, float *d_out, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_bump_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_pts, d_out, n);
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

@@ -771,6 +771,17 @@ class Renderer:
                                      C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()), n, self._stream()))
         return out
 
+    def probe_bump(self, pts, out=None):
+        """The four noise samples of the bump gradient at the (n, 3) points `pts` (include/raymarcher_amd.h, rm_probe_bump; point i
+        runs on lane i % 64 of wave i / 64).  Returns (n, 4): nv, g0, g1, g2."""
+        t = self.torch
+        n = pts.shape[0]
+        if tuple(pts.shape) != (n, 3) or pts.dtype != t.float32 or not pts.is_contiguous() or pts.device != self.device:
+            raise ValueError(f"pts must be a contiguous float32 tensor of shape (n, 3) on {self.device}")
+        out = self._out(out, (n, 4), t.float32)
+        check(lib().rm_probe_bump(C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()), n, self._stream()))
+        return out
+
     def probe_sdscene_variant(self, tables, settings, pts, bulb_class=0, count=0, trap=1, skip=0, track=0, one=-1, ub=None,
                               out=None):
         """One production instantiation of the scene evaluator at the (n, 3) points `pts` (include/raymarcher_amd.h,
