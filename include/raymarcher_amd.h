@@ -504,6 +504,67 @@ int rm_camera_rays(const RmCamera *cam, int W, int H, const int32_t *xy, int n, 
 int rm_shade_rays(const RmRay *d_rays, int numRays, float far, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
                   const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */, float *d_rgba,
                   float *d_bright /* may be NULL */, void *stream);
+/*
+ * rm_shade_rays_layers — rm_shade_rays THROUGH the procedural layers: terrain, sea and clouds (RM_FEAT_TERRAIN, RM_FEAT_SEA,
+ * RM_FEAT_CLOUD), which rm_shade_rays refuses.  For landscape panoramas and environment-probe faces: terrain below, clouds and sky
+ * above, the sea to the horizon.  The arguments are rm_shade_rays' with imageWidth behind `far`.
+ * imageWidth: the width in pixels of the image the rays belong to — the frame's W for a camera's rays, the panorama's W for a
+ * panorama.  It is the one quantity of a frame a ray does not carry: seaRender divides the epsilon of the sea normal by
+ * iResolution.x (frag:2284-2310), and nothing else reads it.  It must be >= 1 in every call, whatever the feature mask.
+ * Definition, bit for bit: rm_shade_rays' with the layer lines of main no longer left out.  Behind render(ro, rd, OUTSIDE, far, bg)
+ * come sea, then terrain, then cloud (frag:2444-2456): the sea bounded by the render's distance, the terrain by the sea's, the cloud
+ * by the terrain's.  Precedence (frag:2459-2475): cloud over terrain over sea over the object hit; a layer hit returns the layer's
+ * colour with alpha 1 and BrightColor of it, and fires no secondary rays.  The same three layers apply behind every reflection
+ * bounce (frag:2506-2518: terrain and cloud end the bounce loop, the sea does not) and behind the refraction exit (frag:2555-2567).
+ * With RM_FEAT_CLOUD the call's `far` is validated but NOT read: the shader sets far = 2000 (frag:2422-2426), and the equality with
+ * rm_render is the anchor.  A ray that copies rm_camera_rays' origin and dir, with imageWidth = W and far = cam->initialFar, gives
+ * rm_render_res's pixel in every bit, colour and bright, for every feature mask.  With no layer bit in s->features the output is
+ * rm_shade_rays' in every bit (the same kernels run).
+ * Invalid rays, dir used as given, ONE far per call, RmRay.tMax not read: as rm_shade_rays has them.
+ * numRays == 0: RM_OK.  Otherwise rm_shade_rays' checks in its order, all but the last before any HIP call, with two differences: no
+ * refusal of the layers, and imageWidth < 1 is RM_ERR_INVALID_ARGUMENT right after `far`.  The scene checks are rm_render_res's, so
+ * RM_FEAT_SEA without the noise sampler is RM_ERR_UNSUPPORTED with its text.  g->isTwoD stays RM_ERR_UNSUPPORTED.
+ * Schedule: ONE launch, one lane per ray (rm_debug_last_path() = 14, rm_debug_last_split() = 0): with a layer bit the layers' shade
+ * kernel of the scene's class (textured or not, secondary rays or not), without one rm_shade_rays' kernel.  One slot of the batch
+ * ring of scene blocks; no tuner, tile-order or workspace state is read or changed.  With rm_set_timing(1) one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageWidth, const RmObject *objs, int numObjects,
+                         const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s,
+                         const RmResources *res /* may be NULL */, float *d_rgba, float *d_bright /* may be NULL */, void *stream);
+/*
+ * rm_trace_rays_layers — rm_trace_rays THROUGH terrain and sea: the closest VISIBLE SURFACE along each ray, by the rules main
+ * applies to its own rays.  For keeping a fly-through camera above the terrain, and for picking on a landscape.  The arguments are
+ * rm_trace_rays' with imageWidth (as above, >= 1 in every call) behind numRays.
+ * Definition, bit for bit:
+ *   res = raymarch(origin, dir, tMax, OUTSIDE), rm_trace_rays' closest hit; d0 = hit ? res.d : tMax
+ *   RM_FEAT_SEA: the geometric part of seaRender(origin, dir, maxT = d0) (frag:2284-2291, 2252-2282): seaHit, t_s, p_s;
+ *     d1 = seaHit ? t_s : d0
+ *   RM_FEAT_TERRAIN: the geometric part of terrainRender(origin, dir, maxT = d1) (frag:2128-2135, 2060-2090; tmin = 15):
+ *     terrainHit, t_t
+ * Terrain hit: objectId = RM_HIT_TERRAIN (−4), t = t_t, position = dir·t_t + origin in terrainRender's fused form, normal =
+ * terrainNormal(position.x, position.z) (frag:2106-2111).  That is the SURFACE's own normal, not the fbm-perturbed `nor` the
+ * terrain's lighting builds from it (frag:2141): a collision response needs the surface.
+ * Sea hit and no terrain hit: objectId = RM_HIT_SEA (−3), t = t_s, position = p_s as seaMapHeight leaves it, normal =
+ * getSeaNormal(p_s, (dot(d, d)·0.1) / imageWidth) with d = p_s − origin (frag:2243-2250, 2296): the shader's normal.
+ * Neither: the object hit, or the miss, exactly as rm_trace_rays stores it, bump included.
+ * RM_FEAT_CLOUD is accepted and ignored: a volume has no closest hit.  RM_TRACE_NO_NORMAL works as before: objectId and t only,
+ * zeros elsewhere, no normal taps.  RM_TRACE_OCCLUSION together with a layer bit is RM_ERR_UNSUPPORTED: the objects' shadow march
+ * does not see the layers; without a layer bit it is rm_trace_rays' occlusion.  With no layer bit every mode gives rm_trace_rays'
+ * output in every bit (the same kernels run).  Per-ray tMax and the invalid-ray rule stay; the result of a ray does not depend on
+ * which other rays share its call.  No resources are read: the sea's geometry does not touch the noise texture.
+ * numRays == 0: RM_OK.  Otherwise rm_trace_rays' checks in its order, all but the last before any HIP call, with two differences:
+ * imageWidth < 1 is RM_ERR_INVALID_ARGUMENT right after the mode bits, and in place of the refusal of the layers stands the refusal
+ * of RM_TRACE_OCCLUSION with one.
+ * Schedule: ONE launch, one lane per ray (rm_debug_last_path() = 15, rm_debug_last_split() = 0): with RM_FEAT_SEA or
+ * RM_FEAT_TERRAIN the layers' trace kernel of the table's march class, otherwise rm_trace_rays' kernel.  One slot of the batch ring
+ * of scene blocks; no tuner, tile-order or workspace state is read or changed.  With rm_set_timing(1) one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_HIT_SEA (-3)
+#define RM_HIT_TERRAIN (-4)
+int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
+                         const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream);
 
 /*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
@@ -620,8 +681,8 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * kernel, or all kernels of the wavefront pipeline), stage 0 = the tile-ordering launches that preceded it in the launches that had
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
- * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer, rm_trace_rays or rm_shade_rays,
- * and so does a whole call of rm_render_adaptive.
+ * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer, rm_trace_rays, rm_shade_rays,
+ * rm_shade_rays_layers or rm_trace_rays_layers, and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -651,8 +712,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
- * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays (none of them is a value rm_set_kernel_path
- * takes). */
+ * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
+ * launch of rm_trace_rays_layers (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -51,6 +51,10 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p]),
     "rm_shade_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_float, _P(abi.RmObject), C.c_int, _P(abi.RmLight), C.c_int, _P(abi.RmGlobals),
                                 _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_shade_rays_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, _P(abi.RmObject), C.c_int, _P(abi.RmLight), C.c_int,
+                                       _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_trace_rays_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings),
+                                       C.c_uint, C.c_void_p, C.c_void_p]),
     "rm_camera_rays": (C.c_int, [_P(abi.RmCamera), C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),

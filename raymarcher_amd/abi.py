@@ -121,6 +121,8 @@ class RmRayHit(C.Structure):
 RM_TRACE_CLOSEST, RM_TRACE_NO_NORMAL, RM_TRACE_OCCLUSION = 0, 1, 2  # mode of rm_trace_rays; NO_NORMAL is a flag on CLOSEST
 RM_RAY_INVALID = -2  # RmRayHit.objectId of an invalid ray
 RM_PATH_TRACE_RAYS, RM_PATH_SHADE_RAYS = 12, 13  # rm_debug_last_path() behind a launch of rm_trace_rays / rm_shade_rays
+RM_HIT_SEA, RM_HIT_TERRAIN = -3, -4  # RmRayHit.objectId of rm_trace_rays_layers where the sea / the terrain is the visible surface
+RM_PATH_SHADE_RAYS_LAYERS, RM_PATH_TRACE_RAYS_LAYERS = 14, 15  # … behind rm_shade_rays_layers / rm_trace_rays_layers
 
 
 def default_settings(**over):

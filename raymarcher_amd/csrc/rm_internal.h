@@ -103,6 +103,14 @@ int launch_trace_kernel(const void *sb, int bulbClass, bool occlusion, bool noNo
 // numRays float4 of colour into d_rgba and, when d_bright is not null, of bright values into d_bright.
 int launch_shade_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const void *d_rays, int numRays, float *d_rgba,
                         float *d_bright, hipStream_t stream);
+// The layer kernels (rm_layers.hip, rm_shade_rays_layers and rm_trace_rays_layers; a translation unit of its own for the same
+// reason), for the calls that have a layer bit — a call without one goes to the two launches above.  shade_rays_layers_kernel<tex,
+// sec> (the env class; imageWidth feeds the sea normal's epsilon) and trace_layers_kernel<bulbClass> (closest mode only) over the
+// ONE staged SceneBlock `sb`, one lane per ray.
+int launch_shade_layers_kernel(const void *sb, bool tex, bool sec, const void *d_rays, int numRays, int imageWidth, float *d_rgba,
+                               float *d_bright, hipStream_t stream);
+int launch_trace_layers_kernel(const void *sb, int bulbClass, bool noNormal, const void *d_rays, int numRays, int imageWidth,
+                               void *d_hits, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + grid.z − 1 of d_rgba (grid: their 8×8 tiles), into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

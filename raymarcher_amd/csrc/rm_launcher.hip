@@ -729,6 +729,13 @@ int refuse_layers(const RmSettings *s, const char *text) {
   set_error(text);
   return RM_ERR_UNSUPPORTED;
 }
+// The width of the image the rays belong to (rm_shade_rays_layers, rm_trace_rays_layers): checked in every call, whatever the
+// feature mask, so that the status does not depend on it.
+int check_image_width(int imageWidth) {
+  if (imageWidth >= 1) return RM_OK;
+  set_error("imageWidth must be at least 1: the width in pixels of the image the rays belong to");
+  return RM_ERR_INVALID_ARGUMENT;
+}
 int refuse_two_d(const RmGlobals *g, const char *text) {
   if (!g->isTwoD) return RM_OK;
   set_error(text);
@@ -1051,10 +1058,13 @@ int launch_gbuffer(const FrameCall &c, float *d_normalDepth, int32_t *d_objectId
 // Without it a soft march ends at tMax, as the reference's does.  (The hard bounds — ball, box, the bulb's own ball — argue about
 // points, not origins, and hold for any ray.)
 // Then ONE launch of trace_kernel (rm_trace.hip), path 12: no tuner, tile-order or workspace state is read or changed.
+// rm_trace_rays_layers is the same call with TraceCall.layers set: imageWidth is checked behind the mode bits, the refusal of the
+// layers holds only for the occlusion mode, the launch is trace_layers_kernel (rm_layers.hip) when TERRAIN or SEA is set, path 15.
 struct TraceCall {
   const RmRay *d_rays; int numRays;
   const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s;
   unsigned mode; RmRayHit *d_hits; hipStream_t stream;
+  bool layers = false; int imageWidth = 1;  // rm_trace_rays_layers: the layers are traced, not refused
 };
 int check_trace(const TraceCall &c) {
   if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
@@ -1069,7 +1079,10 @@ int check_trace(const TraceCall &c) {
     set_error("RM_TRACE_NO_NORMAL is a flag on RM_TRACE_CLOSEST: occlusion stores no normal anyway");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  int st = refuse_layers(c.s, "rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  int st = RM_OK;
+  if (!c.layers) st = refuse_layers(c.s, "rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  else if ((st = check_image_width(c.imageWidth)) == RM_OK && (c.mode & RM_TRACE_OCCLUSION))
+    st = refuse_layers(c.s, "RM_TRACE_OCCLUSION is the objects' shadow march: it does not see TERRAIN / CLOUD / SEA");
   if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
   if ((st = check_object_table(c.objs, c.numObjects, c.s)) != RM_OK) return st;
   if (!c.d_rays || !c.d_hits) { set_error("null d_rays or d_hits"); return RM_ERR_INVALID_ARGUMENT; }
@@ -1089,9 +1102,13 @@ int launch_trace(const TraceCall &c) {
         fill_frames(h, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, &s, kNoResources);
         if (occlusion) h->cullR2Soft = 0.0f;
       })) != RM_OK) return st;
-  if ((st = launch_trace_kernel(sf.slot->dev, bulbClass, occlusion, (c.mode & RM_TRACE_NO_NORMAL) != 0, c.d_rays, c.numRays, c.d_hits,
-                                c.stream)) != RM_OK) return st;
-  return finish_frames(sf, 12);
+  // the layers' kernel only where a layer has a surface: without one (CLOUD alone is a volume) rm_trace_rays' own kernels run
+  const bool noNormal = (c.mode & RM_TRACE_NO_NORMAL) != 0;
+  if (c.layers && (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_SEA)))
+    st = launch_trace_layers_kernel(sf.slot->dev, bulbClass, noNormal, c.d_rays, c.numRays, c.imageWidth, c.d_hits, c.stream);
+  else st = launch_trace_kernel(sf.slot->dev, bulbClass, occlusion, noNormal, c.d_rays, c.numRays, c.d_hits, c.stream);
+  if (st != RM_OK) return st;
+  return finish_frames(sf, c.layers ? 15 : 12);
 }
 
 // ---- rays from memory: the full colour (rm_shade_rays) ----------------------------------------------------------------------------
@@ -1106,11 +1123,14 @@ int launch_trace(const TraceCall &c) {
 // pool ends a pooled ray where).  rayPlane and the rest of cam are staged and never read.  The class is the frame's
 // (classify_frame, bulb_class with the plain form where bulb_plain finds it).  Then ONE launch of shade_rays_kernel
 // (rm_shade.hip), path 13: no wavefront pipeline, no light split, no tuner, tile-order or workspace state is read or changed.
+// rm_shade_rays_layers is the same call with ShadeCall.layers set: imageWidth is checked in place of the refusal of the layers, the
+// launch is shade_rays_layers_kernel (rm_layers.hip) when a layer bit is set, path 14.
 struct ShadeCall {
   const RmRay *d_rays; int numRays; float far;
   const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
   const RmGlobals *g; const RmSettings *s; const RmResources &res;
   float *d_rgba, *d_bright; hipStream_t stream;
+  bool layers = false; int imageWidth = 1;  // rm_shade_rays_layers: the layers are shaded, not refused
 };
 int check_shade(const ShadeCall &c, const RmCamera &cam) {
   if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
@@ -1120,7 +1140,9 @@ int check_shade(const ShadeCall &c, const RmCamera &cam) {
     return RM_ERR_INVALID_ARGUMENT;
   }
   if (!(c.far >= 0.0f) || c.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = refuse_layers(c.s, "rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  int st = RM_OK;
+  if (c.layers) st = check_image_width(c.imageWidth);
+  else st = refuse_layers(c.s, "rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
   if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
   if ((st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) != RM_OK) return st;
   if (!c.d_rays || !c.d_rgba) { set_error("null d_rays or d_rgba"); return RM_ERR_INVALID_ARGUMENT; }
@@ -1142,9 +1164,14 @@ int launch_shade(const ShadeCall &c) {
   if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
         fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
       })) != RM_OK) return st;
-  if ((st = launch_shade_kernel(sf.slot->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba,
-                                c.d_bright, c.stream)) != RM_OK) return st;
-  return finish_frames(sf, 13);
+  // the layers' kernel only with a layer bit (then fc.envFeatures is set and bulbClass is 0): without one, rm_shade_rays' twelve classes
+  if (c.layers && (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)))
+    st = launch_shade_layers_kernel(sf.slot->dev, fc.textured, fc.secondary, c.d_rays, c.numRays, c.imageWidth, c.d_rgba, c.d_bright,
+                                    c.stream);
+  else st = launch_shade_kernel(sf.slot->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba, c.d_bright,
+                                c.stream);
+  if (st != RM_OK) return st;
+  return finish_frames(sf, c.layers ? 14 : 13);
 }
 
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
@@ -1254,6 +1281,18 @@ int rm_shade_rays(const RmRay *d_rays, int numRays, float far, const RmObject *o
                   const RmGlobals *g, const RmSettings *s, const RmResources *res, float *d_rgba, float *d_bright, void *stream) {
   return launch_shade(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba, d_bright,
                                 static_cast<hipStream_t>(stream)});
+}
+
+int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageWidth, const RmObject *objs, int numObjects,
+                         const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s, const RmResources *res, float *d_rgba,
+                         float *d_bright, void *stream) {
+  return launch_shade(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba, d_bright,
+                                static_cast<hipStream_t>(stream), true, imageWidth});
+}
+
+int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
+                         const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream) {
+  return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream), true, imageWidth});
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

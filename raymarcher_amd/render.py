@@ -594,6 +594,53 @@ class Renderer:
         out[t.from_numpy(order).to(self.device)] = colour  # the inverse permutation: ray k is pixel order[k]
         return out.view(H, W, 4)
 
+    def shade_rays_layers(self, tables, settings, rays, image_width, far=None, bright=False, out=None, out_bright=None):
+        """rm_shade_rays_layers: shade_rays through terrain, sea and clouds (RM_FEAT_TERRAIN / SEA / CLOUD in `settings`), which
+        shade_rays refuses → float32 (n, 4), or the pair (colour, bright).  image_width: the width in pixels of the image the rays
+        belong to (a frame's W, a panorama's W; at least 1) — the sea normal's epsilon is divided by it and nothing else reads it.
+        With RM_FEAT_CLOUD the march limit is the shader's 2000 and `far` is not read.  camera_rays of a frame with image_width = W
+        give render()'s pixels bit for bit; without a layer bit the result is shade_rays'.  The definition is in
+        include/raymarcher_amd.h."""
+        t = self.torch
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        out = self._out(out, (n, 4), t.float32)
+        bright = bright or out_bright is not None
+        br = self._out(out_bright, (n, 4), t.float32, "out_bright") if bright else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_shade_rays_layers(C.c_void_p(rays.data_ptr()), n, tables.camera.initialFar if far is None else far, image_width,
+                                         tables.objects, tables.num_objects, tables.lights, tables.num_lights, C.byref(tables.globals_),
+                                         C.byref(settings), C.byref(res), C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(br.data_ptr()) if bright else None, self._stream()))
+        return (out, br) if bright else out
+
+    def trace_rays_layers(self, tables, settings, rays, image_width, normals=True, out=None):
+        """rm_trace_rays_layers: the closest VISIBLE SURFACE along arbitrary rays, the terrain and the sea included → (normal, t,
+        position, object_id) as trace_rays returns them.  object_id: abi.RM_HIT_TERRAIN (−4) with the terrain's own surface normal,
+        abi.RM_HIT_SEA (−3) with the shader's sea normal, else trace_rays' closest hit (an index, −1 a miss, abi.RM_RAY_INVALID).
+        image_width as shade_rays_layers takes it; RM_FEAT_CLOUD is ignored (a volume has no closest hit).  normals=False: object_id
+        and t only.  Occlusion through the layers is not defined: trace_rays has the objects' shadow march.  The definition is in
+        include/raymarcher_amd.h."""
+        t = self.torch
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        hits = self._out(out, (n, 8), t.float32)
+        check(lib().rm_trace_rays_layers(C.c_void_p(rays.data_ptr()), n, image_width, tables.objects, tables.num_objects,
+                                         C.byref(tables.globals_), C.byref(settings),
+                                         abi.RM_TRACE_CLOSEST if normals else abi.RM_TRACE_NO_NORMAL, C.c_void_p(hits.data_ptr()),
+                                         self._stream()))
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def render_panorama_layers(self, tables, settings, W, H, position, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), far=None):
+        """render_panorama through shade_rays_layers with image_width = W: a W×H equirectangular panorama with terrain, sea and
+        clouds → float32 (H, W, 4), row 0 = bottom."""
+        t = self.torch
+        order = tile_order(W, H)
+        colour = self.shade_rays_layers(tables, settings, panorama_rays(position, W, H, forward, up)[order], W, far=far)
+        out = t.empty((H * W, 4), dtype=t.float32, device=self.device)
+        out[t.from_numpy(order).to(self.device)] = colour  # the inverse permutation: ray k is pixel order[k]
+        return out.view(H, W, 4)
+
     def pick(self, tables, settings, W, H, x, y, camera=None):
         """What lies under pixel (x, y) of a W×H frame (y = 0 the bottom row) → (object_id, position, normal, t): an int (−1: nothing),
         two tuples of three floats and a float, through camera_rays and trace_rays — the values rm_render_gbuffer has for that
