@@ -567,6 +567,81 @@ int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const
                          const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream);
 
 /*
+ * rm_sdf_grid — WHERE the surface is: sdScene on a dense lattice (no reference counterpart: the shader evaluates its distance
+ * function only along its own rays).  For a 3-D texture of the field (physics, particles, a caller's own ambient occlusion, keeping
+ * a camera out of the scene without a ray) and as the input of rm_sdf_mesh.  d_dist: nx·ny·nz floats in device memory, d_objectId
+ * (may be NULL): as many int32; the object table, g, s, origin and step are host memory, copied before return.  Asynchronous on
+ * `stream`.
+ * Definition, bit for bit.  Lattice point (i, j, k) is p.x = origin[0] + (float)i · step[0], and likewise y and z: one binary32
+ * multiply, then one binary32 add, never fused (NumPy: origin + np.arange(n, dtype=float32) · step).  d_dist[(k·ny + j)·nx + i] — x
+ * fastest, a 64-bit index — is the minD that sdScene(p) returns (frag:1406-1430), d_objectId at the same index its minObjIdx (−1
+ * for an empty table): exactly what rm_probe_sdscene stores in components 0 and 1 for that point.  Nothing is written to a NULL
+ * d_objectId, and d_dist is the same bits without it.  The sign is the scene's: negative inside an object whose distance function is
+ * signed; a Mandelbulb's estimate is 0 or above, and below 0.001 — the march's hit threshold — only close to its surface.
+ * Of RmSettings the call reads fractalIters, mengerLevels and the power-8 form bit; of RmGlobals power, juliaSeed and iTime.  Lights,
+ * samplers, cameras and the march's settings play no part.  The value of a point does not depend on which other points share its
+ * call.
+ * In this order, and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: null g, s, origin or step, a null table with a
+ * positive count or a negative count, an origin component that is not finite, a step component that is not finite or not greater
+ * than 0, a dimension below 1 or above RM_MAX_LATTICE_DIM, more than INT_MAX points; RM_ERR_UNSUPPORTED: RM_FEAT_TERRAIN,
+ * RM_FEAT_CLOUD or RM_FEAT_SEA in the settings (the lattice holds the object table only), g->isTwoD; rm_trace_rays' checks of the
+ * table: RM_ERR_CAPACITY beyond RM_MAX_OBJECTS, a negative loop bound, RM_ERR_UNSUPPORTED for a CUSTOM or unknown object type;
+ * RM_ERR_INVALID_ARGUMENT: a null d_dist, an output that is not device memory.  There is no empty lattice: every dimension is at
+ * least 1.
+ * Schedule: ONE launch, one lane per lattice point, of the grid kernel of the table's march class — the table walk, the general
+ * Mandelbulb, or its plain form where rm_debug_bulb_plain says 1 (rm_debug_last_path() = 16, rm_debug_last_split() = 0).  A wave
+ * owns a brick of 4×4×4 points, so the lanes of a wave are neighbours in space and a Mandelbulb's iteration counts differ as little
+ * as they can; a workgroup is four bricks along x.  It uses one slot of the batch ring of scene blocks and neither reads nor changes
+ * the per-stream tuner and tile-order state of single-frame renders, and no library workspace.  With rm_set_timing(1) it counts as
+ * one launch, all stage 1.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_MAX_LATTICE_DIM 4096
+int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                const float step[3], int nx, int ny, int nz, float *d_dist, int32_t *d_objectId /* may be NULL */, void *stream);
+/*
+ * rm_sdf_mesh — a QUAD MESH of the surface {v = iso} of any lattice of floats, by naive surface nets: one vertex per cell the surface
+ * passes through, one quad per lattice edge it crosses (no reference counterpart).  For the Mandelbulb or the sponge as a mesh: 3-D
+ * printing, a DCC tool, collision geometry.  d_dist: nx·ny·nz floats in rm_sdf_grid's layout, from rm_sdf_grid or from anywhere else
+ * (smoothed, clipped, two lattices combined); d_objectId (may be NULL): as many int32.  Outputs, all device memory: d_vertices, 4
+ * floats per vertex; d_vertexObject (may be NULL), one int32 per vertex; d_quads, 4 vertex numbers per quad; d_counts, 2 words.
+ * origin and step are host memory, copied before return.  Asynchronous on `stream`; no host synchronisation and no read-back.
+ * Definition, bit for bit.  inside(v) = v < iso; a NaN is outside.
+ * Cells: cell (i, j, k), 0 <= i < nx − 1 and so on, has the corners c = cx + 2·cy + 4·cz at lattice point (i + cx, j + cy, k + cz)
+ * and twelve edges in this order: the x-edges (0,1) (2,3) (4,5) (6,7), the y-edges (0,2) (1,3) (4,6) (5,7), the z-edges (0,4) (1,5)
+ * (2,6) (3,7).  A cell is active iff its corners are neither all inside nor all outside.
+ * Vertex of an active cell: acc = (+0, +0, +0), n = 0; for each edge (a, b), in order, whose ends differ in inside: t = (iso − v_a) /
+ * (v_b − v_a) — one subtraction each, one IEEE division —, t = 0.5f unless (t >= 0 && t <= 1); the crossing is corner a's (cx, cy,
+ * cz) as floats with the edge's axis component replaced by t; acc += crossing, component by component; ++n.  local = acc · (1.0f /
+ * (float)n); vertex.x = origin[0] + ((float)i + local.x) · step[0] — add, multiply, add, unfused —, y and z alike, vertex.w = 0.
+ * d_vertexObject, where it and d_objectId are both given, is the id at the cell's first inside corner in corner order; −1 without
+ * d_objectId.
+ * Vertex order: the cells' linear order (k·(ny − 1) + j)·(nx − 1) + i; a vertex's number is the count of active cells before its own.
+ * Quads: the lattice edge from P = (i, j, k) to P + e_axis gives one quad iff its ends differ in inside and it is interior in the
+ * other two axes (x: 1 <= j <= ny − 2 and 1 <= k <= nz − 2), over the four cells around it — x: (i,j−1,k−1) (i,j,k−1) (i,j,k)
+ * (i,j−1,k); y: (i−1,j,k−1) (i−1,j,k) (i,j,k) (i,j,k−1); z: (i−1,j−1,k) (i,j−1,k) (i,j,k) (i−1,j,k) — in that order when P is inside,
+ * as (c0, c3, c2, c1) otherwise: the normal points to the outside.  All four cells are active.  A surface that leaves the lattice is
+ * left open there.  Quad order: by P's lattice index (k·ny + j)·nx + i, then by axis x, y, z.
+ * Counts and capacity: d_counts[0] and d_counts[1] always receive the FULL number of vertices and quads (the quads' saturates at
+ * 2^32 − 1); only vertices numbered below maxVertices and quads numbered below maxQuads are stored, so a stored quad may name a
+ * vertex that was not: compare the counts with the capacities.  maxVertices = maxQuads = 0 with null outputs is the counting call.
+ * A lattice with a dimension of 1 has no cell: RM_OK, both counts 0.
+ * In this order, and all but the last before any HIP call, RM_ERR_INVALID_ARGUMENT: null origin or step, an origin component that is
+ * not finite, a step component that is not finite or not greater than 0, a dimension below 1 or above RM_MAX_LATTICE_DIM, more than
+ * INT_MAX points (rm_sdf_grid's rules); iso not finite; a negative capacity; a null d_vertices or d_quads with its capacity above 0;
+ * a null d_dist or d_counts; an array that is not device memory.
+ * Schedule: a count of active cells and crossed edges per workgroup of 1024 lattice points, an exclusive scan of the counts that
+ * also stores d_counts, then — unless both capacities are 0 — the vertices and each active cell's vertex number, and the quads from
+ * those numbers: two launches for the counting call, up to four otherwise.  The numbers live in a grow-only workspace per (device,
+ * stream) of 4 B per cell + 12 B per 1024 lattice points: rm_set_workspace_limit applies (a lattice over a set limit: RM_ERR_DEVICE),
+ * rm_release_workspaces frees it.  Not a render launch: rm_debug_last_path() keeps its value and rm_set_timing does not time it.
+ */
+int rm_sdf_mesh(const float *d_dist, const int32_t *d_objectId /* may be NULL */, int nx, int ny, int nz, const float origin[3],
+                const float step[3], float iso, int maxVertices, int maxQuads, float *d_vertices /* float4 each */,
+                int32_t *d_vertexObject /* may be NULL */, int32_t *d_quads /* int4 each */, uint32_t *d_counts /* 2 words */,
+                void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -682,7 +757,7 @@ int rm_get_timing(double *avgKernelMs, int *launches);
  * them (rm_set_tile_order: a new picture and the first repeats of one; a settled picture, a small frame or raster order has none).
  * A batch of rm_render_batch counts as one launch, all of it stage 1 (its wavefront frames as launches of their own); so does a
  * launch of rm_render_supersampled, rm_render_accumulated, rm_render_animated, rm_render_gbuffer, rm_trace_rays, rm_shade_rays,
- * rm_shade_rays_layers or rm_trace_rays_layers, and so does a whole call of rm_render_adaptive.
+ * rm_shade_rays_layers, rm_trace_rays_layers or rm_sdf_grid, and so does a whole call of rm_render_adaptive.
  * Stages 2-3 are zero. */
 int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches);
 /* Which schedule renders a frame: 0 = the measured-fastest one of the scene's class (default), 1 = one lane per pixel
@@ -713,7 +788,7 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
- * launch of rm_trace_rays_layers (none of them is a value rm_set_kernel_path takes). */
+ * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups
@@ -937,6 +1012,13 @@ const char *rm_skybox_face_path(int which, int face);
 
 /* PNG writer for RGBA8 rows (top row first) — stands in for QImage::save (realtime.cpp:346). */
 int rm_write_png(const char *path, const uint8_t *rgba, int W, int H);
+/* PLY writer for the mesh of rm_sdf_mesh, copied to host memory (no reference counterpart): binary little-endian, `element vertex`
+ * with float x, y, z (the fourth float of a vertex is not written) and, with rgb (3 bytes per vertex, may be NULL), uchar red,
+ * green, blue; `element face` with `property list uchar int vertex_indices`, four indices per face.  numVertices or numQuads may be
+ * 0 (its array is then not read).  RM_ERR_INVALID_ARGUMENT: a null path, a negative count, a null array with a positive count, a
+ * quad that names a vertex outside 0 … numVertices − 1 (nothing is written then); RM_ERR_IO: the file cannot be opened or written. */
+int rm_write_ply(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads,
+                 const uint8_t *rgb /* may be NULL, 3 per vertex */);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,10 @@ SIGNATURES = {
                                        _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_trace_rays_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings),
                                        C.c_uint, C.c_void_p, C.c_void_p]),
+    "rm_sdf_grid": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(C.c_float), _P(C.c_float), C.c_int,
+                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_sdf_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), C.c_float, C.c_int, C.c_int,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_camera_rays": (C.c_int, [_P(abi.RmCamera), C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
@@ -130,6 +134,7 @@ SIGNATURES = {
     "rm_scene_camera_lens": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
     "rm_scene_object_texture": (C.c_char_p, [C.c_void_p, C.c_int]),
     "rm_write_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
+    "rm_write_ply": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "rm_abi_sizeof": (C.c_int, [C.c_int]),
 }
 

@@ -123,6 +123,8 @@ RM_RAY_INVALID = -2  # RmRayHit.objectId of an invalid ray
 RM_PATH_TRACE_RAYS, RM_PATH_SHADE_RAYS = 12, 13  # rm_debug_last_path() behind a launch of rm_trace_rays / rm_shade_rays
 RM_HIT_SEA, RM_HIT_TERRAIN = -3, -4  # RmRayHit.objectId of rm_trace_rays_layers where the sea / the terrain is the visible surface
 RM_PATH_SHADE_RAYS_LAYERS, RM_PATH_TRACE_RAYS_LAYERS = 14, 15  # … behind rm_shade_rays_layers / rm_trace_rays_layers
+RM_PATH_SDF_GRID = 16  # … behind rm_sdf_grid
+RM_MAX_LATTICE_DIM = 4096  # points per axis of a lattice of rm_sdf_grid / rm_sdf_mesh
 
 
 def default_settings(**over):

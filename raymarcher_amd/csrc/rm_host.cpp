@@ -360,4 +360,44 @@ int rm_write_png(const char *path, const uint8_t *rgba, int W, int H) {
   return RM_OK;
 }
 
+// Binary little-endian PLY: the header, the vertices (x, y, z and the optional colour), the faces (a count byte and four indices).
+int rm_write_ply(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads, const uint8_t *rgb) {
+  if (!path || numVertices < 0 || numQuads < 0 || (numVertices > 0 && !vertices4) || (numQuads > 0 && !quads4)) {
+    set_error("bad ply arguments");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  for (size_t q = 0; q < (size_t)numQuads * 4; q++)
+    if (quads4[q] < 0 || quads4[q] >= numVertices) {
+      set_error("quad " + std::to_string(q / 4) + " names a vertex outside the vertex array");
+      return RM_ERR_INVALID_ARGUMENT;
+    }
+  static_assert(sizeof(float) == 4 && sizeof(int32_t) == 4, "binary32 and 32-bit indices");
+  const uint16_t probe = 1;
+  if (*reinterpret_cast<const uint8_t *>(&probe) != 1) { set_error("rm_write_ply needs a little-endian host"); return RM_ERR_UNSUPPORTED; }
+  std::string head = "ply\nformat binary_little_endian 1.0\ncomment raymarcher_amd rm_sdf_mesh\nelement vertex " + std::to_string(numVertices) +
+                     "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (rgb) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  head += "element face " + std::to_string(numQuads) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  const size_t vsize = rgb ? 15 : 12;
+  std::vector<uint8_t> body((size_t)numVertices * vsize + (size_t)numQuads * 17);
+  uint8_t *o = body.data();
+  for (int v = 0; v < numVertices; v++) {
+    std::memcpy(o, vertices4 + (size_t)v * 4, 12);
+    o += 12;
+    if (rgb) { std::memcpy(o, rgb + (size_t)v * 3, 3); o += 3; }
+  }
+  for (int q = 0; q < numQuads; q++) {
+    *o++ = 4;
+    std::memcpy(o, quads4 + (size_t)q * 4, 16);
+    o += 16;
+  }
+  FILE *f = std::fopen(path, "wb");
+  if (!f) { set_error(std::string("cannot open ") + path); return RM_ERR_IO; }
+  bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+  ok = (body.empty() || std::fwrite(body.data(), 1, body.size(), f) == body.size()) && ok;
+  ok = (std::fclose(f) == 0) && ok;
+  if (!ok) { set_error("short write"); return RM_ERR_IO; }
+  return RM_OK;
+}
+
 }  // extern "C"

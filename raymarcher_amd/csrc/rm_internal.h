@@ -42,7 +42,7 @@ int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
 // different streams of one device may run concurrently on the GPU and therefore never share scratch.  Growing
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
-enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7 };
+enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 // The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
 // this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).
@@ -111,6 +111,13 @@ int launch_shade_layers_kernel(const void *sb, bool tex, bool sec, const void *d
                                float *d_bright, hipStream_t stream);
 int launch_trace_layers_kernel(const void *sb, int bulbClass, bool noNormal, const void *d_rays, int numRays, int imageWidth,
                                void *d_hits, hipStream_t stream);
+// The lattice kernels (rm_volume.hip, rm_sdf_grid and rm_sdf_mesh; a translation unit of its own for the same reason).
+// check_lattice: the rules both entry points have for origin, step and the dimensions, in the header's order, no HIP call.
+// launch_sdf_grid_kernel: sdf_grid_kernel<bulbClass> over the ONE staged SceneBlock `sb`, one lane per lattice point, a wave per
+// brick — nx·ny·nz values into d_dist and, when d_objectId is not null, as many object indices.  rm_sdf_mesh is whole in rm_volume.hip.
+int check_lattice(const float *origin, const float *step, int nx, int ny, int nz);
+int launch_sdf_grid_kernel(const void *sb, int bulbClass, const float origin[3], const float step[3], int nx, int ny, int nz,
+                           float *d_dist, int32_t *d_objectId, hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + grid.z − 1 of d_rgba (grid: their 8×8 tiles), into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

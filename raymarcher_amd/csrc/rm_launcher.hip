@@ -1174,6 +1174,34 @@ int launch_shade(const ShadeCall &c) {
   return finish_frames(sf, c.layers ? 14 : 13);
 }
 
+// ---- the field on a lattice (rm_sdf_grid) ----------------------------------------------------------------------------------------
+// rm_sdf_grid (the header has the definition): sdScene at the points of a dense lattice against ONE object table.  The checks run in
+// the header's order, every one but the last ahead of the first HIP call: the pointers and the table's count, the lattice
+// (check_lattice, which rm_sdf_mesh shares), the layers and the 2-D mode, check_trace's table checks, then d_dist and whether the
+// outputs are device memory.  Staging is launch_trace's: stage_blocks of one block of the batch ring, filled with a camera of zeros
+// and no lights.  Then ONE launch of sdf_grid_kernel (rm_volume.hip) of the table's march class, path 16: no tuner, tile-order or
+// workspace state is read or changed.
+int launch_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float *origin, const float *step,
+                    int nx, int ny, int nz, float *d_dist, int32_t *d_objectId, hipStream_t stream) {
+  if (!g || !s || !origin || !step) { set_error("null g, s, origin or step"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((numObjects > 0 && !objs) || numObjects < 0) { set_error("null object table or negative count"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = check_lattice(origin, step, nx, ny, nz);
+  if (st != RM_OK) return st;
+  if ((st = refuse_layers(s, "rm_sdf_grid evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK) return st;
+  if ((st = refuse_two_d(g, "the 2-D mode (isTwoD) has no distance field")) != RM_OK) return st;
+  if ((st = check_object_table(objs, numObjects, s)) != RM_OK) return st;
+  if (!d_dist) { set_error("null d_dist"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = require_device_pointers({{"d_dist", d_dist}, {"d_objectId", d_objectId}})) != RM_OK) return st;
+  const int bulbClass = table_bulb_class(objs, numObjects, bulb_plain(objs, numObjects, g) != 0);
+  const RmCamera noCam{};
+  StagedFrames sf(stream);
+  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, &noCam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
+      })) != RM_OK) return st;
+  if ((st = launch_sdf_grid_kernel(sf.slot->dev, bulbClass, origin, step, nx, ny, nz, d_dist, d_objectId, stream)) != RM_OK) return st;
+  return finish_frames(sf, 16);
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
 // single frames, then launch(the device's block) behind it.
 template <class Launch>
@@ -1293,6 +1321,11 @@ int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageW
 int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
                          const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream) {
   return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream), true, imageWidth});
+}
+
+int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3], const float step[3],
+                int nx, int ny, int nz, float *d_dist, int32_t *d_objectId, void *stream) {
+  return launch_sdf_grid(objs, numObjects, g, s, origin, step, nx, ny, nz, d_dist, d_objectId, static_cast<hipStream_t>(stream));
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

@@ -327,6 +327,52 @@ def save_png_sequence(images8, pattern):
     return paths
 
 
+def _vec3(v, name):
+    """Three floats as the (C.c_float * 3) the lattice calls take."""
+    vals = [float(x) for x in v]
+    if len(vals) != 3:
+        raise ValueError(f"{name} must have three components")
+    return (C.c_float * 3)(*vals)
+
+
+def mesh_bounds(tables, margin=0.0):
+    """The axis-aligned box (lo, hi), two float32 arrays of 3, that holds every surface of the object table, widened by `margin` on
+    every side: the box of rm_debug_cull_bounds where the launcher stages one, else the box around its ball.  Raises ValueError for a
+    table without a bound (an empty one, a Sierpinski, a 2-D Mandelbrot as an object): pass bounds to scene_mesh yourself then."""
+    import numpy as np
+    out = (C.c_float * 14)()
+    check(lib().rm_debug_cull_bounds(tables.objects, tables.num_objects, C.byref(tables.globals_), out))
+    v = np.array(list(out), dtype=np.float64)
+    if v[0] == 0.0:
+        raise ValueError("the object table has no bound (rm_debug_cull_bounds): pass bounds=(lo, hi)")
+    if v[6] != 0.0:
+        lo, hi = v[7:10], v[10:13]
+    else:
+        r = np.sqrt(v[4])
+        lo, hi = v[1:4] - r, v[1:4] + r
+    return (lo - margin).astype(np.float32), (hi + margin).astype(np.float32)
+
+
+def write_ply(path, vertices, quads, colours=None):
+    """rm_write_ply: the mesh of extract_mesh / scene_mesh as a binary little-endian PLY.  vertices (n, 4) float32 and quads (m, 4)
+    int32, tensors or arrays; colours: (n, 3) uint8 or None."""
+    import numpy as np
+
+    def host(a, dtype, cols):
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.ndim != 2 or a.shape[1] != cols:
+            raise ValueError(f"expected an (n, {cols}) array, got {a.shape}")
+        return a
+    v, q = host(vertices, np.float32, 4), host(quads, np.int32, 4)
+    c = None if colours is None else host(colours, np.uint8, 3)
+    if c is not None and c.shape[0] != v.shape[0]:
+        raise ValueError("one colour per vertex")
+    check(lib().rm_write_ply(str(path).encode(), C.c_void_p(v.ctypes.data), v.shape[0], C.c_void_p(q.ctypes.data), q.shape[0],
+                             C.c_void_p(c.ctypes.data) if c is not None else None))
+    return path
+
+
 class Renderer:
     """Launches the HIP raymarch on one GPU; outputs are torch tensors on that device."""
 
@@ -640,6 +686,77 @@ class Renderer:
         out = t.empty((H * W, 4), dtype=t.float32, device=self.device)
         out[t.from_numpy(order).to(self.device)] = colour  # the inverse permutation: ray k is pixel order[k]
         return out.view(H, W, 4)
+
+    def sdf_grid(self, tables, settings, origin, step, dims, ids=False):
+        """rm_sdf_grid: the scene's distance function on a dense lattice → float32 (nz, ny, nx), x fastest; with ids=True the pair
+        (distances, int32 (nz, ny, nx) object indices).  Point (i, j, k) is origin + (i, j, k) · step in float32; dims = (nx, ny,
+        nz).  The values are rm_probe_sdscene's minD and minObjIdx at those points; include/raymarcher_amd.h has the definition."""
+        t = self.torch
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 1:
+            raise ValueError("every lattice dimension must be at least 1")
+        dist = t.empty((nz, ny, nx), dtype=t.float32, device=self.device)
+        obj = t.empty((nz, ny, nx), dtype=t.int32, device=self.device) if ids else None
+        check(lib().rm_sdf_grid(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings), _vec3(origin, "origin"),
+                                _vec3(step, "step"), nx, ny, nz, C.c_void_p(dist.data_ptr()),
+                                C.c_void_p(obj.data_ptr()) if ids else None, self._stream()))
+        return (dist, obj) if ids else dist
+
+    def extract_mesh(self, grid, origin, step, iso=0.0, ids=None):
+        """rm_sdf_mesh: the quad mesh of the surface {grid = iso} by naive surface nets → (vertices float32 (n, 4), quads int32 (m,
+        4)), and the vertices' object indices int32 (n) behind them when `ids` (the lattice's int32 indices, same shape) is given.
+        grid: float32 (nz, ny, nx) on this device, from sdf_grid or from anywhere else.  A counting call, one read of two words,
+        then an emitting call with exact capacities; raises if the two calls disagree about the counts."""
+        t = self.torch
+        if grid.dim() != 3 or grid.dtype != t.float32 or not grid.is_contiguous() or grid.device != self.device:
+            raise ValueError(f"grid must be a contiguous float32 tensor of shape (nz, ny, nx) on {self.device}")
+        if ids is not None and (tuple(ids.shape) != tuple(grid.shape) or ids.dtype != t.int32 or not ids.is_contiguous()
+                                or ids.device != self.device):
+            raise ValueError(f"ids must be a contiguous int32 tensor of shape {tuple(grid.shape)} on {self.device}")
+        nz, ny, nx = grid.shape
+        o, st = _vec3(origin, "origin"), _vec3(step, "step")
+        idp = C.c_void_p(ids.data_ptr()) if ids is not None else None
+        counts = t.zeros(2, dtype=t.int64, device=self.device)  # two uint32 words in the first eight bytes
+
+        def call(max_v, max_q, v, vo, q):
+            check(lib().rm_sdf_mesh(C.c_void_p(grid.data_ptr()), idp, nx, ny, nz, o, st, float(iso), max_v, max_q,
+                                    C.c_void_p(v.data_ptr()) if v is not None else None,
+                                    C.c_void_p(vo.data_ptr()) if vo is not None else None,
+                                    C.c_void_p(q.data_ptr()) if q is not None else None, C.c_void_p(counts.data_ptr()), self._stream()))
+            both = int(counts[0].item())
+            return both & 0xFFFFFFFF, (both >> 32) & 0xFFFFFFFF
+
+        nv, nq = call(0, 0, None, None, None)
+        if nv > 2 ** 31 - 1 or nq > 2 ** 31 - 1:
+            raise RaymarcherError(abi.RM_ERR_CAPACITY, f"{nv} vertices and {nq} quads exceed one call's capacity")
+        verts = t.empty((nv, 4), dtype=t.float32, device=self.device)
+        quads = t.empty((nq, 4), dtype=t.int32, device=self.device)
+        vobj = t.empty((nv,), dtype=t.int32, device=self.device) if ids is not None else None
+        if nv or nq:
+            again = call(nv, nq, verts if nv else None, vobj if nv else None, quads if nq else None)
+            if again != (nv, nq):
+                raise RuntimeError(f"rm_sdf_mesh counted {(nv, nq)} vertices and quads, then {again}: the lattice changed between the calls")
+        return (verts, quads, vobj) if ids is not None else (verts, quads)
+
+    def scene_mesh(self, tables, settings, resolution, iso=0.001, bounds=None):
+        """The scene's surface as a quad mesh: sdf_grid over the table's bounds, then extract_mesh → (vertices, quads, vertex object
+        indices).  resolution: lattice points along the longest side of the bounds (at least 4); the step is the same on every axis
+        and the lattice reaches one step past the bounds on every side, so a surface inside the bounds is closed.  iso: 0.001, the
+        march's hit threshold — what the renderer shows as the surface, and the smallest value that has a Mandelbulb's inside.
+        bounds: (lo, hi), or None for mesh_bounds(tables)."""
+        import numpy as np
+        if int(resolution) < 4:
+            raise ValueError("resolution must be at least 4")
+        lo, hi = mesh_bounds(tables) if bounds is None else (np.asarray(b, dtype=np.float64) for b in bounds)
+        lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+        side = hi - lo
+        if lo.shape != (3,) or hi.shape != (3,) or not np.isfinite(side).all() or not (side > 0).all():
+            raise ValueError("bounds must be (lo, hi) with three finite components each and lo < hi")
+        step = float(side.max()) / (int(resolution) - 3)
+        dims = [min(int(resolution), int(np.ceil(sd / step)) + 3) for sd in side]
+        origin = lo - step
+        dist, obj = self.sdf_grid(tables, settings, origin, (step,) * 3, dims, ids=True)
+        return self.extract_mesh(dist, origin, (step,) * 3, iso, obj)
 
     def pick(self, tables, settings, W, H, x, y, camera=None):
         """What lies under pixel (x, y) of a W×H frame (y = 0 the bottom row) → (object_id, position, normal, t): an int (−1: nothing),
