@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle", "tools", "glsl_ref"))
 
 import helpers as h  # noqa: E402
 import run_ref  # noqa: E402
-import test_gpu_parity as tg  # noqa: E402
+import scene_builders as SB  # noqa: E402
 from raymarcher_amd import abi  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "glsl")
@@ -37,7 +37,7 @@ def pack(scene, settings):
 
 
 def frame_case(name, scene, settings, W, H, texture=None, ub10=False, ub1=False, **res):
-    """res: noise= / skybox= (six faces) / ltc1=, ltc2= — the sampler inputs of tg.resource_case, stored in the fixture."""
+    """res: noise= / skybox= (six faces) / ltc1=, ltc2= — the sampler inputs of SB.resource_case, stored in the fixture."""
     ltc = (res["ltc1"], res["ltc2"]) if "ltc1" in res else None
     rgba, bright = run_ref.render(scene, settings, W, H, texture, noise=res.get("noise"), skybox=res.get("skybox"), ltc=ltc, ub10=ub10, ub1=ub1)
     extra = {} if texture is None else {"texture": texture}
@@ -61,14 +61,14 @@ def probe_case(name, kind, scene, settings, pts):
 def env_cases():
     W, H = 64, 36
     sky_terr = abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN
-    frame_case("env_terrain_sky", tg.env_scene(W, H), abi.default_settings(features=sky_terr), W, H)
-    frame_case("env_terrain_cloud_sky", tg.env_scene(W, H), abi.default_settings(features=sky_terr | abi.RM_FEAT_CLOUD), W, H)
-    frame_case("env_all_reflect", tg.env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
-               abi.default_settings(features=tg.ENV_ALL, enableReflection=1), W, H)
+    frame_case("env_terrain_sky", SB.env_scene(W, H), abi.default_settings(features=sky_terr), W, H)
+    frame_case("env_terrain_cloud_sky", SB.env_scene(W, H), abi.default_settings(features=sky_terr | abi.RM_FEAT_CLOUD), W, H)
+    frame_case("env_all_reflect", SB.env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
+               abi.default_settings(features=SB.ENV_ALL, enableReflection=1), W, H)
     # the same two cloud frames with the shader's unset `nnd` given the oracle's UB10 value (essl_adapt.define_ub10)
-    frame_case("env_terrain_cloud_sky_ub10", tg.env_scene(W, H), abi.default_settings(features=sky_terr | abi.RM_FEAT_CLOUD), W, H, ub10=True)
-    frame_case("env_all_reflect_ub10", tg.env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
-               abi.default_settings(features=tg.ENV_ALL, enableReflection=1), W, H, ub10=True)
+    frame_case("env_terrain_cloud_sky_ub10", SB.env_scene(W, H), abi.default_settings(features=sky_terr | abi.RM_FEAT_CLOUD), W, H, ub10=True)
+    frame_case("env_all_reflect_ub10", SB.env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
+               abi.default_settings(features=SB.ENV_ALL, enableReflection=1), W, H, ub10=True)
     if len(sys.argv) > 2 and sys.argv[2] == "frames":
         return
     # function-level probes of the procedural layers (the defines must be on for these functions to exist)
@@ -83,7 +83,7 @@ def env_cases():
     try:
         rng = np.random.default_rng(7)
         pts = np.stack([rng.uniform(-2000, 2000, 4096), rng.uniform(600, 1200, 4096), rng.uniform(-2000, 2000, 4096)], 1)
-        sc, s = tg.env_scene(8, 8), abi.default_settings(features=tg.ENV_ALL)
+        sc, s = SB.env_scene(8, 8), abi.default_settings(features=SB.ENV_ALL)
         probe_case("env_cloudsfbm", "cloudsfbm", sc, s, pts)
         probe_case("env_cloudsmap", "cloudsmap", sc, s, pts)
         probe_case("env_terrain", "terrain", sc, s, pts)
@@ -95,12 +95,12 @@ def texture_cases():
     """unit_sphere.json-like: the four textured primitive types sharing ONE texture (the ESSL adaptation reads
     objTextures[0] for every texLoc), LINEAR filtering, REPEAT wrap."""
     W, H = 64, 48
-    scene = tg.textured_scene(W, H)
+    scene = SB.textured_scene(W, H)
     for o in scene[1]:
         if o.texLoc != -1:
             o.texLoc = 0
     frame_case("textured_prims", scene, abi.default_settings(features=abi.RM_FEAT_WHITE_BACKGROUND), W, H,
-               texture=tg.synthetic_textures()[1])
+               texture=SB.synthetic_textures()[1])
 
 
 def post_cases():
@@ -108,7 +108,7 @@ def post_cases():
     Realtime::applyBloom / applyLightEffects / applyFXAA do, on an over-bright reflective frame from the oracle."""
     import run_post
     W, H = 72, 48
-    scene = tg.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         for k in range(3):
             li.color[k] *= 2.5
@@ -138,23 +138,23 @@ def post_cases():
 def softshadow_cases():
     """Soft shadows with the shader's unset `r.d` given the UB1 value in the harness (essl_adapt.define_ub1)."""
     W, H = 64, 48
-    prims = tg.all_primitives_scene(W, H)
+    prims = SB.all_primitives_scene(W, H)
     WB = abi.RM_FEAT_WHITE_BACKGROUND
     frame_case("prims_a_softshadow_ub1", subset(prims, range(0, 6)), abi.default_settings(features=WB, enableSoftShadow=1), W, H, ub1=True)
     frame_case("prims_softshadow_ao_bump_ub1", subset(prims, [0, 2, 4, 6, 8, 9]),
                abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1), W, H, ub1=True)
-    scene, s, res = tg.resource_case("area_light_soft_bump", 64, 40)
+    scene, s, res = SB.resource_case("area_light_soft_bump", 64, 40)
     frame_case("res_area_light_soft_bump_ub1", scene, s, 64, 40, ub1=True, **res)
 
 
 def resource_cases(only=None):
     """Night sky, sea, sky box and area lights: the reference shader with its noise / cube-map / LTC samplers bound to
-    the synthetic inputs of tests/test_gpu_parity.py."""
+    the synthetic inputs of tests/scene_builders.py."""
     W, H = 64, 40
-    for name in tg.RESOURCE_CASES:
+    for name in SB.RESOURCE_CASES:
         if only and name not in only:
             continue
-        scene, s, res = tg.resource_case(name, W, H)
+        scene, s, res = SB.resource_case(name, W, H)
         if s.enableSoftShadow or (s.features & abi.RM_FEAT_CLOUD):
             continue  # UB1 (soft shadow reads an unset variable) / UB10 (cloud density sample): covered by the env cases
         frame_case("res_" + name, scene, s, W, H, **res)
@@ -162,9 +162,9 @@ def resource_cases(only=None):
         return
     # function-level probes of the sea and the night sky
     rng = np.random.default_rng(3)
-    scene, s = tg.sea_scene(8, 8), abi.default_settings()
+    scene, s = SB.sea_scene(8, 8), abi.default_settings()
     pts = rng.uniform(-30, 30, (4096, 3)).astype(np.float32)
-    noise = tg.synthetic_noise()
+    noise = SB.synthetic_noise()
     for kind in ("sea", "moon", "sinhash"):
         out = run_ref.probe(kind, scene, s, pts, noise=noise)
         np.savez_compressed(os.path.join(OUT, f"probe_{kind}.npz"), kind=kind, pts=pts, out=out, uses_noise=1, **pack(scene, s))
@@ -186,7 +186,7 @@ SCENEFILE_CASES = {
     "unit_mengersponge_defaults": ("simple/unit_mengersponge.json", 96, 54, {}, {}),
     # BASELINE configuration 4: volumetric.json as the file is, with the TERRAIN / CLOUD / SKY_BACKGROUND layers compiled in
     # (`nnd` given the UB10 value) — and the terrain + sky layers alone, which need no such edit
-    "c4_volumetric_terrain_cloud_sky_ub10": ("simple/volumetric.json", 96, 54, dict(features=tg.ENV_ALL), dict(ub10=True)),
+    "c4_volumetric_terrain_cloud_sky_ub10": ("simple/volumetric.json", 96, 54, dict(features=SB.ENV_ALL), dict(ub10=True)),
     "c4_volumetric_terrain_sky": ("simple/volumetric.json", 96, 54,
                                   dict(features=abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN), {}),
 }
@@ -355,14 +355,14 @@ def main():
     softshadow_cases()
     W, H = 64, 48
     WB, DB = abi.RM_FEAT_WHITE_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND
-    prims = tg.all_primitives_scene(W, H)
+    prims = SB.all_primitives_scene(W, H)
     frame_case("prims_a_phong", subset(prims, range(0, 6)), abi.default_settings(features=WB), W, H)
     frame_case("prims_b_phong", subset(prims, [6, 7, 8, 9]), abi.default_settings(features=WB, maxSteps=128), W, H)
     frame_case("prims_a_bump", subset(prims, range(0, 6)), abi.default_settings(), W, H)
     frame_case("prims_ao", subset(prims, [0, 2, 4, 6, 8, 9]), abi.default_settings(features=DB, enableAmbientOcclusion=1), W, H)
-    frame_case("reflect_refract", tg.reflect_refract_scene(W, H),
+    frame_case("reflect_refract", SB.reflect_refract_scene(W, H),
                abi.default_settings(features=WB, enableReflection=1, enableRefraction=1), W, H)
-    frame_case("menger_reflect", tg.menger_scene(W, H), abi.default_settings(features=WB, enableReflection=1), W, H)
+    frame_case("menger_reflect", SB.menger_scene(W, H), abi.default_settings(features=WB, enableReflection=1), W, H)
     frame_case("bulb_reference_consts", h.scene_mandelbulb(96, 54), abi.default_settings(), 96, 54)
     frame_case("bulb_12iters_nobump", h.scene_mandelbulb(96, 54), abi.default_settings(features=WB, fractalIters=12), 96, 54)
     two_d = h.scene_mandelbulb(W, H)[:5] + (h.make_globals(two_d=1, itime=3.0),)
@@ -375,7 +375,7 @@ def main():
     probe_case("sd_bulb_p8_12iters", "sdscene", bulb, abi.default_settings(fractalIters=12), rng.normal(0, 0.8, (2048, 3)))
     julia = bulb[:5] + (h.make_globals(julia=(0.35, -0.2), power=6.0),)
     probe_case("sd_julia_p6", "sdscene", julia, s, rng.normal(0, 0.8, (2048, 3)))
-    probe_case("sd_menger", "sdscene", tg.menger_scene(8, 8), s, rng.uniform(-1.5, 1.5, (4096, 3)))
+    probe_case("sd_menger", "sdscene", SB.menger_scene(8, 8), s, rng.uniform(-1.5, 1.5, (4096, 3)))
     pts = rng.uniform(-3.5, 3.5, (4096, 3))
     pts[:, 2] *= 0.4
     probe_case("sd_prims_a", "sdscene", subset(prims, range(0, 6)), s, pts)

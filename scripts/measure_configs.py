@@ -12,20 +12,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     import torch
-    import test_gpu_parity as tg
+    import helpers as h
+    import scene_builders as SB
     from raymarcher_amd import Renderer, Scene, abi, lib, scenes
     r = Renderer(0)
     L = lib()
-    S = tg.SCENES
+    S = SB.SCENES
     cases = []
     t = Scene(path=os.path.join(S, "simple", "unit_sphere.json")).tables(256, 256, load_textures=False)
-    t.textures = [tg.synthetic_textures()[1]]
+    t.textures = [SB.synthetic_textures()[1]]
     cases.append(("C1 unit_sphere 256x256, 64 steps, Phong", t, abi.default_settings(maxSteps=64), 256, 256))
     t = Scene(path=os.path.join(S, "simple", "unit_sphere.json")).tables(3840, 2160, load_textures=False)
-    t.textures = [tg.synthetic_textures()[1]]
+    t.textures = [SB.synthetic_textures()[1]]
     cases.append(("C1@4K unit_sphere.json (textured floor) 3840x2160, 256 steps", t, abi.default_settings(), 3840, 2160))
-    sk = tg.resource_case("skybox_reflect", 3840, 2160)
-    tk = tg.tables_of(sk[0])
+    sk = SB.resource_case("skybox_reflect", 3840, 2160)
+    tk = h.tables_of(sk[0])
     tk.skybox = sk[2]["skybox"]
     cases.append(("SKY sky box behind reflection + refraction 3840x2160", tk, sk[1], 3840, 2160))
     t = Scene(path=os.path.join(S, "lighting", "directional_light_2.json")).tables(1920, 1080)
@@ -40,10 +41,10 @@ def main():
     cases.append(("C3'' Mandelbulb p8 20 iters (reference constant) 3840x2160", scenes.mandelbulb(3840, 2160), abi.default_settings(), 3840, 2160))
     t = Scene(path=os.path.join(S, "simple", "volumetric.json")).tables(3840, 2160, far=2000.0)
     cases.append(("C4 volumetric.json as is (camera below the terrain, looking down) + terrain + cloud + sky 3840x2160", t,
-                  abi.default_settings(features=tg.ENV_ALL), 3840, 2160))
+                  abi.default_settings(features=SB.ENV_ALL), 3840, 2160))
     t = Scene(path=os.path.join(S, "simple", "volumetric.json")).tables(3840, 2160, far=2000.0)
-    t.camera = tg.env_scene(3840, 2160)[0]
-    cases.append(("C4 same scene, camera turned to the horizon: terrain + cloud + sky 3840x2160 (1 GPU)", t, abi.default_settings(features=tg.ENV_ALL), 3840, 2160))
+    t.camera = SB.env_scene(3840, 2160)[0]
+    cases.append(("C4 same scene, camera turned to the horizon: terrain + cloud + sky 3840x2160 (1 GPU)", t, abi.default_settings(features=SB.ENV_ALL), 3840, 2160))
     cases.append(("C5 unit_mengersponge.json, 5 levels, reflection 2 bounces 7680x4320 (1 GPU)",
                   Scene(path=os.path.join(S, "simple", "unit_mengersponge.json")).tables(7680, 4320),
                   abi.default_settings(mengerLevels=5, numReflection=2, enableReflection=1), 7680, 4320))
@@ -57,12 +58,12 @@ def main():
     cases.append(("RC2 reflections_complex.json 3840x2160, reflection 2 bounces + Perlin bump",
                   Scene(path=os.path.join(S, "lighting", "reflections_complex.json")).tables(3840, 2160),
                   abi.default_settings(enableReflection=1, numReflection=2), 3840, 2160))
-    sea = tg.resource_case("sea_sky", 3840, 2160)
-    ts = tg.tables_of(sea[0])
+    sea = SB.resource_case("sea_sky", 3840, 2160)
+    ts = h.tables_of(sea[0])
     ts.noise = sea[2]["noise"]
     cases.append(("sea + sky + reflective sphere 3840x2160", ts, sea[1], 3840, 2160))
-    al = tg.resource_case("area_light", 1920, 1080)
-    ta = tg.tables_of(al[0])
+    al = SB.resource_case("area_light", 1920, 1080)
+    ta = h.tables_of(al[0])
     ta.ltc1, ta.ltc2 = al[2]["ltc1"], al[2]["ltc2"]
     cases.append(("area light (LTC) + point light, reflection 1920x1080", ta, al[1], 1920, 1080))
     only = os.environ.get("RM_ONLY")  # e.g. RM_ONLY=C5: a single configuration (PMC passes profile one kernel at a time)

@@ -1,60 +1,21 @@
 """The specification of rm_render_gbuffer for the tests: tests/gbuffer_spec/rm_gbuffer_spec.c, which includes the oracle's source and
-restates the head of its render() with the oracle's own static functions, built on demand with gcc and oracle/Makefile's flags into
-tests/gbuffer_spec/_build/ and loaded with ctypes.  Nothing under oracle/ is touched.  Also the scenes that more than one G-buffer test
-module renders."""
+restates the head of its render() with the oracle's own static functions, built on demand and loaded with ctypes by
+helpers.load_spec.  Nothing under oracle/ is touched.  Also the float64 primary rays of the analytic checks."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import helpers as h
 from raymarcher_amd import abi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPEC_DIR = os.path.join(HERE, "gbuffer_spec")
-SPEC_SRC = os.path.join(SPEC_DIR, "rm_gbuffer_spec.c")
-SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_gbuffer_spec.so")
-# oracle/Makefile's CFLAGS (-ffp-contract=off: the numeric contract fuses only where rm_fma() is written)
-CFLAGS = ["-O3", "-std=c99", "-fPIC", "-mfma", "-mavx2", "-mf16c", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
-          "-Wextra", "-Wno-unused-function"]
-_SPEC = None
-SCENES = os.path.join(HERE, "golden", "scenes")
-
-
-def directional_light_2(W, H):
-    """lighting/directional_light_2.json through the library's loader, as the scene tuple the tests pass around."""
-    from raymarcher_amd import Scene
-    t = Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).tables(W, H)
-    return t.camera, t.objects, t.num_objects, t.lights, t.num_lights, t.globals_
-
-
-def moved_bulb_scene(W, H):
-    """helpers.scene_mandelbulb with the bulb translated and rotated: the general Mandelbulb class."""
-    scene = h.scene_mandelbulb(W, H)
-    model = h.translate(0.15, -0.1, 0.2) @ h.rotation((0.3, 1.0, -0.2), 0.7)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_MANDELBULB, model=model))
-    return (scene[0], objs, 1) + tuple(scene[3:])
+P = C.POINTER
+SIGNATURES = {"rmo_spec_gbuffer": (C.c_int, [P(abi.RmCamera), P(abi.RmObject), C.c_int, P(abi.RmGlobals), P(abi.RmSettings), C.c_int,
+                                             C.c_int, P(C.c_float), P(C.c_int32), P(C.c_float)])}
 
 
 def spec():
-    """ctypes handle of the spec library, rebuilt when a source it is made of is newer."""
-    global _SPEC
-    if _SPEC is None:
-        deps = [SPEC_SRC] + [os.path.join(h.ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
-               [os.path.join(h.ROOT, "include", "raymarcher_amd.h")]
-        if not os.path.exists(SPEC_SO) or os.path.getmtime(SPEC_SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(os.path.dirname(SPEC_SO), exist_ok=True)
-            tmp = f"{SPEC_SO}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
-            subprocess.check_call([os.environ.get("CC", "gcc")] + CFLAGS + ["-shared", "-o", tmp, SPEC_SRC, "-lm"])
-            os.replace(tmp, SPEC_SO)
-        lib = C.CDLL(SPEC_SO)
-        lib.rmo_spec_gbuffer.restype = C.c_int
-        lib.rmo_spec_gbuffer.argtypes = [C.POINTER(h.abi.RmCamera), C.POINTER(h.abi.RmObject), C.c_int, C.POINTER(h.abi.RmGlobals),
-                                         C.POINTER(h.abi.RmSettings), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
-                                         C.POINTER(C.c_float)]
-        _SPEC = lib
-    return _SPEC
+    """ctypes handle of the spec library (helpers.load_spec: rebuilt when a source it is made of is newer)."""
+    return h.load_spec("gbuffer", SIGNATURES)
 
 
 def spec_gbuffer(cam, objs, num_objects, g, s, W, H, position=True):

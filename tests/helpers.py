@@ -33,6 +33,87 @@ def fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+# ------------------------------------------------------------------ the specification libraries (tests/<name>_spec)
+# oracle/Makefile's CFLAGS (-ffp-contract=off: the numeric contract fuses only where rm_fma() is written)
+SPEC_CFLAGS = ["-O3", "-std=c99", "-fPIC", "-mfma", "-mavx2", "-mf16c", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall",
+               "-Wextra", "-Wno-unused-function"]
+_SPECS = {}
+
+
+def load_spec(name, signatures):
+    """ctypes handle of tests/<name>_spec/_build/librm_<name>_spec.so, built from tests/<name>_spec/rm_<name>_spec.c when that file,
+    the oracle's sources or the public header are newer, and loaded once per process.  signatures: {symbol: (restype, argtypes)}."""
+    if name not in _SPECS:
+        here = os.path.join(ROOT, "tests", f"{name}_spec")
+        src, so = os.path.join(here, f"rm_{name}_spec.c"), os.path.join(here, "_build", f"librm_{name}_spec.so")
+        deps = [src] + [os.path.join(ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
+               [os.path.join(ROOT, "include", "raymarcher_amd.h")]
+        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
+            os.makedirs(os.path.dirname(so), exist_ok=True)
+            tmp = f"{so}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
+            subprocess.check_call([os.environ.get("CC", "gcc")] + SPEC_CFLAGS + ["-shared", "-o", tmp, src, "-lm"])
+            os.replace(tmp, so)
+        lib = C.CDLL(so)
+        for symbol, (restype, argtypes) in signatures.items():
+            fn = getattr(lib, symbol)
+            fn.restype, fn.argtypes = restype, argtypes
+        _SPECS[name] = lib
+    return _SPECS[name]
+
+
+# ------------------------------------------------------------------ tables for the renderer, the one bit comparator
+def tables_of(scene, res=None, **resources):
+    """SceneTables of the tests' scene tuple (camera, objects, count, lights, count, globals, …) with the resources of `res` (a
+    dict) and of the keywords set on it.  A NumPy array that is not writeable (a shared, cached one) is copied first:
+    Renderer._upload hands the array to torch.from_numpy.  A writeable one is passed on as it is."""
+    from raymarcher_amd.render import SceneTables
+    t = SceneTables(*scene[:6])
+    for k, v in {**(res or {}), **resources}.items():
+        setattr(t, k, v.copy() if isinstance(v, np.ndarray) and not v.flags.writeable else v)
+    return t
+
+
+def bits(a):
+    """The words of an array of 4-byte elements as they are: never a conversion by value."""
+    a = np.ascontiguousarray(a)
+    assert a.dtype.itemsize == 4, f"bits() of {a.dtype}: not a 4-byte type"
+    return a.view(np.uint32)
+
+
+def assert_bit_equal(got, want, what):
+    """Word-for-word equality of two arrays of 4-byte elements with the same shape (+0 is not −0, a NaN equals only itself)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype.itemsize == 4 and want.dtype.itemsize == 4, f"{what}: {got.dtype} against {want.dtype}: not 4-byte types"
+    assert got.shape == want.shape, f"{what}: shape {got.shape} against {want.shape}"
+    bad = bits(got) != bits(want)
+    if bad.any():
+        delta = ""
+        if got.dtype.kind == "f" and want.dtype.kind == "f":
+            with np.errstate(all="ignore"):
+                diff = np.abs(got.astype(np.float64) - want.astype(np.float64))
+            diff = diff[~np.isnan(diff)]
+            delta = f" max |Δ| = {diff.max() if diff.size else np.nan:.3e};"
+        raise AssertionError(f"{what}: {bad.sum()} of {bad.size} words differ;{delta} first at {np.argwhere(bad)[:5].tolist()}")
+
+
+def with_globals(g, **over):
+    """A copy of an RmGlobals with fields replaced (julia=(x, y) sets juliaSeed)."""
+    g2 = abi.RmGlobals()
+    C.memmove(C.byref(g2), C.byref(g), C.sizeof(g))
+    for k, v in over.items():
+        if k == "julia":
+            g2.juliaSeed[0], g2.juliaSeed[1] = v
+        else:
+            setattr(g2, k, v)
+    return g2
+
+
+def table(items, struct=abi.RmObject):
+    """(ctypes array of at least one element, count) of a list of structs."""
+    items = list(items)
+    return (struct * max(len(items), 1))(*items), len(items)
+
+
 # ------------------------------------------------------------------ numpy camera (camera.cpp:74-133)
 def camera_numpy(pos, look, up, height_angle_rad, W, H, near=0.1, far=100.0):
     f = np.float32

@@ -1,26 +1,17 @@
 """The specification of rm_shade_rays_layers and rm_trace_rays_layers for the tests: tests/layers_spec/rm_layers_spec.c, which
 includes the oracle's source and calls its own render, envLayers, seaRender, terrainRender, seaMapHeight, getSeaNormal and
-terrainNormal, built on demand with gcc and oracle/Makefile's flags into tests/layers_spec/_build/ and loaded with ctypes, the way
-shade_helpers.spec() is.  Nothing under oracle/ is touched.  Also the layer scenes and feature masks that more than one layers test
-module uses: the builders of tests/test_gpu_parity.py's env_scene and sea_scene restated here, so that a test without a GPU does
-not import a GPU test module."""
+terrainNormal, built on demand and loaded with ctypes by helpers.load_spec.  Nothing under oracle/ is touched.  Also the layer cases
+(scene_builders' env_scene and sea_scene) and feature masks that more than one layers test module uses."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-import gbuffer_helpers as G
 import helpers as h
+import scene_builders as SB
 import trace_helpers as T
 from raymarcher_amd import abi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPEC_DIR = os.path.join(HERE, "layers_spec")
-SPEC_SRC = os.path.join(SPEC_DIR, "rm_layers_spec.c")
-SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_layers_spec.so")
-_SPEC = None
 PATH_SHADE_LAYERS, PATH_TRACE_LAYERS = 14, 15  # rm_debug_last_path() of a launch of rm_shade_rays_layers / rm_trace_rays_layers
 HIT_SEA, HIT_TERRAIN = -3, -4
 SIZES_WH = ((64, 36), (37, 23))
@@ -32,28 +23,18 @@ TERRAIN, CLOUD, SEA, BUMP = abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_
 LAYER_BITS = TERRAIN | CLOUD | SEA
 
 
+P = C.POINTER
+SIGNATURES = {
+    "rmo_spec_shade_layers": (C.c_int, [P(abi.RmObject), C.c_int, P(abi.RmLight), C.c_int, P(abi.RmGlobals), P(abi.RmSettings),
+                                        P(abi.RmResources), P(C.c_float), C.c_int, C.c_float, C.c_int, P(C.c_float), P(C.c_float)]),
+    "rmo_spec_trace_layers": (C.c_int, [P(abi.RmObject), C.c_int, P(abi.RmGlobals), P(abi.RmSettings), P(C.c_float), C.c_int, C.c_int,
+                                        C.c_uint, P(C.c_float)]),
+}
+
+
 def spec():
-    """ctypes handle of the spec library, rebuilt when a source it is made of is newer."""
-    global _SPEC
-    if _SPEC is None:
-        deps = [SPEC_SRC] + [os.path.join(h.ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
-               [os.path.join(h.ROOT, "include", "raymarcher_amd.h")]
-        if not os.path.exists(SPEC_SO) or os.path.getmtime(SPEC_SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(os.path.dirname(SPEC_SO), exist_ok=True)
-            tmp = f"{SPEC_SO}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
-            subprocess.check_call([os.environ.get("CC", "gcc")] + G.CFLAGS + ["-shared", "-o", tmp, SPEC_SRC, "-lm"])
-            os.replace(tmp, SPEC_SO)
-        lib = C.CDLL(SPEC_SO)
-        Ptr = C.POINTER
-        lib.rmo_spec_shade_layers.restype = C.c_int
-        lib.rmo_spec_shade_layers.argtypes = [Ptr(abi.RmObject), C.c_int, Ptr(abi.RmLight), C.c_int, Ptr(abi.RmGlobals),
-                                              Ptr(abi.RmSettings), Ptr(abi.RmResources), Ptr(C.c_float), C.c_int, C.c_float, C.c_int,
-                                              Ptr(C.c_float), Ptr(C.c_float)]
-        lib.rmo_spec_trace_layers.restype = C.c_int
-        lib.rmo_spec_trace_layers.argtypes = [Ptr(abi.RmObject), C.c_int, Ptr(abi.RmGlobals), Ptr(abi.RmSettings), Ptr(C.c_float), C.c_int,
-                                              C.c_int, C.c_uint, Ptr(C.c_float)]
-        _SPEC = lib
-    return _SPEC
+    """ctypes handle of the spec library (helpers.load_spec: rebuilt when a source it is made of is newer)."""
+    return h.load_spec("layers", SIGNATURES)
 
 
 def spec_shade_layers(scene, s, rays, far, image_width, res=None, expect=0):
@@ -80,56 +61,33 @@ def spec_trace_layers(objs, num_objects, g, s, rays, image_width, mode="closest"
     return hits
 
 
-# ---------------------------------------------------------------- the scenes (tests/test_gpu_parity.py's builders, restated)
-def env_scene(W, H, pos=(0, 500, 5), look=(0.3, 0.12, -1)):
-    """Terrain + volumetric cloud + sky, with a reflective and transparent torus floating in front of the camera so that secondary
-    rays also see the layers (frag:2506-2518, 2555-2567)."""
-    cam = h.make_camera(pos, look, (0, 1, 0), 70.0, W, H, far=2000.0)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_TORUS, model=h.translate(8, pos[1] + 3, -30) @ h.scale(12, 12, 12),
-                                            scale_factor=12, ambient=(.3, .3, .3), specular=(1, 1, 1), shininess=50,
-                                            reflective=(.6, .6, .6), transparent=(.5, .5, .5), ior=1.3))
-    lights = (abi.RmLight * 1)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (3, 2.6, 2.0), (-0.577, -0.577, 0.577)))
-    return cam, objs, 1, lights, 1, h.make_globals()
-
-
-def sea_scene(W, H):
-    cam = h.make_camera((0, 3.5, 6), (0, -0.35, -1), (0, 1, 0), 50.0, W, H, far=100.0)
-    objs = (abi.RmObject * 1)(
-        h.make_object(abi.RM_SPHERE, model=h.translate(0, 1.8, -1.5) @ h.scale(2, 2, 2), scale_factor=2.0, ambient=(.2, .2, .2),
-                      diffuse=(.8, .3, .2), specular=(1, 1, 1), shininess=20, reflective=(.6, .6, .6)))
-    lights = (abi.RmLight * 1)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.4, -1, -0.3)))
-    return cam, objs, 1, lights, 1, h.make_globals(itime=0.7)
+# ---------------------------------------------------------------- the cases
+# name → (scene builder, settings overrides, resources): env_scene with reflection and refraction on, sea_scene with reflection on
+CASES = {
+    "env_sky_terrain": (SB.env_scene, {"features": SKY | TERRAIN, "enableReflection": 1, "enableRefraction": 1}, False),
+    "env_cloud_dark": (SB.env_scene, {"features": CLOUD | DARK, "enableReflection": 1, "enableRefraction": 1}, False),
+    "env_all": (SB.env_scene, {"features": SKY | TERRAIN | CLOUD | BUMP, "enableReflection": 1, "enableRefraction": 1}, False),
+    "env_all_sea": (SB.env_scene, {"features": SKY | TERRAIN | CLOUD | BUMP | SEA, "enableReflection": 1, "enableRefraction": 1}, True),
+    "sea_sky": (SB.sea_scene, {"features": SEA | SKY, "enableReflection": 1}, True),
+    "sea_terrain": (SB.sea_scene, {"features": SKY | TERRAIN | SEA, "enableReflection": 1}, True),
+}
+NAMES = list(CASES)
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic_noise():
-    """256×256 RGBA8 with different channels and a few saturated texels (test_gpu_parity.synthetic_noise's recipe and seed)."""
-    rng = np.random.default_rng(5)
-    a = rng.integers(0, 256, (256, 256, 4), dtype=np.uint8)
-    a[rng.integers(0, 256, 900), rng.integers(0, 256, 900), :2] = 255
-    a[..., 3] = 255
-    a = np.ascontiguousarray(a)
+def shared_noise():
+    """scene_builders.synthetic_noise(), built once and handed out read-only: the cached cases share it, and tables_of copies it
+    before the renderer uploads it."""
+    a = SB.synthetic_noise()
     a.setflags(write=False)
     return a
-
-
-# name → (scene builder, settings overrides, resources): env_scene with reflection and refraction on, sea_scene with reflection on
-CASES = {
-    "env_sky_terrain": (env_scene, {"features": SKY | TERRAIN, "enableReflection": 1, "enableRefraction": 1}, False),
-    "env_cloud_dark": (env_scene, {"features": CLOUD | DARK, "enableReflection": 1, "enableRefraction": 1}, False),
-    "env_all": (env_scene, {"features": SKY | TERRAIN | CLOUD | BUMP, "enableReflection": 1, "enableRefraction": 1}, False),
-    "env_all_sea": (env_scene, {"features": SKY | TERRAIN | CLOUD | BUMP | SEA, "enableReflection": 1, "enableRefraction": 1}, True),
-    "sea_sky": (sea_scene, {"features": SEA | SKY, "enableReflection": 1}, True),
-    "sea_terrain": (sea_scene, {"features": SKY | TERRAIN | SEA, "enableReflection": 1}, True),
-}
-NAMES = list(CASES)
 
 
 @functools.lru_cache(maxsize=None)
 def case(name, W=64, H=36):
     """(scene, settings, resources dict) of a case; W, H only shape the camera."""
     build, over, noise = CASES[name]
-    return build(W, H), abi.default_settings(**over), ({"noise": synthetic_noise()} if noise else {})
+    return build(W, H), abi.default_settings(**over), ({"noise": shared_noise()} if noise else {})
 
 
 def without_layers(s):
@@ -162,7 +120,7 @@ def camera_position(name):
 def seeded_rays(name, n=N):
     """n seeded rays (T.seeded_rays: every kind, invalid ones in every wave) placed around the case's camera position, with a
     radius that reaches the layers from there (read-only, shared)."""
-    radius = 40.0 if CASES[name][0] is env_scene else 4.0
+    radius = 40.0 if CASES[name][0] is SB.env_scene else 4.0
     rays = T.seeded_rays(np.random.default_rng(4000 + NAMES.index(name)), n, camera_position(name), radius)
     rays.setflags(write=False)
     return rays
@@ -179,20 +137,12 @@ def terrain_height(x, z):
 
 def sky_of(rays):
     """getSky(rd) of each ray: the specification's colour over an empty table with SKY alone."""
-    objs, _ = T.table([])
+    objs, _ = h.table([])
     scene = (None, objs, 0, None, 0, h.make_globals())
     return spec_shade_layers(scene, abi.default_settings(features=SKY), rays, 100.0, 1)[0][:, 0:3]
 
 
-def tables_of(scene, res=None):
-    from raymarcher_amd.render import SceneTables
-    t = SceneTables(*scene[:6])
-    for k, v in (res or {}).items():
-        setattr(t, k, np.array(v) if isinstance(v, np.ndarray) else v)
-    return t
-
-
-ids_of, bits, assert_bits = T.ids_of, T.bits, T.assert_bits
+tables_of, ids_of, bits, assert_bits = h.tables_of, T.ids_of, h.bits, h.assert_bit_equal
 
 
 def assert_spec(got, want, what, id_word=None):

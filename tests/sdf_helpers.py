@@ -14,27 +14,13 @@ import sdf_mesh_spec as S
 from raymarcher_amd import abi
 
 f32 = np.float32
+bits, assert_bits = h.bits, h.assert_bit_equal
 HERE = os.path.dirname(os.path.abspath(__file__))
 CPU_SRC = os.path.join(HERE, "sdf_mesh_spec", "rm_sdf_mesh_cpu.cpp")
 CPU_DEPS = [CPU_SRC, os.path.join(h.ROOT, "raymarcher_amd", "csrc", "rm_surface_nets.h")]
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} against {want.shape} {want.dtype}"
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} words differ, the first at {tuple(int(v) for v in np.argwhere(bad)[0])}"
-
-
 # ---------------------------------------------------------------- object tables
-def table(*objs):
-    return (abi.RmObject * len(objs))(*objs), len(objs)
-
-
 def scene(name):
     """(objs, numObjects, globals, settings) of a named table."""
     s = abi.default_settings()
@@ -67,7 +53,7 @@ def scene(name):
         g = h.make_globals(power=6.0)
     else:
         raise KeyError(name)
-    objs, no = table(*objs)
+    objs, no = h.table(objs)
     return objs, no, g, s
 
 

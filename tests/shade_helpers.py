@@ -1,51 +1,31 @@
 """The specification of rm_shade_rays for the tests: tests/shade_spec/rm_shade_spec.c, which includes the oracle's source and restates
-its shadePixel from the background colour on for a given (ro, rd, far), built on demand with gcc and oracle/Makefile's flags into
-tests/shade_spec/_build/ and loaded with ctypes, the way trace_helpers.spec() is.  Nothing under oracle/ is touched.  Also the
-scenes, one or more per kernel class, that more than one shade test module uses."""
+its shadePixel from the background colour on for a given (ro, rd, far), built on demand and loaded with ctypes by
+helpers.load_spec.  Nothing under oracle/ is touched.  Also the scenes, one or more per kernel class, that more than one shade test
+module uses."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-import gbuffer_helpers as G
 import helpers as h
-import test_gpu_parity as P
-import trace_helpers as T
+import scene_builders as SB
 from raymarcher_amd import abi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPEC_DIR = os.path.join(HERE, "shade_spec")
-SPEC_SRC = os.path.join(SPEC_DIR, "rm_shade_spec.c")
-SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_shade_spec.so")
-_SPEC = None
+P = C.POINTER
+SIGNATURES = {"rmo_spec_shade": (C.c_int, [P(abi.RmObject), C.c_int, P(abi.RmLight), C.c_int, P(abi.RmGlobals), P(abi.RmSettings),
+                                           P(abi.RmResources), P(C.c_float), C.c_int, C.c_float, P(C.c_float), P(C.c_float)])}
 PATH_SHADE = 13  # rm_debug_last_path() of a launch of rm_shade_rays
+tables_of, assert_bits = h.tables_of, h.assert_bit_equal
 
 
 def spec():
-    """ctypes handle of the spec library, rebuilt when a source it is made of is newer."""
-    global _SPEC
-    if _SPEC is None:
-        deps = [SPEC_SRC] + [os.path.join(h.ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
-               [os.path.join(h.ROOT, "include", "raymarcher_amd.h")]
-        if not os.path.exists(SPEC_SO) or os.path.getmtime(SPEC_SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(os.path.dirname(SPEC_SO), exist_ok=True)
-            tmp = f"{SPEC_SO}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
-            subprocess.check_call([os.environ.get("CC", "gcc")] + G.CFLAGS + ["-shared", "-o", tmp, SPEC_SRC, "-lm"])
-            os.replace(tmp, SPEC_SO)
-        lib = C.CDLL(SPEC_SO)
-        Ptr = C.POINTER
-        lib.rmo_spec_shade.restype = C.c_int
-        lib.rmo_spec_shade.argtypes = [Ptr(abi.RmObject), C.c_int, Ptr(abi.RmLight), C.c_int, Ptr(abi.RmGlobals), Ptr(abi.RmSettings),
-                                       Ptr(abi.RmResources), Ptr(C.c_float), C.c_int, C.c_float, Ptr(C.c_float), Ptr(C.c_float)]
-        _SPEC = lib
-    return _SPEC
+    """ctypes handle of the spec library (helpers.load_spec: rebuilt when a source it is made of is newer)."""
+    return h.load_spec("shade", SIGNATURES)
 
 
 def spec_shade(scene, s, rays, far, res=None, expect=0):
     """(colour, bright), float32 (n, 4) each, of `rays` (float32 (n, 8)) by the specification.  scene: the tests' tuple (camera,
-    objects, count, lights, count, globals) — the camera is not read; res: the resources dict of test_gpu_parity.resource_case."""
+    objects, count, lights, count, globals) — the camera is not read; res: the resources dict of scene_builders.resource_case."""
     rays = np.ascontiguousarray(rays, dtype=np.float32)
     col = np.full((len(rays), 4), np.nan, dtype=np.float32)
     br = np.full((len(rays), 4), np.nan, dtype=np.float32)
@@ -55,13 +35,6 @@ def spec_shade(scene, s, rays, far, res=None, expect=0):
                                h.fptr(br))
     assert st == expect, f"spec status {st}"
     return col, br
-
-
-def tables_of(scene, res=None):
-    t = P.tables_of(scene)
-    for k, v in (res or {}).items():
-        setattr(t, k, v)
-    return t
 
 
 def _with_materials(scene, reflective):
@@ -75,14 +48,14 @@ def _with_materials(scene, reflective):
 
 
 # name → ((BULB, ENV, TEX, SEC) of the kernel class the launcher must pick, builder(W, H) → (scene, settings, resources)).  BULB: 0 the
-# table walk, 1 the general bulb, 2 the plain bulb.  One scene or more per class of dispatch_class, from test_gpu_parity's builders;
+# table walk, 1 the general bulb, 2 the plain bulb.  One scene or more per class of dispatch_class, from scene_builders;
 # every bulb case has hard shadows from directional lights only, the shadow pool's case.
 def _cases():
     SKY, WB = abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_WHITE_BACKGROUND
     ds = abi.default_settings
 
     def menger(W, H, refl):
-        sc = P.menger_scene(W, H)
+        sc = SB.menger_scene(W, H)
         return (sc[:5] + (h.make_globals(itime=7.5),)), ds(mengerLevels=3, enableReflection=refl), {}
 
     def bulb(builder, refl):
@@ -93,30 +66,30 @@ def _cases():
 
     def resource(name, **over):
         def make(W, H):
-            scene, s, res = P.resource_case(name, W, H)
+            scene, s, res = SB.resource_case(name, W, H)
             for k, v in over.items():
                 setattr(s, k, v)
             return scene, s, res
         return make
 
     def textured(feat):
-        return lambda W, H: (P.textured_scene(W, H), ds(features=feat), {"textures": P.synthetic_textures()})
+        return lambda W, H: (SB.textured_scene(W, H), ds(features=feat), {"textures": SB.synthetic_textures()})
 
     def empty(W, H):
         cam = h.make_camera((0, 0, 4.5), (0, 0, -4.5), (0, 1, 0), 30.0, W, H)
-        objs, _ = T.table([])
+        objs, _ = h.table([])
         return (cam, objs, 0, None, 0, h.make_globals()), ds(), {}
 
     return {
-        "generic_nosec": ((0, 0, 0, 0), lambda W, H: (G.directional_light_2(W, H), ds(enableSoftShadow=1, enableAmbientOcclusion=1), {})),
-        "generic_sec": ((0, 0, 0, 1), lambda W, H: (P.reflect_refract_scene(W, H),
+        "generic_nosec": ((0, 0, 0, 0), lambda W, H: (SB.directional_light_2(W, H), ds(enableSoftShadow=1, enableAmbientOcclusion=1), {})),
+        "generic_sec": ((0, 0, 0, 1), lambda W, H: (SB.reflect_refract_scene(W, H),
                                                     ds(enableReflection=1, enableRefraction=1, numReflection=2), {})),
         "menger_sec": ((0, 0, 0, 1), lambda W, H: menger(W, H, 1)),
         "menger_nosec": ((0, 0, 0, 0), lambda W, H: menger(W, H, 0)),
         "plain_bulb_nosec": ((2, 0, 0, 0), bulb(h.scene_mandelbulb, 0)),
         "plain_bulb_sec": ((2, 0, 0, 1), bulb(h.scene_mandelbulb, 1)),
-        "moved_bulb_nosec": ((1, 0, 0, 0), bulb(G.moved_bulb_scene, 0)),
-        "moved_bulb_sec": ((1, 0, 0, 1), bulb(G.moved_bulb_scene, 1)),
+        "moved_bulb_nosec": ((1, 0, 0, 0), bulb(SB.moved_bulb_scene, 0)),
+        "moved_bulb_sec": ((1, 0, 0, 1), bulb(SB.moved_bulb_scene, 1)),
         "tex_nosec": ((0, 0, 1, 0), textured(WB)),
         "tex_sec": ((0, 0, 1, 1), resource("skybox_reflect")),
         "area_light": ((0, 0, 1, 1), resource("area_light")),
@@ -167,5 +140,3 @@ def normalised(rays):
     return out
 
 
-def assert_bits(got, want, what):
-    P.assert_bit_equal(np.asarray(got), np.asarray(want), what)

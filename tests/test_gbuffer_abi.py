@@ -12,6 +12,7 @@ import pytest
 
 import gbuffer_helpers as G
 import helpers as h
+import scene_builders as SB
 from raymarcher_amd import abi, lib
 from raymarcher_amd._lib import LIB_PATH, SIGNATURES
 
@@ -151,7 +152,7 @@ def test_object_validation_and_outputs():
 @pytest.mark.parametrize("name", ["directional_light_2", "mandelbulb"])
 def test_spec_hits_what_the_oracle_hits(name):
     W, H = 64, 36
-    scene = G.directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
+    scene = SB.directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
     s = abi.default_settings()
     _, cnt = h.oracle_render(scene, s, W, H, counters=True)
     nd, ids, pos = G.spec_gbuffer(scene[0], scene[1], scene[2], scene[5], s, W, H)

@@ -40,7 +40,7 @@ import pytest
 import arbiter_numpy as an
 import gbuffer_helpers as G
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
 from raymarcher_amd import abi
 from raymarcher_amd.render import Scene, SceneTables
 
@@ -81,12 +81,12 @@ def random_table_scene(seed, W, H):
 
 
 def sierpinski_scene(W, H):
-    t = Scene(path=os.path.join(G.SCENES, "simple", "unit_sierpinski.json")).tables(W, H)
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "unit_sierpinski.json")).tables(W, H)
     return t.camera, t.objects, t.num_objects, t.lights, t.num_lights, t.globals_
 
 
 def _bulb_p7(W, H):
-    sc = G.moved_bulb_scene(W, H)
+    sc = SB.moved_bulb_scene(W, H)
     g = abi.RmGlobals()
     C.memmove(C.byref(g), C.byref(sc[5]), C.sizeof(g))
     g.power = 7.0
@@ -94,13 +94,13 @@ def _bulb_p7(W, H):
 
 
 def _menger(W, H):
-    sc = P.menger_scene(W, H)
+    sc = SB.menger_scene(W, H)
     sc[5].iTime = 7.5
     return sc
 
 
 RANDOM_SEEDS = (2, 7, 10, 12, 13, 15)  # 2 and 7: tables whose marches overshoot (see the docstring)
-TABLES = {"directional_light_2": G.directional_light_2, "area_light": P.area_light_scene, "all_types": all_types_scene,
+TABLES = {"directional_light_2": SB.directional_light_2, "area_light": SB.area_light_scene, "all_types": all_types_scene,
           "sierpinski": sierpinski_scene, **{f"random_{s}": (lambda W, H, s=s: random_table_scene(s, W, H)) for s in RANDOM_SEEDS}}
 CASES = [(f"{name}{'+bump' if bump else ''}", build, abi.default_settings(features=WHITE | (BUMP if bump else 0)),
           "sierpinski" if name == "sierpinski" else ("bumped primitives" if bump else "primitives"))
@@ -209,7 +209,7 @@ def test_the_arbiter_reads_neither_the_spec_nor_the_oracle():
 def test_emissive_rectangle_and_miss_in_the_arbiter():
     """The arbiter's own statement of the two rules a shared restatement would hide: an emissive rectangle reports its index, a miss
     is (0, 0, 0), far, −1, (0, 0, 0, 0); an empty table misses everywhere."""
-    scene = P.area_light_scene(W, H)
+    scene = SB.area_light_scene(W, H)
     assert scene[1][3].isEmissive == 1
     n, d, ids, pos, _ = an.gbuffer_frame(SceneTables(*scene), abi.default_settings(), W, H)
     assert (ids == 3).sum() > 10

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as P
-from test_gpu_batch import assert_bit_equal, tables_of, with_globals
+import scene_builders as SB
+from helpers import assert_bit_equal, tables_of, with_globals
 from raymarcher_amd import abi, lib
 from raymarcher_amd.render import lens_cameras, shutter_globals
 
@@ -165,7 +165,7 @@ def test_depth_of_field_scenefile_with_its_own_lens(renderer, n, frames):
     t = sc.tables(W, H)
     radius, focus = sc.lens()
     assert (np.float32(radius), np.float32(focus)) == (np.float32(0.008), np.float32(3.0))
-    scene = P._scene_tuple(t)
+    scene = SB.scene_tuple(t)
     cams = lens_frames(sc.camera_data(), W, H, radius, focus, n, frames, step=0.4)
     for s in (abi.default_settings(), abi.default_settings(enableReflection=1, enableSoftShadow=1)):
         acc_vs_oracle(renderer, scene, s, W, H, cams, t.globals_, n, textures=t.textures, what="depth_of_field.json")
@@ -175,7 +175,7 @@ def test_depth_of_field_scenefile_with_its_own_lens(renderer, n, frames):
 def test_primitive_table_walk_and_its_secondary_rays(renderer, n):
     """The plain table walk (soft shadows + AO), then the same table with reflection and refraction, two bounces (SEC)."""
     W, H = 97, 53
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     cd = camera_data((0, 1.2, 5), (0, -0.2, -1), angle_deg=40.0)
     frames = 3 if n == 2 else 1
     cams = lens_frames(cd, W, H, 0.1, 5.0, n, frames)
@@ -188,12 +188,12 @@ def test_primitive_table_walk_and_its_secondary_rays(renderer, n):
 
 def test_textures_sky_box_and_area_light(renderer):
     W, H, n = 97, 53, 3
-    scene = P.textured_scene(W, H)
+    scene = SB.textured_scene(W, H)
     s = abi.default_settings(features=abi.RM_FEAT_WHITE_BACKGROUND, enableSoftShadow=1, enableSkyBox=1)
     cams = lens_frames(camera_data((0.4, 2.2, 5.5), (-0.05, -0.35, -1), angle_deg=42.0), W, H, 0.15, 5.5, n, 2)
-    acc_vs_oracle(renderer, scene, s, W, H, cams, scene[5], n, textures=P.synthetic_textures(), what="textured + sky box",
-                  skybox=P.synthetic_skybox())
-    scene, s, res = P.resource_case("area_light", W, H)
+    acc_vs_oracle(renderer, scene, s, W, H, cams, scene[5], n, textures=SB.synthetic_textures(), what="textured + sky box",
+                  skybox=SB.synthetic_skybox())
+    scene, s, res = SB.resource_case("area_light", W, H)
     cams = lens_frames(camera_data((0, 1.6, 5.5), (0, -0.2, -1), angle_deg=45.0), W, H, 0.1, 5.0, 5, 1)
     acc_vs_oracle(renderer, scene, s, W, H, cams, scene[5], 5, what="area light", **res)
 
@@ -202,20 +202,20 @@ def test_textures_sky_box_and_area_light(renderer):
 def test_terrain_and_clouds_through_a_shutter(renderer, n):
     """ENV: the layers move with iTime; one camera, the shutter open for 2 s per frame, frames 4 s apart."""
     W, H = 97, 53
-    scene = P.env_scene(W, H)
+    scene = SB.env_scene(W, H)
     frames = 2
     cam = h.make_camera((0, 500, 5), (0.3, 0.12, -1), (0, 1, 0), 70.0, W, H, far=2000.0)
     cams = [cam] * (frames * n)
     globs = [g for f in range(frames) for g in shutter_globals(scene[5], 4.0 * f, 4.0 * f + 2.0, n)]
     assert len({g.iTime for g in globs}) == frames * n
-    out = acc_vs_oracle(renderer, scene, abi.default_settings(features=P.ENV_ALL, enableReflection=1), W, H, cams, globs, n,
+    out = acc_vs_oracle(renderer, scene, abi.default_settings(features=SB.ENV_ALL, enableReflection=1), W, H, cams, globs, n,
                         what="terrain+cloud shutter")
     assert np.abs(out[0] - out[1]).max() > 1e-3  # time moves the picture
 
 
 def test_sea_and_night_sky_through_a_shutter(renderer):
     W, H, n = 64, 40, 5
-    scene, s, res = P.resource_case("sea_sky", W, H)
+    scene, s, res = SB.resource_case("sea_sky", W, H)
     cams = [h.make_camera((0, 3.5, 6), (0, -0.35, -1), (0, 1, 0), 50.0, W, H)] * n
     acc_vs_oracle(renderer, scene, s, W, H, cams, shutter_globals(scene[5], 0.7, 1.6, n), n, what="sea + sky shutter", **res)
 
@@ -226,7 +226,7 @@ def test_menger_sponge_motion_blur(renderer, n):
     request does not reach this entry point."""
     L = lib()
     W, H = 97, 53
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     frames = 3 if n == 2 else 1
     cams = [h.make_camera((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), (0, 1, 0), 30.0, W, H)] * (frames * n)
     # the sponge opens while −cos(iTime / 2) crosses ±0.2 (frag:1052): iTime from 2.74 to 3.54
@@ -247,27 +247,27 @@ def test_menger_sponge_motion_blur(renderer, n):
 # ---------------------------------------------------------------- 2. globals: one for all, or one per sub-frame
 def test_one_globals_equals_the_same_globals_per_sub_frame(renderer):
     W, H, n, frames = 64, 40, 3, 3
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableReflection=1)
     cams = lens_frames(camera_data((0, 1.2, 5), (0, -0.2, -1), angle_deg=40.0), W, H, 0.1, 5.0, n, frames)
     one = renderer.render_accumulated(tables_of(scene), s, W, H, cams, n, globals_=scene[5])
     per = renderer.render_accumulated(tables_of(scene), s, W, H, cams, n, globals_=[with_globals(scene[5]) for _ in cams])
-    assert P._ieq(one, per)
+    assert SB.ieq(one, per)
     none = renderer.render_accumulated(tables_of(scene), s, W, H, cams, n)  # tables.globals_
-    assert P._ieq(one, none)
+    assert SB.ieq(one, none)
 
 
 # ---------------------------------------------------------------- 3. n = 1 is render_batch
 def test_one_sub_frame_is_render_batch(renderer):
     W, H = 77, 45
-    for scene, s in ((P.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1)),
+    for scene, s in ((SB.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1)),
                      (h.scene_mandelbulb(W, H), abi.default_settings(fractalIters=12))):
         cams = lens_frames(camera_data((0, 1.2, 5), (0, -0.2, -1), angle_deg=40.0), W, H, 0.0, 5.0, 1, 3, step=0.3)
         globs = [with_globals(scene[5], iTime=0.25 * f) for f in range(3)]
         a, ab = renderer.render_accumulated(tables_of(scene), s, W, H, cams, 1, globals_=globs, bright=True)
         assert lib().rm_debug_last_path() == 9
         b, bb = renderer.render_batch(tables_of(scene), s, W, H, cams, globals_=globs, bright=True)
-        assert P._ieq(a, b) and P._ieq(ab, bb)
+        assert SB.ieq(a, b) and SB.ieq(ab, bb)
 
 
 def test_two_equal_sub_frames_are_the_frame(renderer):
@@ -278,7 +278,7 @@ def test_two_equal_sub_frames_are_the_frame(renderer):
     one, one_b = renderer.render(tables_of(scene), s, W, H, bright=True)
     out, br = renderer.render_accumulated(tables_of(scene), s, W, H, [scene[0]] * 6, 2, bright=True)
     for f in range(3):
-        assert P._ieq(out[f], one) and P._ieq(br[f], one_b), f
+        assert SB.ieq(out[f], one) and SB.ieq(br[f], one_b), f
 
 
 # ---------------------------------------------------------------- 4. write coverage
@@ -287,7 +287,7 @@ def test_two_equal_sub_frames_are_the_frame(renderer):
 def test_every_word_is_written_and_nothing_else(renderer, W, H, frames):
     n = 3
     for scene, s in ((h.scene_mandelbulb(W, H), abi.default_settings(fractalIters=12)),
-                     (P.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2))):
+                     (SB.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2))):
         t = tables_of(scene)
         cams = [scene[0]] * (frames * n)
         out, c1 = h.guarded((frames, H, W, 4), device=renderer.device)
@@ -300,17 +300,17 @@ def test_every_word_is_written_and_nothing_else(renderer, W, H, frames):
         spare = h.Guarded((frames, H, W, 4), renderer.torch.float32, h.FLOAT_POISON, renderer.device)
         renderer.render_accumulated(t, s, W, H, cams, n, out=out2)
         c3()
-        assert P._ieq(out2, out)
+        assert SB.ieq(out2, out)
         assert bool(spare._unwritten(spare.buf).all()), "a launch without d_bright wrote outside d_rgba"
         for f in range(1, frames):
-            assert P._ieq(out[f], out[0]) and P._ieq(br[f], br[0])
+            assert SB.ieq(out[f], out[0]) and SB.ieq(br[f], br[0])
 
 
 # ---------------------------------------------------------------- 5. schedule and state
 def test_timing_counts_one_launch_all_stage_1(renderer):
     L = lib()
     W, H, n = 64, 40, 4
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     s = abi.default_settings(mengerLevels=3)
     cams = [scene[0]] * (3 * n)
     try:
@@ -354,7 +354,7 @@ def test_accumulated_launch_leaves_the_single_frame_tuners_alone(renderer):
         assert plain[0] == 0 and plain[-1] > 0, plain  # it settles, then splits
         again, frames2 = sequence(acc_after=plain.index(plain[-1]) + 1)
         assert again == plain
-        assert all(P._ieq(a, frames[0]) for a in frames + frames2)
+        assert all(SB.ieq(a, frames[0]) for a in frames + frames2)
     finally:
         L.rm_debug_set_tile_shape(-1)
         L.rm_debug_set_light_split(-1)
@@ -422,7 +422,7 @@ def test_full_size_1080p_depth_of_field_16_lens_samples(renderer):
     assert_bit_equal(br[0], accumulate(sub_b.cpu().numpy()), "1080p depth of field bright against render_batch reduced")
     rng = np.random.default_rng(20261017)
     for r0 in sorted(int(r) for r in rng.integers(0, H - 4, 3)):
-        ref, ref_b = oracle_accumulated(P._scene_tuple(t), cams, t.globals_, s, W, H, n, rows=(r0, r0 + 4), textures=t.textures)
+        ref, ref_b = oracle_accumulated(SB.scene_tuple(t), cams, t.globals_, s, W, H, n, rows=(r0, r0 + 4), textures=t.textures)
         assert_bit_equal(out[0][r0:r0 + 4], ref[0], f"1080p depth of field rows {r0}..{r0 + 4}")
         assert_bit_equal(br[0][r0:r0 + 4], ref_b[0], f"1080p depth of field bright rows {r0}..{r0 + 4}")
     pin = sub[0].cpu().numpy()
@@ -432,13 +432,13 @@ def test_full_size_1080p_depth_of_field_16_lens_samples(renderer):
 # ---------------------------------------------------------------- 7. render_sequence(..., accumulate=n)
 def test_render_sequence_accumulated_equals_the_oracle_chain(renderer):
     W, H, N, n = 75, 45, 2, 3
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         li.color[0] *= 2.5; li.color[1] *= 2.5; li.color[2] *= 2.5  # over-exposed: BrightColor is populated
     s = abi.default_settings(enableReflection=1)
     cams = lens_frames(camera_data((0, 1.2, 5), (0, -0.2, -1), angle_deg=40.0), W, H, 0.1, 5.0, n, N)
     globs = [g for f in range(N) for g in shutter_globals(scene[5], 0.25 * f, 0.25 * f + 0.1, n)]
-    post = abi.RmPostSettings(**{"exposure": 1.0, **P.POST_CASES["bloom_hdr_fxaa"]})
+    post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES["bloom_hdr_fxaa"]})
     imgs = renderer.render_sequence(tables_of(scene), s, W, H, cams, globals_=globs, post=post, accumulate=n)
     assert lib().rm_debug_last_path() == 9
     assert tuple(imgs.shape) == (N, H, W, 4) and imgs.dtype == renderer.torch.uint8

@@ -14,9 +14,10 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
+from helpers import assert_bit_equal, tables_of, with_globals
+from scene_builders import orbit
 from test_adaptive_abi import adaptive
-from test_gpu_batch import assert_bit_equal, orbit, tables_of, with_globals
 from test_gpu_supersample import CLASSES, ODD, SCENES, class_tables, oracle_resolved
 from raymarcher_amd import abi, lib
 from raymarcher_amd._lib import RaymarcherError
@@ -84,14 +85,14 @@ def test_bulb_general_form_mixed_with_plain(renderer):
 
 
 def test_primitives_two_lights_soft_shadows_ao(renderer):
-    scene = P.reflect_refract_scene(64, 36)  # reflection / refraction off below: the plain table walk
+    scene = SB.reflect_refract_scene(64, 36)  # reflection / refraction off below: the plain table walk
     globs = [with_globals(scene[5], iTime=0.25 * f) for f in range(3)]
     adaptive_vs_oracle(renderer, scene, abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1),
                        lambda W, H: orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=6.0), globs, what="primitives soft+AO")
 
 
 def test_reflection_and_refraction_two_bounces(renderer):
-    scene = P.reflect_refract_scene(64, 36)
+    scene = SB.reflect_refract_scene(64, 36)
     s = abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2)
     adaptive_vs_oracle(renderer, scene, s, lambda W, H: orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=8.0), scene[5],
                        what="reflection+refraction")
@@ -99,7 +100,7 @@ def test_reflection_and_refraction_two_bounces(renderer):
 
 def test_menger_sponge_with_reflection_never_takes_the_wavefront_pipeline(renderer):
     L = lib()
-    scene = P.menger_scene(64, 36)
+    scene = SB.menger_scene(64, 36)
     globs = [with_globals(scene[5], iTime=3.7 * f) for f in range(3)]
     s = abi.default_settings(mengerLevels=4, enableReflection=1, numReflection=1)
     cams_of = lambda W, H: orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, 3, deg=5.0)  # noqa: E731
@@ -112,30 +113,30 @@ def test_menger_sponge_with_reflection_never_takes_the_wavefront_pipeline(render
 
 
 def test_textures_sky_box_and_area_light(renderer):
-    scene = P.textured_scene(64, 36)
+    scene = SB.textured_scene(64, 36)
     s = abi.default_settings(features=abi.RM_FEAT_WHITE_BACKGROUND, enableSoftShadow=1, enableSkyBox=1)
     adaptive_vs_oracle(renderer, scene, s, lambda W, H: orbit((0.4, 2.2, 5.5), (-0.05, -0.35, -1), 42.0, W, H, 3, deg=6.0), scene[5],
-                       textures=P.synthetic_textures(), what="textured + sky box", skybox=P.synthetic_skybox())
-    scene, s, res = P.resource_case("area_light", 64, 36)
+                       textures=SB.synthetic_textures(), what="textured + sky box", skybox=SB.synthetic_skybox())
+    scene, s, res = SB.resource_case("area_light", 64, 36)
     s.enableSkyBox = 1
     adaptive_vs_oracle(renderer, scene, s, lambda W, H: orbit((0, 1.6, 5.5), (0, -0.2, -1), 45.0, W, H, 3, deg=7.0), scene[5],
-                       what="area light + sky box", skybox=P.synthetic_skybox(), **res)
+                       what="area light + sky box", skybox=SB.synthetic_skybox(), **res)
 
 
 def test_terrain_and_clouds_with_advancing_time(renderer):
-    scene = P.env_scene(64, 36)
+    scene = SB.env_scene(64, 36)
     globs = [with_globals(scene[5], iTime=4.0 * f) for f in range(3)]
-    adaptive_vs_oracle(renderer, scene, abi.default_settings(features=P.ENV_ALL, enableReflection=1),
+    adaptive_vs_oracle(renderer, scene, abi.default_settings(features=SB.ENV_ALL, enableReflection=1),
                        lambda W, H: orbit((0, 500, 5), (0.3, 0.12, -1), 70.0, W, H, 3, deg=3.0, far=2000.0), globs,
                        what="terrain+cloud")
 
 
 def test_sea_and_night_sky_with_the_noise_texture(renderer):
-    scene, s, res = P.resource_case("sea_sky", 64, 36)
+    scene, s, res = SB.resource_case("sea_sky", 64, 36)
     globs = [with_globals(scene[5], iTime=0.7 + 0.9 * f) for f in range(3)]
     adaptive_vs_oracle(renderer, scene, s, lambda W, H: orbit((0, 3.5, 6), (0, -0.35, -1), 50.0, W, H, 3, deg=5.0), globs,
                        what="sea + sky", **res)
-    scene, s, res = P.resource_case("night_sky", 64, 36)
+    scene, s, res = SB.resource_case("night_sky", 64, 36)
     adaptive_vs_oracle(renderer, scene, s, lambda W, H: orbit((1.6, 0.4, -5), (-0.42, 0.36, 1), 60.0, W, H, 3, deg=4.0), scene[5],
                        what="night sky", **res)
 
@@ -170,7 +171,7 @@ def test_flagged_pixels_are_supersampled_the_rest_is_render_batch(renderer, name
 
 # ---------------------------------------------------------------- 3. limits
 def _three(W, H):
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableReflection=1)
     cams = orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=8.0)
     globs = [with_globals(scene[5], iTime=0.25 * f) for f in range(3)]
@@ -225,7 +226,7 @@ def test_a_1x1_frame_is_never_flagged(renderer, ss):
 @pytest.mark.parametrize("ss", [2, 4])
 def test_pure_background_flags_nothing_at_threshold_0(renderer, ss):
     W, H = 45, 27
-    for scene in (h.scene_mandelbulb(W, H), P.reflect_refract_scene(W, H)):
+    for scene in (h.scene_mandelbulb(W, H), SB.reflect_refract_scene(W, H)):
         away = h.make_camera((0, 0, 4.5), (0, 0, 1), (0, 1, 0), 30.0, W, H)  # every object is behind the camera
         s = abi.default_settings(features=abi.RM_FEAT_WHITE_BACKGROUND)
         t = tables_of((away,) + tuple(scene[1:]))
@@ -266,12 +267,12 @@ def test_every_word_is_written_and_nothing_else(renderer, ss, W, H, n):
             spare = h.Guarded((n, H, W, 4), torch.float32, h.FLOAT_POISON, renderer.device)
             got = renderer.render_adaptive(t, s, W, H, cams, ss, 0.1, out=out2, **kw)
             c4()
-            assert P._ieq(out2, out), kw
+            assert SB.ieq(out2, out), kw
             assert bool(spare._unwritten(spare.buf).all()), f"a launch with {kw} wrote outside its outputs"
             if "mask" in kw:
                 assert bool((got[-2 if "counts" in kw else -1] == mask).all())
         for f in range(1, n):
-            assert P._ieq(out[f], out[0]) and P._ieq(br[f], br[0]) and bool((mask[f] == mask[0]).all())
+            assert SB.ieq(out[f], out[0]) and SB.ieq(br[f], br[0]) and bool((mask[f] == mask[0]).all())
 
 
 # ---------------------------------------------------------------- 5. chunking under a workspace limit
@@ -335,7 +336,7 @@ def _c2(W, H):
 def test_timing_counts_one_launch_all_stage_1(renderer):
     L = lib()
     W, H = 64, 40
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     s = abi.default_settings(mengerLevels=3)
     cams = orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, 3)
     try:
@@ -378,7 +379,7 @@ def test_adaptive_launch_leaves_the_single_frame_tuners_alone(renderer):
         assert plain[0] == 0 and plain[-1] > 0, plain  # it settles, then splits
         again, frames2 = sequence(adaptive_after=plain.index(plain[-1]) + 1)
         assert again == plain
-        assert all(P._ieq(a, frames[0]) for a in frames + frames2)
+        assert all(SB.ieq(a, frames[0]) for a in frames + frames2)
     finally:
         L.rm_debug_set_tile_shape(-1)
         L.rm_debug_set_light_split(-1)
@@ -460,7 +461,7 @@ def test_host_output_pointers_are_refused_and_hip_stays_clean(renderer):
 def test_a_missing_sampler_is_unsupported(renderer):
     W, H = 16, 16
     for name in ("night_sky", "sea_sky", "skybox_reflect", "area_light"):
-        scene, s, _res = P.resource_case(name, W, H)
+        scene, s, _res = SB.resource_case(name, W, H)
         with pytest.raises(RaymarcherError) as e:
             renderer.render_adaptive(tables_of(scene), s, W, H, [scene[0]], 2, 0.1)
         assert e.value.status == abi.RM_ERR_UNSUPPORTED, name
@@ -472,13 +473,13 @@ def test_a_missing_sampler_is_unsupported(renderer):
 # ---------------------------------------------------------------- 9. render_sequence(..., supersample=2, adaptive=0.1)
 def test_render_sequence_adaptive_equals_the_oracle_chain(renderer):
     W, H, N, ss, thr = 75, 45, 3, 2, 0.1
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         li.color[0] *= 2.5; li.color[1] *= 2.5; li.color[2] *= 2.5  # over-exposed: BrightColor is populated
     s = abi.default_settings(enableReflection=1)
     cams = orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, N)
     globs = [with_globals(scene[5], iTime=0.25 * f) for f in range(N)]
-    post = abi.RmPostSettings(**{"exposure": 1.0, **P.POST_CASES["bloom_hdr_fxaa"]})
+    post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES["bloom_hdr_fxaa"]})
     assert post.enableBloom and post.enableHDR and post.enableFXAA
     imgs = renderer.render_sequence(tables_of(scene), s, W, H, cams, globals_=globs, post=post, supersample=ss, adaptive=thr)
     assert lib().rm_debug_last_path() == 8

@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
+from helpers import assert_bit_equal, tables_of, with_globals
 from test_gpu_accumulate import accumulate, oracle_accumulated
-from test_gpu_batch import assert_bit_equal, tables_of, with_globals
 from raymarcher_amd import abi, lib, translated_objects
 from raymarcher_amd.render import shutter_globals
 
@@ -130,7 +130,7 @@ def test_moving_sphere_leaves_block_0s_bounds(renderer, n):
 # ---------------------------------------------------------------- 2. moving lights only
 def test_moving_lights_with_one_object_table(renderer):
     W, H, n, frames = W0, H0, 3, 2
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     blocks = n * frames
     lights = []
     for b in range(blocks):
@@ -150,7 +150,7 @@ def test_moving_lights_with_one_object_table(renderer):
 def restage_pattern(renderer, W, H):
     """Tables A, A, B, B, A over n = 5, two frames (the second B, A, A, B, B): equal neighbours keep the staged table, unequal ones
     must replace it, and going back to A must not find B."""
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     A = [clone(o) for o in scene[1]]
     B = split(translated_objects(A, 0, [(2.5, 0.8, 0.5)]), 4, 1)[0]
     B[3].cDiffuse[0], B[3].type = 0.9, abi.RM_CYLINDER  # a material and a type change as well
@@ -186,7 +186,7 @@ def test_restage_pattern_with_four_waves_per_workgroup():
 # ---------------------------------------------------------------- 4. the class of the call is the union of its blocks'
 def test_union_reflective_object_in_one_sub_frame_only(renderer):
     W, H = W0, H0
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     dull = [clone(o) for o in scene[1]]
     for o in dull:
         for k in range(3):
@@ -198,19 +198,19 @@ def test_union_reflective_object_in_one_sub_frame_only(renderer):
 
 def test_union_textured_object_in_one_block_only(renderer):
     W, H = W0, H0
-    scene = P.textured_scene(W, H)
+    scene = SB.textured_scene(W, H)
     bare = [clone(o) for o in scene[1]]
     for o in bare:
         o.texLoc = -1
     objects = [bare, bare, [clone(o) for o in scene[1]], bare]
     for n in (1, 2):
-        anim_vs_oracle(renderer, scene, abi.default_settings(), W, H, [scene[0]] * 4, n, objects=objects, textures=P.synthetic_textures(),
+        anim_vs_oracle(renderer, scene, abi.default_settings(), W, H, [scene[0]] * 4, n, objects=objects, textures=SB.synthetic_textures(),
                        what="textured in one block")
 
 
 def test_union_area_light_in_a_later_light_table_only(renderer):
     W, H = W0, H0
-    scene, s, res = P.resource_case("area_light", W, H)
+    scene, s, res = SB.resource_case("area_light", W, H)
     point = [h.make_light(abi.RM_LIGHT_POINT, (1.0, 0.9, 0.6), pos=(0.3, 2.2, -1.0), func=(0.7, 0.05, 0)), clone(scene[3][1])]
     lights = [point, point, [clone(scene[3][0]), clone(scene[3][1])]]
     dark = [clone(o) for o in scene[1]]
@@ -247,7 +247,7 @@ def test_menger_sponge_in_a_later_block_only(renderer, n):
     """Block 0 holds a cube in the sponge's place: the sponge's uniforms (computed on the device per block, from its iTime) must be
     there for the blocks that do hold one."""
     W, H = W0, H0
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     cube = clone(scene[1][0])
     cube.type = abi.RM_CUBE
     objects = [[cube], [clone(scene[1][0])], [clone(scene[1][0])]]
@@ -260,7 +260,7 @@ def test_menger_sponge_in_a_later_block_only(renderer, n):
 @pytest.mark.parametrize("n", [1, 4])
 def test_shared_tables_are_render_accumulated_and_repeats_change_nothing(renderer, n):
     W, H, frames = W0, H0, 2
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableReflection=1, enableSoftShadow=1)
     t = tables_of(scene)
     blocks = frames * n
@@ -269,20 +269,20 @@ def test_shared_tables_are_render_accumulated_and_repeats_change_nothing(rendere
     a, ab = renderer.render_accumulated(t, s, W, H, cams, n, globals_=globs, bright=True)
     one, one_b = renderer.render_animated(t, s, W, H, cams, n, globals_=globs, bright=True)
     assert lib().rm_debug_last_path() == 10
-    assert P._ieq(one, a) and P._ieq(one_b, ab)
+    assert SB.ieq(one, a) and SB.ieq(one_b, ab)
     rep_o, rep_l = [list(scene[1])] * blocks, [list(scene[3])] * blocks
     for kw in (dict(objects=rep_o), dict(lights=rep_l), dict(objects=rep_o, lights=rep_l)):
         rep, rep_b = renderer.render_animated(t, s, W, H, cams, n, globals_=globs, bright=True, **kw)
-        assert P._ieq(rep, a) and P._ieq(rep_b, ab), sorted(kw)
+        assert SB.ieq(rep, a) and SB.ieq(rep_b, ab), sorted(kw)
     if n == 1:
         bt, bt_b = renderer.render_batch(t, s, W, H, cams, globals_=globs, bright=True)
-        assert P._ieq(one, bt) and P._ieq(one_b, bt_b)
+        assert SB.ieq(one, bt) and SB.ieq(one_b, bt_b)
 
 
 def test_one_sub_frame_with_tables_per_frame_is_rm_render_res(renderer):
     from raymarcher_amd.render import SceneTables
     W, H, frames = W0, H0, 4
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableSoftShadow=1)
     objects = moving_sphere(scene, frames, reach=3.0)
     lights = [[clone(scene[3][0]), h.make_light(abi.RM_LIGHT_POINT, (.8, .8, 1), pos=(-3 + f, 4, 3), func=(0.6, 0.05, 0.0))] for f in range(frames)]
@@ -290,14 +290,14 @@ def test_one_sub_frame_with_tables_per_frame_is_rm_render_res(renderer):
     for f in range(frames):
         tf = SceneTables(scene[0], table(abi.RmObject, objects[f]), 4, table(abi.RmLight, lights[f]), 2, scene[5])
         one, one_b = renderer.render(tf, s, W, H, bright=True)
-        assert P._ieq(out[f], one) and P._ieq(br[f], one_b), f
+        assert SB.ieq(out[f], one) and SB.ieq(br[f], one_b), f
 
 
 # ---------------------------------------------------------------- 7. write coverage
 @pytest.mark.parametrize("W,H", [(1, 1), (3, 70), (65, 9), (97, 53)])
 @pytest.mark.parametrize("frames", [1, 3])
 def test_every_word_is_written_and_nothing_else(renderer, W, H, frames):
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableReflection=1)
     t = tables_of(scene)
     for n in (1, 3):
@@ -314,7 +314,7 @@ def test_every_word_is_written_and_nothing_else(renderer, W, H, frames):
         spare = h.Guarded((frames, H, W, 4), renderer.torch.float32, h.FLOAT_POISON, renderer.device)
         renderer.render_animated(t, s, W, H, cams, n, objects=objects, out=out2)
         c3()
-        assert P._ieq(out2, out)
+        assert SB.ieq(out2, out)
         assert bool(spare._unwritten(spare.buf).all()), "a launch without d_bright wrote outside d_rgba"
 
 
@@ -322,7 +322,7 @@ def test_every_word_is_written_and_nothing_else(renderer, W, H, frames):
 def test_timing_counts_one_launch_all_stage_1(renderer):
     L = lib()
     W, H, n = 64, 40, 3
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     cube = clone(scene[1][0])
     cube.type = abi.RM_CUBE
     objects = [[cube], [clone(scene[1][0])], [clone(scene[1][0])]] * 2  # the sponge prologue runs ahead of the timed launch
@@ -372,7 +372,7 @@ def test_animated_launch_leaves_the_single_frame_tuners_alone(renderer):
         assert plain[0] == 0 and plain[-1] > 0, plain  # it settles, then splits
         again, frames2 = sequence(anim_after=plain.index(plain[-1]) + 1)
         assert again == plain
-        assert all(P._ieq(a, frames[0]) for a in frames + frames2)
+        assert all(SB.ieq(a, frames[0]) for a in frames + frames2)
     finally:
         L.rm_debug_set_tile_shape(-1)
         L.rm_debug_set_light_split(-1)
@@ -383,7 +383,7 @@ def test_back_to_back_launches_with_different_tables_on_one_stream(renderer):
     import torch
     W = H = 24
     n = 4
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings()
     t = tables_of(scene)
     fa, fb = 60, 10
@@ -414,7 +414,7 @@ def test_back_to_back_launches_with_different_tables_on_one_stream(renderer):
 def test_host_output_pointer_is_refused_and_hip_stays_clean(renderer):
     L = lib()
     W, H = 16, 8
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     cams = (abi.RmCamera * 4)(*[scene[0]] * 4)
     stacked = translated_objects(list(scene[1]), 0, [(0.1 * b, 0, 0) for b in range(4)])
     host = np.zeros((2, H, W, 4), dtype=np.float32)
@@ -429,13 +429,13 @@ def test_host_output_pointer_is_refused_and_hip_stays_clean(renderer):
 # ---------------------------------------------------------------- 9. render_sequence(..., objects=…)
 def test_render_sequence_with_object_tables_equals_the_oracle_chain(renderer):
     W, H, N, n = 75, 45, 2, 3
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         li.color[0] *= 2.5; li.color[1] *= 2.5; li.color[2] *= 2.5  # over-exposed: BrightColor is populated
     s = abi.default_settings(enableReflection=1)
     cams = [scene[0]] * (N * n)
     stacked = translated_objects(list(scene[1]), 0, [(0.25 * b, 0.1 * b, 0) for b in range(N * n)])
-    post = abi.RmPostSettings(**{"exposure": 1.0, **P.POST_CASES["bloom_hdr_fxaa"]})
+    post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES["bloom_hdr_fxaa"]})
     imgs = renderer.render_sequence(tables_of(scene), s, W, H, cams, post=post, accumulate=n, objects=stacked)
     assert lib().rm_debug_last_path() == 10
     assert tuple(imgs.shape) == (N, H, W, 4) and imgs.dtype == renderer.torch.uint8

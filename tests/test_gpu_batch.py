@@ -10,49 +10,15 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
+from helpers import assert_bit_equal, tables_of, with_globals
+from scene_builders import orbit
 from raymarcher_amd import abi, lib
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = os.path.join(ROOT, "tests", "golden", "scenes")
-
-
-def assert_bit_equal(gpu, ref, what):
-    gb = np.ascontiguousarray(gpu, dtype=np.float32).view(np.uint32)
-    rb = np.ascontiguousarray(ref, dtype=np.float32).view(np.uint32)
-    bad = gb != rb
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ; first at {np.argwhere(bad)[:5].tolist()}"
-
-
-def rot_y(v, deg):
-    a = math.radians(deg)
-    return (v[0] * math.cos(a) + v[2] * math.sin(a), v[1], -v[0] * math.sin(a) + v[2] * math.cos(a))
-
-
-def orbit(pos, look, fov, W, H, n, deg=4.0, far=100.0):
-    """n cameras turned about the y axis by deg degrees per frame (position and view direction)."""
-    return [h.make_camera(rot_y(pos, deg * i), rot_y(look, deg * i), (0, 1, 0), fov, W, H, far=far) for i in range(n)]
-
-
-def tables_of(scene, **resources):
-    from raymarcher_amd.render import SceneTables
-    t = SceneTables(*scene)
-    for k, v in resources.items():
-        setattr(t, k, v)
-    return t
-
-
-def with_globals(g, **over):
-    g2 = abi.RmGlobals()
-    C.memmove(C.byref(g2), C.byref(g), C.sizeof(g))
-    for k, v in over.items():
-        if k == "julia":
-            g2.juliaSeed[0], g2.juliaSeed[1] = v
-        else:
-            setattr(g2, k, v)
-    return g2
 
 
 def batch_vs_oracle(renderer, scene, s, W, H, cams, globs, textures=None, what="", **resources):
@@ -93,7 +59,7 @@ def test_bulb_frames_that_disagree_on_the_plain_form(renderer):
 
 def test_primitives_two_lights_soft_shadows_ao(renderer):
     W, H = 128, 80
-    scene = P.reflect_refract_scene(W, H)  # reflection / refraction off below: the plain table walk, c2's class
+    scene = SB.reflect_refract_scene(W, H)  # reflection / refraction off below: the plain table walk, c2's class
     cams = orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 5, deg=6.0)
     globs = [with_globals(scene[5], iTime=0.25 * f) for f in range(5)]
     batch_vs_oracle(renderer, scene, abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1), W, H, cams, globs,
@@ -102,7 +68,7 @@ def test_primitives_two_lights_soft_shadows_ao(renderer):
 
 def test_reflection_and_refraction(renderer):
     W, H = 112, 72
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     cams = orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=8.0)
     s = abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2)
     batch_vs_oracle(renderer, scene, s, W, H, cams, scene[5], what="reflection+refraction")
@@ -110,34 +76,34 @@ def test_reflection_and_refraction(renderer):
 
 def test_textures_and_sky_box(renderer):
     W, H = 112, 72
-    scene = P.textured_scene(W, H)
+    scene = SB.textured_scene(W, H)
     cams = orbit((0.4, 2.2, 5.5), (-0.05, -0.35, -1), 42.0, W, H, 3, deg=6.0)
-    batch_vs_oracle(renderer, scene, abi.default_settings(enableSoftShadow=1), W, H, cams, scene[5], textures=P.synthetic_textures(),
+    batch_vs_oracle(renderer, scene, abi.default_settings(enableSoftShadow=1), W, H, cams, scene[5], textures=SB.synthetic_textures(),
                     what="textured")
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(features=abi.RM_FEAT_WHITE_BACKGROUND, enableSkyBox=1, enableReflection=1, enableRefraction=1)
     batch_vs_oracle(renderer, scene, s, W, H, orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=9.0), scene[5],
-                    what="sky box", skybox=P.synthetic_skybox())
+                    what="sky box", skybox=SB.synthetic_skybox())
 
 
 def test_terrain_and_clouds_with_advancing_time(renderer):
     W, H = 96, 54
-    scene = P.env_scene(W, H)
+    scene = SB.env_scene(W, H)
     cams = orbit((0, 500, 5), (0.3, 0.12, -1), 70.0, W, H, 4, deg=3.0, far=2000.0)
     globs = [with_globals(scene[5], iTime=4.0 * f) for f in range(4)]
-    out = batch_vs_oracle(renderer, scene, abi.default_settings(features=P.ENV_ALL, enableReflection=1), W, H, cams, globs,
+    out = batch_vs_oracle(renderer, scene, abi.default_settings(features=SB.ENV_ALL, enableReflection=1), W, H, cams, globs,
                           what="terrain+cloud")
     # sky + textures together (the ENV × TEX kernel)
-    scene = P.reflect_refract_scene(W, H)
-    s = abi.default_settings(features=P.ENV_ALL, enableSkyBox=1)
+    scene = SB.reflect_refract_scene(W, H)
+    s = abi.default_settings(features=SB.ENV_ALL, enableSkyBox=1)
     batch_vs_oracle(renderer, scene, s, W, H, orbit((0, 1.2, 5), (0, -0.2, -1), 40.0, W, H, 3, deg=9.0), globs[:3],
-                    what="env+skybox", skybox=P.synthetic_skybox())
+                    what="env+skybox", skybox=SB.synthetic_skybox())
     assert np.isfinite(out).all()
 
 
 def test_menger_sponge_with_advancing_time(renderer):
     W, H = 96, 72
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     cams = orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, 4, deg=5.0)
     globs = [with_globals(scene[5], iTime=3.7 * f) for f in range(4)]  # ani / off of sdMengerSponge move with iTime
     s = abi.default_settings(mengerLevels=4, enableReflection=1, numReflection=1)
@@ -179,18 +145,18 @@ def test_each_frame_equals_rm_render_including_bright(renderer):
         tf = tables_of((cams[f], t.objects, t.num_objects, t.lights, t.num_lights, globs[f]))
         for _ in range(3):  # a new picture, then repeats of it (cost-ordered tiles)
             o1, b1 = h.render_guarded(renderer, tf, s, W, H, bright=True)
-            assert P._ieq(o1, out[f]) and P._ieq(b1, br[f]), f"frame {f}"
+            assert SB.ieq(o1, out[f]) and SB.ieq(b1, br[f]), f"frame {f}"
     # numGlobals = 1 equals N identical explicit entries
     one = renderer.render_batch(t, s, W, H, cams, globals_=globs[0]).clone()
     many = renderer.render_batch(t, s, W, H, cams, globals_=[globs[0]] * 4)
-    assert P._ieq(one, many)
-    assert P._ieq(one[0], out[0])
+    assert SB.ieq(one, many)
+    assert SB.ieq(one[0], out[0])
 
 
 # ---------------------------------------------------------------- 3. launch and fallback
 def test_wavefront_frames_are_rendered_one_by_one(renderer):
     W = H = 2048  # 2^22 pixels with two reflection bounces: the single-frame launcher takes the wavefront pipeline
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     s = abi.default_settings(mengerLevels=4, enableReflection=1, numReflection=2)
     cams = orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, 2, deg=10.0)
     globs = [with_globals(scene[5], iTime=2.0 * f) for f in range(2)]
@@ -199,7 +165,7 @@ def test_wavefront_frames_are_rendered_one_by_one(renderer):
     for f in range(2):
         single = renderer.render(tables_of((cams[f],) + tuple(scene[1:5]) + (globs[f],)), s, W, H)
         assert lib().rm_debug_last_path() == 5
-        assert P._ieq(single, out[f]), f"frame {f}"
+        assert SB.ieq(single, out[f]), f"frame {f}"
     small = renderer.render_batch(tables_of(scene), s, 64, 48, orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, 64, 48, 2), scene[5])
     assert lib().rm_debug_last_path() == 6 and small.shape[0] == 2
 
@@ -222,9 +188,9 @@ def test_back_to_back_batches_on_one_stream(renderer):
     stream.synchronize()
     for f in range(300):
         tf = tables_of((cams_a[f],) + tuple(scene[1:5]) + (globs_a[f],))
-        assert P._ieq(renderer.render(tf, s, W, H), a[f]), f"first batch, frame {f}"
+        assert SB.ieq(renderer.render(tf, s, W, H), a[f]), f"first batch, frame {f}"
     for f in range(40):
-        assert P._ieq(renderer.render(tables_of((cams_b[f],) + tuple(scene[1:])), s, W, H), b[f]), f"second batch, frame {f}"
+        assert SB.ieq(renderer.render(tables_of((cams_b[f],) + tuple(scene[1:])), s, W, H), b[f]), f"second batch, frame {f}"
 
 
 # ---------------------------------------------------------------- 5. the single-frame tuners are not disturbed

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import helpers as h
+from helpers import assert_bit_equal, tables_of
+from scene_builders import bulb_scene
 from raymarcher_amd import abi, lib
 
 pytestmark = pytest.mark.gpu
@@ -20,29 +22,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # directional light directions: the c3 frame's three, then ones that light the bulb from the sides and from behind the camera
-DIRS = [(0, 0, 1), (0, -1, 0), (0, 0, -1), (1, -0.3, -0.2), (-0.7, 0.2, -0.6), (0.2, 0.9, -0.1), (-0.3, -0.4, 0.8),
-        (0.6, 0.5, 0.6), (-1, -1, -1), (0.1, -0.2, -1)]
-
-
-def tables_of(scene):
-    from raymarcher_amd.render import SceneTables
-    return SceneTables(*scene)
-
-
-def assert_bit_equal(gpu, ref, what):
-    gb = np.ascontiguousarray(gpu, dtype=np.float32).view(np.uint32)
-    rb = np.ascontiguousarray(ref, dtype=np.float32).view(np.uint32)
-    bad = gb != rb
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ; first at {np.argwhere(bad)[:5].tolist()}"
-
-
-def bulb_scene(W, H, nl=3, model=None, sf=1.0, julia=(0, 0), pos=(0, 0, 4.5), look=(0, 0, -1), far=100.0):
-    cam = h.make_camera(pos, look, (0, 1, 0), 30.0, W, H, far=far)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_MANDELBULB, model=model, scale_factor=sf, ambient=(.3, .3, .3),
-                                            diffuse=(1, 1, 1), specular=(1, 1, 1), shininess=100.0, ior=1.5))
-    colors = [(1, 1, 1), (1.5, 1.1, 0.7), (1, 1, 1), (0.4, 0.6, 0.9), (0.9, 0.3, 0.3)]
-    lights = (abi.RmLight * nl)(*[h.make_light(abi.RM_LIGHT_DIRECTIONAL, colors[i % 5], DIRS[i]) for i in range(nl)])
-    return cam, objs, 1, lights, nl, h.make_globals(julia=julia)
 
 
 CLOSE = dict(pos=(0.35, 0.25, 1.9))  # a close-up: the frame is mostly silhouette and crevices

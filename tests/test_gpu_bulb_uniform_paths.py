@@ -9,29 +9,11 @@ import numpy as np
 import pytest
 
 import helpers as h
+from helpers import assert_bit_equal, tables_of
+from scene_builders import bulb_scene
 from raymarcher_amd import abi, lib
 
 pytestmark = pytest.mark.gpu
-
-
-def tables_of(scene):
-    from raymarcher_amd.render import SceneTables
-    return SceneTables(*scene)
-
-
-def assert_bit_equal(gpu, ref, what):
-    gb = np.ascontiguousarray(gpu, dtype=np.float32).view(np.uint32)
-    rb = np.ascontiguousarray(ref, dtype=np.float32).view(np.uint32)
-    bad = gb != rb
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ; first at {np.argwhere(bad)[:5].tolist()}"
-
-
-def bulb_scene(W, H, model=None, sf=1.0, julia=(0, 0), pos=(0, 0, 4.5), look=(0, 0, -1), up=(0, 1, 0), refl=(0, 0, 0)):
-    cam, _, _, lights, nl, _ = h.scene_mandelbulb(W, H)
-    cam = h.make_camera(pos, look, up, 30.0, W, H)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_MANDELBULB, model=model, scale_factor=sf, ambient=(.3, .3, .3),
-                                            diffuse=(1, 1, 1), specular=(1, 1, 1), shininess=100.0, ior=1.5, reflective=refl))
-    return cam, objs, 1, lights, nl, h.make_globals(julia=julia)
 
 
 CASES = {

@@ -17,6 +17,7 @@ import pytest
 
 import gbuffer_helpers as gh
 import helpers as h
+from helpers import assert_bit_equal, tables_of
 from raymarcher_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
@@ -48,11 +49,6 @@ def scene_of(name):
     return (cam, objs, 1, t.lights, t.num_lights, t.globals_), W, H
 
 
-def tables_of(scene):
-    from raymarcher_amd.render import SceneTables
-    return SceneTables(*scene)
-
-
 def tile_classes(name):
     """(3, 3) counts over the frame's 8×8 tiles that hold a hit: [axis][no hit lane crosses, some do, all do], and the scaled hit
     points — crossing = floor(ps_k + 0.1f) != floor(ps_k) with ps = 10 p in float32, p the oracle's hit point."""
@@ -71,11 +67,6 @@ def tile_classes(name):
                     n = c[:, k].sum()
                     out[k, 0 if n == 0 else (2 if n == len(c) else 1)] += 1
     return out, ps[hit]
-
-
-def assert_bit_equal(got, ref, what):
-    bad = got.view(np.uint32) != ref.view(np.uint32)
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ, first at {np.argwhere(bad)[:4].tolist()}"
 
 
 def check(renderer, name):

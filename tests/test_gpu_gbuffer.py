@@ -3,7 +3,7 @@ for bit against the specification (tests/gbuffer_spec/rm_gbuffer_spec.c: the ora
 the three march classes, the sponge prologue, a fractal in a table walk and an emissive rectangle; batches with partial tiles; the
 optional position output; the schedule (rm_debug_last_path 11) and the single-frame state left alone.  Every output goes into
 poisoned, guarded buffers: an element the launch never wrote, or a write outside them, fails.
-Further down: the wide random tables of test_gpu_parity (nested, coincident, sheared and strongly scaled objects: what the skip-test
+Further down: the wide random tables of scene_builders (nested, coincident, sheared and strongly scaled objects: what the skip-test
 seeds handed to getNormal must survive), the edges of the definition, ragged frames with 1, 2 and 4 waves per workgroup, four
 launches back to back on one stream, the hit count of the colour path and the timing record."""
 import ctypes as C
@@ -18,7 +18,8 @@ import torch
 import arbiter_numpy as an
 import gbuffer_helpers as G
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
+from helpers import assert_bit_equal as assert_bits, bits, tables_of, with_globals
 from raymarcher_amd import abi, lib
 
 pytestmark = pytest.mark.gpu
@@ -26,28 +27,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = os.path.join(ROOT, "tests", "golden", "scenes")
 INT_POISON = 0x5AA5A55A  # no object index and not −1
-
-
-def tables_of(scene):
-    from raymarcher_amd.render import SceneTables
-    return SceneTables(*scene)
-
-
-def with_globals(g, **over):
-    g2 = abi.RmGlobals()
-    C.memmove(C.byref(g2), C.byref(g), C.sizeof(g))
-    for k, v in over.items():
-        setattr(g2, k, v)
-    return g2
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ; first at {np.argwhere(bad)[:5].tolist()}"
 
 
 def gbuffer_guarded(renderer, t, s, W, H, cameras=None, globals_=None, position=True):
@@ -83,7 +62,7 @@ def check_against_spec(renderer, scene, s, W, H, what, cameras=None, globals_=No
     return nd, ids, pos, spec_ids
 
 
-moved_bulb_scene, directional_light_2 = G.moved_bulb_scene, G.directional_light_2
+moved_bulb_scene, directional_light_2 = SB.moved_bulb_scene, SB.directional_light_2
 
 
 # ---------------------------------------------------------------- the march classes, bit for bit
@@ -127,7 +106,7 @@ def test_table_walk(renderer):
 
 def test_menger_sponge_with_the_prologue(renderer):
     W, H = 48, 27
-    scene = P.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     scene[5].iTime = 7.5
     _, ids, _, _ = check_against_spec(renderer, scene, abi.default_settings(mengerLevels=3), W, H, "menger depth 3")
     assert 0.05 < (ids >= 0).mean() < 0.95
@@ -145,7 +124,7 @@ def test_fractal_behind_a_primitive_runs_the_table_walk(renderer):
 
 def test_emissive_rectangle_reports_its_own_index(renderer):
     W, H = 64, 36
-    scene = P.area_light_scene(W, H)
+    scene = SB.area_light_scene(W, H)
     assert scene[1][3].isEmissive == 1
     _, ids, _, _ = check_against_spec(renderer, scene, abi.default_settings(), W, H, "area light")
     assert (ids == 3).sum() > 10 and -1 in ids
@@ -225,7 +204,7 @@ def test_single_frame_renders_are_the_same_bits_before_and_after(renderer):
     after = [renderer.render(t, s, W, H).clone() for _ in range(2)]
     assert lib().rm_debug_last_path() == 1
     for a in before + after:
-        assert P._ieq(a, before[0])
+        assert SB.ieq(a, before[0])
 
 
 # ---------------------------------------------------------------- random wide tables
@@ -241,11 +220,11 @@ def _eye_inside_an_object(scene):
 
 @pytest.mark.parametrize("kind", ["tablewalk", "primitive"])
 def test_random_tables_bit_exact(renderer, kind):
-    """test_gpu_parity's random tables — up to 30 objects, nested, coincident, sheared, anisotropic, scaleFactors that are not the
+    """scene_builders' random tables — up to 30 objects, nested, coincident, sheared, anisotropic, scaleFactors that are not the
     smallest scale, cameras inside objects and on their bounding balls — with each case's own maxSteps and bump bit: the three
     outputs equal the spec in every bit.  The normal's taps may pass over an object only where render's skip-test seeds allow it."""
     cases, seed = _fuzz(48 if kind == "tablewalk" else 16, 20261018 if kind == "tablewalk" else 20261019)
-    gen = P._random_tablewalk_case if kind == "tablewalk" else P._random_primitive_case
+    gen = SB.random_tablewalk_case if kind == "tablewalk" else SB.random_primitive_case
     rng = np.random.default_rng(seed)
     W, H = 56, 40
     seen = {"max_objects": 0, "inside": 0, "bump": 0, "plain": 0, "hits": 0}
@@ -266,7 +245,7 @@ def test_random_tables_bit_exact(renderer, kind):
 
 
 def test_random_bulbs_bit_exact(renderer):
-    """test_gpu_parity's random single-Mandelbulb scenes (tiny and anisotropic models, Julia seeds, powers, maxSteps 1…256,
+    """scene_builders' random single-Mandelbulb scenes (tiny and anisotropic models, Julia seeds, powers, maxSteps 1…256,
     fractalIters 1…20, the algebraic power-8 form, bump on and off, cameras inside the ball).  The generator never draws the plain
     class (its model is never the identity), so every fourth case keeps its camera and settings and takes the identity model,
     power 8 and no Julia seed."""
@@ -275,7 +254,7 @@ def test_random_bulbs_bit_exact(renderer):
     W, H = 48, 40
     seen = {"plain": 0, "general": 0, "algebraic": 0, "bump": 0, "no_bump": 0, "hits": 0}
     for i in range(cases):
-        scene, s = P._random_bulb_case(rng, W, H)
+        scene, s = SB.random_bulb_case(rng, W, H)
         if i % 4 == 3:
             g = with_globals(scene[5], power=8.0)
             g.juliaSeed[0] = g.juliaSeed[1] = 0.0
@@ -335,7 +314,7 @@ def test_table_of_rm_max_objects_with_every_type(renderer):
 @pytest.mark.parametrize("over", [{"maxSteps": 0}, {"maxSteps": 1}, {"fractalIters": 0}, {"mengerLevels": 0}], ids=lambda o: "-".join(f"{k}{v}" for k, v in o.items()))
 def test_degenerate_loop_bounds(renderer, over):
     for name, scene in (("table", directional_light_2(EW, EH)), ("bulb", h.scene_mandelbulb(EW, EH)), ("general bulb", moved_bulb_scene(EW, EH)),
-                        ("sponge", P.menger_scene(EW, EH)), ("full table", full_table_scene(EW, EH))):
+                        ("sponge", SB.menger_scene(EW, EH)), ("full table", full_table_scene(EW, EH))):
         s = abi.default_settings(**{"maxSteps": 64, "fractalIters": 6, "mengerLevels": 2, **over})
         _, ids, _, _ = check_against_spec(renderer, scene, s, EW, EH, f"{name} {over}")
         if over.get("maxSteps") == 0:
@@ -359,9 +338,9 @@ def test_camera_on_the_bounding_ball_and_a_staged_box(renderer):
     objs = (abi.RmObject * 5)(
         h.make_object(abi.RM_CUBE, model=h.translate(0, -1, 0) @ h.scale(14, 0.2, 6), scale_factor=0.2),
         h.make_object(abi.RM_SPHERE, model=h.translate(-4, -0.4, 0)),
-        h.make_object(abi.RM_CONE, model=h.translate(-1.5, -0.4, 0.5) @ P.rot_x(0.3)),
+        h.make_object(abi.RM_CONE, model=h.translate(-1.5, -0.4, 0.5) @ SB.rot_x(0.3)),
         h.make_object(abi.RM_CYLINDER, model=h.translate(1.5, -0.4, -0.5)),
-        h.make_object(abi.RM_TORUS, model=h.translate(4.5, -0.3, 0.2) @ P.rot_x(1.2) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5))
+        h.make_object(abi.RM_TORUS, model=h.translate(4.5, -0.3, 0.2) @ SB.rot_x(1.2) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5))
     g = h.make_globals()
     b = cull_bounds(objs, 5, g)
     assert b[0] == 1 and b[6] == 1, "the table must have its ball and its staged box"
@@ -476,7 +455,7 @@ def test_four_launches_back_to_back_on_one_stream(renderer):
     while len(objs) != 28:
         objs = h.random_tablewalk_objects(rng, max_objects=28)
     big = (h.make_camera((0.3, 1.5, 6.0), (-0.03, -0.22, -1), (0, 1, 0), 55.0, W, H), (abi.RmObject * 28)(*objs), 28, None, 0, h.make_globals())
-    sponge = P.menger_scene(W, H)
+    sponge = SB.menger_scene(W, H)
     sponge[5].iTime = 7.5
     bulb = moved_bulb_scene(W, H)
     calls = [(bulb, abi.default_settings(fractalIters=8)), (big, abi.default_settings()), (sponge, abi.default_settings(mengerLevels=3)),
@@ -515,7 +494,7 @@ def test_hit_count_equals_the_colour_paths(renderer):
     cases = [("directional_light_2", directional_light_2(W, H), abi.default_settings()), ("mandelbulb", h.scene_mandelbulb(W, H), abi.default_settings())]
     rng = np.random.default_rng(20261021)
     for i in range(4):
-        scene, s = P._random_tablewalk_case(rng, W, H)
+        scene, s = SB.random_tablewalk_case(rng, W, H)
         assert not any(scene[1][k].isEmissive for k in range(scene[2]))
         cases.append((f"random table walk {i}", scene, s))
     for name, scene, s in cases:
@@ -526,7 +505,7 @@ def test_hit_count_equals_the_colour_paths(renderer):
 def test_timing_counts_one_launch_all_stage_1(renderer):
     L = lib()
     W, H = 64, 40
-    sponge = P.menger_scene(W, H)  # the sponge prologue runs ahead of the timed launch
+    sponge = SB.menger_scene(W, H)  # the sponge prologue runs ahead of the timed launch
     for scene, s, frames in ((sponge, abi.default_settings(mengerLevels=3), 3), (directional_light_2(W, H), abi.default_settings(), 1)):
         try:
             assert L.rm_set_timing(1) == 0

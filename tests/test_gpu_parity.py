@@ -10,29 +10,11 @@ import numpy as np
 import pytest
 
 import helpers as h
+import scene_builders as SB
+from helpers import assert_bit_equal, bits, tables_of
 from raymarcher_amd import abi
 
 pytestmark = pytest.mark.gpu
-
-
-def tables_of(scene):
-    from raymarcher_amd.render import SceneTables
-    cam, objs, no, lights, nl, g = scene
-    return SceneTables(cam, objs, no, lights, nl, g)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_bit_equal(gpu, ref, what):
-    gb, rb = bits(gpu), bits(ref)
-    bad = gb != rb
-    if bad.any():
-        idx = np.argwhere(bad)[:5]
-        diff = np.abs(gpu.astype(np.float64) - ref.astype(np.float64))
-        raise AssertionError(f"{what}: {bad.sum()} of {bad.size} words differ; max |Δ| = {np.nanmax(diff):.3e}; "
-                             f"first at {idx.tolist()}")
 
 
 # ---------------------------------------------------------------- the numeric contract, function by function
@@ -213,27 +195,9 @@ def test_pnoise_bit_exact(renderer):
 
 
 # ---------------------------------------------------------------- sdScene on random points, every primitive type
-def all_primitives_scene(W=64, H=64):
-    cam = h.make_camera((0, 0, 6), (0, 0, -1), (0, 1, 0), 45.0, W, H)
-    types = [abi.RM_CUBE, abi.RM_CONE, abi.RM_CYLINDER, abi.RM_SPHERE, abi.RM_OCTAHEDRON, abi.RM_TORUS, abi.RM_CAPSULE,
-             abi.RM_DEATHSTAR, abi.RM_RECTANGLE, abi.RM_SIERPINSKI, abi.RM_MENGERSPONGE, abi.RM_MANDELBULB]
-    objs = (abi.RmObject * len(types))()
-    for i, t in enumerate(types):
-        gx, gy = (i % 4) - 1.5, (i // 4) - 1.0
-        M = h.translate(1.6 * gx, 1.6 * gy, 0.0) @ h.scale(0.9, 0.8 + 0.05 * i, 0.9)
-        objs[i] = h.make_object(t, model=M, scale_factor=min(0.9, 0.8 + 0.05 * i), ambient=(.2, .2, .2),
-                                diffuse=(0.3 + 0.05 * i, 0.8, 1.0 - 0.05 * i), specular=(1, 1, 1), shininess=15.0 + i)
-    lights = (abi.RmLight * 3)(
-        h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.3, -1, -0.6)),
-        h.make_light(abi.RM_LIGHT_POINT, (1, 0.8, 0.6), pos=(3, 3, 4), func=(0.5, 0.1, 0.01)),
-        h.make_light(abi.RM_LIGHT_SPOT, (0.7, 0.8, 1), direction=(0, -1, -1), pos=(0, 5, 5), func=(0.8, 0.02, 0.0),
-                     angle=np.deg2rad(35.0), penumbra=np.deg2rad(12.0)))
-    return cam, objs, len(types), lights, 3, h.make_globals()
-
-
 def test_sdscene_bit_exact_all_primitives(renderer):
     import torch
-    scene = all_primitives_scene()
+    scene = SB.all_primitives_scene()
     s = abi.default_settings()
     rng = np.random.default_rng(3)
     pts = rng.uniform(-3.5, 3.5, (50000, 3)).astype(np.float32)
@@ -275,26 +239,13 @@ def test_sdscene_algebraic_power8(renderer):
     assert_bit_equal(both(p6, alg), both(p6, trig), "the bit is ignored unless power == 8")
 
 
-def env_scene(W, H, pos=(0, 500, 5), look=(0.3, 0.12, -1)):
-    """Terrain + volumetric cloud + sky (the shader's TERRAIN / CLOUD / SKY_BACKGROUND defines), with a reflective
-    torus floating in front of the camera so secondary rays also see the layers (frag:2506-2518)."""
-    cam = h.make_camera(pos, look, (0, 1, 0), 70.0, W, H, far=2000.0)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_TORUS, model=h.translate(8, pos[1] + 3, -30) @ h.scale(12, 12, 12),
-                                            scale_factor=12, ambient=(.3, .3, .3), specular=(1, 1, 1), shininess=50,
-                                            reflective=(.6, .6, .6), transparent=(.5, .5, .5), ior=1.3))
-    lights = (abi.RmLight * 1)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (3, 2.6, 2.0), (-0.577, -0.577, 0.577)))
-    return cam, objs, 1, lights, 1, h.make_globals()
-
-
-ENV_ALL = abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN | abi.RM_FEAT_CLOUD | abi.RM_FEAT_PERLIN_BUMP
-
 # ---------------------------------------------------------------- whole frames
 FRAME_CASES = {
-    "env_terrain_cloud_sky_reflect": (lambda W, H: env_scene(W, H), {"features": ENV_ALL, "enableReflection": 1}, 96, 54),
-    "env_terrain_cloud_refract_time": (lambda W, H: env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
-                                       {"features": ENV_ALL, "enableRefraction": 1, "enableReflection": 1}, 80, 45),
-    "env_terrain_sky_only": (lambda W, H: env_scene(W, H), {"features": abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN}, 64, 36),
-    "env_cloud_only_dark": (lambda W, H: env_scene(W, H), {"features": abi.RM_FEAT_CLOUD | abi.RM_FEAT_DARK_BACKGROUND}, 64, 36),
+    "env_terrain_cloud_sky_reflect": (lambda W, H: SB.env_scene(W, H), {"features": SB.ENV_ALL, "enableReflection": 1}, 96, 54),
+    "env_terrain_cloud_refract_time": (lambda W, H: SB.env_scene(W, H, (0, 560, 0), (0.2, 0.3, -1)),
+                                       {"features": SB.ENV_ALL, "enableRefraction": 1, "enableReflection": 1}, 80, 45),
+    "env_terrain_sky_only": (lambda W, H: SB.env_scene(W, H), {"features": abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN}, 64, 36),
+    "env_cloud_only_dark": (lambda W, H: SB.env_scene(W, H), {"features": abi.RM_FEAT_CLOUD | abi.RM_FEAT_DARK_BACKGROUND}, 64, 36),
     "bulb_reference_consts": (lambda W, H: h.scene_mandelbulb(W, H), {}, 96, 54),
     "bulb_bench_consts_12iters": (lambda W, H: h.scene_mandelbulb(W, H), {"fractalIters": 12}, 96, 54),
     "bulb_softshadow_ao": (lambda W, H: h.scene_mandelbulb(W, H), {"enableSoftShadow": 1, "enableAmbientOcclusion": 1}, 64, 36),
@@ -303,8 +254,8 @@ FRAME_CASES = {
     "bulb_algebraic_julia_ao": (lambda W, H: h.scene_mandelbulb(W, H)[:5] + (h.make_globals(julia=(0.35, -0.2)),),
                                      {"enableAmbientOcclusion": 1,
                                       "features": abi.RM_FEAT_REFERENCE_DEFAULT | abi.RM_FEAT_BULB_POWER8_ALGEBRAIC}, 64, 36),
-    "primitives_phong": (lambda W, H: all_primitives_scene(W, H), {"maxSteps": 64}, 96, 64),
-    "primitives_softshadow_ao_nobump": (lambda W, H: all_primitives_scene(W, H),
+    "primitives_phong": (lambda W, H: SB.all_primitives_scene(W, H), {"maxSteps": 64}, 96, 64),
+    "primitives_softshadow_ao_nobump": (lambda W, H: SB.all_primitives_scene(W, H),
                                         {"enableSoftShadow": 1, "enableAmbientOcclusion": 1,
                                          "features": abi.RM_FEAT_DARK_BACKGROUND}, 80, 48),
 }
@@ -329,31 +280,13 @@ def test_frame_bit_exact(renderer, name):
     assert 0.05 < hit <= 1.0, "frame should not be constant"
 
 
-def reflect_refract_scene(W, H):
-    cam = h.make_camera((0, 1.2, 5), (0, -0.2, -1), (0, 1, 0), 40.0, W, H)
-    objs = (abi.RmObject * 4)(
-        h.make_object(abi.RM_SPHERE, model=h.translate(-1.1, 0, 0) @ h.scale(1.6, 1.6, 1.6), scale_factor=1.6,
-                      ambient=(.1, .1, .1), diffuse=(.8, .2, .2), specular=(1, 1, 1), shininess=30, reflective=(.8, .8, .8)),
-        h.make_object(abi.RM_SPHERE, model=h.translate(1.1, 0, 0.3) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5,
-                      ambient=(.1, .1, .1), diffuse=(.2, .3, .8), specular=(1, 1, 1), shininess=50,
-                      transparent=(.9, .9, .9), ior=1.4),
-        h.make_object(abi.RM_CUBE, model=h.translate(0, -1.3, 0) @ h.scale(8, 1, 8), scale_factor=1.0,
-                      ambient=(.2, .2, .2), diffuse=(.6, .6, .5), specular=(.3, .3, .3), shininess=5, reflective=(.3, .3, .3)),
-        h.make_object(abi.RM_TORUS, model=h.translate(0.2, 0.4, -2.0) @ h.scale(2, 2, 2), scale_factor=2.0,
-                      ambient=(.1, .2, .1), diffuse=(.3, .9, .3), specular=(1, 1, 1), shininess=10))
-    lights = (abi.RmLight * 2)(
-        h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.5, -1, -0.4)),
-        h.make_light(abi.RM_LIGHT_POINT, (.8, .8, 1), pos=(-3, 4, 3), func=(0.6, 0.05, 0.0)))
-    return cam, objs, 4, lights, 2, h.make_globals(kt=0.8)
-
-
 def test_kernels_without_secondary_rays_pick_up_exactly_where_they_may(renderer):
     """The launcher compiles main's reflection loop and refraction out (render_kernel<…, SEC = false>) when they cannot fire for
     any pixel: reflection off, or on with zero bounces, or no reflective material; refraction off or no transparent material.
     Every combination around that decision — for the table walk, the bulb class, the sampler kernel and the layer kernel — is the
     oracle's frame bit for bit, and frames that differ only in a switch that cannot matter are identical to each other."""
     W, H = 80, 48
-    cam, objs, no, lights, nl, g = reflect_refract_scene(W, H)
+    cam, objs, no, lights, nl, g = SB.reflect_refract_scene(W, H)
 
     def variant(reflective, transparent):
         o = (abi.RmObject * no)(*[abi.RmObject.from_buffer_copy(bytes(objs[i])) for i in range(no)])
@@ -376,8 +309,8 @@ def test_kernels_without_secondary_rays_pick_up_exactly_where_they_may(renderer)
             assert_bit_equal(br.cpu().numpy(), ref_b, f"materials {mat}, reflection {refl} x{nb}, refraction {refr} bright")
             frames[(mat, refl, nb, refr)] = out
     # switches that cannot matter: reflection on with zero bounces or without a reflective material adds 0 to rgb (alpha aside)
-    assert _ieq(frames[((0, 0), 0, 1, 0)][..., :3].contiguous(), frames[((0, 0), 1, 2, 1)][..., :3].contiguous())
-    assert _ieq(frames[((1, 0), 0, 1, 0)][..., :3].contiguous(), frames[((1, 0), 1, 0, 0)][..., :3].contiguous())
+    assert SB.ieq(frames[((0, 0), 0, 1, 0)][..., :3].contiguous(), frames[((0, 0), 1, 2, 1)][..., :3].contiguous())
+    assert SB.ieq(frames[((1, 0), 0, 1, 0)][..., :3].contiguous(), frames[((1, 0), 1, 0, 0)][..., :3].contiguous())
     # the other kernel classes: a bulb (reflective material, reflection off / on), a textured scene, the procedural layers
     bulb = h.scene_mandelbulb(W, H)
     for k in range(3):
@@ -386,7 +319,7 @@ def test_kernels_without_secondary_rays_pick_up_exactly_where_they_may(renderer)
               abi.default_settings(fractalIters=8, enableReflection=1, numReflection=0)):
         assert_bit_equal(renderer.render(tables_of(bulb), s, W, H).cpu().numpy(), h.oracle_render(bulb, s, W, H), "bulb class")
     for name in ("skybox_reflect", "sea_sky"):
-        scene, s, res = resource_case(name, W, H)
+        scene, s, res = SB.resource_case(name, W, H)
         for refl in (0, 1):
             s.enableReflection, s.enableRefraction = refl, refl
             t = tables_of(scene)
@@ -398,7 +331,7 @@ def test_kernels_without_secondary_rays_pick_up_exactly_where_they_may(renderer)
 @pytest.mark.parametrize("bounces", [1, 2])
 def test_reflection_refraction_bit_exact(renderer, bounces):
     W, H = 96, 64
-    scene = reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     s = abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=bounces)
     ref = h.oracle_render(scene, s, W, H)
     plain = h.oracle_render(scene, abi.default_settings(), W, H)
@@ -408,19 +341,10 @@ def test_reflection_refraction_bit_exact(renderer, bounces):
     assert ref[..., 3].max() >= 2.0  # alpha accumulates per bounce (frag:2520, 2568, 2572)
 
 
-def menger_scene(W, H):
-    cam = h.make_camera((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), (0, 1, 0), 30.0, W, H)
-    objs = (abi.RmObject * 1)(h.make_object(abi.RM_MENGERSPONGE, ambient=(.3, .3, .3), diffuse=(1, 1, 1),
-                                            specular=(1, 1, 1), shininess=25.0, reflective=(.4, .4, .4)))
-    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-1, -1.5, -0.7)),
-                               h.make_light(abi.RM_LIGHT_DIRECTIONAL, (.5, .5, .6), (1, -0.5, 0.3)))
-    return cam, objs, 1, lights, 2, h.make_globals()
-
-
 @pytest.mark.parametrize("levels,bounces,itime", [(4, 1, 0.0), (5, 2, 0.0), (4, 1, 7.5)])
 def test_menger_bit_exact(renderer, levels, bounces, itime):
     W, H = 80, 60
-    scene = menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     scene[5].iTime = itime
     s = abi.default_settings(mengerLevels=levels, numReflection=bounces, enableReflection=1)
     ref = h.oracle_render(scene, s, W, H)
@@ -498,46 +422,12 @@ def test_bulb_class_with_every_light_kind_and_kernel_path_requests(renderer):
         assert lib().rm_set_kernel_path(gone) == abi.RM_ERR_INVALID_ARGUMENT
 
 
-def synthetic_textures():
-    """Two procedural RGBA8 textures (rows bottom-up): a 37×23 colour gradient with a grid and a 64×64 checker."""
-    rng = np.random.default_rng(11)
-    yy, xx = np.mgrid[0:23, 0:37]
-    a = np.stack([xx * 255 // 36, yy * 255 // 22, (xx * 7 + yy * 13) % 256, np.full_like(xx, 255)], -1).astype(np.uint8)
-    a[::4, :, :3] //= 2
-    yy, xx = np.mgrid[0:64, 0:64]
-    b = np.where(((xx // 8 + yy // 8) % 2)[..., None] == 0, np.array([230, 40, 40, 255]), np.array([30, 60, 220, 255])).astype(np.uint8)
-    b[..., :3] = np.clip(b[..., :3].astype(int) + rng.integers(-20, 20, (64, 64, 3)), 0, 255).astype(np.uint8)
-    return [np.ascontiguousarray(a), np.ascontiguousarray(b)]
-
-
-def textured_scene(W, H):
-    """scenefiles/textures_tests in one frame: textured cube (floor), sphere, cone and cylinder + an untextured torus."""
-    cam = h.make_camera((0.4, 2.2, 5.5), (-0.05, -0.35, -1), (0, 1, 0), 42.0, W, H)
-    def tex(o, loc, ru, rv, blend):
-        o.texLoc, o.repeatU, o.repeatV, o.blend = loc, ru, rv, blend
-        return o
-    objs = (abi.RmObject * 5)(
-        tex(h.make_object(abi.RM_CUBE, model=h.translate(0, -0.8, 0) @ h.scale(7, 0.5, 7), scale_factor=0.5, ambient=(.2, .2, .2),
-                          diffuse=(.9, .9, .9), specular=(.4, .4, .4), shininess=8), 1, 6.0, 6.0, 0.8),
-        tex(h.make_object(abi.RM_SPHERE, model=h.translate(-1.5, 0.3, 0) @ h.scale(1.6, 1.6, 1.6), scale_factor=1.6,
-                          ambient=(.1, .1, .1), diffuse=(1, 1, 1), specular=(1, 1, 1), shininess=30), 0, 2.0, 1.0, 1.0),
-        tex(h.make_object(abi.RM_CONE, model=h.translate(0.3, 0.2, 0.8) @ h.scale(1.2, 1.5, 1.2), scale_factor=1.2,
-                          ambient=(.1, .1, .1), diffuse=(.7, .9, .7), specular=(.5, .5, .5), shininess=12), 0, 3.0, 2.0, 0.5),
-        tex(h.make_object(abi.RM_CYLINDER, model=h.translate(1.9, 0.2, -0.4) @ h.scale(1.1, 1.5, 1.1), scale_factor=1.1,
-                          ambient=(.1, .1, .1), diffuse=(.9, .8, .6), specular=(.5, .5, .5), shininess=12), 1, 2.0, 1.0, 0.9),
-        h.make_object(abi.RM_TORUS, model=h.translate(0, 1.6, -1.5) @ h.scale(2, 2, 2), scale_factor=2.0, ambient=(.1, .1, .2),
-                      diffuse=(.3, .4, .9), specular=(1, 1, 1), shininess=20))
-    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.4, -1, -0.5)),
-                               h.make_light(abi.RM_LIGHT_POINT, (.9, .8, .7), pos=(3, 4, 4), func=(0.7, 0.04, 0.0)))
-    return cam, objs, 5, lights, 2, h.make_globals()
-
-
 @pytest.mark.parametrize("over", [{}, {"features": abi.RM_FEAT_WHITE_BACKGROUND, "enableSoftShadow": 1, "enableAmbientOcclusion": 1},
-                                  {"features": ENV_ALL}])
+                                  {"features": SB.ENV_ALL}])
 def test_textured_frames_bit_exact(renderer, over):
     W, H = 112, 72
-    scene = textured_scene(W, H)
-    texs = synthetic_textures()
+    scene = SB.textured_scene(W, H)
+    texs = SB.synthetic_textures()
     s = abi.default_settings(**over)
     ref = h.oracle_render(scene, s, W, H, textures=texs)
     plain = [o for o in scene[1]]
@@ -554,12 +444,12 @@ def test_textured_frames_bit_exact(renderer, over):
 def test_texture_errors(renderer):
     from raymarcher_amd import RaymarcherError
     W, H = 16, 16
-    scene = textured_scene(W, H)
+    scene = SB.textured_scene(W, H)
     t = tables_of(scene)
     with pytest.raises(RaymarcherError) as e:  # texLoc set but no textures supplied
         renderer.render(t, abi.default_settings(), W, H)
     assert e.value.status == abi.RM_ERR_UNSUPPORTED
-    t.textures = synthetic_textures()
+    t.textures = SB.synthetic_textures()
     t.objects[4].texLoc = 0  # torus: the reference has no uv map for it
     with pytest.raises(RaymarcherError) as e:
         renderer.render(t, abi.default_settings(), W, H)
@@ -572,7 +462,7 @@ def test_scenefile_with_texture_end_to_end(renderer, tmp_path):
     from raymarcher_amd.render import Scene
     (tmp_path / "scenes").mkdir()
     (tmp_path / "texture_store").mkdir()
-    tex = synthetic_textures()[0]
+    tex = SB.synthetic_textures()[0]
     Image.fromarray(tex[::-1, :, :3]).save(tmp_path / "texture_store" / "grad.png")  # file rows are top-down
     scene_json = """{"globalData": {"ambientCoeff": 0.5, "diffuseCoeff": 0.5, "specularCoeff": 0.5},
       "cameraData": {"position": [0, 1.5, 4], "up": [0, 1, 0], "heightAngle": 40, "focus": [0, 0, 0]},
@@ -589,28 +479,17 @@ def test_scenefile_with_texture_end_to_end(renderer, tmp_path):
     assert_bit_equal(renderer.render(t, s, W, H).cpu().numpy(), ref, "scenefile with texture")
 
 
-POST_CASES = {
-    "gamma": dict(enableGammaCorrection=1),
-    "hdr": dict(enableHDR=1, exposure=1.7),
-    "bloom": dict(enableBloom=1, exposure=1.0),
-    "bloom_hdr_fxaa": dict(enableBloom=1, enableHDR=1, enableFXAA=1, exposure=0.8),
-    "fxaa_only": dict(enableFXAA=1),
-    "gamma_fxaa": dict(enableGammaCorrection=1, enableFXAA=1),
-    "none": dict(),
-}
-
-
-@pytest.mark.parametrize("name", list(POST_CASES))
+@pytest.mark.parametrize("name", list(SB.POST_CASES))
 def test_post_passes_bit_exact(renderer, name):
     """applyLightEffects + applyFXAA (realtimerender.cpp:78-165) on a rendered frame with bright pixels."""
     W, H = 150, 90  # not multiples of the 256-wide blocks
-    scene = reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         li.color[0] *= 2.5; li.color[1] *= 2.5; li.color[2] *= 2.5  # over-exposed: BrightColor is populated
     s = abi.default_settings(enableReflection=1)
     frag, bright = renderer.render(tables_of(scene), s, W, H, bright=True)
     assert float(bright[..., :3].max()) > 1.0
-    post = abi.RmPostSettings(**{"exposure": 1.0, **POST_CASES[name]})
+    post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES[name]})
     got = renderer.post_process(frag, bright, post).cpu().numpy()
     ref = h.oracle_post(frag.cpu().numpy(), bright.cpu().numpy(), post)
     assert_bit_equal(got, ref, f"post {name}")
@@ -636,7 +515,7 @@ def test_post_passes_bit_exact_on_wide_synthetic_frames(renderer, W, H):
     bright[..., 3] = 1.0
     fd, bd = torch.from_numpy(frag).to(renderer.device), torch.from_numpy(bright).to(renderer.device)
     for name in ("bloom", "bloom_hdr_fxaa", "hdr", "gamma_fxaa"):
-        post = abi.RmPostSettings(**{"exposure": 1.0, **POST_CASES[name]})
+        post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES[name]})
         got = renderer.post_process(fd, bd, post).cpu().numpy()
         assert_bit_equal(got, h.oracle_post(frag, bright, post), f"post {name} {W}x{H}")
 
@@ -661,134 +540,10 @@ def test_post_full_size_4k(renderer):
 
 # ---------------------------------------------------------------- samplers beyond object textures: noise (night sky, sea),
 # sky box, LTC tables (area lights).  All inputs are synthetic — the ABI takes them as data.
-def synthetic_noise():
-    """256×256 RGBA8 with DIFFERENT channels (the reference's noise_texture_1.png is grey; distinct channels also
-    exercise noiseV's .yx swizzle).  A few texels are pushed to 255 so that stars (noise > 0.99) exist."""
-    rng = np.random.default_rng(5)
-    a = rng.integers(0, 256, (256, 256, 4), dtype=np.uint8)
-    a[rng.integers(0, 256, 900), rng.integers(0, 256, 900), :2] = 255
-    a[..., 3] = 255
-    return np.ascontiguousarray(a)
-
-
-def synthetic_skybox(n=24):
-    """Six n×n RGBA8 faces, each a different two-colour gradient with a bright spot (bloom source)."""
-    yy, xx = np.mgrid[0:n, 0:n]
-    faces = []
-    for f in range(6):
-        c0 = np.array([(f * 40) % 256, (255 - f * 30) % 256, (f * 90 + 30) % 256])
-        c1 = np.array([(200 + f * 10) % 256, (f * 50) % 256, (120 + f * 20) % 256])
-        t = ((xx + (f + 1) * yy) / ((f + 2) * (n - 1.0)))[..., None]
-        img = c0 * (1 - t) + c1 * t
-        img[(xx - n // 3) ** 2 + (yy - n // 2) ** 2 < 6] = 255
-        faces.append(np.ascontiguousarray(np.concatenate([img, np.full((n, n, 1), 255)], -1).astype(np.uint8)))
-    return faces
-
-
-def synthetic_ltc():
-    """Smooth stand-ins for the LTC tables (float, 64×64×4; u = column): t1 ≈ the inverse-matrix parameters,
-    t2 = (fresnel scale, fresnel bias, unused, horizon-clipping form factor)."""
-    v, u = np.mgrid[0:64, 0:64] / 63.0
-    t1 = np.stack([0.55 + 0.45 * v, 0.25 * u * v, 0.15 * (1 - v), 0.5 + 0.5 * np.sqrt(v)], -1)
-    t2 = np.stack([0.9 - 0.5 * v, 0.1 + 0.3 * u, 0 * u, np.clip(0.35 + 0.65 * u + 0.1 * v, 0, 1.2)], -1)
-    return t1.astype(np.float32), t2.astype(np.float32)
-
-
-def night_scene(W, H):
-    cam = h.make_camera((1.6, 0.4, -5), (-0.42, 0.36, 1), (0, 1, 0), 60.0, W, H)  # looks toward MOON (frag:107)
-    objs = (abi.RmObject * 2)(
-        h.make_object(abi.RM_SPHERE, model=h.translate(-0.9, 0, 0) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5, ambient=(.1, .1, .15),
-                      diffuse=(.5, .5, .7), specular=(1, 1, 1), shininess=25, reflective=(.9, .9, .9)),
-        h.make_object(abi.RM_CUBE, model=h.translate(1.3, -0.2, 0.4) @ h.scale(1.1, 1.1, 1.1), scale_factor=1.1, ambient=(.1, .1, .1),
-                      diffuse=(.7, .4, .3), specular=(.5, .5, .5), shininess=10))
-    lights = (abi.RmLight * 1)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (.9, .9, 1), (0.4, -0.4, -0.3)))
-    return cam, objs, 2, lights, 1, h.make_globals(itime=1.3)
-
-
-def sea_scene(W, H):
-    cam = h.make_camera((0, 3.5, 6), (0, -0.35, -1), (0, 1, 0), 50.0, W, H, far=100.0)
-    objs = (abi.RmObject * 1)(
-        h.make_object(abi.RM_SPHERE, model=h.translate(0, 1.8, -1.5) @ h.scale(2, 2, 2), scale_factor=2.0, ambient=(.2, .2, .2),
-                      diffuse=(.8, .3, .2), specular=(1, 1, 1), shininess=20, reflective=(.6, .6, .6)))
-    lights = (abi.RmLight * 1)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.4, -1, -0.3)))
-    return cam, objs, 1, lights, 1, h.make_globals(itime=0.7)
-
-
-def area_light_scene(W, H):
-    """A floor, a sphere and a torus under one rectangular area light with its emissive rectangle
-    (RayMarchScene::initScene appends one per area light, raymarchscene.cpp:121-133) plus a point light."""
-    cam = h.make_camera((0, 1.6, 5.5), (0, -0.2, -1), (0, 1, 0), 45.0, W, H)
-    ctm = h.translate(0.3, 2.2, -1.0) @ rot_x(np.deg2rad(65.0)) @ h.scale(2.4, 1.4, 1.0)
-    rect = h.make_object(abi.RM_RECTANGLE, model=ctm, scale_factor=1.0)
-    rect.isEmissive, rect.lightIdx = 1, 0
-    rect.color[0], rect.color[1], rect.color[2] = 1.0, 0.9, 0.6
-    objs = (abi.RmObject * 4)(
-        h.make_object(abi.RM_CUBE, model=h.translate(0, -1.0, 0) @ h.scale(9, 0.4, 9), scale_factor=0.4, ambient=(.1, .1, .1),
-                      diffuse=(.7, .7, .7), specular=(.6, .6, .6), shininess=12, reflective=(.25, .25, .25)),
-        h.make_object(abi.RM_SPHERE, model=h.translate(-1.2, 0, 0.2) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5, ambient=(.1, .1, .1),
-                      diffuse=(.3, .5, .9), specular=(1, 1, 1), shininess=40),
-        h.make_object(abi.RM_TORUS, model=h.translate(1.4, -0.2, 0) @ h.scale(1.8, 1.8, 1.8), scale_factor=1.8, ambient=(.1, .1, .1),
-                      diffuse=(.9, .5, .2), specular=(.8, .8, .8), shininess=20),
-        rect)
-    area = h.make_light(abi.RM_LIGHT_AREA, (1.0, 0.9, 0.6), func=(1, 0, 0))
-    area.intensity, area.twoSided = 0.0, 1  # sceneparser.cpp:18-30 drops the parsed intensity; twoSided is always set
-    corners = [(-0.5, 0.5, 0), (0.5, 0.5, 0), (0.5, -0.5, 0), (-0.5, -0.5, 0)]  # realtime.h:136-141
-    for k, c in enumerate(corners):
-        w = ctm @ np.array([*c, 1.0])
-        for j in range(3):
-            area.points[k][j] = float(np.float32(w[j]))
-    lights = (abi.RmLight * 2)(area, h.make_light(abi.RM_LIGHT_POINT, (.5, .5, .6), pos=(-3, 3, 3), func=(0.8, 0.05, 0)))
-    return cam, objs, 4, lights, 2, h.make_globals()
-
-
-def rot_x(a):
-    M = np.eye(4)
-    M[1, 1], M[1, 2], M[2, 1], M[2, 2] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
-    return M
-
-
-def resource_case(name, W, H):
-    """name → (scene, settings, resources dict) of the sampler-driven cases."""
-    WB = abi.RM_FEAT_WHITE_BACKGROUND
-    if name == "night_sky":
-        return night_scene(W, H), abi.default_settings(features=abi.RM_FEAT_NIGHTSKY_BACKGROUND, enableReflection=1), {"noise": synthetic_noise()}
-    if name == "sea_sky":
-        return sea_scene(W, H), abi.default_settings(features=abi.RM_FEAT_SEA | abi.RM_FEAT_SKY_BACKGROUND, enableReflection=1), \
-            {"noise": synthetic_noise()}
-    if name == "sea_terrain_cloud":
-        sc = sea_scene(W, H)
-        sc = (h.make_camera((0, 700, 6), (0, -0.2, -1), (0, 1, 0), 50.0, W, H),) + sc[1:]
-        return sc, abi.default_settings(features=ENV_ALL | abi.RM_FEAT_SEA), {"noise": synthetic_noise()}
-    if name == "sea_terrain":
-        sc = sea_scene(W, H)
-        sc = (h.make_camera((0, 700, 6), (0, -0.2, -1), (0, 1, 0), 50.0, W, H, far=2000.0),) + sc[1:]
-        return sc, abi.default_settings(features=abi.RM_FEAT_SKY_BACKGROUND | abi.RM_FEAT_TERRAIN | abi.RM_FEAT_SEA), {"noise": synthetic_noise()}
-    if name == "skybox_reflect":
-        return reflect_refract_scene(W, H), abi.default_settings(features=WB, enableSkyBox=1, enableReflection=1, enableRefraction=1), \
-            {"skybox": synthetic_skybox()}
-    if name == "area_light":
-        t1, t2 = synthetic_ltc()
-        return area_light_scene(W, H), abi.default_settings(features=WB, enableReflection=1), \
-            {"ltc1": h.oracle_ltc_quantise(t1), "ltc2": h.oracle_ltc_quantise(t2)}
-    if name == "area_light_soft_bump":
-        t1, t2 = synthetic_ltc()
-        return area_light_scene(W, H), abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1), \
-            {"ltc1": h.oracle_ltc_quantise(t1), "ltc2": h.oracle_ltc_quantise(t2)}
-    if name == "area_light_bump_ao":
-        t1, t2 = synthetic_ltc()
-        return area_light_scene(W, H), abi.default_settings(enableAmbientOcclusion=1), \
-            {"ltc1": h.oracle_ltc_quantise(t1), "ltc2": h.oracle_ltc_quantise(t2)}
-    raise KeyError(name)
-
-
-RESOURCE_CASES = ["night_sky", "sea_sky", "sea_terrain", "sea_terrain_cloud", "skybox_reflect", "area_light", "area_light_soft_bump",
-                  "area_light_bump_ao"]
-
-
-@pytest.mark.parametrize("name", RESOURCE_CASES)
+@pytest.mark.parametrize("name", SB.RESOURCE_CASES)
 def test_resource_frames_bit_exact(renderer, name):
     W, H = 96, 64
-    scene, s, res = resource_case(name, W, H)
+    scene, s, res = SB.resource_case(name, W, H)
     ref, ref_b = h.oracle_render(scene, s, W, H, bright=True, **res)
     t = tables_of(scene)
     for k, v in res.items():
@@ -805,7 +560,7 @@ def test_resource_frames_in_row_tiles(renderer):
     from raymarcher_amd import lib
     W, H, T, N = 96, 70, 8, 3
     for name in ("sea_sky", "area_light", "skybox_reflect"):
-        scene, s, res = resource_case(name, W, H)
+        scene, s, res = SB.resource_case(name, W, H)
         t = tables_of(scene)
         for k, v in res.items():
             setattr(t, k, v)
@@ -830,7 +585,7 @@ def test_host_pointers_are_refused(renderer):
     with pytest.raises(RaymarcherError) as e:
         check(lib().rm_render(*t.args(s), W, H, 0, H, C.c_void_p(host.ctypes.data), None, None))
     assert e.value.status == abi.RM_ERR_INVALID_ARGUMENT and "device" in str(e.value)
-    scene, s2, res = resource_case("night_sky", W, H)
+    scene, s2, res = SB.resource_case("night_sky", W, H)
     hres, _keep = h.host_resources(**res)          # HOST pixel pointers
     out = renderer.torch.empty((H, W, 4), dtype=renderer.torch.float32, device=renderer.device)
     with pytest.raises(RaymarcherError) as e:
@@ -843,19 +598,19 @@ def test_resource_errors(renderer):
     from raymarcher_amd import RaymarcherError
     W, H = 16, 16
     for name in ("night_sky", "sea_sky", "skybox_reflect", "area_light"):
-        scene, s, _res = resource_case(name, W, H)
+        scene, s, _res = SB.resource_case(name, W, H)
         with pytest.raises(RaymarcherError) as e:
             renderer.render(tables_of(scene), s, W, H)
         assert e.value.status == abi.RM_ERR_UNSUPPORTED, name
         h.oracle_render(scene, s, W, H, expect=abi.RM_ERR_UNSUPPORTED)
-    assert (renderer.torch.from_numpy(h.oracle_ltc_quantise(synthetic_ltc()[0])).numpy() ==
-            __import__("raymarcher_amd").render.ltc_quantise(synthetic_ltc()[0])).all()
+    assert (renderer.torch.from_numpy(h.oracle_ltc_quantise(SB.synthetic_ltc()[0])).numpy() ==
+            __import__("raymarcher_amd").render.ltc_quantise(SB.synthetic_ltc()[0])).all()
 
 
 # ---------------------------------------------------------------- edge cases of the boundary
 def test_row_ranges_and_ragged_sizes(renderer):
     W, H = 37, 29  # not multiples of the 8×8 wave tile
-    scene = all_primitives_scene(W, H)
+    scene = SB.all_primitives_scene(W, H)
     s = abi.default_settings(maxSteps=48)
     ref = h.oracle_render(scene, s, W, H)
     full = renderer.render(tables_of(scene), s, W, H).cpu().numpy()
@@ -917,7 +672,7 @@ def test_tiles_gather_roundtrip_with_root_relief(renderer):
             for k, p in enumerate(parts):
                 rows = [L.rm_shard_row_to_frame(H, T, k, shards, r) for r in range(p.shape[0])]
                 assert_bit_equal(p.cpu().numpy(), ref[rows], f"shard {k}/{shards}, relief {K}")
-            assert _ieq(renderer.deinterleave(torch.cat(parts, 0).contiguous(), W, H, T, shards), full)
+            assert SB.ieq(renderer.deinterleave(torch.cat(parts, 0).contiguous(), W, H, T, shards), full)
             slot = L.rm_gather_slot_rows(H, T, shards)
             assert slot == max(p.shape[0] for p in parts)
             gathered = torch.zeros((shards * slot, W, 4), dtype=torch.float32, device=full.device)
@@ -925,7 +680,7 @@ def test_tiles_gather_roundtrip_with_root_relief(renderer):
             for k, p in enumerate(parts):
                 gathered[k * slot:k * slot + p.shape[0]] = p
                 g8[k * slot:k * slot + p.shape[0]] = renderer.tiles_to_rgba8(p)
-            assert _ieq(renderer.deinterleave(gathered, W, H, T, shards, slot), full)
+            assert SB.ieq(renderer.deinterleave(gathered, W, H, T, shards, slot), full)
             assert bool((renderer.deinterleave_rgba8(g8, W, H, T, shards, slot, flip=True) == img).all())
             assert bool((renderer.deinterleave_rgba8(g8, W, H, T, shards, slot, flip=False) == img.flip(0)).all())
     finally:
@@ -969,9 +724,9 @@ def test_counters_of_every_kernel_class_match_oracle(renderer):
     evaluations — from the counting instantiations of the plain, layer and sampler kernels against the oracle's own count, and
     the counted frames against the production frames."""
     W, H = 64, 40
-    cases = [(reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2), {}),
-             (env_scene(W, H), abi.default_settings(features=ENV_ALL, enableReflection=1), {}),
-             (textured_scene(W, H), abi.default_settings(), {"textures": synthetic_textures()})]
+    cases = [(SB.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2), {}),
+             (SB.env_scene(W, H), abi.default_settings(features=SB.ENV_ALL, enableReflection=1), {}),
+             (SB.textured_scene(W, H), abi.default_settings(), {"textures": SB.synthetic_textures()})]
     for scene, s, res in cases:
         ref, cnt = h.oracle_render(scene, s, W, H, counters=True, **res)
         t = tables_of(scene)
@@ -987,7 +742,7 @@ def test_counters_of_every_kernel_class_match_oracle(renderer):
     scene, s, _ = cases[0]
     out, g1 = renderer.render_counted(tables_of(scene), s, W, H)
     out2, g2 = renderer.render_counted(tables_of(scene), s, W, H, abi.RM_COUNT_EXECUTED)
-    assert _ieq(out, out2) and g2.sceneEvals <= g1.sceneEvals and 0 < g2.shapeEvals < g1.shapeEvals
+    assert SB.ieq(out, out2) and g2.sceneEvals <= g1.sceneEvals and 0 < g2.shapeEvals < g1.shapeEvals
 
 
 def test_rgba8_flip_and_png(renderer, tmp_path):
@@ -1017,15 +772,15 @@ def test_full_size_properties_4k_bulb(renderer):
     s = abi.default_settings(fractalIters=12)
     a = renderer.render(t, s, W, H).clone()
     b = renderer.render(t, s, W, H)  # second frame: tiles start heaviest-first by the first frame's costs
-    assert _ieq(a, b)
+    assert SB.ieq(a, b)
     lib().rm_set_tile_order(0)
     try:
-        assert _ieq(a, renderer.render(t, s, W, H))  # raster order
+        assert SB.ieq(a, renderer.render(t, s, W, H))  # raster order
     finally:
         lib().rm_set_tile_order(-1)
     band = renderer.render(t, s, W, H, 1000, 1100)
-    assert _ieq(band, a[1000:1100])
-    ref = h.oracle_render(_scene_tuple(t), s, W, H, threads=16)
+    assert SB.ieq(band, a[1000:1100])
+    ref = h.oracle_render(SB.scene_tuple(t), s, W, H, threads=16)
     assert_bit_equal(a.cpu().numpy(), ref, "the whole 4K Mandelbulb frame")
     hit = float((a[..., 0] != 1.0).float().mean())
     assert 0.25 < hit < 0.40  # ≈0.33 of the pixels hit the bulb
@@ -1048,7 +803,7 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
             outs.append(h.render_guarded(renderer, tables_of(scene), s, W, H, **kw).clone())
         return outs
 
-    prim = all_primitives_scene(W, H)
+    prim = SB.all_primitives_scene(W, H)
     moved = (h.make_camera((0.6, 2.2, 6.5), (-0.1, -0.3, -1), (0, 1, 0), 45.0, W, H),) + prim[1:]
     bulb = h.scene_mandelbulb(W, H)
     sier = (prim[0], (abi.RmObject * 2)(h.make_object(abi.RM_SIERPINSKI, model=h.scale(0.8, 0.8, 0.8), scale_factor=0.8, diffuse=(.8, .6, .3)),
@@ -1058,14 +813,14 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
     sb = abi.default_settings(fractalIters=8, maxSteps=96)
     # new, same, same, moved camera, back, changed settings, another class, an unbounded object (raster fallback), the layers
     seq = [(prim, s0), (prim, s0), (prim, s0), (moved, s0), (prim, s0), (prim, s1), (bulb, sb), (bulb, sb), (sier, s0), (sier, s0),
-           (env_scene(W, H), abi.default_settings(features=ENV_ALL, maxSteps=64))]
+           (SB.env_scene(W, H), abi.default_settings(features=SB.ENV_ALL, maxSteps=64))]
     try:
         assert L.rm_set_tile_order(0) == 0
         want = frames(seq)
         assert L.rm_set_tile_order(1) == 0
         got = frames(seq)
         for k, (a, b) in enumerate(zip(got, want)):
-            assert _ieq(a, b), f"frame {k} of the sequence differs from its raster-order render"
+            assert SB.ieq(a, b), f"frame {k} of the sequence differs from its raster-order render"
         for k in (0, 3, 6):
             scene, s = seq[k]
             assert_bit_equal(got[k].cpu().numpy(), h.oracle_render(scene, s, W, H), f"frame {k} vs oracle")
@@ -1077,11 +832,11 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
         full = h.render_guarded(renderer, t, s0, W, H2).clone()
         L.rm_set_tile_order(1)
         for _ in range(2):
-            assert _ieq(h.render_guarded(renderer, t, s0, W, H2), full)
-            assert _ieq(h.render_guarded(renderer, t, s0, W, H2, row_begin=200, row_end=904), full[200:904])
+            assert SB.ieq(h.render_guarded(renderer, t, s0, W, H2), full)
+            assert SB.ieq(h.render_guarded(renderer, t, s0, W, H2, row_begin=200, row_end=904), full[200:904])
             mine = h.render_tiles_guarded(renderer, t, s0, W, H2, 8, 1, 2)
             rows = [L.rm_shard_row_to_frame(H2, 8, 1, 2, i) for i in range(mine.shape[0])]
-            assert _ieq(mine, full[torch.tensor(rows, device=full.device)])
+            assert SB.ieq(mine, full[torch.tensor(rows, device=full.device)])
         # a picture that repeats settles (the fourth cost-ordered frame on reuses the third's order: no ordering launches, no cost
         # atomics); the picture after a settled one is ordered by geometry + the costs the last sort kept
         settle = [(bulb, sb)] * 7 + [(prim, s0)] + [(bulb, sb)] * 6 + [(moved, s0)] * 14 + [(prim, s0), (moved, s0)]
@@ -1089,7 +844,7 @@ def test_tile_order_of_new_and_repeated_pictures_never_changes_a_pixel(renderer)
         want = {id(sc): h.render_guarded(renderer, tables_of(sc), st, W, H).clone() for sc, st in ((bulb, sb), (prim, s0), (moved, s0))}
         L.rm_set_tile_order(1)
         for k, (sc, st) in enumerate(settle):
-            assert _ieq(h.render_guarded(renderer, tables_of(sc), st, W, H), want[id(sc)]), f"frame {k} of the settling sequence"
+            assert SB.ieq(h.render_guarded(renderer, tables_of(sc), st, W, H), want[id(sc)]), f"frame {k} of the settling sequence"
     finally:
         L.rm_set_tile_order(-1)
 
@@ -1105,7 +860,7 @@ def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, 
     from raymarcher_amd import lib
     L = lib()
     W, H = 636, 388  # 80 x 49 8×8 tiles, ragged on both edges
-    prim = all_primitives_scene(W, H)
+    prim = SB.all_primitives_scene(W, H)
     lights = (abi.RmLight * 4)(
         h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.4, -1, -0.5)),
         h.make_light(abi.RM_LIGHT_POINT, (1, .9, .7), pos=(3, 2, 4), func=(0.7, 0.05, 0.01)),
@@ -1123,37 +878,37 @@ def test_light_split_of_a_settled_picture_never_changes_a_pixel(renderer, soft, 
         assert L.rm_debug_last_split() == 0
         split = 0
         for k in range(8):
-            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"repeat {k + 1} differs"
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H), first), f"repeat {k + 1} differs"
             split = max(split, L.rm_debug_last_split())
         tiles = (-(-W // 8)) * (-(-H // 8)) if shape == 3 else (-(-W // 4)) * (-(-H // 16))
         assert split == tiles // 32, "the settled picture was not split"
         # a row range is another picture: it settles and splits on its own
         for k in range(7):
-            assert _ieq(h.render_guarded(renderer, t, s, W, H, row_begin=40, row_end=364), first[40:364]), f"row range, frame {k}"
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H, row_begin=40, row_end=364), first[40:364]), f"row range, frame {k}"
         assert L.rm_debug_last_split() > 0
         # a frame whose pixels can spawn secondary rays is not eligible
-        prim2 = all_primitives_scene(W, H)
+        prim2 = SB.all_primitives_scene(W, H)
         for c in range(3):
             prim2[1][3].cReflective[c] = 0.4
         t2 = tables_of((prim2[0], prim2[1], prim2[2], lights, 4, prim2[5]))
         s2 = abi.default_settings(maxSteps=96, enableSoftShadow=soft, enableAmbientOcclusion=ao, enableReflection=1)
         ref2 = h.render_guarded(renderer, t2, s2, W, H).clone()
         for k in range(6):
-            assert _ieq(h.render_guarded(renderer, t2, s2, W, H), ref2)
+            assert SB.ieq(h.render_guarded(renderer, t2, s2, W, H), ref2)
         assert L.rm_debug_last_split() == 0
         # every tile split — 200 frames of it: the tiles' workgroups hand their results over through memory inside one launch
         # (release / acquire around a per-tile arrival counter), and whichever of them arrives last finishes the tile
         assert L.rm_debug_set_light_split(1) == 0
         for k in range(200):
-            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"all tiles split, frame {k}"
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H), first), f"all tiles split, frame {k}"
         assert L.rm_debug_last_split() == tiles
         assert L.rm_debug_set_light_split(0) == 0
-        assert _ieq(h.render_guarded(renderer, t, s, W, H), first) and L.rm_debug_last_split() == 0
+        assert SB.ieq(h.render_guarded(renderer, t, s, W, H), first) and L.rm_debug_last_split() == 0
         # the default: the launcher measures (two plain frames, two split, then the better) — whatever it decides, the same frame
         assert L.rm_debug_set_light_split(-1) == 0
         seen = set()
         for k in range(20):
-            assert _ieq(h.render_guarded(renderer, t, s, W, H), first), f"measured mode, frame {k}"
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H), first), f"measured mode, frame {k}"
             seen.add(L.rm_debug_last_split())
         assert seen <= {0, tiles // 256} and tiles // 256 in seen  # its two split frames ran
     finally:
@@ -1169,7 +924,7 @@ def test_tile_shape_tuner_never_changes_a_pixel(renderer):
     from raymarcher_amd import lib
     L = lib()
     W, H = 640, 400  # 4000 8×8 tiles, 4000 4×16 tiles
-    scene = all_primitives_scene(W, H)
+    scene = SB.all_primitives_scene(W, H)
     t = tables_of(scene)
     s = abi.default_settings(maxSteps=96, enableSoftShadow=1)
     try:
@@ -1178,14 +933,14 @@ def test_tile_shape_tuner_never_changes_a_pixel(renderer):
         assert_bit_equal(ref.cpu().numpy(), h.oracle_render(scene, s, W, H), "8×8 tiles vs oracle")
         assert L.rm_debug_set_tile_shape(2) == 0
         for _ in range(2):
-            assert _ieq(h.render_guarded(renderer, t, s, W, H), ref)
-        assert _ieq(h.render_guarded(renderer, t, s, W, H, row_begin=33, row_end=377), ref[33:377])
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H), ref)
+        assert SB.ieq(h.render_guarded(renderer, t, s, W, H, row_begin=33, row_end=377), ref[33:377])
         mine = h.render_tiles_guarded(renderer, t, s, W, H, 8, 1, 3)
         rows = [L.rm_shard_row_to_frame(H, 8, 1, 3, i) for i in range(mine.shape[0])]
-        assert _ieq(mine, ref[torch.tensor(rows, device=ref.device)])
+        assert SB.ieq(mine, ref[torch.tensor(rows, device=ref.device)])
         assert L.rm_debug_set_tile_shape(0) == 0
         for k in range(14):  # the tuner's eight frames, its decision, and frames after it
-            assert _ieq(h.render_guarded(renderer, t, s, W, H), ref), f"frame {k} of the tuned sequence differs"
+            assert SB.ieq(h.render_guarded(renderer, t, s, W, H), ref), f"frame {k} of the tuned sequence differs"
         moved = (h.make_camera((0.5, 2.0, 6.5), (-0.1, -0.3, -1), (0, 1, 0), 45.0, W, H),) + scene[1:]
         want = h.oracle_render(moved, s, W, H)
         for k in range(3):  # a new picture restarts the measurement
@@ -1196,29 +951,17 @@ def test_tile_shape_tuner_never_changes_a_pixel(renderer):
 
 
 # ---------------------------------------------------------------- the other BASELINE.json configurations, at their full sizes
-SCENES = os.path.join(os.path.dirname(__file__), "golden", "scenes")
-
-
-def _scene_tuple(t):
-    return t.camera, t.objects, t.num_objects, t.lights, t.num_lights, t.globals_
-
-
-def _ieq(a, b):
-    import torch
-    return bool((a.view(dtype=torch.int32) == b.view(dtype=torch.int32)).all())
-
-
 def test_config1_unit_sphere_256(renderer):
     """configs[0]: scenefiles/simple/unit_sphere.json through the product's loader and PNG reader, 256×256, 64 steps, Phong
     only — the whole frame against the oracle, the floor textured with the reference's own texture_store/blackmarble.png
     (tests/golden/scenes/texture_store/, input data)."""
     from raymarcher_amd import Scene
     W = H = 256
-    t = Scene(path=os.path.join(SCENES, "simple", "unit_sphere.json")).tables(W, H)
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "unit_sphere.json")).tables(W, H)
     assert t.num_objects == 2 and t.num_lights == 3 and sum(t.objects[i].texLoc == 0 for i in range(2)) == 1
     assert len(t.textures) == 1 and t.textures[0].shape == (1320, 1990, 4)  # blackmarble.png, decoded by rm_image_load
     s = abi.default_settings(maxSteps=64)
-    ref = h.oracle_render(_scene_tuple(t), s, W, H, textures=t.textures)
+    ref = h.oracle_render(SB.scene_tuple(t), s, W, H, textures=t.textures)
     assert_bit_equal(renderer.render(t, s, W, H).cpu().numpy(), ref, "unit_sphere 256²")
     assert ref[..., :3].std() > 0.05 and np.isfinite(ref).all()  # the floor fills the view behind the sphere
 
@@ -1228,13 +971,13 @@ def test_config2_lighting_1080p_softshadow_ao(renderer):
     shadows + AO: the WHOLE frame against the oracle, a row-range render against the same rows of the full frame."""
     from raymarcher_amd import Scene
     W, H = 1920, 1080
-    t = Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).tables(W, H)
+    t = Scene(path=os.path.join(SB.SCENES, "lighting", "directional_light_2.json")).tables(W, H)
     assert t.num_objects == 5 and t.num_lights == 3
     s = abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1)
     full = renderer.render(t, s, W, H)
-    ref = h.oracle_render(_scene_tuple(t), s, W, H, threads=16)
+    ref = h.oracle_render(SB.scene_tuple(t), s, W, H, threads=16)
     assert_bit_equal(full.cpu().numpy(), ref, "the whole 1080p directional_light_2 frame")
-    assert _ieq(renderer.render(t, s, W, H, 411, 623), full[411:623])
+    assert SB.ieq(renderer.render(t, s, W, H, 411, 623), full[411:623])
     assert 0.2 < float((full[..., :3] != 1.0).any(-1).float().mean()) < 0.95
 
 
@@ -1245,17 +988,17 @@ def test_config4_terrain_cloud_4k_row_tiles(renderer):
     import torch
     from raymarcher_amd import Scene, lib
     W, H, T, N = 3840, 2160, 8, 8
-    t = Scene(path=os.path.join(SCENES, "simple", "volumetric.json")).tables(W, H, far=2000.0)
-    s = abi.default_settings(features=ENV_ALL)
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "volumetric.json")).tables(W, H, far=2000.0)
+    s = abi.default_settings(features=SB.ENV_ALL)
     # (i) the scenefile exactly as it is: its camera (0,500,5) sits below the terrain surface and looks straight down, so
     # every ray starts inside the height field — a nearly black frame, but the reference's own; rows against the oracle
     asis = renderer.render(t, s, W, H)
     for r0 in (7, 1080, 2100):
-        ref = h.oracle_render(_scene_tuple(t), s, W, H, r0, r0 + 8, threads=16)
+        ref = h.oracle_render(SB.scene_tuple(t), s, W, H, r0, r0 + 8, threads=16)
         assert_bit_equal(asis[r0:r0 + 8].cpu().numpy(), ref, f"4K volumetric.json as is, rows {r0}..{r0 + 8}")
     # (ii) the view the layers are made for — the reference's user flies the camera: same position, looking at the
-    # horizon, as in env_scene() (DESIGN.md §6 lists both)
-    t.camera = env_scene(W, H)[0]
+    # horizon, as in SB.env_scene() (DESIGN.md §6 lists both)
+    t.camera = SB.env_scene(W, H)[0]
     full = renderer.render(t, s, W, H)
     assert 0.1 < float(torch.nan_to_num(full[..., :3]).mean()) < 1.5
     slot = lib().rm_shard_rows(H, T, 0, N)
@@ -1264,9 +1007,9 @@ def test_config4_terrain_cloud_4k_row_tiles(renderer):
         mine = renderer.render_tiles(t, s, W, H, T, k, N)
         assert mine.shape[0] == lib().rm_shard_rows(H, T, k, N)
         gathered[k * slot:k * slot + mine.shape[0]] = mine
-    assert _ieq(renderer.deinterleave(gathered, W, H, T, N, slot), full)
+    assert SB.ieq(renderer.deinterleave(gathered, W, H, T, N, slot), full)
     for r0 in (40, 1400):
-        ref = h.oracle_render(_scene_tuple(t), s, W, H, r0, r0 + 16, threads=16)
+        ref = h.oracle_render(SB.scene_tuple(t), s, W, H, r0, r0 + 16, threads=16)
         assert_bit_equal(full[r0:r0 + 16].cpu().numpy(), ref, f"4K env rows {r0}..{r0 + 16}")
     # a cloud sample exactly at y = 900 has gradient sign(0) = 0 and the reference normalises it (frag:1996): NaN there too
     assert float((~torch.isfinite(full).all(-1)).float().mean()) < 1e-4
@@ -1278,7 +1021,7 @@ def test_config5_menger_8k_reflection(renderer):
     import torch
     from raymarcher_amd import Scene, lib
     W, H, T, N = 7680, 4320, 8, 8
-    t = Scene(path=os.path.join(SCENES, "simple", "unit_mengersponge.json")).tables(W, H)  # the reference's own scenefile
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "unit_mengersponge.json")).tables(W, H)  # the reference's own scenefile
     assert t.num_objects == 1 and t.num_lights == 3 and t.objects[0].type == abi.RM_MENGERSPONGE
     s = abi.default_settings(mengerLevels=5, numReflection=2, enableReflection=1)
     full = renderer.render(t, s, W, H)
@@ -1288,11 +1031,11 @@ def test_config5_menger_8k_reflection(renderer):
     # a row-TILE shard of 4.1 M pixels takes the wavefront pipeline too (multi-GPU hosts keep frames in flight: threshold 2^21)
     assert lib().rm_debug_last_path() == 5
     rows = [lib().rm_shard_row_to_frame(H, T, k, N, i) for i in range(mine.shape[0])]
-    assert _ieq(mine, full[torch.tensor(rows, device=full.device)])
+    assert SB.ieq(mine, full[torch.tensor(rows, device=full.device)])
     band = renderer.render(t, s, W, H, row_begin=1000, row_end=1000 + mine.shape[0])  # the same pixel count as a plain row range: 2^22 applies
-    assert lib().rm_debug_last_path() == 1 and _ieq(band, full[1000:1000 + mine.shape[0]])
+    assert lib().rm_debug_last_path() == 1 and SB.ieq(band, full[1000:1000 + mine.shape[0]])
     for r0 in (2160, 3000):
-        ref = h.oracle_render(_scene_tuple(t), s, W, H, r0, r0 + 8, threads=16)
+        ref = h.oracle_render(SB.scene_tuple(t), s, W, H, r0, r0 + 8, threads=16)
         assert_bit_equal(full[r0:r0 + 8].cpu().numpy(), ref, f"8K rows {r0}..{r0 + 8}")
     hit = float((full[..., :3] != 1.0).any(-1).float().mean())
     assert 0.1 < hit < 0.9
@@ -1346,13 +1089,13 @@ def _random_case(rng, W, H):
     n_obj = int(rng.integers(1, 7))
     types = [abi.RM_CUBE, abi.RM_CONE, abi.RM_CYLINDER, abi.RM_SPHERE, abi.RM_OCTAHEDRON, abi.RM_TORUS, abi.RM_CAPSULE,
              abi.RM_DEATHSTAR, abi.RM_RECTANGLE, abi.RM_MANDELBULB, abi.RM_MENGERSPONGE, abi.RM_SIERPINSKI]
-    texs = synthetic_textures()
+    texs = SB.synthetic_textures()
     objs = []
     for _ in range(n_obj):
         ty = int(rng.choice(types))
         sc = float(f(0.6, 1.8))
         sx, sy, sz = (sc * float(f(0.8, 1.25)) for _ in range(3))
-        M = h.translate(f(-2.2, 2.2), f(-1.0, 1.2), f(-2.5, 1.0)) @ rot_x(f(-0.6, 0.6)) @ h.scale(sx, sy, sz)
+        M = h.translate(f(-2.2, 2.2), f(-1.0, 1.2), f(-2.5, 1.0)) @ SB.rot_x(f(-0.6, 0.6)) @ h.scale(sx, sy, sz)
         o = h.make_object(ty, model=M, scale_factor=min(sx, sy, sz), ambient=tuple(f(0, .3, 3)), diffuse=tuple(f(.2, 1, 3)),
                           specular=tuple(f(0, 1, 3)), shininess=float(rng.choice([0, 1, 7.5, 25, 100])),
                           reflective=tuple(f(0, .8, 3)) if f() < 0.4 else (0, 0, 0),
@@ -1375,7 +1118,7 @@ def _random_case(rng, W, H):
     if any(o.texLoc >= 0 for o in objs):
         res["textures"] = texs
     if f() < 0.3:  # an area light with its emissive rectangle
-        ctm = h.translate(f(-1, 1), f(2, 3), f(-2, 0)) @ rot_x(f(0.8, 1.5)) @ h.scale(f(1, 3), f(1, 2), 1.0)
+        ctm = h.translate(f(-1, 1), f(2, 3), f(-2, 0)) @ SB.rot_x(f(0.8, 1.5)) @ h.scale(f(1, 3), f(1, 2), 1.0)
         rect = h.make_object(abi.RM_RECTANGLE, model=ctm, scale_factor=1.0)
         rect.isEmissive, rect.lightIdx = 1, len(lights)
         area = h.make_light(abi.RM_LIGHT_AREA, tuple(f(.5, 1.2, 3)))
@@ -1386,7 +1129,7 @@ def _random_case(rng, W, H):
                 area.points[k][j], rect.color[j] = float(np.float32(w[j])), area.color[j]
         objs.append(rect)
         lights.append(area)
-        t1, t2 = synthetic_ltc()
+        t1, t2 = SB.synthetic_ltc()
         res["ltc1"], res["ltc2"] = h.oracle_ltc_quantise(t1), h.oracle_ltc_quantise(t2)
     feats = int(rng.choice([abi.RM_FEAT_WHITE_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, 0, abi.RM_FEAT_SKY_BACKGROUND,
                             abi.RM_FEAT_NIGHTSKY_BACKGROUND]))
@@ -1397,10 +1140,10 @@ def _random_case(rng, W, H):
     if f() < 0.3:
         feats |= abi.RM_FEAT_BULB_POWER8_ALGEBRAIC
     if feats & (abi.RM_FEAT_NIGHTSKY_BACKGROUND | abi.RM_FEAT_SEA):
-        res["noise"] = synthetic_noise()
+        res["noise"] = SB.synthetic_noise()
     sky = f() < 0.25
     if sky:
-        res["skybox"] = synthetic_skybox(12)
+        res["skybox"] = SB.synthetic_skybox(12)
     s = abi.default_settings(features=feats, enableSoftShadow=int(f() < 0.3), enableAmbientOcclusion=int(f() < 0.4),
                              enableReflection=int(f() < 0.5), enableRefraction=int(f() < 0.4), enableSkyBox=int(sky),
                              maxSteps=int(rng.choice([64, 128, 256])), fractalIters=int(rng.choice([6, 12, 20])),
@@ -1429,50 +1172,9 @@ def test_random_scenes_bit_exact(renderer):
         assert_bit_equal(br.cpu().numpy(), ref_b, f"random scene {i} bright")
         if (W // 8) * (H // 8) >= 2048:
             for rep in range(3):
-                assert _ieq(h.render_guarded(renderer, t, s, W, H), out), f"random scene {i}: repeat {rep + 1} differs"
+                assert SB.ieq(h.render_guarded(renderer, t, s, W, H), out), f"random scene {i}: repeat {rep + 1} differs"
         kinds |= {scene[1][k].type for k in range(scene[2])}
     assert len(kinds) >= 10
-
-
-def _random_primitive_case(rng, W, H):
-    """A random all-primitive table (the class of the table walk's pass-over test AND of the march loops' single-object fast
-    path), one to eight objects, sometimes over a floor slab, two to ten lights of the three plain kinds, every shading option."""
-    f = rng.uniform
-    types = [abi.RM_CUBE, abi.RM_CONE, abi.RM_CYLINDER, abi.RM_SPHERE, abi.RM_OCTAHEDRON, abi.RM_TORUS, abi.RM_CAPSULE,
-             abi.RM_DEATHSTAR, abi.RM_RECTANGLE]
-    objs = []
-    for _ in range(int(rng.integers(1, 9))):
-        ty = int(rng.choice(types))
-        sc = float(f(0.6, 1.8))
-        sx, sy, sz = (sc * float(f(0.8, 1.25)) for _ in range(3))
-        M = h.translate(f(-2.2, 2.2), f(-1.0, 1.2), f(-2.5, 1.0)) @ rot_x(f(-0.6, 0.6)) @ h.scale(sx, sy, sz)
-        objs.append(h.make_object(ty, model=M, scale_factor=min(sx, sy, sz), ambient=tuple(f(0, .3, 3)), diffuse=tuple(f(.2, 1, 3)),
-                                  specular=tuple(f(0, 1, 3)), shininess=float(rng.choice([0, 1, 7.5, 25, 100])),
-                                  reflective=tuple(f(0, .8, 3)) if f() < 0.4 else (0, 0, 0),
-                                  transparent=tuple(f(0, .8, 3)) if f() < 0.3 else (0, 0, 0), ior=float(f(1.05, 1.6))))
-    if f() < 0.5:  # a floor: long grazing shadow rays
-        objs.append(h.make_object(abi.RM_CUBE, model=h.translate(0, -1.6, -1) @ h.scale(9, 0.2, 9), scale_factor=0.2,
-                                  diffuse=(.7, .7, .7), ambient=(.1, .1, .1)))
-    lights = []
-    for _ in range(int(rng.choice([2, 2, 3, 3, 3, 4, 5, 6, 7, 10]))):
-        kind = int(rng.integers(0, 3))
-        col = tuple(f(.2, 1.2, 3))
-        if kind == abi.RM_LIGHT_DIRECTIONAL:
-            lights.append(h.make_light(kind, col, direction=(f(-1, 1), f(-1, 0.6), f(-1, 1))))
-        elif kind == abi.RM_LIGHT_POINT:
-            lights.append(h.make_light(kind, col, pos=(f(-4, 4), f(-1, 5), f(-3, 5)), func=(f(.5, 1), f(0, .1), f(0, .02))))
-        else:
-            lights.append(h.make_light(kind, col, direction=(f(-.3, .3), -1, f(-.6, 0)), pos=(f(-2, 2), f(3, 5), f(0, 3)),
-                                       func=(f(.5, 1), f(0, .1), 0), angle=float(f(.4, .9)), penumbra=float(f(.05, .3))))
-    feats = int(rng.choice([abi.RM_FEAT_WHITE_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, 0]))
-    if f() < 0.5:
-        feats |= abi.RM_FEAT_PERLIN_BUMP
-    s = abi.default_settings(features=feats, enableSoftShadow=int(f() < 0.5), enableAmbientOcclusion=int(f() < 0.4),
-                             enableReflection=int(f() < 0.4), enableRefraction=int(f() < 0.3),
-                             maxSteps=int(rng.choice([16, 64, 256])), numReflection=int(rng.choice([1, 2, 3])))
-    g = h.make_globals(ka=f(.2, .8), kd=f(.3, 1), ks=f(.2, 1), kt=f(.2, 1))
-    cam = h.make_camera((f(-1, 1), f(0.5, 2.5), f(4.5, 6.5)), (f(-.15, .15), f(-.45, -.05), -1), (0, 1, 0), float(f(35, 60)), W, H)
-    return (cam, (abi.RmObject * len(objs))(*objs), len(objs), (abi.RmLight * len(lights))(*lights), len(lights), g), s
 
 
 def test_random_primitive_scenes_bit_exact(renderer):
@@ -1482,7 +1184,7 @@ def test_random_primitive_scenes_bit_exact(renderer):
     W, H = 56, 40
     rng = np.random.default_rng(int(os.environ.get("RM_FUZZ_SEED", "20261007")))
     for i in range(int(os.environ.get("RM_FUZZ_CASES", "32"))):
-        scene, s = _random_primitive_case(rng, W, H)
+        scene, s = SB.random_primitive_case(rng, W, H)
         ref, ref_b = h.oracle_render(scene, s, W, H, bright=True)
         out, br = renderer.render(tables_of(scene), s, W, H, bright=True)
         assert_bit_equal(out.cpu().numpy(), ref, f"random primitive scene {i}")
@@ -1491,59 +1193,9 @@ def test_random_primitive_scenes_bit_exact(renderer):
             try:
                 lib().rm_set_kernel_path(5)
                 wf = renderer.render(tables_of(scene), s, W, H)
-                assert lib().rm_debug_last_path() == 5 and _ieq(wf, out)
+                assert lib().rm_debug_last_path() == 5 and SB.ieq(wf, out)
             finally:
                 lib().rm_set_kernel_path(0)
-
-
-def _random_tablewalk_case(rng, W, H):
-    """A WIDE random all-primitive scene (helpers.random_tablewalk_objects: arbitrary-axis rotations, shear, anisotropy 0.2–5,
-    scaleFactors that are not the smallest scale, nested and coincident objects, tables of up to 30), sometimes over a floor slab
-    or inside an enclosing box, one to ten lights of the three plain kinds, every shading option, cameras outside, inside an
-    object, or on an object's surface."""
-    f = rng.uniform
-    objs = h.random_tablewalk_objects(rng, max_objects=28)
-    if f() < 0.4:  # a floor: long grazing shadow rays
-        objs.append(h.make_object(abi.RM_CUBE, model=h.translate(0, -1.8, -1) @ h.scale(11, 0.2, 11), scale_factor=0.2,
-                                  diffuse=(.7, .7, .7), ambient=(.1, .1, .1), reflective=(.3, .3, .3) if f() < 0.3 else (0, 0, 0)))
-    if f() < 0.15:  # everything (camera too) inside one big cube: every ray hits, negative distances never occur but no ray leaves
-        objs.append(h.make_object(abi.RM_CUBE, model=h.scale(24, 24, 24), scale_factor=24, diffuse=(.4, .5, .4), ambient=(.1, .1, .1)))
-    lights = []
-    for _ in range(int(rng.choice([1, 2, 2, 3, 3, 3, 4, 5, 7, 10]))):
-        kind = int(rng.integers(0, 3))
-        col = tuple(f(.2, 1.2, 3))
-        if kind == abi.RM_LIGHT_DIRECTIONAL:
-            lights.append(h.make_light(kind, col, direction=(f(-1, 1), f(-1, 0.6), f(-1, 1))))
-        elif kind == abi.RM_LIGHT_POINT:
-            lights.append(h.make_light(kind, col, pos=(f(-4, 4), f(-1, 5), f(-3, 5)), func=(f(.5, 1), f(0, .1), f(0, .02))))
-        else:
-            lights.append(h.make_light(kind, col, direction=(f(-.3, .3), -1, f(-.6, 0)), pos=(f(-2, 2), f(3, 5), f(0, 3)),
-                                       func=(f(.5, 1), f(0, .1), 0), angle=float(f(.4, .9)), penumbra=float(f(.05, .3))))
-    feats = int(rng.choice([abi.RM_FEAT_WHITE_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, 0]))
-    if f() < 0.5:
-        feats |= abi.RM_FEAT_PERLIN_BUMP
-    s = abi.default_settings(features=feats, enableSoftShadow=int(f() < 0.5), enableAmbientOcclusion=int(f() < 0.4),
-                             enableReflection=int(f() < 0.4), enableRefraction=int(f() < 0.3),
-                             maxSteps=int(rng.choice([16, 64, 256, 256])), numReflection=int(rng.choice([1, 2, 3])))
-    g = h.make_globals(ka=f(.2, .8), kd=f(.3, 1), ks=f(.2, 1), kt=f(.2, 1))
-    where = f()
-    if where < 0.2:  # the camera inside an object (its near plane, where rays start, may still be outside a small one)
-        o = objs[int(rng.integers(0, len(objs)))]
-        M = np.linalg.inv(np.array(list(o.invModel), dtype=np.float64).reshape(4, 4).T)
-        pos = tuple((M @ np.array([*f(-0.15, 0.15, 3), 1.0]))[:3])
-        look = tuple(f(-1, 1, 3) + np.array([0, 0, -0.3]))
-    elif where < 0.3:  # on (about) the bounding ball of an object, looking along it
-        o = objs[int(rng.integers(0, len(objs)))]
-        M = np.linalg.inv(np.array(list(o.invModel), dtype=np.float64).reshape(4, 4).T)
-        d = rng.normal(size=3)
-        pos = tuple((M @ np.array([*(d / np.linalg.norm(d) * 0.6), 1.0]))[:3])
-        look = tuple(np.cross(d, rng.normal(size=3)))
-    else:
-        pos, look = (f(-1, 1), f(0.5, 2.5), f(4.5, 6.5)), (f(-.15, .15), f(-.45, -.05), -1)
-    if np.linalg.norm(look) < 1e-3 or abs(np.dot(look, (0, 1, 0))) > 0.98 * np.linalg.norm(look):
-        look = (0.1, -0.2, -1)
-    cam = h.make_camera(pos, look, (0, 1, 0), float(f(35, 70)), W, H)
-    return (cam, (abi.RmObject * len(objs))(*objs), len(objs), (abi.RmLight * len(lights))(*lights), len(lights), g), s
 
 
 def test_random_tablewalk_scenes_bit_exact(renderer):
@@ -1561,21 +1213,21 @@ def test_random_tablewalk_scenes_bit_exact(renderer):
     cases = int(os.environ.get("RM_FUZZ_CASES", "128"))
     stats = {"objects": 0, "max_objects": 0, "wavefront": 0}
     for i in range(cases):
-        scene, s = _random_tablewalk_case(rng, W, H)
+        scene, s = SB.random_tablewalk_case(rng, W, H)
         ref, ref_b = h.oracle_render(scene, s, W, H, bright=True)
         out, br = renderer.render(tables_of(scene), s, W, H, bright=True)
         assert_bit_equal(out.cpu().numpy(), ref, f"seed {seed} wide table-walk scene {i} ({scene[2]} objects)")
         assert_bit_equal(br.cpu().numpy(), ref_b, f"seed {seed} wide table-walk scene {i} bright")
         if (W // 8) * (H // 8) >= 2048:
             for rep in range(3):
-                assert _ieq(renderer.render(tables_of(scene), s, W, H), out), f"seed {seed} scene {i}: repeat {rep + 1} differs"
+                assert SB.ieq(renderer.render(tables_of(scene), s, W, H), out), f"seed {seed} scene {i}: repeat {rep + 1} differs"
             # … and with the tile shape pinned the picture settles by its fifth frame: the sixth has its heaviest eighth of the tiles
             # rendered one light per workgroup where the scene is eligible (no secondary rays, two or more lights)
             try:
                 lib().rm_debug_set_tile_shape(3)
                 lib().rm_debug_set_light_split(8)
                 for rep in range(6):
-                    assert _ieq(renderer.render(tables_of(scene), s, W, H), out), f"seed {seed} scene {i}: pinned repeat {rep + 1} differs"
+                    assert SB.ieq(renderer.render(tables_of(scene), s, W, H), out), f"seed {seed} scene {i}: pinned repeat {rep + 1} differs"
                 stats["split"] = stats.get("split", 0) + (1 if lib().rm_debug_last_split() > 0 else 0)
             finally:
                 lib().rm_debug_set_tile_shape(-1)
@@ -1586,57 +1238,13 @@ def test_random_tablewalk_scenes_bit_exact(renderer):
             try:
                 lib().rm_set_kernel_path(5)
                 wf = renderer.render(tables_of(scene), s, W, H)
-                assert lib().rm_debug_last_path() == 5 and _ieq(wf, out), f"seed {seed} scene {i}: wavefront differs"
+                assert lib().rm_debug_last_path() == 5 and SB.ieq(wf, out), f"seed {seed} scene {i}: wavefront differs"
                 stats["wavefront"] += 1
             finally:
                 lib().rm_set_kernel_path(0)
     print(f"FUZZ_SUMMARY seed={seed} cases={cases} mismatched_words=0 mean_objects={stats['objects'] / max(cases, 1):.1f} "
           f"max_objects={stats['max_objects']} wavefront_cases={stats['wavefront']} light_split_cases={stats.get('split', 0)}")
     assert stats["max_objects"] >= 20 or cases < 32
-
-
-def _random_bulb_case(rng, W, H):
-    """A random scene of the single-Mandelbulb class (its own kernel instantiation: bounding-ball culls of two radii,
-    v_min orbit trap, per-lane shadow-ray queue): model transform incl. anisotropic scales and tiny objects, Julia seeds
-    inside and outside the tight ball's bound, powers, 1–5 lights of any kind (all-directional sets take the queue), every
-    option, camera anywhere around — also inside the ball."""
-    f = rng.uniform
-    sc = float(rng.choice([1.0, 1.0, 1.7, 0.4, 0.04, 0.008]))
-    an = (1.0, 1.0, 1.0) if f() < 0.7 else tuple(f(0.6, 2.5, 3))
-    M = h.translate(*(f(-0.4, 0.4, 3) * sc)) @ rot_x(f(-1.0, 1.0)) @ h.scale(sc * an[0], sc * an[1], sc * an[2])
-    o = h.make_object(abi.RM_MANDELBULB, model=M, scale_factor=sc * min(an), ambient=tuple(f(0, .4, 3)), diffuse=tuple(f(.2, 1, 3)),
-                      specular=tuple(f(0, 1, 3)), shininess=float(rng.choice([0, 7.5, 25, 100])),
-                      reflective=tuple(f(0, .8, 3)) if f() < 0.3 else (0, 0, 0),
-                      transparent=tuple(f(0, .8, 3)) if f() < 0.2 else (0, 0, 0), ior=float(f(1.05, 1.6)))
-    lights = []
-    all_dir = f() < 0.6
-    for _ in range(int(rng.integers(1, 6))):
-        kind = abi.RM_LIGHT_DIRECTIONAL if all_dir else int(rng.integers(0, 3))
-        col = tuple(f(.3, 1.6, 3))
-        if kind == abi.RM_LIGHT_DIRECTIONAL:
-            d = f(-1, 1, 3)
-            lights.append(h.make_light(kind, col, direction=tuple(d if np.abs(d).max() > 0.1 else (0, -1, 0))))
-        elif kind == abi.RM_LIGHT_POINT:
-            lights.append(h.make_light(kind, col, pos=tuple(f(-4, 4, 3) * max(sc, 0.2)), func=(f(.5, 1), f(0, .1), f(0, .02))))
-        else:
-            lights.append(h.make_light(kind, col, direction=(f(-.3, .3), -1, f(-.6, 0)), pos=(f(-2, 2) * sc, f(3, 5) * sc, f(0, 3) * sc),
-                                       func=(f(.5, 1), f(0, .1), 0), angle=float(f(.4, .9)), penumbra=float(f(.05, .3))))
-    feats = int(rng.choice([abi.RM_FEAT_WHITE_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, 0])) | (abi.RM_FEAT_PERLIN_BUMP if f() < 0.6 else 0)
-    if f() < 0.2:
-        feats |= abi.RM_FEAT_BULB_POWER8_ALGEBRAIC
-    s = abi.default_settings(features=feats, enableSoftShadow=int(f() < 0.25), enableAmbientOcclusion=int(f() < 0.3),
-                             enableReflection=int(f() < 0.4), enableRefraction=int(f() < 0.3),
-                             maxSteps=int(rng.choice([1, 17, 64, 256])), fractalIters=int(rng.choice([1, 4, 12, 20])),
-                             numReflection=int(rng.choice([1, 2])))
-    julia = (0, 0) if f() < 0.6 else (tuple(f(-.6, .6, 2)) if f() < 0.6 else tuple(f(-1.6, 1.6, 2)))
-    g = h.make_globals(ka=f(.2, .8), kd=f(.3, 1), ks=f(.2, 1), kt=f(.2, 1), power=float(rng.choice([8.0, 8.0, 8.0, 6.0, 3.5])), julia=julia)
-    dist = float(rng.choice([4.5, 3.0, 1.6, 0.8])) * sc * max(an)
-    dirv = f(-1, 1, 3)
-    dirv = dirv / (np.linalg.norm(dirv) + 1e-9)
-    pos = tuple(dirv * dist)
-    look = tuple(-dirv + f(-0.15, 0.15, 3))
-    cam = h.make_camera(pos, look, (0.1, 1, 0.05), float(f(25, 70)), W, H, near=0.02 * dist, far=float(rng.choice([100.0, 100.0, 6.0 * dist])))
-    return (cam, (abi.RmObject * 1)(o), 1, (abi.RmLight * len(lights))(*lights), len(lights), g), s
 
 
 def test_random_bulb_scenes_bit_exact(renderer):
@@ -1647,7 +1255,7 @@ def test_random_bulb_scenes_bit_exact(renderer):
     rng = np.random.default_rng(int(os.environ.get("RM_FUZZ_SEED", "20261004")))
     hits = 0
     for i in range(int(os.environ.get("RM_FUZZ_CASES", "24"))):
-        scene, s = _random_bulb_case(rng, W, H)
+        scene, s = SB.random_bulb_case(rng, W, H)
         ref, ref_b = h.oracle_render(scene, s, W, H, bright=True)
         out, br = renderer.render(tables_of(scene), s, W, H, bright=True)
         assert_bit_equal(out.cpu().numpy(), ref, f"random bulb scene {i}")
@@ -1675,7 +1283,7 @@ def test_bounding_ball_cull_edge_cases(renderer):
     # 1: slab + needle, strongly non-uniform, rotated
     objs = (abi.RmObject * 3)(
         h.make_object(abi.RM_CUBE, model=h.translate(0, -1, 0) @ rz @ h.scale(6, 0.15, 3), scale_factor=0.15, **refl),
-        h.make_object(abi.RM_CYLINDER, model=h.translate(1, 0.5, -1) @ rot_x(0.9) @ h.scale(0.2, 4, 0.2), scale_factor=0.2, **refl),
+        h.make_object(abi.RM_CYLINDER, model=h.translate(1, 0.5, -1) @ SB.rot_x(0.9) @ h.scale(0.2, 4, 0.2), scale_factor=0.2, **refl),
         h.make_object(abi.RM_TORUS, model=h.translate(-1.5, 0.4, 0.5) @ rz @ h.scale(2, 2, 0.7), scale_factor=0.7, **refl))
     cases.append((h.make_camera((0, 1.5, 6), (0, -0.25, -1), (0, 1, 0), 45.0, W, H), objs, 3, h.make_globals()))
     # 2: tiny and huge objects, far from the origin; camera inside the bounding ball
@@ -1708,7 +1316,6 @@ def test_bounding_ball_cull_edge_cases(renderer):
             assert (ref[..., :3] != 1.0).any(-1).mean() > 0.02, f"case {k}: the objects must be in view"
 
 
-
 def test_bounding_box_cull_edge_cases(renderer):
     """The launcher's bounding BOX on top of the ball (flat / elongated scenes; rm_debug_cull_bounds) must never change a bit:
     rays with exactly zero direction components (axis-aligned views and lights — the slab test divides by them), the camera on
@@ -1720,9 +1327,9 @@ def test_bounding_box_cull_edge_cases(renderer):
     objs = (abi.RmObject * 5)(
         h.make_object(abi.RM_CUBE, model=h.translate(0, -1, 0) @ h.scale(14, 0.2, 6), scale_factor=0.2, **mat),
         h.make_object(abi.RM_SPHERE, model=h.translate(-4, -0.4, 0), **mat),
-        h.make_object(abi.RM_CONE, model=h.translate(-1.5, -0.4, 0.5) @ rot_x(0.3), **mat),
+        h.make_object(abi.RM_CONE, model=h.translate(-1.5, -0.4, 0.5) @ SB.rot_x(0.3), **mat),
         h.make_object(abi.RM_CYLINDER, model=h.translate(1.5, -0.4, -0.5), **mat),
-        h.make_object(abi.RM_TORUS, model=h.translate(4.5, -0.3, 0.2) @ rot_x(1.2) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5, **mat))
+        h.make_object(abi.RM_TORUS, model=h.translate(4.5, -0.3, 0.2) @ SB.rot_x(1.2) @ h.scale(1.5, 1.5, 1.5), scale_factor=1.5, **mat))
     g = h.make_globals()
     b = np.zeros(13, dtype=np.float32)
     assert lib().rm_debug_cull_bounds(objs, 5, C.byref(g), b.ctypes.data_as(C.POINTER(C.c_float))) == 0
@@ -1760,7 +1367,6 @@ def test_bounding_box_cull_edge_cases(renderer):
         lib().rm_set_kernel_path(0)
 
 
-
 def test_table_walk_skip_edge_cases(renderer):
     """The table walk passes over objects that cannot lower a lane's minimum (sdScene<…, SKIP>, seeded by a Lipschitz bound from
     the previous step) and follows a single object while the runner-up stays above that bound (march()'s fast path): neither may
@@ -1782,8 +1388,8 @@ def test_table_walk_skip_edge_cases(renderer):
     # ties: the same sphere twice (and the same torus twice, the second pair in the other order of materials)
     cases.append((cam, [h.make_object(abi.RM_SPHERE, model=h.translate(-1.5, 0, 0), **red),
                         h.make_object(abi.RM_SPHERE, model=h.translate(-1.5, 0, 0), **blue),
-                        h.make_object(abi.RM_TORUS, model=h.translate(1.5, 0, 0) @ rot_x(0.8) @ h.scale(2, 2, 2), scale_factor=2, **blue),
-                        h.make_object(abi.RM_TORUS, model=h.translate(1.5, 0, 0) @ rot_x(0.8) @ h.scale(2, 2, 2), scale_factor=2, **red), floor]))
+                        h.make_object(abi.RM_TORUS, model=h.translate(1.5, 0, 0) @ SB.rot_x(0.8) @ h.scale(2, 2, 2), scale_factor=2, **blue),
+                        h.make_object(abi.RM_TORUS, model=h.translate(1.5, 0, 0) @ SB.rot_x(0.8) @ h.scale(2, 2, 2), scale_factor=2, **red), floor]))
     # the camera inside a large cube that holds everything else
     cases.append((cam, [h.make_object(abi.RM_CUBE, model=h.scale(30, 30, 30), scale_factor=30, diffuse=(.3, .5, .3)),
                         h.make_object(abi.RM_CONE, model=h.translate(0, 0, 0) @ h.scale(2, 2, 2), scale_factor=2, **red),
@@ -1798,9 +1404,9 @@ def test_table_walk_skip_edge_cases(renderer):
     shear[0, 1], shear[2, 0] = 0.6, -0.4
     cases.append((cam, [h.make_object(abi.RM_SPHERE, model=h.translate(-2, 0, 0) @ h.scale(1.5, 0.5, 1.5), scale_factor=1.0, **red),
                         h.make_object(abi.RM_CYLINDER, model=h.translate(0.5, 0, 0) @ shear @ h.scale(1.2, 1.2, 1.2), scale_factor=1.2, **blue),
-                        h.make_object(abi.RM_RECTANGLE, model=h.translate(2.5, 0.2, -0.5) @ rot_x(0.4) @ h.scale(2, 2, 2), scale_factor=2, **red), floor]))
+                        h.make_object(abi.RM_RECTANGLE, model=h.translate(2.5, 0.2, -0.5) @ SB.rot_x(0.4) @ h.scale(2, 2, 2), scale_factor=2, **red), floor]))
     # a single object (the runner-up bound is +inf: the march follows that object alone from its second step on)
-    cases.append((cam, [h.make_object(abi.RM_TORUS, model=rot_x(0.9) @ h.scale(3, 3, 3), scale_factor=3, **red)]))
+    cases.append((cam, [h.make_object(abi.RM_TORUS, model=SB.rot_x(0.9) @ h.scale(3, 3, 3), scale_factor=3, **red)]))
     # objects that touch: crevices where two of them stay equally near for hundreds of steps, rays that pass one object closely
     # and hit the next (the nearest object changes along the ray)
     cases.append((cam, [h.make_object(abi.RM_SPHERE, model=h.translate(-0.5, -0.5, 0), **red),
@@ -1828,7 +1434,6 @@ def test_table_walk_skip_edge_cases(renderer):
             lib().rm_set_kernel_path(0)
 
 
-
 def test_stamped_diagnostic_builds_render_the_same_frame(renderer):
     """rm_render_clocked (production code + per-wave clock stamps; scripts/wave_timeline.py, wave_lives.py): the frame is the
     production frame, the shader clock plausible, every wave that holds pixels has a life span — for the single-Mandelbulb class
@@ -1836,18 +1441,18 @@ def test_stamped_diagnostic_builds_render_the_same_frame(renderer):
     from raymarcher_amd import Scene
     W, H = 200, 120
     cases = [(tables_of(h.scene_mandelbulb(W, H)), abi.default_settings(fractalIters=8)),
-             (Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).tables(W, H),
+             (Scene(path=os.path.join(SB.SCENES, "lighting", "directional_light_2.json")).tables(W, H),
               abi.default_settings(enableSoftShadow=1, enableAmbientOcclusion=1))]
     for t, s in cases:
         ref = renderer.render(t, s, W, H)
         out, mhz, spans = renderer.render_clocked(t, s, W, H, wave_spans=True)
-        assert _ieq(out, ref)
+        assert SB.ieq(out, ref)
         assert 500.0 < mhz < 4000.0
         sp = spans.cpu().numpy()
         live = sp[sp[:, 1] > 0]
         assert len(live) == ((W + 7) // 8) * ((H + 7) // 8) and (live[:, 1] >= live[:, 0]).all()
     with pytest.raises(Exception):
-        renderer.render_clocked(tables_of(env_scene(W, H)), abi.default_settings(features=ENV_ALL), W, H)
+        renderer.render_clocked(tables_of(SB.env_scene(W, H)), abi.default_settings(features=SB.ENV_ALL), W, H)
 
 
 CXX_HOST = r'''
@@ -1981,7 +1586,7 @@ def test_cxx_host_without_python(renderer, tmp_path):
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     png = tmp_path / "bulb.png"
-    r = subprocess.run([str(exe), os.path.join(SCENES, "simple", "unit_mandelbulb.json"), str(png)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([str(exe), os.path.join(SB.SCENES, "simple", "unit_mandelbulb.json"), str(png)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "ok" in r.stdout, (r.returncode, r.stdout, r.stderr[-800:])
     from PIL import Image
     img = np.asarray(Image.open(png))
@@ -2003,7 +1608,7 @@ def test_single_process_multi_gpu_host_runs(renderer, tmp_path):
     p = subprocess.run([hipcc, "-std=c++17", "-O1", "-I", os.path.join(root, "include"), os.path.join(root, "scripts", "mgpu_host.cpp"), "-o",
                         str(exe), "-L", libdir, "-lraymarcher_amd", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
-    scene = os.path.join(SCENES, "simple", "unit_mandelbulb.json")
+    scene = os.path.join(SB.SCENES, "simple", "unit_mandelbulb.json")
     for extra in ([], ["--rgba8"]):
         r = subprocess.run([str(exe), scene, "--size", "640", "360", "--frames", "12", "--iters", "12", "--force-comm"] + extra,
                            capture_output=True, text=True, timeout=120)
@@ -2016,9 +1621,9 @@ def test_degenerate_knobs_bit_exact(renderer):
     """Loop bounds at zero, no lights, one-pixel frames, NaN / inf in the tables: no hang, no fault, same bits as the oracle."""
     W, H = 40, 24
     cases = [(h.scene_mandelbulb(W, H), dict(maxSteps=0)), (h.scene_mandelbulb(W, H), dict(fractalIters=0)),
-             (h.scene_mandelbulb(W, H), dict(maxSteps=1, fractalIters=1)), (menger_scene(W, H), dict(mengerLevels=0, enableReflection=1)),
-             (reflect_refract_scene(W, H), dict(numReflection=0, enableReflection=1, enableRefraction=1)),
-             (reflect_refract_scene(W, H)[:3] + ((abi.RmLight * 1)(), 0) + (h.make_globals(),), dict(enableAmbientOcclusion=1))]
+             (h.scene_mandelbulb(W, H), dict(maxSteps=1, fractalIters=1)), (SB.menger_scene(W, H), dict(mengerLevels=0, enableReflection=1)),
+             (SB.reflect_refract_scene(W, H), dict(numReflection=0, enableReflection=1, enableRefraction=1)),
+             (SB.reflect_refract_scene(W, H)[:3] + ((abi.RmLight * 1)(), 0) + (h.make_globals(),), dict(enableAmbientOcclusion=1))]
     for k, (scene, over) in enumerate(cases):
         s = abi.default_settings(**over)
         assert_bit_equal(renderer.render(tables_of(scene), s, W, H).cpu().numpy(), h.oracle_render(scene, s, W, H), f"degenerate {k} {over}")
@@ -2027,7 +1632,7 @@ def test_degenerate_knobs_bit_exact(renderer):
         s = abi.default_settings(fractalIters=12)
         assert_bit_equal(renderer.render(tables_of(scene), s, w, hh).cpu().numpy(), h.oracle_render(scene, s, w, hh), f"{w}x{hh}")
     # non-finite numbers in the tables must not hang or fault (values then follow IEEE on both sides)
-    scene = reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     scene[1][0].invModel[12] = float("nan")
     scene[1][1].scaleFactor = float("inf")
     scene[3][0].dir[0] = float("nan")

@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as P
-from test_gpu_batch import assert_bit_equal, orbit, tables_of, with_globals
+import scene_builders as SB
+from helpers import assert_bit_equal, tables_of, with_globals
+from scene_builders import orbit
 from raymarcher_amd import abi, lib
 from raymarcher_amd._lib import RaymarcherError
 
@@ -31,7 +32,7 @@ def synthetic_frames(N, W, H, seed=0):
 
 
 def post_of(name, exposure=None):
-    kw = {"exposure": 1.0, **P.POST_CASES[name]}
+    kw = {"exposure": 1.0, **SB.POST_CASES[name]}
     if exposure is not None:
         kw["exposure"] = exposure
     return abi.RmPostSettings(**kw)
@@ -69,7 +70,7 @@ def test_every_frame_equals_the_oracle(renderer, W, H, N):
             oracle[key] = h.oracle_post(frag[f], bright[f], p)
         return oracle[key]
 
-    for name in P.POST_CASES:
+    for name in SB.POST_CASES:
         oracle.clear()
         for posts in ([post_of(name)], fade(name, N)):
             got = renderer.post_process_batch(fd, bd, posts if len(posts) > 1 else posts[0]).cpu().numpy()
@@ -84,12 +85,12 @@ def test_every_word_of_every_frame_is_written_and_nothing_else(renderer, W, H):
     N = 5
     frag, bright = synthetic_frames(N, W, H, seed=2)
     fd, bd = device(renderer, frag, bright)
-    for name in P.POST_CASES:
+    for name in SB.POST_CASES:
         posts = fade(name, N)
         out, check = h.guarded((N, H, W, 4), device=renderer.device)
         renderer.post_process_batch(fd, bd if posts[0].enableBloom else None, posts, out=out)
         check()
-        assert P._ieq(out, per_frame(renderer, fd, bd, posts)), name
+        assert SB.ieq(out, per_frame(renderer, fd, bd, posts)), name
 
 
 # ---------------------------------------------------------------- 3. chunk boundaries
@@ -102,7 +103,7 @@ def test_batches_across_the_64_frame_chunk(renderer, N):
     out, check = h.guarded((N, H, W, 4), device=renderer.device)
     renderer.post_process_batch(fd, bd, posts, out=out)
     check()
-    assert P._ieq(out, per_frame(renderer, fd, bd, posts))
+    assert SB.ieq(out, per_frame(renderer, fd, bd, posts))
     got = out.cpu().numpy()
     for f in (0, 63, 64, N - 1):
         assert_bit_equal(got[f], h.oracle_post(frag[f], bright[f], posts[f]), f"frame {f} of {N}")
@@ -123,7 +124,7 @@ def test_workspace_limit_cuts_the_chunks(renderer):
         out, check = h.guarded((N, H, W, 4), device=renderer.device)
         renderer.post_process_batch(fd, bd, posts, out=out)  # chunks of 2, 2, 1
         check()
-        assert P._ieq(out, expect)
+        assert SB.ieq(out, expect)
         assert L.rm_release_workspaces(C.byref(freed)) == abi.RM_OK
         assert 0 < freed.value <= 2 * need, freed.value
         # below one frame's need: the workspace cannot be allocated, as for rm_post_process
@@ -134,7 +135,7 @@ def test_workspace_limit_cuts_the_chunks(renderer):
         assert "rm_set_workspace_limit" in L.rm_last_error().decode()
     finally:
         L.rm_set_workspace_limit(0)
-    assert P._ieq(renderer.post_process_batch(fd, bd, posts), expect)
+    assert SB.ieq(renderer.post_process_batch(fd, bd, posts), expect)
 
 
 # ---------------------------------------------------------------- 4. in place
@@ -147,7 +148,7 @@ def test_in_place_equals_out_of_place(renderer):
         ref = renderer.post_process_batch(fd, bd, posts).clone()
         inplace = fd.clone()
         assert renderer.post_process_batch(inplace, bd, posts, out=inplace).data_ptr() == inplace.data_ptr()
-        assert P._ieq(inplace, ref), name
+        assert SB.ieq(inplace, ref), name
 
 
 # ---------------------------------------------------------------- 5. two streams
@@ -167,7 +168,7 @@ def test_two_streams_use_their_own_workspaces(renderer):
         with torch.cuda.stream(s2):
             out_b = renderer.post_process_batch(fbd, bbd, posts[::-1])
         torch.cuda.synchronize(renderer.device)
-        assert P._ieq(out_a, ref_a) and P._ieq(out_b, ref_b)
+        assert SB.ieq(out_a, ref_a) and SB.ieq(out_b, ref_b)
 
 
 # ---------------------------------------------------------------- 6. to_rgba8_batch
@@ -187,7 +188,7 @@ def test_to_rgba8_batch_flips_every_frame_in_itself(renderer, W, H, N):
 # ---------------------------------------------------------------- 7. end to end
 def test_render_sequence_equals_the_per_frame_export(renderer, tmp_path):
     W, H, N = 150, 90, 8
-    scene = P.reflect_refract_scene(W, H)
+    scene = SB.reflect_refract_scene(W, H)
     for li in scene[3]:
         li.color[0] *= 2.5; li.color[1] *= 2.5; li.color[2] *= 2.5  # over-exposed: BrightColor is populated
     s = abi.default_settings(enableReflection=1)

@@ -14,7 +14,8 @@ import pytest
 
 import helpers as h
 import test_post_values as V
-from test_gpu_parity import POST_CASES
+from helpers import assert_bit_equal as assert_bits
+from scene_builders import POST_CASES
 from raymarcher_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -40,11 +41,6 @@ def assert_same(got, ref, what):
         i = tuple(np.argwhere(bad)[0])
         raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} words differ, first at {i}: got {got[i]!r} "
                              f"({int(got.view(np.uint32)[i]):#010x}), expected {ref[i]!r} ({int(ref.view(np.uint32)[i]):#010x})")
-
-
-def assert_bits(got, ref, what):
-    bad = got.view(np.uint32) != ref.view(np.uint32)
-    assert not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {tuple(np.argwhere(bad)[0])}"
 
 
 def ordinary(W, H, seed=0, N=None):

@@ -12,7 +12,7 @@ import helpers as h
 import sdf_helpers as V
 import sdf_mesh_spec as S
 from raymarcher_amd import abi, lib, mesh_bounds, write_ply
-from raymarcher_amd.render import Scene, SceneTables
+from raymarcher_amd.render import Scene
 
 pytestmark = pytest.mark.gpu
 
@@ -29,8 +29,9 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def tables_of(objs, no, g):
-    return SceneTables(abi.RmCamera(), objs, no, None, 0, g)
+def table_only(objs, no, g):
+    """SceneTables of an object table alone: no camera, no lights."""
+    return h.tables_of((abi.RmCamera(), objs, no, None, 0, g))
 
 
 def grid_call(renderer, name, origin, step, dims, ids=True):
@@ -59,7 +60,7 @@ def test_grid_equals_the_oracle_and_the_probe_in_every_bit(renderer, name):
         V.assert_bits(got_d, ref_d, f"{name} {dims}: d_dist against the oracle")
         assert (got_i == ref_i).all(), f"{name} {dims}: d_objectId against the oracle"
         pts = torch.from_numpy(S.lattice_points(origin, step, dims)).to(renderer.device)
-        probe = renderer.probe_sdscene(tables_of(objs, no, g), s, pts).cpu().numpy()
+        probe = renderer.probe_sdscene(table_only(objs, no, g), s, pts).cpu().numpy()
         nx, ny, nz = dims
         V.assert_bits(got_d, np.ascontiguousarray(probe[:, 0]).reshape(nz, ny, nx), f"{name} {dims}: d_dist against rm_probe_sdscene")
         assert (got_i == probe[:, 1].astype(np.int32).reshape(nz, ny, nx)).all(), f"{name} {dims}: ids against rm_probe_sdscene"
@@ -75,7 +76,7 @@ def test_grid_python_layer_and_timing(renderer):
     objs, no, g, s = V.scene("primitives")
     dims = (17, 16, 3)
     ref_d, ref_i, origin, step = V.oracle_lattice("primitives", dims)
-    t = tables_of(objs, no, g)
+    t = table_only(objs, no, g)
     dist, ids = renderer.sdf_grid(t, s, origin, step, dims, ids=True)
     assert tuple(dist.shape) == (3, 16, 17) and dist.dtype == torch.float32 and ids.dtype == torch.int32
     V.assert_bits(dist.cpu().numpy(), ref_d, "Renderer.sdf_grid")
@@ -208,7 +209,7 @@ def test_extract_mesh_equals_the_two_c_calls(renderer):
     objs, no, g, s = V.scene("sphere_cube")
     dims = (21, 11, 11)
     ref_d, ref_i, origin, step = V.oracle_lattice("sphere_cube", dims)
-    t = tables_of(objs, no, g)
+    t = table_only(objs, no, g)
     dist, ids = renderer.sdf_grid(t, s, origin, step, dims, ids=True)
     v, q, vo = renderer.extract_mesh(dist, origin, step, 0.0, ids)
     want = S.surface_nets(ref_d, origin, step, 0.0, ref_i)

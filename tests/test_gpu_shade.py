@@ -14,7 +14,6 @@ import torch
 
 import helpers as h
 import shade_helpers as S
-import test_gpu_parity as P
 import trace_helpers as T
 from raymarcher_amd import RaymarcherError, abi, camera_rays, lib, panorama_rays, tile_order
 from raymarcher_amd.render import SceneTables

@@ -12,9 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-import gbuffer_helpers as G
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
 import trace_helpers as T
 from raymarcher_amd import abi, camera_rays, lib
 from raymarcher_amd.render import SceneTables
@@ -27,7 +26,7 @@ BUMP, PLAIN = abi.RM_FEAT_WHITE_BACKGROUND | abi.RM_FEAT_PERLIN_BUMP, abi.RM_FEA
 
 
 def _random(seed, max_objects=30):
-    return T.table(h.random_tablewalk_objects(np.random.default_rng(seed), max_objects=max_objects, materials=False))
+    return h.table(h.random_tablewalk_objects(np.random.default_rng(seed), max_objects=max_objects, materials=False))
 
 
 # name → (object table, count, globals, settings).  The random seeds: 7 = 30 objects with scaleFactors 0.14 … 3.6, 0 = 25 objects,
@@ -49,18 +48,18 @@ def case(name):
         s = abi.default_settings(features=PLAIN if name.endswith("_nobump") else BUMP, fractalIters=12)
         assert lib().rm_debug_bulb_plain(objs, 1, C.byref(g)) == 1
     elif name == "moved_bulb":
-        objs, n = G.moved_bulb_scene(8, 8)[1:3]
+        objs, n = SB.moved_bulb_scene(8, 8)[1:3]
         s = abi.default_settings(fractalIters=12)
         assert lib().rm_debug_bulb_plain(objs, 1, C.byref(g)) == 0
     elif name == "menger":
-        objs, n = P.menger_scene(8, 8)[1:3]
+        objs, n = SB.menger_scene(8, 8)[1:3]
         g = h.make_globals(itime=7.5)
         s = abi.default_settings(mengerLevels=3)
     elif name == "sierpinski":
-        objs, n = T.table([h.make_object(abi.RM_SIERPINSKI, model=h.scale(0.8, 0.8, 0.8), scale_factor=0.8),
+        objs, n = h.table([h.make_object(abi.RM_SIERPINSKI, model=h.scale(0.8, 0.8, 0.8), scale_factor=0.8),
                            h.make_object(abi.RM_CUBE, model=h.translate(1.2, 0.1, -0.3) @ h.scale(0.6, 0.6, 0.6), scale_factor=0.6)])
     elif name == "empty":
-        objs, n = T.table([])
+        objs, n = h.table([])
     else:
         raise KeyError(name)
     return objs, n, g, s
@@ -88,16 +87,16 @@ def spec_of(name, mode):
     return hits
 
 
-def tables_of(name):
+def case_tables(name):
     objs, n, g, _ = case(name)
-    return SceneTables(abi.RmCamera(), objs, n, None, 0, g)
+    return h.tables_of((abi.RmCamera(), objs, n, None, 0, g))
 
 
 def trace_guarded(renderer, name, rays, mode):
     """Renderer.trace_rays into a poisoned, guarded (n, 8) buffer, checked → numpy (n, 8)."""
     out, check = h.guarded((len(rays), 8), device=renderer.device)
     kw = dict(mode="occlusion") if mode == "occlusion" else dict(normals=mode == "closest")
-    got = renderer.trace_rays(tables_of(name), case(name)[3], np.array(rays), out=out, **kw)  # a writable copy of the shared rays
+    got = renderer.trace_rays(case_tables(name), case(name)[3], np.array(rays), out=out, **kw)  # a writable copy of the shared rays
     assert len(got) == 4 and got[0].data_ptr() == out.data_ptr() and got[3].dtype == torch.int32
     assert lib().rm_debug_last_path() == 12 and lib().rm_debug_last_split() == 0
     check()
@@ -125,7 +124,7 @@ def test_kernel_equals_the_spec_in_every_bit(renderer, name, mode):
 def test_rays_may_be_a_device_tensor_and_normals_off_keeps_id_and_t(renderer):
     name = "random_9"
     rays = torch.from_numpy(np.array(rays_of(name)[:257])).to(renderer.device)
-    t = tables_of(name)
+    t = case_tables(name)
     nrm, tt, pos, ids = renderer.trace_rays(t, case(name)[3], rays)
     want = spec_of(name, "closest")[:257]
     T.assert_bits(nrm.cpu().numpy(), want[:, 0:3], "normal view")
@@ -156,7 +155,7 @@ def test_a_shuffled_call_gives_the_shuffled_results(renderer, name, mode):
 @pytest.mark.parametrize("W,H", [(64, 36), (37, 23)])
 @pytest.mark.parametrize("scene_name", ["directional_light_2", "plain_bulb", "moved_bulb"])
 def test_camera_rays_traced_equal_the_gbuffer(renderer, scene_name, W, H):
-    scene = {"directional_light_2": G.directional_light_2, "plain_bulb": h.scene_mandelbulb, "moved_bulb": G.moved_bulb_scene}[scene_name](W, H)
+    scene = {"directional_light_2": SB.directional_light_2, "plain_bulb": h.scene_mandelbulb, "moved_bulb": SB.moved_bulb_scene}[scene_name](W, H)
     t = SceneTables(*scene)
     s = abi.default_settings()
     nd, ids, pos = renderer.render_gbuffer(t, s, W, H, position=True)
@@ -179,7 +178,7 @@ def test_four_launches_back_to_back_keep_their_tables_apart(renderer):
     dev = [torch.from_numpy(np.array(rays_of(name)[:n])).to(renderer.device) for name in names]
     torch.cuda.synchronize()
     for name, (out, _), rays in zip(names, outs, dev):  # nothing waits between the four
-        renderer.trace_rays(tables_of(name), case(name)[3], rays, out=out)
+        renderer.trace_rays(case_tables(name), case(name)[3], rays, out=out)
     assert lib().rm_debug_last_path() == 12
     for name, (out, check) in zip(names, outs):
         check()
@@ -188,7 +187,7 @@ def test_four_launches_back_to_back_keep_their_tables_apart(renderer):
 
 def test_single_frames_before_and_after_are_the_same_bits(renderer):
     W, H = 64, 36
-    t = SceneTables(*G.directional_light_2(W, H))
+    t = SceneTables(*SB.directional_light_2(W, H))
     s = abi.default_settings(enableSoftShadow=1)
     before = renderer.render(t, s, W, H).cpu().numpy()
     path = lib().rm_debug_last_path()
@@ -202,7 +201,7 @@ def test_single_frames_before_and_after_are_the_same_bits(renderer):
 
 def test_pick_agrees_with_the_gbuffers_centre_pixel(renderer):
     W, H = 64, 36
-    scene = G.directional_light_2(W, H)
+    scene = SB.directional_light_2(W, H)
     t = SceneTables(*scene)
     s = abi.default_settings()
     nd, ids, pos = renderer.render_gbuffer(t, s, W, H, position=True)

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_parity as tg
+import scene_builders as SB
 from raymarcher_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +25,8 @@ def render_path(renderer, path, t, s, W, H, **kw):
 
 
 def reflective_scene(W, H):
-    """tg.reflect_refract_scene without the transparent material (refraction stays on rm::render_kernel)."""
-    cam, objs, no, lights, nl, g = tg.reflect_refract_scene(W, H)
+    """SB.reflect_refract_scene without the transparent material (refraction stays on rm::render_kernel)."""
+    cam, objs, no, lights, nl, g = SB.reflect_refract_scene(W, H)
     for k in range(3):
         objs[1].cTransparent[k] = 0.0
         objs[1].cReflective[k] = 0.5
@@ -34,8 +34,8 @@ def reflective_scene(W, H):
 
 
 def primitives_scene(W, H):
-    """tg.all_primitives_scene with a sphere in place of its Mandelbulb (data-dependent evaluation cost: not this pipeline's class)."""
-    cam, objs, no, lights, nl, g = tg.all_primitives_scene(W, H)
+    """SB.all_primitives_scene with a sphere in place of its Mandelbulb (data-dependent evaluation cost: not this pipeline's class)."""
+    cam, objs, no, lights, nl, g = SB.all_primitives_scene(W, H)
     for i in range(no):
         if objs[i].type == abi.RM_MANDELBULB:
             objs[i].type = abi.RM_SPHERE
@@ -50,8 +50,8 @@ WF_CASES = {
     "reflective_soft_ao_ragged": (reflective_scene, {"enableReflection": 1, "numReflection": 2, "enableSoftShadow": 1,
                                                      "enableAmbientOcclusion": 1}, 101, 37),
     "reflection_enabled_zero_bounces": (reflective_scene, {"enableReflection": 1, "numReflection": 0}, 64, 40),
-    "menger_5_levels_2_bounces": (lambda W, H: tg.menger_scene(W, H), {"mengerLevels": 5, "numReflection": 2, "enableReflection": 1}, 80, 60),
-    "menger_animated": (lambda W, H: tg.menger_scene(W, H)[:5] + (h.make_globals(itime=7.5),),
+    "menger_5_levels_2_bounces": (lambda W, H: SB.menger_scene(W, H), {"mengerLevels": 5, "numReflection": 2, "enableReflection": 1}, 80, 60),
+    "menger_animated": (lambda W, H: SB.menger_scene(W, H)[:5] + (h.make_globals(itime=7.5),),
                         {"mengerLevels": 4, "numReflection": 1, "enableReflection": 1}, 80, 60),
     "one_step": (primitives_scene, {"maxSteps": 1}, 40, 24),
 }
@@ -63,23 +63,23 @@ def test_wavefront_frames_bit_exact(renderer, name):
     scene = build(W, H)
     s = abi.default_settings(**over)
     ref, ref_b = h.oracle_render(scene, s, W, H, bright=True)
-    (out, br), ran = render_path(renderer, 5, tg.tables_of(scene), s, W, H, bright=True)
+    (out, br), ran = render_path(renderer, 5, h.tables_of(scene), s, W, H, bright=True)
     assert ran == 5, "the wavefront pipeline must be the schedule that ran"
-    tg.assert_bit_equal(out.cpu().numpy(), ref, f"{name} fragColor")
-    tg.assert_bit_equal(br.cpu().numpy(), ref_b, f"{name} BrightColor")
+    h.assert_bit_equal(out.cpu().numpy(), ref, f"{name} fragColor")
+    h.assert_bit_equal(br.cpu().numpy(), ref_b, f"{name} BrightColor")
 
 
 def test_wavefront_falls_back_where_it_does_not_apply(renderer):
     """Refraction through a transparent object, a Mandelbulb in the table, procedural layers: rm_set_kernel_path(5) renders
     them with rm::render_kernel — and still the oracle's bits."""
     W, H = 64, 40
-    cases = [(tg.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1)),
+    cases = [(SB.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1)),
              (h.scene_mandelbulb(W, H), abi.default_settings(fractalIters=8)),
-             (tg.env_scene(W, H), abi.default_settings(features=tg.ENV_ALL))]
+             (SB.env_scene(W, H), abi.default_settings(features=SB.ENV_ALL))]
     for scene, s in cases:
-        out, ran = render_path(renderer, 5, tg.tables_of(scene), s, W, H)
+        out, ran = render_path(renderer, 5, h.tables_of(scene), s, W, H)
         assert ran == 1
-        tg.assert_bit_equal(out.cpu().numpy(), h.oracle_render(scene, s, W, H), "fallback")
+        h.assert_bit_equal(out.cpu().numpy(), h.oracle_render(scene, s, W, H), "fallback")
 
 
 def _random_wf_case(rng, W, H):
@@ -93,7 +93,7 @@ def _random_wf_case(rng, W, H):
         ty = int(rng.choice(types))
         sc = float(f(0.6, 1.8))
         sx, sy, sz = (sc * float(f(0.8, 1.25)) for _ in range(3))
-        M = h.translate(f(-2.2, 2.2), f(-1.0, 1.2), f(-2.5, 1.0)) @ tg.rot_x(f(-0.6, 0.6)) @ h.scale(sx, sy, sz)
+        M = h.translate(f(-2.2, 2.2), f(-1.0, 1.2), f(-2.5, 1.0)) @ SB.rot_x(f(-0.6, 0.6)) @ h.scale(sx, sy, sz)
         objs.append(h.make_object(ty, model=M, scale_factor=min(sx, sy, sz), ambient=tuple(f(0, .3, 3)), diffuse=tuple(f(.2, 1, 3)),
                                   specular=tuple(f(0, 1, 3)), shininess=float(rng.choice([0, 1, 7.5, 25, 100])),
                                   reflective=tuple(f(0, .8, 3)) if f() < 0.5 else (0, 0, 0),
@@ -130,12 +130,12 @@ def test_wavefront_random_scenes_bit_exact(renderer):
     for i in range(int(os.environ.get("RM_FUZZ_CASES", "24"))):
         scene, s = _random_wf_case(rng, W, H)
         ref, ref_b = h.oracle_render(scene, s, W, H, bright=True)
-        (out, br), ran = render_path(renderer, 5, tg.tables_of(scene), s, W, H, bright=True)
+        (out, br), ran = render_path(renderer, 5, h.tables_of(scene), s, W, H, bright=True)
         assert ran == 5
-        tg.assert_bit_equal(out.cpu().numpy(), ref, f"random wavefront scene {i}")
-        tg.assert_bit_equal(br.cpu().numpy(), ref_b, f"random wavefront scene {i} bright")
-        (mono, _), ran1 = render_path(renderer, 1, tg.tables_of(scene), s, W, H, bright=True)
-        assert ran1 == 1 and tg._ieq(mono, out)
+        h.assert_bit_equal(out.cpu().numpy(), ref, f"random wavefront scene {i}")
+        h.assert_bit_equal(br.cpu().numpy(), ref_b, f"random wavefront scene {i} bright")
+        (mono, _), ran1 = render_path(renderer, 1, h.tables_of(scene), s, W, H, bright=True)
+        assert ran1 == 1 and SB.ieq(mono, out)
 
 
 def test_wavefront_row_ranges_tiles_and_streams(renderer):
@@ -144,21 +144,21 @@ def test_wavefront_row_ranges_tiles_and_streams(renderer):
     import torch
     from raymarcher_amd import lib
     W, H = 150, 83
-    scene = tg.menger_scene(W, H)
-    t = tg.tables_of(scene)
+    scene = SB.menger_scene(W, H)
+    t = h.tables_of(scene)
     s = abi.default_settings(mengerLevels=4, numReflection=2, enableReflection=1)
     full, ran = render_path(renderer, 5, t, s, W, H)
     assert ran == 5
-    tg.assert_bit_equal(full.cpu().numpy(), h.oracle_render(scene, s, W, H), "whole frame")
+    h.assert_bit_equal(full.cpu().numpy(), h.oracle_render(scene, s, W, H), "whole frame")
     part, _ = render_path(renderer, 5, t, s, W, H, row_begin=17, row_end=60)
-    assert tg._ieq(part, full[17:60])
+    assert SB.ieq(part, full[17:60])
     try:
         lib().rm_set_kernel_path(5)
         for N in (2, 3):
             for k in range(N):
                 mine = renderer.render_tiles(t, s, W, H, 8, k, N)
                 rows = [lib().rm_shard_row_to_frame(H, 8, k, N, i) for i in range(mine.shape[0])]
-                assert tg._ieq(mine, full[torch.tensor(rows, device=full.device)])
+                assert SB.ieq(mine, full[torch.tensor(rows, device=full.device)])
         streams = [torch.cuda.Stream(device=renderer.device) for _ in range(2)]
         outs = []
         for st in streams * 2:
@@ -169,7 +169,7 @@ def test_wavefront_row_ranges_tiles_and_streams(renderer):
         torch.cuda.synchronize()
         for _, check in outs:
             check()
-        assert all(tg._ieq(o, full) for o, _ in outs)
+        assert all(SB.ieq(o, full) for o, _ in outs)
     finally:
         lib().rm_set_kernel_path(0)
 
@@ -179,15 +179,15 @@ def test_wavefront_config5_bands_8k(renderer):
     one-lane-per-pixel frame everywhere, and to the oracle on two bands of rows."""
     from raymarcher_amd import Scene
     W, H = 7680, 4320
-    t = Scene(path=os.path.join(tg.SCENES, "simple", "unit_mengersponge.json")).tables(W, H)
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "unit_mengersponge.json")).tables(W, H)
     s = abi.default_settings(mengerLevels=5, numReflection=2, enableReflection=1)
     wf, ran = render_path(renderer, 5, t, s, W, H)
     assert ran == 5
     mono, ran1 = render_path(renderer, 1, t, s, W, H)
-    assert ran1 == 1 and tg._ieq(wf, mono)
+    assert ran1 == 1 and SB.ieq(wf, mono)
     for r0 in (1000, 2164):
-        ref = h.oracle_render(tg._scene_tuple(t), s, W, H, r0, r0 + 4, threads=16)
-        tg.assert_bit_equal(wf[r0:r0 + 4].cpu().numpy(), ref, f"8K rows {r0}..{r0 + 4}")
+        ref = h.oracle_render(SB.scene_tuple(t), s, W, H, r0, r0 + 4, threads=16)
+        h.assert_bit_equal(wf[r0:r0 + 4].cpu().numpy(), ref, f"8K rows {r0}..{r0 + 4}")
 
 
 def test_wavefront_workspace_refused_falls_back_to_the_pixel_kernel(renderer):
@@ -201,7 +201,7 @@ def test_wavefront_workspace_refused_falls_back_to_the_pixel_kernel(renderer):
     from raymarcher_amd._lib import RaymarcherError
     L = lib()
     W, H = 2560, 1664  # 4.26 M pixels: above the pipeline's 2^22-pixel threshold
-    t = Scene(path=os.path.join(tg.SCENES, "simple", "unit_mengersponge.json")).tables(W, H)
+    t = Scene(path=os.path.join(SB.SCENES, "simple", "unit_mengersponge.json")).tables(W, H)
     s = abi.default_settings(mengerLevels=5, numReflection=2, enableReflection=1)
     need = 150 * W * H  # a lower bound of what the pipeline asks for
     freed = C.c_ulonglong(0)
@@ -211,7 +211,7 @@ def test_wavefront_workspace_refused_falls_back_to_the_pixel_kernel(renderer):
         capped, ran = render_path(renderer, 0, t, s, W, H)
         assert ran == 1, "a refused workspace must fall back to the one-lane-per-pixel kernel"
         again, ran2 = render_path(renderer, 0, t, s, W, H)  # the refusal is remembered: no second attempt, same frame
-        assert ran2 == 1 and tg._ieq(again, capped)
+        assert ran2 == 1 and SB.ieq(again, capped)
         with pytest.raises(RaymarcherError):  # an explicit request reports instead of silently switching
             render_path(renderer, 5, t, s, W, H)
         torch.cuda.synchronize()  # no sticky HIP error: torch's own calls on this device still succeed
@@ -220,10 +220,10 @@ def test_wavefront_workspace_refused_falls_back_to_the_pixel_kernel(renderer):
     finally:
         assert L.rm_set_workspace_limit(0) == 0
     wf, ran4 = render_path(renderer, 0, t, s, W, H)  # limit lifted: the refusal is forgotten, the pipeline runs
-    assert ran4 == 5 and tg._ieq(wf, capped)
+    assert ran4 == 5 and SB.ieq(wf, capped)
     for r0 in (400, 830):
-        ref = h.oracle_render(tg._scene_tuple(t), s, W, H, r0, r0 + 4, threads=16)
-        tg.assert_bit_equal(capped[r0:r0 + 4].cpu().numpy(), ref, f"capped frame rows {r0}..{r0 + 4}")
+        ref = h.oracle_render(SB.scene_tuple(t), s, W, H, r0, r0 + 4, threads=16)
+        h.assert_bit_equal(capped[r0:r0 + 4].cpu().numpy(), ref, f"capped frame rows {r0}..{r0 + 4}")
     assert L.rm_release_workspaces(C.byref(freed)) == 0 and freed.value >= need
     after, ran5 = render_path(renderer, 0, t, s, W, H)  # buffers come back on demand
-    assert ran5 == 5 and tg._ieq(after, wf)
+    assert ran5 == 5 and SB.ieq(after, wf)

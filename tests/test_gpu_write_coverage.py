@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_gpu_batch as tb
-import test_gpu_bulb_shadow_pool as sp
-import test_gpu_parity as tg
+import scene_builders as SB
+from helpers import tables_of
+from scene_builders import ieq
 from raymarcher_amd import abi, lib
 
 pytestmark = pytest.mark.gpu
@@ -21,17 +21,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(1, 1), (3, 70), (65, 9), (636, 388)]  # neither 8×8 nor 4×16 tiles divide any of them
 SHAPES = (3, 2)  # rm_debug_set_tile_shape: 8×8, 4 wide × 16 tall
-
-
-def tables_of(scene, res=None):
-    t = tg.tables_of(scene[:6])
-    for k, v in (res or {}).items():
-        setattr(t, k, v)
-    return t
-
-
-def ieq(a, b):
-    return tg._ieq(a, b)
 
 
 def single_object_scene(W, H):
@@ -48,19 +37,19 @@ def kernel_class(name, W, H):
     if name == "bulb_plain":
         return h.scene_mandelbulb(W, H), abi.default_settings(fractalIters=10), {}
     if name == "bulb_general":  # a Julia seed: the general form of the bulb kernel, with the shadow pool
-        return sp.bulb_scene(W, H, nl=4, julia=(0.35, -0.2)), abi.default_settings(fractalIters=10), {}
+        return SB.bulb_scene(W, H, nl=4, julia=(0.35, -0.2)), abi.default_settings(fractalIters=10), {}
     if name == "table":
-        return tg.all_primitives_scene(W, H), abi.default_settings(maxSteps=96, enableSoftShadow=1), {}
+        return SB.all_primitives_scene(W, H), abi.default_settings(maxSteps=96, enableSoftShadow=1), {}
     if name == "table_single":  # one object: the table walk's single-object fast path
         return single_object_scene(W, H), abi.default_settings(enableAmbientOcclusion=1), {}
     if name == "table_sec":  # secondary rays compiled in and firing
-        return tg.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2), {}
+        return SB.reflect_refract_scene(W, H), abi.default_settings(enableReflection=1, enableRefraction=1, numReflection=2), {}
     if name == "layers":
-        return tg.env_scene(W, H), abi.default_settings(features=tg.ENV_ALL, maxSteps=64), {}
+        return SB.env_scene(W, H), abi.default_settings(features=SB.ENV_ALL, maxSteps=64), {}
     if name == "textures":
-        return tg.textured_scene(W, H), abi.default_settings(), {"textures": tg.synthetic_textures()}
+        return SB.textured_scene(W, H), abi.default_settings(), {"textures": SB.synthetic_textures()}
     if name == "skybox":
-        return tg.resource_case("skybox_reflect", W, H)
+        return SB.resource_case("skybox_reflect", W, H)
     if name == "mandelbrot_2d":
         sc = h.scene_mandelbulb(W, H)
         return sc[:5] + (h.make_globals(two_d=1),), abi.default_settings(), {}
@@ -80,8 +69,8 @@ def check_class(renderer, name, W, H, shapes=SHAPES):
         for shape in shapes:
             assert lib().rm_debug_set_tile_shape(shape) == 0
             out, br = h.render_guarded(renderer, t, s, W, H, bright=True)
-            tg.assert_bit_equal(out.cpu().numpy(), ref, f"{name} {W}x{H} shape {shape}")
-            tg.assert_bit_equal(br.cpu().numpy(), ref_b, f"{name} {W}x{H} shape {shape} bright")
+            h.assert_bit_equal(out.cpu().numpy(), ref, f"{name} {W}x{H} shape {shape}")
+            h.assert_bit_equal(br.cpu().numpy(), ref_b, f"{name} {W}x{H} shape {shape} bright")
     finally:
         lib().rm_debug_set_tile_shape(-1)
 
@@ -121,7 +110,7 @@ def test_every_tile_order_writes_each_tile(renderer):
     RM_TILE_ORDER_SETTLE) and the raster fallback of an object without a bounding ball — each frame in a fresh buffer."""
     L = lib()
     W, H = 640, 384  # 3840 8×8 tiles
-    prim = tg.all_primitives_scene(W, H)
+    prim = SB.all_primitives_scene(W, H)
     sier = (prim[0], (abi.RmObject * 2)(h.make_object(abi.RM_SIERPINSKI, model=h.scale(0.8, 0.8, 0.8), scale_factor=0.8,
                                                       diffuse=(.8, .6, .3)),
                                         h.make_object(abi.RM_SPHERE, model=h.translate(1.5, 0, 0))), 2) + prim[3:]
@@ -132,12 +121,12 @@ def test_every_tile_order_writes_each_tile(renderer):
             t = tables_of(scene)
             ref = h.oracle_render(scene, s, W, H, threads=16)
             assert L.rm_set_tile_order(0) == 0
-            tg.assert_bit_equal(h.render_guarded(renderer, t, s, W, H).cpu().numpy(), ref, "raster order")
+            h.assert_bit_equal(h.render_guarded(renderer, t, s, W, H).cpu().numpy(), ref, "raster order")
             assert L.rm_set_tile_order(1) == 0
             if scene is prim:  # an ordered frame of another picture of this size first (a raster-order frame leaves no history)
                 h.render_guarded(renderer, tables_of(moved), s, W, H)
             first = h.render_guarded(renderer, t, s, W, H)  # a new picture: geometric order (raster for the Sierpinski table)
-            tg.assert_bit_equal(first.cpu().numpy(), ref, "ordered, new picture")
+            h.assert_bit_equal(first.cpu().numpy(), ref, "ordered, new picture")
             for k in range(8):  # cost-ordered repeats, the last sort, then the settled order
                 assert ieq(h.render_guarded(renderer, t, s, W, H), first), f"repeat {k + 1}"
     finally:
@@ -146,7 +135,7 @@ def test_every_tile_order_writes_each_tile(renderer):
 
 # ---------------------------------------------------------------- light split
 def split_scene(W, H, nl):
-    prim = tg.all_primitives_scene(W, H)
+    prim = SB.all_primitives_scene(W, H)
     lights = [h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (-0.4, -1, -0.5)),
               h.make_light(abi.RM_LIGHT_POINT, (1, .9, .7), pos=(3, 2, 4), func=(0.7, 0.05, 0.01)),
               h.make_light(abi.RM_LIGHT_SPOT, (.6, .8, 1), direction=(0, -1, -0.3), pos=(0, 5, 1.5), func=(1, 0, 0),
@@ -170,7 +159,7 @@ def test_light_split_writes_every_tile(renderer, nl, shape):
             assert L.rm_debug_set_light_split(div) == 0
             first = h.render_guarded(renderer, t, s, W, H)
             if div == 32:
-                tg.assert_bit_equal(first.cpu().numpy(), h.oracle_render(scene, s, W, H, threads=16), "first frame vs oracle")
+                h.assert_bit_equal(first.cpu().numpy(), h.oracle_render(scene, s, W, H, threads=16), "first frame vs oracle")
                 want = first
             assert ieq(first, want)
             split = 0
@@ -192,7 +181,7 @@ def test_wavefront_pipeline_writes_every_pixel(renderer):
     import torch
     L = lib()
     W, H = 150, 83
-    scene = tg.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     t = tables_of(scene)
     s = abi.default_settings(mengerLevels=4, numReflection=2, enableReflection=1)
     ref, ref_b = h.oracle_render(scene, s, W, H, bright=True, threads=16)
@@ -200,11 +189,11 @@ def test_wavefront_pipeline_writes_every_pixel(renderer):
         assert L.rm_set_kernel_path(5) == 0
         out, br = h.render_guarded(renderer, t, s, W, H, bright=True)
         assert L.rm_debug_last_path() == 5
-        tg.assert_bit_equal(out.cpu().numpy(), ref, "wavefront frame")
-        tg.assert_bit_equal(br.cpu().numpy(), ref_b, "wavefront bright")
+        h.assert_bit_equal(out.cpu().numpy(), ref, "wavefront frame")
+        h.assert_bit_equal(br.cpu().numpy(), ref_b, "wavefront bright")
         for r0, r1 in ((17, 60), (0, 1), (82, 83), (40, 40)):
             part = h.render_guarded(renderer, t, s, W, H, r0, r1)
-            tg.assert_bit_equal(part.cpu().numpy(), ref[r0:r1], f"wavefront rows {r0}-{r1}")
+            h.assert_bit_equal(part.cpu().numpy(), ref[r0:r1], f"wavefront rows {r0}-{r1}")
         for N in (2, 3):
             for k in range(N):
                 rows = [L.rm_shard_row_to_frame(H, 8, k, N, i) for i in range(L.rm_shard_rows(H, 8, k, N))]
@@ -230,8 +219,8 @@ def test_row_ranges_off_tile_boundaries(renderer):
                 assert lib().rm_debug_set_tile_shape(shape) == 0
                 for r0, r1 in ((3, 61), (9, 10), (0, 1), (69, 70), (17, 69), (40, 40), (0, 0), (70, 70)):
                     out, br = h.render_guarded(renderer, t, s, W, H, r0, r1, bright=True)
-                    tg.assert_bit_equal(out.cpu().numpy(), ref[r0:r1], f"{name} rows {r0}-{r1} shape {shape}")
-                    tg.assert_bit_equal(br.cpu().numpy(), ref_b[r0:r1], f"{name} rows {r0}-{r1} shape {shape} bright")
+                    h.assert_bit_equal(out.cpu().numpy(), ref[r0:r1], f"{name} rows {r0}-{r1} shape {shape}")
+                    h.assert_bit_equal(br.cpu().numpy(), ref_b[r0:r1], f"{name} rows {r0}-{r1} shape {shape} bright")
         finally:
             lib().rm_debug_set_tile_shape(-1)
 
@@ -260,14 +249,14 @@ def test_row_tiles_gathers_and_rgba8(renderer, relief):
                 p, check = h.guarded((len(rows), W, 4), device=dev)
                 renderer.render_tiles(t, s, W, H, T, k, shards, out=p)
                 check()
-                tg.assert_bit_equal(p.cpu().numpy(), ref[rows], f"shard {k}/{shards}")
+                h.assert_bit_equal(p.cpu().numpy(), ref[rows], f"shard {k}/{shards}")
                 p8 = h.guarded_u8((len(rows), W, 4), lambda o: renderer.tiles_to_rgba8(p, out=o), device=dev)
                 assert (p8.cpu().numpy() == exp8[rows]).all(), f"tiles_to_rgba8 {k}/{shards}"
                 parts.append((p, p8))
             frame, check = h.guarded((H, W, 4), device=dev)
             renderer.deinterleave(torch.cat([p for p, _ in parts], 0).contiguous(), W, H, T, shards, out=frame)
             check()
-            tg.assert_bit_equal(frame.cpu().numpy(), ref, f"deinterleave {shards}")
+            h.assert_bit_equal(frame.cpu().numpy(), ref, f"deinterleave {shards}")
             slot = L.rm_gather_slot_rows(H, T, shards)
             g8 = torch.zeros((shards * slot, W, 4), dtype=torch.uint8, device=dev)
             for k, (_, p8) in enumerate(parts):
@@ -297,13 +286,13 @@ def render_batch_guarded(renderer, t, s, W, H, cams, globs):
 def test_batch_writes_every_frame_and_nothing_after_the_last(renderer, n):
     W, H = 37, 23
     scene, s, _ = kernel_class("table", W, H)
-    cams = tb.orbit((0.5, 1.8, 6), (-0.1, -0.25, -1), 45.0, W, H, n)
+    cams = SB.orbit((0.5, 1.8, 6), (-0.1, -0.25, -1), 45.0, W, H, n)
     globs = [scene[5]] * n
     out, br, check = render_batch_guarded(renderer, tables_of(scene), s, W, H, cams, globs)
     check()  # the guard after frame N − 1 is intact
     for f, (ref, ref_b) in enumerate(batch_refs(scene, s, W, H, cams, globs)):
-        tg.assert_bit_equal(out[f].cpu().numpy(), ref, f"batch of {n}, frame {f}")
-        tg.assert_bit_equal(br[f].cpu().numpy(), ref_b, f"batch of {n}, frame {f} bright")
+        h.assert_bit_equal(out[f].cpu().numpy(), ref, f"batch of {n}, frame {f}")
+        h.assert_bit_equal(br[f].cpu().numpy(), ref_b, f"batch of {n}, frame {f} bright")
 
 
 def test_batch_with_frames_taking_the_wavefront_pipeline_alone(renderer):
@@ -311,11 +300,11 @@ def test_batch_with_frames_taking_the_wavefront_pipeline_alone(renderer):
     them through the batched launches — two writers into one buffer, every frame written once."""
     L = lib()
     W, H = 45, 31
-    scene = tg.menger_scene(W, H)
+    scene = SB.menger_scene(W, H)
     s = abi.default_settings(mengerLevels=3, numReflection=1, enableReflection=1)
     n = 5
-    cams = tb.orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, n)
-    globs = [tb.with_globals(scene[5], iTime=0.7 * f, isTwoD=int(f in (1, 2))) for f in range(n)]
+    cams = SB.orbit((2.6, 2.2, 3.0), (-2.6, -2.2, -3.0), 30.0, W, H, n)
+    globs = [h.with_globals(scene[5], iTime=0.7 * f, isTwoD=int(f in (1, 2))) for f in range(n)]
     refs = batch_refs(scene, s, W, H, cams, globs)
     try:
         assert L.rm_set_kernel_path(5) == 0
@@ -324,8 +313,8 @@ def test_batch_with_frames_taking_the_wavefront_pipeline_alone(renderer):
     finally:
         L.rm_set_kernel_path(0)
     for f, (ref, ref_b) in enumerate(refs):
-        tg.assert_bit_equal(out[f].cpu().numpy(), ref, f"frame {f}")
-        tg.assert_bit_equal(br[f].cpu().numpy(), ref_b, f"frame {f} bright")
+        h.assert_bit_equal(out[f].cpu().numpy(), ref, f"frame {f}")
+        h.assert_bit_equal(br[f].cpu().numpy(), ref_b, f"frame {f} bright")
 
 
 # ---------------------------------------------------------------- post passes and probes
@@ -340,13 +329,13 @@ def test_post_process_writes_every_pixel(renderer, W, H):
     bright[..., 3] = 1.0
     fd, bd = torch.from_numpy(frag).to(renderer.device), torch.from_numpy(bright).to(renderer.device)
     for name in ("bloom", "bloom_hdr_fxaa", "hdr", "gamma_fxaa"):
-        post = abi.RmPostSettings(**{"exposure": 1.0, **tg.POST_CASES[name]})
+        post = abi.RmPostSettings(**{"exposure": 1.0, **SB.POST_CASES[name]})
         for with_bright in (True, False) if "bloom" not in name else (True,):  # bloom needs the BrightColor plane
             b = bright if with_bright else None
             out, check = h.guarded((H, W, 4), device=renderer.device)
             renderer.post_process(fd, bd if with_bright else None, post, out=out)
             check()
-            tg.assert_bit_equal(out.cpu().numpy(), h.oracle_post(frag, b, post), f"post {name} {W}x{H} bright={with_bright}")
+            h.assert_bit_equal(out.cpu().numpy(), h.oracle_post(frag, b, post), f"post {name} {W}x{H} bright={with_bright}")
 
 
 @pytest.mark.parametrize("n", [1, 63, 65, 1000])
@@ -359,8 +348,8 @@ def test_probes_write_exactly_n_results(renderer, n):
     out, check = h.guarded((n,), device=renderer.device)
     renderer.probe_math(abi.RM_FN_SIN, torch.from_numpy(x).to(renderer.device), out=out)
     check()
-    tg.assert_bit_equal(out.cpu().numpy(), ref, f"probe_math n={n}")
-    scene = tg.all_primitives_scene(64, 64)
+    h.assert_bit_equal(out.cpu().numpy(), ref, f"probe_math n={n}")
+    scene = SB.all_primitives_scene(64, 64)
     s = abi.default_settings()
     pts = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
     ref4 = np.empty((n, 4), dtype=np.float32)
@@ -370,7 +359,7 @@ def test_probes_write_exactly_n_results(renderer, n):
     out4, check4 = h.guarded((n, 4), device=renderer.device)
     renderer.probe_sdscene(tables_of(scene), s, torch.from_numpy(pts).to(renderer.device), out=out4)
     check4()
-    tg.assert_bit_equal(out4.cpu().numpy(), ref4, f"probe_sdscene n={n}")
+    h.assert_bit_equal(out4.cpu().numpy(), ref4, f"probe_sdscene n={n}")
 
 
 # ---------------------------------------------------------------- frames in flight
@@ -385,7 +374,7 @@ def test_frames_in_flight_on_three_streams(renderer):
     table = split_scene(W, H, 3)
     st = abi.default_settings(maxSteps=96, enableSoftShadow=1, enableAmbientOcclusion=1)
     Wm, Hm = 96, 61
-    menger = tg.menger_scene(Wm, Hm)
+    menger = SB.menger_scene(Wm, Hm)
     sm = abi.default_settings(mengerLevels=4, numReflection=2, enableReflection=1)
     Wl, Hl = 72, 40
     layers, sl, _ = kernel_class("layers", Wl, Hl)
@@ -414,7 +403,7 @@ def test_frames_in_flight_on_three_streams(renderer):
         L.rm_debug_set_light_split(-1)
     for name, k, out, check in outs:
         check()
-        tg.assert_bit_equal(out.cpu().numpy(), want[name], f"{name}, frame {k}")
+        h.assert_bit_equal(out.cpu().numpy(), want[name], f"{name}, frame {k}")
 
 
 # Both launch rings of acquire_slot (single frames, batches) only grow, once per process: their cases run in a fresh child process,
@@ -432,7 +421,7 @@ def ring_growth_case(renderer):
     heavy = h.scene_mandelbulb(W, H)
     sh = abi.default_settings(fractalIters=20, maxSteps=256)
     Ws, Hs = 33, 19
-    prim = tg.all_primitives_scene(Ws, Hs)
+    prim = SB.all_primitives_scene(Ws, Hs)
     small = [(h.make_camera((0.2 * i - 1.3, 1.6, 6), (0, -0.2, -1), (0, 1, 0), 45.0, Ws, Hs),) + prim[1:] for i in range(14)]
     s = abi.default_settings(maxSteps=96)
     # every table and buffer before the first launch: nothing but the launches themselves between the gate and the last one
@@ -447,9 +436,9 @@ def ring_growth_case(renderer):
     cbig()
     for i, (scene, (out, check)) in enumerate(zip(small, outs)):
         check()
-        tg.assert_bit_equal(out.cpu().numpy(), h.oracle_render(scene, s, Ws, Hs), f"small frame {i}")
+        h.assert_bit_equal(out.cpu().numpy(), h.oracle_render(scene, s, Ws, Hs), f"small frame {i}")
     for r in (0, 360, 719):  # the heavy frame: its first, middle and last rows against the oracle
-        tg.assert_bit_equal(big[r:r + 1].cpu().numpy(), h.oracle_render(heavy, sh, W, H, r, r + 1, threads=16), f"heavy row {r}")
+        h.assert_bit_equal(big[r:r + 1].cpu().numpy(), h.oracle_render(heavy, sh, W, H, r, r + 1, threads=16), f"heavy row {r}")
 
 
 def batch_slot_case(renderer):
@@ -461,8 +450,8 @@ def batch_slot_case(renderer):
     W, H = 64, 40
     scene, s, _ = kernel_class("bulb_plain", W, H)
     t = tables_of(scene)
-    cams = tb.orbit((0, 0, 4.5), (0, 0, -1), 30.0, W, H, 40, deg=3.0)
-    globs = [tb.with_globals(scene[5], iTime=0.1 * f) for f in range(40)]
+    cams = SB.orbit((0, 0, 4.5), (0, 0, -1), 30.0, W, H, 40, deg=3.0)
+    globs = [h.with_globals(scene[5], iTime=0.1 * f) for f in range(40)]
     refs = batch_refs(scene, s, W, H, cams, globs)
     sizes = [3, 2, 3, 1, 3, 2]
     bufs = [(h.guarded((k, H, W, 4), device=renderer.device), h.guarded((k, H, W, 4), device=renderer.device)) for k in sizes]
@@ -473,14 +462,14 @@ def batch_slot_case(renderer):
     torch.cuda.synchronize()
     check_big()
     for f in range(len(cams)):
-        tg.assert_bit_equal(big[f].cpu().numpy(), refs[f][0], f"40-frame batch, frame {f}")
-        tg.assert_bit_equal(big_br[f].cpu().numpy(), refs[f][1], f"40-frame batch, frame {f} bright")
+        h.assert_bit_equal(big[f].cpu().numpy(), refs[f][0], f"40-frame batch, frame {f}")
+        h.assert_bit_equal(big_br[f].cpu().numpy(), refs[f][1], f"40-frame batch, frame {f} bright")
     for i, (k, ((out, c1), (br, c2))) in enumerate(zip(sizes, bufs)):
         c1()
         c2()
         for f in range(k):
-            tg.assert_bit_equal(out[f].cpu().numpy(), refs[f][0], f"batch {i}, frame {f}")
-            tg.assert_bit_equal(br[f].cpu().numpy(), refs[f][1], f"batch {i}, frame {f} bright")
+            h.assert_bit_equal(out[f].cpu().numpy(), refs[f][0], f"batch {i}, frame {f}")
+            h.assert_bit_equal(br[f].cpu().numpy(), refs[f][1], f"batch {i}, frame {f} bright")
 
 
 _RING_CHILD = r'''

@@ -35,7 +35,7 @@ def shade(name, W, H, rays, s=None, image_width=None, scene=None):
 
 def trace(name, W, H, rays, s=None, image_width=None, mode="closest", empty=False):
     sc, s0, _ = L.case(name, W, H)
-    objs, no = (T.table([])) if empty else (sc[1], sc[2])
+    objs, no = (h.table([])) if empty else (sc[1], sc[2])
     return L.spec_trace_layers(objs, no, sc[5], s0 if s is None else s, rays, W if image_width is None else image_width, mode)
 
 
@@ -74,8 +74,8 @@ def test_classification_agrees_between_the_two_specs(name):
     scene, s, _ = L.case(name, W, H)
     s = L.with_features(s, L.SKY | L.TERRAIN | L.SEA)
     rays = L.primary_rays(name, W, H)
-    empty = (scene[0], T.table([])[0], 0, None, 0, scene[5])
-    col = np.concatenate(L.spec_shade_layers(empty, s, rays, scene[0].initialFar, W, {"noise": L.synthetic_noise()}), axis=1)[:, 0:3]
+    empty = (scene[0], h.table([])[0], 0, None, 0, scene[5])
+    col = np.concatenate(L.spec_shade_layers(empty, s, rays, scene[0].initialFar, W, {"noise": L.shared_noise()}), axis=1)[:, 0:3]
     ids = L.ids_of(trace(name, W, H, rays, s=s, empty=True))
     sky = L.sky_of(rays)
     differs = (L.bits(col) != L.bits(sky)).any(axis=1)

@@ -161,8 +161,8 @@ def test_phong_directional_light_on_a_sphere_centre():
 
 def test_shadow_reflection_refraction_change_the_image_in_the_expected_places():
     W, Hh = 64, 48
-    import test_gpu_parity as tg
-    scene = tg.reflect_refract_scene(W, Hh)
+    import scene_builders as SB
+    scene = SB.reflect_refract_scene(W, Hh)
     base = h.oracle_render(scene, abi.default_settings(), W, Hh)
     refl = h.oracle_render(scene, abi.default_settings(enableReflection=1), W, Hh)
     refr = h.oracle_render(scene, abi.default_settings(enableRefraction=1), W, Hh)

@@ -114,8 +114,8 @@ def vec(*v):
 
 # ---------------------------------------------------------------- rm_sdf_grid's refusals, in the header's order
 def _scene():
-    objs, no = V.table(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                       h.make_object(abi.RM_TORUS))
+    objs, no = h.table([h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
+                        h.make_object(abi.RM_TORUS)])
     return objs, no, h.make_globals()
 
 
@@ -165,7 +165,7 @@ def test_grid_unsupported_table_and_outputs():
         assert refused(grid(objs, no, g, s=abi.default_settings(features=feat), dims=(0, 1, 1)), text="lattice dimension"), feat
         assert refused(grid(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN"), feat
     assert refused(grid(objs, no, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
-    many, nm = V.table(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
+    many, nm = h.table([h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
     assert refused(grid(many, nm, g), CAPACITY, "RM_MAX_OBJECTS")
     assert refused(grid(many, nm, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")  # the 2-D mode comes before the table
     assert refused(grid(many, nm, g, dist=None), CAPACITY, "RM_MAX_OBJECTS")        # and the table before the output

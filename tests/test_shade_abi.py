@@ -9,7 +9,7 @@ import re
 import numpy as np
 
 import helpers as h
-import test_gpu_parity as P
+import scene_builders as SB
 from raymarcher_amd import abi, lib
 from raymarcher_amd._lib import LIB_PATH, SIGNATURES
 
@@ -184,7 +184,7 @@ def test_samplers_are_asked_for_as_by_rm_render_res():
     objs[2].texLoc = -1
     res.numTextures = abi.RM_MAX_TEXTURES + 1
     assert refused(call(objs, no, lights, nl, g, res=res), CAPACITY, "RM_MAX_TEXTURES")
-    scene = P.area_light_scene(8, 8)
+    scene = SB.area_light_scene(8, 8)
     assert refused(call(*scene[1:6]), UNSUPPORTED, "LTC")
     res = abi.RmResources()
     res.ltc1 = 0x3000

@@ -82,7 +82,7 @@ def test_spec_of_a_ray_aimed_away_is_exactly_the_background(feat, what):
         want = np.zeros((200, 3), dtype=np.float32)
     else:
         # getSky through the one-object-free frame of the oracle: an empty table renders the background for every pixel
-        empty, _ = T.table([])
+        empty, _ = h.table([])
         want = S.spec_shade((None, empty, 0, None, 0, scene[5]), s, rays, 100.0)[0][:, 0:3]
         assert len(np.unique(want, axis=0)) > 100, "the sky varies with the direction"
     S.assert_bits(col[:, 0:3], want, what)

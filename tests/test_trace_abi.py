@@ -10,8 +10,8 @@ import re
 import numpy as np
 import pytest
 
-import gbuffer_helpers as G
 import helpers as h
+import scene_builders as SB
 import trace_helpers as T
 from raymarcher_amd import abi, camera_rays, lib
 from raymarcher_amd._lib import LIB_PATH, SIGNATURES
@@ -168,7 +168,7 @@ def test_the_two_arrays():
 
 # ---------------------------------------------------------------- rm_camera_rays against the specification
 def _cameras(W, H):
-    return {"directional_light_2": G.directional_light_2(W, H)[0], "mandelbulb": h.scene_mandelbulb(W, H)[0]}
+    return {"directional_light_2": SB.directional_light_2(W, H)[0], "mandelbulb": h.scene_mandelbulb(W, H)[0]}
 
 
 @pytest.mark.parametrize("W,H", [(64, 36), (37, 23)])

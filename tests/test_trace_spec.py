@@ -6,6 +6,7 @@ import pytest
 
 import gbuffer_helpers as G
 import helpers as h
+import scene_builders as SB
 import trace_helpers as T
 from raymarcher_amd import abi, camera_rays
 
@@ -16,7 +17,7 @@ SURFACE_DIST = 1e-3  # frag:32
 @pytest.mark.parametrize("W,H", [(64, 36), (37, 23)])
 @pytest.mark.parametrize("name", ["directional_light_2", "mandelbulb"])
 def test_spec_on_a_cameras_rays_equals_the_gbuffer_spec_in_every_bit(name, W, H):
-    scene = G.directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
+    scene = SB.directional_light_2(W, H) if name == "directional_light_2" else h.scene_mandelbulb(W, H)
     s = abi.default_settings()
     rays = camera_rays(scene[0], W, H)
     hits = T.spec_trace(scene[1], scene[2], scene[5], s, rays)
@@ -49,7 +50,7 @@ def test_spec_invalid_rays_and_edges():
     assert T.ids_of(first).tolist() == [0, -1] and first[1, 3] == 0.0
     far = T.make_rays([[0, 0, 5]], [[0, 0, -1]], 50.0)
     assert T.ids_of(T.spec_trace(objs, n, g, s, far))[0] == 0
-    empty, _ = T.table([])
+    empty, _ = h.table([])
     for mode in T.MODES:
         assert T.ids_of(T.spec_trace(empty, 0, g, s, far, mode))[0] == -1
         assert T.ids_of(T.spec_trace(objs, n, g, abi.default_settings(maxSteps=0), far, mode))[0] == -1

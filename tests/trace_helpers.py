@@ -1,45 +1,27 @@
 """The specification of rm_trace_rays and rm_camera_rays for the tests: tests/trace_spec/rm_trace_spec.c, which includes the oracle's
-source and calls its own raymarch, getNormal, bumpNormal, v3_madd and softshadow as the definition reads, built on demand with gcc
-and oracle/Makefile's flags into tests/trace_spec/_build/ and loaded with ctypes, the way gbuffer_helpers.spec() is.  Nothing under
-oracle/ is touched.  Also the seeded ray sets and object tables that more than one trace test module uses."""
+source and calls its own raymarch, getNormal, bumpNormal, v3_madd and softshadow as the definition reads, built on demand and
+loaded with ctypes by helpers.load_spec.  Nothing under oracle/ is touched.  Also the seeded ray sets and object tables that more
+than one trace test module uses."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import gbuffer_helpers as G
 import helpers as h
 from raymarcher_amd import abi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPEC_DIR = os.path.join(HERE, "trace_spec")
-SPEC_SRC = os.path.join(SPEC_DIR, "rm_trace_spec.c")
-SPEC_SO = os.path.join(SPEC_DIR, "_build", "librm_trace_spec.so")
-_SPEC = None
+P = C.POINTER
+SIGNATURES = {
+    "rmo_spec_trace": (C.c_int, [P(abi.RmObject), C.c_int, P(abi.RmGlobals), P(abi.RmSettings), P(C.c_float), C.c_int, C.c_uint,
+                                 P(C.c_float)]),
+    "rmo_spec_primary_rays": (C.c_int, [P(abi.RmCamera), C.c_int, C.c_int, P(C.c_int32), C.c_int, P(C.c_float)]),
+}
 MODES = {"closest": abi.RM_TRACE_CLOSEST, "no_normal": abi.RM_TRACE_NO_NORMAL, "occlusion": abi.RM_TRACE_OCCLUSION}
+bits, assert_bits = h.bits, h.assert_bit_equal
 
 
 def spec():
-    """ctypes handle of the spec library, rebuilt when a source it is made of is newer."""
-    global _SPEC
-    if _SPEC is None:
-        deps = [SPEC_SRC] + [os.path.join(h.ROOT, "oracle", f) for f in ("rm_oracle.c", "rm_oracle.h", "rm_math.h")] + \
-               [os.path.join(h.ROOT, "include", "raymarcher_amd.h")]
-        if not os.path.exists(SPEC_SO) or os.path.getmtime(SPEC_SO) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(os.path.dirname(SPEC_SO), exist_ok=True)
-            tmp = f"{SPEC_SO}.{os.getpid()}.tmp"  # two test processes may build at once: each links its own file, then renames
-            subprocess.check_call([os.environ.get("CC", "gcc")] + G.CFLAGS + ["-shared", "-o", tmp, SPEC_SRC, "-lm"])
-            os.replace(tmp, SPEC_SO)
-        lib = C.CDLL(SPEC_SO)
-        P = C.POINTER
-        lib.rmo_spec_trace.restype = C.c_int
-        lib.rmo_spec_trace.argtypes = [P(abi.RmObject), C.c_int, P(abi.RmGlobals), P(abi.RmSettings), P(C.c_float), C.c_int, C.c_uint,
-                                       P(C.c_float)]
-        lib.rmo_spec_primary_rays.restype = C.c_int
-        lib.rmo_spec_primary_rays.argtypes = [P(abi.RmCamera), C.c_int, C.c_int, P(C.c_int32), C.c_int, P(C.c_float)]
-        _SPEC = lib
-    return _SPEC
+    """ctypes handle of the spec library (helpers.load_spec: rebuilt when a source it is made of is newer)."""
+    return h.load_spec("trace", SIGNATURES)
 
 
 def spec_trace(objs, num_objects, g, s, rays, mode="closest"):
@@ -65,15 +47,6 @@ def spec_primary_rays(cam, W, H, pixels=None):
 
 def ids_of(hits):
     return np.ascontiguousarray(hits[:, 7]).view(np.int32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ; first (ray, word) at {np.argwhere(bad)[:5].tolist()}"
 
 
 def make_rays(origin, direction, tmax):
@@ -157,14 +130,9 @@ def seeded_rays(rng, n, centre=(0.0, 0.0, 0.0), radius=2.0):
     return rays
 
 
-def table(objs):
-    objs = list(objs)
-    return (abi.RmObject * max(len(objs), 1))(*objs), len(objs)
-
-
 def sphere_table(scale, centre):
     """One RM_SPHERE of radius 0.5·scale at `centre` (the loader's uniform scale: scaleFactor = scale)."""
-    return table([h.make_object(abi.RM_SPHERE, model=h.translate(*centre) @ h.scale(scale, scale, scale), scale_factor=float(scale))])
+    return h.table([h.make_object(abi.RM_SPHERE, model=h.translate(*centre) @ h.scale(scale, scale, scale), scale_factor=float(scale))])
 
 
 def sphere_rays(rng, n, centre, R, impact_lo, impact_hi, tmax=100.0):
