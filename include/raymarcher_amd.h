@@ -642,6 +642,67 @@ int rm_sdf_mesh(const float *d_dist, const int32_t *d_objectId /* may be NULL */
                 void *stream);
 
 /*
+ * rm_shade_points — what the renderer thinks of POINTS the caller already has: the scene's distance and object at each point, its
+ * normal, its ambient occlusion and its shaded colour, with the point optionally projected onto the iso-surface first (no reference
+ * counterpart: the shader reaches a surface point only at the end of a ray of its own).  The points counterpart of rm_trace_rays /
+ * rm_shade_rays.  For the vertices of rm_sdf_mesh — normals, AO, baked colours, and vertices moved from the mean of their cell's
+ * edge crossings onto the surface —, particles and decals placed on a surface, a physics engine's contact normal, lighting baked
+ * into any point cloud.  d_points: numPoints float4 in device memory, rm_sdf_mesh's d_vertices as they are (w is not read); d_view
+ * (may be NULL): numPoints float4, the direction the point is seen along, rm_shade_rays' dir (w is not read).  Outputs, each may be
+ * NULL but not all three: d_surface, numPoints RmSurfacePoint; d_ao, a float each; d_rgba, a float4 each.  The tables, ps, g, s and
+ * res (may be NULL) are host memory, copied before return.  Asynchronous on `stream`.
+ * Definition for point i, bit for bit (the oracle's functions under the rm_math contract; madd is render's fused a·s + b).
+ * 1. p = points[i].xyz; with d_view, rd = view[i].xyz.  Invalid point: a non-finite component of p or, with d_view, a non-finite
+ *    component of rd or rd all zeros.  It stores objectId = RM_RAY_INVALID and zeros in the rest of d_surface, 0 in d_ao, (0, 0, 0, 0)
+ *    in d_rgba, and evaluates nothing.  Points are device data: the host cannot refuse them.
+ * 2. Projection.  p0 = p; projectSteps times: sc = sdScene(p) (frag:1406-1430), stop if sc.minObjIdx == −1; e = sc.minD − iso; N =
+ *    getNormal(p) (frag:1436-1444, never bumped); q = madd(N, −e, p); stop if a component of q is not finite; m = q − p0; stop unless
+ *    dot(m, m) <= maxMove·maxMove (one binary32 product; +inf admits every finite q); p = q.  A stop keeps the last accepted p.
+ * 3. sc = sdScene(p) with the shader's trap (UB3: the trap of the last fractal evaluated, as the primary march has it); distance =
+ *    sc.minD, objectId = sc.minObjIdx, position = p.  objectId == −1 (an empty table, a NaN estimate): normal zeros, ao 0, colour
+ *    (0, 0, 0, 0), done.
+ * 4. N = getNormal(p) (frag:1436-1444), then bumpNormal(N, p, 10, 2) (frag:1679-1691) under RM_FEAT_PERLIN_BUMP; normal = N.
+ * 5. With d_ao: calcAO(p, N) (frag:1729-1740), whatever s->enableAmbientOcclusion says.
+ * 6. With d_rgba: rd = view[i].xyz if d_view is given, else −N (the point seen head-on: the view-independent bake).  Then render()
+ *    from behind its march (frag:2337-2375) with res.intersectObj = objectId, res.trap = sc.trap and maxT = ps->far: an emissive
+ *    object gives (color, 1); otherwise getPhong(N, objectId, p, rd, far) (frag:1842-1933; ambient occlusion under
+ *    s->enableAmbientOcclusion, shadow rays, area lights) times the Mandelbulb's or the sponge's trap palette (frag:2354-2365), alpha
+ *    1.  No reflection and no refraction: those are rays, rm_shade_rays' business.  A hit point of rm_trace_rays with view = the ray's
+ *    dir gives rm_shade_rays' colour where that ray fires no secondary ray and the march's object is sdScene's at the hit point
+ *    (on a Mandelbulb or a sponge up to the orbit trap, which the march has from its last evaluated point, res.d short of the hit).
+ *    An area light seen head-on is degenerate where V = N in every bit — LTC_Evaluate (frag:368-424) normalises V − N·(N·V), a zero
+ *    vector — and the colour is NaN there, as it is for a ray that meets a surface exactly along its normal: pass d_view with area lights.
+ * Work follows the outputs: d_surface alone costs 1 + 4 evaluations of sdScene plus 5 per projection step; d_ao adds AO's taps;
+ * only d_rgba marches shadow rays and reads lights and samplers (without it `lights` may be NULL and the samplers are not checked).
+ * The result of a point does not depend on which points share its call, and every output holds the same bits whichever of the
+ * others are NULL.  `far` is ONE value per call, as rm_shade_rays has it.
+ * numPoints == 0: RM_OK, nothing read or written.  Otherwise, in this order and all but the last before any HIP call:
+ * RM_ERR_INVALID_ARGUMENT: numPoints < 0; null ps, g or s, a null table with a positive count (the lights' only with d_rgba) or a
+ * negative count; far NaN, negative or infinite; iso not finite; maxMove NaN or negative (+inf is valid); projectSteps outside 0 …
+ * RM_MAX_PROJECT_STEPS; all three outputs NULL.  RM_ERR_UNSUPPORTED: RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA, g->isTwoD.  Then
+ * the scene: with d_rgba rm_render_res's checks with its statuses (rm_shade_rays' list), without it rm_trace_rays' checks of the
+ * table.  RM_ERR_INVALID_ARGUMENT: null or misaligned d_points, a misaligned d_view, d_surface or d_rgba (16 bytes) or d_ao (4
+ * bytes); an array or, with d_rgba, a sampler's pixels that are not device memory.
+ * Schedule: ONE launch, one lane per point, 256-lane workgroups, of the points kernel of the scene's class — the table walk, the
+ * general Mandelbulb, its plain form, or the samplers' (rm_debug_last_path() = 17, rm_debug_last_split() = 0); the Mandelbulb
+ * classes march hard shadows from directional lights in the wave's shadow pool, as rm_shade_rays does.  It uses one slot of the batch
+ * ring of scene blocks and neither reads nor changes the per-stream tuner and tile-order state of single-frame renders, and no
+ * library workspace.  With rm_set_timing(1) it counts as one launch, all stage 1.  Points that share a wave (64 consecutive points)
+ * cost what the dearest of them costs: keep neighbours together (rm_sdf_mesh's vertex order does).
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmSurfacePoint { float normal[3]; float distance; float position[3]; int32_t objectId; } RmSurfacePoint; /* 32 bytes, RmRayHit's shape */
+typedef struct RmPointsSettings { float far; float iso; float maxMove; int32_t projectSteps; } RmPointsSettings;
+void rm_points_settings_default(RmPointsSettings *ps);   /* far 100, iso 0.001 (the march's hit threshold), maxMove +inf, projectSteps 0 */
+#define RM_MAX_PROJECT_STEPS 16
+int rm_shade_points(const float *d_points /* float4 each: rm_sdf_mesh's d_vertices as they are; w is not read */,
+                    const float *d_view /* float4 each, may be NULL */, int numPoints, const RmPointsSettings *ps,
+                    const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
+                    const RmSettings *s, const RmResources *res /* may be NULL */,
+                    RmSurfacePoint *d_surface /* may be NULL */, float *d_ao /* 1 float each, may be NULL */,
+                    float *d_rgba /* float4 each, may be NULL */, void *stream);
+
+/*
  * rm_render_tiles — the multi-GPU shard of the same frame (no reference counterpart; the reference
  * renders whole frames on one GPU).  The frame is cut into tiles of `tileRows` rows; this call renders
  * tiles t with t % numShards == shard, packed contiguously in tile order into d_rgba
@@ -788,7 +849,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
- * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid (none of them is a value rm_set_kernel_path takes). */
+ * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points (none of them is a value
+ * rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups
@@ -1019,6 +1081,11 @@ int rm_write_png(const char *path, const uint8_t *rgba, int W, int H);
  * quad that names a vertex outside 0 … numVertices − 1 (nothing is written then); RM_ERR_IO: the file cannot be opened or written. */
 int rm_write_ply(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads,
                  const uint8_t *rgb /* may be NULL, 3 per vertex */);
+/* rm_write_ply with vertex normals: with normals4 (4 floats per vertex — RmSurfacePoint's first four, or any float4 array —, the
+ * fourth not written; may be NULL) `property float nx`, `ny`, `nz` follow z, ahead of the colour.  With normals4 == NULL the file is
+ * rm_write_ply's, byte for byte; the statuses are rm_write_ply's. */
+int rm_write_ply_ex(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads,
+                    const uint8_t *rgb /* may be NULL */, const float *normals4 /* may be NULL; 4 floats per vertex, the fourth not written */);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,10 @@ SIGNATURES = {
                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_sdf_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), C.c_float, C.c_int, C.c_int,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_points_settings_default": (None, [_P(abi.RmPointsSettings)]),
+    "rm_shade_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(abi.RmPointsSettings), _P(abi.RmObject), C.c_int, _P(abi.RmLight),
+                                  C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     "rm_camera_rays": (C.c_int, [_P(abi.RmCamera), C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_void_p]),
     "rm_render_tiles_res": (C.c_int, _SCENE_ARGS + [_P(abi.RmResources), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
@@ -135,6 +139,7 @@ SIGNATURES = {
     "rm_scene_object_texture": (C.c_char_p, [C.c_void_p, C.c_int]),
     "rm_write_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "rm_write_ply": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "rm_write_ply_ex": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rm_abi_sizeof": (C.c_int, [C.c_int]),
 }
 

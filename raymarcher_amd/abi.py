@@ -127,6 +127,18 @@ RM_PATH_SDF_GRID = 16  # … behind rm_sdf_grid
 RM_MAX_LATTICE_DIM = 4096  # points per axis of a lattice of rm_sdf_grid / rm_sdf_mesh
 
 
+class RmSurfacePoint(C.Structure):
+    _fields_ = [("normal", f32 * 3), ("distance", f32), ("position", f32 * 3), ("objectId", i32)]
+
+
+class RmPointsSettings(C.Structure):
+    _fields_ = [("far", f32), ("iso", f32), ("maxMove", f32), ("projectSteps", i32)]
+
+
+RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
+RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
+
+
 def default_settings(**over):
     """RmSettings with the reference's constants (frag:28,29,45,1056; frag:9,15)."""
     s = RmSettings(0, 0, 0, 0, 0, 256, 20, 4, 1, RM_FEAT_REFERENCE_DEFAULT)

@@ -360,8 +360,12 @@ int rm_write_png(const char *path, const uint8_t *rgba, int W, int H) {
   return RM_OK;
 }
 
-// Binary little-endian PLY: the header, the vertices (x, y, z and the optional colour), the faces (a count byte and four indices).
+// Binary little-endian PLY: the header, the vertices (x, y, z and the optional normal and colour), the faces (a count byte and four indices).
 int rm_write_ply(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads, const uint8_t *rgb) {
+  return rm_write_ply_ex(path, vertices4, numVertices, quads4, numQuads, rgb, nullptr);
+}
+int rm_write_ply_ex(const char *path, const float *vertices4, int numVertices, const int32_t *quads4, int numQuads, const uint8_t *rgb,
+                    const float *normals4) {
   if (!path || numVertices < 0 || numQuads < 0 || (numVertices > 0 && !vertices4) || (numQuads > 0 && !quads4)) {
     set_error("bad ply arguments");
     return RM_ERR_INVALID_ARGUMENT;
@@ -376,14 +380,16 @@ int rm_write_ply(const char *path, const float *vertices4, int numVertices, cons
   if (*reinterpret_cast<const uint8_t *>(&probe) != 1) { set_error("rm_write_ply needs a little-endian host"); return RM_ERR_UNSUPPORTED; }
   std::string head = "ply\nformat binary_little_endian 1.0\ncomment raymarcher_amd rm_sdf_mesh\nelement vertex " + std::to_string(numVertices) +
                      "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (normals4) head += "property float nx\nproperty float ny\nproperty float nz\n";
   if (rgb) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
   head += "element face " + std::to_string(numQuads) + "\nproperty list uchar int vertex_indices\nend_header\n";
-  const size_t vsize = rgb ? 15 : 12;
+  const size_t vsize = 12 + (normals4 ? 12 : 0) + (rgb ? 3 : 0);
   std::vector<uint8_t> body((size_t)numVertices * vsize + (size_t)numQuads * 17);
   uint8_t *o = body.data();
   for (int v = 0; v < numVertices; v++) {
     std::memcpy(o, vertices4 + (size_t)v * 4, 12);
     o += 12;
+    if (normals4) { std::memcpy(o, normals4 + (size_t)v * 4, 12); o += 12; }
     if (rgb) { std::memcpy(o, rgb + (size_t)v * 3, 3); o += 3; }
   }
   for (int q = 0; q < numQuads; q++) {

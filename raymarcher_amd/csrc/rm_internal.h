@@ -118,6 +118,13 @@ int launch_trace_layers_kernel(const void *sb, int bulbClass, bool noNormal, con
 int check_lattice(const float *origin, const float *step, int nx, int ny, int nz);
 int launch_sdf_grid_kernel(const void *sb, int bulbClass, const float origin[3], const float step[3], int nx, int ny, int nz,
                            float *d_dist, int32_t *d_objectId, hipStream_t stream);
+// The points kernels (rm_points.hip, rm_shade_points; a translation unit of its own for the same reason): the launch of
+// shade_points_kernel<bulbClass, tex> over the ONE staged SceneBlock `sb`, one lane per point — numPoints float4 from d_points and,
+// when d_view is not null, from d_view; into whichever of d_surface (numPoints RmSurfacePoint), d_ao (a float each) and d_rgba (a
+// float4 each) are not null.
+int launch_points_kernel(const void *sb, int bulbClass, bool tex, const float *d_points, const float *d_view, int numPoints,
+                         int projectSteps, float iso, float maxMove, void *d_surface, float *d_ao, float *d_rgba,
+                         hipStream_t stream);
 // The kernels of rm_render_adaptive (rm_adaptive.hip, a translation unit of its own for the same reason).  Classify: the contrast
 // test over frames f0 … f0 + grid.z − 1 of d_rgba (grid: their 8×8 tiles), into d_mask (may be null; whole-batch pointer) and the chunk's lists and
 // counters (frame z of the chunk: W·H words from d_list + z·W·H, count in d_counts[z], zeroed by the caller).  Refine: the

@@ -1174,6 +1174,75 @@ int launch_shade(const ShadeCall &c) {
   return finish_frames(sf, c.layers ? 14 : 13);
 }
 
+// ---- points from memory (rm_shade_points) -----------------------------------------------------------------------------------------
+// rm_shade_points (the header has the definition): the scene's distance, object, normal, ambient occlusion and shaded colour at the
+// caller's points against ONE scene.  PointsCall stands beside ShadeCall and its checks run in check_shade's order with its helpers,
+// every one but the last ahead of the first HIP call: numPoints, the pointers and counts, the point settings, the outputs (at least
+// one), the layers and the 2-D mode, the scene, the arrays, device memory.  Only a call with d_rgba reads lights and samplers: it is
+// checked and staged as launch_shade's (validate_scene, the caller's lights and resources, the frame's class); a call without it as
+// launch_trace's (check_object_table, no lights, no resources, the table's march class).  The camera is zeros but for initialFar =
+// ps->far.  Then ONE launch of shade_points_kernel (rm_points.hip), path 17: no tuner, tile-order or workspace state is read or changed.
+struct PointsCall {
+  const float *d_points, *d_view; int numPoints; const RmPointsSettings *ps;
+  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
+  const RmGlobals *g; const RmSettings *s; const RmResources &res;
+  RmSurfacePoint *d_surface; float *d_ao, *d_rgba; hipStream_t stream;
+};
+int check_points(const PointsCall &c, const RmCamera &cam) {
+  if (c.numPoints < 0) { set_error("negative numPoints"); return RM_ERR_INVALID_ARGUMENT; }
+  if (c.numPoints == 0) return RM_OK;
+  if (!c.ps || !c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.d_rgba && c.numLights > 0 && !c.lights) || c.numObjects < 0 ||
+      c.numLights < 0) {
+    set_error("null ps, scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  const RmPointsSettings &ps = *c.ps;
+  if (!(ps.far >= 0.0f) || ps.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!(ps.iso - ps.iso == 0.0f)) { set_error("iso must be finite"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!(ps.maxMove >= 0.0f)) { set_error("maxMove must not be negative (+inf: no limit)"); return RM_ERR_INVALID_ARGUMENT; }
+  if (ps.projectSteps < 0 || ps.projectSteps > RM_MAX_PROJECT_STEPS) {
+    set_error("projectSteps outside 0 … RM_MAX_PROJECT_STEPS");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (!c.d_surface && !c.d_ao && !c.d_rgba) { set_error("d_surface, d_ao and d_rgba are all null: nothing to compute"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = refuse_layers(c.s, "rm_shade_points shades points of the object table: TERRAIN / CLOUD / SEA have no distance field here");
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) has no surface points")) != RM_OK) return st;
+  if (c.d_rgba) st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res);
+  else st = check_object_table(c.objs, c.numObjects, c.s);
+  if (st != RM_OK) return st;
+  if (!c.d_points) { set_error("null d_points"); return RM_ERR_INVALID_ARGUMENT; }
+  if (((uintptr_t)c.d_points | (uintptr_t)c.d_view | (uintptr_t)c.d_surface | (uintptr_t)c.d_rgba) & 15u) {
+    set_error("d_points, d_view, d_surface and d_rgba must be 16-byte aligned");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if ((uintptr_t)c.d_ao & 3u) { set_error("d_ao must be 4-byte aligned"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = require_device_pointers({{"d_points", c.d_points}, {"d_view", c.d_view}, {"d_surface", c.d_surface}, {"d_ao", c.d_ao}})) != RM_OK)
+    return st;
+  return c.d_rgba ? check_device_pointers(c.res, c.d_rgba, nullptr) : RM_OK;
+}
+int launch_points(const PointsCall &c) {
+  RmCamera cam{};
+  if (c.ps) cam.initialFar = c.ps->far;
+  int st = check_points(c, cam);
+  if (st != RM_OK || c.numPoints == 0) return st;
+  const bool plain = bulb_plain(c.objs, c.numObjects, c.g) != 0;
+  int bulbClass = table_bulb_class(c.objs, c.numObjects, plain);
+  bool tex = false;
+  if (c.d_rgba) {
+    const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
+    bulbClass = bulb_class(fc, plain);
+    tex = fc.textured;
+  }
+  StagedFrames sf(c.stream);
+  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        if (c.d_rgba) fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
+        else fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
+      })) != RM_OK) return st;
+  if ((st = launch_points_kernel(sf.slot->dev, bulbClass, tex, c.d_points, c.d_view, c.numPoints, c.ps->projectSteps, c.ps->iso,
+                                 c.ps->maxMove, c.d_surface, c.d_ao, c.d_rgba, c.stream)) != RM_OK) return st;
+  return finish_frames(sf, 17);
+}
+
 // ---- the field on a lattice (rm_sdf_grid) ----------------------------------------------------------------------------------------
 // rm_sdf_grid (the header has the definition): sdScene at the points of a dense lattice against ONE object table.  The checks run in
 // the header's order, every one but the last ahead of the first HIP call: the pointers and the table's count, the lattice
@@ -1321,6 +1390,20 @@ int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageW
 int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
                          const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream) {
   return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream), true, imageWidth});
+}
+
+void rm_points_settings_default(RmPointsSettings *ps) {
+  if (!ps) return;
+  ps->far = 100.0f;
+  ps->iso = 0.001f;
+  ps->maxMove = __builtin_inff();
+  ps->projectSteps = 0;
+}
+int rm_shade_points(const float *d_points, const float *d_view, int numPoints, const RmPointsSettings *ps, const RmObject *objs,
+                    int numObjects, const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s, const RmResources *res,
+                    RmSurfacePoint *d_surface, float *d_ao, float *d_rgba, void *stream) {
+  return launch_points(PointsCall{d_points, d_view, numPoints, ps, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources,
+                                  d_surface, d_ao, d_rgba, static_cast<hipStream_t>(stream)});
 }
 
 int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3], const float step[3],

@@ -356,20 +356,35 @@ def mesh_bounds(tables, margin=0.0):
 def write_ply(path, vertices, quads, colours=None):
     """rm_write_ply: the mesh of extract_mesh / scene_mesh as a binary little-endian PLY.  vertices (n, 4) float32 and quads (m, 4)
     int32, tensors or arrays; colours: (n, 3) uint8 or None."""
+    return write_ply_ex(path, vertices, quads, colours)
+
+
+def write_ply_ex(path, vertices, quads, colours=None, normals=None):
+    """write_ply with vertex normals, the mesh of bake_mesh as it is: normals (n, 3) or (n, 4) float32 or None — with them the file
+    goes through rm_write_ply_ex and carries nx, ny, nz behind z; without them it is write_ply's file, byte for byte."""
     import numpy as np
 
     def host(a, dtype, cols):
         a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
         a = np.ascontiguousarray(a, dtype=dtype)
-        if a.ndim != 2 or a.shape[1] != cols:
-            raise ValueError(f"expected an (n, {cols}) array, got {a.shape}")
+        if a.ndim != 2 or a.shape[1] not in cols:
+            raise ValueError(f"expected an (n, {cols[0]}) array, got {a.shape}")
         return a
-    v, q = host(vertices, np.float32, 4), host(quads, np.int32, 4)
-    c = None if colours is None else host(colours, np.uint8, 3)
+    v, q = host(vertices, np.float32, (4,)), host(quads, np.int32, (4,))
+    c = None if colours is None else host(colours, np.uint8, (3,))
     if c is not None and c.shape[0] != v.shape[0]:
         raise ValueError("one colour per vertex")
-    check(lib().rm_write_ply(str(path).encode(), C.c_void_p(v.ctypes.data), v.shape[0], C.c_void_p(q.ctypes.data), q.shape[0],
-                             C.c_void_p(c.ctypes.data) if c is not None else None))
+    cp = C.c_void_p(c.ctypes.data) if c is not None else None
+    if normals is None:
+        check(lib().rm_write_ply(str(path).encode(), C.c_void_p(v.ctypes.data), v.shape[0], C.c_void_p(q.ctypes.data), q.shape[0], cp))
+        return path
+    n3 = host(normals, np.float32, (3, 4))
+    if n3.shape[0] != v.shape[0]:
+        raise ValueError("one normal per vertex")
+    n4 = np.zeros((v.shape[0], 4), dtype=np.float32)
+    n4[:, :n3.shape[1]] = n3
+    check(lib().rm_write_ply_ex(str(path).encode(), C.c_void_p(v.ctypes.data), v.shape[0], C.c_void_p(q.ctypes.data), q.shape[0], cp,
+                                C.c_void_p(n4.ctypes.data)))
     return path
 
 
@@ -744,6 +759,10 @@ class Renderer:
         and the lattice reaches one step past the bounds on every side, so a surface inside the bounds is closed.  iso: 0.001, the
         march's hit threshold — what the renderer shows as the surface, and the smallest value that has a Mandelbulb's inside.
         bounds: (lo, hi), or None for mesh_bounds(tables)."""
+        return self._scene_mesh(tables, settings, resolution, iso, bounds)[:3]
+
+    def _scene_mesh(self, tables, settings, resolution, iso, bounds):
+        """scene_mesh's mesh and, behind it, the lattice step it chose."""
         import numpy as np
         if int(resolution) < 4:
             raise ValueError("resolution must be at least 4")
@@ -756,7 +775,71 @@ class Renderer:
         dims = [min(int(resolution), int(np.ceil(sd / step)) + 3) for sd in side]
         origin = lo - step
         dist, obj = self.sdf_grid(tables, settings, origin, (step,) * 3, dims, ids=True)
-        return self.extract_mesh(dist, origin, (step,) * 3, iso, obj)
+        return self.extract_mesh(dist, origin, (step,) * 3, iso, obj) + (step,)
+
+    def shade_points(self, tables, settings, points, view=None, far=None, colour=True, ao=False, project=0, iso=0.001,
+                     max_move=float("inf")):
+        """rm_shade_points: what the renderer thinks of points the caller already has, one lane per point in one launch → (normal,
+        distance, position, object_id, ao or None, colour or None): float32 (n, 3), (n), (n, 3) and int32 (n), views of ONE float32
+        (n, 8) device tensor of RmSurfacePoint rows; float32 (n) with ao=True; float32 (n, 4) with colour=True.  points: float32
+        (n, 3) or (n, 4) (scene_mesh's vertices as they are; the fourth is not read), view: the same shapes or None — numpy arrays,
+        which are uploaded, or tensors on this device.  project: steps that move each point onto the surface {distance = iso}
+        before anything is evaluated, none of them farther than max_move from where the point began; position is where it ended.
+        object_id −1: no object there (zeros everywhere); abi.RM_RAY_INVALID: a non-finite point or a non-finite or zero view.
+        colour: render()'s shading at the point — materials, textures, trap palettes, shadows from the scene's lights, no reflection
+        or refraction — seen along view, or head-on (−normal) without one; far (None = tables.camera.initialFar): the shadow
+        marches' limit.  ao: calcAO at the point whatever settings.enableAmbientOcclusion says.  The definition is in
+        include/raymarcher_amd.h."""
+        t = self.torch
+        pts = self._points(points, "points")
+        n = pts.shape[0]
+        vw = None if view is None else self._points(view, "view")
+        if vw is not None and vw.shape[0] != n:
+            raise ValueError("one view direction per point")
+        ps = abi.RmPointsSettings(tables.camera.initialFar if far is None else far, iso, max_move, int(project))
+        surface = t.empty((n, 8), dtype=t.float32, device=self.device)
+        aos = t.empty((n,), dtype=t.float32, device=self.device) if ao else None
+        col = t.empty((n, 4), dtype=t.float32, device=self.device) if colour else None
+        res, _keep = self._resources(tables)
+        check(lib().rm_shade_points(C.c_void_p(pts.data_ptr()), C.c_void_p(vw.data_ptr()) if vw is not None else None, n, C.byref(ps),
+                                    tables.objects, tables.num_objects, tables.lights, tables.num_lights, C.byref(tables.globals_),
+                                    C.byref(settings), C.byref(res), C.c_void_p(surface.data_ptr()),
+                                    C.c_void_p(aos.data_ptr()) if ao else None, C.c_void_p(col.data_ptr()) if colour else None,
+                                    self._stream()))
+        return surface[:, 0:3], surface[:, 3], surface[:, 4:7], surface[:, 7].view(t.int32), aos, col
+
+    def _points(self, a, name):
+        """`a` as shade_points takes points and views: (n, 3) or (n, 4) float32, uploaded if it is a numpy array → a contiguous
+        (n, 4) tensor on this device (an (n, 4) tensor that is one already is used in place)."""
+        t = self.torch
+        if not t.is_tensor(a):
+            import numpy as np
+            a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        if a.dim() != 2 or a.shape[1] not in (3, 4) or a.dtype != t.float32:
+            raise ValueError(f"{name} must be float32 of shape (n, 3) or (n, 4)")
+        a = a.to(self.device)
+        if a.shape[1] == 3:
+            a = t.cat([a, t.zeros((a.shape[0], 1), dtype=t.float32, device=self.device)], dim=1)
+        return a.contiguous()
+
+    def bake_mesh(self, tables, settings, resolution, iso=0.001, bounds=None, project=2, ao=True, colour=True):
+        """scene_mesh with everything a DCC tool wants on its vertices → (vertices float32 (n, 4), quads int32 (m, 4), object indices
+        int32 (n), normals float32 (n, 3), ao float32 (n) or None, colours uint8 (n, 3) or None).  The mesh is scene_mesh's; its
+        vertices then go through shade_points with `project` steps onto {distance = iso}, none farther than half the diagonal of a
+        lattice cell from where surface nets put it, so a vertex stays near its cell; the vertices returned are the projected ones
+        (w = 0) and the object indices are sdScene's at them.  Colours are the view-independent bake (each vertex seen head-on)
+        through to_rgba8, the library's one float → 8-bit conversion.  write_ply_ex takes the result as it is."""
+        t = self.torch
+        verts, quads, _vobj, step = self._scene_mesh(tables, settings, resolution, iso, bounds)
+        normal, _d, position, object_id, aos, col = self.shade_points(tables, settings, verts, colour=colour, ao=ao, project=project,
+                                                                        iso=iso, max_move=0.5 * step * 3.0 ** 0.5)
+        n = verts.shape[0]
+        out = t.zeros((n, 4), dtype=t.float32, device=self.device)
+        out[:, 0:3] = position
+        rgb = None
+        if colour:  # the n colours as one row of a frame: a single row has nothing to flip
+            rgb = self.to_rgba8(col.view(1, n, 4))[0, :, 0:3].contiguous() if n else t.empty((0, 3), dtype=t.uint8, device=self.device)
+        return out, quads, object_id.contiguous(), normal.contiguous(), aos, rgb
 
     def pick(self, tables, settings, W, H, x, y, camera=None):
         """What lies under pixel (x, y) of a W×H frame (y = 0 the bottom row) → (object_id, position, normal, t): an int (−1: nothing),
