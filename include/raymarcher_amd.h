@@ -642,6 +642,95 @@ int rm_sdf_mesh(const float *d_dist, const int32_t *d_objectId /* may be NULL */
                 void *stream);
 
 /*
+ * Block-sparse lattices — rm_sdf_grid and rm_sdf_mesh beyond the dense lattice's limits (no reference counterpart).  A dense lattice
+ * holds 4 B per point of distances, of ids and of vertex numbers and at most INT_MAX points, to find a surface that passes through a
+ * few per cent of its cells.  The three entry points below keep only the blocks the surface passes through.
+ * Terms.  A BLOCK is 8×8×8 cells: 9×9×9 lattice points.  The VIRTUAL LATTICE has mx × my × mz blocks, each dimension 1 …
+ * RM_MAX_LATTICE_BLOCKS, so 8·m + 1 points per axis; lattice point (i, j, k) is origin + (float)i · step per axis, rm_sdf_grid's
+ * formula exactly, and there is no INT_MAX rule on the number of points.  A BLOCK LIST is numBlocks entries of int32[4], (bi, bj, bk,
+ * unused), in device memory, numBlocks 0 … RM_MAX_BLOCK_LIST (2^31 cells: vertex numbers fit 32 bits).  An entry is VOID if a
+ * coordinate lies outside [0, m) or an earlier entry has the same coordinates — of equal entries the first counts.  Lists are device
+ * data, which the host cannot refuse: void entries are skipped everywhere.
+ * All three: asynchronous on `stream`; the table, g, s, origin and step are host memory, copied before return; added without a change
+ * of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_MAX_LATTICE_BLOCKS 512
+#define RM_MAX_BLOCK_LIST (1 << 22)
+/*
+ * rm_sdf_blocks_select — WHICH blocks hold surface.  Block (bi, bj, bk) is ACTIVE iff inside(v) = v < iso (a NaN is outside) is not
+ * the same for all 729 of its lattice points, v being sdScene(p).minD in rm_sdf_grid's bits.  That is equivalent to "one of its 512
+ * cells is active in rm_sdf_mesh's sense" (a cell is active iff its eight corners differ in inside; the block's points are connected
+ * through its cells' edges, so two points that differ have a cell between them whose corners differ) — decided exactly, from the
+ * block's own points, with no Lipschitz bound, which the estimators do not honour.  The active blocks are listed in their linear order
+ * (bk·my + bj)·mx + bi, as (bi, bj, bk, 0).  d_count always receives the FULL number of active blocks; only the first maxBlocks
+ * entries are stored.  maxBlocks = 0 with a null d_blocks is the counting call.  Nothing of the lattice is stored: every point is
+ * evaluated once, in every block that has it, and only a flag per block is kept.
+ * In this order, and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: null g, s, origin or step, a null table with a
+ * positive count or a negative count, an origin component that is not finite, a step component that is not finite or not greater
+ * than 0, a block dimension below 1 or above RM_MAX_LATTICE_BLOCKS, iso not finite, a negative maxBlocks; RM_ERR_UNSUPPORTED:
+ * RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA in the settings, g->isTwoD; rm_trace_rays' checks of the table (rm_sdf_grid's);
+ * RM_ERR_INVALID_ARGUMENT: a null d_count, a null d_blocks with maxBlocks above 0, an output that is not device memory.
+ * Schedule: staging is rm_sdf_grid's.  One workgroup per block of the virtual lattice and one lane per point of it, in runs of 64 of
+ * the block's x-fastest order: twelve waves, the evaluator of rm_sdf_grid's kernel of the table's march class; a lane outside the 729
+ * points leaves before the evaluation, so a point's value does not depend on its wave.  Per block the waves' ballots of inside and of
+ * !inside are ORed: active iff both are non-empty.  Then a count / scan / emit compaction of the flags in linear order
+ * (rm_debug_last_path() = 18, rm_debug_last_split() = 0; with rm_set_timing(1) it counts as one launch, all stage 1).  Workspace, grow-
+ * only per (device, stream), shared with the two entry points below: 4 B per block of the virtual lattice + 8 B per 1024 blocks;
+ * rm_set_workspace_limit applies (a lattice over a set limit: RM_ERR_DEVICE), rm_release_workspaces frees it.
+ */
+int rm_sdf_blocks_select(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                         const float step[3], int mx, int my, int mz, float iso, int maxBlocks, int32_t *d_blocks /* int4 each */,
+                         uint32_t *d_count /* 1 word */, void *stream);
+/*
+ * rm_sdf_grid_blocks — the lattice, stored only where listed.  Entry n owns floats [n·729, (n + 1)·729) of d_dist (and as many int32
+ * of d_objectId, which may be NULL); its local point (a, b, c), each 0 … 8, is stored at (c·9 + b)·9 + a and holds the value at
+ * lattice point (8·bi + a, 8·bj + b, 8·bk + c): the bits rm_sdf_grid stores for that point of the dense lattice.  Points on shared
+ * faces are stored once per block that has them (1.42× the storage): blocks are independent, rm_sdf_mesh_blocks needs no
+ * neighbour's values.  A void entry's slot is not written.  numBlocks = 0: RM_OK, nothing is read or written.
+ * In this order, and all but the last before any HIP call: rm_sdf_blocks_select's refusals up to the block dimensions;
+ * RM_ERR_INVALID_ARGUMENT: numBlocks below 0 or above RM_MAX_BLOCK_LIST; the layers, the 2-D mode and the table's checks as above;
+ * then, with numBlocks above 0, RM_ERR_INVALID_ARGUMENT: a null d_blocks or d_dist, an array that is not device memory.
+ * Schedule: staging is rm_sdf_grid's.  The block map of the list — 4 B per block of the virtual lattice in the workspace above, filled
+ * by a scatter that keeps the smallest list position, which is what makes a later equal entry void — then ONE launch of
+ * rm_sdf_blocks_select's evaluation kernel, a workgroup per entry (rm_debug_last_path() = 19, rm_debug_last_split() = 0).
+ */
+int rm_sdf_grid_blocks(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                       const float step[3], int mx, int my, int mz, const int32_t *d_blocks /* int4 each */, int numBlocks,
+                       float *d_dist /* numBlocks·729 */, int32_t *d_objectId /* may be NULL */, void *stream);
+/*
+ * rm_sdf_mesh_blocks — surface nets over a block list: rm_sdf_mesh's mesh of the virtual lattice, restricted to the listed blocks and
+ * renumbered.  d_dist and d_objectId (may be NULL) in rm_sdf_grid_blocks' layout, from there or from anywhere else.
+ * Cells and vertices: cell (i, j, k) of a block that is not void reads that block's own 729 values; its corner mask, whether it is
+ * active, its vertex and its vertex object are rm_sdf_mesh's, computed with the GLOBAL cell index: a vertex has the bits rm_sdf_mesh
+ * gives that cell on the dense lattice.  Vertex order: by list position of the block, then by local cell index (c·8 + b)·8 + a.
+ * Quads: the lattice edge from P along an axis gives a quad under rm_sdf_mesh's rule — its ends differ in inside and it is interior in
+ * the other two axes of the VIRTUAL lattice —, over the same four cells in the same orientation.  P is always corner 0 of an existing
+ * cell, and that cell's block owns the edge.  The quad is stored iff all four cells lie in listed blocks that are not void.  Quad
+ * order: by list position of the owning block, then by P's local index (c·8 + b)·8 + a, then by axis x, y, z.
+ * d_counts: [0] the number of vertices and [1] the number of quads, FULL numbers whatever the capacities (the quads' saturates at
+ * 2^32 − 1); [2] the number of OPEN vertices: active cells of listed blocks with at least one crossed, quad-giving edge one of whose
+ * four cells lies in an unlisted block — the listed vertices of the dense mesh's quads that this list drops.  [2] = 0 means that every
+ * component of the dense mesh that has a vertex in the list is complete; with the list of rm_sdf_blocks_select at the same iso it is 0
+ * and the mesh is the whole dense mesh.  Capacities and the counting call (maxVertices = maxQuads = 0, null outputs) are rm_sdf_mesh's.
+ * numBlocks = 0: RM_OK, all three counts 0.
+ * Precondition: a point on a face that two listed blocks share holds equal bits in both, which rm_sdf_grid_blocks guarantees.
+ * Otherwise the result is unspecified but memory-safe: stored vertex numbers stay below d_counts[0].
+ * In this order, and all but the last before any HIP call, RM_ERR_INVALID_ARGUMENT: null origin or step, an origin component that is
+ * not finite, a step component that is not finite or not greater than 0, a block dimension below 1 or above RM_MAX_LATTICE_BLOCKS;
+ * iso not finite; numBlocks below 0 or above RM_MAX_BLOCK_LIST; a negative capacity; a null d_vertices or d_quads with its capacity
+ * above 0; a null d_counts, or a null d_dist or d_blocks with numBlocks above 0; an array that is not device memory.
+ * Schedule: the block map; one workgroup per list entry that counts its active cells, stored quads and open vertices and keeps the
+ * 512-bit mask of its active cells; an exclusive scan over the entries that also stores d_counts; then — unless both capacities are 0
+ * — one workgroup per entry for its vertices and quads, a cell's vertex number being its block's base + the mask's bits below the
+ * cell: 68 B per entry in place of rm_sdf_mesh's 4 B per cell.  Workspace (the one above): 4 B per block of the virtual lattice + 88 B
+ * per list entry.  Not a render launch: rm_debug_last_path() keeps its value and rm_set_timing does not time it.
+ */
+int rm_sdf_mesh_blocks(const float *d_dist, const int32_t *d_objectId /* may be NULL */, const int32_t *d_blocks /* int4 each */,
+                       int numBlocks, int mx, int my, int mz, const float origin[3], const float step[3], float iso, int maxVertices,
+                       int maxQuads, float *d_vertices /* float4 each */, int32_t *d_vertexObject /* may be NULL */,
+                       int32_t *d_quads /* int4 each */, uint32_t *d_counts /* 3 words */, void *stream);
+
+/*
  * rm_shade_points — what the renderer thinks of POINTS the caller already has: the scene's distance and object at each point, its
  * normal, its ambient occlusion and its shaded colour, with the point optionally projected onto the iso-surface first (no reference
  * counterpart: the shader reaches a surface point only at the end of a ray of its own).  The points counterpart of rm_trace_rays /
@@ -849,8 +938,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * batch of rm_render_batch that went out as one launch of the one-lane-per-pixel kernel, 7 = a launch of rm_render_supersampled
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
- * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points (none of them is a value
- * rm_set_kernel_path takes). */
+ * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
+ * 19 = a launch of rm_sdf_grid_blocks (none of them is a value rm_set_kernel_path takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

@@ -42,7 +42,7 @@ int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
 // different streams of one device may run concurrently on the GPU and therefore never share scratch.  Growing
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
-enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8 };
+enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8, kWsBlocks = 9 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 // The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
 // this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).
@@ -118,6 +118,20 @@ int launch_trace_layers_kernel(const void *sb, int bulbClass, bool noNormal, con
 int check_lattice(const float *origin, const float *step, int nx, int ny, int nz);
 int launch_sdf_grid_kernel(const void *sb, int bulbClass, const float origin[3], const float step[3], int nx, int ny, int nz,
                            float *d_dist, int32_t *d_objectId, hipStream_t stream);
+// The block-sparse lattice kernels (rm_blocks.hip, rm_sdf_blocks_select, rm_sdf_grid_blocks and rm_sdf_mesh_blocks; a translation
+// unit of its own for the same reason).  check_block_lattice: the rules the three entry points have for origin, step and the block
+// dimensions, no HIP call.  launch_blocks_select_kernels: blocks_eval_kernel<bulbClass, select> over the ONE staged SceneBlock `sb`,
+// a workgroup per block of the virtual lattice, then the compaction of the flags into d_blocks and d_count; `workspace` holds
+// blocks_select_workspace bytes.  launch_blocks_grid_kernels: the block map of the list, then blocks_eval_kernel<bulbClass, grid>, a
+// workgroup per entry — 729 values per entry that is not void into d_dist and, when d_objectId is not null, as many object indices;
+// `workspace` holds blocks_map_workspace bytes.  rm_sdf_mesh_blocks is whole in rm_blocks.hip.
+int check_block_lattice(const float *origin, const float *step, int mx, int my, int mz);
+size_t blocks_select_workspace(int mx, int my, int mz);
+size_t blocks_map_workspace(int mx, int my, int mz);
+int launch_blocks_select_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz, float iso,
+                                 int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace, hipStream_t stream);
+int launch_blocks_grid_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz,
+                               const int32_t *d_blocks, int numBlocks, float *d_dist, int32_t *d_objectId, void *workspace, hipStream_t stream);
 // The points kernels (rm_points.hip, rm_shade_points; a translation unit of its own for the same reason): the launch of
 // shade_points_kernel<bulbClass, tex> over the ONE staged SceneBlock `sb`, one lane per point — numPoints float4 from d_points and,
 // when d_view is not null, from d_view; into whichever of d_surface (numPoints RmSurfacePoint), d_ao (a float each) and d_rgba (a

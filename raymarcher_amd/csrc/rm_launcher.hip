@@ -1271,6 +1271,69 @@ int launch_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, co
   return finish_frames(sf, 16);
 }
 
+// ---- the field on the blocks of a virtual lattice (rm_sdf_blocks_select, rm_sdf_grid_blocks) -------------------------------------
+// Both (the header has the definitions) are rm_sdf_grid on blocks of 8×8×8 cells: launch_sdf_grid's checks in its order with
+// check_block_lattice in check_lattice's place and the call's own behind it, every one but the last ahead of the first HIP call;
+// launch_sdf_grid's staging behind the stream's workspace (kWsBlocks), which is taken under the device's lock as launch_adaptive
+// takes its own.  rm_sdf_blocks_select: one launch of blocks_eval_kernel (rm_blocks.hip) over every block of the lattice, which
+// keeps a flag per block, and the compaction of the flags, path 18.  rm_sdf_grid_blocks: the block map of the list (void entries),
+// then one launch of the same kernel over the list's entries, path 19.
+struct BlocksCall {
+  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s; const float *origin, *step; int mx, my, mz;
+  hipStream_t stream;
+};
+int check_blocks_scene(const BlocksCall &c, const char *layersText) {
+  int st = refuse_layers(c.s, layersText);
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) has no distance field")) != RM_OK) return st;
+  return check_object_table(c.objs, c.numObjects, c.s);
+}
+int check_blocks_head(const BlocksCall &c) {
+  if (!c.g || !c.s || !c.origin || !c.step) { set_error("null g, s, origin or step"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((c.numObjects > 0 && !c.objs) || c.numObjects < 0) { set_error("null object table or negative count"); return RM_ERR_INVALID_ARGUMENT; }
+  return check_block_lattice(c.origin, c.step, c.mx, c.my, c.mz);
+}
+template <class Launch>
+int stage_blocks_call(const BlocksCall &c, size_t workspaceBytes, int path, Launch launch) {
+  const int bulbClass = table_bulb_class(c.objs, c.numObjects, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  const RmCamera noCam{};
+  StagedFrames sf(c.stream);
+  int st = sf.lock_device();  // ahead of the workspace, which is in use until the last launch (rm_release_workspaces)
+  if (st != RM_OK) return st;
+  void *mem = nullptr;
+  if ((st = stream_workspace(kWsBlocks, c.stream, workspaceBytes, &mem)) != RM_OK) return st;
+  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
+      })) != RM_OK) return st;
+  if ((st = launch(sf.slot->dev, bulbClass, mem)) != RM_OK) return st;
+  return finish_frames(sf, path);
+}
+int launch_sdf_blocks_select(const BlocksCall &c, float iso, int maxBlocks, int32_t *d_blocks, uint32_t *d_count) {
+  int st = check_blocks_head(c);
+  if (st != RM_OK) return st;
+  if (!(iso - iso == 0.0f)) { set_error("iso must be finite"); return RM_ERR_INVALID_ARGUMENT; }
+  if (maxBlocks < 0) { set_error("negative maxBlocks"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = check_blocks_scene(c, "rm_sdf_blocks_select evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK)
+    return st;
+  if ((maxBlocks > 0 && !d_blocks) || !d_count) { set_error("null d_count, or null d_blocks with maxBlocks above 0"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = require_device_pointers({{"d_blocks", d_blocks}, {"d_count", d_count}})) != RM_OK) return st;
+  return stage_blocks_call(c, blocks_select_workspace(c.mx, c.my, c.mz), 18, [&](const SceneBlock *sb, int bulbClass, void *mem) {
+    return launch_blocks_select_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, iso, maxBlocks, d_blocks, d_count, mem, c.stream);
+  });
+}
+int launch_sdf_grid_blocks(const BlocksCall &c, const int32_t *d_blocks, int numBlocks, float *d_dist, int32_t *d_objectId) {
+  int st = check_blocks_head(c);
+  if (st != RM_OK) return st;
+  if (numBlocks < 0 || numBlocks > RM_MAX_BLOCK_LIST) { set_error("numBlocks must be 0 … RM_MAX_BLOCK_LIST"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = check_blocks_scene(c, "rm_sdf_grid_blocks evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK)
+    return st;
+  if (numBlocks == 0) return RM_OK;
+  if (!d_blocks || !d_dist) { set_error("null d_blocks or d_dist"); return RM_ERR_INVALID_ARGUMENT; }
+  if ((st = require_device_pointers({{"d_blocks", d_blocks}, {"d_dist", d_dist}, {"d_objectId", d_objectId}})) != RM_OK) return st;
+  return stage_blocks_call(c, blocks_map_workspace(c.mx, c.my, c.mz), 19, [&](const SceneBlock *sb, int bulbClass, void *mem) {
+    return launch_blocks_grid_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, d_blocks, numBlocks, d_dist, d_objectId, mem, c.stream);
+  });
+}
+
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
 // single frames, then launch(the device's block) behind it.
 template <class Launch>
@@ -1409,6 +1472,20 @@ int rm_shade_points(const float *d_points, const float *d_view, int numPoints, c
 int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3], const float step[3],
                 int nx, int ny, int nz, float *d_dist, int32_t *d_objectId, void *stream) {
   return launch_sdf_grid(objs, numObjects, g, s, origin, step, nx, ny, nz, d_dist, d_objectId, static_cast<hipStream_t>(stream));
+}
+
+int rm_sdf_blocks_select(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                         const float step[3], int mx, int my, int mz, float iso, int maxBlocks, int32_t *d_blocks, uint32_t *d_count,
+                         void *stream) {
+  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, maxBlocks,
+                                  d_blocks, d_count);
+}
+
+int rm_sdf_grid_blocks(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                       const float step[3], int mx, int my, int mz, const int32_t *d_blocks, int numBlocks, float *d_dist,
+                       int32_t *d_objectId, void *stream) {
+  return launch_sdf_grid_blocks(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, d_blocks,
+                                numBlocks, d_dist, d_objectId);
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,

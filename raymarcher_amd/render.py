@@ -763,6 +763,13 @@ class Renderer:
 
     def _scene_mesh(self, tables, settings, resolution, iso, bounds):
         """scene_mesh's mesh and, behind it, the lattice step it chose."""
+        origin, step, dims = self._scene_lattice(tables, resolution, bounds)
+        dist, obj = self.sdf_grid(tables, settings, origin, (step,) * 3, dims, ids=True)
+        return self.extract_mesh(dist, origin, (step,) * 3, iso, obj) + (step,)
+
+    @staticmethod
+    def _scene_lattice(tables, resolution, bounds):
+        """The lattice scene_mesh lays over the bounds → (origin, step, dims)."""
         import numpy as np
         if int(resolution) < 4:
             raise ValueError("resolution must be at least 4")
@@ -773,9 +780,126 @@ class Renderer:
             raise ValueError("bounds must be (lo, hi) with three finite components each and lo < hi")
         step = float(side.max()) / (int(resolution) - 3)
         dims = [min(int(resolution), int(np.ceil(sd / step)) + 3) for sd in side]
-        origin = lo - step
-        dist, obj = self.sdf_grid(tables, settings, origin, (step,) * 3, dims, ids=True)
-        return self.extract_mesh(dist, origin, (step,) * 3, iso, obj) + (step,)
+        return lo - step, step, dims
+
+    # ---- block-sparse lattices: blocks of 8×8×8 cells, kept only where the surface passes (include/raymarcher_amd.h) ----
+    @staticmethod
+    def _blocks3(blocks):
+        mx, my, mz = (int(b) for b in blocks)
+        if min(mx, my, mz) < 1:
+            raise ValueError("every block dimension must be at least 1")
+        return mx, my, mz
+
+    def _block_list(self, block_list):
+        t = self.torch
+        if (not t.is_tensor(block_list) or block_list.dim() != 2 or block_list.shape[1] != 4 or block_list.dtype != t.int32
+                or not block_list.is_contiguous() or block_list.device != self.device):
+            raise ValueError(f"block_list must be a contiguous int32 tensor of shape (n, 4) on {self.device}")
+        return block_list
+
+    def sdf_active_blocks(self, tables, settings, origin, step, blocks, iso):
+        """rm_sdf_blocks_select: the blocks of the virtual lattice of blocks = (mx, my, mz) blocks — 8·m + 1 points per axis, point
+        (i, j, k) at origin + (i, j, k) · step — whose 729 points are not all on one side of iso → int32 (n, 4) rows (bi, bj, bk,
+        0) in linear order.  One call with a capacity guess, one more with the exact capacity if the count exceeded it."""
+        t = self.torch
+        mx, my, mz = self._blocks3(blocks)
+        o, st = _vec3(origin, "origin"), _vec3(step, "step")
+        count = t.zeros(1, dtype=t.int32, device=self.device)
+
+        def call(capacity):
+            out = t.empty((capacity, 4), dtype=t.int32, device=self.device)
+            check(lib().rm_sdf_blocks_select(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings), o, st, mx,
+                                             my, mz, float(iso), capacity, C.c_void_p(out.data_ptr()) if capacity else None,
+                                             C.c_void_p(count.data_ptr()), self._stream()))
+            return out, int(count.item()) & 0xFFFFFFFF
+
+        # a surface crosses about as many blocks as a few of the lattice's faces have
+        guess = min(mx * my * mz, max(64, 4 * (mx * my + my * mz + mz * mx)))
+        out, n = call(guess)
+        if n > guess:
+            if n > abi.RM_MAX_BLOCK_LIST:
+                raise RaymarcherError(abi.RM_ERR_CAPACITY, f"{n} active blocks exceed RM_MAX_BLOCK_LIST: split the bounds")
+            out, again = call(n)
+            if again != n:
+                raise RuntimeError(f"rm_sdf_blocks_select counted {n} blocks, then {again}: the scene changed between the calls")
+        return out[:n]
+
+    def sdf_grid_blocks(self, tables, settings, origin, step, blocks, block_list, ids=False):
+        """rm_sdf_grid_blocks: the scene's distance function on the listed blocks only → float32 (n, 9, 9, 9), entry n's values as
+        [c, b, a], x fastest; with ids=True the pair (distances, int32 object indices of the same shape).  The values are
+        sdf_grid's at those lattice points; the slot of a void entry (outside the lattice, or a repeat) is left unwritten."""
+        t = self.torch
+        mx, my, mz = self._blocks3(blocks)
+        bl = self._block_list(block_list)
+        n = bl.shape[0]
+        dist = t.empty((n, 9, 9, 9), dtype=t.float32, device=self.device)
+        obj = t.empty((n, 9, 9, 9), dtype=t.int32, device=self.device) if ids else None
+        check(lib().rm_sdf_grid_blocks(tables.objects, tables.num_objects, C.byref(tables.globals_), C.byref(settings), _vec3(origin, "origin"),
+                                       _vec3(step, "step"), mx, my, mz, C.c_void_p(bl.data_ptr()) if n else None, n,
+                                       C.c_void_p(dist.data_ptr()) if n else None, C.c_void_p(obj.data_ptr()) if ids and n else None,
+                                       self._stream()))
+        return (dist, obj) if ids else dist
+
+    def extract_mesh_blocks(self, grid_blocks, block_list, blocks, origin, step, iso=0.0, ids=None):
+        """rm_sdf_mesh_blocks: extract_mesh over a block list → (vertices float32 (n, 4), quads int32 (m, 4), open_vertices), with the
+        vertices' object indices int32 (n) ahead of open_vertices when `ids` (int32, grid_blocks' shape) is given.  grid_blocks:
+        float32 (n, 9, 9, 9) from sdf_grid_blocks.  open_vertices = 0: no quad of the dense mesh that touches a listed block is
+        missing.  A counting call, one read of three words, then an emitting call with exact capacities; raises if the two disagree."""
+        t = self.torch
+        mx, my, mz = self._blocks3(blocks)
+        bl = self._block_list(block_list)
+        n = bl.shape[0]
+        if (tuple(grid_blocks.shape) != (n, 9, 9, 9) or grid_blocks.dtype != t.float32 or not grid_blocks.is_contiguous()
+                or grid_blocks.device != self.device):
+            raise ValueError(f"grid_blocks must be a contiguous float32 tensor of shape ({n}, 9, 9, 9) on {self.device}")
+        if ids is not None and (tuple(ids.shape) != (n, 9, 9, 9) or ids.dtype != t.int32 or not ids.is_contiguous() or ids.device != self.device):
+            raise ValueError(f"ids must be a contiguous int32 tensor of shape ({n}, 9, 9, 9) on {self.device}")
+        o, st = _vec3(origin, "origin"), _vec3(step, "step")
+        counts = t.zeros(4, dtype=t.int32, device=self.device)
+
+        def call(max_v, max_q, v, vo, q):
+            check(lib().rm_sdf_mesh_blocks(C.c_void_p(grid_blocks.data_ptr()) if n else None, C.c_void_p(ids.data_ptr()) if ids is not None and n else None,
+                                           C.c_void_p(bl.data_ptr()) if n else None, n, mx, my, mz, o, st, float(iso), max_v, max_q,
+                                           C.c_void_p(v.data_ptr()) if v is not None else None,
+                                           C.c_void_p(vo.data_ptr()) if vo is not None else None,
+                                           C.c_void_p(q.data_ptr()) if q is not None else None, C.c_void_p(counts.data_ptr()), self._stream()))
+            return tuple(int(x) & 0xFFFFFFFF for x in counts[:3].tolist())
+
+        nv, nq, nopen = call(0, 0, None, None, None)
+        if nv > 2 ** 31 - 1 or nq > 2 ** 31 - 1:
+            raise RaymarcherError(abi.RM_ERR_CAPACITY, f"{nv} vertices and {nq} quads exceed one call's capacity")
+        verts = t.empty((nv, 4), dtype=t.float32, device=self.device)
+        quads = t.empty((nq, 4), dtype=t.int32, device=self.device)
+        vobj = t.empty((nv,), dtype=t.int32, device=self.device) if ids is not None else None
+        if nv or nq:
+            again = call(nv, nq, verts if nv else None, vobj if nv else None, quads if nq else None)
+            if again != (nv, nq, nopen):
+                raise RuntimeError(f"rm_sdf_mesh_blocks counted {(nv, nq, nopen)}, then {again}: the blocks changed between the calls")
+        return (verts, quads, vobj, nopen) if ids is not None else (verts, quads, nopen)
+
+    def scene_mesh_sparse(self, tables, settings, resolution, iso=0.001, bounds=None):
+        """scene_mesh beyond the dense lattice's limits: the active blocks of the lattice (sdf_active_blocks), the field on them
+        (sdf_grid_blocks), the mesh over them (extract_mesh_blocks) → (vertices, quads, vertex object indices).  resolution (4 …
+        4097), step and origin are scene_mesh's; the lattice has ceil((points − 1) / 8) blocks per axis, so it runs past the
+        bounds on the high side.  The mesh is the dense mesh of that lattice."""
+        return self._scene_mesh_sparse(tables, settings, resolution, iso, bounds)[:3]
+
+    def _scene_mesh_sparse(self, tables, settings, resolution, iso, bounds):
+        """scene_mesh_sparse's mesh and, behind it, the lattice step it chose."""
+        if int(resolution) > 8 * abi.RM_MAX_LATTICE_BLOCKS + 1:
+            raise ValueError("resolution must be at most 4097")
+        origin, step, dims = self._scene_lattice(tables, resolution, bounds)
+        blocks = [(d - 1 + 7) // 8 for d in dims]
+        bl = self.sdf_active_blocks(tables, settings, origin, (step,) * 3, blocks, iso)
+        dist, obj = self.sdf_grid_blocks(tables, settings, origin, (step,) * 3, blocks, bl, ids=True)
+        verts, quads, vobj, nopen = self.extract_mesh_blocks(dist, bl, blocks, origin, (step,) * 3, iso, obj)
+        if nopen != 0:
+            raise RuntimeError(f"{nopen} open vertices over the list of the lattice's own active blocks")
+        return verts, quads, vobj, step
+
+    def bake_mesh_sparse(self, tables, settings, resolution, iso=0.001, bounds=None, project=2, ao=True, colour=True):
+        """bake_mesh on top of scene_mesh_sparse: the same outputs, resolution up to 4097."""
+        return self._bake(tables, settings, self._scene_mesh_sparse(tables, settings, resolution, iso, bounds), iso, project, ao, colour)
 
     def shade_points(self, tables, settings, points, view=None, far=None, colour=True, ao=False, project=0, iso=0.001,
                      max_move=float("inf")):
@@ -829,8 +953,12 @@ class Renderer:
         lattice cell from where surface nets put it, so a vertex stays near its cell; the vertices returned are the projected ones
         (w = 0) and the object indices are sdScene's at them.  Colours are the view-independent bake (each vertex seen head-on)
         through to_rgba8, the library's one float → 8-bit conversion.  write_ply_ex takes the result as it is."""
+        return self._bake(tables, settings, self._scene_mesh(tables, settings, resolution, iso, bounds), iso, project, ao, colour)
+
+    def _bake(self, tables, settings, mesh, iso, project, ao, colour):
+        """bake_mesh behind its mesh: (vertices, quads, vertex objects, step) of _scene_mesh or _scene_mesh_sparse."""
         t = self.torch
-        verts, quads, _vobj, step = self._scene_mesh(tables, settings, resolution, iso, bounds)
+        verts, quads, _vobj, step = mesh
         normal, _d, position, object_id, aos, col = self.shade_points(tables, settings, verts, colour=colour, ao=ao, project=project,
                                                                         iso=iso, max_move=0.5 * step * 3.0 ** 0.5)
         n = verts.shape[0]
