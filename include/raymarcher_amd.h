@@ -567,6 +567,59 @@ int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const
                          const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream);
 
 /*
+ * rm_rays_order — a COHERENCE ORDERING of an RmRay array, on the device (no reference counterpart).  rm_trace_rays, rm_shade_rays
+ * and their _layers twins run one lane per ray, 64 consecutive rays per wave, and a wave costs what its longest ray costs: rays that
+ * come in no order — secondary and ambient-occlusion rays from hit points, light probes, line-of-sight queries, rays read back from
+ * another tracer — pay several times what the same rays cost in the order of a picture's 8×8 tiles.  This entry sorts them so that
+ * the rays of a wave start close together and go the same way; rm_rays_restore puts results back in the caller's order.  Since the
+ * result of a ray does not depend on which other rays share its call, sorting changes no result bit.
+ * d_rays: numRays RmRay; d_order: numRays int32, required; d_sorted (may be NULL): numRays RmRay; d_keys (may be NULL): numRays
+ * uint64; all device memory.  Asynchronous on `stream`.
+ * Definition, bit for bit (raymarcher_amd/csrc/rm_ray_key.h is the same text as code).  All arithmetic is binary32, round to nearest
+ * even, denormals kept, nothing fused, `/` correctly rounded.
+ * VALID for ordering: every component of origin and dir is finite and dir is not all zeros.  tMax and `reserved` are NOT read: a ray
+ * that only rm_trace_rays calls invalid, by its tMax, is ordered by its geometry.
+ * Direction coordinates of a valid ray, an octahedral map: s = (|dx| + |dy|) + |dz|; px = dx / s; py = dy / s; if dz < 0: u = (1 −
+ * |py|) · sgn(px) and v = (1 − |px|) · sgn(py), sgn being −1 where the sign bit is set and +1 otherwise; else u = px, v = py.  Where s
+ * overflows to +inf, px = py = 0: that is the definition, and harmless.
+ * Bounds: lo and hi of each of the five coordinates ox, oy, oz, u, v over the valid rays of the call — an exact minimum and maximum,
+ * so they do not depend on an order.  Which of −0 and +0 becomes a bound where both occur changes no key.
+ * Quantise x to b bits: 0 unless hi > lo; else t = (x − lo) / (hi − lo), three rounded operations, and q = t >= 1 ? 2^b − 1 : (t > 0
+ * ? (uint)(t · 2^b) : 0); a NaN t (inf / inf) gives 0.
+ * Key, with originBits in 0 … 10 and dirBits in 0 … 11: morton3(q_ox, q_oy, q_oz) << (2·dirBits) | morton2(q_u, q_v), x the lowest
+ * bit of each origin triple and u the lowest bit of each direction pair.  A ray that is not valid gets 1 << (3·originBits +
+ * 2·dirBits), above every valid key: such rays end together in the last waves.
+ * Order: the STABLE ascending sort of the keys.  d_order[k] = the input index of the ray at sorted position k; equal keys keep
+ * their input order.  d_sorted[k] = d_rays[d_order[k]], all 32 bytes verbatim, tMax and `reserved` included.  d_keys receives the
+ * keys in INPUT order (for callers who merge orderings).  Every output holds the same bits whichever of the others are NULL.
+ * In this order, and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: numRays < 0; originBits or dirBits out of
+ * range.  Then numRays == 0: RM_OK, nothing read or written.  RM_ERR_INVALID_ARGUMENT: null d_rays or d_order; a misaligned pointer
+ * (16 bytes for d_rays and d_sorted, 8 for d_keys, 4 for d_order); d_sorted == d_rays; an array that is not device memory.
+ * Schedule: the bounds (per workgroup: lanes, the wave, LDS; one partial per workgroup, then a one-workgroup merge — no float
+ * atomic), the keys, then a least-significant-digit radix sort of (key, index) pairs, 8 bits per pass over the 3·originBits +
+ * 2·dirBits + 1 key bits: per pass a histogram per tile of RM_RAYS_ORDER_TILE keys, a scan (a launch of its own) and a stable
+ * scatter; a pass whose digit is the same in every key is skipped (with ONE origin for all rays every origin digit is); then the
+ * gather of d_sorted.  No kernel waits for another workgroup.  Workspace, grow-only and per (device, stream): 24 B per ray (two key
+ * and two index buffers) + 1 KB per tile + 24 KB; rm_set_workspace_limit applies (over a set limit, or when the allocation fails:
+ * RM_ERR_DEVICE, as rm_sdf_blocks_select has it, and HIP's error state is left clean), rm_release_workspaces frees it.  Not a render
+ * launch: rm_debug_last_path() and rm_debug_last_split() keep their values and rm_set_timing does not time it.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_RAYS_ORDER_TILE 2048 /* keys per workgroup of the sort */
+int rm_rays_order(const RmRay *d_rays, int numRays, int originBits, int dirBits, int32_t *d_order, RmRay *d_sorted /* may be NULL */,
+                  uint64_t *d_keys /* may be NULL */, void *stream);
+/*
+ * rm_rays_restore — the inverse of an ordering, for results: d_out[d_order[k]] = d_rows[k] for k < numRows.  rowBytes is 16 (a float4
+ * colour of rm_shade_rays) or 32 (RmRayHit, RmSurfacePoint).  An entry of d_order outside [0, numRows) is skipped and that row is
+ * not written: the order is device data, the host cannot refuse it.  With a permutation — rm_rays_order's d_order — every row of
+ * d_out is written once.  Asynchronous on `stream`; one launch, one lane per 16 bytes; no workspace; not a render launch.
+ * In this order, and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: numRows < 0; rowBytes other than 16 or 32.  Then
+ * numRows == 0: RM_OK, nothing read or written.  RM_ERR_INVALID_ARGUMENT: null d_rows, d_order or d_out; a misaligned pointer (16
+ * bytes for d_rows and d_out, 4 for d_order); d_out == d_rows; an array that is not device memory.
+ */
+int rm_rays_restore(const void *d_rows, const int32_t *d_order, int numRows, int rowBytes, void *d_out, void *stream);
+
+/*
  * rm_sdf_grid — WHERE the surface is: sdScene on a dense lattice (no reference counterpart: the shader evaluates its distance
  * function only along its own rays).  For a 3-D texture of the field (physics, particles, a caller's own ambient occlusion, keeping
  * a camera out of the scene without a ray) and as the input of rm_sdf_mesh.  d_dist: nx·ny·nz floats in device memory, d_objectId

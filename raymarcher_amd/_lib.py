@@ -55,6 +55,8 @@ SIGNATURES = {
                                        _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_trace_rays_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings),
                                        C.c_uint, C.c_void_p, C.c_void_p]),
+    "rm_rays_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_rays_restore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rm_sdf_grid": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(C.c_float), _P(C.c_float), C.c_int,
                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_sdf_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), C.c_float, C.c_int, C.c_int,

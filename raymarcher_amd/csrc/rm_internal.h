@@ -42,7 +42,7 @@ int lock_current_device(std::unique_lock<std::mutex> &lock);
 // Grow-only device scratch memory owned by the library, one buffer per (current device, stream, user tag): calls on
 // different streams of one device may run concurrently on the GPU and therefore never share scratch.  Growing
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
-enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8, kWsBlocks = 9 };
+enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8, kWsBlocks = 9, kWsRayOrder = 10 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
 // The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
 // this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).

@@ -692,6 +692,78 @@ class Renderer:
                                          self._stream()))
         return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
 
+    def order_rays(self, rays, origin_bits=7, dir_bits=8, sorted_rays=True, keys=False):
+        """rm_rays_order: a coherence ordering of rays that come in no order, on the device → `order`, int32 (n,): order[k] is the
+        input index of the ray at sorted position k.  After it, with sorted_rays (the default), the rays in that order, float32
+        (n, 8) — rays[order] in every bit — and, with keys=True, the keys in INPUT order, int64 (n,) holding the uint64 bits: so the
+        default is the pair (order, sorted), and with neither it is `order` alone.  rays as trace_rays takes them.  The key is the
+        Morton code of the origin quantised to origin_bits (0 … 10) per axis over an octahedral map of the direction quantised to
+        dir_bits (0 … 11), within the bounds of the call's rays; the order is the stable sort of the keys, rays with a non-finite
+        component or a zero direction last.  tMax is not read.  Fewer bits are fewer sort passes (8 key bits each) and a coarser
+        grouping: the defaults 7 and 8 (five passes) were as fast end to end as the finest key, 10 and 11 (seven passes), or
+        faster, on seven of the eight tables of profiles/ray_order.md and 2 % slower on one; rays that all start at ONE point,
+        and a camera's rays (whose origins on the near plane repeat what the directions say), do best with origin_bits=0 (three
+        passes).  The definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        order = t.empty((n,), dtype=t.int32, device=self.device)
+        srt = t.empty((n, 8), dtype=t.float32, device=self.device) if sorted_rays else None
+        ks = t.empty((n,), dtype=t.int64, device=self.device) if keys else None
+        check(lib().rm_rays_order(C.c_void_p(rays.data_ptr()), n, origin_bits, dir_bits, C.c_void_p(order.data_ptr()),
+                                  C.c_void_p(srt.data_ptr()) if sorted_rays else None, C.c_void_p(ks.data_ptr()) if keys else None,
+                                  self._stream()))
+        extra = ([srt] if sorted_rays else []) + ([ks] if keys else [])
+        return (order, *extra) if extra else order
+
+    def restore_order(self, rows, order, out=None):
+        """rm_rays_restore: results computed in sorted order back in the caller's order → out[order[k]] = rows[k], a tensor of
+        rows' shape and dtype (`out`, if given; it may not be `rows`).  rows: a contiguous (n, 4) or (n, 8) tensor of a 4-byte dtype
+        on this device — colours, RmRayHit or RmSurfacePoint rows; order: order_rays' int32 (n,).  An entry of `order` outside
+        [0, n) is skipped; with a fresh `out` such a row is left uninitialised."""
+        t = self.torch
+        ok = t.is_tensor(rows) and rows.dim() == 2 and rows.shape[1] in (4, 8) and rows.element_size() == 4 and rows.is_contiguous() and \
+            rows.device == self.device
+        if not ok:
+            raise ValueError(f"rows must be a contiguous (n, 4) or (n, 8) tensor of a 4-byte dtype on {self.device}")
+        n = rows.shape[0]
+        if not t.is_tensor(order) or tuple(order.shape) != (n,) or order.dtype != t.int32 or not order.is_contiguous() or order.device != self.device:
+            raise ValueError(f"order must be a contiguous int32 tensor of shape ({n},) on {self.device}")
+        out = self._out(out, rows.shape, rows.dtype)
+        check(lib().rm_rays_restore(C.c_void_p(rows.data_ptr()), C.c_void_p(order.data_ptr()), n, 4 * rows.shape[1],
+                                    C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def trace_rays_sorted(self, tables, settings, rays, mode="closest", normals=True, image_width=None, origin_bits=7, dir_bits=8):
+        """trace_rays for rays in no order: order_rays, the trace on the sorted rays, restore_order → trace_rays' 4-tuple (normal, t,
+        position, object_id) in the CALLER's order, the same bits trace_rays gives (a ray's result does not depend on which rays
+        share its call), for the price of the sort instead of the price of incoherent waves.  With image_width the trace is
+        trace_rays_layers (terrain and sea; mode "closest" only)."""
+        t = self.torch
+        if image_width is not None and mode != "closest":
+            raise ValueError("with image_width (trace_rays_layers) the mode is 'closest'")
+        order, srt = self.order_rays(rays, origin_bits, dir_bits)
+        hits = t.empty((srt.shape[0], 8), dtype=t.float32, device=self.device)
+        if image_width is None:
+            self.trace_rays(tables, settings, srt, mode=mode, normals=normals, out=hits)
+        else:
+            self.trace_rays_layers(tables, settings, srt, image_width, normals=normals, out=hits)
+        hits = self.restore_order(hits, order)
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def shade_rays_sorted(self, tables, settings, rays, far=None, bright=False, image_width=None, origin_bits=7, dir_bits=8):
+        """shade_rays for rays in no order: order_rays, the shading of the sorted rays, restore_order → float32 (n, 4), or the pair
+        (colour, bright) with bright=True, in the CALLER's order and the same bits shade_rays gives.  With image_width the shading
+        is shade_rays_layers (terrain, sea and clouds)."""
+        order, srt = self.order_rays(rays, origin_bits, dir_bits)
+        if image_width is None:
+            got = self.shade_rays(tables, settings, srt, far=far, bright=bright)
+        else:
+            got = self.shade_rays_layers(tables, settings, srt, image_width, far=far, bright=bright)
+        if bright:
+            return self.restore_order(got[0], order), self.restore_order(got[1], order)
+        return self.restore_order(got, order)
+
     def render_panorama_layers(self, tables, settings, W, H, position, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), far=None):
         """render_panorama through shade_rays_layers with image_width = W: a W×H equirectangular panorama with terrain, sea and
         clouds → float32 (H, W, 4), row 0 = bottom."""

@@ -1,0 +1,142 @@
+"""rm_rays_order and rm_rays_restore without a GPU: the header declares them and the library exports them under the unchanged ABI
+version, the Python layer has its methods with their defaults, and every refusal that is made before the first HIP call returns its
+status — with pointers that would fault if read — in the order the header states."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+
+from raymarcher_amd import abi, lib
+from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
+INVALID = abi.RM_ERR_INVALID_ARGUMENT
+FAKE = C.c_void_p(0x10000)  # aligned, never dereferenced: every call that gets it fails its checks first
+
+
+def _params(name):
+    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
+    assert m, f"include/raymarcher_amd.h does not declare {name}"
+    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+
+
+def test_header_declares_and_library_exports_both_symbols():
+    assert _params("rm_rays_order") == ["const RmRay *d_rays", "int numRays", "int originBits", "int dirBits", "int32_t *d_order",
+                                        "RmRay *d_sorted", "uint64_t *d_keys", "void *stream"]
+    assert _params("rm_rays_restore") == ["const void *d_rows", "const int32_t *d_order", "int numRows", "int rowBytes", "void *d_out",
+                                          "void *stream"]
+    lib()
+    L = C.CDLL(LIB_PATH)
+    for name, n in (("rm_rays_order", 8), ("rm_rays_restore", 6)):
+        assert hasattr(L, name), f"the library does not export {name}"
+        assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int and len(SIGNATURES[name][1]) == n
+
+
+def test_abi_version_stays_and_the_header_carries_the_definition():
+    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
+    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    assert re.search(r"#define\s+RM_RAYS_ORDER_TILE\s+2048\b", HEADER) and abi.RM_RAYS_ORDER_TILE == 2048
+    assert (abi.RM_RAYS_MAX_ORIGIN_BITS, abi.RM_RAYS_MAX_DIR_BITS) == (10, 11)
+    words = {"rm_rays_order": ("s = (|dx| + |dy|) + |dz|", "sgn being −1 where the sign bit is set", "tMax and `reserved` are NOT read",
+                               "changes no key", "a NaN t (inf / inf) gives 0", "x the lowest bit of each origin triple",
+                               "1 << (3·originBits + 2·dirBits)", "STABLE ascending sort", "keys in INPUT order", "before any HIP call",
+                               "No kernel waits for another workgroup", "24 B per ray", "rm_set_workspace_limit",
+                               "rm_debug_last_path() and rm_debug_last_split() keep their values"),
+             "rm_rays_restore": ("d_out[d_order[k]] = d_rows[k]", "is skipped", "rowBytes other than 16 or 32", "d_out == d_rows",
+                                 "before any HIP call")}
+    for name, ws in words.items():
+        m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*(?:#define[^\n]*\n)*int " + name + r"\b", HEADER, flags=re.S)
+        assert m, f"no comment in front of {name}"
+        text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
+        for w in ws:
+            assert w in text, f"the comment of {name} lacks: {w}"
+
+
+def test_python_signatures_and_defaults():
+    from raymarcher_amd.render import Renderer
+    sig = lambda f: list(inspect.signature(f).parameters)  # noqa: E731
+    dflt = lambda f: {k: p.default for k, p in inspect.signature(f).parameters.items() if p.default is not inspect.Parameter.empty}  # noqa: E731
+    assert sig(Renderer.order_rays) == ["self", "rays", "origin_bits", "dir_bits", "sorted_rays", "keys"]
+    assert dflt(Renderer.order_rays) == {"origin_bits": 7, "dir_bits": 8, "sorted_rays": True, "keys": False}
+    assert sig(Renderer.restore_order) == ["self", "rows", "order", "out"] and dflt(Renderer.restore_order) == {"out": None}
+    assert sig(Renderer.trace_rays_sorted) == ["self", "tables", "settings", "rays", "mode", "normals", "image_width", "origin_bits", "dir_bits"]
+    assert dflt(Renderer.trace_rays_sorted) == {"mode": "closest", "normals": True, "image_width": None, "origin_bits": 7, "dir_bits": 8}
+    assert sig(Renderer.shade_rays_sorted) == ["self", "tables", "settings", "rays", "far", "bright", "image_width", "origin_bits", "dir_bits"]
+    assert dflt(Renderer.shade_rays_sorted) == {"far": None, "bright": False, "image_width": None, "origin_bits": 7, "dir_bits": 8}
+    # and the entries they are built on keep theirs
+    assert sig(Renderer.trace_rays) == ["self", "tables", "settings", "rays", "mode", "normals", "out"]
+    assert sig(Renderer.shade_rays) == ["self", "tables", "settings", "rays", "far", "bright", "out", "out_bright"]
+
+
+def refused(status, text):
+    msg = lib().rm_last_error().decode()
+    return status == INVALID and text in msg
+
+
+def order(rays=FAKE, n=100, ob=10, db=11, out=FAKE, srt=C.c_void_p(0x20000), keys=C.c_void_p(0x30000)):
+    return lib().rm_rays_order(rays, n, ob, db, out, srt, keys, None)
+
+
+def restore(rows=FAKE, order_=C.c_void_p(0x20000), n=100, row_bytes=32, out=C.c_void_p(0x30000)):
+    return lib().rm_rays_restore(rows, order_, n, row_bytes, out, None)
+
+
+def test_order_refusals_in_order():
+    for n in (-1, -2 ** 31):
+        assert refused(order(n=n), "negative numRays"), n
+        assert refused(order(n=n, ob=11, rays=None), "negative numRays"), n           # numRays comes before the bits
+    for ob, db in ((-1, 0), (11, 0), (0, -1), (0, 12), (2 ** 31 - 1, 5), (5, -2 ** 31)):
+        assert refused(order(ob=ob, db=db), "originBits must be 0 … 10 and dirBits 0 … 11"), (ob, db)
+        assert refused(order(ob=ob, db=db, n=0), "originBits"), (ob, db)               # the bits before the empty call
+        assert refused(order(ob=ob, db=db, rays=None), "originBits"), (ob, db)         # and before the pointers
+    for ob, db in ((0, 0), (10, 11), (0, 11), (10, 0)):                                # every pair in range gets as far as the pointers
+        assert refused(order(ob=ob, db=db, rays=None), "null d_rays or d_order"), (ob, db)
+    assert refused(order(rays=None), "null d_rays or d_order")
+    assert refused(order(out=None), "null d_rays or d_order")
+    assert refused(order(out=None, rays=C.c_void_p(0x10008)), "null d_rays or d_order")  # null before misaligned
+    for kw in (dict(rays=C.c_void_p(0x10008)), dict(rays=C.c_void_p(0x10004)), dict(srt=C.c_void_p(0x20008)), dict(keys=C.c_void_p(0x30004)),
+               dict(out=C.c_void_p(0x10002)), dict(out=C.c_void_p(0x10001))):
+        assert refused(order(**kw), "misaligned"), kw
+    assert refused(order(srt=FAKE), "d_sorted must not be d_rays")
+    assert refused(order(srt=FAKE, keys=C.c_void_p(0x30004)), "misaligned")            # alignment before the alias
+    # the optional outputs may be null, an 8-byte aligned d_keys and a 4-byte aligned d_order are in order: each of these gets
+    # as far as the device-memory check of an array that is host memory
+    host = np.zeros(100 * 8 + 4, dtype=np.float32)
+    base = host.ctypes.data + (-host.ctypes.data) % 16
+    hp = C.c_void_p(base)
+    assert refused(order(rays=hp, srt=None, keys=None), "d_rays is not device-accessible")
+    assert refused(order(rays=hp, srt=None, keys=C.c_void_p(0x30008), out=C.c_void_p(0x10004)), "d_rays is not device-accessible")
+
+
+def test_restore_refusals_in_order():
+    for n in (-1, -2 ** 31):
+        assert refused(restore(n=n), "negative numRows"), n
+        assert refused(restore(n=n, row_bytes=8), "negative numRows"), n
+    for rb in (0, 4, 8, 12, 24, 48, 64, -16, 2 ** 31 - 1):
+        assert refused(restore(row_bytes=rb), "rowBytes must be 16 or 32"), rb
+        assert refused(restore(row_bytes=rb, n=0), "rowBytes"), rb
+        assert refused(restore(row_bytes=rb, rows=None), "rowBytes"), rb
+    for kw in (dict(rows=None), dict(order_=None), dict(out=None)):
+        assert refused(restore(**kw), "null d_rows, d_order or d_out"), kw
+        assert refused(restore(row_bytes=16, **kw), "null d_rows, d_order or d_out"), kw
+    assert refused(restore(rows=None, out=C.c_void_p(0x30008)), "null d_rows")
+    for kw in (dict(rows=C.c_void_p(0x10008)), dict(out=C.c_void_p(0x30004)), dict(order_=C.c_void_p(0x20002))):
+        assert refused(restore(**kw), "misaligned"), kw
+    assert refused(restore(out=FAKE), "d_out must not be d_rows")
+    assert refused(restore(out=FAKE, order_=C.c_void_p(0x20001)), "misaligned")
+    host = np.zeros(100 * 8 + 4, dtype=np.float32)
+    hp = C.c_void_p(host.ctypes.data + (-host.ctypes.data) % 16)
+    assert refused(restore(rows=hp), "d_rows is not device-accessible")
+    assert refused(restore(rows=hp, order_=C.c_void_p(0x20004), row_bytes=16), "d_rows is not device-accessible")
+
+
+def test_empty_calls_read_and_write_nothing():
+    assert order(n=0) == abi.RM_OK
+    assert order(n=0, rays=None, out=None, srt=None, keys=None) == abi.RM_OK
+    assert order(n=0, rays=C.c_void_p(1), out=C.c_void_p(3), srt=C.c_void_p(1), ob=0, db=0) == abi.RM_OK
+    assert restore(n=0) == abi.RM_OK and restore(n=0, row_bytes=16, rows=None, order_=None, out=None) == abi.RM_OK
+    assert restore(n=0, out=FAKE) == abi.RM_OK
