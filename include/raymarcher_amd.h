@@ -784,6 +784,95 @@ int rm_sdf_mesh_blocks(const float *d_dist, const int32_t *d_objectId /* may be 
                        int32_t *d_quads /* int4 each */, uint32_t *d_counts /* 3 words */, void *stream);
 
 /*
+ * Lattice queries — rm_sdf_sample, rm_sdf_sample_blocks, rm_sdf_trace, rm_sdf_trace_blocks: READ a baked lattice back at arbitrary
+ * points and MARCH rays through it (no reference counterpart).  For what is asked over and over of one static scene: particle
+ * collision (distance and gradient at many points per tick), line of sight, picking, camera collision, a caller's own ambient
+ * occlusion or shadow rays.  A march step costs eight loads and seven lerps instead of an evaluation of the scene.  d_dist and
+ * d_objectId (may be NULL) are a lattice in rm_sdf_grid's layout (x fastest) or in rm_sdf_grid_blocks' (729 values per list entry,
+ * void entries skipped, of equal entries the first counts), from there or from anywhere else.  d_points: numPoints float4 (w is not
+ * read); d_rays: numRays RmRay; d_samples: numPoints RmFieldSample; d_hits: numRays RmRayHit.  origin and step are host memory,
+ * copied before return.  Asynchronous on `stream`.
+ * Definition, bit for bit.  Every operation is one binary32 operation, never fused; division and square root are correctly rounded.
+ * min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b, clamp(x, lo, hi) = min(max(x, lo), hi) with max(x, lo) = x > lo ? x : lo: a
+ * NaN clamps to lo.
+ * Lattice coordinates.  The extent per axis is N_a = n_a − 1 (dense) or 8·m_a (blocks).  A point has u_a = (p_a − origin_a) / step_a;
+ * a ray has uo_a = (ro_a − origin_a) / step_a, ud_a = rd_a / step_a and u(t)_a = uo_a + ud_a · t.
+ * Cell sample — of cell (i, j, k) with its eight values v[c], c = cx + 2·cy + 4·cz as in rm_sdf_mesh, at u: f_a = u_a − (float)cell_a;
+ * lerp(a, b, w) = a + w·(b − a).  value: lerp along x on the four x-edges (v0,v1) (v2,v3) (v4,v5) (v6,v7), then along y on the
+ * pairs (0,1) (2,3) of those results, then along z.  gradient: that interpolant's derivative in world units,
+ *   gx = lerp(lerp(v1−v0, v3−v2, fy), lerp(v5−v4, v7−v6, fy), fz) / step_x
+ *   gy = lerp(lerp(v2−v0, v3−v1, fx), lerp(v6−v4, v7−v5, fx), fz) / step_y
+ *   gz = lerp(lerp(v4−v0, v5−v1, fx), lerp(v6−v2, v7−v3, fx), fy) / step_z
+ * object id: with d_objectId the id stored at the corner (fx >= 0.5, fy >= 0.5, fz >= 0.5); without it −1 for a sample and 0 for a ray
+ * hit.  NaN and infinite lattice values get no special case: the arithmetic is as written (WHICH NaN an operation returns, its sign
+ * and payload, is the hardware's; that a word is a NaN is defined).  A cell needs only its own eight values, which in the block
+ * layout all live in one entry's slot: no neighbour is looked up.
+ * rm_sdf_sample.  Invalid point: a non-finite component; it stores objectId = RM_RAY_INVALID and zeros.  Inside iff 0 <= u_a <= N_a on
+ * every axis, decided on the floats (a NaN or infinite u is outside); an outside point stores objectId = RM_FIELD_OUTSIDE and zeros.
+ * An inside point has cell_a = min((int)floor(u_a), N_a − 1) and stores the cell sample: gradient, value, cell, objectId.
+ * rm_sdf_sample_blocks.  The same, and: block b_a = min(cell_a >> 3, m_a − 1); where no entry that counts names b it stores objectId =
+ * RM_FIELD_UNLISTED with `cell` filled and value and gradient zeros; otherwise it reads local cell cell − 8·b of the slot of the first
+ * entry that names b.  Wherever the block is listed the record is rm_sdf_sample's on the dense lattice in every bit.
+ * rm_sdf_trace_blocks.
+ * 1. Invalid ray: rm_trace_rays' rules (a non-finite component of origin or dir, dir all zeros, tMax NaN or negative), or a component
+ *    of uo or ud that is not finite, or ud all zeros (a dir that underflows in lattice units).  It stores objectId = RM_RAY_INVALID,
+ *    t = 0 and zeros.
+ * 2. Box entry by slabs on [0, N_a].  near = −inf, far = +inf; for each axis with ud_a != 0: t1 = (0 − uo_a) / ud_a, t2 = ((float)N_a −
+ *    uo_a) / ud_a, near = max(near, min(t1, t2)), far = min(far, max(t1, t2)); an axis with ud_a == 0 makes the ray miss if uo_a < 0 or
+ *    uo_a > N_a.  t = max(near, 0) (a near of −0 or below gives +0), tEnd = min(tMax, far).  The ray misses unless t <= tEnd.
+ * 3. forced = false; then maxSteps times at most: miss if t > tEnd.  u_a = uo_a + ud_a · t.  If not forced: u_a = clamp(u_a, 0, N_a)
+ *    and b_a = min((int)floor(u_a) >> 3, m_a − 1).  If forced: b stays and u_a = clamp(u_a, 8·b_a, 8·b_a + 8).
+ *    Listed block: cell_a = min((int)floor(u_a), 8·b_a + 7); the cell's value at u; forced = false; HIT iff value < iso (rm_sdf_mesh's
+ *    inside: a NaN is no hit); otherwise t = t + value (the renderer's march step: t is in units of |dir|).
+ *    Unlisted block: skip to its exit.  For each axis with ud_a != 0: F_a = (float)(8·(b_a + (ud_a > 0 ? 1 : 0))), ta = (F_a − uo_a) /
+ *    ud_a.  The exit axis is the one with the smallest ta, the first in x, y, z order on a tie; b[axis] += (ud_axis > 0 ? 1 : −1), an
+ *    exact integer step; miss if that leaves [0, m_axis); t = max(ta, t) (ta > t ? ta : t); forced = true.
+ *    Every skip changes an integer block coordinate, so a ray cannot stall on a rounded boundary; a skip costs one of the maxSteps
+ *    iterations.
+ * 4. Hit: t as it is; position_a = ro_a + rd_a · t, unfused; normal = g / sqrt((gx·gx + gy·gy) + gz·gz) with g the cell sample's
+ *    gradient, zeros where that length is 0 or not finite; objectId as in the cell sample.  With RM_TRACE_NO_NORMAL normal and position
+ *    are zeros; objectId and t are the same bits.
+ * 5. Miss, exhausted steps included: rm_trace_rays' miss, objectId = −1, t = tMax as given, zeros.
+ * rm_sdf_trace is the same loop on ONE region in which everything is listed: the clamp is to [0, n_a − 1] and cell_a = min((int)floor(
+ * u_a), n_a − 2).  With n = 8·m + 1 and a list of every block the two give equal bits.
+ * The sparse march knows nothing about the inside of unlisted blocks: a ray that starts inside an object in an unlisted block reports
+ * the first listed sample below iso, not t = 0.  With the list of rm_sdf_blocks_select at the same iso a ray that starts outside the
+ * surface meets it where the dense march does.  The result of a point or ray does not depend on which others share its call.
+ * In this order, and all but the last before any HIP call, RM_ERR_INVALID_ARGUMENT: a negative numPoints / numRays; null origin or
+ * step, an origin component that is not finite, a step component that is not finite or not greater than 0; dense: a dimension above
+ * RM_MAX_LATTICE_DIM or more than INT_MAX points (rm_sdf_mesh's rules) or a dimension below 2 (these entries need a cell); blocks: a
+ * block dimension below 1 or above RM_MAX_LATTICE_BLOCKS, then numBlocks below 0 or above RM_MAX_BLOCK_LIST; the marches: iso not
+ * finite, maxSteps outside 0 … RM_MAX_FIELD_STEPS, mode bits other than RM_TRACE_NO_NORMAL.  Then a count of 0: RM_OK, nothing read or
+ * written.  RM_ERR_INVALID_ARGUMENT: a null d_points / d_rays or d_samples / d_hits, a null d_dist or d_blocks with numBlocks above 0; a
+ * misaligned pointer (16 bytes for points, rays, samples and hits, 4 for the rest); an array that is not device memory.  numBlocks =
+ * 0 with points or rays is valid: every point in the box is RM_FIELD_UNLISTED, every valid ray misses.
+ * Schedule: ONE launch, one lane per point or ray, 256-lane workgroups; the block entries build the block map of the list first (4 B
+ * per block of the virtual lattice in the workspace of rm_sdf_blocks_select: rm_set_workspace_limit and rm_release_workspaces apply;
+ * it is rebuilt on every call).  A marching lane keeps the slot of its current block while the block does not change.  No scene is
+ * staged and no slot of the ring of scene blocks is used.  Not render launches: rm_debug_last_path() keeps its value and
+ * rm_set_timing does not time them.  Rays that share a wave cost what the longest of them costs: keep neighbours together
+ * (rm_rays_order).
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmFieldSample { float gradient[3]; float value; int32_t cell[3]; int32_t objectId; } RmFieldSample; /* 32 bytes */
+#define RM_FIELD_OUTSIDE (-5)  /* RmFieldSample.objectId of a point outside the lattice's box */
+#define RM_FIELD_UNLISTED (-6) /* … of a point in a block that no entry of the list names */
+#define RM_MAX_FIELD_STEPS 65536
+int rm_sdf_sample(const float *d_points /* float4 each, w not read */, int numPoints, const float *d_dist,
+                  const int32_t *d_objectId /* may be NULL */, int nx, int ny, int nz, const float origin[3], const float step[3],
+                  RmFieldSample *d_samples, void *stream);
+int rm_sdf_sample_blocks(const float *d_points /* float4 each, w not read */, int numPoints, const float *d_dist,
+                         const int32_t *d_objectId /* may be NULL */, const int32_t *d_blocks /* int4 each */, int numBlocks, int mx,
+                         int my, int mz, const float origin[3], const float step[3], RmFieldSample *d_samples, void *stream);
+int rm_sdf_trace(const RmRay *d_rays, int numRays, const float *d_dist, const int32_t *d_objectId /* may be NULL */, int nx, int ny,
+                 int nz, const float origin[3], const float step[3], float iso, int maxSteps,
+                 unsigned mode /* 0 or RM_TRACE_NO_NORMAL */, RmRayHit *d_hits, void *stream);
+int rm_sdf_trace_blocks(const RmRay *d_rays, int numRays, const float *d_dist, const int32_t *d_objectId /* may be NULL */,
+                        const int32_t *d_blocks /* int4 each */, int numBlocks, int mx, int my, int mz, const float origin[3],
+                        const float step[3], float iso, int maxSteps, unsigned mode /* 0 or RM_TRACE_NO_NORMAL */, RmRayHit *d_hits,
+                        void *stream);
+
+/*
  * rm_shade_points — what the renderer thinks of POINTS the caller already has: the scene's distance and object at each point, its
  * normal, its ambient occlusion and its shaded colour, with the point optionally projected onto the iso-surface first (no reference
  * counterpart: the shader reaches a surface point only at the end of a ray of its own).  The points counterpart of rm_trace_rays /

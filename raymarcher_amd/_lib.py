@@ -67,6 +67,14 @@ SIGNATURES = {
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_sdf_mesh_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float),
                                      C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_sdf_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float),
+                                C.c_void_p, C.c_void_p]),
+    "rm_sdf_sample_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_void_p]),
+    "rm_sdf_trace": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float),
+                               C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
+    "rm_sdf_trace_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      _P(C.c_float), _P(C.c_float), C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "rm_points_settings_default": (None, [_P(abi.RmPointsSettings)]),
     "rm_shade_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(abi.RmPointsSettings), _P(abi.RmObject), C.c_int, _P(abi.RmLight),
                                   C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p,

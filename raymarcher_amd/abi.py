@@ -140,6 +140,12 @@ class RmPointsSettings(C.Structure):
     _fields_ = [("far", f32), ("iso", f32), ("maxMove", f32), ("projectSteps", i32)]
 
 
+class RmFieldSample(C.Structure):
+    _fields_ = [("gradient", f32 * 3), ("value", f32), ("cell", i32 * 3), ("objectId", i32)]
+
+
+RM_FIELD_OUTSIDE, RM_FIELD_UNLISTED = -5, -6  # RmFieldSample.objectId of a point outside the lattice's box / in an unlisted block
+RM_MAX_FIELD_STEPS = 65536  # march steps of one rm_sdf_trace / rm_sdf_trace_blocks call
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

@@ -973,6 +973,105 @@ class Renderer:
         """bake_mesh on top of scene_mesh_sparse: the same outputs, resolution up to 4097."""
         return self._bake(tables, settings, self._scene_mesh_sparse(tables, settings, resolution, iso, bounds), iso, project, ao, colour)
 
+    # ---- lattice queries: a baked lattice read back at points and marched by rays (include/raymarcher_amd.h) ----
+    def _lattice(self, grid, ids, shape_text, shape_ok):
+        t = self.torch
+        if (not t.is_tensor(grid) or not shape_ok(grid) or grid.dtype != t.float32 or not grid.is_contiguous() or grid.device != self.device):
+            raise ValueError(f"grid must be a contiguous float32 tensor of shape {shape_text} on {self.device}")
+        if ids is not None and (not t.is_tensor(ids) or tuple(ids.shape) != tuple(grid.shape) or ids.dtype != t.int32
+                                or not ids.is_contiguous() or ids.device != self.device):
+            raise ValueError(f"ids must be a contiguous int32 tensor of shape {tuple(grid.shape)} on {self.device}")
+        return C.c_void_p(grid.data_ptr()) if grid.numel() else None, C.c_void_p(ids.data_ptr()) if ids is not None and ids.numel() else None
+
+    def sample_lattice(self, grid, origin, step, points, ids=None):
+        """rm_sdf_sample: a dense lattice read back at arbitrary points, trilinearly → (gradient, value, cell, object_id): float32 (n,
+        3) in world units, float32 (n), int32 (n, 3) and int32 (n), views of ONE float32 (n, 8) device tensor of RmFieldSample rows.
+        grid: float32 (nz, ny, nx) on this device, from sdf_grid or from anywhere else, every dimension at least 2; ids: its int32
+        object indices or None; points as shade_points takes them.  object_id: the id stored at the nearest corner of the point's
+        cell (−1 without ids), abi.RM_FIELD_OUTSIDE for a point outside the lattice's box, abi.RM_RAY_INVALID for a non-finite
+        point, both with zeros elsewhere.  The definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        gp, ip = self._lattice(grid, ids, "(nz, ny, nx)", lambda g: g.dim() == 3)
+        nz, ny, nx = grid.shape
+        pts = self._points(points, "points")
+        n = pts.shape[0]
+        out = t.empty((n, 8), dtype=t.float32, device=self.device)
+        check(lib().rm_sdf_sample(C.c_void_p(pts.data_ptr()) if n else None, n, gp, ip, nx, ny, nz, _vec3(origin, "origin"),
+                                  _vec3(step, "step"), C.c_void_p(out.data_ptr()) if n else None, self._stream()))
+        return out[:, 0:3], out[:, 3], out[:, 4:7].view(t.int32), out[:, 7].view(t.int32)
+
+    def sample_lattice_blocks(self, grid_blocks, block_list, blocks, origin, step, points, ids=None):
+        """rm_sdf_sample_blocks: sample_lattice on a block-sparse lattice → the same 4-tuple.  grid_blocks: float32 (n, 9, 9, 9) from
+        sdf_grid_blocks, block_list its int32 (n, 4) list, blocks = (mx, my, mz), ids: int32 of grid_blocks' shape or None.  A point
+        in a block the list does not name gets object_id abi.RM_FIELD_UNLISTED with its cell and zeros; everywhere else the record
+        is sample_lattice's on the dense lattice in every bit."""
+        t = self.torch
+        mx, my, mz = self._blocks3(blocks)
+        bl = self._block_list(block_list)
+        nb = bl.shape[0]
+        gp, ip = self._lattice(grid_blocks, ids, f"({nb}, 9, 9, 9)", lambda g: tuple(g.shape) == (nb, 9, 9, 9))
+        pts = self._points(points, "points")
+        n = pts.shape[0]
+        out = t.empty((n, 8), dtype=t.float32, device=self.device)
+        check(lib().rm_sdf_sample_blocks(C.c_void_p(pts.data_ptr()) if n else None, n, gp, ip,
+                                         C.c_void_p(bl.data_ptr()) if nb else None, nb, mx, my, mz, _vec3(origin, "origin"),
+                                         _vec3(step, "step"), C.c_void_p(out.data_ptr()) if n else None, self._stream()))
+        return out[:, 0:3], out[:, 3], out[:, 4:7].view(t.int32), out[:, 7].view(t.int32)
+
+    def trace_lattice(self, grid, origin, step, rays, iso=0.001, max_steps=256, ids=None, normals=True, out=None):
+        """rm_sdf_trace: rays marched through a dense lattice instead of the scene → (normal, t, position, object_id) as trace_rays
+        returns them, views of ONE float32 (n, 8) device tensor of RmRayHit rows (`out`, if given).  grid, ids as sample_lattice
+        takes them, rays as trace_rays does.  A ray enters the lattice's box, steps by the interpolated value as the renderer's
+        march steps by the distance, and hits at the first sample below iso: object_id = the id at the nearest corner (0 without
+        ids), normal = the interpolant's normalised gradient; −1: a miss — the box or tMax left, or max_steps (at most
+        abi.RM_MAX_FIELD_STEPS) used up — with t = tMax and zeros; abi.RM_RAY_INVALID as trace_rays has it.  normals=False leaves
+        the point and the normal out (zeros).  The definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        gp, ip = self._lattice(grid, ids, "(nz, ny, nx)", lambda g: g.dim() == 3)
+        nz, ny, nx = grid.shape
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        hits = self._out(out, (n, 8), t.float32)
+        check(lib().rm_sdf_trace(C.c_void_p(rays.data_ptr()) if n else None, n, gp, ip, nx, ny, nz, _vec3(origin, "origin"), _vec3(step, "step"),
+                                 float(iso), int(max_steps), abi.RM_TRACE_CLOSEST if normals else abi.RM_TRACE_NO_NORMAL,
+                                 C.c_void_p(hits.data_ptr()) if n else None, self._stream()))
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def trace_lattice_blocks(self, grid_blocks, block_list, blocks, origin, step, rays, iso=0.001, max_steps=256, ids=None, normals=True,
+                             out=None):
+        """rm_sdf_trace_blocks: trace_lattice through a block-sparse lattice → the same 4-tuple.  grid_blocks, block_list, blocks and
+        ids as sample_lattice_blocks takes them.  A ray skips a block the list does not name in one step, to the face it leaves it
+        through, so the march knows nothing of the inside of unlisted blocks: with scene_field_sparse's list (the blocks the
+        surface passes through) a ray that starts outside the surface meets it where the dense march does; one that starts inside
+        an object in an unlisted block reports the first listed sample below iso, not t = 0.  With every block listed the result
+        is trace_lattice's in every bit."""
+        t = self.torch
+        mx, my, mz = self._blocks3(blocks)
+        bl = self._block_list(block_list)
+        nb = bl.shape[0]
+        gp, ip = self._lattice(grid_blocks, ids, f"({nb}, 9, 9, 9)", lambda g: tuple(g.shape) == (nb, 9, 9, 9))
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        hits = self._out(out, (n, 8), t.float32)
+        check(lib().rm_sdf_trace_blocks(C.c_void_p(rays.data_ptr()) if n else None, n, gp, ip,
+                                        C.c_void_p(bl.data_ptr()) if nb else None, nb, mx, my, mz, _vec3(origin, "origin"), _vec3(step, "step"),
+                                        float(iso), int(max_steps), abi.RM_TRACE_CLOSEST if normals else abi.RM_TRACE_NO_NORMAL,
+                                        C.c_void_p(hits.data_ptr()) if n else None, self._stream()))
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def scene_field_sparse(self, tables, settings, resolution, iso=0.001, bounds=None):
+        """The scene's distance field baked where its surface is, ready for sample_lattice_blocks and trace_lattice_blocks →
+        (grid_blocks, ids, block_list, blocks, origin, step): scene_mesh_sparse's lattice (resolution 4 … 4097, the same step on
+        every axis, returned as a 3-tuple), its active blocks at iso (sdf_active_blocks) and the field and object indices on them
+        (sdf_grid_blocks)."""
+        if int(resolution) > 8 * abi.RM_MAX_LATTICE_BLOCKS + 1:
+            raise ValueError("resolution must be at most 4097")
+        origin, step, dims = self._scene_lattice(tables, resolution, bounds)
+        blocks = tuple((d - 1 + 7) // 8 for d in dims)
+        bl = self.sdf_active_blocks(tables, settings, origin, (step,) * 3, blocks, iso)
+        dist, obj = self.sdf_grid_blocks(tables, settings, origin, (step,) * 3, blocks, bl, ids=True)
+        return dist, obj, bl, blocks, origin, (step,) * 3
+
     def shade_points(self, tables, settings, points, view=None, far=None, colour=True, ao=False, project=0, iso=0.001,
                      max_move=float("inf")):
         """rm_shade_points: what the renderer thinks of points the caller already has, one lane per point in one launch → (normal,
