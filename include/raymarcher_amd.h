@@ -1132,6 +1132,13 @@ int rm_debug_cull_bounds(const RmObject *objs, int numObjects, const RmGlobals *
  * power 8, both Julia seed components zero — whose evaluations skip the object transform, the ·scaleFactor and the Julia
  * select (same bits); 0 otherwise (another table, or the general Mandelbulb kernel); -1 on a null pointer.  No GPU needed. */
 int rm_debug_bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g);
+/* Tests: the per-light constants the launcher stages for the single-Mandelbulb kernels' shadow pool, computed on the host exactly
+ * as it stages them: out[8·numLights], per light { L xyz, pd xyz, a, 0 } with L = normalize(−dir) (v · (1 / sqrt(dot(v, v))),
+ * dot = fma(z, z, fma(y, y, x·x))), pd = the 3×3 part of objs[0].invModel times L (fma(M[8 + r], L.z, fma(M[4 + r], L.y,
+ * M[r]·L.x))) and a = dot(pd, pd): the bits the kernels computed per ray before.  Zeros for a light that is not directional;
+ * pd and a are zero for an empty object table.  RM_ERR_INVALID_ARGUMENT: a null pointer with a count above 0, null out, a count
+ * below 0 or above RM_MAX_OBJECTS / RM_MAX_LIGHTS.  No GPU needed. */
+int rm_debug_light_prep(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, float *out);
 /* Tests: the kernels' cheap exact forms against the IEEE operations for every one of the 2^32 inputs, on the current device
  * (≈2 s).  mismatches5[0]: the reciprocal (v_rcp_f32 + one Newton step inside 2^-126 <= |y| < 2^126, the IEEE expansion
  * outside) vs 1.0f / y; [1]: the bare fast form over its range; [2]: the square root (v_sqrt_f32 + residual selection, the
@@ -1231,6 +1238,18 @@ int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGloba
  * wave may be partial).  n == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT: n < 0, a null pointer or one that is not
  * device memory. */
 int rm_probe_bump(const float *d_pts, float *d_out, int n, void *stream);
+/* The cull end of a hard-shadow ray as the single-Mandelbulb kernels' shadow pool computes it when it hands the ray out (tests
+ * only): for n shadow origins d_pts[3n] and directional light `light` of the table, with march end `far`,
+ * d_out[8n] = (end, own as 0 / 1) from the light's staged constants (rm_debug_light_prep) and the per-pixel part alone, then
+ * (end, own) from the whole computation with the direction normalised on the device, then that direction xyz, then 0.  The two
+ * pairs must be equal bit for bit, and the direction equal to the staged one.  bulbClass: 1 the general form, 2 the plain form
+ * (a table rm_debug_bulb_plain accepts), which takes the origin for its object-space image unless an origin of the wave is not
+ * finite.  Point i runs on lane i % 64 of wave i / 64 (that choice sees exactly those 64 origins; the last wave may be partial).
+ * n == 0: RM_OK, nothing written.  RM_ERR_INVALID_ARGUMENT before any HIP call: a table that is not one Mandelbulb, a plain
+ * request for a table that is not plain, `light` out of range or not directional, n < 0, a null pointer or one that is not device
+ * memory; rm_render's checks of the tables apply. */
+int rm_probe_pool_cull(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
+                       const RmSettings *s, int bulbClass, int light, float far, const float *d_pts, float *d_out, int n, void *stream);
 
 /* ---- host side kept from the reference: scenefile loader, camera, Settings -------------------- */
 /* Settings surface — src/settings.h:19-55 (render-relevant fields only). */

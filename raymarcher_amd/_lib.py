@@ -123,6 +123,7 @@ SIGNATURES = {
     "rm_debug_ray_planes": (C.c_int, [_P(abi.RmCamera), _P(C.c_float)]),
     "rm_debug_cull_bounds": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmGlobals), _P(C.c_float)]),
     "rm_debug_bulb_plain": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmGlobals)]),
+    "rm_debug_light_prep": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmLight), C.c_int, _P(C.c_float)]),
     "rm_debug_check_math": (C.c_int, [_P(C.c_ulonglong)]),
     "rm_frame_to_rgba8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rm_post_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(abi.RmPostSettings), C.c_void_p]),
@@ -136,6 +137,8 @@ SIGNATURES = {
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p]),
     "rm_probe_bump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rm_probe_pool_cull": (C.c_int, [_P(abi.RmObject), C.c_int, _P(abi.RmLight), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), C.c_int,
+                                     C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rm_host_settings_default": (None, [_P(abi.RmHostSettings)]),
     "rm_camera_build": (C.c_int, [_P(abi.RmCameraData), C.c_int, C.c_int, C.c_float, C.c_float, _P(C.c_float),
                                   _P(C.c_float), _P(abi.RmCamera)]),

@@ -589,6 +589,55 @@ RM_DEV float bulbCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end) {
   bool own;
   return bulbCullEnd(sb, ro, rd, end, own);
 }
+// bulbCullEnd in the parts the shadow pool needs (shadowPool's PREP form), the same operations on the same operands:
+//  * what the launch decides (wave-uniform), once in front of the loop that hands rays out: bulbCullSetup;
+//  * what the light decides — pd = invModel·rd (the 3×3 part) and a = dot(pd, pd) — comes from SceneBlock::lightPrep;
+//  * what the pixel decides, per ray: bulbCullEndPrepared.
+// PLAIN (kBulbPlain) takes the origin for its object-space image.  The argument is sdSceneImpl's: invModel is 1 on the diagonal
+// and a zero of either sign elsewhere, the translation included (bulb_plain in rm_frame.cpp), so for a finite ro every product
+// of the transform but the diagonal one is a zero and every sum exact: po is ro, except that a zero coordinate may come out as
+// the other zero.  The cull reads po only through
+//  * c = dot(po, po) − R²: squares, the same for both zeros;
+//  * b = dot(po, pd): a zero factor gives a zero term, and a zero term changes a sum only if the sum is zero, in its sign — b is
+//    the same value, or the other zero;
+//  * b >= 0 and disc = fma(b, b, −(a·c)): alike for both zeros (b·b is +0);
+//  * sqrt(max(disc, 0)) − b: the root is +0 or positive (the contract's max takes +0 over −0), and s − (±0) is s, +0 for s = +0
+//    either way.
+// So t_exit, `own` and the end returned are the same bits.  A non-finite coordinate is another matter: the transform turns it into
+// NaN in all three (±0·inf), which ro itself does not.  dot(ro, ro) < inf — the value c needs anyway — implies that all three are
+// finite; a wave with a lane that fails it takes the transform, for all lanes (either form is exact for the finite ones).
+struct BulbCull { bool ok; float R2; };
+RM_DEV BulbCull bulbCullSetup(const SceneBlock *sb) {
+  const RmObject &o = sb->objs[0];
+  const float jx = sb->g.juliaSeed[0], jy = sb->g.juliaSeed[1];
+  const float seed2 = fma(jx, jx, jy * jy);
+  BulbCull cu;
+  cu.ok = (sb->g.power == 8.0f) && (o.scaleFactor >= 0.01f) && (seed2 <= 4.0f);
+  const bool tight = (o.scaleFactor >= 0.05f) && (seed2 <= 1.2996f);
+  cu.R2 = tight ? 1.3225f : 4.41f;
+  return cu;
+}
+template <bool PLAIN>
+RM_DEV float bulbCullEndPrepared(const SceneBlock *sb, const BulbCull &cu, V3 ro, V3 pd, float a, float end, bool &own) {
+  own = false;
+  if (!cu.ok) return end;  // wave-uniform
+  V3 po = ro;
+  float pp = dot(ro, ro);
+  if (!PLAIN || __ballot(!(pp < __builtin_inff())) != 0ull) {
+    const float *M = sb->objs[0].invModel;
+    po = v3(fma(M[8], ro.z, fma(M[4], ro.y, fma(M[0], ro.x, M[12]))), fma(M[9], ro.z, fma(M[5], ro.y, fma(M[1], ro.x, M[13]))),
+            fma(M[10], ro.z, fma(M[6], ro.y, fma(M[2], ro.x, M[14]))));
+    pp = dot(po, po);
+  }
+  const float b = dot(po, pd), c = pp - cu.R2;
+  const float disc = fma(b, b, -(a * c));
+  float tExit = (sqrt_fast_(max_(disc, 0.0f)) - b) / a;
+  tExit = fma(tExit, 1.0001f, 1.0e-3f);
+  if (c > 0.0f && (b >= 0.0f || disc < 0.0f)) tExit = -1.0f;  // outside and never entering
+  if (!(a > 0.0f)) return end;
+  own = (tExit <= end) && (c > 0.0f || tExit > 0.0f);  // false for a NaN tExit
+  return min_(end, tExit);  // a NaN tExit leaves `end` untouched
+}
 // The same idea for any scene: the launcher bounds every object by a world-space ball (exact SDFs are >= the distance
 // to their object's ball; the bound includes a margin δ with minScale·δ >> the hit threshold), and a march whose miss
 // distance is unused ends where its ray leaves the ball around all of them.  Soft-shadow rays use a larger ball, beyond
@@ -1008,6 +1057,11 @@ RM_DEV LightGeom lightSetup(const RmLight &li, V3 p, float far) {
   }
   return g;
 }
+// lightSetup's L of directional light i (wave-uniform index: scalar loads) as the host prepared it, SceneBlock::lightPrep.
+RM_DEV V3 preparedL(const SceneBlock *sb, int i) {
+  const LightPrep &q = sb->lightPrep[i];
+  return v3(q.L[0], q.L[1], q.L[2]);
+}
 // Shadow-ray origin p + N·SURFACE_DIST·5 (frag:1908).
 RM_DEV V3 shadowOrigin(V3 p, V3 N) {
   return v3(fma(N.x * kSurfaceDist, 5.0f, p.x), fma(N.y * kSurfaceDist, 5.0f, p.y), fma(N.z * kSurfaceDist, 5.0f, p.z));
@@ -1087,12 +1141,14 @@ RM_DEV bool hardDirectionalOnly(const SceneBlock *sb) {
 }
 // getPhong's light sum over hard shadows, given the mask of lights whose shadow ray hit (bit i = light i): the shadow queue's and
 // the shadow pool's (renderPooled).  `total` holds the ambient term.
+// PREP (the pool's callers, whose lights are all directional): L from SceneBlock::lightPrep, what lightSetup's normalize gives.
+template <bool PREP = false>
 RM_DEV V3 hardLightSum(const SceneBlock *sb, const Material &mat, V3 N, V3 p, V3 V, float far, float ks, uint32_t hitMask,
                        V3 total) {
   const int nl = sb->numLights;
   for (int i = 0; i < nl; i++) {
     const RmLight &li = sb->lights[i];
-    const LightGeom g = lightSetup(li, p, far);
+    const LightGeom g = PREP ? LightGeom{preparedL(sb, i), far, 1.0f, 1.0f} : lightSetup(li, p, far);
     V3 cur;
     if (lightTerm(li, g, mat, N, V, ks, ((hitMask >> i) & 1u) ? 0 : -1, 1.0f, false, cur)) total = add(total, cur);
   }
@@ -1200,7 +1256,19 @@ RM_DEV V3 bulbTrapColor(float ty, float tz, float tw) {
 // 16 bits per lane: 5.6 KB per workgroup.
 constexpr int kPoolWaves = 4, kPoolList = 64 * RM_MAX_LIGHTS;
 static_assert(RM_MAX_LIGHTS <= 16, "a pool entry holds the light in 10 bits, a hit mask 16 lights");
-template <int BULB, int COUNT>
+// PREP: a lane that takes a ray reads its light's constants (SceneBlock::lightPrep: L, pd, a) from a copy in LDS instead of
+// loading the light through its per-lane index, normalising its direction and transforming it — all of which depend on the
+// light alone — and computes only the pixel's part of the cull (bulbCullEndPrepared); the launch's part is decided in front of
+// the loop.  The same bits (scene_light_prep in rm_frame.cpp).  The copy is ONE table per workgroup (320 B; one per wave would
+// take the workgroup's LDS past the 6826 B at which 24 one-wave workgroups fit a CU), written by every wave at the start of
+// its call: the waves of a workgroup write the same words, so none of them waits for another.  That holds where all waves of a
+// workgroup read one scene block at a time; the kernels whose waves walk a frame's blocks without a barrier between them
+// (render_anim_kernel, whose blocks have light tables of their own) keep PREP = false, the former hand-out.
+RM_DEV float *poolLightTable() {
+  __shared__ __attribute__((aligned(16))) float s_prep[RM_MAX_LIGHTS * 8];
+  return s_prep;
+}
+template <int BULB, int COUNT, bool PREP = false>
 RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dStart, float far, Counters &cnt) {
   __shared__ uint16_t s_list[kPoolWaves][kPoolList];
   __shared__ uint32_t s_hits[kPoolWaves][32];
@@ -1208,6 +1276,20 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
   uint16_t *list = s_list[wave];
   uint32_t *hitw = s_hits[wave];
   hitw[lane >> 1] = 0u;  // every lane zeroes the word that holds its mask (its pair partner may too)
+  const float *prep = nullptr;
+  BulbCull cu{false, 0.0f};  // wave-uniform
+  if constexpr (PREP) {
+    float *table = poolLightTable();
+    const float *src = reinterpret_cast<const float *>(sb->lightPrep);
+    // the calling lanes share the words among themselves by their rank: a wave of an edge tile has fewer than 64 of them, and
+    // the table must be whole whichever they are (two trips at most for a full wave)
+    const uint64_t act = __ballot(true);
+    const int me = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+    const int na = __popcll(act), nw = min(sb->numLights, (int)RM_MAX_LIGHTS) * 8;
+    for (int i = me; i < nw; i += na) table[i] = src[i];
+    prep = table;
+    cu = bulbCullSetup(sb);
+  }
   // the list, light by light: offset = the earlier lights' rays + this lane's rank among the lanes that march this light
   const int nl = sb->numLights;
   uint32_t n = 0u;  // wave-uniform
@@ -1248,9 +1330,15 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
         cur = (int)(e >> 6);
         own = src;
         o = os;
-        const RmLight &li = sb->lights[cur];  // per-lane index: a vector load, once per ray
-        L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));  // lightSetup's direction of a directional light
-        end = bulbCullEnd(sb, o, L, far, endOwn);
+        if constexpr (PREP) {
+          const float *q = prep + 8 * cur;  // per-lane index into LDS
+          L = v3(q[0], q[1], q[2]);
+          end = bulbCullEndPrepared<BULB == kBulbPlain>(sb, cu, o, v3(q[3], q[4], q[5]), q[6], far, endOwn);
+        } else {
+          const RmLight &li = sb->lights[cur];  // per-lane index: a vector load, once per ray
+          L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));  // lightSetup's direction of a directional light
+          end = bulbCullEnd(sb, o, L, far, endOwn);
+        }
         const bool resume = !(ds < 0.0f);  // after the shared first step (a NaN |d0| resumes too, as march() would go on)
         depth = resume ? ds : 0.0f;
         step = resume ? 1 : 0;
@@ -1302,9 +1390,16 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
 // SHARE: the bump's four noise samples from one lattice (bumpNormalShared) instead of four pnoise calls: the same bits; chosen per
 // kernel by the compiler's register report (shadePixel's SHARE: the kernels that hold several samples' or frames' state live
 // across this function spill more with the eight gradients and keep bumpNormal).
-template <int BULB, int COUNT, bool SHARE>
+// PREP: the lights' normalised directions, and in the pool their object-space images, from SceneBlock::lightPrep instead of
+// once per light and lane in phases (a) and (c) and once per ray in (b): the same bits; see shadowPool for the kernels without it.
+// -DRM_X_PREP_PARTS=1 / 2 (experiments; profiles/pool_handout.md measured the parts alone): the hand-out only / the phases only.
+#ifndef RM_X_PREP_PARTS
+#define RM_X_PREP_PARTS 3
+#endif
+template <int BULB, int COUNT, bool SHARE, bool PREP>
 RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, const MarchRes &res, Hit &info,
                               float maxT, V3 bg, Counters &cnt) {
+  constexpr bool PREP_B = PREP && (RM_X_PREP_PARTS & 1) != 0, PREP_AC = PREP && (RM_X_PREP_PARTS & 2) != 0;
   const bool surf = res.obj != -1;
   const int nl = sb->numLights;
   V3 p = v3(0.0f, 0.0f, 0.0f), N = p, so = p;
@@ -1321,7 +1416,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
     uint32_t need = 0u;
     for (int i = 0; i < nl; i++) {
       const RmLight &li = sb->lights[i];
-      const V3 L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
+      const V3 L = PREP_AC ? preparedL(sb, i) : normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
       shared = shared && (fabs_(L.x) + fabs_(L.y) + fabs_(L.z) <= 2.0f);  // false for a NaN / inf direction
       if (!(dot(N, L) <= 0.005f)) need |= 1u << i;  // a light that N·L drops is not marched (getPhong)
     }
@@ -1336,7 +1431,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
       }
     }
   }
-  const uint32_t hitMask = hits | shadowPool<BULB, COUNT>(sb, so, pend, dStart, maxT, cnt);
+  const uint32_t hitMask = hits | shadowPool<BULB, COUNT, PREP_B>(sb, so, pend, dStart, maxT, cnt);
   RenderOut out;
   if (!surf) {
     out.col = bg;
@@ -1355,7 +1450,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
   const float ka = sb->g.ka, ks = sb->g.ks;
   const V3 total = v3((mat.amb.x * ka) * ao, (mat.amb.y * ka) * ao, (mat.amb.z * ka) * ao);
   // lightSetup reads the point for point and spot lights only: not keeping p live across the pool frees three registers
-  const V3 ph = hardLightSum(sb, mat, N, v3(0.0f, 0.0f, 0.0f), normalize(neg(rd)), maxT, ks, hitMask, total);
+  const V3 ph = hardLightSum<PREP_AC>(sb, mat, N, v3(0.0f, 0.0f, 0.0f), normalize(neg(rd)), maxT, ks, hitMask, total);
   const V3 c = bulbTrapColor(res.trap.y, res.trap.z, res.trap.w);
   out.col = v3(c.x * (ph.x * 8.0f), c.y * (ph.y * 8.0f), c.z * (ph.z * 8.0f));
   info.p = p; info.n = N; info.rd = rd; info.obj = res.obj;
@@ -1366,7 +1461,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
 // POOL (bulb kernels without procedural layers or textures, not counting the reference's work; the primary call of shadePixel,
 // which every lane of the wave that renders a pixel reaches): renderPooled takes the frames whose shadow rays the pool may
 // schedule.  The secondary rays' render() calls are divergent and keep getPhong's queue.
-template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false, bool SHARE = false>
+template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false, bool SHARE = false, bool PREP = false>
 RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, Hit &info, float side, float maxT,
                         V3 bg, Counters &cnt, LightSplit split = LightSplit{-1, nullptr, 0}) {
   RenderOut out;
@@ -1385,7 +1480,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
       q[0] = __int_as_float(res.obj); q[1] = res.d; q[2] = res.trap.x; q[3] = res.trap.y; q[4] = res.trap.z; q[5] = res.trap.w;
     }
   }
-  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT, SHARE>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
+  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT, SHARE, PREP>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
   if (res.obj == -1) {
     out.col = (TEX && sb->s.enableSkyBox) ? sampleCube(sb->skybox, rd) : bg;  // frag:2325-2327
     out.isEnv = 1;
@@ -1502,7 +1597,11 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // The pixel form is written so that its instantiations compile to what they did before the ray form existed: the code objects of
 // the render kernels are byte-identical.
 // SHARE = false keeps bumpNormal in the pooled surface phase (renderPooled): render_adaptive, render_acc and render_anim kernels.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false, bool SHARE = true>
+// PREP: the pool reads the lights' prepared constants (renderPooled, shadowPool).  It follows SHARE: render_anim_kernel must not
+// take it (shadowPool says why), and the other two kernels that hold several samples' or frames' state across the pool keep the
+// code their register reports were settled with.
+template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false, bool SHARE = true,
+          bool PREP = SHARE>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0},
                        const V3 *rayO = nullptr, const V3 *rayD = nullptr) {
@@ -1526,7 +1625,7 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
 
   Hit info;
   constexpr bool POOL = BULB && !ENV && !TEX && COUNT != 1 && SPLIT == 0;  // the shadow pool (renderPooled)
-  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL, SHARE>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
+  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL, SHARE, PREP>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
   EnvOut e;
   e.terrainHit = false; e.cloudHit = false; e.seaHit = false;
   if (env) e = envLayers(feat, sb->noise, iTime, W, ro, rd, ri.d, bg, cnt);  // frag:2444-2456

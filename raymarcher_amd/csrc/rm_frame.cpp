@@ -331,6 +331,27 @@ int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {
   return (g->juliaSeed[0] == 0.0f && g->juliaSeed[1] == 0.0f) ? 1 : 0;
 }
 
+// SceneBlock::lightPrep from the block's light table and objs[0]: what the bulb kernels' shadow pool read per light instead of
+// computing it per ray.  The device's own operations in the device's order, so the same bits: normalize(−dir) is
+// scale(v, rcp_(len(v))) with dot = fma(z, z, fma(y, y, x·x)), sqrt_ the correctly rounded square root (sqrtf) and rcp_ the
+// correctly rounded reciprocal (1.0f / x; both for every input, denormals, zeros and non-finite values included); pd and a are
+// bulbCullEnd's products.  -ffp-contract=off: nothing is fused but the fmaf calls.
+void scene_light_prep(SceneBlock *h) {
+  const float *M = h->objs[0].invModel;
+  for (int i = 0; i < RM_MAX_LIGHTS; i++) {
+    LightPrep &q = h->lightPrep[i];
+    q = LightPrep{};
+    if (i >= h->numLights || h->lights[i].type != RM_LIGHT_DIRECTIONAL) continue;
+    const float x = -h->lights[i].dir[0], y = -h->lights[i].dir[1], z = -h->lights[i].dir[2];
+    const float inv = 1.0f / std::sqrt(std::fmaf(z, z, std::fmaf(y, y, x * x)));
+    const float lx = x * inv, ly = y * inv, lz = z * inv;
+    q.L[0] = lx; q.L[1] = ly; q.L[2] = lz;
+    if (h->numObjects < 1) continue;
+    for (int r = 0; r < 3; r++) q.pd[r] = std::fmaf(M[8 + r], lz, std::fmaf(M[4 + r], ly, M[r] * lx));
+    q.a = std::fmaf(q.pd[2], q.pd[2], std::fmaf(q.pd[1], q.pd[1], q.pd[0] * q.pd[0]));
+  }
+}
+
 // The fill step of a launch: everything of the SceneBlocks of frames 0 … n−1 of one scene that the caller's tables decide (the
 // launch fields are upload_frames').  Block 0 from the tables; every other frame a copy of it with its own camera and globals
 // (globals[numGlobals == 1 ? 0 : f]) and what they decide: the ray planes, the plain-bulb flag and, where the globals differ per
@@ -342,6 +363,7 @@ void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *gl
   for (int i = 0; i < numObjects; i++) h->objs[i] = objs[i];
   scene_eval_records(h);
   for (int i = 0; i < numLights; i++) h->lights[i] = lights[i];
+  scene_light_prep(h);  // reads the two tables only: the copies below take it over
   h->numTextures = res.numTextures;
   for (int i = 0; i < res.numTextures; i++) h->tex[i] = res.textures[i];
   h->noise = res.noise;
@@ -365,7 +387,7 @@ void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *gl
 
 // The fill step of rm_render_animated: fill_frames where every block may have an object table and a light table of its own
 // (objs + b·numObjects when numObjectTables > 1, table 0 otherwise; the lights likewise).  Nothing is taken over from block 0 but
-// what a call shares (settings, resources, the counts): the table copies, the evaluation records, the cull ball and box with
+// what a call shares (settings, resources, the counts): the table copies, the evaluation records, the per-light constants, the cull ball and box with
 // cullLip, cullOneOk and objBall, the ray planes and the plain-bulb flag all come from the block's own tables, camera and globals.
 // With both counts 1 every block holds what fill_frames gives it.  restage (or null): bit b set where block b's object table
 // differs, byte for byte, from block b − 1's (never for b = 0) — what render_anim_kernel stages anew.
@@ -394,6 +416,7 @@ void fill_frames_animated(SceneBlock *h, int n, const RmCamera *cams, const RmGl
       if (restage) restage->set(f);
     }
     for (int i = 0; i < numLights; i++) b->lights[i] = l[i];
+    if (!sameObjs || numLightTables > 1) scene_light_prep(b);  // the block's own tables
     // the cull bounds read the table and, for a Mandelbulb, the globals: recomputed whenever either may differ from the previous block's
     if (!sameObjs || numGlobals > 1) scene_cull_ball(b);
     ray_planes(b);
@@ -523,6 +546,21 @@ int rm_debug_cull_bounds(const RmObject *objs, int numObjects, const RmGlobals *
   for (int k = 0; k < 3; k++) { out14[1 + k] = blk.cullC[k]; out14[7 + k] = blk.cullLo[k]; out14[10 + k] = blk.cullHi[k]; }
   out14[4] = blk.cullR2; out14[5] = blk.cullR2Soft; out14[6] = (float)blk.cullBoxOk;
   out14[13] = blk.cullLip;
+  return RM_OK;
+}
+int rm_debug_light_prep(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, float *out) {
+  if ((!objs && numObjects > 0) || (!lights && numLights > 0) || !out) { set_error("null pointer"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numObjects < 0 || numObjects > RM_MAX_OBJECTS) { set_error("numObjects out of range"); return RM_ERR_INVALID_ARGUMENT; }
+  if (numLights < 0 || numLights > RM_MAX_LIGHTS) { set_error("numLights out of range"); return RM_ERR_INVALID_ARGUMENT; }
+  static SceneBlock blk;  // host-only scratch; the constants are a pure function of the two tables
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  blk.numObjects = numObjects;
+  blk.numLights = numLights;
+  if (numObjects > 0) blk.objs[0] = objs[0];
+  for (int i = 0; i < numLights; i++) blk.lights[i] = lights[i];
+  scene_light_prep(&blk);
+  for (int i = 0; i < numLights; i++) std::memcpy(out + 8 * i, &blk.lightPrep[i], sizeof(LightPrep));
   return RM_OK;
 }
 int rm_debug_bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g) {

@@ -21,6 +21,7 @@ double sigma_max3(const double m[3][3]);
 void scene_cull_ball(SceneBlock *h);
 void ray_planes(SceneBlock *h);
 void scene_eval_records(SceneBlock *h);
+void scene_light_prep(SceneBlock *h);
 int bulb_plain(const RmObject *objs, int numObjects, const RmGlobals *g);
 void fill_frames(SceneBlock *h, int n, const RmCamera *cams, const RmGlobals *globals, int numGlobals, const RmObject *objs,
                  int numObjects, const RmLight *lights, int numLights, const RmSettings *s, const RmResources &res);

@@ -54,6 +54,8 @@ int launch_sdscene_variant(const void *sb, int bulbClass, int count, int trap, i
 int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, float *d_out, int n, hipStream_t stream);
 int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream);
 int launch_probe_bump(const float *d_pts, float *d_out, int n, hipStream_t stream);  // rm_probe_bump's kernel: bumpGradient
+// rm_probe_pool_cull's kernel: the shadow pool's prepared cull beside bulbCullEnd (rm_probe.hip)
+int launch_probe_pool_cull(const void *sb, int bulbClass, int light, float far, const float *d_pts, float *d_out, int n, hipStream_t stream);
 void launch_check_math(unsigned long long *d_out5);
 // The kernels of rm_kernels.hip, as the launcher calls them (the structs are rm_launch.h's, FrameClass rm_frame.h's).  Scene prep:
 // the sponge uniforms of the n staged blocks.  Tile order: the ordering launches of a plan, ahead of the render.  Wavefront: the

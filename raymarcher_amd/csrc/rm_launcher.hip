@@ -1337,12 +1337,13 @@ int launch_sdf_grid_blocks(const BlocksCall &c, const int32_t *d_blocks, int num
 // The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
 // single frames, then launch(the device's block) behind it.
 template <class Launch>
-int probe_scene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, hipStream_t stream, Launch launch) {
+int probe_scene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, hipStream_t stream, Launch launch,
+                const RmLight *lights = nullptr, int numLights = 0) {
   StagedFrames sf(stream);
   sf.timer.on = false;  // a probe is no timed launch: only the slot's event follows it
   const RmCamera cam{};
   if (int st = stage_blocks(&sf, &DeviceState::frames, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &cam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
+        fill_frames(h, 1, &cam, g, 1, objs, numObjects, lights, numLights, s, kNoResources);
       })) return st;
   const int st = launch(sf.slot->dev);
   HIP_OK(hipEventRecord(sf.slot->done, stream));
@@ -1762,6 +1763,25 @@ int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGloba
   return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) {
     return launch_sdscene_variant(sb, bulbClass, count, trap, skip, track, one, d_pts, d_ub, d_out, n, hs);
   });
+}
+
+int rm_probe_pool_cull(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
+                       const RmSettings *s, int bulbClass, int light, float far, const float *d_pts, float *d_out, int n, void *stream) {
+  RmCamera cam{};
+  int st = validate_scene(&cam, objs, numObjects, lights, numLights, g, s, kNoResources);
+  if (st != RM_OK) return st;
+  auto bad = [](const char *msg) { set_error(msg); return (int)RM_ERR_INVALID_ARGUMENT; };
+  if (bulbClass != kBulbGeneral && bulbClass != kBulbPlain) return bad("bulbClass must be 1 (general) or 2 (plain)");
+  if (numObjects != 1 || objs[0].type != RM_MANDELBULB) return bad("a bulb class needs a table of one Mandelbulb");
+  if (bulbClass == kBulbPlain && !bulb_plain(objs, numObjects, g)) return bad("the plain bulb form does not apply to this table");
+  if (light < 0 || light >= numLights || lights[light].type != RM_LIGHT_DIRECTIONAL) return bad("`light` must name a directional light of the table");
+  if (!d_pts || !d_out || n < 0) return bad("bad probe arguments");
+  if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st2;
+  if (n == 0) return RM_OK;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) {
+    return launch_probe_pool_cull(sb, bulbClass, light, far, d_pts, d_out, n, hs);
+  }, lights, numLights);
 }
 
 }  // extern "C"

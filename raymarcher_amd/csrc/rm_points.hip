@@ -120,8 +120,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
       bool shared = f2u(so.x) != 0x80000000u && f2u(so.y) != 0x80000000u && f2u(so.z) != 0x80000000u;
       uint32_t need = 0u;
       for (int l = 0; l < nl; l++) {
-        const RmLight &li = sb->lights[l];
-        const V3 L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
+        const V3 L = preparedL(sb, l);  // lightSetup's normalize(−dir), from the host (SceneBlock::lightPrep)
         shared = shared && (fabs_(L.x) + fabs_(L.y) + fabs_(L.z) <= 2.0f);  // false for a NaN / inf direction
         if (!(dot(N, L) <= 0.005f)) need |= 1u << l;
       }
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
         }
       }
     }
-    const uint32_t hitMask = hits | shadowPool<BULB, 0>(sb, so, pend, dStart, far, cnt);
+    const uint32_t hitMask = hits | shadowPool<BULB, 0, true>(sb, so, pend, dStart, far, cnt);
     if (surf) {
       const RmObject &o = s_objs[0];
       Material mat;
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
       mat.shininess = o.shininess;
       const float ka = sb->g.ka, ks = sb->g.ks;
       const V3 total = v3((mat.amb.x * ka) * aoT, (mat.amb.y * ka) * aoT, (mat.amb.z * ka) * aoT);
-      const V3 ph = hardLightSum(sb, mat, N, v3(0.0f, 0.0f, 0.0f), normalize(neg(rd)), far, ks, hitMask, total);
+      const V3 ph = hardLightSum<true>(sb, mat, N, v3(0.0f, 0.0f, 0.0f), normalize(neg(rd)), far, ks, hitMask, total);
       const V3 c = bulbTrapColor(sc.trap.y, sc.trap.z, sc.trap.w);
       col = v4(c.x * (ph.x * 8.0f), c.y * (ph.y * 8.0f), c.z * (ph.z * 8.0f), 1.0f);
     }

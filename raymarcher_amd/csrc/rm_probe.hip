@@ -1,6 +1,6 @@
 // rm_probe.hip — the test-only device probes: the scene evaluator's production instantiations (rm_probe_sdscene_variant), the
-// plain evaluator (rm_probe_sdscene), the rm_math built-ins (rm_probe_math), the bump gradient's four noise samples (rm_probe_bump)
-// and the 2^32-input checker of the cheap exact forms (rm_debug_check_math).
+// plain evaluator (rm_probe_sdscene), the rm_math built-ins (rm_probe_math), the bump gradient's four noise samples (rm_probe_bump),
+// the shadow pool's cull of a hand-out (rm_probe_pool_cull) and the 2^32-input checker of the cheap exact forms (rm_debug_check_math).
 //
 // Kept out of rm_kernels.hip so that the production translation unit's compile time and code stay as they are.  The variant kernels
 // below call the very template functions the render kernels call (sdSceneImpl, sdSceneOne in rm_device.hip.h) with the same
@@ -68,6 +68,29 @@ __global__ void __launch_bounds__(64) probe_bump_kernel(const float *pts, float 
   o[1] = g[0];
   o[2] = g[1];
   o[3] = g[2];
+}
+
+// The shadow pool's hand-out (shadowPool's PREP form) for shadow origin i and light `light`, beside the forms it replaces: the
+// end and `own` of bulbCullEndPrepared from the block's prepared constants, then those of bulbCullEnd with the direction
+// normalised on the device, then that direction.  Point i on lane i % 64 of wave i / 64, lanes past n leave first: the plain
+// form's fallback for a non-finite origin is a choice of the wave and sees exactly those 64 origins.
+template <int BULB>
+__global__ void __launch_bounds__(64) probe_pool_cull_kernel(const SceneBlock *__restrict__ sb, int light, float far, const float *pts,
+                                                             float *out, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const V3 o = v3(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]);
+  const LightPrep &q = sb->lightPrep[light];
+  const BulbCull cu = bulbCullSetup(sb);
+  bool ownP, ownF;
+  const float endP = bulbCullEndPrepared<BULB == kBulbPlain>(sb, cu, o, v3(q.pd[0], q.pd[1], q.pd[2]), q.a, far, ownP);
+  const RmLight &li = sb->lights[light];
+  const V3 L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
+  const float endF = bulbCullEnd(sb, o, L, far, ownF);
+  float *w = out + 8 * (size_t)i;
+  w[0] = endP; w[1] = ownP ? 1.0f : 0.0f;
+  w[2] = endF; w[3] = ownF ? 1.0f : 0.0f;
+  w[4] = L.x; w[5] = L.y; w[6] = L.z; w[7] = 0.0f;
 }
 
 namespace {
@@ -163,6 +186,14 @@ int launch_probe_math(int fn, const float *d_x, const float *d_y, const float *d
 }
 int launch_probe_sdscene(const void *sb, const float *d_pts, float *d_out, int n, hipStream_t stream) {
   hipLaunchKernelGGL(probe_sdscene_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, static_cast<const SceneBlock *>(sb), d_pts, d_out, n);
+  HIP_OK(hipGetLastError());
+  return RM_OK;
+}
+int launch_probe_pool_cull(const void *sb, int bulbClass, int light, float far, const float *d_pts, float *d_out, int n, hipStream_t stream) {
+  const SceneBlock *b = static_cast<const SceneBlock *>(sb);
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  if (bulbClass == kBulbPlain) hipLaunchKernelGGL(probe_pool_cull_kernel<kBulbPlain>, grid, block, 0, stream, b, light, far, d_pts, d_out, n);
+  else hipLaunchKernelGGL(probe_pool_cull_kernel<kBulbGeneral>, grid, block, 0, stream, b, light, far, d_pts, d_out, n);
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

@@ -18,6 +18,15 @@ struct EvalRecord {
   float invScale, boundR;
 };
 static_assert(sizeof(EvalRecord) == 64, "one cache line");
+// What the bulb kernels' shadow pool (rm_device.hip.h: renderPooled, shadowPool, hardLightSum) would recompute from a light and
+// the single Mandelbulb's transform for every ray: L = normalize(−dir) of a directional light with the contract's dot, sqrt_ and
+// rcp_; pd = invModel·L (the 3×3 part, bulbCullEnd's fma nesting) and a = dot(pd, pd).  Filled on the host by scene_light_prep
+// (rm_frame.cpp) with the same bits the device computes: correctly rounded sqrtf and 1.0f / x, fmaf where the device writes fma.
+// Zeros for a light of another type; pd and a are read only in the single-bulb classes.
+struct LightPrep {
+  float L[3], pd[3], a, pad;
+};
+static_assert(sizeof(LightPrep) == 32, "eight words per light: two 16-byte LDS reads");
 struct SceneBlock {
   RmCamera cam;
   RmGlobals g;
@@ -26,6 +35,7 @@ struct SceneBlock {
   int32_t numLights;
   RmObject objs[RM_MAX_OBJECTS];
   RmLight lights[RM_MAX_LIGHTS];
+  LightPrep lightPrep[RM_MAX_LIGHTS];  // per-light constants of the shadow pool, from lights[] and objs[0] (scene_light_prep)
   RmTexture tex[RM_MAX_TEXTURES];  // device pixel pointers
   int32_t numTextures;
   RmTexture noise;                 // `noise` (night sky, sea)
@@ -88,7 +98,7 @@ struct RowMap {
     return rowBegin + tile_of(shard, r / tileRows, numShards, relief) * tileRows + (r % tileRows);
   }
 };
-static_assert(sizeof(SceneBlock) == 9664, "host and device agree on the block's layout");
+static_assert(sizeof(SceneBlock) == 9984, "host and device agree on the block's layout");
 
 // rm_render_animated: one bit per scene block of a call, beside the blocks (a kernel argument of render_anim_kernel, rm_animate.hip).
 // Bit b set: block b's object table differs from block b − 1's, so a workgroup that walks from one to the other stages it anew.

@@ -1345,3 +1345,17 @@ class Renderer:
                                              C.c_void_p(ub.data_ptr()) if ub is not None else None,
                                              C.c_void_p(out.data_ptr()), n, self._stream()))
         return out
+
+    def probe_pool_cull(self, tables, settings, pts, bulb_class, light, far, out=None):
+        """The shadow pool's cull end for the (n, 3) shadow origins `pts` and directional light `light` (include/raymarcher_amd.h,
+        rm_probe_pool_cull; point i runs on lane i % 64 of wave i / 64).  Returns (n, 8): end and own from the staged constants,
+        end and own from the whole computation, the direction normalised on the device, 0."""
+        t = self.torch
+        n = pts.shape[0]
+        if tuple(pts.shape) != (n, 3) or pts.dtype != t.float32 or not pts.is_contiguous() or pts.device != self.device:
+            raise ValueError(f"pts must be a contiguous float32 tensor of shape (n, 3) on {self.device}")
+        out = self._out(out, (n, 8), t.float32)
+        check(lib().rm_probe_pool_cull(tables.objects, tables.num_objects, tables.lights, tables.num_lights, C.byref(tables.globals_),
+                                       C.byref(settings), bulb_class, light, far, C.c_void_p(pts.data_ptr()),
+                                       C.c_void_p(out.data_ptr()), n, self._stream()))
+        return out
