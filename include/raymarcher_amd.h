@@ -873,6 +873,75 @@ int rm_sdf_trace_blocks(const RmRay *d_rays, int numRays, const float *d_dist, c
                         void *stream);
 
 /*
+ * Lattice handles — rm_field_create, rm_field_create_blocks, rm_field_destroy, rm_field_sample, rm_field_trace: the lattice queries
+ * above for a caller that asks ONE lattice again and again (particle collision every tick, a frame's shadow rays).  An RmField is
+ * built once and owns what is derived from the block list, so a query is one launch and nothing else; and its march takes
+ * RM_TRACE_OCCLUSION, which rm_sdf_trace and rm_sdf_trace_blocks refuse.
+ * Ownership and lifetime.  The handle borrows d_dist and d_objectId (may be NULL): they are not copied, the caller keeps them alive
+ * until rm_field_destroy, and may rewrite the VALUES in place between calls (ordered against the queries by the caller's streams); a
+ * query reads what is there when it runs.  The handle consumes d_blocks: rm_field_create_blocks enqueues its build on `stream` and
+ * synchronises that stream before it returns, so the list may be freed at once and the handle is usable on any stream afterwards.
+ * The handle owns its block map (4 B per block of the virtual lattice) and its coarse level (8 B per group of 4×4×4 blocks) in device
+ * memory of its own, from plain hipMalloc and not the kWsBlocks workspace: rm_set_workspace_limit and rm_release_workspaces do not
+ * apply to it, and only rm_field_destroy frees it.  A dense handle owns no device memory.  origin and step are host memory, copied.
+ * The handle records the device current at create; a query with another device current is RM_ERR_INVALID_ARGUMENT.  A magic word in
+ * the struct guards against a destroyed or garbage handle — best effort only: a pointer that was never a handle may fault, and a
+ * destroyed handle's memory may be reused.  Queries of one handle may run concurrently from several threads and streams;
+ * rm_field_destroy may not run beside them, and the caller synchronises the streams that still use the handle first.
+ * rm_field_sample is rm_sdf_sample (dense handle) / rm_sdf_sample_blocks (block handle) on the handle's lattice, in every bit.
+ * rm_field_trace, modes RM_TRACE_CLOSEST and RM_TRACE_NO_NORMAL, on a dense handle is rm_sdf_trace in every bit, for every maxSteps.
+ * On a block handle the march is rm_sdf_trace_blocks' state machine (its step 3) with ONE change: maxSteps counts samples only, a
+ * skip is free.  samples = 0; then repeat: miss if t > tEnd; u and b as in step 3, forced or not; if the block is unlisted, the skip
+ * of step 3 exactly as written (exit axis by the smallest ta, x before y before z; the integer step; miss if it leaves the lattice;
+ * t = max(ta, t); forced = true) and start over; otherwise miss if samples == maxSteps; samples += 1; the cell's value at u; forced
+ * = false; HIT iff value < iso; else t = t + value.  A run of skips between two samples is at most mx + my + mz long, so the loop ends.
+ * Wherever rm_sdf_trace_blocks with the same list needed no more than its budget, skips included, and this march no more than
+ * maxSteps samples, the two records are equal in every word.  The coarse level (Schedule, below) is an implementation detail: what
+ * it does in one step has the bits of the run of skips written here, and a build without it (-DRM_FIELD_COARSE=0) gives the same words.
+ * RM_TRACE_OCCLUSION, dense or blocks: the same loop with the renderer's penumbra tracker (softshadow, frag:1703-1725, k =
+ * RM_FIELD_PENUMBRA_K).  res = 1 before the loop.  At every sample that is not a hit, BEFORE t advances: q = (8·value) / t, unfused,
+ * the division correctly rounded, t as it stands (a first sample at t = 0 gives ±inf or NaN); res = q < res ? q : res, so a NaN q
+ * never enters.  Hit: objectId as the cell sample has it (0 without ids), t = res.  Miss — a missed box, the box, the lattice or tMax
+ * left, the samples used up —: objectId = −1, t = res; a ray that never sampled stores 1.  normal and position are zeros in both.
+ * Invalid ray: as in the closest march.  What a caller reads as visibility is objectId == −1 ? t : 0, as with rm_trace_rays.  The t
+ * sequence is the closest march's, so occlusion hits iff closest hits, with the same objectId.
+ * rm_field_create / rm_field_create_blocks refuse, in this order and all but the last before any HIP call, with *field = NULL on every
+ * failure, RM_ERR_INVALID_ARGUMENT: what rm_sdf_sample / rm_sdf_sample_blocks refuse about the lattice, with their messages (null
+ * origin or step, origin, step; dense: the dimensions, INT_MAX points, a dimension below 2; blocks: the block dimensions, then
+ * numBlocks); a null `field`; a null d_dist (unless numBlocks == 0) or a null d_blocks with numBlocks above 0; a misaligned d_dist,
+ * d_objectId or d_blocks (4 bytes); an array that is not device memory.  A HIP failure (no memory for the map) is RM_ERR_DEVICE.
+ * rm_field_destroy(NULL) is a no-op.
+ * rm_field_sample / rm_field_trace refuse, in this order, RM_ERR_INVALID_ARGUMENT: a null or bad handle; a negative numPoints /
+ * numRays; the march: iso not finite, maxSteps outside 0 … RM_MAX_FIELD_STEPS, mode bits other than RM_TRACE_NO_NORMAL and
+ * RM_TRACE_OCCLUSION, or both of them together (rm_trace_rays' rule).  Then a count of 0: RM_OK, nothing read or written.  Then a null
+ * d_points / d_rays or d_samples / d_hits; a misaligned one (16 bytes); — from here on with HIP calls — another device current than
+ * the handle's; an array that is not device memory.
+ * Schedule: ONE launch per query, one lane per point or ray, 256-lane workgroups, two 16-byte stores per record.  At create a block
+ * handle builds, beside the block map, one 64-bit occupancy mask per group of 4×4×4 blocks (bit (bx&3) | (by&3)<<2 | (bz&3)<<4; the
+ * groups at the high faces are ragged).  A marching lane keeps its group's mask in registers while the group does not change and
+ * loads the block map only for a listed block whose slot it does not hold: one 8-byte load per group crossed instead of one
+ * dependent 4-byte load per block crossed.  A group whose mask is 0 is left in ONE step: the run of skips that crosses it is the
+ * stable merge of the three axes' face sequences by (ta, axis), each of them sorted because a rounded subtraction and a correctly
+ * rounded division by a fixed ud are monotone; so the run leaves on the axis whose last face inside the group (clipped to the
+ * lattice) has the smallest (ta, axis) = (T, A), every other axis c has by then crossed its faces inside the group with (ta, c) <
+ * (T, A), at most three; the run's t = ta > t ? ta : t, skip after skip, is T > t ? T : t in every bit as long as T is not ±0 (equal
+ * binary32 numbers have equal bits unless they are zeros of two signs), and for T = ±0 the step is not taken: the fine skips run
+ * (rm_field_skip.h has the argument, tests/test_field_handle_spec.py the proof by campaign against the build without the level).  No scene is staged and no slot of the ring of scene blocks is used.  Not render launches:
+ * rm_debug_last_path() keeps its value and rm_set_timing does not time them.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmField RmField;   /* opaque */
+#define RM_FIELD_PENUMBRA_K 8.0f  /* the k of lightTerm's softshadow, rm_trace_rays' */
+int  rm_field_create(const float *d_dist, const int32_t *d_objectId /* may be NULL */, int nx, int ny, int nz,
+                     const float origin[3], const float step[3], RmField **field);
+int  rm_field_create_blocks(const float *d_dist, const int32_t *d_objectId /* may be NULL */, const int32_t *d_blocks, int numBlocks,
+                            int mx, int my, int mz, const float origin[3], const float step[3], void *stream, RmField **field);
+void rm_field_destroy(RmField *field);   /* NULL is a no-op */
+int  rm_field_sample(const RmField *field, const float *d_points, int numPoints, RmFieldSample *d_samples, void *stream);
+int  rm_field_trace(const RmField *field, const RmRay *d_rays, int numRays, float iso, int maxSteps,
+                    unsigned mode /* RM_TRACE_CLOSEST, | RM_TRACE_NO_NORMAL, or RM_TRACE_OCCLUSION */, RmRayHit *d_hits, void *stream);
+
+/*
  * rm_shade_points — what the renderer thinks of POINTS the caller already has: the scene's distance and object at each point, its
  * normal, its ambient occlusion and its shaded colour, with the point optionally projected onto the iso-surface first (no reference
  * counterpart: the shader reaches a surface point only at the end of a ray of its own).  The points counterpart of rm_trace_rays /

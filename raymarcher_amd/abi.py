@@ -146,6 +146,7 @@ class RmFieldSample(C.Structure):
 
 RM_FIELD_OUTSIDE, RM_FIELD_UNLISTED = -5, -6  # RmFieldSample.objectId of a point outside the lattice's box / in an unlisted block
 RM_MAX_FIELD_STEPS = 65536  # march steps of one rm_sdf_trace / rm_sdf_trace_blocks call
+RM_FIELD_PENUMBRA_K = 8.0  # the k of the penumbra tracker of rm_field_trace's RM_TRACE_OCCLUSION
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

@@ -388,6 +388,64 @@ def write_ply_ex(path, vertices, quads, colours=None, normals=None):
     return path
 
 
+class LatticeField:
+    """An RmField handle (Renderer.lattice_field, lattice_field_blocks, scene_field): one lattice queried again and again.  It keeps
+    references to the tensors the handle borrows.  A context manager; close() is idempotent, and the handle is destroyed on garbage
+    collection at the latest.  Synchronise the streams that still run its queries before closing it."""
+
+    def __init__(self, renderer, handle, borrowed):
+        self._r, self._h, self._borrowed = renderer, handle, borrowed
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            lib().rm_field_destroy(h)
+        self._borrowed = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the LatticeField is closed")
+        return self._h
+
+    def sample(self, points):
+        """rm_field_sample → sample_lattice's 4-tuple (gradient, value, cell, object_id), in every bit."""
+        r, h = self._r, self._handle()
+        t = r.torch
+        pts = r._points(points, "points")
+        n = pts.shape[0]
+        out = t.empty((n, 8), dtype=t.float32, device=r.device)
+        check(lib().rm_field_sample(h, C.c_void_p(pts.data_ptr()) if n else None, n, C.c_void_p(out.data_ptr()) if n else None, r._stream()))
+        return out[:, 0:3], out[:, 3], out[:, 4:7].view(t.int32), out[:, 7].view(t.int32)
+
+    def trace(self, rays, iso=0.001, max_steps=256, mode="closest", normals=True, out=None):
+        """rm_field_trace → trace_lattice's 4-tuple (normal, t, position, object_id).  max_steps counts samples only: crossing
+        unlisted blocks is free.  mode "occlusion", trace_rays' spelling: object_id = the occluder's id (−1: none), t = the penumbra
+        factor; visibility is t where object_id == −1, else 0."""
+        r, h = self._r, self._handle()
+        t = r.torch
+        if mode not in ("closest", "occlusion"):
+            raise ValueError(f"mode = {mode!r}: 'closest' or 'occlusion'")
+        rays = r._rays(rays)
+        n = rays.shape[0]
+        hits = r._out(out, (n, 8), t.float32)
+        bits = abi.RM_TRACE_OCCLUSION if mode == "occlusion" else (abi.RM_TRACE_CLOSEST if normals else abi.RM_TRACE_NO_NORMAL)
+        check(lib().rm_field_trace(h, C.c_void_p(rays.data_ptr()) if n else None, n, float(iso), int(max_steps), bits,
+                                   C.c_void_p(hits.data_ptr()) if n else None, r._stream()))
+        return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+
 class Renderer:
     """Launches the HIP raymarch on one GPU; outputs are torch tensors on that device."""
 
@@ -1071,6 +1129,35 @@ class Renderer:
         bl = self.sdf_active_blocks(tables, settings, origin, (step,) * 3, blocks, iso)
         dist, obj = self.sdf_grid_blocks(tables, settings, origin, (step,) * 3, blocks, bl, ids=True)
         return dist, obj, bl, blocks, origin, (step,) * 3
+
+    # ---- lattice handles: what is derived from the block list built once (include/raymarcher_amd.h, "Lattice handles") ----
+    def lattice_field(self, grid, origin, step, ids=None):
+        """rm_field_create: a handle on a dense lattice → LatticeField.  grid, ids as sample_lattice takes them; the handle borrows
+        them (the LatticeField keeps references) and reads their values as they are when a query runs."""
+        gp, ip = self._lattice(grid, ids, "(nz, ny, nx)", lambda g: g.dim() == 3)
+        nz, ny, nx = grid.shape
+        h = C.c_void_p()
+        check(lib().rm_field_create(gp, ip, nx, ny, nz, _vec3(origin, "origin"), _vec3(step, "step"), C.byref(h)))
+        return LatticeField(self, h, (grid, ids))
+
+    def lattice_field_blocks(self, grid_blocks, block_list, blocks, origin, step, ids=None):
+        """rm_field_create_blocks: a handle on a block-sparse lattice → LatticeField.  grid_blocks, block_list, blocks and ids as
+        sample_lattice_blocks takes them.  The block map and the coarse level are built here, once, on the current stream, which is
+        synchronised; block_list is not needed afterwards, grid_blocks and ids are borrowed as lattice_field borrows."""
+        mx, my, mz = self._blocks3(blocks)
+        bl = self._block_list(block_list)
+        nb = bl.shape[0]
+        gp, ip = self._lattice(grid_blocks, ids, f"({nb}, 9, 9, 9)", lambda g: tuple(g.shape) == (nb, 9, 9, 9))
+        h = C.c_void_p()
+        check(lib().rm_field_create_blocks(gp, ip, C.c_void_p(bl.data_ptr()) if nb else None, nb, mx, my, mz, _vec3(origin, "origin"),
+                                           _vec3(step, "step"), self._stream(), C.byref(h)))
+        return LatticeField(self, h, (grid_blocks, ids))
+
+    def scene_field(self, tables, settings, resolution, iso=0.001, bounds=None):
+        """scene_field_sparse's lattice behind a handle → LatticeField: the scene's distance field baked where its surface is, ready
+        for sample and trace, occlusion marches included."""
+        dist, obj, bl, blocks, origin, step = self.scene_field_sparse(tables, settings, resolution, iso, bounds)
+        return self.lattice_field_blocks(dist, bl, blocks, origin, step, obj)
 
     def shade_points(self, tables, settings, points, view=None, far=None, colour=True, ao=False, project=0, iso=0.001,
                      max_move=float("inf")):
