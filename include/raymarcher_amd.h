@@ -735,6 +735,45 @@ int rm_sdf_blocks_select(const RmObject *objs, int numObjects, const RmGlobals *
                          const float step[3], int mx, int my, int mz, float iso, int maxBlocks, int32_t *d_blocks /* int4 each */,
                          uint32_t *d_count /* 1 word */, void *stream);
 /*
+ * rm_sdf_blocks_select_pruned — rm_sdf_blocks_select without the sweep over blocks far from the surface.  The surface passes through
+ * under 1 % of the blocks of a large lattice; this entry evaluates the block corners first and the 729 points only of the blocks
+ * the corners do not rule out.
+ * Definition.  c(i, j, k), i in 0 … mx (j, k likewise), is sdScene(p).minD at lattice point (8i, 8j, 8k), in rm_sdf_grid's bits
+ * (origin + (float)(8i) · step).  h = 4 · sqrt((sx·sx + sy·sy) + sz·sz), half a block's diagonal, every operation rounded to binary32
+ * with no contraction and the square root correctly rounded (computed on the host); bOut = lipschitzOut · h and bIn = lipschitzIn ·
+ * h, one rounded multiplication each; a NaN bound (0 · inf) discards nothing.  For a corner value c: d = c − iso, farOut = d > bOut,
+ * farIn = d < −bIn; a NaN c is neither, a value exactly at a bound is not far.  A block is DISCARDED iff farOut holds at all eight of
+ * its corners, or farIn holds at all eight; every other block is a CANDIDATE.  The list is the candidates that are ACTIVE by
+ * rm_sdf_blocks_select's exact rule, decided from the block's own 729 points: the same linear order (bk·my + bj)·mx + bi, the same
+ * rows (bi, bj, bk, 0).  d_count[0] receives the FULL number of listed blocks, as in rm_sdf_blocks_select, and maxBlocks = 0 with a
+ * null d_blocks is the counting call; d_count[1] receives the number of candidates, saturated at 2^32 − 1.
+ * Properties.  The list is a sub-sequence of rm_sdf_blocks_select's list.  With both constants +INFINITY the two lists and d_count[0]
+ * are equal in every word.  They are also equal whenever every lattice point p of a block and every corner q of it satisfy v(p) ≥
+ * v(q) − lipschitzOut·|p − q| on the outside, and the mirrored condition with lipschitzIn on the inside (|p − q| ≤ h for the nearest
+ * corner, so a block with all corners far on one side has all 729 points on that side).  A true distance function honours this with
+ * 1.  The Mandelbulb's estimate on the outside exceeds the distance near fine structure: measured on the headline bulb, 1 loses
+ * nothing up to 2049 points per axis and 16 of a million blocks at 4097, 2 loses none (profiles/sdf_prune.md); the Python layer
+ * passes 4.  The fractal estimators' interior honours no constant — the Mandelbulb's reports one value that is no distance, and a Julia
+ * set has pockets of escaping points inside — so lipschitzIn = +INFINITY is what a caller who wants the exact list of a fractal
+ * passes.  The rule is flat on purpose: a hierarchy of single probes fails on estimators that return a huge value at one point.
+ * In this order, and all but the last before any HIP call: rm_sdf_blocks_select's refusals in its order, with one more between "iso
+ * not finite" and "a negative maxBlocks": RM_ERR_INVALID_ARGUMENT for a lipschitzOut or lipschitzIn that is NaN or below 0
+ * (+INFINITY and 0 are valid).
+ * Schedule: staging is rm_sdf_grid's; asynchronous on `stream` with no host synchronisation inside the call.  (1) The corner lattice,
+ * (mx + 1)(my + 1)(mz + 1) values, one lane per corner with the evaluator of rm_sdf_grid's kernel of the table's march class; a lane
+ * past the last corner leaves before the evaluation, so a corner's value does not depend on its wave.  (2) One lane per block reads
+ * its eight corners and writes the block's flag; count / scan / emit turn the flags into the list of candidates.  (3) Workgroups of
+ * rm_sdf_blocks_select's shape loop over that list, whose length they read from device memory, and turn each candidate's flag into
+ * its active flag; the grid is sized from the device's compute units.  (4) rm_sdf_blocks_select's compaction of the flags
+ * (rm_debug_last_path() = 20, rm_debug_last_split() = 0; with rm_set_timing(1) it counts as one launch, all stage 1).  Workspace, the
+ * one of rm_sdf_blocks_select: 4 B per corner + 8 B per block of the virtual lattice + 8 B per 1024 blocks, which is at most 12 B per
+ * block of a lattice with many blocks per axis; rm_set_workspace_limit applies (a lattice over a set limit: RM_ERR_DEVICE),
+ * rm_release_workspaces frees it.  Added without a change of RM_ABI_VERSION, as the entries around it.
+ */
+int rm_sdf_blocks_select_pruned(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                                const float step[3], int mx, int my, int mz, float iso, float lipschitzOut, float lipschitzIn,
+                                int maxBlocks, int32_t *d_blocks /* int4 each */, uint32_t *d_count /* 2 words */, void *stream);
+/*
  * rm_sdf_grid_blocks — the lattice, stored only where listed.  Entry n owns floats [n·729, (n + 1)·729) of d_dist (and as many int32
  * of d_objectId, which may be NULL); its local point (a, b, c), each 0 … 8, is stored at (c·9 + b)·9 + a and holds the value at
  * lattice point (8·bi + a, 8·bj + b, 8·bk + c): the bits rm_sdf_grid stores for that point of the dense lattice.  Points on shared
@@ -1150,7 +1189,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
  * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
- * 19 = a launch of rm_sdf_grid_blocks (none of them is a value rm_set_kernel_path takes). */
+ * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned (none of them is a value rm_set_kernel_path
+ * takes). */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups

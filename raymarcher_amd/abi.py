@@ -126,6 +126,7 @@ RM_PATH_SHADE_RAYS_LAYERS, RM_PATH_TRACE_RAYS_LAYERS = 14, 15  # … behind rm_s
 RM_PATH_SDF_GRID = 16  # … behind rm_sdf_grid
 RM_MAX_LATTICE_DIM = 4096  # points per axis of a lattice of rm_sdf_grid / rm_sdf_mesh
 RM_PATH_SDF_BLOCKS_SELECT, RM_PATH_SDF_GRID_BLOCKS = 18, 19  # … behind rm_sdf_blocks_select / rm_sdf_grid_blocks
+RM_PATH_SDF_BLOCKS_SELECT_PRUNED = 20  # … behind rm_sdf_blocks_select_pruned
 RM_MAX_LATTICE_BLOCKS = 512  # blocks of 8×8×8 cells per axis of a virtual lattice (rm_sdf_blocks_select and its two companions)
 RM_MAX_BLOCK_LIST = 1 << 22  # entries of one block list
 RM_RAYS_ORDER_TILE = 2048  # keys per workgroup of rm_rays_order's sort

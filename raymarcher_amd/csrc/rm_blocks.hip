@@ -43,8 +43,6 @@ RM_DEV int eval_point_of(unsigned wave, unsigned lane) {
   return c <= 8u ? snb::point_index((int)a, (int)b, (int)c) : -1;
 }
 
-struct BlockLattice { float ox, oy, oz, sx, sy, sz; int mx, my, mz; };
-
 // SELECT: the grid is the virtual lattice's blocks, flags[(bk·my + bj)·mx + bi] = 1 iff the block is active.
 // otherwise: the grid is the list, entry n's values go to dist[n·729 …] (and ids); a void entry's workgroup leaves at once.
 template <int BULB, bool SELECT>
@@ -126,8 +124,7 @@ RM_DEV unsigned below(unsigned long long ballot, unsigned lane) { return (unsign
 // ---- rm_sdf_blocks_select's compaction ------------------------------------------------------------------------------------------
 // The flags in the blocks' linear order are dealt to workgroups of ONE wave, 1024 consecutive flags each (16 rounds of 64):
 // select_count_kernel → blocks_scan_kernel → select_emit_kernel, which numbers the set flags behind its share's offset (ballot +
-// popcount) and stores the entries numbered below maxBlocks.
-constexpr int kShareRounds = 16, kShare = 64 * kShareRounds;
+// popcount) and stores the entries numbered below maxBlocks.  kShareRounds and kShare are rm_internal.h's.
 
 __global__ __launch_bounds__(64) void select_count_kernel(const uint32_t *__restrict__ flags, size_t numFlags, unsigned long long *__restrict__ off) {
   unsigned count = 0;  // wave-uniform
@@ -155,6 +152,16 @@ __global__ __launch_bounds__(64) void select_emit_kernel(const uint32_t *__restr
     }
     base += (unsigned long long)__popcll(ballot);
   }
+}
+void enqueue_flags_count(const uint32_t *flags, size_t numFlags, unsigned long long *off, uint32_t *d_count, hipStream_t stream) {
+  const size_t shares = flag_shares(numFlags);
+  hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)shares), dim3(64), 0, stream, flags, numFlags, off);
+  hipLaunchKernelGGL(blocks_scan_kernel, dim3(1), dim3(1024), 0, stream, off, (unsigned)shares, off + shares, d_count);
+}
+void enqueue_flags_emit(const uint32_t *flags, size_t numFlags, int mx, int my, const unsigned long long *off, int maxBlocks, int32_t *d_blocks,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(select_emit_kernel, dim3((unsigned)flag_shares(numFlags)), dim3(64), 0, stream, flags, numFlags, mx, my, off, maxBlocks,
+                     d_blocks);
 }
 
 // ---- the block map ----------------------------------------------------------------------------------------------------------------
@@ -185,22 +192,20 @@ static void launch_eval(int bulbClass, dim3 grid, hipStream_t stream, Args... ar
 }
 
 size_t blocks_select_workspace(int mx, int my, int mz) {
-  const size_t blocks = (size_t)mx * (size_t)my * (size_t)mz, shares = (blocks + kShare - 1) / kShare;
-  return align256(blocks * sizeof(uint32_t)) + align256((shares + 1) * sizeof(unsigned long long));
+  const size_t blocks = (size_t)mx * (size_t)my * (size_t)mz;
+  return align256(blocks * sizeof(uint32_t)) + align256((flag_shares(blocks) + 1) * sizeof(unsigned long long));
 }
 int launch_blocks_select_kernels(const void *sbv, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz, float iso,
                                  int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace, hipStream_t stream) {
-  const size_t blocks = (size_t)mx * (size_t)my * (size_t)mz, shares = (blocks + kShare - 1) / kShare;
+  const size_t blocks = (size_t)mx * (size_t)my * (size_t)mz;
   uint32_t *flags = static_cast<uint32_t *>(workspace);
   unsigned long long *off = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + align256(blocks * sizeof(uint32_t)));
   const BlockLattice L{origin[0], origin[1], origin[2], step[0], step[1], step[2], mx, my, mz};
   // at most 512 blocks along every axis: every grid dimension is far below its limit of 65535
   launch_eval<true>(bulbClass, dim3((unsigned)mx, (unsigned)my, (unsigned)mz), stream, static_cast<const SceneBlock *>(sbv), L, iso,
                     (const int32_t *)nullptr, (const uint32_t *)nullptr, flags, (float *)nullptr, (int32_t *)nullptr);
-  hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)shares), dim3(64), 0, stream, flags, blocks, off);
-  hipLaunchKernelGGL(blocks_scan_kernel, dim3(1), dim3(1024), 0, stream, off, (unsigned)shares, off + shares, d_count);
-  if (maxBlocks > 0)
-    hipLaunchKernelGGL(select_emit_kernel, dim3((unsigned)shares), dim3(64), 0, stream, flags, blocks, mx, my, off, maxBlocks, d_blocks);
+  enqueue_flags_count(flags, blocks, off, d_count, stream);
+  if (maxBlocks > 0) enqueue_flags_emit(flags, blocks, mx, my, off, maxBlocks, d_blocks, stream);
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

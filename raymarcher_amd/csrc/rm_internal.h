@@ -134,6 +134,23 @@ int launch_blocks_select_kernels(const void *sb, int bulbClass, const float orig
                                  int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace, hipStream_t stream);
 int launch_blocks_grid_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz,
                                const int32_t *d_blocks, int numBlocks, float *d_dist, int32_t *d_objectId, void *workspace, hipStream_t stream);
+// What rm_blocks.hip shares with rm_blocks_prune.hip (rm_sdf_blocks_select_pruned; a translation unit of its own for the same
+// reason).  The lattice as the evaluation kernels take it.  The compaction of one flag per block in linear order: the flags are
+// dealt in shares of kShare to workgroups of one wave; enqueue_flags_count counts each share into off[share], scans the
+// flag_shares(numFlags) counts into exclusive offsets in place, stores the total in off[shares] and, saturated at 2^32 − 1, in
+// *d_count; enqueue_flags_emit stores the rows (bi, bj, bk, 0) of the set flags numbered below maxBlocks.
+// launch_blocks_prune_kernels: the corner lattice, the classification, the candidates' exact evaluation and the compaction of the
+// active flags into d_blocks and d_count[0], the candidates' number into d_count[1]; `workspace` holds blocks_prune_workspace bytes.
+struct BlockLattice { float ox, oy, oz, sx, sy, sz; int mx, my, mz; };
+constexpr int kShareRounds = 16, kShare = 64 * kShareRounds;
+inline size_t flag_shares(size_t numFlags) { return (numFlags + kShare - 1) / kShare; }
+void enqueue_flags_count(const uint32_t *flags, size_t numFlags, unsigned long long *off, uint32_t *d_count, hipStream_t stream);
+void enqueue_flags_emit(const uint32_t *flags, size_t numFlags, int mx, int my, const unsigned long long *off, int maxBlocks, int32_t *d_blocks,
+                        hipStream_t stream);
+size_t blocks_prune_workspace(int mx, int my, int mz);
+int launch_blocks_prune_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz, float iso,
+                                float lipschitzOut, float lipschitzIn, int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace,
+                                hipStream_t stream);
 // The points kernels (rm_points.hip, rm_shade_points; a translation unit of its own for the same reason): the launch of
 // shade_points_kernel<bulbClass, tex> over the ONE staged SceneBlock `sb`, one lane per point — numPoints float4 from d_points and,
 // when d_view is not null, from d_view; into whichever of d_surface (numPoints RmSurfacePoint), d_ao (a float each) and d_rgba (a

@@ -1276,8 +1276,9 @@ int launch_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, co
 // check_block_lattice in check_lattice's place and the call's own behind it, every one but the last ahead of the first HIP call;
 // launch_sdf_grid's staging behind the stream's workspace (kWsBlocks), which is taken under the device's lock as launch_adaptive
 // takes its own.  rm_sdf_blocks_select: one launch of blocks_eval_kernel (rm_blocks.hip) over every block of the lattice, which
-// keeps a flag per block, and the compaction of the flags, path 18.  rm_sdf_grid_blocks: the block map of the list (void entries),
-// then one launch of the same kernel over the list's entries, path 19.
+// keeps a flag per block, and the compaction of the flags, path 18; rm_sdf_blocks_select_pruned: the same flags from the kernels of
+// rm_blocks_prune.hip, which evaluate only the blocks near the surface, path 20.  rm_sdf_grid_blocks: the block map of the list
+// (void entries), then one launch of blocks_eval_kernel over the list's entries, path 19.
 struct BlocksCall {
   const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s; const float *origin, *step; int mx, my, mz;
   hipStream_t stream;
@@ -1307,15 +1308,26 @@ int stage_blocks_call(const BlocksCall &c, size_t workspaceBytes, int path, Laun
   if ((st = launch(sf.slot->dev, bulbClass, mem)) != RM_OK) return st;
   return finish_frames(sf, path);
 }
-int launch_sdf_blocks_select(const BlocksCall &c, float iso, int maxBlocks, int32_t *d_blocks, uint32_t *d_count) {
+// lipschitz: null for rm_sdf_blocks_select; (lipschitzOut, lipschitzIn) for rm_sdf_blocks_select_pruned, which has the same checks
+// with its own between iso and maxBlocks, the same staging, the kernels of rm_blocks_prune.hip and path 20.
+int launch_sdf_blocks_select(const BlocksCall &c, float iso, const float *lipschitz, int maxBlocks, int32_t *d_blocks, uint32_t *d_count) {
   int st = check_blocks_head(c);
   if (st != RM_OK) return st;
   if (!(iso - iso == 0.0f)) { set_error("iso must be finite"); return RM_ERR_INVALID_ARGUMENT; }
+  if (lipschitz && !(lipschitz[0] >= 0.0f && lipschitz[1] >= 0.0f)) {
+    set_error("lipschitzOut and lipschitzIn must not be NaN or negative (+inf: that side discards nothing)");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
   if (maxBlocks < 0) { set_error("negative maxBlocks"); return RM_ERR_INVALID_ARGUMENT; }
   if ((st = check_blocks_scene(c, "rm_sdf_blocks_select evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK)
     return st;
   if ((maxBlocks > 0 && !d_blocks) || !d_count) { set_error("null d_count, or null d_blocks with maxBlocks above 0"); return RM_ERR_INVALID_ARGUMENT; }
   if ((st = require_device_pointers({{"d_blocks", d_blocks}, {"d_count", d_count}})) != RM_OK) return st;
+  if (lipschitz)
+    return stage_blocks_call(c, blocks_prune_workspace(c.mx, c.my, c.mz), 20, [&](const SceneBlock *sb, int bulbClass, void *mem) {
+      return launch_blocks_prune_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, iso, lipschitz[0], lipschitz[1], maxBlocks, d_blocks,
+                                         d_count, mem, c.stream);
+    });
   return stage_blocks_call(c, blocks_select_workspace(c.mx, c.my, c.mz), 18, [&](const SceneBlock *sb, int bulbClass, void *mem) {
     return launch_blocks_select_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, iso, maxBlocks, d_blocks, d_count, mem, c.stream);
   });
@@ -1478,8 +1490,16 @@ int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const 
 int rm_sdf_blocks_select(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
                          const float step[3], int mx, int my, int mz, float iso, int maxBlocks, int32_t *d_blocks, uint32_t *d_count,
                          void *stream) {
-  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, maxBlocks,
-                                  d_blocks, d_count);
+  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, nullptr,
+                                  maxBlocks, d_blocks, d_count);
+}
+
+int rm_sdf_blocks_select_pruned(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
+                                const float step[3], int mx, int my, int mz, float iso, float lipschitzOut, float lipschitzIn, int maxBlocks,
+                                int32_t *d_blocks, uint32_t *d_count, void *stream) {
+  const float lipschitz[2] = {lipschitzOut, lipschitzIn};
+  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, lipschitz,
+                                  maxBlocks, d_blocks, d_count);
 }
 
 int rm_sdf_grid_blocks(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
