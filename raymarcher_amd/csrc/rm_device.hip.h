@@ -151,7 +151,12 @@ enum BulbMode { BULB_GENERIC = 0, BULB_TRIG8 = 1, BULB_ALGEBRAIC8 = 2 };
 // NOJULIA: the launcher has found both juliaSeed components zero (SceneBlock::bulbPlain): frag:782's test is false, c = pos
 // without a per-lane select.
 // FUSE (the single-bulb classes): one range guard for the estimate's logarithm, square root and reciprocal (see the return).
-template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false, bool FUSE = false>
+// SCALAR (the loops of the plain class's pooled kernels, kBulbScalarLoop): the iteration loop's control on the scalar unit (below).
+// -DRM_X_SCALAR_LOOP=0 (experiment; profiles/bulb_scalar_loop.md): off everywhere, the parent's code.
+#ifndef RM_X_SCALAR_LOOP
+#define RM_X_SCALAR_LOOP 1
+#endif
+template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false, bool FUSE = false, bool SCALAR = false>
 RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
   // the power-8 instantiations are only entered with sb->g.power == 8.0f: the literal (an inline constant of the multiplies)
   // instead of a scalar-register operand, which halves a VALU instruction's issue rate (profiles/r03_c_valu_microbench.md)
@@ -168,7 +173,11 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
   V4 trap = v4(fabs_(w.x), fabs_(w.y), fabs_(w.z), m);
   float dz = 1.0f;
   const V3 c = NOJULIA ? pos : (julia ? v3(sb->g.juliaSeed[0], sb->g.juliaSeed[1], 0.0f) : pos);
-  for (int i = 0; i < iters; i++) {
+  // SCALAR: the trip count in a scalar register.  Written `i < iters` beside the divergent bailout, the compiler counts the
+  // trips down in a per-lane register whose borrow is the exit's lane mask — a VOP3 subtract with a scalar-register pair, half
+  // rate, in every iteration — though the count is the same number on every lane; with the signed count-down it keeps the
+  // counter and its compare on the scalar unit.  The same trips either way: `left` is iters − i.
+  for (int i = 0, left = iters; SCALAR ? left > 0 : i < iters; i++, left--) {
     if (COUNT) cnt.iters++;
     // ONE range check per iteration for its square root and its two reciprocals (trigonometric forms), built from
     // mx = max(|w.x|, |w.z|) — atan2's divisor, computed once for both — and m < inf.  Every lane with 2^-48 <= mx, m < inf:
@@ -185,14 +194,18 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
     // that is not on it: the same bits, and no more often than such points occur.
     const float mx = absmax_(w.x, w.z);
     const bool raw = (MODE != BULB_ALGEBRAIC8) && __ballot(!(mx >= 3.5527136788e-15f) || !(m < __builtin_inff())) == 0;
-    // the iteration's arithmetic, instantiated twice: RAW (unguarded fast forms) and guarded — a wave-uniform branch
+    // the iteration's arithmetic, instantiated twice: RAW (unguarded fast forms) and guarded — a wave-uniform branch.
+    // SCALAR: dz's update (frag:787) is written once behind the two forms, which hand over its factor: the same fma on the same
+    // operands, and the new dz needs no copy where the forms join.
+    float dzFactor = 0.0f;
     auto step = [&](auto rawTag) __attribute__((always_inline)) {
       constexpr bool RAW = decltype(rawTag)::value;
       float r = RAW ? sqrt_noscale_(m) : sqrt_fast_(m);  // frag:789
       if (MODE == BULB_ALGEBRAIC8) {
         // (y + iρ)^8 = r^8·(cos 8θ + i sin 8θ), ((z + ix)/ρ)^8 = cos 8φ + i sin 8φ by three complex squarings each,
         // m^3.5 = m³·√m — no acos/atan/sin/cos/pow in the loop
-        dz = fma(8.0f * (((m * m) * m) * r), dz, 1.0f);
+        if constexpr (SCALAR) dzFactor = 8.0f * (((m * m) * m) * r);
+        else dz = fma(8.0f * (((m * m) * m) * r), dz, 1.0f);
         float rho = sqrt_fast_(dot2(w.x, w.z, w.x, w.z));
         float inv = rcp_(rho);
         float cz = (rho == 0.0f) ? 1.0f : w.z * inv, sx = (rho == 0.0f) ? 0.0f : w.x * inv;
@@ -217,7 +230,8 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
           pm = powApply(m, pexp, planPexp);
           pr = powApply(r, power, planPower);
         }
-        dz = fma(power * pm, dz, 1.0f);       // frag:787
+        if constexpr (SCALAR) dzFactor = power * pm;
+        else dz = fma(power * pm, dz, 1.0f);  // frag:787
         float b = power * acos_(RAW ? w.y * rcp_raw_(r) : divr_(w.y, r));  // frag:790
         float a = power * atan2_mx_<RAW>(w.x, w.z, mx);                     // frag:791
         float sb_, cb_, sa_, ca_;
@@ -227,6 +241,7 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
       }
     };
     if (raw) step(std::true_type{}); else step(std::false_type{});
+    if constexpr (SCALAR) dz = fma(dzFactor, dz, 1.0f);
     if (TRAP) {  // trap.x is never read (resColor below)
       if (TRAPMIN) trap = v4(trap.x, hwmin_abs_(trap.y, w.y), hwmin_abs_(trap.z, w.z), hwmin_(trap.w, m));
       else trap = v4(trap.x, min_(trap.y, fabs_(w.y)), min_(trap.z, fabs_(w.z)), min_(trap.w, m));
@@ -253,11 +268,12 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
   return divr_((0.25f * log_(m)) * sqrt_fast_(m), dz);  // frag:802
 }
 // PLAIN (SceneBlock::bulbPlain: power 8, no Julia seed): only the two power-8 forms, without the Julia select.
-template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false, bool FUSE = false>
+// SCALAR: bulbIterate's, handed through to the power-8 forms.
+template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false, bool FUSE = false, bool SCALAR = false>
 RM_DEV float sdMandelBulb(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
   if (PLAIN || sb->g.power == 8.0f) {  // wave-uniform
-    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN, FUSE>(sb, pos, resColor, cnt);
-    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN, FUSE>(sb, pos, resColor, cnt);
+    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN, FUSE, SCALAR>(sb, pos, resColor, cnt);
+    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN, FUSE, SCALAR>(sb, pos, resColor, cnt);
   }
   return bulbIterate<COUNT, BULB_GENERIC, TRAPMIN, TRAP>(sb, pos, resColor, cnt);  // the generic power keeps the guarded forms
 }
@@ -380,7 +396,8 @@ RM_DEV float sdMengerSponge(const SceneBlock *sb, V3 p, V4 &res) {
 // TRACK (with SKIP): also return in `second` a lower bound of every OTHER object's value at p — the runner-up of the minimum:
 // the values of the objects evaluated, and (|p_object|·(1 − ε) − boundR)·scaleFactor for the ones passed over.  The march
 // loops use it for the single-object fast path (sdSceneOne below).
-template <int BULB, int COUNT, int TRAP, bool SKIP, bool TRACK>  // TRAP: 0 none, 1 the shader's, 2 the sponge's .z alone (mengerImpl)
+// SCALAR (bulb classes): sdMandelBulb's, handed through.
+template <int BULB, int COUNT, int TRAP, bool SKIP, bool TRACK, bool SCALAR = false>  // TRAP: 0 none, 1 the shader's, 2 the sponge's .z alone (mengerImpl)
 RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub, float &second) {
   SceneMin res;
   if (TRACK) second = __builtin_inff();
@@ -455,7 +472,7 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
       case RM_DEATHSTAR: d = sdDeathStar(po, 0.5f, 0.35f, 0.5f); break;
       case RM_RECTANGLE: d = sdBox(po, 0.5f, 0.5f, 0.0f); break;
       case RM_MANDELBROT: d = sdMandelBrot(sb, po.x, po.y); break;
-      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain, BULB != 0>(sb, po, res.trap, cnt); break;
+      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain, BULB != 0, SCALAR>(sb, po, res.trap, cnt); break;
       case RM_MENGERSPONGE: d = sdMengerSponge<TRAP>(sb, po, res.trap); break;
       case RM_SIERPINSKI: d = sdSierpinski(po); break;
       default: continue;
@@ -471,11 +488,17 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
   }
   return res;
 }
-template <int BULB, int COUNT, int TRAP = 1, bool SKIP = false>
+template <int BULB, int COUNT, int TRAP = 1, bool SKIP = false, bool SCALAR = false>
 RM_DEV SceneMin sdScene(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
   float unused;
-  return sdSceneImpl<BULB, COUNT, TRAP, SKIP, false>(sb, p, cnt, ub, unused);
+  return sdSceneImpl<BULB, COUNT, TRAP, SKIP, false, SCALAR>(sb, p, cnt, ub, unused);
 }
+// Who takes bulbIterate's SCALAR form: the evaluations on the pooled path of the plain class's kernels that take PREP — the
+// primary march, the normal's taps, the shared first shadow step and the pool's loop, which is where the headline frame spends its
+// time.  Every other evaluation (the general class, secondary rays, shadowQueue, the AO taps, the kernels that hold several
+// samples' or frames' state across the pool) keeps the loop it had, and with it its kernel's code and register report.
+template <int BULB, bool PREP>
+constexpr bool kBulbScalarLoop = BULB == kBulbPlain && PREP && RM_X_SCALAR_LOOP != 0;
 // One object of the table alone (wave-uniform index j, a primitive): what sdScene returns when every other object is known to
 // be farther than the minimum (see march()).
 template <int COUNT>
@@ -516,7 +539,7 @@ RM_DEV float nextMinBound(float d, float lipLen, float depth) {
 
 // frag:1436-1444
 // ub: an upper bound of sdScene at p + any tap (the taps are 0.0005 from p), +inf = none; SKIP as in sdScene.
-template <int BULB, int COUNT, bool SKIP = false>
+template <int BULB, int COUNT, bool SKIP = false, bool SCALAR = false>  // SCALAR: sdScene's
 RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
   const float ex = (1.0f * 0.5773f) * 0.0005f, ey = (-1.0f * 0.5773f) * 0.0005f;
   float d[4];
@@ -526,7 +549,7 @@ RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __buil
     float ox = (k == 0 || k == 3) ? ex : ey;
     float oy = (k >= 2) ? ex : ey;
     float oz = (k == 1 || k == 3) ? ex : ey;
-    float v = sdScene<BULB, COUNT, false, SKIP>(sb, v3(p.x + ox, p.y + oy, p.z + oz), cnt, ub).d;
+    float v = sdScene<BULB, COUNT, false, SKIP, SCALAR>(sb, v3(p.x + ox, p.y + oy, p.z + oz), cnt, ub).d;
     d[0] = (k == 0) ? v : d[0];
     d[1] = (k == 1) ? v : d[1];
     d[2] = (k == 2) ? v : d[2];
@@ -666,7 +689,7 @@ RM_DEV float sceneCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end, float R
   return min_(end, tExit);
 }
 // ub0: an upper bound of sdScene at ro (+inf = none), for the first evaluation's skip test.
-template <int BULB, int COUNT, bool SHADOW, bool CULL = false>
+template <int BULB, int COUNT, bool SHADOW, bool CULL = false, bool SCALAR = false>  // SCALAR: sdSceneImpl's, in the bulb branch
 RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side, Counters &cnt, float ub0 = __builtin_inff()) {
   bool own = false;  // this lane's `end` is the bulb cull's own t_exit (bulbCullEnd)
   if (CULL && COUNT != 1) {
@@ -712,7 +735,7 @@ RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side,
       constexpr bool PRE = decltype(preTag)::value;
       for (int i = 0; i < steps; i++) {
         if (PRE && depth > end) break;
-        c = sdSceneImpl<BULB, COUNT, !SHADOW, false, false>(sb, madd(rd, depth, ro), cnt, ub, second);
+        c = sdSceneImpl<BULB, COUNT, !SHADOW, false, false, SCALAR>(sb, madd(rd, depth, ro), cnt, ub, second);
         if (fabs_(c.d) < kSurfaceDist || (!PRE && depth > end)) break;
         if (SHADOW) {
           if (soft) pen = min_(pen, divr_(8.0f * c.d, depth));
@@ -1268,7 +1291,7 @@ RM_DEV float *poolLightTable() {
   __shared__ __attribute__((aligned(16))) float s_prep[RM_MAX_LIGHTS * 8];
   return s_prep;
 }
-template <int BULB, int COUNT, bool PREP = false>
+template <int BULB, int COUNT, bool PREP = false, bool SCALAR = false>  // SCALAR: sdScene's
 RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dStart, float far, Counters &cnt) {
   __shared__ uint16_t s_list[kPoolWaves][kPoolList];
   __shared__ uint32_t s_hits[kPoolWaves][32];
@@ -1351,7 +1374,7 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
       pre = pre && __ballot(!endOwn) == 0ull;
     }
     if (cur >= 0) {
-      const SceneMin c = sdScene<BULB, COUNT, false>(sb, madd(L, depth, o), cnt);
+      const SceneMin c = sdScene<BULB, COUNT, false, false, SCALAR>(sb, madd(L, depth, o), cnt);
       const bool hit = fabs_(c.d) < kSurfaceDist;
       bool fin;
       if (pre) {  // scalar branch
@@ -1400,6 +1423,7 @@ template <int BULB, int COUNT, bool SHARE, bool PREP>
 RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, const MarchRes &res, Hit &info,
                               float maxT, V3 bg, Counters &cnt) {
   constexpr bool PREP_B = PREP && (RM_X_PREP_PARTS & 1) != 0, PREP_AC = PREP && (RM_X_PREP_PARTS & 2) != 0;
+  constexpr bool SCALAR = kBulbScalarLoop<BULB, PREP>;
   const bool surf = res.obj != -1;
   const int nl = sb->numLights;
   V3 p = v3(0.0f, 0.0f, 0.0f), N = p, so = p;
@@ -1408,7 +1432,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
   if (surf) {
     if (COUNT) cnt.shades++;
     p = madd(rd, res.d, ro);
-    N = getNormal<BULB, COUNT>(sb, p, cnt);
+    N = getNormal<BULB, COUNT, false, SCALAR>(sb, p, cnt);
     if (sb->s.features & RM_FEAT_PERLIN_BUMP) N = SHARE ? bumpNormalShared(N, p) : bumpNormal(N, p);
     if (sb->s.enableAmbientOcclusion) ao = calcAO<BULB, COUNT>(sb, p, N, cnt);
     so = shadowOrigin(p, N);
@@ -1425,13 +1449,13 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
       if (!shared) {
         pend = need;
       } else {
-        const float d0 = fabs_(sdScene<BULB, COUNT, false>(sb, so, cnt).d);
+        const float d0 = fabs_(sdScene<BULB, COUNT, false, false, SCALAR>(sb, so, cnt).d);
         if (d0 < kSurfaceDist) hits = need;                 // every ray hits on its first evaluation
         else if (maxSteps > 1) { pend = need; dStart = d0; }  // else every ray's loop runs out after it: a miss
       }
     }
   }
-  const uint32_t hitMask = hits | shadowPool<BULB, COUNT, PREP_B>(sb, so, pend, dStart, maxT, cnt);
+  const uint32_t hitMask = hits | shadowPool<BULB, COUNT, PREP_B, SCALAR>(sb, so, pend, dStart, maxT, cnt);
   RenderOut out;
   if (!surf) {
     out.col = bg;
@@ -1474,7 +1498,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
     const float *q = split.slot + 2 * sb->numLights;
     res.obj = __float_as_int(q[0]); res.d = q[1]; res.trap = v4(q[2], q[3], q[4], q[5]);
   } else {
-    res = march<BULB, COUNT, false, CULLS>(sb, ro, rd, maxT, side, cnt);  // a miss returns maxT, not res.d
+    res = march<BULB, COUNT, false, CULLS, POOL && kBulbScalarLoop<BULB, PREP>>(sb, ro, rd, maxT, side, cnt);  // a miss returns maxT, not res.d
     if (SPLIT == 1 && split.part == 0) {
       float *q = split.slot + 2 * sb->numLights;
       q[0] = __int_as_float(res.obj); q[1] = res.d; q[2] = res.trap.x; q[3] = res.trap.y; q[4] = res.trap.z; q[5] = res.trap.w;

@@ -29,7 +29,7 @@ def main():
     t = scenes.mandelbulb(a.W, a.H)
     s = abi.default_settings(fractalIters=a.iters)
     out = (C.c_double * 5)()
-    cost = (C.c_double * 6)(148, 75, 156, 90, 60, 1700)
+    cost = (C.c_double * 6)(146, 69, 156, 90, 60, 1700)  # run_wave_sim.py's defaults
     st = sim.sim_sorted(C.byref(t.camera), t.objects, t.num_objects, t.lights, t.num_lights, C.byref(t.globals_), C.byref(s),
                         a.W, a.H, a.stride, C.c_float(1.15), cost, out, len(os.sched_getaffinity(0)))
     assert st == 0
