@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
     V4 col, br;
     Counters cnt{0, 0, 0, 0, 0, 0};
     bool hit;
-    shadePixel<BULB, 0, ENV, TEX, SEC, 0, false, false>(sb + j, s_objs, x, y, W, H, col, br, cnt, hit);
+    shadePixel<BULB, 0, optClass(ENV, TEX, SEC)>(sb + j, s_objs, x, y, W, H, col, br, cnt, hit);
     acc[0] += col.x; acc[1] += col.y; acc[2] += col.z; acc[3] += col.w;
     acc[4] += br.x; acc[5] += br.y; acc[6] += br.z; acc[7] += br.w;
   }

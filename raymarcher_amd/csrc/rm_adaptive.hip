@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void adapti
     V4 col, br;
     Counters cnt{0, 0, 0, 0, 0, 0};
     bool hit;
-    shadePixel<BULB, 0, ENV, TEX, SEC, 0, false, false>(sb, s_objs, X * ss + si, Y * ss + sj, sW, sH, col, br, cnt, hit);
+    shadePixel<BULB, 0, optClass(ENV, TEX, SEC)>(sb, s_objs, X * ss + si, Y * ss + sj, sW, sH, col, br, cnt, hit);
     float v[8] = {col.x, col.y, col.z, col.w, br.x, br.y, br.z, br.w};
     reduceLevel<1>(v);               // lanes ^ 1, ^ 8: the 2×2 blocks of the samples
     if (ss == 4) reduceLevel<2>(v);  // wave-uniform; lanes ^ 2, ^ 16: the 2×2 blocks of the first level's result

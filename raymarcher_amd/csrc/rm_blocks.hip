@@ -25,7 +25,7 @@ namespace rm {
 // profiles/sdf_blocks.md has the measurement.  A lane outside the 729 points is masked off before the evaluation, as the lanes of
 // sdf_grid_kernel past the lattice are: the evaluator's ballots are proofs about the lanes that are live, so a point's value does
 // not depend on which other points share its wave, and is rm_sdf_grid's for that lattice point — the same instantiation
-// sdSceneImpl<BULB, 0, 0, false, false> on the same point origin + (float)i · step.
+// sdSceneImpl<BULB, 0, kTrapNone> on the same point origin + (float)i · step.
 #ifndef RM_BLOCKS_MAP
 #define RM_BLOCKS_MAP 0
 #endif
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64 * kEvalWaves) void blocks_eval_kernel(const Scen
     const V3 p = v3(L.ox + fx, L.oy + fy, L.oz + fz);
     Counters cnt{0, 0, 0, 0, 0, 0};
     float unused;
-    const SceneMin m = sdSceneImpl<BULB, 0, 0, false, false>(sb, p, cnt, __builtin_inff(), unused);
+    const SceneMin m = sdSceneImpl<BULB, 0, kTrapNone>(sb, p, cnt, __builtin_inff(), unused);
     if (SELECT) {
       in = sn::inside(m.d, iso);
       out = !in;
@@ -186,9 +186,9 @@ static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 template <bool SELECT, class... Args>
 static void launch_eval(int bulbClass, dim3 grid, hipStream_t stream, Args... args) {
   const dim3 block(64 * kEvalWaves);
-  if (bulbClass == kBulbPlain) hipLaunchKernelGGL((blocks_eval_kernel<kBulbPlain, SELECT>), grid, block, 0, stream, args...);
-  else if (bulbClass == kBulbGeneral) hipLaunchKernelGGL((blocks_eval_kernel<kBulbGeneral, SELECT>), grid, block, 0, stream, args...);
-  else hipLaunchKernelGGL((blocks_eval_kernel<0, SELECT>), grid, block, 0, stream, args...);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    hipLaunchKernelGGL((blocks_eval_kernel<decltype(c)::bulb, SELECT>), grid, block, 0, stream, args...);
+  });
 }
 
 size_t blocks_select_workspace(int mx, int my, int mz) {

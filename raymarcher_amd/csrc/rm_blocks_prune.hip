@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void prune_corners_kernel(const SceneBlock *__
   const V3 p = v3(L.ox + fx, L.oy + fy, L.oz + fz);
   Counters cnt{0, 0, 0, 0, 0, 0};
   float unused;
-  corners[q] = sdSceneImpl<BULB, 0, 0, false, false>(sb, p, cnt, __builtin_inff(), unused).d;
+  corners[q] = sdSceneImpl<BULB, 0, kTrapNone>(sb, p, cnt, __builtin_inff(), unused).d;
 }
 
 // ---- 2. the classification ------------------------------------------------------------------------------------------------------
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64 * kEvalWaves) void prune_eval_kernel(const Scene
       const V3 p = v3(L.ox + fx, L.oy + fy, L.oz + fz);
       Counters cnt{0, 0, 0, 0, 0, 0};
       float unused;
-      const SceneMin m = sdSceneImpl<BULB, 0, 0, false, false>(sb, p, cnt, __builtin_inff(), unused);
+      const SceneMin m = sdSceneImpl<BULB, 0, kTrapNone>(sb, p, cnt, __builtin_inff(), unused);
       in = sn::inside(m.d, iso);
       out = !in;
     }
@@ -127,18 +127,16 @@ int launch_blocks_prune_kernels(const void *sbv, int bulbClass, const float orig
   // the candidates' workgroups: a few per CU, so that a slow block holds up few others, and never more than there are blocks
   const size_t evalGroups = (size_t)(numCUs > 0 ? numCUs : 256) * 4;
   const dim3 evalGrid((unsigned)(blocks < evalGroups ? blocks : evalGroups)), evalBlock(64 * kEvalWaves);
-  auto go = [&](auto cornersKernel, auto evalKernel) {
-    hipLaunchKernelGGL(cornersKernel, cornerGrid, dim3(256), 0, stream, sb, L, numCorners, corners);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    constexpr int BULB = decltype(c)::bulb;
+    hipLaunchKernelGGL(prune_corners_kernel<BULB>, cornerGrid, dim3(256), 0, stream, sb, L, numCorners, corners);
     hipLaunchKernelGGL(prune_classify_kernel, blockGrid, dim3(256), 0, stream, (const float *)corners, mx, my, blocks, iso, bounds, flags);
     enqueue_flags_count(flags, blocks, off, d_count + 1, stream);  // the candidates' number: off[shares] and d_count[1]
     hipLaunchKernelGGL(prune_candidates_kernel, dim3((unsigned)shares), dim3(64), 0, stream, (const uint32_t *)flags, blocks,
                        (const unsigned long long *)off, list);
-    hipLaunchKernelGGL(evalKernel, evalGrid, evalBlock, 0, stream, sb, L, iso, (const uint32_t *)list, (const unsigned long long *)(off + shares),
-                       flags);
-  };
-  if (bulbClass == kBulbPlain) go(prune_corners_kernel<kBulbPlain>, prune_eval_kernel<kBulbPlain>);
-  else if (bulbClass == kBulbGeneral) go(prune_corners_kernel<kBulbGeneral>, prune_eval_kernel<kBulbGeneral>);
-  else go(prune_corners_kernel<0>, prune_eval_kernel<0>);
+    hipLaunchKernelGGL(prune_eval_kernel<BULB>, evalGrid, evalBlock, 0, stream, sb, L, iso, (const uint32_t *)list,
+                       (const unsigned long long *)(off + shares), flags);
+  });
   // the flags are the active flags now (a discarded block's is still 0): rm_sdf_blocks_select's compaction
   enqueue_flags_count(flags, blocks, off, d_count, stream);
   if (maxBlocks > 0) enqueue_flags_emit(flags, blocks, mx, my, off, maxBlocks, d_blocks, stream);

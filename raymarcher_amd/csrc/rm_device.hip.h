@@ -48,6 +48,44 @@ RM_DEV V3 mix(V3 a, V3 b, float t) { return v3(mix_(a.x, b.x, t), mix_(a.y, b.y,
 
 constexpr float kSurfaceDist = 0.001f;  // frag:32
 
+// ---- template options -----------------------------------------------------------------------------------
+// The device function templates below take BULB and COUNT (bulbIterate: COUNT and MODE) and then ONE set of these bits, O.  A set
+// bit turns something on; what each one means is told at the function that reads it.  Every template static_asserts that O holds
+// only bits it understands (optOnly), reads them back into the constexpr names its body uses, and hands options down by masking:
+// sdScene<BULB, COUNT, O & (kSkip | kScalar)>.  A kernel spells the set from its own parameters with optIf / optTrap / optSplit.
+enum Opt : unsigned {
+  kShadow = 1u << 0,    // march: a shadow march (the penumbra factor instead of the distance, no orbit trap)
+  kCull = 1u << 1,      // march, shadowQueue, getPhong, render: marches end at the scene's bounds, the table walk skips far objects
+  kScalar = 1u << 2,    // bulbIterate … march, getNormal, shadowPool: the iteration loop's trip count on the scalar unit
+  kSkip = 1u << 3,      // sdSceneImpl, sdScene, getNormal, calcAO: pass over objects whose bounding ball is out of reach
+  kTrack = 1u << 4,     // sdSceneImpl: also return the runner-up of the minimum
+  kTex = 1u << 5,       // render, shadePixel, shadeRay: textures, sky box, area lights
+  kEnv = 1u << 6,       // shadePixel, shadeRay: the procedural layers
+  kSec = 1u << 7,       // shadePixel, shadeRay: secondary rays
+  kRay = 1u << 8,       // shadePixel: the caller's ray instead of a pixel's
+  kPool = 1u << 9,      // render: the wave's shadow pool (renderPooled)
+  kShareBump = 1u << 10,  // renderPooled, render, shadePixel: the bump's four samples from one lattice
+  kPrep = 1u << 11,     // shadowPool, renderPooled, render, shadePixel: the lights' prepared constants
+  kRes = 1u << 12,      // getPhong: the area-light branch
+  kTrapMin = 1u << 13,  // bulbIterate, sdMandelBulb: the orbit-trap minima in their one-instruction form
+  kPlain = 1u << 14,    // bulbIterate, sdMandelBulb: power 8 and no Julia seed (SceneBlock::bulbPlain)
+  kFuse = 1u << 15,     // bulbIterate, sdMandelBulb: one range guard for the estimate
+  // the orbit trap, a two-bit field (bulbIterate … sdScene): none / the shader's vec4 / the sponge's .z alone (mengerImpl)
+  kTrapShift = 16, kTrapNone = 0u, kTrapShader = 1u << kTrapShift, kTrapZ = 2u << kTrapShift, kTrapMask = 3u << kTrapShift,
+  // the light split, a two-bit field (getPhong, render, shadePixel, shadeRay; see LightSplit): none / a tile's partial workgroup /
+  // the workgroup that finishes the tile
+  kSplitShift = 18, kSplitNone = 0u, kSplitPart = 1u << kSplitShift, kSplitFinish = 2u << kSplitShift, kSplitMask = 3u << kSplitShift,
+};
+constexpr unsigned optIf(bool on, unsigned bits) { return on ? bits : 0u; }
+// the two fields to and from the numbers 0 / 1 / 2 that the kernels' own TRAP and SPLIT parameters and the bodies below use
+constexpr unsigned optTrap(int trap) { return (unsigned)trap << kTrapShift; }
+constexpr unsigned optSplit(int split) { return (unsigned)split << kSplitShift; }
+constexpr int trapOf(unsigned o) { return (int)((o & kTrapMask) >> kTrapShift); }
+constexpr int splitOf(unsigned o) { return (int)((o & kSplitMask) >> kSplitShift); }
+constexpr bool optOnly(unsigned o, unsigned known) { return (o & ~known) == 0u; }
+// the three flags of a render class (KernelClass, rm_internal.h) as shadePixel / shadeRay take them
+constexpr unsigned optClass(bool env, bool tex, bool sec) { return optIf(env, kEnv) | optIf(tex, kTex) | optIf(sec, kSec); }
+
 // Per-lane work counters (only live in the counting instantiations; where nothing reads them the increments are dead code).
 // COUNT is a mode: 0 = no counters (production), 1 = count the REFERENCE's work (no bounding-ball culls, shadow rays of
 // dropped lights still marched — the algorithmic figure of the roofline), 2 = count the work the production kernel really
@@ -156,8 +194,11 @@ enum BulbMode { BULB_GENERIC = 0, BULB_TRIG8 = 1, BULB_ALGEBRAIC8 = 2 };
 #ifndef RM_X_SCALAR_LOOP
 #define RM_X_SCALAR_LOOP 1
 #endif
-template <int COUNT, int MODE, bool TRAPMIN, bool TRAP, bool NOJULIA = false, bool FUSE = false, bool SCALAR = false>
+template <int COUNT, int MODE, unsigned O>
 RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
+  static_assert(optOnly(O, kTrapMin | kTrapMask | kPlain | kFuse | kScalar), "bulbIterate: an option it does not take");
+  constexpr bool TRAPMIN = (O & kTrapMin) != 0, TRAP = (O & kTrapMask) != kTrapNone, NOJULIA = (O & kPlain) != 0;
+  constexpr bool FUSE = (O & kFuse) != 0, SCALAR = (O & kScalar) != 0;
   // the power-8 instantiations are only entered with sb->g.power == 8.0f: the literal (an inline constant of the multiplies)
   // instead of a scalar-register operand, which halves a VALU instruction's issue rate (profiles/r03_c_valu_microbench.md)
   const float power = (MODE == BULB_GENERIC) ? sb->g.power : 8.0f;
@@ -269,13 +310,15 @@ RM_DEV float bulbIterate(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &c
 }
 // PLAIN (SceneBlock::bulbPlain: power 8, no Julia seed): only the two power-8 forms, without the Julia select.
 // SCALAR: bulbIterate's, handed through to the power-8 forms.
-template <int COUNT, bool TRAPMIN, bool TRAP, bool PLAIN = false, bool FUSE = false, bool SCALAR = false>
+template <int COUNT, unsigned O>
 RM_DEV float sdMandelBulb(const SceneBlock *sb, V3 pos, V4 &resColor, Counters &cnt) {
+  static_assert(optOnly(O, kTrapMin | kTrapMask | kPlain | kFuse | kScalar), "sdMandelBulb: an option it does not take");
+  constexpr bool PLAIN = (O & kPlain) != 0;
   if (PLAIN || sb->g.power == 8.0f) {  // wave-uniform
-    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, TRAPMIN, TRAP, PLAIN, FUSE, SCALAR>(sb, pos, resColor, cnt);
-    return bulbIterate<COUNT, BULB_TRIG8, TRAPMIN, TRAP, PLAIN, FUSE, SCALAR>(sb, pos, resColor, cnt);
+    if (sb->s.features & RM_FEAT_BULB_POWER8_ALGEBRAIC) return bulbIterate<COUNT, BULB_ALGEBRAIC8, O>(sb, pos, resColor, cnt);
+    return bulbIterate<COUNT, BULB_TRIG8, O>(sb, pos, resColor, cnt);
   }
-  return bulbIterate<COUNT, BULB_GENERIC, TRAPMIN, TRAP>(sb, pos, resColor, cnt);  // the generic power keeps the guarded forms
+  return bulbIterate<COUNT, BULB_GENERIC, O & (kTrapMin | kTrapMask)>(sb, pos, resColor, cnt);  // the generic power keeps the guarded forms
 }
 
 // frag:808-827
@@ -397,8 +440,11 @@ RM_DEV float sdMengerSponge(const SceneBlock *sb, V3 p, V4 &res) {
 // the values of the objects evaluated, and (|p_object|·(1 − ε) − boundR)·scaleFactor for the ones passed over.  The march
 // loops use it for the single-object fast path (sdSceneOne below).
 // SCALAR (bulb classes): sdMandelBulb's, handed through.
-template <int BULB, int COUNT, int TRAP, bool SKIP, bool TRACK, bool SCALAR = false>  // TRAP: 0 none, 1 the shader's, 2 the sponge's .z alone (mengerImpl)
+template <int BULB, int COUNT, unsigned O>  // the trap field: kTrapNone, kTrapShader, kTrapZ — the sponge's .z alone (mengerImpl)
 RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub, float &second) {
+  static_assert(optOnly(O, kTrapMask | kSkip | kTrack | kScalar), "sdSceneImpl: an option it does not take");
+  constexpr int TRAP = trapOf(O);  // mengerImpl's 0 / 1 / 2
+  constexpr bool SKIP = (O & kSkip) != 0, TRACK = (O & kTrack) != 0;
   SceneMin res;
   if (TRACK) second = __builtin_inff();
   res.d = 1000000.0f;
@@ -472,7 +518,10 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
       case RM_DEATHSTAR: d = sdDeathStar(po, 0.5f, 0.35f, 0.5f); break;
       case RM_RECTANGLE: d = sdBox(po, 0.5f, 0.5f, 0.0f); break;
       case RM_MANDELBROT: d = sdMandelBrot(sb, po.x, po.y); break;
-      case RM_MANDELBULB: d = sdMandelBulb<COUNT, BULB && COUNT == 0, TRAP != 0, BULB == kBulbPlain, BULB != 0, SCALAR>(sb, po, res.trap, cnt); break;
+      case RM_MANDELBULB:
+        d = sdMandelBulb<COUNT, (O & (kTrapMask | kScalar)) | optIf(BULB && COUNT == 0, kTrapMin) | optIf(BULB == kBulbPlain, kPlain) |
+                                    optIf(BULB != 0, kFuse)>(sb, po, res.trap, cnt);
+        break;
       case RM_MENGERSPONGE: d = sdMengerSponge<TRAP>(sb, po, res.trap); break;
       case RM_SIERPINSKI: d = sdSierpinski(po); break;
       default: continue;
@@ -488,12 +537,13 @@ RM_DEV SceneMin sdSceneImpl(const SceneBlock *sb, V3 p, Counters &cnt, float ub,
   }
   return res;
 }
-template <int BULB, int COUNT, int TRAP = 1, bool SKIP = false, bool SCALAR = false>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV SceneMin sdScene(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
+  static_assert(optOnly(O, kTrapMask | kSkip | kScalar), "sdScene: an option it does not take");
   float unused;
-  return sdSceneImpl<BULB, COUNT, TRAP, SKIP, false, SCALAR>(sb, p, cnt, ub, unused);
+  return sdSceneImpl<BULB, COUNT, O>(sb, p, cnt, ub, unused);
 }
-// Who takes bulbIterate's SCALAR form: the evaluations on the pooled path of the plain class's kernels that take PREP — the
+// Who takes kScalar, bulbIterate's SCALAR form: the evaluations on the pooled path of the plain class's kernels that take kPrep — the
 // primary march, the normal's taps, the shared first shadow step and the pool's loop, which is where the headline frame spends its
 // time.  Every other evaluation (the general class, secondary rays, shadowQueue, the AO taps, the kernels that hold several
 // samples' or frames' state across the pool) keeps the loop it had, and with it its kernel's code and register report.
@@ -539,8 +589,9 @@ RM_DEV float nextMinBound(float d, float lipLen, float depth) {
 
 // frag:1436-1444
 // ub: an upper bound of sdScene at p + any tap (the taps are 0.0005 from p), +inf = none; SKIP as in sdScene.
-template <int BULB, int COUNT, bool SKIP = false, bool SCALAR = false>  // SCALAR: sdScene's
+template <int BULB, int COUNT, unsigned O = 0>  // kScalar: sdScene's
 RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __builtin_inff()) {
+  static_assert(optOnly(O, kSkip | kScalar), "getNormal: an option it does not take");
   const float ex = (1.0f * 0.5773f) * 0.0005f, ey = (-1.0f * 0.5773f) * 0.0005f;
   float d[4];
 #pragma unroll 1
@@ -549,7 +600,7 @@ RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __buil
     float ox = (k == 0 || k == 3) ? ex : ey;
     float oy = (k >= 2) ? ex : ey;
     float oz = (k == 1 || k == 3) ? ex : ey;
-    float v = sdScene<BULB, COUNT, false, SKIP, SCALAR>(sb, v3(p.x + ox, p.y + oy, p.z + oz), cnt, ub).d;
+    float v = sdScene<BULB, COUNT, kTrapNone | O>(sb, v3(p.x + ox, p.y + oy, p.z + oz), cnt, ub).d;
     d[0] = (k == 0) ? v : d[0];
     d[1] = (k == 1) ? v : d[1];
     d[2] = (k == 2) ? v : d[2];
@@ -563,8 +614,8 @@ RM_DEV V3 getNormal(const SceneBlock *sb, V3 p, Counters &cnt, float ub = __buil
 }
 
 // frag:1453-1484 (side = +1 outside, −1 inside) and frag:1703-1725 (SHADOW) share one loop body.
-// SHADOW=false: returns obj, d = rayDepth − minD on a hit, rayDepth on a miss (contract UB2).
-// SHADOW=true : returns obj, d = penumbra factor res (contract UB1), k = 8, start depth 0.
+// without kShadow (SHADOW = false): returns obj, d = rayDepth − minD on a hit, rayDepth on a miss (contract UB2).
+// with kShadow (SHADOW = true): returns obj, d = penumbra factor res (contract UB1), k = 8, start depth 0.
 //
 // CULL (single-Mandelbulb class only; never in the reference-counted variant, COUNT == 1, whose counters are the reference's
 // work; the executed-counted and clocked variants follow production): a march
@@ -689,8 +740,11 @@ RM_DEV float sceneCullEnd(const SceneBlock *sb, V3 ro, V3 rd, float end, float R
   return min_(end, tExit);
 }
 // ub0: an upper bound of sdScene at ro (+inf = none), for the first evaluation's skip test.
-template <int BULB, int COUNT, bool SHADOW, bool CULL = false, bool SCALAR = false>  // SCALAR: sdSceneImpl's, in the bulb branch
+template <int BULB, int COUNT, unsigned O = 0>  // kScalar: sdSceneImpl's, in the bulb branch
 RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side, Counters &cnt, float ub0 = __builtin_inff()) {
+  static_assert(optOnly(O, kShadow | kCull | kScalar), "march: an option it does not take");
+  constexpr bool SHADOW = (O & kShadow) != 0, CULL = (O & kCull) != 0;
+  constexpr unsigned TRAP = SHADOW ? kTrapNone : kTrapShader;  // a shadow march reads no trap
   bool own = false;  // this lane's `end` is the bulb cull's own t_exit (bulbCullEnd)
   if (CULL && COUNT != 1) {
     const bool softRay = SHADOW && sb->s.enableSoftShadow != 0;  // wave-uniform
@@ -735,7 +789,7 @@ RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side,
       constexpr bool PRE = decltype(preTag)::value;
       for (int i = 0; i < steps; i++) {
         if (PRE && depth > end) break;
-        c = sdSceneImpl<BULB, COUNT, !SHADOW, false, false, SCALAR>(sb, madd(rd, depth, ro), cnt, ub, second);
+        c = sdSceneImpl<BULB, COUNT, TRAP | (O & kScalar)>(sb, madd(rd, depth, ro), cnt, ub, second);
         if (fabs_(c.d) < kSurfaceDist || (!PRE && depth > end)) break;
         if (SHADOW) {
           if (soft) pen = min_(pen, divr_(8.0f * c.d, depth));
@@ -757,7 +811,7 @@ RM_DEV MarchRes march(const SceneBlock *sb, V3 ro, V3 rd, float end, float side,
       one = sb->cullOneOk && __ballot(!(c.idx == nearU && nearU >= 0 && second > ub)) == 0ull;
     }
     if (SKIP && one) c = sdSceneOne<COUNT>(sb, nearU, p, cnt);
-    else c = sdSceneImpl<BULB, COUNT, !SHADOW, SKIP, SKIP>(sb, p, cnt, ub, second);
+    else c = sdSceneImpl<BULB, COUNT, TRAP | optIf(SKIP, kSkip | kTrack)>(sb, p, cnt, ub, second);
     if (fabs_(c.d) < kSurfaceDist || depth > end) break;
     if (SHADOW) {
       if (soft) pen = min_(pen, divr_(8.0f * c.d, depth));
@@ -920,13 +974,15 @@ RM_DEV V3 bumpNormalShared(V3 normal, V3 pos) {  // bumpNormal with bumpGradient
 // ---- shading --------------------------------------------------------------------------------------------
 // frag:1729-1740
 // ubPos: an upper bound of sdScene at pos (+inf = none); a tap lies h·|nor| from it.
-template <int BULB, int COUNT, bool SKIP = false>
+template <int BULB, int COUNT, unsigned O = 0>
 RM_DEV float calcAO(const SceneBlock *sb, V3 pos, V3 nor, Counters &cnt, float ubPos = __builtin_inff()) {
+  static_assert(optOnly(O, kSkip), "calcAO: an option it does not take");
+  constexpr bool SKIP = (O & kSkip) != 0;
   float occ = 0.0f, sca = 1.0f;
   const float lipN = SKIP ? (sb->cullLip * len(nor)) * 1.001f : 0.0f;
   for (int i = 0; i < 5; i++) {
     float h = 0.01f + ((0.12f * (float)i) / 4.0f);
-    float d = sdScene<BULB, COUNT, false, SKIP>(sb, madd(nor, h, pos), cnt, SKIP ? fma(h, lipN, ubPos) : ubPos).d;
+    float d = sdScene<BULB, COUNT, kTrapNone | O>(sb, madd(nor, h, pos), cnt, SKIP ? fma(h, lipN, ubPos) : ubPos).d;
     occ = fma(h - d, sca, occ);
     sca = sca * 0.95f;
     if (occ > 0.35f) break;
@@ -1111,12 +1167,14 @@ RM_DEV bool lightTerm(const RmLight &li, const LightGeom &g, const Material &mat
 // wave marches light 0's rays, then light 1's, …: every light costs the LONGEST of its rays, and lanes whose light is
 // dropped (N·L <= 0.005) idle through it.  Here every lane marches its own rays back to back — bit i of `need` = light i
 // wants a march — one evaluation per trip; a lane whose ray ends starts its next one in the same trip.  Each ray is the very
-// same sequence of evaluations as in march<…, SHADOW = true>: same origin, direction, cull end, step cap, hit test.
+// same sequence of evaluations as in march<…, kShadow>: same origin, direction, cull end, step cap, hit test.
 // Returns the mask of lights whose ray hit.  (The schedule simulators, scripts/sim/, price this at ×0.95 of the
 // instructions of the per-light loop on the bench frame and ×0.87 on the 8K Menger frame.)  It balances the rays within a lane
 // only: the primary rays of the bulb kernels without layers or textures pool them across the wave instead (shadowPool).
-template <int BULB, int COUNT, bool CULLS>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float far, Counters &cnt) {
+  static_assert(optOnly(O, kCull), "shadowQueue: an option it does not take");
+  constexpr bool CULLS = (O & kCull) != 0;
   const int maxSteps = sb->s.maxSteps;
   if (maxSteps <= 0) return 0u;  // march() then evaluates nothing and reports a miss
   uint32_t hitMask = 0u, rest = need;
@@ -1138,7 +1196,7 @@ RM_DEV uint32_t shadowQueue(const SceneBlock *sb, V3 so, uint32_t need, float fa
   nextRay();
   while (__ballot(cur >= 0) != 0ull) {
     if (cur >= 0) {
-      const SceneMin c = sdScene<BULB, COUNT, false>(sb, madd(L, depth, so), cnt);
+      const SceneMin c = sdScene<BULB, COUNT, kTrapNone>(sb, madd(L, depth, so), cnt);
       const bool hit = fabs_(c.d) < kSurfaceDist;
       bool fin = hit || depth > end;
       if (!fin) {
@@ -1183,14 +1241,17 @@ RM_DEV V3 hardLightSum(const SceneBlock *sb, const Material &mat, V3 N, V3 p, V3
 // CULLS: end marches at the scene's bounds and pass over far objects in the table walk (off in the ENV instantiations, whose
 // register budget it would break).
 // SPLIT (table-walk kernels without samplers or secondary rays only): see LightSplit.
-template <int BULB, int COUNT, bool RES, bool CULLS, int SPLIT = 0>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &mat, V3 N, V3 p, V3 rd, float far, Counters &cnt,
                    float ubPos = __builtin_inff(), LightSplit split = LightSplit{-1, nullptr, 0}) {
+  static_assert(optOnly(O, kRes | kCull | kSplitMask), "getPhong: an option it does not take");
+  constexpr bool RES = (O & kRes) != 0, CULLS = (O & kCull) != 0;
+  constexpr int SPLIT = splitOf(O);  // 0 none, 1 kSplitPart, 2 kSplitFinish
   constexpr bool SKIP = CULLS && !BULB && COUNT != 1;
   const bool partial = SPLIT == 1 && split.part >= 0;  // wave-uniform
   const float ka = sb->g.ka, ks = sb->g.ks;
   float ao = 1.0f;
-  if (sb->s.enableAmbientOcclusion && !partial) ao = calcAO<BULB, COUNT, SKIP>(sb, p, N, cnt, ubPos);
+  if (sb->s.enableAmbientOcclusion && !partial) ao = calcAO<BULB, COUNT, optIf(SKIP, kSkip)>(sb, p, N, cnt, ubPos);
   // the shadow rays start 0.005·|N| from p
   const float ubSo = SKIP ? fma(0.005f, (sb->cullLip * len(N)) * 1.001f, ubPos) : ubPos;
   V3 total = v3((mat.amb.x * ka) * ao, (mat.amb.y * ka) * ao, (mat.amb.z * ka) * ao);
@@ -1210,7 +1271,7 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
         const V3 L = normalize(v3(-li.dir[0], -li.dir[1], -li.dir[2]));
         if (!(dot(N, L) <= 0.005f)) need |= 1u << i;  // a light that N·L drops is not marched (see below)
       }
-      const uint32_t hitMask = shadowQueue<BULB, COUNT, CULLS>(sb, so, need, far, cnt);
+      const uint32_t hitMask = shadowQueue<BULB, COUNT, O & kCull>(sb, so, need, far, cnt);
       return hardLightSum(sb, mat, N, p, V, far, ks, hitMask, total);
     }
   }
@@ -1223,7 +1284,7 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
       V3 toL = sub(madd(side2, rd.y + 0.0f, madd(side1, rd.x + 0.0f, p1)), p);
       V3 L = normalize(toL);
       if (dot(N, L) <= 0.005f) continue;
-      MarchRes sh = march<BULB, COUNT, true, CULLS>(sb, so, L, len(toL), 1.0f, cnt, ubSo);
+      MarchRes sh = march<BULB, COUNT, kShadow | (O & kCull)>(sb, so, L, len(toL), 1.0f, cnt, ubSo);
       if (sh.obj != -1 && objs[sh.obj].lightIdx != i) continue;  // only the light's own rectangle may be "in the way"
       total = add(total, getAreaLight(sb, N, V, p, li, mat));
       continue;
@@ -1237,7 +1298,7 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
     const bool need = COUNT == 1 || !(dot(N, g.L) <= 0.005f);
     if (partial) {  // this workgroup's one light: the very march every other schedule runs for it; its result travels by memory
       if (i == split.part && need) {
-        sh = march<BULB, COUNT, true, CULLS>(sb, so, g.L, g.maxT, 1.0f, cnt, ubSo);
+        sh = march<BULB, COUNT, kShadow | (O & kCull)>(sb, so, g.L, g.maxT, 1.0f, cnt, ubSo);
         split.slot[2 * i] = __int_as_float(sh.obj);
         split.slot[2 * i + 1] = sh.d;
       }
@@ -1245,7 +1306,7 @@ RM_DEV V3 getPhong(const SceneBlock *sb, const RmObject *objs, const Material &m
     }
     if (need) {
       if (SPLIT == 2) { sh.obj = __float_as_int(split.slot[2 * i]); sh.d = split.slot[2 * i + 1]; }
-      else sh = march<BULB, COUNT, true, CULLS>(sb, so, g.L, g.maxT, 1.0f, cnt, ubSo);
+      else sh = march<BULB, COUNT, kShadow | (O & kCull)>(sb, so, g.L, g.maxT, 1.0f, cnt, ubSo);
     }
     V3 cur;
     if (lightTerm(li, g, mat, N, V, ks, sh.obj, sh.d, soft, cur)) total = add(total, cur);
@@ -1269,7 +1330,7 @@ RM_DEV V3 bulbTrapColor(float ty, float tz, float tw) {
 // takes the next unclaimed ray of any pixel, and the hit bit goes back to the pixel that owns the ray.  The list is
 // light-major (light 0's rays of every pixel, then light 1's, …): listed pixel-major, the first pixels' rays would start first
 // and the others' long rays would be left for the tail (an offline schedule simulation prices that above the queue).  Each ray is still the
-// very same sequence of evaluations as in march<…, SHADOW = true> — only the lane that computes it changes, and sdScene's
+// very same sequence of evaluations as in march<…, kShadow> — only the lane that computes it changes, and sdScene's
 // per-lane result does not depend on the other lanes (its wave-uniform choices are bit-neutral).
 //
 // Every lane of the wave that renders a pixel calls it, converged.  pend: the lights whose ray is still to march from `so`
@@ -1291,8 +1352,10 @@ RM_DEV float *poolLightTable() {
   __shared__ __attribute__((aligned(16))) float s_prep[RM_MAX_LIGHTS * 8];
   return s_prep;
 }
-template <int BULB, int COUNT, bool PREP = false, bool SCALAR = false>  // SCALAR: sdScene's
+template <int BULB, int COUNT, unsigned O = 0>  // kScalar: sdScene's
 RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dStart, float far, Counters &cnt) {
+  static_assert(optOnly(O, kPrep | kScalar), "shadowPool: an option it does not take");
+  constexpr bool PREP = (O & kPrep) != 0;
   __shared__ uint16_t s_list[kPoolWaves][kPoolList];
   __shared__ uint32_t s_hits[kPoolWaves][32];
   const int wave = (int)(threadIdx.x >> 6), lane = (int)__lane_id();
@@ -1374,7 +1437,7 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
       pre = pre && __ballot(!endOwn) == 0ull;
     }
     if (cur >= 0) {
-      const SceneMin c = sdScene<BULB, COUNT, false, false, SCALAR>(sb, madd(L, depth, o), cnt);
+      const SceneMin c = sdScene<BULB, COUNT, kTrapNone | (O & kScalar)>(sb, madd(L, depth, o), cnt);
       const bool hit = fabs_(c.d) < kSurfaceDist;
       bool fin;
       if (pre) {  // scalar branch
@@ -1419,9 +1482,11 @@ RM_DEV uint32_t shadowPool(const SceneBlock *sb, V3 so, uint32_t pend, float dSt
 #ifndef RM_X_PREP_PARTS
 #define RM_X_PREP_PARTS 3
 #endif
-template <int BULB, int COUNT, bool SHARE, bool PREP>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, const MarchRes &res, Hit &info,
                               float maxT, V3 bg, Counters &cnt) {
+  static_assert(optOnly(O, kShareBump | kPrep), "renderPooled: an option it does not take");
+  constexpr bool SHARE = (O & kShareBump) != 0, PREP = (O & kPrep) != 0;
   constexpr bool PREP_B = PREP && (RM_X_PREP_PARTS & 1) != 0, PREP_AC = PREP && (RM_X_PREP_PARTS & 2) != 0;
   constexpr bool SCALAR = kBulbScalarLoop<BULB, PREP>;
   const bool surf = res.obj != -1;
@@ -1432,7 +1497,7 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
   if (surf) {
     if (COUNT) cnt.shades++;
     p = madd(rd, res.d, ro);
-    N = getNormal<BULB, COUNT, false, SCALAR>(sb, p, cnt);
+    N = getNormal<BULB, COUNT, optIf(SCALAR, kScalar)>(sb, p, cnt);
     if (sb->s.features & RM_FEAT_PERLIN_BUMP) N = SHARE ? bumpNormalShared(N, p) : bumpNormal(N, p);
     if (sb->s.enableAmbientOcclusion) ao = calcAO<BULB, COUNT>(sb, p, N, cnt);
     so = shadowOrigin(p, N);
@@ -1449,13 +1514,13 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
       if (!shared) {
         pend = need;
       } else {
-        const float d0 = fabs_(sdScene<BULB, COUNT, false, false, SCALAR>(sb, so, cnt).d);
+        const float d0 = fabs_(sdScene<BULB, COUNT, kTrapNone | optIf(SCALAR, kScalar)>(sb, so, cnt).d);
         if (d0 < kSurfaceDist) hits = need;                 // every ray hits on its first evaluation
         else if (maxSteps > 1) { pend = need; dStart = d0; }  // else every ray's loop runs out after it: a miss
       }
     }
   }
-  const uint32_t hitMask = hits | shadowPool<BULB, COUNT, PREP_B, SCALAR>(sb, so, pend, dStart, maxT, cnt);
+  const uint32_t hitMask = hits | shadowPool<BULB, COUNT, optIf(PREP_B, kPrep) | optIf(SCALAR, kScalar)>(sb, so, pend, dStart, maxT, cnt);
   RenderOut out;
   if (!surf) {
     out.col = bg;
@@ -1485,9 +1550,12 @@ RM_DEV RenderOut renderPooled(const SceneBlock *sb, const RmObject *objs, V3 ro,
 // POOL (bulb kernels without procedural layers or textures, not counting the reference's work; the primary call of shadePixel,
 // which every lane of the wave that renders a pixel reaches): renderPooled takes the frames whose shadow rays the pool may
 // schedule.  The secondary rays' render() calls are divergent and keep getPhong's queue.
-template <int BULB, int COUNT, bool TEX, bool CULLS, int SPLIT = 0, bool POOL = false, bool SHARE = false, bool PREP = false>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, Hit &info, float side, float maxT,
                         V3 bg, Counters &cnt, LightSplit split = LightSplit{-1, nullptr, 0}) {
+  static_assert(optOnly(O, kTex | kCull | kSplitMask | kPool | kShareBump | kPrep), "render: an option it does not take");
+  constexpr bool TEX = (O & kTex) != 0, CULLS = (O & kCull) != 0, POOL = (O & kPool) != 0, PREP = (O & kPrep) != 0;
+  constexpr int SPLIT = splitOf(O);  // 0 none, 1 kSplitPart, 2 kSplitFinish
   RenderOut out;
   info.obj = -1;
   MarchRes res;
@@ -1498,13 +1566,13 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
     const float *q = split.slot + 2 * sb->numLights;
     res.obj = __float_as_int(q[0]); res.d = q[1]; res.trap = v4(q[2], q[3], q[4], q[5]);
   } else {
-    res = march<BULB, COUNT, false, CULLS, POOL && kBulbScalarLoop<BULB, PREP>>(sb, ro, rd, maxT, side, cnt);  // a miss returns maxT, not res.d
+    res = march<BULB, COUNT, (O & kCull) | optIf(POOL && kBulbScalarLoop<BULB, PREP>, kScalar)>(sb, ro, rd, maxT, side, cnt);  // a miss returns maxT, not res.d
     if (SPLIT == 1 && split.part == 0) {
       float *q = split.slot + 2 * sb->numLights;
       q[0] = __int_as_float(res.obj); q[1] = res.d; q[2] = res.trap.x; q[3] = res.trap.y; q[4] = res.trap.z; q[5] = res.trap.w;
     }
   }
-  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT, SHARE, PREP>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
+  if (POOL && hardDirectionalOnly(sb)) return renderPooled<BULB, COUNT, O & (kShareBump | kPrep)>(sb, objs, ro, rd, res, info, maxT, bg, cnt);
   if (res.obj == -1) {
     out.col = (TEX && sb->s.enableSkyBox) ? sampleCube(sb->skybox, rd) : bg;  // frag:2325-2327
     out.isEnv = 1;
@@ -1523,7 +1591,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
     const float lipLen = (sb->cullLip * len(rd)) * 1.0001f;
     ubP = fma(kSurfaceDist, lipLen, kSurfaceDist) * 1.001f + fma(fabs_(res.d), 1.0e-6f, 1.0e-5f);
   }
-  V3 pn = getNormal<BULB, COUNT, SKIP>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
+  V3 pn = getNormal<BULB, COUNT, optIf(SKIP, kSkip)>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
   if (sb->s.features & RM_FEAT_PERLIN_BUMP) pn = bumpNormal(pn, p);
   const RmObject &o = objs[BULB ? 0 : res.obj];
   if (TEX && o.isEmissive) {  // frag:2339-2342: the rectangle of an area light; info.obj stays -1
@@ -1536,7 +1604,7 @@ RM_DEV RenderOut render(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd
   mat.spec = v3(o.cSpecular[0], o.cSpecular[1], o.cSpecular[2]);
   mat.shininess = o.shininess;
   const int type = BULB ? (int)RM_MANDELBULB : o.type;
-  V3 ph = getPhong<BULB, COUNT, TEX, CULLS, SPLIT>(sb, objs, mat, pn, p, rd, maxT, cnt, ubP, split);
+  V3 ph = getPhong<BULB, COUNT, optIf(TEX, kRes) | (O & (kCull | kSplitMask))>(sb, objs, mat, pn, p, rd, maxT, cnt, ubP, split);
   V3 col = ph;
   if (type == RM_MANDELBULB) {  // frag:2354-2361
     V3 c = bulbTrapColor(res.trap.y, res.trap.z, res.trap.w);
@@ -1621,14 +1689,19 @@ RM_DEV V3 backgroundColor(const SceneBlock *sb, V3 rd) {  // frag:2405-2419
 // The pixel form is written so that its instantiations compile to what they did before the ray form existed: the code objects of
 // the render kernels are byte-identical.
 // SHARE = false keeps bumpNormal in the pooled surface phase (renderPooled): render_adaptive, render_acc and render_anim kernels.
-// PREP: the pool reads the lights' prepared constants (renderPooled, shadowPool).  It follows SHARE: render_anim_kernel must not
-// take it (shadowPool says why), and the other two kernels that hold several samples' or frames' state across the pool keep the
-// code their register reports were settled with.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0, bool RAY = false, bool SHARE = true,
-          bool PREP = SHARE>
+// PREP: the pool reads the lights' prepared constants (renderPooled, shadowPool).  The kernels that set kShareBump set kPrep too:
+// render_anim_kernel must not take it (shadowPool says why), and the other two kernels that hold several samples' or frames' state
+// across the pool keep the code their register reports were settled with.
+// The names above are the body's: ENV, TEX, SEC, RAY are the bits kEnv, kTex, kSec, kRay of O, SPLIT its split field, SHARE and
+// PREP the bits kShareBump and kPrep that render() takes on.  No bit is on by default: render_kernel and render_ss_kernel spell
+// kShareBump | kPrep, shadeRay adds them.
+template <int BULB, int COUNT, unsigned O>
 RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int py, int W, int H, V4 &fragColor,
                        V4 &bright, Counters &cnt, bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0},
                        const V3 *rayO = nullptr, const V3 *rayD = nullptr) {
+  static_assert(optOnly(O, kEnv | kTex | kSec | kSplitMask | kRay | kShareBump | kPrep), "shadePixel: an option it does not take");
+  constexpr bool ENV = (O & kEnv) != 0, TEX = (O & kTex) != 0, SEC = (O & kSec) != 0, RAY = (O & kRay) != 0;
+  constexpr int SPLIT = splitOf(O);  // 0 none, 1 kSplitPart, 2 kSplitFinish
   float ndcx, ndcy;
   if (!RAY) pixelNdc(px, py, W, H, ndcx, ndcy);
   bright = v4(0.0f, 0.0f, 0.0f, 1.0f);
@@ -1649,7 +1722,8 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
 
   Hit info;
   constexpr bool POOL = BULB && !ENV && !TEX && COUNT != 1 && SPLIT == 0;  // the shadow pool (renderPooled)
-  RenderOut ri = render<BULB, COUNT, TEX, !ENV, SPLIT, POOL, SHARE, PREP>(sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
+  RenderOut ri = render<BULB, COUNT, (O & (kTex | kSplitMask | kShareBump | kPrep)) | optIf(!ENV, kCull) | optIf(POOL, kPool)>(
+      sb, objs, ro, rd, info, 1.0f, far, bg, cnt, split);  // frag:2443
   EnvOut e;
   e.terrainHit = false; e.cloudHit = false; e.seaHit = false;
   if (env) e = envLayers(feat, sb->noise, iTime, W, ro, rd, ri.d, bg, cnt);  // frag:2444-2456
@@ -1682,7 +1756,7 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
       V3 sro = v3(fma(r.x * kSurfaceDist, 3.0f, info.p.x), fma(r.y * kSurfaceDist, 3.0f, info.p.y),
                   fma(r.z * kSurfaceDist, 3.0f, info.p.z));
       fil = mul(fil, cRefl);
-      RenderOut res = render<BULB, COUNT, TEX, !ENV>(sb, objs, sro, r, info, 1.0f, far, bg, cnt);
+      RenderOut res = render<BULB, COUNT, (O & kTex) | optIf(!ENV, kCull)>(sb, objs, sro, r, info, 1.0f, far, bg, cnt);
       if (env) {  // frag:2506-2518 (a sea hit sets sr.isEnv, not res.isEnv: the bounce loop goes on)
         EnvOut b = envLayers(feat, sb->noise, iTime, W, sro, r, res.d, bg, cnt);
         if (b.seaHit) res.col = b.scol;
@@ -1700,14 +1774,14 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
     V3 rdIn = refract(oi.rd, oi.n, 1.0f / ior);
     V3 pEnter = v3(fma(-(oi.n.x * kSurfaceDist), 3.0f, oi.p.x), fma(-(oi.n.y * kSurfaceDist), 3.0f, oi.p.y),
                    fma(-(oi.n.z * kSurfaceDist), 3.0f, oi.p.z));
-    float dIn = march<BULB, COUNT, false>(sb, pEnter, rdIn, far, -1.0f, cnt).d;
+    float dIn = march<BULB, COUNT>(sb, pEnter, rdIn, far, -1.0f, cnt).d;
     V3 pExit = madd(rdIn, dIn, pEnter);
     V3 nExit = neg(getNormal<BULB, COUNT>(sb, pExit, cnt));
     V3 rdOut = refract(rdIn, nExit, ior);
     if (len(rdOut) != 0.0f) {
       V3 sro = v3(fma(-(nExit.x * kSurfaceDist), 5.0f, pExit.x), fma(-(nExit.y * kSurfaceDist), 5.0f, pExit.y),
                   fma(-(nExit.z * kSurfaceDist), 5.0f, pExit.z));
-      RenderOut res = render<BULB, COUNT, TEX, !ENV>(sb, objs, sro, rdOut, info, 1.0f, far, bg, cnt);
+      RenderOut res = render<BULB, COUNT, (O & kTex) | optIf(!ENV, kCull)>(sb, objs, sro, rdOut, info, 1.0f, far, bg, cnt);
       if (env) {  // frag:2555-2567
         EnvOut b = envLayers(feat, sb->noise, iTime, W, sro, rdOut, res.d, bg, cnt);
         if (b.seaHit) res.col = b.scol;
@@ -1727,10 +1801,11 @@ RM_DEV void shadePixel(const SceneBlock *sb, const RmObject *objs, int px, int p
   if (brightness > 1.0f) bright = v4(c.x, c.y, c.z, 1.0f);
 }
 // The ray part alone: the colour, bright value and hit flag of the ray (ro, rd), for rays that do not come from a pixel.
-template <int BULB, int COUNT, bool ENV, bool TEX, bool SEC = true, int SPLIT = 0>
+template <int BULB, int COUNT, unsigned O>
 RM_DEV void shadeRay(const SceneBlock *sb, const RmObject *objs, V3 ro, V3 rd, int W, V4 &fragColor, V4 &bright, Counters &cnt,
                      bool &hitFlag, LightSplit split = LightSplit{-1, nullptr, 0}) {
-  shadePixel<BULB, COUNT, ENV, TEX, SEC, SPLIT, true>(sb, objs, 0, 0, W, 1, fragColor, bright, cnt, hitFlag, split, &ro, &rd);
+  static_assert(optOnly(O, kEnv | kTex | kSec | kSplitMask), "shadeRay: an option it does not take");
+  shadePixel<BULB, COUNT, O | kRay | kShareBump | kPrep>(sb, objs, 0, 0, W, 1, fragColor, bright, cnt, hitFlag, split, &ro, &rd);
 }
 
 // The workgroup prologue of a kernel that shades: the object table into the kernel's own s_objs, its LDS copy for per-lane

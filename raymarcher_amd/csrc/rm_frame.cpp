@@ -304,7 +304,7 @@ void scene_eval_records(SceneBlock *h) {
       for (int r = 0; r < 3; r++) e.m[c * 3 + r] = o.invModel[c * 4 + r];
     e.scaleFactor = o.scaleFactor;
     e.type = o.type;
-    // the skip test's bound (rm_device.hip.h, sdScene<…, SKIP>): radius of the unit shape's bounding ball, with a margin
+    // the skip test's bound (rm_device.hip.h, sdScene<…, kSkip>): radius of the unit shape's bounding ball, with a margin
     static const float kBound[] = {0.8662f, 0.7073f, 0.7073f, 0.5001f, 0.5001f, 0.6252f, 0.6002f, 0.5001f, 0.7073f};  // cube … rectangle
     const float sf = o.scaleFactor;
     const bool ok = std::isfinite(sf) && sf > 1e-6f && sf < 1e6f;
@@ -430,7 +430,7 @@ void fill_frames_animated(SceneBlock *h, int n, const RmCamera *cams, const RmGl
 // 25.4 -> 20.2 ms, with one 16.8 -> 16.4 ms); at 1080p its dozen launches of persistent waves cost more than the idle lanes
 // they remove (4.5 -> 5.2 ms, 5.4 -> 7.2 ms), and without secondary rays the one-lane-per-pixel kernel keeps 89-95 % of its
 // lanes busy by itself (directional_light_2.json: 1.3 ms against 3.5 ms).
-// Round 3, after the table walk learnt to pass over far objects (sdScene<…, SKIP>) and to follow a single object (march()'s
+// Round 3, after the table walk learnt to pass over far objects (sdScene<…, kSkip>) and to follow a single object (march()'s
 // fast path, all-primitive tables): for all-primitive tables the one-lane-per-pixel kernel is ahead at every bounce count
 // (reflections_complex.json 4K: 7.5 ms against 12.4 with one bounce, 12.4 against 15.7 with two) — in the wavefront kernels a
 // wave's lanes are unrelated rays, and both tests need the whole wave to agree.  Mixed tables (primitives and a fractal): the

@@ -12,7 +12,7 @@ namespace rm {
 // rm_render_gbuffer: frame blockIdx.z of the grid reads scene block sb[blockIdx.z] and writes W·H elements of each output from
 // frame·W·H (the header has the definition).  A lane is a pixel of its wave's 8×8 tile, the waves of a workgroup side by side, as in
 // render_kernel's raster order.  The lane runs the head of render() (rm_device.hip.h) for shadePixel's primary ray and stops there:
-// primaryRay, march<BULB, 0, false, true> to cam.initialFar, the surface point rd·d + ro in render's fused form, getNormal with the
+// primaryRay, march<BULB, 0, kCull> to cam.initialFar, the surface point rd·d + ro in render's fused form, getNormal with the
 // skip-test seeds render derives (ubP from the march's stopping rule, the taps' 0.0005 on top), bumpNormal behind the feature bit —
 // the same calls with the same arguments, so the same bits as the values render hands getPhong.  The march's index is stored as it
 // comes: an emissive rectangle reports its own index.  A miss stores (0, 0, 0, far), −1 and (0, 0, 0, 0).
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256, gbuffer_waves(BULB)) void gbuffer_kernel(
   primaryRay(sb, x, y, W, H, ro, rd);
   const float far = sb->cam.initialFar;
   Counters cnt{0, 0, 0, 0, 0, 0};
-  const MarchRes res = march<BULB, 0, false, true>(sb, ro, rd, far, 1.0f, cnt);  // a miss reports far, not res.d (frag:2328)
+  const MarchRes res = march<BULB, 0, kCull>(sb, ro, rd, far, 1.0f, cnt);  // a miss reports far, not res.d (frag:2328)
   V3 p = v3(0.0f, 0.0f, 0.0f), n = v3(0.0f, 0.0f, 0.0f);
   float depth = far;
   if (res.obj != -1) {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256, gbuffer_waves(BULB)) void gbuffer_kernel(
       const float lipLen = (sb->cullLip * len(rd)) * 1.0001f;
       ubP = fma(kSurfaceDist, lipLen, kSurfaceDist) * 1.001f + fma(fabs_(res.d), 1.0e-6f, 1.0e-5f);
     }
-    n = getNormal<BULB, 0, SKIP>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
+    n = getNormal<BULB, 0, optIf(SKIP, kSkip)>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
     if (sb->s.features & RM_FEAT_PERLIN_BUMP) n = bumpNormal(n, p);
   }
   const size_t o = ((size_t)blockIdx.z * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
@@ -67,14 +67,14 @@ __global__ __launch_bounds__(256, gbuffer_waves(BULB)) void gbuffer_kernel(
   if (position) position[o] = make_float4(p.x, p.y, p.z, res.obj != -1 ? 1.0f : 0.0f);
 }
 
-// The three march classes (0 the table walk, kBulbGeneral, kBulbPlain) and nothing more.
+// The three march classes (dispatch_march_class, rm_internal.h) and nothing more.
 int launch_gbuffer_kernel(const void *sbv, int bulbClass, dim3 grid, dim3 block, int W, int H, float *d_normalDepth,
                           int32_t *d_objectId, float *d_position, hipStream_t stream) {
   const SceneBlock *sb = static_cast<const SceneBlock *>(sbv);
   float4 *nd = reinterpret_cast<float4 *>(d_normalDepth), *pos = reinterpret_cast<float4 *>(d_position);
-  if (bulbClass == kBulbPlain) hipLaunchKernelGGL((gbuffer_kernel<kBulbPlain>), grid, block, 0, stream, sb, W, H, nd, d_objectId, pos);
-  else if (bulbClass == kBulbGeneral) hipLaunchKernelGGL((gbuffer_kernel<kBulbGeneral>), grid, block, 0, stream, sb, W, H, nd, d_objectId, pos);
-  else hipLaunchKernelGGL((gbuffer_kernel<0>), grid, block, 0, stream, sb, W, H, nd, d_objectId, pos);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    hipLaunchKernelGGL((gbuffer_kernel<decltype(c)::bulb>), grid, block, 0, stream, sb, W, H, nd, d_objectId, pos);
+  });
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

@@ -222,6 +222,16 @@ void dispatch_class(int bulbClass, bool env, bool tex, bool sec, F &&f) {
   else if (bulbClass == kBulbGeneral) either(KernelClass<kBulbGeneral, false, false, true>{}, KernelClass<kBulbGeneral, false, false, false>{});
   else either(KernelClass<0, false, false, true>{}, KernelClass<0, false, false, false>{});
 }
+// The three march classes — the plain bulb, the general bulb, the table walk — of the kernels that march or evaluate the scene
+// without shading it (rays, G-buffer, lattices): f(MarchClass<…>{}), as dispatch_class calls its f.
+template <int BULB>
+struct MarchClass { static constexpr int bulb = BULB; };
+template <class F>
+void dispatch_march_class(int bulbClass, F &&f) {
+  if (bulbClass == kBulbPlain) f(MarchClass<kBulbPlain>{});
+  else if (bulbClass == kBulbGeneral) f(MarchClass<kBulbGeneral>{});
+  else f(MarchClass<0>{});
+}
 
 // The largest single workspace buffer stream_workspace may allocate, 0 = no limit (rm_set_workspace_limit).
 unsigned long long workspace_limit();

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
   V4 col, br;
   Counters cnt{0, 0, 0, 0, 0, 0};
   bool hit;
-  shadePixel<BULB, CM, ENV, TEX, SEC, SPLIT>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
+  shadePixel<BULB, CM, optClass(ENV, TEX, SEC) | optSplit(SPLIT) | kShareBump | kPrep>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
   if (SPLIT == 1 && split.part >= 0) {
     // A partial workgroup: its results are in memory.  The LAST of the tile's numLights workgroups to get here finishes the tile —
     // surface point, AO and the light sum from the stored results, no march (shadePixel in mode 2) — the others are done.  Release /
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, ENV, TEX, SEC)) void render
     if ((int)old != sb->numLights - 1) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // only the finisher invalidates its view before it reads the others' records
     split.part = -1;
-    shadePixel<BULB, CM, ENV, TEX, SEC, 2>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
+    shadePixel<BULB, CM, optClass(ENV, TEX, SEC) | kSplitFinish | kShareBump | kPrep>(sb, s_objs, x, y, W, H, col, br, cnt, hit, split);
   }
   if (FRAMES) {
     const size_t f = (size_t)sb->frame * (size_t)nRows * (size_t)W;

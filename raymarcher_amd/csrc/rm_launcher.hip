@@ -1052,7 +1052,7 @@ int launch_gbuffer(const FrameCall &c, float *d_normalDepth, int32_t *d_objectId
 // table's limits and types, the arrays (null, alignment of the float4 accesses), then whether they are device memory.
 // Staging is stage_blocks of one block, filled with a zeroed camera, no lights and no resources — the evaluation records, the
 // cull ball and box with cullLip and cullOneOk, bulbPlain.  rayPlane and cam are staged (zeros) and never read.  The occlusion mode
-// stages two fields of its own: s.enableSoftShadow = 1, so that march<…, SHADOW> tracks the penumbra factor whatever the caller's
+// stages two fields of its own: s.enableSoftShadow = 1, so that march<…, kShadow> tracks the penumbra factor whatever the caller's
 // settings say, and cullR2Soft = 0.  scene_cull_ball derives that larger ball for shadow rays that start on a surface, inside the
 // cull ball, where t <= ρ + R; a caller's ray may start anywhere, so with it a far origin would settle the factor too early.
 // Without it a soft march ends at tMax, as the reference's does.  (The hard bounds — ball, box, the bulb's own ball — argue about

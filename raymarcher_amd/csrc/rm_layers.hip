@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256, shade_layers_waves(TEX, SEC)) void shade_rays_
   V4 col, br = v4(0.0f, 0.0f, 0.0f, 1.0f);
   Counters cnt{0, 0, 0, 0, 0, 0};
   bool hit = false;
-  shadeRay<0, 0, true, TEX, SEC, 0>(sb, s_objs, ro, rd, imageWidth, col, br, cnt, hit);
+  shadeRay<0, 0, kEnv | optIf(TEX, kTex) | optIf(SEC, kSec)>(sb, s_objs, ro, rd, imageWidth, col, br, cnt, hit);
   out[i] = make_float4(col.x, col.y, col.z, col.w);
   if (bright) bright[i] = make_float4(br.x, br.y, br.z, br.w);
 }
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256, trace_layers_waves(BULB)) void trace_layers_ke
     return;
   }
   Counters cnt{0, 0, 0, 0, 0, 0};
-  const MarchRes res = march<BULB, 0, false, true>(sb, ro, rd, tMax, 1.0f, cnt);  // a miss reports tMax, not res.d
+  const MarchRes res = march<BULB, 0, kCull>(sb, ro, rd, tMax, 1.0f, cnt);  // a miss reports tMax, not res.d
   const float d0 = res.obj != -1 ? res.d : tMax;
   const LayerSurface ls = layerSurface(sb->s.features, sb->g.iTime, imageWidth, ro, rd, d0, noNormal != 0, cnt);
   h0.w = ls.t;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, trace_layers_waves(BULB)) void trace_layers_ke
         const float lipLen = (sb->cullLip * len(rd)) * 1.0001f;
         ubP = fma(kSurfaceDist, lipLen, kSurfaceDist) * 1.001f + fma(fabs_(res.d), 1.0e-6f, 1.0e-5f);
       }
-      V3 n = getNormal<BULB, 0, SKIP>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
+      V3 n = getNormal<BULB, 0, optIf(SKIP, kSkip)>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
       if (sb->s.features & RM_FEAT_PERLIN_BUMP) n = bumpNormal(n, p);
       h0.x = n.x; h0.y = n.y; h0.z = n.z;
       h1.x = p.x; h1.y = p.y; h1.z = p.z;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, trace_layers_waves(BULB)) void trace_layers_ke
   hits[2 * (size_t)i + 1] = h1;
 }
 
-// The three march classes (0 the table walk, kBulbGeneral, kBulbPlain), closest mode only.
+// The three march classes (dispatch_march_class, rm_internal.h), closest mode only.
 int launch_trace_layers_kernel(const void *sbv, int bulbClass, bool noNormal, const void *d_rays, int numRays, int imageWidth,
                                void *d_hits, hipStream_t stream) {
   static_assert(sizeof(RmRay) == 2 * sizeof(float4) && sizeof(RmRayHit) == 2 * sizeof(float4), "a ray and a hit are two float4 each");
@@ -183,11 +183,9 @@ int launch_trace_layers_kernel(const void *sbv, int bulbClass, bool noNormal, co
   float4 *hits = static_cast<float4 *>(d_hits);
   const dim3 grid((unsigned)(((long long)numRays + 255) / 256)), block(256);
   const int nn = noNormal ? 1 : 0;
-  if (bulbClass == kBulbPlain)
-    hipLaunchKernelGGL((trace_layers_kernel<kBulbPlain>), grid, block, 0, stream, sb, rays, numRays, imageWidth, nn, hits);
-  else if (bulbClass == kBulbGeneral)
-    hipLaunchKernelGGL((trace_layers_kernel<kBulbGeneral>), grid, block, 0, stream, sb, rays, numRays, imageWidth, nn, hits);
-  else hipLaunchKernelGGL((trace_layers_kernel<0>), grid, block, 0, stream, sb, rays, numRays, imageWidth, nn, hits);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    hipLaunchKernelGGL((trace_layers_kernel<decltype(c)::bulb>), grid, block, 0, stream, sb, rays, numRays, imageWidth, nn, hits);
+  });
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

@@ -17,7 +17,7 @@ namespace rm {
 // lanes with i >= numPoints and the invalid points leave (an invalid point after storing its zeros) — for the same reason: the
 // bulb classes' shadow pool is called by every lane of the wave that is still there, converged.
 // One loop serves the projection and the final evaluation: each trip evaluates sdScene at p in the primary march's trap form
-// (sdSceneImpl<BULB, 0, 1, …>: UB3, the trap of the last fractal evaluated) and, with an object there, getNormal(p); a trip that is a
+// (sdSceneImpl<BULB, 0, kTrapShader>: UB3, the trap of the last fractal evaluated) and, with an object there, getNormal(p); a trip that is a
 // projection step then moves p, and the trip that stops — the steps are used up, the table is empty, q is not finite or too far from
 // p0 — leaves the loop with sc and N belonging to the last accepted p, which is what steps 3 and 4 of the definition ask for.  So
 // the kernel holds one copy of the evaluator and one of the normal: 1 + 4 evaluations, plus 5 per projection step.
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
   float ubP = __builtin_inff();
   for (int k = 0;; k++) {
     float unused;
-    sc = sdSceneImpl<BULB, 0, 1, false, false>(sb, p, cnt, __builtin_inff(), unused);
+    sc = sdSceneImpl<BULB, 0, kTrapShader>(sb, p, cnt, __builtin_inff(), unused);
     if (sc.idx == -1) {  // no object here: whatever normal an earlier trip left is not this point's
       N = v3(0.0f, 0.0f, 0.0f);
       break;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
       const float pm = max_(max_(fabs_(p.x), fabs_(p.y)), fabs_(p.z));
       ubP = fma(fabs_(sc.d), 1.0e-4f, sc.d) + fma(pm, sb->cullLip * 1.0e-6f, 1.0e-5f);
     }
-    N = getNormal<BULB, 0, SKIP>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);  // never bumped here
+    N = getNormal<BULB, 0, optIf(SKIP, kSkip)>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);  // never bumped here
     if (k >= a.projectSteps) break;
     const V3 q = madd(N, -(sc.d - a.iso), p);
     if (!(finiteBits(q.x) && finiteBits(q.y) && finiteBits(q.z))) break;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
   }
   float ao = 0.0f;
   if (a.ao) {
-    if (surf) ao = calcAO<BULB, 0, SKIP>(sb, p, N, cnt, ubP);
+    if (surf) ao = calcAO<BULB, 0, optIf(SKIP, kSkip)>(sb, p, N, cnt, ubP);
     a.ao[i] = ao;
   }
   if (!a.rgba) return;
@@ -129,13 +129,13 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
         if (!shared) {
           pend = need;
         } else {
-          const float d0 = fabs_(sdScene<BULB, 0, false>(sb, so, cnt).d);
+          const float d0 = fabs_(sdScene<BULB, 0, kTrapNone>(sb, so, cnt).d);
           if (d0 < kSurfaceDist) hits = need;
           else if (maxSteps > 1) { pend = need; dStart = d0; }
         }
       }
     }
-    const uint32_t hitMask = hits | shadowPool<BULB, 0, true>(sb, so, pend, dStart, far, cnt);
+    const uint32_t hitMask = hits | shadowPool<BULB, 0, kPrep>(sb, so, pend, dStart, far, cnt);
     if (surf) {
       const RmObject &o = s_objs[0];
       Material mat;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256, render_waves(BULB, false, TEX, false)) void sh
       mat.spec = v3(o.cSpecular[0], o.cSpecular[1], o.cSpecular[2]);
       mat.shininess = o.shininess;
       const int type = BULB ? (int)RM_MANDELBULB : o.type;
-      const V3 ph = getPhong<BULB, 0, TEX, true>(sb, s_objs, mat, N, p, rd, far, cnt, ubP);
+      const V3 ph = getPhong<BULB, 0, optIf(TEX, kRes) | kCull>(sb, s_objs, mat, N, p, rd, far, cnt, ubP);
       V3 c3 = ph;
       if (type == RM_MANDELBULB) {
         const V3 c = bulbTrapColor(sc.trap.y, sc.trap.z, sc.trap.w);

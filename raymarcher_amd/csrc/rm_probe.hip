@@ -49,7 +49,7 @@ __global__ void probe_sdscene_kernel(const SceneBlock *__restrict__ sb, const fl
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Counters cnt{0, 0, 0, 0, 0, 0};
-  SceneMin m = sdScene<false, 0>(sb, v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), cnt);
+  SceneMin m = sdScene<0, 0, kTrapShader>(sb, v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), cnt);
   out[4 * i] = m.d;
   out[4 * i + 1] = (float)m.idx;
   out[4 * i + 2] = m.trap.y;
@@ -107,8 +107,9 @@ __global__ void __launch_bounds__(64) probe_variant_kernel(const SceneBlock *__r
   const V3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
   float second = __builtin_inff();
   SceneMin m;
+  constexpr unsigned O = optTrap(TRAP) | optIf(SKIP, kSkip) | optIf(TRACK, kTrack);
   if (ONE) m = sdSceneOne<COUNT>(sb, one, p, cnt);
-  else m = sdSceneImpl<BULB, COUNT, TRAP, SKIP, TRACK>(sb, p, cnt, ubs ? ubs[i] : __builtin_inff(), second);
+  else m = sdSceneImpl<BULB, COUNT, O>(sb, p, cnt, ubs ? ubs[i] : __builtin_inff(), second);
   float *o = out + 8 * (size_t)i;
   o[0] = m.d;
   o[1] = (float)m.idx;
@@ -127,9 +128,9 @@ void launch(const SceneBlock *sb, const float *pts, const float *ubs, float *out
                      stream, sb, pts, ubs, out, n, one);
 }
 
-// Every combination a production kernel instantiates, found at the call sites: march (sdSceneImpl<BULB, COUNT, !SHADOW, SKIP,
-// SKIP> with SKIP = CULL && !BULB && COUNT != 1, and sdSceneOne<COUNT> on its fast path), getNormal and calcAO (sdScene<…, 0,
-// SKIP>, same SKIP), the hard-shadow pools and the refraction march (no SKIP), the wavefront march (table walk, COUNT 0, TRAP 2
+// Every combination a production kernel instantiates, found at the call sites: march (sdSceneImpl<BULB, COUNT, the trap unless
+// kShadow | kSkip | kTrack> with the last two for SKIP = CULL && !BULB && COUNT != 1, and sdSceneOne<COUNT> on its fast path), getNormal
+// and calcAO (sdScene<…, kTrapNone | kSkip>, same SKIP), the hard-shadow pools and the refraction march (no SKIP), the wavefront march (table walk, COUNT 0, TRAP 2
 // or 0, SKIP either); the plain bulb form only in the production (COUNT 0) kernels.
 struct Variant { int bulbClass, count, trap, skip, track, one; Launch fn; };
 const Variant kVariants[] = {

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, shade_waves(BULB, ENV, TEX, SEC)) void shade_r
   V4 col, br = v4(0.0f, 0.0f, 0.0f, 1.0f);
   Counters cnt{0, 0, 0, 0, 0, 0};
   bool hit = false;
-  shadeRay<BULB, 0, ENV, TEX, SEC, 0>(sb, s_objs, ro, rd, kShadeEnvWidth, col, br, cnt, hit);
+  shadeRay<BULB, 0, optClass(ENV, TEX, SEC)>(sb, s_objs, ro, rd, kShadeEnvWidth, col, br, cnt, hit);
   out[i] = make_float4(col.x, col.y, col.z, col.w);
   if (bright) bright[i] = make_float4(br.x, br.y, br.z, br.w);
 }

@@ -13,10 +13,10 @@ namespace rm {
 // the definition).  A lane loads its RmRay as two float4 (origin, tMax | dir, reserved) and stores its RmRayHit as two float4
 // (normal, t | position, objectId): 2 KB contiguous per wave each way, plain vector loads and stores.  Between them it makes
 // gbuffer_kernel's device calls (rm_gbuffer.hip) with the ray in place of primaryRay's:
-//   closest (MODE 0): march<BULB, 0, false, true> to the ray's tMax, the surface point rd·d + ro in render's fused form, getNormal
+//   closest (MODE 0): march<BULB, 0, kCull> to the ray's tMax, the surface point rd·d + ro in render's fused form, getNormal
 //     with the skip-test seeds render derives (ubP from the march's stopping rule, the taps' 0.0005 on top), bumpNormal behind the
 //     feature bit.  noNormal (a kernel argument, so wave-uniform) leaves the surface point and the taps out: zeros are stored.
-//   occlusion (MODE 1): march<BULB, 0, true, true> with the default ub0 — lightTerm's shadow march.  The launcher stages
+//   occlusion (MODE 1): march<BULB, 0, kShadow | kCull> with the default ub0 — lightTerm's shadow march.  The launcher stages
 //     enableSoftShadow = 1, so the penumbra factor is always tracked, and cullR2Soft = 0: the larger ball of the soft-shadow rays is
 //     derived for rays that START inside the cull ball (rm_frame.cpp, scene_cull_ball), which a caller's rays need not.
 // dir is used as given: len(rd) enters the skip test's Lipschitz seeds exactly as for a unit direction, and the cull ball and box
@@ -59,11 +59,11 @@ __global__ __launch_bounds__(256, trace_waves(BULB)) void trace_kernel(
   }
   Counters cnt{0, 0, 0, 0, 0, 0};
   if (MODE == kTraceOcclusion) {
-    const MarchRes res = march<BULB, 0, true, true>(sb, ro, rd, tMax, 1.0f, cnt);  // softshadow(ro, rd, 0, tMax, 8)
+    const MarchRes res = march<BULB, 0, kShadow | kCull>(sb, ro, rd, tMax, 1.0f, cnt);  // softshadow(ro, rd, 0, tMax, 8)
     h0.w = res.d;
     h1.w = u2f((uint32_t)res.obj);
   } else {
-    const MarchRes res = march<BULB, 0, false, true>(sb, ro, rd, tMax, 1.0f, cnt);  // a miss reports tMax, not res.d
+    const MarchRes res = march<BULB, 0, kCull>(sb, ro, rd, tMax, 1.0f, cnt);  // a miss reports tMax, not res.d
     h0.w = tMax;
     h1.w = u2f((uint32_t)res.obj);
     if (res.obj != -1) {
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256, trace_waves(BULB)) void trace_kernel(
           const float lipLen = (sb->cullLip * len(rd)) * 1.0001f;
           ubP = fma(kSurfaceDist, lipLen, kSurfaceDist) * 1.001f + fma(fabs_(res.d), 1.0e-6f, 1.0e-5f);
         }
-        V3 n = getNormal<BULB, 0, SKIP>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
+        V3 n = getNormal<BULB, 0, optIf(SKIP, kSkip)>(sb, p, cnt, SKIP ? fma(0.0005f, sb->cullLip * 1.001f, ubP) : ubP);
         if (sb->s.features & RM_FEAT_PERLIN_BUMP) n = bumpNormal(n, p);
         h0.x = n.x; h0.y = n.y; h0.z = n.z;
         h1.x = p.x; h1.y = p.y; h1.z = p.z;
@@ -88,16 +88,14 @@ __global__ __launch_bounds__(256, trace_waves(BULB)) void trace_kernel(
   hits[2 * (size_t)i + 1] = h1;
 }
 
-// The three march classes (0 the table walk, kBulbGeneral, kBulbPlain) × closest / occlusion, and nothing more.
+// The three march classes (dispatch_march_class, rm_internal.h) × closest / occlusion, and nothing more.
 template <int MODE>
 static void launch_trace_mode(const SceneBlock *sb, int bulbClass, dim3 grid, const float4 *rays, int numRays, int noNormal,
                               float4 *hits, hipStream_t stream) {
   const dim3 block(256);
-  if (bulbClass == kBulbPlain)
-    hipLaunchKernelGGL((trace_kernel<kBulbPlain, MODE>), grid, block, 0, stream, sb, rays, numRays, noNormal, hits);
-  else if (bulbClass == kBulbGeneral)
-    hipLaunchKernelGGL((trace_kernel<kBulbGeneral, MODE>), grid, block, 0, stream, sb, rays, numRays, noNormal, hits);
-  else hipLaunchKernelGGL((trace_kernel<0, MODE>), grid, block, 0, stream, sb, rays, numRays, noNormal, hits);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    hipLaunchKernelGGL((trace_kernel<decltype(c)::bulb, MODE>), grid, block, 0, stream, sb, rays, numRays, noNormal, hits);
+  });
 }
 int launch_trace_kernel(const void *sbv, int bulbClass, bool occlusion, bool noNormal, const void *d_rays, int numRays, void *d_hits,
                         hipStream_t stream) {

@@ -22,7 +22,7 @@ namespace rm {
 // least inside a compact brick.  A workgroup is four bricks that follow each other in x.  A lane outside the lattice leaves
 // before the evaluation, as the probe kernels' lanes past n do: the evaluator's ballots are proofs about the lanes that are live,
 // so a point's value does not depend on which other points share its wave.
-// The evaluation is sdSceneImpl<BULB, 0, 0, false, false>: the instantiation of the table's march class (the table walk, the
+// The evaluation is sdSceneImpl<BULB, 0, kTrapNone>: the instantiation of the table's march class (the table walk, the
 // general Mandelbulb, the plain Mandelbulb) that the shadow marches of rm_trace_rays' kernels call, with no pass-over bound, no
 // runner-up and no orbit trap — minD and minObjIdx are the same bits with and without the trap (rm_probe_sdscene_variant's tests).
 // The point is origin + (float)i · step per axis: one multiply, one add, never fused (-ffp-contract=off, like every kernel here).
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void sdf_grid_kernel(const SceneBlock *__restr
   const V3 p = v3(ox + fx, oy + fy, oz + fz);
   Counters cnt{0, 0, 0, 0, 0, 0};
   float unused;
-  const SceneMin m = sdSceneImpl<BULB, 0, 0, false, false>(sb, p, cnt, __builtin_inff(), unused);
+  const SceneMin m = sdSceneImpl<BULB, 0, kTrapNone>(sb, p, cnt, __builtin_inff(), unused);
   const size_t at = ((size_t)k * (size_t)ny + (size_t)j) * (size_t)nx + (size_t)i;
   dist[at] = m.d;
   if (ids) ids[at] = m.idx;
@@ -61,13 +61,10 @@ int launch_sdf_grid_kernel(const void *sbv, int bulbClass, const float origin[3]
   const unsigned bricksX = (unsigned)((nx + kBrickX - 1) / kBrickX), bricksY = (unsigned)((ny + kBrickY - 1) / kBrickY),
                  bricksZ = (unsigned)((nz + kBrickZ - 1) / kBrickZ);
   const dim3 grid((bricksX + 3u) / 4u, bricksY, bricksZ), block(256);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, sb, origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, d_dist,
-                       d_objectId);
-  };
-  if (bulbClass == kBulbPlain) go(sdf_grid_kernel<kBulbPlain>);
-  else if (bulbClass == kBulbGeneral) go(sdf_grid_kernel<kBulbGeneral>);
-  else go(sdf_grid_kernel<0>);
+  dispatch_march_class(bulbClass, [&](auto c) {
+    hipLaunchKernelGGL(sdf_grid_kernel<decltype(c)::bulb>, grid, block, 0, stream, sb, origin[0], origin[1], origin[2], step[0], step[1],
+                       step[2], nx, ny, nz, d_dist, d_objectId);
+  });
   HIP_OK(hipGetLastError());
   return RM_OK;
 }

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64, wfMarchWaves(KIND)) void wf_march_kernel(const 
   uint32_t src = 0;
   V3 ro = v3(0, 0, 0), rd = v3(0, 0, 0);
   float depth = 0.0f, end = 0.0f, pen = 1.0f;
-  // the table walk's skip test (rm_device.hip.h, sdScene<…, SKIP>): ub = upper bound of the next evaluation's minimum; every ray
+  // the table walk's skip test (rm_device.hip.h, sdScene<…, kSkip>): ub = upper bound of the next evaluation's minimum; every ray
   // direction here is a normalised vector (|rd| within a few ulp of 1), hence one padded constant for all lanes
   float ub = __builtin_inff();
   const float lipLen = sb->cullLip * 1.001f;
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(64, wfMarchWaves(KIND)) void wf_march_kernel(const 
     int hitObj = -1;
     if (st == ST_MARCH) {
       // trap mode 2: a hit record carries trap.z alone (the sponge's palette index) and this pipeline's tables hold no bulb
-      const SceneMin c = sdScene<false, 0, KIND != 2 ? 2 : 0, SKIP>(sb, madd(rd, depth, ro), none, ub);
+      const SceneMin c = sdScene<0, 0, (KIND != 2 ? kTrapZ : kTrapNone) | optIf(SKIP, kSkip)>(sb, madd(rd, depth, ro), none, ub);
       const bool hit = fabs_(c.d) < kSurfaceDist;
       bool fin = hit || depth > end;
       if (!fin) {
@@ -298,10 +298,10 @@ __global__ __launch_bounds__(256) void wf_surface_kernel(const SceneBlock *__res
     const V3 p = madd(rd, u2f((uint32_t)rec.y), ro);
     // seeds of the skip test as in render(): the march stopped within SURFACE_DIST of a surface, p at most that far (× |rd|) from there
     const float ubP = fma(kSurfaceDist, (sb->cullLip * len(rd)) * 1.0001f, kSurfaceDist) * 1.001f + fma(fabs_(u2f((uint32_t)rec.y)), 1.0e-6f, 1.0e-5f);
-    V3 n = getNormal<false, 0, SKIP>(sb, p, none, fma(0.0005f, sb->cullLip * 1.001f, ubP));
+    V3 n = getNormal<0, 0, optIf(SKIP, kSkip)>(sb, p, none, fma(0.0005f, sb->cullLip * 1.001f, ubP));
     if (sb->s.features & RM_FEAT_PERLIN_BUMP) n = bumpNormal(n, p);
     float ao = 1.0f;
-    if (sb->s.enableAmbientOcclusion) ao = calcAO<false, 0, SKIP>(sb, p, n, none, ubP);
+    if (sb->s.enableAmbientOcclusion) ao = calcAO<0, 0, optIf(SKIP, kSkip)>(sb, p, n, none, ubP);
     ws.surfP[h] = make_float4(p.x, p.y, p.z, ao);
     ws.surfN[h] = make_float4(n.x, n.y, n.z, 0.0f);
   }
