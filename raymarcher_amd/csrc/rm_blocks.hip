@@ -1,7 +1,7 @@
 // rm_blocks.hip — block-sparse lattices (gfx950 only): the kernels of rm_sdf_blocks_select (which 8×8×8-cell blocks of a virtual
 // lattice hold surface), of rm_sdf_grid_blocks (sdScene on the 9×9×9 points of listed blocks only) and the kernels and the entry
 // point of rm_sdf_mesh_blocks (rm_sdf_mesh's quad mesh over a block list).  include/raymarcher_amd.h has the definitions.  The
-// argument checks and staging of the first two are launch_sdf_blocks_select / launch_sdf_grid_blocks in rm_launcher.hip; everything
+// argument checks and staging of the first two are launch_sdf_blocks_select / launch_sdf_grid_blocks in rm_queries.hip; everything
 // of rm_sdf_mesh_blocks is here, as rm_sdf_mesh is in rm_volume.hip.  A translation unit of its own, so that adding it leaves the
 // code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
@@ -181,7 +181,7 @@ int enqueue_block_map(const int32_t *d_blocks, int numBlocks, int mx, int my, in
   return RM_OK;
 }
 
-// ---- the launches of the two staged entry points (rm_launcher.hip checks and stages) ----------------------------------------------
+// ---- the launches of the two staged entry points (rm_queries.hip checks and stages) ----------------------------------------------
 static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 template <bool SELECT, class... Args>
 static void launch_eval(int bulbClass, dim3 grid, hipStream_t stream, Args... args) {

@@ -1,8 +1,8 @@
 // rm_blocks_prune.hip — rm_sdf_blocks_select_pruned (gfx950 only): rm_sdf_blocks_select's list without the sweep over every block.
 // The corners of the blocks are evaluated once; a block whose eight corners are all far from the iso surface on the same side is
 // discarded (rm_blocks_prune.h has the rule, include/raymarcher_amd.h the definition), and only the others — the candidates — get
-// the exact evaluation of their 729 points.  The argument checks and the staging are launch_sdf_blocks_select_pruned in
-// rm_launcher.hip; the count / scan / emit compaction is rm_blocks.hip's.  A translation unit of its own, so that adding it leaves
+// the exact evaluation of their 729 points.  The argument checks and the staging are launch_sdf_blocks_select in
+// rm_queries.hip; the count / scan / emit compaction is rm_blocks.hip's.  A translation unit of its own, so that adding it leaves
 // the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64 * kEvalWaves) void prune_eval_kernel(const Scene
   }
 }
 
-// ---- the launches (rm_launcher.hip checks and stages) ---------------------------------------------------------------------------
+// ---- the launches (rm_queries.hip checks and stages) ---------------------------------------------------------------------------
 static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 static size_t corner_count(int mx, int my, int mz) { return (size_t)(mx + 1) * (size_t)(my + 1) * (size_t)(mz + 1); }
 

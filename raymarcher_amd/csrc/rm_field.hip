@@ -8,20 +8,17 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cmath>
 #include <mutex>
 #include <string>
 
 #include "../../include/raymarcher_amd.h"
+#include "rm_field_check.h"
 #include "rm_field_march.h"
 #include "rm_internal.h"
 
 namespace rm {
 
 int enqueue_block_map(const int32_t *d_blocks, int numBlocks, int mx, int my, int mz, uint32_t *first, hipStream_t stream);  // rm_blocks.hip
-
-static_assert(sizeof(fm::Sample) == 32 && sizeof(RmFieldSample) == 32 && sizeof(fm::Hit) == 32 && sizeof(RmRayHit) == 32, "two float4 per record");
-static_assert(fm::kInvalid == RM_RAY_INVALID && fm::kOutside == RM_FIELD_OUTSIDE && fm::kUnlisted == RM_FIELD_UNLISTED, "the header's codes");
 
 template <class Field>
 __global__ __launch_bounds__(256) void field_sample_kernel(const float4 *__restrict__ points, unsigned n, Field F, fm::Frame L,
@@ -47,13 +44,10 @@ __global__ __launch_bounds__(256) void field_trace_kernel(const float4 *__restri
   out[2 * i + 1] = make_float4(h.position[0], h.position[1], h.position[2], __int_as_float(h.objectId));
 }
 
-static bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-static int bad(const char *msg) {
-  set_error(msg);
-  return (int)RM_ERR_INVALID_ARGUMENT;
-}
+using fchk::bad;
 
-// What the four entry points check, in the header's order; no HIP call.  A dense call has d_blocks = nullptr and numBlocks = −1.
+// What the four entry points check, in the header's order (the steps rm_field_handle.hip shares are rm_field_check.h's); no HIP
+// call.  A dense call has d_blocks = nullptr and numBlocks = −1.
 struct FieldCall {
   const void *in;       // d_points or d_rays
   int count;
@@ -72,25 +66,16 @@ struct FieldCall {
 static int check_field_call(const FieldCall &c, bool *launch) {
   *launch = false;
   if (c.count < 0) return bad(c.trace ? "negative numRays" : "negative numPoints");
-  if (c.sparse) {
-    if (int st = check_block_lattice(c.origin, c.step, c.dims[0], c.dims[1], c.dims[2])) return st;
-    if (c.numBlocks < 0 || c.numBlocks > RM_MAX_BLOCK_LIST) return bad("numBlocks must be 0 … RM_MAX_BLOCK_LIST");
-  } else {
-    if (int st = check_lattice(c.origin, c.step, c.dims[0], c.dims[1], c.dims[2])) return st;
-    if (c.dims[0] < 2 || c.dims[1] < 2 || c.dims[2] < 2) return bad("every lattice dimension must be at least 2: a query needs a cell");
-  }
-  if (c.trace) {
-    if (!std::isfinite(c.iso)) return bad("iso must be finite");
-    if (c.maxSteps < 0 || c.maxSteps > RM_MAX_FIELD_STEPS) return bad("maxSteps must be 0 … RM_MAX_FIELD_STEPS (65536)");
-    if ((c.mode & ~RM_TRACE_NO_NORMAL) != 0u) return bad("mode bits other than RM_TRACE_NO_NORMAL");
-  }
+  if (int st = fchk::check_field_lattice(c.sparse, c.dims, c.origin, c.step, c.numBlocks)) return st;
+  if (c.trace)
+    if (int st = fchk::check_field_march(c.iso, c.maxSteps, c.mode, RM_TRACE_NO_NORMAL, "mode bits other than RM_TRACE_NO_NORMAL")) return st;
   if (c.count == 0) return RM_OK;
-  const bool emptyList = c.sparse && c.numBlocks == 0;  // nothing of d_dist is read
-  if (!c.in || !c.out || (!c.dist && !emptyList)) return bad(c.trace ? "null d_rays, d_hits or d_dist" : "null d_points, d_samples or d_dist");
-  if (c.sparse && c.numBlocks > 0 && !c.blocks) return bad("null d_blocks with numBlocks above 0");
-  if (!aligned(c.in, 16) || !aligned(c.out, 16) || !aligned(c.dist, 4) || !aligned(c.ids, 4) || !aligned(c.blocks, 4))
-    return bad(c.trace ? "misaligned d_rays or d_hits (16 bytes), d_dist, d_objectId or d_blocks (4 bytes)"
-                       : "misaligned d_points or d_samples (16 bytes), d_dist, d_objectId or d_blocks (4 bytes)");
+  const char *nullText = c.trace ? "null d_rays, d_hits or d_dist" : "null d_points, d_samples or d_dist";
+  if (!c.in || !c.out) return bad(nullText);
+  if (int st = fchk::check_field_arrays(c.in, c.out, c.dist, c.ids, c.blocks, c.numBlocks, c.sparse, nullText,
+                                        c.trace ? "misaligned d_rays or d_hits (16 bytes), d_dist, d_objectId or d_blocks (4 bytes)"
+                                                : "misaligned d_points or d_samples (16 bytes), d_dist, d_objectId or d_blocks (4 bytes)"))
+    return st;
   if (int st = require_device_pointers({{c.trace ? "d_rays" : "d_points", c.in}, {"d_dist", c.dist}, {"d_objectId", c.ids},
                                         {"d_blocks", c.numBlocks > 0 ? c.blocks : nullptr}, {c.trace ? "d_hits" : "d_samples", c.out}}))
     return st;

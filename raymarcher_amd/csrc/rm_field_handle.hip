@@ -6,10 +6,10 @@
 //   One lane per point or ray, 256-lane workgroups, one launch per call.  A record is two 16-byte stores.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 
 #include "../../include/raymarcher_amd.h"
+#include "rm_field_check.h"
 #include "rm_field_skip.h"
 #include "rm_internal.h"
 
@@ -29,8 +29,6 @@ namespace rm {
 
 int enqueue_block_map(const int32_t *d_blocks, int numBlocks, int mx, int my, int mz, uint32_t *first, hipStream_t stream);  // rm_blocks.hip
 
-static_assert(sizeof(fm::Sample) == 32 && sizeof(RmFieldSample) == 32 && sizeof(fm::Hit) == 32 && sizeof(RmRayHit) == 32, "two float4 per record");
-static_assert(fm::kInvalid == RM_RAY_INVALID && fm::kOutside == RM_FIELD_OUTSIDE && fm::kUnlisted == RM_FIELD_UNLISTED, "the header's codes");
 static_assert(RM_FIELD_PENUMBRA_K == 8.0f, "rm_field_skip.h has the 8 written out");
 constexpr uint32_t kMagic = 0x524d4644u;  // "RMFD"
 
@@ -69,11 +67,8 @@ __global__ __launch_bounds__(256) void handle_trace_kernel(const float4 *__restr
   out[2 * i + 1] = make_float4(h.position[0], h.position[1], h.position[2], __int_as_float(h.objectId));
 }
 
-static bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-static int bad(const char *msg) {
-  set_error(msg);
-  return (int)RM_ERR_INVALID_ARGUMENT;
-}
+using fchk::aligned;
+using fchk::bad;
 
 // frees what a create has allocated unless the handle took it over
 struct Owned {
@@ -85,21 +80,15 @@ struct Owned {
   }
 };
 
-// What both creates check, in the header's order; all but the last before any HIP call.  Dense: blocks = nullptr, numBlocks = −1.
+// What both creates check, in the header's order (the steps rm_field.hip shares are rm_field_check.h's); all but the last before
+// any HIP call.  Dense: blocks = nullptr, numBlocks = −1.
 static int check_create(const float *dist, const int32_t *ids, const int32_t *blocks, int numBlocks, bool sparse, const int dims[3],
                         const float *origin, const float *step, RmField **field) {
-  if (sparse) {
-    if (int st = check_block_lattice(origin, step, dims[0], dims[1], dims[2])) return st;
-    if (numBlocks < 0 || numBlocks > RM_MAX_BLOCK_LIST) return bad("numBlocks must be 0 … RM_MAX_BLOCK_LIST");
-  } else {
-    if (int st = check_lattice(origin, step, dims[0], dims[1], dims[2])) return st;
-    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return bad("every lattice dimension must be at least 2: a query needs a cell");
-  }
+  if (int st = fchk::check_field_lattice(sparse, dims, origin, step, numBlocks)) return st;
   if (!field) return bad("null field");
-  const bool emptyList = sparse && numBlocks == 0;  // nothing of d_dist is ever read
-  if (!dist && !emptyList) return bad("null d_dist");
-  if (sparse && numBlocks > 0 && !blocks) return bad("null d_blocks with numBlocks above 0");
-  if (!aligned(dist, 4) || !aligned(ids, 4) || !aligned(blocks, 4)) return bad("misaligned d_dist, d_objectId or d_blocks (4 bytes)");
+  if (int st = fchk::check_field_arrays(nullptr, nullptr, dist, ids, blocks, numBlocks, sparse, "null d_dist",
+                                        "misaligned d_dist, d_objectId or d_blocks (4 bytes)"))
+    return st;
   return require_device_pointers({{"d_dist", dist}, {"d_objectId", ids}, {"d_blocks", numBlocks > 0 ? blocks : nullptr}});
 }
 
@@ -137,13 +126,10 @@ static int check_query(const RmField *f, const void *in, int count, bool trace, 
   *launch = false;
   if (!f || !aligned(f, alignof(RmField)) || f->magic != kMagic) return bad("null or stale RmField handle");
   if (count < 0) return bad(trace ? "negative numRays" : "negative numPoints");
-  if (trace) {
-    if (!std::isfinite(iso)) return bad("iso must be finite");
-    if (maxSteps < 0 || maxSteps > RM_MAX_FIELD_STEPS) return bad("maxSteps must be 0 … RM_MAX_FIELD_STEPS (65536)");
-    if ((mode & ~(RM_TRACE_NO_NORMAL | RM_TRACE_OCCLUSION)) != 0u) return bad("mode bits other than RM_TRACE_NO_NORMAL and RM_TRACE_OCCLUSION");
-    if ((mode & RM_TRACE_NO_NORMAL) && (mode & RM_TRACE_OCCLUSION))
-      return bad("RM_TRACE_NO_NORMAL is a flag on RM_TRACE_CLOSEST: occlusion stores no normal anyway");
-  }
+  if (trace)
+    if (int st = fchk::check_field_march(iso, maxSteps, mode, RM_TRACE_NO_NORMAL | RM_TRACE_OCCLUSION,
+                                         "mode bits other than RM_TRACE_NO_NORMAL and RM_TRACE_OCCLUSION"))
+      return st;
   if (count == 0) return RM_OK;
   if (!in || !out) return bad(trace ? "null d_rays or d_hits" : "null d_points or d_samples");
   if (!aligned(in, 16) || !aligned(out, 16)) return bad(trace ? "misaligned d_rays or d_hits (16 bytes)" : "misaligned d_points or d_samples (16 bytes)");

@@ -1,8 +1,10 @@
 // rm_launch.h — what the launcher (rm_launcher.hip) hands the launch functions of the kernels (rm_kernels.hip; declared in
 // rm_internal.h): the arguments every render launch of a frame shares and the plans of its tile order, light split and
-// wavefront pipeline.
+// wavefront pipeline; and what it lends the query entry points (rm_queries.hip): the one-block staging call and the shared checks.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <functional>
 
 #include "rm_scene_block.h"
 #include "rm_wavefront.h"
@@ -56,5 +58,34 @@ struct Wavefront {
   int primaryWaves = 0, shadowWaves = 0, flush = 16;
   uint32_t slotChunk = 0, maxChunk = 0, rayChunk = 0, pixelChunk = 0;
 };
+
+// ---- what the launcher lends the query entry points (rm_queries.hip) -----------------------------------------------------------
+// "One block, one launch": the description of a call that stages ONE scene block of one table and launches behind it.
+struct BlockCall {
+  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s;
+  hipStream_t stream;
+  int path;                         // what rm_debug_last_path reports behind the launch
+  const RmCamera *cam = nullptr;    // null: a camera of zeros
+  const RmLight *lights = nullptr; int numLights = 0;
+  const RmResources *res = nullptr; // null: none
+  bool singleFrameRing = false;     // the slot's ring: the batch ring, or (the probes) the ring of single frames
+  bool timed = true;                // false (the probes): no timing stamps, no path, only the slot's event follows the launch
+  size_t workspaceBytes = 0;        // not 0: that much of the stream's kWsBlocks workspace, taken under the device's lock ahead of the staging
+  void (*afterFill)(SceneBlock *host) = nullptr;  // the occlusion mode's own staged fields (rm_trace_rays); not a second fill
+};
+// The launch behind the staged block (device and pinned host copy) with the call's workspace, or null: an rm_status.
+using BlockLaunch = std::function<int(const SceneBlock *dev, const SceneBlock *host, void *workspace)>;
+// The device and its lock, the workspace, a slot of the ring filled by fill_frames and uploaded, the timing's start, the launch,
+// then the timing's end, the path and the slot's event (rm_launcher.hip).
+int stage_block_launch(const BlockCall &c, const BlockLaunch &launch);
+
+// The checks the launcher's own entry points share with the queries: a scene without resources, the pointers of a call's
+// resources and outputs, and the refusals of the entry points that are defined by the object table alone, each with the entry
+// point's own text.
+extern const RmResources kNoResources;
+int check_device_pointers(const RmResources &res, const float *d_rgba, const float *d_bright);
+int refuse_layers(const RmSettings *s, const char *text);
+int refuse_two_d(const RmGlobals *g, const char *text);
+int check_image_width(int imageWidth);
 
 }  // namespace rm

@@ -1,7 +1,8 @@
 // rm_launcher.hip — the launcher of the per-pixel raymarch and the C ABI (gfx950 only): per-device and per-stream state (scene
-// block rings, tuners, workspaces, tile-order history), the plan of a launch, the single-frame and multi-frame launch paths and
-// every rm_* entry point that touches the GPU.  Host code only: the kernels and the functions that launch them are in
-// rm_kernels.hip and its sibling translation units (declared in rm_internal.h), the scene prep that needs no GPU in rm_frame.cpp.
+// block rings, tuners, workspaces, tile-order history), the plan of a launch, the single-frame and multi-frame launch paths, the
+// rm_render* entry points, the conversions, timing and debug entries, and stage_block_launch, the one staging call of the query
+// entry points (rays, points, lattices, probes: rm_queries.hip).  Host code only: the kernels and the functions that launch them are
+// in rm_kernels.hip and its sibling translation units (declared in rm_internal.h), the scene prep that needs no GPU in rm_frame.cpp.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -300,6 +301,38 @@ int release_workspaces(size_t *freedOut) {
   if (freedOut) *freedOut = freed;
   return RM_OK;
 }
+
+// ---- the checks shared with the query entry points (rm_queries.hip; declared in rm_launch.h) -----------------------------------
+int check_device_pointers(const RmResources &res, const float *d_rgba, const float *d_bright) {
+  if (int st = require_device_pointers({{"d_rgba", d_rgba}, {"d_bright", d_bright}})) return st;
+  for (int i = 0; i < res.numTextures; i++)
+    if (int st = require_device_pointers({{"a texture's pixels", res.textures[i].pixels}})) return st;
+  if (int st = require_device_pointers({{"RmResources.noise.pixels", res.noise.pixels}})) return st;
+  for (int f = 0; f < 6; f++)
+    if (int st = require_device_pointers({{"a sky-box face", res.skybox[f].pixels}})) return st;
+  return require_device_pointers({{"RmResources.ltc1", res.ltc1}, {"RmResources.ltc2", res.ltc2}});
+}
+const RmResources kNoResources{};
+// The refusals of the entry points that are defined by the object table alone, each with the entry point's own text: the layers
+// that may cover the table, and the 2-D mode, which marches no ray.
+int refuse_layers(const RmSettings *s, const char *text) {
+  if (!(s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA))) return RM_OK;
+  set_error(text);
+  return RM_ERR_UNSUPPORTED;
+}
+// The width of the image the rays belong to (rm_shade_rays_layers, rm_trace_rays_layers): checked in every call, whatever the
+// feature mask, so that the status does not depend on it.
+int check_image_width(int imageWidth) {
+  if (imageWidth >= 1) return RM_OK;
+  set_error("imageWidth must be at least 1: the width in pixels of the image the rays belong to");
+  return RM_ERR_INVALID_ARGUMENT;
+}
+int refuse_two_d(const RmGlobals *g, const char *text) {
+  if (!g->isTwoD) return RM_OK;
+  set_error(text);
+  return RM_ERR_UNSUPPORTED;
+}
+
 namespace {
 
 // Carve the wavefront pipeline's records for `cap` hit slots and `nl` lights out of the stream's workspace.
@@ -337,17 +370,6 @@ int wavefront_workspace(size_t cap, int nl, hipStream_t stream, WfWs *ws) {
   ws->cap = (uint32_t)cap;
   return RM_OK;
 }
-
-int check_device_pointers(const RmResources &res, const float *d_rgba, const float *d_bright) {
-  if (int st = require_device_pointers({{"d_rgba", d_rgba}, {"d_bright", d_bright}})) return st;
-  for (int i = 0; i < res.numTextures; i++)
-    if (int st = require_device_pointers({{"a texture's pixels", res.textures[i].pixels}})) return st;
-  if (int st = require_device_pointers({{"RmResources.noise.pixels", res.noise.pixels}})) return st;
-  for (int f = 0; f < 6; f++)
-    if (int st = require_device_pointers({{"a sky-box face", res.skybox[f].pixels}})) return st;
-  return require_device_pointers({{"RmResources.ltc1", res.ltc1}, {"RmResources.ltc2", res.ltc2}});
-}
-const RmResources kNoResources{};
 
 // The fields of a SceneBlock that the launch decides, the same in every block of the launch (the defaults: raster order, no
 // cost feedback, 8×8 tiles, no light split).
@@ -722,25 +744,6 @@ int check_frames(const FrameCall &c, int ss, bool sampled, int (*sizeCheck)(cons
   if (!c.d_rgba) { set_error("null output buffer"); return RM_ERR_INVALID_ARGUMENT; }
   return check_device_pointers(c.res, c.d_rgba, c.d_bright);
 }
-// The refusals of the entry points that are defined by the object table alone, each with the entry point's own text: the layers
-// that may cover the table, and the 2-D mode, which marches no ray.
-int refuse_layers(const RmSettings *s, const char *text) {
-  if (!(s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA))) return RM_OK;
-  set_error(text);
-  return RM_ERR_UNSUPPORTED;
-}
-// The width of the image the rays belong to (rm_shade_rays_layers, rm_trace_rays_layers): checked in every call, whatever the
-// feature mask, so that the status does not depend on it.
-int check_image_width(int imageWidth) {
-  if (imageWidth >= 1) return RM_OK;
-  set_error("imageWidth must be at least 1: the width in pixels of the image the rays belong to");
-  return RM_ERR_INVALID_ARGUMENT;
-}
-int refuse_two_d(const RmGlobals *g, const char *text) {
-  if (!g->isTwoD) return RM_OK;
-  set_error(text);
-  return RM_ERR_UNSUPPORTED;
-}
 
 // What the staging step hands a launcher, and what holds the device's lock for it: from lock_device (or stage_blocks) until the
 // object goes, behind finish_frames.
@@ -1044,324 +1047,31 @@ int launch_gbuffer(const FrameCall &c, float *d_normalDepth, int32_t *d_objectId
                                   d_objectId, d_position, c.stream)) != RM_OK) return st;
   return finish_frames(sf, 11);
 }
-
-// ---- rays from memory: closest hits and occlusion (rm_trace_rays) -----------------------------------------------------------------
-// rm_trace_rays (the header has the definition): the caller's rays against ONE object table.  Its checks run in check_gbuffer's
-// order, every one but the last ahead of the first HIP call: numRays (negative; zero is RM_OK; every int fits one grid of
-// 256-lane workgroups), the scene pointers, the mode bits, the layers and the 2-D mode a ray is not defined through, the
-// table's limits and types, the arrays (null, alignment of the float4 accesses), then whether they are device memory.
-// Staging is stage_blocks of one block, filled with a zeroed camera, no lights and no resources — the evaluation records, the
-// cull ball and box with cullLip and cullOneOk, bulbPlain.  rayPlane and cam are staged (zeros) and never read.  The occlusion mode
-// stages two fields of its own: s.enableSoftShadow = 1, so that march<…, kShadow> tracks the penumbra factor whatever the caller's
-// settings say, and cullR2Soft = 0.  scene_cull_ball derives that larger ball for shadow rays that start on a surface, inside the
-// cull ball, where t <= ρ + R; a caller's ray may start anywhere, so with it a far origin would settle the factor too early.
-// Without it a soft march ends at tMax, as the reference's does.  (The hard bounds — ball, box, the bulb's own ball — argue about
-// points, not origins, and hold for any ray.)
-// Then ONE launch of trace_kernel (rm_trace.hip), path 12: no tuner, tile-order or workspace state is read or changed.
-// rm_trace_rays_layers is the same call with TraceCall.layers set: imageWidth is checked behind the mode bits, the refusal of the
-// layers holds only for the occlusion mode, the launch is trace_layers_kernel (rm_layers.hip) when TERRAIN or SEA is set, path 15.
-struct TraceCall {
-  const RmRay *d_rays; int numRays;
-  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s;
-  unsigned mode; RmRayHit *d_hits; hipStream_t stream;
-  bool layers = false; int imageWidth = 1;  // rm_trace_rays_layers: the layers are traced, not refused
-};
-int check_trace(const TraceCall &c) {
-  if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.numRays == 0) return RM_OK;
-  static_assert(((long long)INT_MAX + 255) / 256 <= INT_MAX, "every int numRays fits one grid of 256-lane workgroups");
-  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || c.numObjects < 0) {
-    set_error("null scene pointer or negative count");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if (c.mode & ~(RM_TRACE_NO_NORMAL | RM_TRACE_OCCLUSION)) { set_error("unknown mode bits"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((c.mode & RM_TRACE_NO_NORMAL) && (c.mode & RM_TRACE_OCCLUSION)) {
-    set_error("RM_TRACE_NO_NORMAL is a flag on RM_TRACE_CLOSEST: occlusion stores no normal anyway");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  int st = RM_OK;
-  if (!c.layers) st = refuse_layers(c.s, "rm_trace_rays traces the object table: rays through TERRAIN / CLOUD / SEA are not defined");
-  else if ((st = check_image_width(c.imageWidth)) == RM_OK && (c.mode & RM_TRACE_OCCLUSION))
-    st = refuse_layers(c.s, "RM_TRACE_OCCLUSION is the objects' shadow march: it does not see TERRAIN / CLOUD / SEA");
-  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
-  if ((st = check_object_table(c.objs, c.numObjects, c.s)) != RM_OK) return st;
-  if (!c.d_rays || !c.d_hits) { set_error("null d_rays or d_hits"); return RM_ERR_INVALID_ARGUMENT; }
-  if (((uintptr_t)c.d_rays | (uintptr_t)c.d_hits) & 15u) { set_error("d_rays and d_hits must be 16-byte aligned"); return RM_ERR_INVALID_ARGUMENT; }
-  return require_device_pointers({{"d_rays", c.d_rays}, {"d_hits", c.d_hits}});
-}
-int launch_trace(const TraceCall &c) {
-  int st = check_trace(c);
-  if (st != RM_OK || c.numRays == 0) return st;
-  const bool occlusion = (c.mode & RM_TRACE_OCCLUSION) != 0;
-  const int bulbClass = table_bulb_class(c.objs, c.numObjects, bulb_plain(c.objs, c.numObjects, c.g) != 0);
-  RmSettings s = *c.s;
-  if (occlusion) s.enableSoftShadow = 1;
-  const RmCamera noCam{};
-  StagedFrames sf(c.stream);
-  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, &s, kNoResources);
-        if (occlusion) h->cullR2Soft = 0.0f;
-      })) != RM_OK) return st;
-  // the layers' kernel only where a layer has a surface: without one (CLOUD alone is a volume) rm_trace_rays' own kernels run
-  const bool noNormal = (c.mode & RM_TRACE_NO_NORMAL) != 0;
-  if (c.layers && (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_SEA)))
-    st = launch_trace_layers_kernel(sf.slot->dev, bulbClass, noNormal, c.d_rays, c.numRays, c.imageWidth, c.d_hits, c.stream);
-  else st = launch_trace_kernel(sf.slot->dev, bulbClass, occlusion, noNormal, c.d_rays, c.numRays, c.d_hits, c.stream);
-  if (st != RM_OK) return st;
-  return finish_frames(sf, c.layers ? 15 : 12);
-}
-
-// ---- rays from memory: the full colour (rm_shade_rays) ----------------------------------------------------------------------------
-// rm_shade_rays (the header has the definition): the shader's whole main for the caller's rays against ONE scene.  ShadeCall stands
-// beside TraceCall; its checks run in check_trace's order, every one but the last ahead of the first HIP call: numRays (negative;
-// zero is RM_OK), the scene pointers and counts, far, the layers and the 2-D mode a ray is not defined through, then what
-// validate_scene checks of a frame — the limits, the loop bounds, the samplers a feature, an object or a light reads, the types,
-// with rm_render_res's statuses and texts — the arrays (null, alignment of the float4 accesses), and whether they, and the
-// resources' pixels, are device memory.
-// Staging is stage_blocks of one block, filled with the caller's lights and resources and a camera that is zeros but for
-// initialFar = far — the one far every device function reads, wave-uniform (a per-ray far would change which lane of the shadow
-// pool ends a pooled ray where).  rayPlane and the rest of cam are staged and never read.  The class is the frame's
-// (classify_frame, bulb_class with the plain form where bulb_plain finds it).  Then ONE launch of shade_rays_kernel
-// (rm_shade.hip), path 13: no wavefront pipeline, no light split, no tuner, tile-order or workspace state is read or changed.
-// rm_shade_rays_layers is the same call with ShadeCall.layers set: imageWidth is checked in place of the refusal of the layers, the
-// launch is shade_rays_layers_kernel (rm_layers.hip) when a layer bit is set, path 14.
-struct ShadeCall {
-  const RmRay *d_rays; int numRays; float far;
-  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
-  const RmGlobals *g; const RmSettings *s; const RmResources &res;
-  float *d_rgba, *d_bright; hipStream_t stream;
-  bool layers = false; int imageWidth = 1;  // rm_shade_rays_layers: the layers are shaded, not refused
-};
-int check_shade(const ShadeCall &c, const RmCamera &cam) {
-  if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.numRays == 0) return RM_OK;
-  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.numLights > 0 && !c.lights) || c.numObjects < 0 || c.numLights < 0) {
-    set_error("null scene pointer or negative count");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if (!(c.far >= 0.0f) || c.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = RM_OK;
-  if (c.layers) st = check_image_width(c.imageWidth);
-  else st = refuse_layers(c.s, "rm_shade_rays shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
-  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
-  if ((st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) != RM_OK) return st;
-  if (!c.d_rays || !c.d_rgba) { set_error("null d_rays or d_rgba"); return RM_ERR_INVALID_ARGUMENT; }
-  if (((uintptr_t)c.d_rays | (uintptr_t)c.d_rgba | (uintptr_t)c.d_bright) & 15u) {
-    set_error("d_rays, d_rgba and d_bright must be 16-byte aligned");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if ((st = require_device_pointers({{"d_rays", c.d_rays}})) != RM_OK) return st;
-  return check_device_pointers(c.res, c.d_rgba, c.d_bright);
-}
-int launch_shade(const ShadeCall &c) {
-  RmCamera cam{};
-  cam.initialFar = c.far;
-  int st = check_shade(c, cam);
-  if (st != RM_OK || c.numRays == 0) return st;
-  const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
-  const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
-  StagedFrames sf(c.stream);
-  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
-      })) != RM_OK) return st;
-  // the layers' kernel only with a layer bit (then fc.envFeatures is set and bulbClass is 0): without one, rm_shade_rays' twelve classes
-  if (c.layers && (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)))
-    st = launch_shade_layers_kernel(sf.slot->dev, fc.textured, fc.secondary, c.d_rays, c.numRays, c.imageWidth, c.d_rgba, c.d_bright,
-                                    c.stream);
-  else st = launch_shade_kernel(sf.slot->dev, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba, c.d_bright,
-                                c.stream);
-  if (st != RM_OK) return st;
-  return finish_frames(sf, c.layers ? 14 : 13);
-}
-
-// ---- points from memory (rm_shade_points) -----------------------------------------------------------------------------------------
-// rm_shade_points (the header has the definition): the scene's distance, object, normal, ambient occlusion and shaded colour at the
-// caller's points against ONE scene.  PointsCall stands beside ShadeCall and its checks run in check_shade's order with its helpers,
-// every one but the last ahead of the first HIP call: numPoints, the pointers and counts, the point settings, the outputs (at least
-// one), the layers and the 2-D mode, the scene, the arrays, device memory.  Only a call with d_rgba reads lights and samplers: it is
-// checked and staged as launch_shade's (validate_scene, the caller's lights and resources, the frame's class); a call without it as
-// launch_trace's (check_object_table, no lights, no resources, the table's march class).  The camera is zeros but for initialFar =
-// ps->far.  Then ONE launch of shade_points_kernel (rm_points.hip), path 17: no tuner, tile-order or workspace state is read or changed.
-struct PointsCall {
-  const float *d_points, *d_view; int numPoints; const RmPointsSettings *ps;
-  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
-  const RmGlobals *g; const RmSettings *s; const RmResources &res;
-  RmSurfacePoint *d_surface; float *d_ao, *d_rgba; hipStream_t stream;
-};
-int check_points(const PointsCall &c, const RmCamera &cam) {
-  if (c.numPoints < 0) { set_error("negative numPoints"); return RM_ERR_INVALID_ARGUMENT; }
-  if (c.numPoints == 0) return RM_OK;
-  if (!c.ps || !c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.d_rgba && c.numLights > 0 && !c.lights) || c.numObjects < 0 ||
-      c.numLights < 0) {
-    set_error("null ps, scene pointer or negative count");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  const RmPointsSettings &ps = *c.ps;
-  if (!(ps.far >= 0.0f) || ps.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!(ps.iso - ps.iso == 0.0f)) { set_error("iso must be finite"); return RM_ERR_INVALID_ARGUMENT; }
-  if (!(ps.maxMove >= 0.0f)) { set_error("maxMove must not be negative (+inf: no limit)"); return RM_ERR_INVALID_ARGUMENT; }
-  if (ps.projectSteps < 0 || ps.projectSteps > RM_MAX_PROJECT_STEPS) {
-    set_error("projectSteps outside 0 … RM_MAX_PROJECT_STEPS");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if (!c.d_surface && !c.d_ao && !c.d_rgba) { set_error("d_surface, d_ao and d_rgba are all null: nothing to compute"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = refuse_layers(c.s, "rm_shade_points shades points of the object table: TERRAIN / CLOUD / SEA have no distance field here");
-  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) has no surface points")) != RM_OK) return st;
-  if (c.d_rgba) st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res);
-  else st = check_object_table(c.objs, c.numObjects, c.s);
-  if (st != RM_OK) return st;
-  if (!c.d_points) { set_error("null d_points"); return RM_ERR_INVALID_ARGUMENT; }
-  if (((uintptr_t)c.d_points | (uintptr_t)c.d_view | (uintptr_t)c.d_surface | (uintptr_t)c.d_rgba) & 15u) {
-    set_error("d_points, d_view, d_surface and d_rgba must be 16-byte aligned");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if ((uintptr_t)c.d_ao & 3u) { set_error("d_ao must be 4-byte aligned"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = require_device_pointers({{"d_points", c.d_points}, {"d_view", c.d_view}, {"d_surface", c.d_surface}, {"d_ao", c.d_ao}})) != RM_OK)
-    return st;
-  return c.d_rgba ? check_device_pointers(c.res, c.d_rgba, nullptr) : RM_OK;
-}
-int launch_points(const PointsCall &c) {
-  RmCamera cam{};
-  if (c.ps) cam.initialFar = c.ps->far;
-  int st = check_points(c, cam);
-  if (st != RM_OK || c.numPoints == 0) return st;
-  const bool plain = bulb_plain(c.objs, c.numObjects, c.g) != 0;
-  int bulbClass = table_bulb_class(c.objs, c.numObjects, plain);
-  bool tex = false;
-  if (c.d_rgba) {
-    const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
-    bulbClass = bulb_class(fc, plain);
-    tex = fc.textured;
-  }
-  StagedFrames sf(c.stream);
-  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        if (c.d_rgba) fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res);
-        else fill_frames(h, 1, &cam, c.g, 1, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
-      })) != RM_OK) return st;
-  if ((st = launch_points_kernel(sf.slot->dev, bulbClass, tex, c.d_points, c.d_view, c.numPoints, c.ps->projectSteps, c.ps->iso,
-                                 c.ps->maxMove, c.d_surface, c.d_ao, c.d_rgba, c.stream)) != RM_OK) return st;
-  return finish_frames(sf, 17);
-}
-
-// ---- the field on a lattice (rm_sdf_grid) ----------------------------------------------------------------------------------------
-// rm_sdf_grid (the header has the definition): sdScene at the points of a dense lattice against ONE object table.  The checks run in
-// the header's order, every one but the last ahead of the first HIP call: the pointers and the table's count, the lattice
-// (check_lattice, which rm_sdf_mesh shares), the layers and the 2-D mode, check_trace's table checks, then d_dist and whether the
-// outputs are device memory.  Staging is launch_trace's: stage_blocks of one block of the batch ring, filled with a camera of zeros
-// and no lights.  Then ONE launch of sdf_grid_kernel (rm_volume.hip) of the table's march class, path 16: no tuner, tile-order or
-// workspace state is read or changed.
-int launch_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float *origin, const float *step,
-                    int nx, int ny, int nz, float *d_dist, int32_t *d_objectId, hipStream_t stream) {
-  if (!g || !s || !origin || !step) { set_error("null g, s, origin or step"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((numObjects > 0 && !objs) || numObjects < 0) { set_error("null object table or negative count"); return RM_ERR_INVALID_ARGUMENT; }
-  int st = check_lattice(origin, step, nx, ny, nz);
-  if (st != RM_OK) return st;
-  if ((st = refuse_layers(s, "rm_sdf_grid evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK) return st;
-  if ((st = refuse_two_d(g, "the 2-D mode (isTwoD) has no distance field")) != RM_OK) return st;
-  if ((st = check_object_table(objs, numObjects, s)) != RM_OK) return st;
-  if (!d_dist) { set_error("null d_dist"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = require_device_pointers({{"d_dist", d_dist}, {"d_objectId", d_objectId}})) != RM_OK) return st;
-  const int bulbClass = table_bulb_class(objs, numObjects, bulb_plain(objs, numObjects, g) != 0);
-  const RmCamera noCam{};
-  StagedFrames sf(stream);
-  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &noCam, g, 1, objs, numObjects, nullptr, 0, s, kNoResources);
-      })) != RM_OK) return st;
-  if ((st = launch_sdf_grid_kernel(sf.slot->dev, bulbClass, origin, step, nx, ny, nz, d_dist, d_objectId, stream)) != RM_OK) return st;
-  return finish_frames(sf, 16);
-}
-
-// ---- the field on the blocks of a virtual lattice (rm_sdf_blocks_select, rm_sdf_grid_blocks) -------------------------------------
-// Both (the header has the definitions) are rm_sdf_grid on blocks of 8×8×8 cells: launch_sdf_grid's checks in its order with
-// check_block_lattice in check_lattice's place and the call's own behind it, every one but the last ahead of the first HIP call;
-// launch_sdf_grid's staging behind the stream's workspace (kWsBlocks), which is taken under the device's lock as launch_adaptive
-// takes its own.  rm_sdf_blocks_select: one launch of blocks_eval_kernel (rm_blocks.hip) over every block of the lattice, which
-// keeps a flag per block, and the compaction of the flags, path 18; rm_sdf_blocks_select_pruned: the same flags from the kernels of
-// rm_blocks_prune.hip, which evaluate only the blocks near the surface, path 20.  rm_sdf_grid_blocks: the block map of the list
-// (void entries), then one launch of blocks_eval_kernel over the list's entries, path 19.
-struct BlocksCall {
-  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s; const float *origin, *step; int mx, my, mz;
-  hipStream_t stream;
-};
-int check_blocks_scene(const BlocksCall &c, const char *layersText) {
-  int st = refuse_layers(c.s, layersText);
-  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) has no distance field")) != RM_OK) return st;
-  return check_object_table(c.objs, c.numObjects, c.s);
-}
-int check_blocks_head(const BlocksCall &c) {
-  if (!c.g || !c.s || !c.origin || !c.step) { set_error("null g, s, origin or step"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((c.numObjects > 0 && !c.objs) || c.numObjects < 0) { set_error("null object table or negative count"); return RM_ERR_INVALID_ARGUMENT; }
-  return check_block_lattice(c.origin, c.step, c.mx, c.my, c.mz);
-}
-template <class Launch>
-int stage_blocks_call(const BlocksCall &c, size_t workspaceBytes, int path, Launch launch) {
-  const int bulbClass = table_bulb_class(c.objs, c.numObjects, bulb_plain(c.objs, c.numObjects, c.g) != 0);
-  const RmCamera noCam{};
-  StagedFrames sf(c.stream);
-  int st = sf.lock_device();  // ahead of the workspace, which is in use until the last launch (rm_release_workspaces)
-  if (st != RM_OK) return st;
-  void *mem = nullptr;
-  if ((st = stream_workspace(kWsBlocks, c.stream, workspaceBytes, &mem)) != RM_OK) return st;
-  if ((st = stage_blocks(&sf, &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &noCam, c.g, 1, c.objs, c.numObjects, nullptr, 0, c.s, kNoResources);
-      })) != RM_OK) return st;
-  if ((st = launch(sf.slot->dev, bulbClass, mem)) != RM_OK) return st;
-  return finish_frames(sf, path);
-}
-// lipschitz: null for rm_sdf_blocks_select; (lipschitzOut, lipschitzIn) for rm_sdf_blocks_select_pruned, which has the same checks
-// with its own between iso and maxBlocks, the same staging, the kernels of rm_blocks_prune.hip and path 20.
-int launch_sdf_blocks_select(const BlocksCall &c, float iso, const float *lipschitz, int maxBlocks, int32_t *d_blocks, uint32_t *d_count) {
-  int st = check_blocks_head(c);
-  if (st != RM_OK) return st;
-  if (!(iso - iso == 0.0f)) { set_error("iso must be finite"); return RM_ERR_INVALID_ARGUMENT; }
-  if (lipschitz && !(lipschitz[0] >= 0.0f && lipschitz[1] >= 0.0f)) {
-    set_error("lipschitzOut and lipschitzIn must not be NaN or negative (+inf: that side discards nothing)");
-    return RM_ERR_INVALID_ARGUMENT;
-  }
-  if (maxBlocks < 0) { set_error("negative maxBlocks"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = check_blocks_scene(c, "rm_sdf_blocks_select evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK)
-    return st;
-  if ((maxBlocks > 0 && !d_blocks) || !d_count) { set_error("null d_count, or null d_blocks with maxBlocks above 0"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = require_device_pointers({{"d_blocks", d_blocks}, {"d_count", d_count}})) != RM_OK) return st;
-  if (lipschitz)
-    return stage_blocks_call(c, blocks_prune_workspace(c.mx, c.my, c.mz), 20, [&](const SceneBlock *sb, int bulbClass, void *mem) {
-      return launch_blocks_prune_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, iso, lipschitz[0], lipschitz[1], maxBlocks, d_blocks,
-                                         d_count, mem, c.stream);
-    });
-  return stage_blocks_call(c, blocks_select_workspace(c.mx, c.my, c.mz), 18, [&](const SceneBlock *sb, int bulbClass, void *mem) {
-    return launch_blocks_select_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, iso, maxBlocks, d_blocks, d_count, mem, c.stream);
-  });
-}
-int launch_sdf_grid_blocks(const BlocksCall &c, const int32_t *d_blocks, int numBlocks, float *d_dist, int32_t *d_objectId) {
-  int st = check_blocks_head(c);
-  if (st != RM_OK) return st;
-  if (numBlocks < 0 || numBlocks > RM_MAX_BLOCK_LIST) { set_error("numBlocks must be 0 … RM_MAX_BLOCK_LIST"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = check_blocks_scene(c, "rm_sdf_grid_blocks evaluates the object table: TERRAIN / CLOUD / SEA are not part of the lattice")) != RM_OK)
-    return st;
-  if (numBlocks == 0) return RM_OK;
-  if (!d_blocks || !d_dist) { set_error("null d_blocks or d_dist"); return RM_ERR_INVALID_ARGUMENT; }
-  if ((st = require_device_pointers({{"d_blocks", d_blocks}, {"d_dist", d_dist}, {"d_objectId", d_objectId}})) != RM_OK) return st;
-  return stage_blocks_call(c, blocks_map_workspace(c.mx, c.my, c.mz), 19, [&](const SceneBlock *sb, int bulbClass, void *mem) {
-    return launch_blocks_grid_kernels(sb, bulbClass, c.origin, c.step, c.mx, c.my, c.mz, d_blocks, numBlocks, d_dist, d_objectId, mem, c.stream);
-  });
-}
-
-// The scene evaluator's probes (rm_probe_sdscene*): the table staged as a frame's (zero camera, no lights) on the ring of
-// single frames, then launch(the device's block) behind it.
-template <class Launch>
-int probe_scene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, hipStream_t stream, Launch launch,
-                const RmLight *lights = nullptr, int numLights = 0) {
-  StagedFrames sf(stream);
-  sf.timer.on = false;  // a probe is no timed launch: only the slot's event follows it
-  const RmCamera cam{};
-  if (int st = stage_blocks(&sf, &DeviceState::frames, 1, LaunchFields{}, false, [&](SceneBlock *h) {
-        fill_frames(h, 1, &cam, g, 1, objs, numObjects, lights, numLights, s, kNoResources);
-      })) return st;
-  const int st = launch(sf.slot->dev);
-  HIP_OK(hipEventRecord(sf.slot->done, stream));
-  return st;
-}
 }  // namespace
+
+// ---- one block, one launch: what the query entry points (rm_queries.hip) are staged with -----------------------------------------
+// rm_launch.h has the call.  The device's lock first where the call takes a workspace, which is in use until the last launch
+// (rm_release_workspaces); stage_blocks of one block filled by fill_frames; the launch; finish_frames.  An untimed call (the
+// probes) takes no stamps and ends with the slot's event alone, whatever the launch returned.
+int stage_block_launch(const BlockCall &c, const BlockLaunch &launch) {
+  const RmCamera noCam{};
+  StagedFrames sf(c.stream);
+  sf.timer.on = sf.timer.on && c.timed;
+  int st = RM_OK;
+  void *mem = nullptr;
+  if (c.workspaceBytes != 0 && ((st = sf.lock_device()) != RM_OK || (st = stream_workspace(kWsBlocks, c.stream, c.workspaceBytes, &mem)) != RM_OK))
+    return st;
+  if ((st = stage_blocks(&sf, c.singleFrameRing ? &DeviceState::frames : &DeviceState::batches, 1, LaunchFields{}, false, [&](SceneBlock *h) {
+        fill_frames(h, 1, c.cam ? c.cam : &noCam, c.g, 1, c.objs, c.numObjects, c.lights, c.numLights, c.s, c.res ? *c.res : kNoResources);
+        if (c.afterFill) c.afterFill(h);
+      })) != RM_OK) return st;
+  st = launch(sf.slot->dev, sf.slot->host, mem);
+  if (!c.timed) {
+    HIP_OK(hipEventRecord(sf.slot->done, c.stream));
+    return st;
+  }
+  return st != RM_OK ? st : finish_frames(sf, c.path);
+}
 }  // namespace rm
 
 using namespace rm;
@@ -1443,70 +1153,6 @@ int rm_render_gbuffer(const RmCamera *cams, const RmGlobals *globals, int numGlo
                       const RmSettings *s, int W, int H, float *d_normalDepth, int32_t *d_objectId, float *d_position, void *stream) {
   return launch_gbuffer(FrameCall{cams, globals, numGlobals, numFrames, objs, numObjects, nullptr, 0, s, kNoResources, W, H, nullptr, nullptr,
                                   static_cast<hipStream_t>(stream)}, d_normalDepth, d_objectId, d_position);
-}
-
-int rm_trace_rays(const RmRay *d_rays, int numRays, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
-                  unsigned mode, RmRayHit *d_hits, void *stream) {
-  return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream)});
-}
-
-int rm_shade_rays(const RmRay *d_rays, int numRays, float far, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
-                  const RmGlobals *g, const RmSettings *s, const RmResources *res, float *d_rgba, float *d_bright, void *stream) {
-  return launch_shade(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba, d_bright,
-                                static_cast<hipStream_t>(stream)});
-}
-
-int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageWidth, const RmObject *objs, int numObjects,
-                         const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s, const RmResources *res, float *d_rgba,
-                         float *d_bright, void *stream) {
-  return launch_shade(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba, d_bright,
-                                static_cast<hipStream_t>(stream), true, imageWidth});
-}
-
-int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
-                         const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream) {
-  return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream), true, imageWidth});
-}
-
-void rm_points_settings_default(RmPointsSettings *ps) {
-  if (!ps) return;
-  ps->far = 100.0f;
-  ps->iso = 0.001f;
-  ps->maxMove = __builtin_inff();
-  ps->projectSteps = 0;
-}
-int rm_shade_points(const float *d_points, const float *d_view, int numPoints, const RmPointsSettings *ps, const RmObject *objs,
-                    int numObjects, const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s, const RmResources *res,
-                    RmSurfacePoint *d_surface, float *d_ao, float *d_rgba, void *stream) {
-  return launch_points(PointsCall{d_points, d_view, numPoints, ps, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources,
-                                  d_surface, d_ao, d_rgba, static_cast<hipStream_t>(stream)});
-}
-
-int rm_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3], const float step[3],
-                int nx, int ny, int nz, float *d_dist, int32_t *d_objectId, void *stream) {
-  return launch_sdf_grid(objs, numObjects, g, s, origin, step, nx, ny, nz, d_dist, d_objectId, static_cast<hipStream_t>(stream));
-}
-
-int rm_sdf_blocks_select(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
-                         const float step[3], int mx, int my, int mz, float iso, int maxBlocks, int32_t *d_blocks, uint32_t *d_count,
-                         void *stream) {
-  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, nullptr,
-                                  maxBlocks, d_blocks, d_count);
-}
-
-int rm_sdf_blocks_select_pruned(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
-                                const float step[3], int mx, int my, int mz, float iso, float lipschitzOut, float lipschitzIn, int maxBlocks,
-                                int32_t *d_blocks, uint32_t *d_count, void *stream) {
-  const float lipschitz[2] = {lipschitzOut, lipschitzIn};
-  return launch_sdf_blocks_select(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, iso, lipschitz,
-                                  maxBlocks, d_blocks, d_count);
-}
-
-int rm_sdf_grid_blocks(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float origin[3],
-                       const float step[3], int mx, int my, int mz, const int32_t *d_blocks, int numBlocks, float *d_dist,
-                       int32_t *d_objectId, void *stream) {
-  return launch_sdf_grid_blocks(BlocksCall{objs, numObjects, g, s, origin, step, mx, my, mz, static_cast<hipStream_t>(stream)}, d_blocks,
-                                numBlocks, d_dist, d_objectId);
 }
 
 int rm_render_counted_ex(const RmCamera *cam, const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
@@ -1735,73 +1381,6 @@ int rm_release_workspaces(unsigned long long *freedBytes) {
   ds->splitChoice.clear();
   if (freedBytes) *freedBytes = freed;
   return RM_OK;
-}
-
-int rm_probe_math(int fn, const float *d_x, const float *d_y, const float *d_z, float *d_out, int n, void *stream) {
-  if (fn < 0 || fn >= RM_FN_COUNT || !d_x || !d_out || n < 0) { set_error("bad probe arguments"); return RM_ERR_INVALID_ARGUMENT; }
-  if (int st = require_device_pointers({{"d_x", d_x}, {"d_y", d_y}, {"d_z", d_z}, {"d_out", d_out}})) return st;
-  if (n == 0) return RM_OK;
-  return launch_probe_math(fn, d_x, d_y, d_z, d_out, n, static_cast<hipStream_t>(stream));
-}
-
-int rm_probe_bump(const float *d_pts, float *d_out, int n, void *stream) {
-  if (!d_pts || !d_out || n < 0) { set_error("bad probe arguments"); return RM_ERR_INVALID_ARGUMENT; }
-  if (int st = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st;
-  if (n == 0) return RM_OK;
-  return launch_probe_bump(d_pts, d_out, n, static_cast<hipStream_t>(stream));
-}
-
-int rm_probe_sdscene(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, const float *d_pts,
-                     float *d_out, int n, void *stream) {
-  RmCamera cam{};
-  int st = validate_scene(&cam, objs, numObjects, nullptr, 0, g, s, kNoResources);
-  if (st != RM_OK) return st;
-  if (!d_pts || !d_out || n < 0) { set_error("bad probe arguments"); return RM_ERR_INVALID_ARGUMENT; }
-  if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st2;
-  if (n == 0) return RM_OK;
-  const hipStream_t hs = static_cast<hipStream_t>(stream);
-  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) { return launch_probe_sdscene(sb, d_pts, d_out, n, hs); });
-}
-
-int rm_probe_sdscene_variant(const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s, int bulbClass,
-                             int count, int trap, int skip, int track, int one, const float *d_pts, const float *d_ub,
-                             float *d_out, int n, void *stream) {
-  RmCamera cam{};
-  int st = validate_scene(&cam, objs, numObjects, nullptr, 0, g, s, kNoResources);
-  if (st != RM_OK) return st;
-  auto bad = [](const char *msg) { set_error(msg); return (int)RM_ERR_INVALID_ARGUMENT; };
-  if (!sdscene_variant_exists(bulbClass, count, trap, skip, track, one >= 0))
-    return bad("no production kernel instantiates this sdScene variant");
-  if (bulbClass != 0 && (numObjects != 1 || objs[0].type != RM_MANDELBULB)) return bad("a bulb class needs a table of one Mandelbulb");
-  if (bulbClass == kBulbPlain && !bulb_plain(objs, numObjects, g)) return bad("the plain bulb form does not apply to this table");
-  if (one < -1 || one >= numObjects || (one >= 0 && !(objs[one].type >= RM_CUBE && objs[one].type <= RM_RECTANGLE)))
-    return bad("`one` must name a primitive of the table");
-  if (!d_pts || !d_out || n < 0) return bad("bad probe arguments");
-  if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_ub", d_ub}, {"d_out", d_out}})) return st2;
-  if (n == 0) return RM_OK;
-  const hipStream_t hs = static_cast<hipStream_t>(stream);
-  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) {
-    return launch_sdscene_variant(sb, bulbClass, count, trap, skip, track, one, d_pts, d_ub, d_out, n, hs);
-  });
-}
-
-int rm_probe_pool_cull(const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
-                       const RmSettings *s, int bulbClass, int light, float far, const float *d_pts, float *d_out, int n, void *stream) {
-  RmCamera cam{};
-  int st = validate_scene(&cam, objs, numObjects, lights, numLights, g, s, kNoResources);
-  if (st != RM_OK) return st;
-  auto bad = [](const char *msg) { set_error(msg); return (int)RM_ERR_INVALID_ARGUMENT; };
-  if (bulbClass != kBulbGeneral && bulbClass != kBulbPlain) return bad("bulbClass must be 1 (general) or 2 (plain)");
-  if (numObjects != 1 || objs[0].type != RM_MANDELBULB) return bad("a bulb class needs a table of one Mandelbulb");
-  if (bulbClass == kBulbPlain && !bulb_plain(objs, numObjects, g)) return bad("the plain bulb form does not apply to this table");
-  if (light < 0 || light >= numLights || lights[light].type != RM_LIGHT_DIRECTIONAL) return bad("`light` must name a directional light of the table");
-  if (!d_pts || !d_out || n < 0) return bad("bad probe arguments");
-  if (int st2 = require_device_pointers({{"d_pts", d_pts}, {"d_out", d_out}})) return st2;
-  if (n == 0) return RM_OK;
-  const hipStream_t hs = static_cast<hipStream_t>(stream);
-  return probe_scene(objs, numObjects, g, s, hs, [&](const SceneBlock *sb) {
-    return launch_probe_pool_cull(sb, bulbClass, light, far, d_pts, d_out, n, hs);
-  }, lights, numLights);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // layers — terrain, sea and clouds — as main sends its own rays through them.  The rays come from device memory; everything behind
 // the ray is the render kernels' own device code (shadeRay with envLayers in rm_device.hip.h; seaMapHeight, getSeaNormal,
 // raymarchTerrain and terrainNormal in rm_env.hip.h).  The launchers (argument checks, staging, the class of the call) are
-// launch_shade_layers and launch_trace_layers in rm_launcher.hip; the kernels live here so that adding them leaves the code objects
+// launch_shade and launch_trace in rm_queries.hip; the kernels live here so that adding them leaves the code objects
 // of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // rm_points.hip — the kernels of rm_shade_points (gfx950 only): what the renderer thinks of POINTS the caller already has — the
 // scene's distance and object at the point, its normal, its ambient occlusion and its shaded colour — with the point optionally
 // projected onto the iso-surface first.  Everything behind the point is the render kernels' own device code (rm_device.hip.h).  The
-// launcher (argument checks, staging, the class of the call) is launch_points in rm_launcher.hip; the kernels live here so that
+// launcher (argument checks, staging, the class of the call) is launch_points in rm_queries.hip; the kernels live here so that
 // adding them leaves the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 

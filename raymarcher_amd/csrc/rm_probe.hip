@@ -4,7 +4,7 @@
 //
 // Kept out of rm_kernels.hip so that the production translation unit's compile time and code stay as they are.  The variant kernels
 // below call the very template functions the render kernels call (sdSceneImpl, sdSceneOne in rm_device.hip.h) with the same
-// template arguments; the launcher (rm_launcher.hip) validates the request and stages the production SceneBlock, then hands it
+// template arguments; the entry point (rm_queries.hip) validates the request and stages the production SceneBlock, then hands it
 // to launch_sdscene_variant.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // rm_shade.hip — the kernels of rm_shade_rays (gfx950 only): the renderer's full colour for ARBITRARY rays — the rays come from
 // device memory instead of from primaryRay, and everything behind the ray is the render kernels' own device code (shadeRay,
-// rm_device.hip.h).  The launcher (argument checks, staging, the class of the call) is launch_shade in rm_launcher.hip; the kernels
+// rm_device.hip.h).  The launcher (argument checks, staging, the class of the call) is launch_shade in rm_queries.hip; the kernels
 // live here so that adding them leaves the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 

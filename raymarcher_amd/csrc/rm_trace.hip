@@ -1,6 +1,6 @@
 // rm_trace.hip — the kernels of rm_trace_rays (gfx950 only): what ARBITRARY rays hit — the rays come from device memory instead of
 // from primaryRay.  Closest hit (object index, t, surface point, normal) or the renderer's own shadow march (occluder index and
-// penumbra factor).  The launcher (argument checks, staging, the class of the call) is launch_trace in rm_launcher.hip; the kernels
+// penumbra factor).  The launcher (argument checks, staging, the class of the call) is launch_trace in rm_queries.hip; the kernels
 // live here so that adding them leaves the code objects of the existing kernels as they were.
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // rm_volume.hip — where the surface is (gfx950 only): the kernel of rm_sdf_grid, sdScene on a dense lattice, and the kernels and the
 // entry point of rm_sdf_mesh, a quad mesh from any lattice of floats by naive surface nets.  include/raymarcher_amd.h has both
-// definitions.  rm_sdf_grid's argument checks and staging are launch_sdf_grid in rm_launcher.hip; everything of rm_sdf_mesh is
+// definitions.  rm_sdf_grid's argument checks and staging are launch_sdf_grid in rm_queries.hip; everything of rm_sdf_mesh is
 // here, as the post passes are in rm_post.hip.  A translation unit of its own, so that adding it leaves the code objects of the
 // existing kernels as they were.
 #include <hip/hip_runtime.h>
