@@ -37,6 +37,34 @@ def orbit(pos, look, fov, W, H, n, deg=4.0, far=100.0):
     return [h.make_camera(rot_y(pos, deg * i), rot_y(look, deg * i), (0, 1, 0), fov, W, H, far=far) for i in range(n)]
 
 
+def batch(n, W=32, H=24):
+    """max(n, 1) equal cameras on helpers.scene_mandelbulb, one RmGlobals per camera 0.1 apart in iTime → (cameras, globals, scene)."""
+    cams = (abi.RmCamera * max(n, 1))(*[h.make_camera((0, 0, 4.5), (0, 0, -1), (0, 1, 0), 30.0, W, H) for _ in range(max(n, 1))])
+    globs = (abi.RmGlobals * max(n, 1))(*[h.make_globals(itime=0.1 * i) for i in range(max(n, 1))])
+    return cams, globs, h.scene_mandelbulb(W, H)
+
+
+def three_primitives():
+    """A sphere, a cube and a torus, each moved one unit its own way → (objects, 3, globals)."""
+    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
+                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
+    return objs, 3, h.make_globals()
+
+
+def three_primitives_lit():
+    """three_primitives under a directional and a point light → (objects, 3, lights, 2, globals)."""
+    objs, no, g = three_primitives()
+    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (0, -1, 0)), h.make_light(abi.RM_LIGHT_POINT, pos=(1, 2, 3)))
+    return objs, no, lights, 2, g
+
+
+def three_primitives_table():
+    """helpers.table of a sphere and a cube one unit left and right and a torus at the origin → (objects, 3, globals)."""
+    objs, no = h.table([h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
+                        h.make_object(abi.RM_TORUS)])
+    return objs, no, h.make_globals()
+
+
 def all_primitives_scene(W=64, H=64):
     cam = h.make_camera((0, 0, 6), (0, 0, -1), (0, 1, 0), 45.0, W, H)
     types = [abi.RM_CUBE, abi.RM_CONE, abi.RM_CYLINDER, abi.RM_SPHERE, abi.RM_OCTAHEDRON, abi.RM_TORUS, abi.RM_CAPSULE,

@@ -7,27 +7,16 @@ import re
 import numpy as np
 import pytest
 
+import abi_helpers as ah
+from abi_helpers import HEADER, ROOT
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-
-
-def declared_functions():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(rm_[a-z0-9_]+)\s*\(", body)))
+from raymarcher_amd._lib import SIGNATURES
 
 
 def test_library_exports_every_declared_symbol():
-    # the package's loader first: a bare dlopen of the library would bind the system HIP runtime, and the GPU tests later in
-    # the same process would then find no device through torch's (_lib._share_torchs_hip_runtime); this handle is the same library
-    lib()
-    L = C.CDLL(LIB_PATH)
-    names = declared_functions()
+    names = ah.declared_functions()
     assert len(names) >= 30
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/raymarcher_amd.h but not exported"
+    ah.assert_exported(names)
     assert set(names) == set(SIGNATURES), set(names) ^ set(SIGNATURES)
 
 
@@ -38,7 +27,7 @@ def test_struct_sizes_match_the_compiled_library():
     for i, s in enumerate(structs):
         assert L.rm_abi_sizeof(i) == C.sizeof(s), s.__name__
     assert L.rm_abi_sizeof(99) == -1
-    assert L.rm_abi_version() == abi.RM_ABI_VERSION
+    ah.assert_abi_version()
     # sizes quoted in SURVEY §8a: RayMarchObject 176 B, LightSource 116 B
     assert C.sizeof(abi.RmObject) == 176 and C.sizeof(abi.RmLight) == 116
 

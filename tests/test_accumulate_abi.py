@@ -9,55 +9,39 @@ import re
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import helpers as h
+import scene_builders as SB
+from abi_helpers import FAKE, HEADER, INT_MAX, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-SCENES = os.path.join(ROOT, "tests", "golden", "scenes")
-INT_MAX = 2 ** 31 - 1
+from raymarcher_amd._lib import SIGNATURES
 
 
 # ---------------------------------------------------------------- the entry point
 def test_header_declares_and_library_exports_the_entry_point():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+rm_render_accumulated\s*\(([^)]*)\)", body)
-    assert m, "include/raymarcher_amd.h does not declare rm_render_accumulated"
-    params = [p.strip() for p in m.group(1).split(",")]
+    params = ah.params("rm_render_accumulated")
     assert len(params) == 16 and params[3] == "int numFrames" and params[4] == "int subFrames" and params[13] == "float *d_rgba"
     res, args = SIGNATURES["rm_render_accumulated"]
     batch = SIGNATURES["rm_render_batch"][1]
     assert res is C.c_int and args == batch[:4] + [C.c_int] + batch[4:]  # rm_render_batch's arguments plus subFrames after numFrames
-    lib()
-    handle = C.CDLL(LIB_PATH)
-    for name in ("rm_render_accumulated", "rm_camera_lens_samples", "rm_scene_camera_lens"):
-        assert hasattr(handle, name), name
-        assert name in SIGNATURES and re.search(rf"\bint\s+{name}\s*\(", body), name
+    names = ("rm_render_accumulated", "rm_camera_lens_samples", "rm_scene_camera_lens")
+    ah.assert_exported(names)
+    for name in names:
+        assert name in SIGNATURES and ah.params(name), name
 
 
 def test_abi_version_and_struct_sizes_stay():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert abi.RM_MAX_SUBFRAMES == 64 and re.search(r"#define\s+RM_MAX_SUBFRAMES\s+64\b", HEADER)
     assert lib().rm_abi_sizeof(7) == C.sizeof(abi.RmCameraData) == 52  # the lens fields did not go into RmCameraData
 
 
 def test_header_comment_carries_the_definition_of_a_pixel():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int\s+rm_render_accumulated\s*\(", HEADER, flags=re.S)
-    assert m, "no comment in front of the declaration"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("cams[f·subFrames + j]", "acc = S_0", "acc = acc + S_j", "in that order", "binary32", "denormals kept",
-                  "1.0f / (float)n", "acc = S[0].copy()", "out = acc * (np.float32(1) / np.float32(n))",
-                  "subFrames == 1 is rm_render_batch", "no subFrames-sized image exists in device memory", "RM_MAX_SUBFRAMES",
-                  "rm_debug_last_path() = 9", "symbol lookup", "before any HIP call"):
-        assert words in text, f"the comment of rm_render_accumulated lacks: {words}"
-
-
-def _batch(n, W=32, H=24):
-    cams = (abi.RmCamera * max(n, 1))(*[h.make_camera((0, 0, 4.5), (0, 0, -1), (0, 1, 0), 30.0, W, H) for _ in range(max(n, 1))])
-    globs = (abi.RmGlobals * max(n, 1))(*[h.make_globals(itime=0.1 * i) for i in range(max(n, 1))])
-    return cams, globs, h.scene_mandelbulb(W, H)
+    ah.assert_comment_has("rm_render_accumulated", (
+        "cams[f·subFrames + j]", "acc = S_0", "acc = acc + S_j", "in that order", "binary32", "denormals kept",
+        "1.0f / (float)n", "acc = S[0].copy()", "out = acc * (np.float32(1) / np.float32(n))",
+        "subFrames == 1 is rm_render_batch", "no subFrames-sized image exists in device memory", "RM_MAX_SUBFRAMES",
+        "rm_debug_last_path() = 9", "symbol lookup", "before any HIP call"))
 
 
 def call(cams, globs, num_globals, n, sub, objs, num_objects, lights, num_lights, W=32, H=24, out=None, s=None):
@@ -66,60 +50,48 @@ def call(cams, globs, num_globals, n, sub, objs, num_objects, lights, num_lights
                                        out, None, None)
 
 
-def refused(status, want=None):
-    """The status is `want` (RM_ERR_INVALID_ARGUMENT by default) and rm_last_error() says why."""
-    want = abi.RM_ERR_INVALID_ARGUMENT if want is None else want
-    return status == want and len(lib().rm_last_error().decode()) > 0
-
-
 def test_argument_errors_return_before_any_hip_call():
-    """Null or fake device pointers throughout: no call below may reach HIP (this machine has no device to reach)."""
+    """Null or FAKE device pointers throughout: no call below may reach HIP (this machine has no device to reach)."""
     L = lib()
-    cams, globs, scene = _batch(12)
+    cams, globs, scene = SB.batch(12)
     objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
-    fake = C.c_void_p(0x1000)  # never dereferenced: every call below fails its checks first
     # subFrames outside 1 … RM_MAX_SUBFRAMES
     for sub in (0, -1, -64, abi.RM_MAX_SUBFRAMES + 1, 1000, INT_MAX):
-        assert refused(call(cams, globs, 1, 1, sub, objs, no, lights, nl, out=fake)), sub
-        assert "subFrames" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 1, 1, sub, objs, no, lights, nl, out=FAKE), "subFrames"), sub
     # numFrames·subFrames over the ring's cap: RM_ERR_CAPACITY, also where neither factor is over it and where the product
     # would not fit an int
     for n, sub in ((abi.RM_MAX_BATCH_FRAMES + 1, 1), (abi.RM_MAX_BATCH_FRAMES // 64 + 1, 64), (513, 2), (INT_MAX, 64)):
-        assert refused(call(cams, globs, 1, n, sub, objs, no, lights, nl, out=fake), abi.RM_ERR_CAPACITY), (n, sub)
-        assert "RM_MAX_BATCH_FRAMES" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 1, n, sub, objs, no, lights, nl, out=FAKE), "RM_MAX_BATCH_FRAMES", want=abi.RM_ERR_CAPACITY), (n, sub)
     for sub in (1, 3, 4):
         n = 12 // sub
         # numFrames == 0: nothing to write, a null output is fine
         assert call(cams, globs, 1, 0, sub, objs, no, lights, nl, out=None) == abi.RM_OK, sub
         assert call(None, None, 0, 0, sub, objs, no, lights, nl, out=None) == abi.RM_OK, sub
         # negative numFrames
-        assert refused(call(cams, globs, 1, -1, sub, objs, no, lights, nl, out=fake)), sub
+        assert refused(call(cams, globs, 1, -1, sub, objs, no, lights, nl, out=FAKE)), sub
         # numGlobals neither 1 nor numFrames·subFrames (numFrames alone is not enough)
         for ng in (0, 2, 13, -1) + ((n,) if sub > 1 else ()):
-            assert refused(call(cams, globs, ng, n, sub, objs, no, lights, nl, out=fake)), (sub, ng)
-            assert "numGlobals" in L.rm_last_error().decode()
+            assert refused(call(cams, globs, ng, n, sub, objs, no, lights, nl, out=FAKE), "numGlobals"), (sub, ng)
         # null arrays
-        assert refused(call(None, globs, 1, n, sub, objs, no, lights, nl, out=fake)), sub
-        assert refused(call(cams, None, 1, n, sub, objs, no, lights, nl, out=fake)), sub
+        assert refused(call(None, globs, 1, n, sub, objs, no, lights, nl, out=FAKE)), sub
+        assert refused(call(cams, None, 1, n, sub, objs, no, lights, nl, out=FAKE)), sub
         # bad frame size
         for W, H in ((0, 24), (32, 0), (-5, 24), (32, -1), (INT_MAX // 8 + 1, 8), (8, 65536 * 8)):
-            assert refused(call(cams, globs, 12, n, sub, objs, no, lights, nl, W=W, H=H, out=fake)), (sub, W, H)
+            assert refused(call(cams, globs, 12, n, sub, objs, no, lights, nl, W=W, H=H, out=FAKE)), (sub, W, H)
         # the tables are checked as rm_render_batch checks them: too many objects, null settings, null output
         many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-        assert refused(call(cams, globs, 12, n, sub, many, abi.RM_MAX_OBJECTS + 1, lights, nl, out=fake), abi.RM_ERR_CAPACITY), sub
-        assert refused(L.rm_render_accumulated(cams, globs, 12, n, sub, objs, no, lights, nl, None, None, 32, 24, fake, None, None)), sub
-        assert refused(call(cams, globs, 12, n, sub, objs, no, lights, nl, out=None)), sub
-        assert "null output" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 12, n, sub, many, abi.RM_MAX_OBJECTS + 1, lights, nl, out=FAKE), want=abi.RM_ERR_CAPACITY), sub
+        assert refused(L.rm_render_accumulated(cams, globs, 12, n, sub, objs, no, lights, nl, None, None, 32, 24, FAKE, None, None)), sub
+        assert refused(call(cams, globs, 12, n, sub, objs, no, lights, nl, out=None), "null output"), sub
 
 
 def test_argument_errors_report_in_the_order_of_the_header():
     """An input that violates several checks reports the earliest: subFrames, the cap on numFrames·subFrames, numFrames == 0,
     numGlobals, then rm_render_batch's own."""
-    L = lib()
-    cams, globs, scene = _batch(6)
+    cams, globs, scene = SB.batch(6)
     objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
-    a = dict(cams=None, globs=None, ng=2, n=abi.RM_MAX_BATCH_FRAMES, sub=0, W=0, H=0, out=None)
-    walk = [
+    start = dict(cams=None, globs=None, ng=2, n=abi.RM_MAX_BATCH_FRAMES, sub=0, W=0, H=0, out=None)
+    ah.walk(lambda a: call(a["cams"], a["globs"], a["ng"], a["n"], a["sub"], objs, no, lights, nl, W=a["W"], H=a["H"], out=a["out"]), start, [
         (dict(), abi.RM_ERR_INVALID_ARGUMENT, "subFrames"),
         (dict(sub=2), abi.RM_ERR_CAPACITY, "RM_MAX_BATCH_FRAMES"),
         (dict(n=0), abi.RM_OK, None),
@@ -127,24 +99,18 @@ def test_argument_errors_report_in_the_order_of_the_header():
         (dict(ng=6), abi.RM_ERR_INVALID_ARGUMENT, "null cameras or globals"),
         (dict(cams=cams, globs=globs), abi.RM_ERR_INVALID_ARGUMENT, "bad frame size"),
         (dict(W=32, H=24), abi.RM_ERR_INVALID_ARGUMENT, "null output"),
-    ]
-    for step, (mend, status, word) in enumerate(walk):
-        a.update(mend)
-        got = call(a["cams"], a["globs"], a["ng"], a["n"], a["sub"], objs, no, lights, nl, W=a["W"], H=a["H"], out=a["out"])
-        assert got == status, (step, mend, got, L.rm_last_error().decode())
-        if word is not None:
-            assert word in L.rm_last_error().decode(), (step, mend, L.rm_last_error().decode())
+    ])
 
 
 # ---------------------------------------------------------------- the scenefile's lens fields
 def test_scene_camera_lens_returns_the_fields_of_the_scenefile():
     from raymarcher_amd import Scene
-    sc = Scene(path=os.path.join(SCENES, "lighting", "depth_of_field.json"))
+    sc = Scene(path=os.path.join(SB.SCENES, "lighting", "depth_of_field.json"))
     a, f = sc.lens()
     assert np.float32(a) == np.float32(0.008) and np.float32(f) == np.float32(3.0)
     cd = sc.camera_data()  # untouched by the lens fields
     assert (cd.pos[0], cd.pos[1], cd.pos[2]) == (0.0, 0.0, 16.0) and (cd.look[0], cd.look[1], cd.look[2]) == (0.0, 0.0, -1.0)
-    assert Scene(path=os.path.join(SCENES, "lighting", "directional_light_2.json")).lens() == (0.0, 0.0)
+    assert Scene(path=os.path.join(SB.SCENES, "lighting", "directional_light_2.json")).lens() == (0.0, 0.0)
     one = '{"name": "root", "globalData": {"ambientCoeff": 1, "diffuseCoeff": 1, "specularCoeff": 1}, "cameraData": {"position": ' \
           '[0, 0, 5], "up": [0, 1, 0], "heightAngle": 30, "look": [0, 0, -1], "focalLength": 2.5}, "groups": []}'
     assert Scene(text=one).lens() == (0.0, 2.5)

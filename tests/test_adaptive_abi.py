@@ -3,19 +3,16 @@ exports it under the unchanged ABI version, every argument error returns its sta
 checks ss, the threshold and lengths in Python, and `adaptive` below — the definition in NumPy, which the GPU tests import — agrees
 with the same rule written out per pixel."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import helpers as h
+import scene_builders as SB
+from abi_helpers import FAKE, INT_MAX, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
+from raymarcher_amd._lib import SIGNATURES
 
 
 # ---------------------------------------------------------------- the definition in NumPy
@@ -116,44 +113,28 @@ PARAMS = ["const RmCamera *cams", "const RmGlobals *globals", "int numGlobals", 
 
 
 def test_header_declares_and_library_exports_the_entry_point():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+rm_render_adaptive\s*\(([^)]*)\)", body)
-    assert m, "include/raymarcher_amd.h does not declare rm_render_adaptive"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+    params = ah.params("rm_render_adaptive")
     assert len(params) == 19 and params == PARAMS
     assert "rm_render_adaptive" in SIGNATURES
     res, args = SIGNATURES["rm_render_adaptive"]
     ssig = SIGNATURES["rm_render_supersampled"][1]
     # rm_render_supersampled's arguments plus the threshold after ss and the two outputs after d_bright
     assert res is C.c_int and args == ssig[:13] + [C.c_float] + ssig[13:15] + [C.c_void_p, C.c_void_p] + ssig[15:]
-    lib()
-    assert hasattr(C.CDLL(LIB_PATH), "rm_render_adaptive")
+    ah.assert_exported(["rm_render_adaptive"])
 
 
 def test_abi_version_stays_5():
-    assert abi.RM_ABI_VERSION == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
-    assert lib().rm_abi_version() == 5
+    ah.assert_abi_version()
 
 
 def test_header_comment_carries_the_definition_of_a_pixel():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int\s+rm_render_adaptive\s*\(", HEADER, flags=re.S)
-    assert m, "no comment in front of the declaration"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("4-neighbour", "inside the frame", "not (", "<= threshold", "r, g, b", "rm_render_batch", "rm_render_supersampled",
-                  "rm_debug_last_path() = 8", "before any HIP call", "symbol lookup", "binary32", "denormals kept", "NaN difference",
-                  "d_mask", "d_refined", "rm_set_workspace_limit"):
-        assert words in text, f"the comment of rm_render_adaptive lacks: {words}"
+    ah.assert_comment_has("rm_render_adaptive", (
+        "4-neighbour", "inside the frame", "not (", "<= threshold", "r, g, b", "rm_render_batch", "rm_render_supersampled",
+        "rm_debug_last_path() = 8", "before any HIP call", "symbol lookup", "binary32", "denormals kept", "NaN difference",
+        "d_mask", "d_refined", "rm_set_workspace_limit"))
 
 
 # ---------------------------------------------------------------- argument errors
-def _batch(n, W=32, H=24):
-    cams = (abi.RmCamera * max(n, 1))(*[h.make_camera((0, 0, 4.5), (0, 0, -1), (0, 1, 0), 30.0, W, H) for _ in range(max(n, 1))])
-    globs = (abi.RmGlobals * max(n, 1))(*[h.make_globals(itime=0.1 * i) for i in range(max(n, 1))])
-    scene = h.scene_mandelbulb(W, H)
-    return cams, globs, scene
-
-
 def call(cams, globs, num_globals, n, objs, num_objects, lights, num_lights, W=32, H=24, ss=2, thr=0.1, out=None, s=None, mask=None,
          refined=None):
     s = s if s is not None else abi.default_settings()
@@ -161,67 +142,56 @@ def call(cams, globs, num_globals, n, objs, num_objects, lights, num_lights, W=3
                                     out, None, mask, refined, None)
 
 
-def refused(status, want=None):
-    """The status is `want` (RM_ERR_INVALID_ARGUMENT by default) and rm_last_error() says why."""
-    want = abi.RM_ERR_INVALID_ARGUMENT if want is None else want
-    return status == want and len(lib().rm_last_error().decode()) > 0
-
-
 def test_argument_errors_return_before_any_hip_call():
     L = lib()
-    cams, globs, scene = _batch(3)
+    cams, globs, scene = SB.batch(3)
     objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
-    fake = C.c_void_p(0x1000)  # never dereferenced: every call below fails its checks first
     # a NaN threshold, with and without the optional outputs
     for ss in (1, 2, 4):
-        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, thr=float("nan"), out=fake)), ss
-        assert "threshold" in L.rm_last_error().decode()
-        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, thr=float("nan"), out=fake, mask=fake, refined=fake)), ss
+        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, thr=float("nan"), out=FAKE), "threshold"), ss
+        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, thr=float("nan"), out=FAKE, mask=FAKE, refined=FAKE)), ss
     # ss outside {1, 2, 4}
     for ss in (0, 3, 8, -2, 5, 16):
-        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, out=fake)), ss
-        assert "ss" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, out=FAKE), "ss"), ss
     for ss in (1, 2, 4):
         for thr in (0.1, float("inf"), -1.0):
             # numFrames == 0: nothing to write, a null output is fine
             assert call(cams, globs, 1, 0, objs, no, lights, nl, ss=ss, thr=thr, out=None) == abi.RM_OK, ss
             assert call(None, None, 0, 0, objs, no, lights, nl, ss=ss, thr=thr, out=None) == abi.RM_OK, ss
         # negative numFrames
-        assert refused(call(cams, globs, 1, -1, objs, no, lights, nl, ss=ss, out=fake)), ss
+        assert refused(call(cams, globs, 1, -1, objs, no, lights, nl, ss=ss, out=FAKE)), ss
         # numGlobals neither 1 nor numFrames
         for ng in (0, 2, 4, -1):
-            assert refused(call(cams, globs, ng, 3, objs, no, lights, nl, ss=ss, out=fake)), (ss, ng)
+            assert refused(call(cams, globs, ng, 3, objs, no, lights, nl, ss=ss, out=FAKE)), (ss, ng)
         # null arrays
-        assert refused(call(None, globs, 1, 3, objs, no, lights, nl, ss=ss, out=fake)), ss
-        assert refused(call(cams, None, 1, 3, objs, no, lights, nl, ss=ss, out=fake)), ss
+        assert refused(call(None, globs, 1, 3, objs, no, lights, nl, ss=ss, out=FAKE)), ss
+        assert refused(call(cams, None, 1, 3, objs, no, lights, nl, ss=ss, out=FAKE)), ss
         # bad frame size
         for W, H in ((0, 24), (32, 0), (-5, 24), (32, -1)):
-            assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, W=W, H=H, ss=ss, out=fake)), (ss, W, H)
+            assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, W=W, H=H, ss=ss, out=FAKE)), (ss, W, H)
         # over the cap
-        assert refused(call(cams, globs, 1, abi.RM_MAX_BATCH_FRAMES + 1, objs, no, lights, nl, ss=ss, out=fake), abi.RM_ERR_CAPACITY), ss
+        assert refused(call(cams, globs, 1, abi.RM_MAX_BATCH_FRAMES + 1, objs, no, lights, nl, ss=ss, out=FAKE), want=abi.RM_ERR_CAPACITY), ss
         # the tables are checked as rm_render_batch checks them: too many objects, null settings, null output
         many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-        assert refused(call(cams, globs, 3, 3, many, abi.RM_MAX_OBJECTS + 1, lights, nl, ss=ss, out=fake), abi.RM_ERR_CAPACITY), ss
-        assert refused(L.rm_render_adaptive(cams, globs, 3, 3, objs, no, lights, nl, None, None, 32, 24, ss, 0.1, fake, None, None, None,
+        assert refused(call(cams, globs, 3, 3, many, abi.RM_MAX_OBJECTS + 1, lights, nl, ss=ss, out=FAKE), want=abi.RM_ERR_CAPACITY), ss
+        assert refused(L.rm_render_adaptive(cams, globs, 3, 3, objs, no, lights, nl, None, None, 32, 24, ss, 0.1, FAKE, None, None, None,
                                             None)), ss
-        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, out=None)), ss
-        assert "null output" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 3, 3, objs, no, lights, nl, ss=ss, out=None), "null output"), ss
 
 
 def test_sample_frames_too_large_are_refused_before_any_hip_call():
-    cams, globs, scene = _batch(1)
+    cams, globs, scene = SB.batch(1)
     objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
-    fake = C.c_void_p(0x1000)
     for ss in (2, 4):
         over = INT_MAX // 8 // ss + 1  # ss·over > INT_MAX / 8
-        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=over, H=8, ss=ss, out=fake)), ss
-        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=8, H=over, ss=ss, out=fake)), ss
+        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=over, H=8, ss=ss, out=FAKE)), ss
+        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=8, H=over, ss=ss, out=FAKE)), ss
         # within INT_MAX / 8 on each axis, but more 8×8 sample tiles than one launch can index
-        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=8, H=65536 * 8 // ss, ss=ss, out=fake)), ss
-        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=INT_MAX // 8 // ss, H=32768, ss=ss, out=fake)), ss
+        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=8, H=65536 * 8 // ss, ss=ss, out=FAKE)), ss
+        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=INT_MAX // 8 // ss, H=32768, ss=ss, out=FAKE)), ss
     # more pixels per frame than a 32-bit list entry indexes, whatever ss
     for ss in (1, 2, 4):
-        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=65536, H=32768, ss=ss, out=fake)), ss
+        assert refused(call(cams, globs, 1, 1, objs, no, lights, nl, W=65536, H=32768, ss=ss, out=FAKE)), ss
 
 
 def test_shared_argument_errors_report_in_precedence_order():
@@ -229,13 +199,17 @@ def test_shared_argument_errors_report_in_precedence_order():
     mends them one at a time, in the order the entry point has checked them since it exists (statuses and words written down from
     the library before the multi-frame launchers shared one checking function).  ss = 1 included: the entry point holds the
     1-sample frame to the sample frame's bounds too."""
-    L = lib()
-    cams, globs, scene = _batch(3)
+    cams, globs, scene = SB.batch(3)
     objs, no, lights, nl = scene[1], scene[2], scene[3], scene[4]
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
+
+    def walked(a):
+        return call(a["cams"], a["globs"], a["ng"], a["n"], a["objs"], a["no"], lights, nl, W=a["W"], H=a["H"], ss=a["ss"], thr=a["thr"],
+                    out=a["out"])
+
     for ss in (1, 2, 4):
-        a = dict(cams=None, globs=None, ng=2, n=-1, objs=many, no=abi.RM_MAX_OBJECTS + 1, W=0, H=0, ss=3, thr=float("nan"), out=None)
-        walk = [
+        start = dict(cams=None, globs=None, ng=2, n=-1, objs=many, no=abi.RM_MAX_OBJECTS + 1, W=0, H=0, ss=3, thr=float("nan"), out=None)
+        ah.walk(walked, start, [
             (dict(), abi.RM_ERR_INVALID_ARGUMENT, "ss (samples per pixel"),
             (dict(ss=ss), abi.RM_ERR_INVALID_ARGUMENT, "threshold is NaN"),
             (dict(thr=0.1), abi.RM_ERR_INVALID_ARGUMENT, "negative numFrames"),
@@ -251,14 +225,7 @@ def test_shared_argument_errors_report_in_precedence_order():
             (dict(W=65536), abi.RM_ERR_INVALID_ARGUMENT, "list entry"),                        # 2^31 pixels, with a bad table
             (dict(W=32, H=24), abi.RM_ERR_CAPACITY, "RM_MAX_OBJECTS"),
             (dict(objs=objs, no=no), abi.RM_ERR_INVALID_ARGUMENT, "null output"),
-        ]
-        for step, (mend, status, word) in enumerate(walk):
-            a.update(mend)
-            got = call(a["cams"], a["globs"], a["ng"], a["n"], a["objs"], a["no"], lights, nl, W=a["W"], H=a["H"], ss=a["ss"], thr=a["thr"],
-                       out=a["out"])
-            assert got == status, (ss, step, mend, got, L.rm_last_error().decode())
-            if word is not None:
-                assert word in L.rm_last_error().decode(), (ss, step, mend, L.rm_last_error().decode())
+        ])
 
 
 def test_python_wrapper_checks_ss_threshold_and_lengths():

@@ -3,57 +3,43 @@ ABI version, every argument error — the table counts and an invalid table in a
 status before the first HIP call, and the translation helper is invModel · T(−t) in float64, rounded once."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import helpers as h
+from abi_helpers import FAKE, INT_MAX, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
+from raymarcher_amd._lib import SIGNATURES
 
 
 # ---------------------------------------------------------------- the entry points
 def test_header_declares_and_library_exports_both_symbols():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+rm_render_animated\s*\(([^)]*)\)", body)
-    assert m, "include/raymarcher_amd.h does not declare rm_render_animated"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    assert params == ["const RmCamera *cams", "const RmGlobals *globals", "int numGlobals", "const RmObject *objs", "int numObjects",
-                      "int numObjectTables", "const RmLight *lights", "int numLights", "int numLightTables", "int numFrames",
-                      "int subFrames", "const RmSettings *s", "const RmResources *res", "int W", "int H", "float *d_rgba",
-                      "float *d_bright", "void *stream"]
+    assert ah.params("rm_render_animated") == [
+        "const RmCamera *cams", "const RmGlobals *globals", "int numGlobals", "const RmObject *objs", "int numObjects",
+        "int numObjectTables", "const RmLight *lights", "int numLights", "int numLightTables", "int numFrames",
+        "int subFrames", "const RmSettings *s", "const RmResources *res", "int W", "int H", "float *d_rgba", "float *d_bright", "void *stream"]
     res, args = SIGNATURES["rm_render_animated"]
     P = C.POINTER
     assert res is C.c_int and args == [P(abi.RmCamera), P(abi.RmGlobals), C.c_int, P(abi.RmObject), C.c_int, C.c_int, P(abi.RmLight),
                                        C.c_int, C.c_int, C.c_int, C.c_int, P(abi.RmSettings), P(abi.RmResources), C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    assert re.search(r"\bint\s+rm_object_translated\s*\(\s*const RmObject \*in,\s*const float t\[3\],\s*RmObject \*out\s*\)", body)
+    assert ah.params("rm_object_translated") == ["const RmObject *in", "const float t[3]", "RmObject *out"]
     assert SIGNATURES["rm_object_translated"] == (C.c_int, [P(abi.RmObject), P(C.c_float), P(abi.RmObject)])
-    lib()
-    handle = C.CDLL(LIB_PATH)
-    assert hasattr(handle, "rm_render_animated") and hasattr(handle, "rm_object_translated")
+    ah.assert_exported(["rm_render_animated", "rm_object_translated"])
 
 
 def test_abi_version_stays():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert lib().rm_abi_sizeof(0) == C.sizeof(abi.RmObject) == 176
 
 
 def test_header_comment_carries_the_definition():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int\s+rm_render_animated\s*\(", HEADER, flags=re.S)
-    assert m, "no comment in front of the declaration"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("b = f·subFrames + j", "objs + b·numObjects", "lights + b·numLights", "rm_render_res writes for block b", "in that order",
-                  "binary32", "1.0f / (float)n", "is rm_render_accumulated, exactly", "names the block", "before any HIP call",
-                  "rm_debug_last_path() = 10", "symbol lookup"):
-        assert words in text, f"the comment of rm_render_animated lacks: {words}"
+    ah.assert_comment_has("rm_render_animated", (
+        "b = f·subFrames + j", "objs + b·numObjects", "lights + b·numLights", "rm_render_res writes for block b", "in that order",
+        "binary32", "1.0f / (float)n", "is rm_render_accumulated, exactly", "names the block", "before any HIP call",
+        "rm_debug_last_path() = 10", "symbol lookup"))
 
 
 def test_python_signatures():
@@ -94,44 +80,29 @@ def call(cams, globs, ng, objs, no, not_, lights, nl, nlt, n, sub, W=32, H=24, o
     return lib().rm_render_animated(cams, globs, ng, objs, no, not_, lights, nl, nlt, n, sub, C.byref(s), res, W, H, out, None, None)
 
 
-def refused(status, want=None):
-    want = abi.RM_ERR_INVALID_ARGUMENT if want is None else want
-    return status == want and len(lib().rm_last_error().decode()) > 0
-
-
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
-
-
 def test_table_counts_are_one_or_blocks():
-    L = lib()
     cams, globs, objs, no, lights, nl = _scene(12)
     for n, sub in ((12, 1), (4, 3), (3, 4), (1, 12)):
         for bad in (0, 2, 5, 13, -1) + ((n,) if sub > 1 and n > 1 else ()):  # numFrames alone is not enough
-            assert refused(call(cams, globs, 1, objs, no, bad, lights, nl, 1, n, sub, out=FAKE)), (n, sub, bad)
-            assert "numObjectTables" in L.rm_last_error().decode()
-            assert refused(call(cams, globs, 1, objs, no, 12, lights, nl, bad, n, sub, out=FAKE)), (n, sub, bad)
-            assert "numLightTables" in L.rm_last_error().decode()
+            assert refused(call(cams, globs, 1, objs, no, bad, lights, nl, 1, n, sub, out=FAKE), "numObjectTables"), (n, sub, bad)
+            assert refused(call(cams, globs, 1, objs, no, 12, lights, nl, bad, n, sub, out=FAKE), "numLightTables"), (n, sub, bad)
         # null tables where the count needs them, fine where it does not
         assert refused(call(cams, globs, 1, None, no, 12, lights, nl, 12, n, sub, out=FAKE)), (n, sub)
         assert refused(call(cams, globs, 1, objs, no, 12, None, nl, 12, n, sub, out=FAKE)), (n, sub)
         assert refused(call(cams, globs, 1, None, no, 1, lights, nl, 1, n, sub, out=FAKE)), (n, sub)
         # valid counts get as far as the output pointer
         for not_, nlt in ((1, 1), (12, 1), (1, 12), (12, 12)):
-            assert refused(call(cams, globs, 12, objs, no, not_, lights, nl, nlt, n, sub, out=None)), (n, sub, not_, nlt)
-            assert "null output" in L.rm_last_error().decode()
-    assert refused(call(cams, globs, 1, None, 0, 12, None, 0, 12, 4, 3, out=None))  # empty tables need no pointer
-    assert "null output" in L.rm_last_error().decode()
+            assert refused(call(cams, globs, 12, objs, no, not_, lights, nl, nlt, n, sub, out=None), "null output"), (n, sub, not_, nlt)
+    assert refused(call(cams, globs, 1, None, 0, 12, None, 0, 12, 4, 3, out=None), "null output")  # empty tables need no pointer
 
 
 def test_everything_rm_render_accumulated_refuses():
     L = lib()
     cams, globs, objs, no, lights, nl = _scene(12)
     for sub in (0, -1, abi.RM_MAX_SUBFRAMES + 1, INT_MAX):
-        assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, 1, 1, sub, out=FAKE)), sub
-        assert "subFrames" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, 1, 1, sub, out=FAKE), "subFrames"), sub
     for n, sub in ((abi.RM_MAX_BATCH_FRAMES + 1, 1), (abi.RM_MAX_BATCH_FRAMES // 64 + 1, 64), (513, 2), (INT_MAX, 64)):
-        assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, 1, n, sub, out=FAKE), abi.RM_ERR_CAPACITY), (n, sub)
-        assert "RM_MAX_BATCH_FRAMES" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, 1, n, sub, out=FAKE), "RM_MAX_BATCH_FRAMES", want=abi.RM_ERR_CAPACITY), (n, sub)
     for sub in (1, 3, 4):
         n = 12 // sub
         # numFrames == 0: RM_OK whatever the table counts say, nothing is read
@@ -140,17 +111,15 @@ def test_everything_rm_render_accumulated_refuses():
         assert call(None, None, 0, None, 0, 1, None, 0, 1, 0, sub, out=None) == abi.RM_OK, sub
         assert refused(call(cams, globs, 1, objs, no, 12, lights, nl, 12, -1, sub, out=FAKE)), sub
         for ng in (0, 2, 13, -1) + ((n,) if sub > 1 else ()):
-            assert refused(call(cams, globs, ng, objs, no, 12, lights, nl, 12, n, sub, out=FAKE)), (sub, ng)
-            assert "numGlobals" in L.rm_last_error().decode()
+            assert refused(call(cams, globs, ng, objs, no, 12, lights, nl, 12, n, sub, out=FAKE), "numGlobals"), (sub, ng)
         assert refused(call(None, globs, 1, objs, no, 12, lights, nl, 12, n, sub, out=FAKE)), sub
         assert refused(call(cams, None, 1, objs, no, 12, lights, nl, 12, n, sub, out=FAKE)), sub
         for W, H in ((0, 24), (32, 0), (-5, 24), (32, -1), (INT_MAX // 8 + 1, 8), (8, 65536 * 8)):
             assert refused(call(cams, globs, 12, objs, no, 12, lights, nl, 12, n, sub, W=W, H=H, out=FAKE)), (sub, W, H)
         many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-        assert refused(call(cams, globs, 12, many, abi.RM_MAX_OBJECTS + 1, 1, lights, nl, 12, n, sub, out=FAKE), abi.RM_ERR_CAPACITY), sub
+        assert refused(call(cams, globs, 12, many, abi.RM_MAX_OBJECTS + 1, 1, lights, nl, 12, n, sub, out=FAKE), want=abi.RM_ERR_CAPACITY), sub
         assert refused(L.rm_render_animated(cams, globs, 12, objs, no, 12, lights, nl, 12, n, sub, None, None, 32, 24, FAKE, None, None)), sub
-        assert refused(call(cams, globs, 12, objs, no, 12, lights, nl, 12, n, sub, out=None)), sub
-        assert "null output" in L.rm_last_error().decode()
+        assert refused(call(cams, globs, 12, objs, no, 12, lights, nl, 12, n, sub, out=None), "null output"), sub
 
 
 @pytest.mark.parametrize("n,sub", [(12, 1), (4, 3), (2, 6)])
@@ -161,7 +130,7 @@ def test_every_block_is_validated_and_the_error_names_it(n, sub):
     # a CUSTOM object in table 5
     cams, globs, objs, no, lights, nl = _scene(blocks)
     objs[5 * no + 1].type = abi.RM_CUSTOM
-    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, 1, n, sub, out=FAKE), abi.RM_ERR_UNSUPPORTED)
+    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, 1, n, sub, out=FAKE), want=abi.RM_ERR_UNSUPPORTED)
     assert "block 5" in L.rm_last_error().decode() and "object 1" in L.rm_last_error().decode()
     # with one shared table the same bytes are never read as table 5
     assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, 1, n, sub, out=None)) and "null output" in L.rm_last_error().decode()
@@ -173,18 +142,17 @@ def test_every_block_is_validated_and_the_error_names_it(n, sub):
     tex[0].pixels, tex[0].width, tex[0].height = px.ctypes.data, 2, 2
     res = abi.RmResources()
     res.textures, res.numTextures = tex, 1
-    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, blocks, n, sub, out=FAKE, res=C.byref(res)), abi.RM_ERR_UNSUPPORTED)
+    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, blocks, n, sub, out=FAKE, res=C.byref(res)), want=abi.RM_ERR_UNSUPPORTED)
     assert "block 3" in L.rm_last_error().decode() and "texLoc" in L.rm_last_error().decode()
     # an area light without LTC tables in the last light table only
     cams, globs, objs, no, lights, nl = _scene(blocks)
     lights[(blocks - 1) * nl + 1].type = abi.RM_LIGHT_AREA
-    assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, blocks, n, sub, out=FAKE), abi.RM_ERR_UNSUPPORTED)
+    assert refused(call(cams, globs, 1, objs, no, 1, lights, nl, blocks, n, sub, out=FAKE), want=abi.RM_ERR_UNSUPPORTED)
     assert f"block {blocks - 1}" in L.rm_last_error().decode() and "LTC" in L.rm_last_error().decode()
     # an unknown light type in table 1
     cams, globs, objs, no, lights, nl = _scene(blocks)
     lights[1 * nl + 0].type = 77
-    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, blocks, n, sub, out=FAKE), abi.RM_ERR_UNSUPPORTED)
-    assert "block 1" in L.rm_last_error().decode()
+    assert refused(call(cams, globs, 1, objs, no, blocks, lights, nl, blocks, n, sub, out=FAKE), "block 1", want=abi.RM_ERR_UNSUPPORTED)
 
 
 # ---------------------------------------------------------------- rm_object_translated

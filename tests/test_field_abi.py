@@ -3,27 +3,14 @@ exports them under the unchanged ABI version, the Python layer has its methods, 
 first HIP call — with pointers that would fault if read — in the order the header states."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
+from abi_helpers import FAKE, HEADER, HP, fake, inf, nan, refused, vec3 as vec
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INVALID = abi.RM_ERR_INVALID_ARGUMENT
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
-inf, nan = float("inf"), float("nan")
 NAMES = {"rm_sdf_sample": 11, "rm_sdf_sample_blocks": 13, "rm_sdf_trace": 14, "rm_sdf_trace_blocks": 16}
-
-
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
 
 
 def test_header_declares_and_library_exports_the_four_symbols():
@@ -31,34 +18,28 @@ def test_header_declares_and_library_exports_the_four_symbols():
     sparse = ["const float *d_dist", "const int32_t *d_objectId", "const int32_t *d_blocks", "int numBlocks", "int mx", "int my", "int mz",
               "const float origin[3]", "const float step[3]"]
     march = ["float iso", "int maxSteps", "unsigned mode", "RmRayHit *d_hits", "void *stream"]
-    assert _params("rm_sdf_sample") == ["const float *d_points", "int numPoints"] + dense + ["RmFieldSample *d_samples", "void *stream"]
-    assert _params("rm_sdf_sample_blocks") == ["const float *d_points", "int numPoints"] + sparse + ["RmFieldSample *d_samples", "void *stream"]
-    assert _params("rm_sdf_trace") == ["const RmRay *d_rays", "int numRays"] + dense + march
-    assert _params("rm_sdf_trace_blocks") == ["const RmRay *d_rays", "int numRays"] + sparse + march
-    lib()
-    L = C.CDLL(LIB_PATH)
+    assert ah.params("rm_sdf_sample") == ["const float *d_points", "int numPoints"] + dense + ["RmFieldSample *d_samples", "void *stream"]
+    assert ah.params("rm_sdf_sample_blocks") == ["const float *d_points", "int numPoints"] + sparse + ["RmFieldSample *d_samples", "void *stream"]
+    assert ah.params("rm_sdf_trace") == ["const RmRay *d_rays", "int numRays"] + dense + march
+    assert ah.params("rm_sdf_trace_blocks") == ["const RmRay *d_rays", "int numRays"] + sparse + march
+    ah.assert_exported(NAMES)
     for name, n in NAMES.items():
-        assert hasattr(L, name), f"the library does not export {name}"
-        assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int and len(SIGNATURES[name][1]) == n == len(_params(name))
+        assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int and len(SIGNATURES[name][1]) == n == len(ah.params(name))
 
 
 def test_abi_version_stays_and_the_header_carries_the_definitions():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert C.sizeof(abi.RmFieldSample) == 32 and "} RmFieldSample; /* 32 bytes */" in HEADER
     assert [f[0] for f in abi.RmFieldSample._fields_] == ["gradient", "value", "cell", "objectId"]
     assert abi.RmFieldSample.value.offset == 12 and abi.RmFieldSample.cell.offset == 16 and abi.RmFieldSample.objectId.offset == 28
     assert re.search(r"#define\s+RM_FIELD_OUTSIDE\s+\(-5\)", HEADER) and abi.RM_FIELD_OUTSIDE == -5
     assert re.search(r"#define\s+RM_FIELD_UNLISTED\s+\(-6\)", HEADER) and abi.RM_FIELD_UNLISTED == -6
     assert re.search(r"#define\s+RM_MAX_FIELD_STEPS\s+65536\b", HEADER) and abi.RM_MAX_FIELD_STEPS == 65536
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*typedef struct RmFieldSample\b", HEADER, flags=re.S)
-    assert m, "no comment in front of RmFieldSample"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for w in ("never fused", "a NaN clamps to lo", "lerp(a, b, w) = a + w·(b − a)", "(fx >= 0.5, fy >= 0.5, fz >= 0.5)", "RM_FIELD_UNLISTED",
-              "ud all zeros", "Every skip changes an integer block coordinate", "knows nothing about the inside of unlisted blocks",
-              "the first listed sample below iso, not t = 0", "before any HIP call", "rm_set_workspace_limit", "rebuilt on every call",
-              "rm_debug_last_path() keeps its value"):
-        assert w in text, f"the header's definition lacks: {w}"
+    ah.assert_comment_has("RmFieldSample", (
+        "never fused", "a NaN clamps to lo", "lerp(a, b, w) = a + w·(b − a)", "(fx >= 0.5, fy >= 0.5, fz >= 0.5)", "RM_FIELD_UNLISTED",
+        "ud all zeros", "Every skip changes an integer block coordinate", "knows nothing about the inside of unlisted blocks",
+        "the first listed sample below iso, not t = 0", "before any HIP call", "rm_set_workspace_limit", "rebuilt on every call",
+        "rm_debug_last_path() keeps its value"))
 
 
 def test_python_signatures():
@@ -74,15 +55,6 @@ def test_python_signatures():
         assert (p["iso"].default, p["max_steps"].default, p["ids"].default, p["normals"].default) == (0.001, 256, None, True)
     assert sig(Renderer.scene_field_sparse) == sig(Renderer.scene_mesh_sparse)
     assert inspect.signature(Renderer.scene_field_sparse).parameters["iso"].default == 0.001
-
-
-def refused(status, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == INVALID and len(msg) > 0 and (text is None or text in msg)
-
-
-def vec(v):
-    return (C.c_float * 3)(*v) if v is not None else None
 
 
 def sample(n=5, points=FAKE, dist=FAKE, ids=FAKE, dims=(4, 3, 2), origin=(0, 0, 0), step=(0.1, 0.1, 0.1), out=FAKE):
@@ -102,44 +74,12 @@ def trace_blocks(n=5, rays=FAKE, dist=FAKE, ids=FAKE, bl=FAKE, nb=3, dims=(2, 2,
     return lib().rm_sdf_trace_blocks(rays, n, dist, ids, bl, nb, dims[0], dims[1], dims[2], vec(origin), vec(step), iso, steps, mode, out, None)
 
 
-BAD_STEPS = ((nan, 1, 1), (1, inf, 1), (1, 1, 0.0), (-0.5, 1, 1), (1, -0.0, 1), (1, 1, -inf))
-BAD_ORIGINS = ((nan, 0, 0), (0, inf, 0), (0, 0, -inf))
-BAD_DIMS = ((0, 2, 2), (2, -1, 2), (4097, 2, 2), (2, 2, 2 ** 31 - 1), (-2 ** 31, 2, 2))
-ONE_DIMS = ((1, 2, 2), (2, 1, 2), (2, 2, 1), (1, 1, 1), (4096, 4096, 1))
-BAD_BLOCKS = ((0, 2, 2), (2, -1, 2), (2, 2, 0), (513, 1, 1), (1, 513, 1), (1, 1, 2 ** 31 - 1), (-2 ** 31, 2, 2))
-BAD_COUNTS = (-1, -2 ** 31, (1 << 22) + 1, 2 ** 31 - 1)
-HOST = np.zeros(4096, dtype=np.float32)
-HP = C.c_void_p(HOST.ctypes.data)  # 16-byte aligned host memory: it gets as far as the device-memory check
-assert HOST.ctypes.data % 16 == 0
-
-
 def _lattice_refusals(call, dense, first):
     """What all four refuse alike up to the lattice, in order; first: the name of the count's message."""
     for n in (-1, -2 ** 31):
         assert refused(call(n=n), f"negative {first}"), n
         assert refused(call(n=n, origin=None), f"negative {first}"), n  # the count comes first
-    assert refused(call(origin=None), "null origin or step") and refused(call(step=None), "null origin or step")
-    assert refused(call(n=0, origin=None), "null origin or step")  # a call of nothing is still checked
-    for o in BAD_ORIGINS:
-        assert refused(call(origin=o), "origin must be finite"), o
-    for st in BAD_STEPS:
-        assert refused(call(step=st), "step must be finite and greater than 0"), st
-        assert refused(call(origin=(nan, 0, 0), step=st), "origin"), st
-    if dense:
-        for d in BAD_DIMS:
-            assert refused(call(dims=d), "lattice dimension must be 1 … RM_MAX_LATTICE_DIM"), d
-            assert refused(call(dims=d, step=(0, 1, 1)), "step"), d
-        assert refused(call(dims=(4096, 4096, 4096)), "more than INT_MAX lattice points")
-        for d in ONE_DIMS:
-            assert refused(call(dims=d), "at least 2"), d
-            assert refused(call(dims=d, n=0), "at least 2"), d
-    else:
-        for b in BAD_BLOCKS:
-            assert refused(call(dims=b), "block dimension"), b
-            assert refused(call(dims=b, step=(0, 1, 1)), "step"), b
-        for nb in BAD_COUNTS:
-            assert refused(call(nb=nb), "numBlocks must be 0 … RM_MAX_BLOCK_LIST"), nb
-            assert refused(call(nb=nb, dims=(0, 1, 1)), "block dimension"), nb  # the lattice comes before numBlocks
+    ah.lattice_refusals(call, dense, still=dict(n=0))  # a call of nothing is still checked
 
 
 def _array_refusals(call, inp, out, what):
@@ -149,10 +89,10 @@ def _array_refusals(call, inp, out, what):
     assert refused(call(**{inp: None}), f"null {what}") and refused(call(**{out: None}), f"null {what}")
     assert refused(call(dist=None), f"null {what}")
     for k in (inp, out):
-        assert refused(call(**{k: C.c_void_p(0x1008)}), "misaligned"), k
+        assert refused(call(**{k: fake(0x1008)}), "misaligned"), k
     for k in ("dist", "ids"):
-        assert refused(call(**{k: C.c_void_p(0x1002)}), "misaligned"), k
-    assert refused(call(**{inp: None, "dist": C.c_void_p(0x1002)}), f"null {what}")  # null comes before misaligned
+        assert refused(call(**{k: fake(0x1002)}), "misaligned"), k
+    assert refused(call(**{inp: None, "dist": fake(0x1002)}), f"null {what}")  # null comes before misaligned
     name = {"points": "d_points", "rays": "d_rays"}[inp]
     assert refused(call(**{inp: HP, out: HP}, dist=HP, ids=None), f"{name} is not device-accessible")
 
@@ -183,7 +123,7 @@ def test_sample_blocks_refusals_in_order_and_the_empty_list():
     _lattice_refusals(sample_blocks, False, "numPoints")
     _array_refusals(sample_blocks, "points", "out", "d_points, d_samples or d_dist")
     assert refused(sample_blocks(bl=None), "null d_blocks with numBlocks above 0")
-    assert refused(sample_blocks(bl=C.c_void_p(0x1002)), "misaligned")
+    assert refused(sample_blocks(bl=fake(0x1002)), "misaligned")
     assert refused(sample_blocks(nb=1 << 22, dims=(512, 512, 512), out=None), "null d_points")  # the largest lattice and list are valid
     # an empty list is valid and needs neither values nor a list: it gets as far as the device-memory check
     assert refused(sample_blocks(nb=0, bl=None, dist=None, ids=None, points=HP, out=HP), "d_points is not device-accessible")

@@ -4,55 +4,45 @@ argument error returns its status before the first HIP call, and the specificati
 its misses and normals are what the definition says, and on a sphere it agrees with the analytic intersection."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import gbuffer_helpers as G
 import helpers as h
 import scene_builders as SB
+from abi_helpers import FAKE, HEADER, HP, INT_MAX, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
 SURFACE_DIST = 1e-3  # frag:32
 
 
 # ---------------------------------------------------------------- symbol and signature
 def test_header_declares_and_library_exports_the_symbol():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+rm_render_gbuffer\s*\(([^)]*)\)", body)
-    assert m, "include/raymarcher_amd.h does not declare rm_render_gbuffer"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    assert params == ["const RmCamera *cams", "const RmGlobals *globals", "int numGlobals", "int numFrames", "const RmObject *objs",
-                      "int numObjects", "const RmSettings *s", "int W", "int H", "float *d_normalDepth", "int32_t *d_objectId",
-                      "float *d_position", "void *stream"]
+    assert ah.params("rm_render_gbuffer") == [
+        "const RmCamera *cams", "const RmGlobals *globals", "int numGlobals", "int numFrames", "const RmObject *objs",
+        "int numObjects", "const RmSettings *s", "int W", "int H", "float *d_normalDepth", "int32_t *d_objectId", "float *d_position",
+        "void *stream"]
     res, args = SIGNATURES["rm_render_gbuffer"]
     P = C.POINTER
     assert res is C.c_int and args == [P(abi.RmCamera), P(abi.RmGlobals), C.c_int, C.c_int, P(abi.RmObject), C.c_int, P(abi.RmSettings),
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib()
-    assert hasattr(C.CDLL(LIB_PATH), "rm_render_gbuffer")
+    ah.assert_exported(["rm_render_gbuffer"])
 
 
 def test_abi_version_stays():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
 
 
 def test_header_comment_carries_the_definition():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int\s+rm_render_gbuffer\s*\(", HEADER, flags=re.S)
-    assert m, "no comment in front of the declaration"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("frag:2388-2392", "2443", "2318-2337", "1453-1484", "1436-1444", "1679-1691", "raymarch(ro, rd, far, OUTSIDE)",
-                  "reports its own index", "not a view-space z", "bumpNormal(n, p, 10, 2)", "depth = far", "frag:2328",
-                  "(n.x, n.y, n.z, depth)", "hit ? 1 : 0", "names the frame", "before any HIP call", "rm_debug_last_path() = 11",
-                  "symbol lookup"):
-        assert words in text, f"the comment of rm_render_gbuffer lacks: {words}"
+    ah.assert_comment_has("rm_render_gbuffer", (
+        "frag:2388-2392", "2443", "2318-2337", "1453-1484", "1436-1444", "1679-1691", "raymarch(ro, rd, far, OUTSIDE)",
+        "reports its own index", "not a view-space z", "bumpNormal(n, p, 10, 2)", "depth = far", "frag:2328",
+        "(n.x, n.y, n.z, depth)", "hit ? 1 : 0", "names the frame", "before any HIP call", "rm_debug_last_path() = 11",
+        "symbol lookup"))
     assert re.search(r"11 = a launch\s+\*?\s*of rm_render_gbuffer", HEADER), "rm_debug_last_path's comment does not document 11"
 
 
@@ -66,14 +56,10 @@ def test_python_signature():
 
 # ---------------------------------------------------------------- refusals, all without a device
 def _scene(n, W=32, H=24):
-    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
+    objs, no, _ = SB.three_primitives()
     cams = (abi.RmCamera * n)(*[h.make_camera((0, 0, 5), (0, 0, -1), (0, 1, 0), 40.0, W, H) for _ in range(n)])
     globs = (abi.RmGlobals * n)(*[h.make_globals(itime=0.1 * i) for i in range(n)])
-    return cams, globs, objs, 3
-
-
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
+    return cams, globs, objs, no
 
 
 def call(cams, globs, ng, n, objs, no, s="default", W=32, H=24, nd=FAKE, ids=FAKE, pos=None):
@@ -81,17 +67,11 @@ def call(cams, globs, ng, n, objs, no, s="default", W=32, H=24, nd=FAKE, ids=FAK
     return lib().rm_render_gbuffer(cams, globs, ng, n, objs, no, C.byref(s) if s is not None else None, W, H, nd, ids, pos, None)
 
 
-def refused(status, want=None, text=None):
-    want = abi.RM_ERR_INVALID_ARGUMENT if want is None else want
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
-
-
 def test_frame_counts_globals_and_sizes():
     cams, globs, objs, no = _scene(3)
     assert refused(call(cams, globs, 1, -1, objs, no), text="numFrames")
     for n in (abi.RM_MAX_BATCH_FRAMES + 1, INT_MAX):
-        assert refused(call(cams, globs, 1, n, objs, no), abi.RM_ERR_CAPACITY, "RM_MAX_BATCH_FRAMES")
+        assert refused(call(cams, globs, 1, n, objs, no), "RM_MAX_BATCH_FRAMES", want=abi.RM_ERR_CAPACITY)
     # numFrames == 0: RM_OK with null outputs, nothing is read
     assert call(cams, globs, 1, 0, objs, no, nd=None, ids=None) == abi.RM_OK
     assert call(None, None, 0, 0, None, 0, s=None, nd=None, ids=None) == abi.RM_OK
@@ -107,20 +87,20 @@ def test_the_three_unsupported_cases():
     L = lib()
     cams, globs, objs, no = _scene(3)
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_TERRAIN | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(call(cams, globs, 3, 3, objs, no, s=abi.default_settings(features=feat)), abi.RM_ERR_UNSUPPORTED), feat
+        assert refused(call(cams, globs, 3, 3, objs, no, s=abi.default_settings(features=feat)), want=abi.RM_ERR_UNSUPPORTED), feat
     # the other feature bits are fine: they get as far as the output pointers
     for feat in (0, abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_NIGHTSKY_BACKGROUND, abi.RM_FEAT_REFERENCE_DEFAULT):
         assert refused(call(cams, globs, 3, 3, objs, no, s=abi.default_settings(features=feat), nd=None), text="null output"), feat
     # isTwoD in frame 2 of 3: the error names the frame
     globs[2].isTwoD = 1
-    assert refused(call(cams, globs, 3, 3, objs, no), abi.RM_ERR_UNSUPPORTED, "frame 2")
+    assert refused(call(cams, globs, 3, 3, objs, no), "frame 2", want=abi.RM_ERR_UNSUPPORTED)
     assert refused(call(cams, globs, 1, 3, objs, no, nd=None), text="null output")  # with one shared globals frame 2's is never read
     globs[2].isTwoD = 0
     globs[0].isTwoD = 1
-    assert refused(call(cams, globs, 1, 3, objs, no), abi.RM_ERR_UNSUPPORTED, "frame 0")
+    assert refused(call(cams, globs, 1, 3, objs, no), "frame 0", want=abi.RM_ERR_UNSUPPORTED)
     globs[0].isTwoD = 0
     objs[1].type = abi.RM_CUSTOM
-    assert refused(call(cams, globs, 3, 3, objs, no), abi.RM_ERR_UNSUPPORTED, "object 1")
+    assert refused(call(cams, globs, 3, 3, objs, no), "object 1", want=abi.RM_ERR_UNSUPPORTED)
     assert "CUSTOM" in L.rm_last_error().decode()
 
 
@@ -130,10 +110,10 @@ def test_object_validation_and_outputs():
     assert refused(call(cams, globs, 3, 3, objs, -1))
     assert refused(call(cams, globs, 3, 3, objs, no, s=None))
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(call(cams, globs, 3, 3, many, abi.RM_MAX_OBJECTS + 1), abi.RM_ERR_CAPACITY)
+    assert refused(call(cams, globs, 3, 3, many, abi.RM_MAX_OBJECTS + 1), want=abi.RM_ERR_CAPACITY)
     assert refused(call(cams, globs, 3, 3, objs, no, s=abi.default_settings(maxSteps=-1)), text="loop bound")
     objs[2].type = 99
-    assert refused(call(cams, globs, 3, 3, objs, no), abi.RM_ERR_UNSUPPORTED, "object 2")
+    assert refused(call(cams, globs, 3, 3, objs, no), "object 2", want=abi.RM_ERR_UNSUPPORTED)
     objs[2].type = abi.RM_TORUS
     # a texLoc, a sky box or an emissive rectangle without its sampler is not an error here: the call gets to its outputs
     objs[0].texLoc = 3
@@ -143,9 +123,7 @@ def test_object_validation_and_outputs():
     assert refused(call(cams, globs, 3, 3, objs, no, s=s, ids=None), text="null output")
     assert refused(call(cams, globs, 3, 3, None, 0, nd=None), text="null output")  # an empty table needs no pointer
     # host memory is not device memory: each output is checked, the optional one too
-    host = np.zeros(3 * 24 * 32 * 4, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(call(cams, globs, 3, 3, objs, no, nd=hp, ids=hp), text="d_normalDepth")
+    assert refused(call(cams, globs, 3, 3, objs, no, nd=HP, ids=HP), text="d_normalDepth")
 
 
 # ---------------------------------------------------------------- the specification, on the CPU

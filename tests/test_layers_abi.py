@@ -3,79 +3,59 @@ unchanged ABI version, the comments carry the definitions, the Python methods ha
 error returns its status, in the documented order, before the first HIP call — with pointers that would fault if read."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
 import helpers as h
+from abi_helpers import CAPACITY, FAKE, HEADER, HP, INT_MAX, fake, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
+from scene_builders import three_primitives_lit as _scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
-INVALID, CAPACITY, UNSUPPORTED = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED
+UNSUPPORTED = abi.RM_ERR_UNSUPPORTED
 TERRAIN, CLOUD, SEA = abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA
 LAYER_MASKS = (TERRAIN, CLOUD, SEA, TERRAIN | abi.RM_FEAT_PERLIN_BUMP, TERRAIN | CLOUD | SEA | abi.RM_FEAT_SKY_BACKGROUND)
 
 
 # ---------------------------------------------------------------- the symbols and the written definitions
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-
-
-def _comment(name):
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*(?:#define[^\n]*\n)*int " + name + r"\b", HEADER, flags=re.S)
-    assert m, f"no comment in front of {name}"
-    return re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-
-
 def test_header_declares_and_library_exports_both_symbols():
-    assert _params("rm_shade_rays_layers") == [
+    assert ah.params("rm_shade_rays_layers") == [
         "const RmRay *d_rays", "int numRays", "float far", "int imageWidth", "const RmObject *objs", "int numObjects",
         "const RmLight *lights", "int numLights", "const RmGlobals *g", "const RmSettings *s", "const RmResources *res", "float *d_rgba",
         "float *d_bright", "void *stream"]
-    assert _params("rm_trace_rays_layers") == [
+    assert ah.params("rm_trace_rays_layers") == [
         "const RmRay *d_rays", "int numRays", "int imageWidth", "const RmObject *objs", "int numObjects", "const RmGlobals *g",
         "const RmSettings *s", "unsigned mode", "RmRayHit *d_hits", "void *stream"]
     # the old symbols' arguments with imageWidth put in: nothing else moved
-    old = _params("rm_shade_rays")
-    assert _params("rm_shade_rays_layers") == old[:3] + ["int imageWidth"] + old[3:]
-    old = _params("rm_trace_rays")
-    assert _params("rm_trace_rays_layers") == old[:2] + ["int imageWidth"] + old[2:]
+    old = ah.params("rm_shade_rays")
+    assert ah.params("rm_shade_rays_layers") == old[:3] + ["int imageWidth"] + old[3:]
+    old = ah.params("rm_trace_rays")
+    assert ah.params("rm_trace_rays_layers") == old[:2] + ["int imageWidth"] + old[2:]
     s, t = SIGNATURES["rm_shade_rays"], SIGNATURES["rm_trace_rays"]
     assert SIGNATURES["rm_shade_rays_layers"] == (C.c_int, s[1][:3] + [C.c_int] + s[1][3:])
     assert SIGNATURES["rm_trace_rays_layers"] == (C.c_int, t[1][:2] + [C.c_int] + t[1][2:])
-    lib()
-    handle = C.CDLL(LIB_PATH)  # bindings detect the symbols by lookup
-    assert hasattr(handle, "rm_shade_rays_layers") and hasattr(handle, "rm_trace_rays_layers")
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5 and re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_exported(["rm_shade_rays_layers", "rm_trace_rays_layers"])  # bindings detect the symbols by lookup
+    ah.assert_abi_version()
     for name, val in (("RM_HIT_SEA", r"\(-3\)"), ("RM_HIT_TERRAIN", r"\(-4\)")):
         assert re.search(rf"#define\s+{name}\s+{val}", HEADER), name
     assert (abi.RM_HIT_SEA, abi.RM_HIT_TERRAIN, abi.RM_PATH_SHADE_RAYS_LAYERS, abi.RM_PATH_TRACE_RAYS_LAYERS) == (-3, -4, 14, 15)
 
 
 def test_header_comments_carry_the_definitions():
-    text = _comment("rm_shade_rays_layers")
-    for words in ("imageWidth", "iResolution.x", "frag:2284-2310", "frag:2444-2456", "frag:2459-2475", "frag:2506-2518", "frag:2555-2567",
-                  "frag:2422-2426", "validated but NOT read", "cloud over terrain over sea over the object hit", "fires no secondary rays",
-                  "in every bit", "before any HIP call", "rm_debug_last_path() = 14", "symbol lookup", "RM_ERR_INVALID_ARGUMENT",
-                  "isTwoD"):
-        assert words in text, f"the comment of rm_shade_rays_layers lacks: {words}"
-    text = _comment("rm_trace_rays_layers")
-    for words in ("raymarch(origin, dir, tMax, OUTSIDE)", "frag:2284-2291, 2252-2282", "frag:2128-2135, 2060-2090; tmin = 15",
-                  "frag:2106-2111", "frag:2243-2250", "RM_HIT_TERRAIN (−4)", "RM_HIT_SEA (−3)", "a collision response needs the surface",
-                  "not the fbm-perturbed", "(dot(d, d)·0.1) / imageWidth", "a volume has no closest hit", "RM_TRACE_NO_NORMAL",
-                  "does not see the layers", "does not touch the noise texture", "does not depend on which other rays",
-                  "before any HIP call", "rm_debug_last_path() = 15", "symbol lookup"):
-        assert words in text, f"the comment of rm_trace_rays_layers lacks: {words}"
+    ah.assert_comment_has("rm_shade_rays_layers", (
+        "imageWidth", "iResolution.x", "frag:2284-2310", "frag:2444-2456", "frag:2459-2475", "frag:2506-2518", "frag:2555-2567",
+        "frag:2422-2426", "validated but NOT read", "cloud over terrain over sea over the object hit", "fires no secondary rays",
+        "in every bit", "before any HIP call", "rm_debug_last_path() = 14", "symbol lookup", "RM_ERR_INVALID_ARGUMENT",
+        "isTwoD"))
+    ah.assert_comment_has("rm_trace_rays_layers", (
+        "raymarch(origin, dir, tMax, OUTSIDE)", "frag:2284-2291, 2252-2282", "frag:2128-2135, 2060-2090; tmin = 15",
+        "frag:2106-2111", "frag:2243-2250", "RM_HIT_TERRAIN (−4)", "RM_HIT_SEA (−3)", "a collision response needs the surface",
+        "not the fbm-perturbed", "(dot(d, d)·0.1) / imageWidth", "a volume has no closest hit", "RM_TRACE_NO_NORMAL",
+        "does not see the layers", "does not touch the noise texture", "does not depend on which other rays",
+        "before any HIP call", "rm_debug_last_path() = 15", "symbol lookup"))
     assert re.search(r"14 = a launch of rm_shade_rays_layers, 15 = a\s+\*?\s*launch of rm_trace_rays_layers", HEADER), \
         "rm_debug_last_path's comment does not document 14 and 15"
-    timing = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int rm_get_stage_timing\b", HEADER, flags=re.S).group(1)
+    timing = ah.comment_before("rm_get_stage_timing")
     assert "rm_shade_rays_layers" in timing and "rm_trace_rays_layers" in timing
 
 
@@ -96,17 +76,9 @@ def test_python_signatures():
 
 
 # ---------------------------------------------------------------- refusals, all without a device
-FAKE = C.c_void_p(0x1000)  # 16-byte aligned and never dereferenced: every call that gets it fails its checks first
 DEFAULT = object()
 SHADE_ARRAYS = "null d_rays or d_rgba"  # the first check behind the scene's: a call that gets this far passed everything before it
 TRACE_ARRAYS = "null d_rays or d_hits"
-
-
-def _scene():
-    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
-    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (0, -1, 0)), h.make_light(abi.RM_LIGHT_POINT, pos=(1, 2, 3)))
-    return objs, 3, lights, 2, h.make_globals()
 
 
 def _noise():
@@ -125,11 +97,6 @@ def trace(objs, no, g, s=DEFAULT, n=100, width=64, mode=0, rays=FAKE, hits=FAKE)
     s = abi.default_settings() if s is DEFAULT else s
     return lib().rm_trace_rays_layers(rays, n, width, objs, no, C.byref(g) if g is not None else None,
                                       C.byref(s) if s is not None else None, mode, hits, None)
-
-
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
 
 
 def feat(bits, **over):
@@ -194,22 +161,22 @@ def test_the_layers_are_accepted_and_occlusion_with_one_is_refused():
         assert refused(shade(objs, no, lights, nl, g, s=feat(bits), res=_noise(), rays=None), text=SHADE_ARRAYS), bits
         for mode in (abi.RM_TRACE_CLOSEST, abi.RM_TRACE_NO_NORMAL):
             assert refused(trace(objs, no, g, s=feat(bits), mode=mode, rays=None), text=TRACE_ARRAYS), (bits, mode)
-        assert refused(trace(objs, no, g, s=feat(bits), mode=abi.RM_TRACE_OCCLUSION), UNSUPPORTED, "RM_TRACE_OCCLUSION"), bits
+        assert refused(trace(objs, no, g, s=feat(bits), mode=abi.RM_TRACE_OCCLUSION), "RM_TRACE_OCCLUSION", want=UNSUPPORTED), bits
         assert "TERRAIN / CLOUD / SEA" in lib().rm_last_error().decode()
     for bits in (0, abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_REFERENCE_DEFAULT):  # without a layer bit occlusion is rm_trace_rays'
         assert refused(trace(objs, no, g, s=feat(bits), mode=abi.RM_TRACE_OCCLUSION, rays=None), text=TRACE_ARRAYS), bits
     # occlusion with a layer comes before the 2-D mode and the table's content
-    assert refused(trace(objs, no, h.make_globals(two_d=1), s=feat(CLOUD), mode=abi.RM_TRACE_OCCLUSION), UNSUPPORTED, "RM_TRACE_OCCLUSION")
+    assert refused(trace(objs, no, h.make_globals(two_d=1), s=feat(CLOUD), mode=abi.RM_TRACE_OCCLUSION), "RM_TRACE_OCCLUSION", want=UNSUPPORTED)
     objs[1].type = abi.RM_CUSTOM
-    assert refused(trace(objs, no, g, s=feat(TERRAIN), mode=abi.RM_TRACE_OCCLUSION), UNSUPPORTED, "RM_TRACE_OCCLUSION")
-    assert refused(trace(objs, no, g, s=feat(TERRAIN)), UNSUPPORTED, "object 1")
+    assert refused(trace(objs, no, g, s=feat(TERRAIN), mode=abi.RM_TRACE_OCCLUSION), "RM_TRACE_OCCLUSION", want=UNSUPPORTED)
+    assert refused(trace(objs, no, g, s=feat(TERRAIN)), "object 1", want=UNSUPPORTED)
 
 
 def test_the_sea_needs_the_noise_sampler_to_shade_and_not_to_trace():
     objs, no, lights, nl, g = _scene()
     for bits in (SEA, SEA | TERRAIN | CLOUD, SEA | abi.RM_FEAT_SKY_BACKGROUND):
-        assert refused(shade(objs, no, lights, nl, g, s=feat(bits)), UNSUPPORTED, "noise"), bits
-        assert refused(shade(objs, no, lights, nl, g, s=feat(bits), res=abi.RmResources()), UNSUPPORTED, "noise"), bits
+        assert refused(shade(objs, no, lights, nl, g, s=feat(bits)), "noise", want=UNSUPPORTED), bits
+        assert refused(shade(objs, no, lights, nl, g, s=feat(bits), res=abi.RmResources()), "noise", want=UNSUPPORTED), bits
         assert "supply RmResources.noise" in lib().rm_last_error().decode()  # rm_render_res's text
         assert refused(shade(objs, no, lights, nl, g, s=feat(bits), res=_noise(), rays=None), text=SHADE_ARRAYS), bits
         assert refused(trace(objs, no, g, s=feat(bits), rays=None), text=TRACE_ARRAYS), bits  # the sea's geometry reads no sampler
@@ -223,38 +190,38 @@ def test_two_d_capacity_loop_bounds_and_types_in_order():
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
     lots = (abi.RmLight * (abi.RM_MAX_LIGHTS + 1))(*[h.make_light(abi.RM_LIGHT_POINT) for _ in range(abi.RM_MAX_LIGHTS + 1)])
     for bits in (abi.RM_FEAT_REFERENCE_DEFAULT, TERRAIN | CLOUD):
-        assert refused(shade(objs, no, lights, nl, two_d, s=feat(bits)), UNSUPPORTED, "isTwoD"), bits
-        assert refused(trace(objs, no, two_d, s=feat(bits)), UNSUPPORTED, "isTwoD"), bits
-        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=feat(bits)), CAPACITY, "RM_MAX_OBJECTS"), bits
-        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, g, s=feat(bits)), CAPACITY, "RM_MAX_OBJECTS"), bits
+        assert refused(shade(objs, no, lights, nl, two_d, s=feat(bits)), "isTwoD", want=UNSUPPORTED), bits
+        assert refused(trace(objs, no, two_d, s=feat(bits)), "isTwoD", want=UNSUPPORTED), bits
+        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=feat(bits)), "RM_MAX_OBJECTS", want=CAPACITY), bits
+        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, g, s=feat(bits)), "RM_MAX_OBJECTS", want=CAPACITY), bits
         assert refused(shade(many, abi.RM_MAX_OBJECTS, lights, nl, g, s=feat(bits), rays=None), text=SHADE_ARRAYS), bits
         assert refused(trace(many, abi.RM_MAX_OBJECTS, g, s=feat(bits), rays=None), text=TRACE_ARRAYS), bits
-        assert refused(shade(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g, s=feat(bits)), CAPACITY, "RM_MAX_LIGHTS"), bits
+        assert refused(shade(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g, s=feat(bits)), "RM_MAX_LIGHTS", want=CAPACITY), bits
         assert refused(shade(objs, no, lots, abi.RM_MAX_LIGHTS, g, s=feat(bits), rays=None), text=SHADE_ARRAYS), bits
         for field in ("maxSteps", "fractalIters", "mengerLevels", "numReflection"):
             assert refused(shade(objs, no, lights, nl, g, s=feat(bits, **{field: -1})), text="loop bound"), (bits, field)
         for field in ("maxSteps", "fractalIters", "mengerLevels"):
             assert refused(trace(objs, no, g, s=feat(bits, **{field: -1})), text="loop bound"), (bits, field)
         # the 2-D mode comes before the capacity, the capacity before the loop bounds
-        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, two_d, s=feat(bits)), UNSUPPORTED, "isTwoD"), bits
-        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, two_d, s=feat(bits)), UNSUPPORTED, "isTwoD"), bits
-        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=feat(bits, maxSteps=-1)), CAPACITY), bits
-        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, g, s=feat(bits, maxSteps=-1)), CAPACITY), bits
+        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, two_d, s=feat(bits)), "isTwoD", want=UNSUPPORTED), bits
+        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, two_d, s=feat(bits)), "isTwoD", want=UNSUPPORTED), bits
+        assert refused(shade(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=feat(bits, maxSteps=-1)), want=CAPACITY), bits
+        assert refused(trace(many, abi.RM_MAX_OBJECTS + 1, g, s=feat(bits, maxSteps=-1)), want=CAPACITY), bits
     # the loop bounds come before the types
     layers = feat(TERRAIN | CLOUD)
     objs[1].type = abi.RM_CUSTOM
     assert refused(shade(objs, no, lights, nl, g, s=feat(TERRAIN | CLOUD, maxSteps=-1)), text="loop bound")
     assert refused(trace(objs, no, g, s=feat(TERRAIN | CLOUD, maxSteps=-1)), text="loop bound")
-    assert refused(shade(objs, no, lights, nl, g, s=layers), UNSUPPORTED, "object 1") and "CUSTOM" in lib().rm_last_error().decode()
-    assert refused(trace(objs, no, g, s=layers), UNSUPPORTED, "object 1") and "CUSTOM" in lib().rm_last_error().decode()
+    assert refused(shade(objs, no, lights, nl, g, s=layers), "object 1", want=UNSUPPORTED) and "CUSTOM" in lib().rm_last_error().decode()
+    assert refused(trace(objs, no, g, s=layers), "object 1", want=UNSUPPORTED) and "CUSTOM" in lib().rm_last_error().decode()
     for ty in (99, -1):
         objs[1].type = abi.RM_CUBE
         objs[2].type = ty
-        assert refused(shade(objs, no, lights, nl, g, s=layers), UNSUPPORTED, "object 2"), ty
-        assert refused(trace(objs, no, g, s=layers), UNSUPPORTED, "object 2"), ty
+        assert refused(shade(objs, no, lights, nl, g, s=layers), "object 2", want=UNSUPPORTED), ty
+        assert refused(trace(objs, no, g, s=layers), "object 2", want=UNSUPPORTED), ty
     objs[2].type = abi.RM_TORUS
     lights[1].type = 7
-    assert refused(shade(objs, no, lights, nl, g, s=layers), UNSUPPORTED, "light 1")
+    assert refused(shade(objs, no, lights, nl, g, s=layers), "light 1", want=UNSUPPORTED)
     assert refused(trace(objs, no, g, s=layers, rays=None), text=TRACE_ARRAYS)  # a trace reads no light
 
 
@@ -269,7 +236,7 @@ def test_the_arrays():
         assert refused(trace(None, 0, g, s=s, hits=None), text=TRACE_ARRAYS)  # an empty table needs no pointer
         assert refused(shade(None, 0, None, 0, g, s=s, rays=None), text=SHADE_ARRAYS)
         for off in (4, 8, 12, 1):
-            bad = C.c_void_p(0x1000 + off)
+            bad = fake(0x1000 + off)
             assert refused(shade(objs, no, lights, nl, g, s=s, rays=bad), text="16-byte aligned"), off
             assert refused(shade(objs, no, lights, nl, g, s=s, rgba=bad), text="16-byte aligned"), off
             assert refused(shade(objs, no, lights, nl, g, s=s, bright=bad), text="16-byte aligned"), off
@@ -277,11 +244,9 @@ def test_the_arrays():
             assert refused(trace(objs, no, g, s=s, hits=bad), text="16-byte aligned"), off
     # the arrays come behind everything about the scene
     objs[0].type = abi.RM_CUSTOM
-    assert refused(shade(objs, no, lights, nl, g, s=layers, rays=None), UNSUPPORTED, "object 0")
-    assert refused(trace(objs, no, g, s=layers, rays=None), UNSUPPORTED, "object 0")
+    assert refused(shade(objs, no, lights, nl, g, s=layers, rays=None), "object 0", want=UNSUPPORTED)
+    assert refused(trace(objs, no, g, s=layers, rays=None), "object 0", want=UNSUPPORTED)
     objs[0].type = abi.RM_SPHERE
     # host memory is not device memory: the only check that asks the HIP runtime, and the last
-    host = np.zeros(100 * 8 + 8, dtype=np.float32)
-    hp = C.c_void_p((host.ctypes.data + 15) & ~15)
-    assert refused(shade(objs, no, lights, nl, g, s=layers, rays=hp, rgba=hp), text="d_rays")
-    assert refused(trace(objs, no, g, s=layers, rays=hp, hits=hp), text="d_rays")
+    assert refused(shade(objs, no, lights, nl, g, s=layers, rays=HP, rgba=HP), text="d_rays")
+    assert refused(trace(objs, no, g, s=layers, rays=HP, hits=HP), text="d_rays")

@@ -3,47 +3,39 @@ version, the comment carries the definition, every argument error returns its st
 call — with pointers that would fault if read — and rm_write_ply_ex, a host function, writes what a few lines of NumPy read back."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 
+import abi_helpers as ah
 import helpers as h
 import scene_builders as SB
+from abi_helpers import CAPACITY, FAKE, HEADER, HP, INT_MAX, INVALID, fake, refused
+from abi_helpers import inf as INF
 from raymarcher_amd import abi, lib, write_ply, write_ply_ex
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
+from scene_builders import three_primitives_lit as _scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
-INF = float("inf")
-INVALID, CAPACITY, UNSUPPORTED = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED
-
-
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\b(?:int|void)\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+UNSUPPORTED = abi.RM_ERR_UNSUPPORTED
 
 
 # ---------------------------------------------------------------- the symbols and the written definition
 def test_header_declares_and_library_exports_the_symbols():
-    assert _params("rm_shade_points") == [
+    assert ah.params("rm_shade_points") == [
         "const float *d_points", "const float *d_view", "int numPoints", "const RmPointsSettings *ps", "const RmObject *objs",
         "int numObjects", "const RmLight *lights", "int numLights", "const RmGlobals *g", "const RmSettings *s", "const RmResources *res",
         "RmSurfacePoint *d_surface", "float *d_ao", "float *d_rgba", "void *stream"]
-    assert _params("rm_points_settings_default") == ["RmPointsSettings *ps"]
-    assert _params("rm_write_ply_ex") == ["const char *path", "const float *vertices4", "int numVertices", "const int32_t *quads4",
-                                          "int numQuads", "const uint8_t *rgb", "const float *normals4"]
-    lib()
-    handle = C.CDLL(LIB_PATH)
+    assert ah.params("rm_points_settings_default", "void") == ["RmPointsSettings *ps"]
+    assert ah.params("rm_write_ply_ex") == [
+        "const char *path", "const float *vertices4", "int numVertices", "const int32_t *quads4",
+        "int numQuads", "const uint8_t *rgb", "const float *normals4"]
+    ah.assert_exported(["rm_shade_points", "rm_points_settings_default", "rm_write_ply_ex"])
     for name in ("rm_shade_points", "rm_points_settings_default", "rm_write_ply_ex"):
-        assert hasattr(handle, name) and name in SIGNATURES, name
+        assert name in SIGNATURES, name
     assert len(SIGNATURES["rm_shade_points"][1]) == 15 and len(SIGNATURES["rm_write_ply_ex"][1]) == 7
     assert abi.RM_PATH_SHADE_POINTS == 17 and abi.RM_MAX_PROJECT_STEPS == 16
     assert re.search(r"#define\s+RM_MAX_PROJECT_STEPS\s+16\b", HEADER)
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5 and re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
 
 
 def test_struct_sizes_and_layouts():
@@ -64,16 +56,13 @@ def test_points_settings_default():
 
 
 def test_header_comment_carries_the_definition():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*typedef struct RmSurfacePoint\b", HEADER, flags=re.S)
-    assert m, "no comment in front of rm_shade_points' types"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("bit for bit", "Invalid point", "RM_RAY_INVALID", "evaluates nothing", "cannot refuse them", "frag:1406-1430",
-                  "frag:1436-1444", "never bumped", "madd(N, −e, p)", "maxMove·maxMove", "keeps the last accepted p", "UB3",
-                  "frag:1679-1691", "frag:1729-1740", "whatever s->enableAmbientOcclusion says", "frag:2337-2375", "frag:1842-1933",
-                  "frag:2354-2365", "−N", "No reflection and no refraction", "1 + 4 evaluations", "5 per projection step",
-                  "does not depend on which points", "same bits whichever", "before any HIP call", "rm_debug_last_path() = 17",
-                  "symbol lookup"):
-        assert words in text, f"the comment of rm_shade_points lacks: {words}"
+    ah.assert_comment_has("RmSurfacePoint", (
+        "bit for bit", "Invalid point", "RM_RAY_INVALID", "evaluates nothing", "cannot refuse them", "frag:1406-1430",
+        "frag:1436-1444", "never bumped", "madd(N, −e, p)", "maxMove·maxMove", "keeps the last accepted p", "UB3",
+        "frag:1679-1691", "frag:1729-1740", "whatever s->enableAmbientOcclusion says", "frag:2337-2375", "frag:1842-1933",
+        "frag:2354-2365", "−N", "No reflection and no refraction", "1 + 4 evaluations", "5 per projection step",
+        "does not depend on which points", "same bits whichever", "before any HIP call", "rm_debug_last_path() = 17",
+        "symbol lookup"))
     assert re.search(r"17 = a launch of rm_shade_points", HEADER), "rm_debug_last_path's comment does not document 17"
 
 
@@ -93,15 +82,7 @@ def test_python_signatures():
 
 
 # ---------------------------------------------------------------- refusals, all without a device
-FAKE = C.c_void_p(0x1000)  # 16-byte aligned and never dereferenced: every call that gets it fails its checks first
 DEFAULT = object()
-
-
-def _scene():
-    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
-    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (0, -1, 0)), h.make_light(abi.RM_LIGHT_POINT, pos=(1, 2, 3)))
-    return objs, 3, lights, 2, h.make_globals()
 
 
 def call(objs, no, lights, nl, g, s=DEFAULT, n=100, ps=DEFAULT, res=None, points=FAKE, view=None, surface=None, ao=None, rgba=FAKE,
@@ -115,11 +96,6 @@ def call(objs, no, lights, nl, g, s=DEFAULT, n=100, ps=DEFAULT, res=None, points
     return lib().rm_shade_points(points, view, n, C.byref(ps) if ps is not None else None, objs, no, lights, nl,
                                  C.byref(g) if g is not None else None, C.byref(s) if s is not None else None,
                                  C.byref(res) if res is not None else None, surface, ao, rgba, None)
-
-
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
 
 
 ARRAYS = "null d_points"  # the first check behind the scene's: a call that gets this far passed everything before it
@@ -180,38 +156,38 @@ def test_point_settings_in_order():
     del bad["maxMove"]
     assert refused(call(objs, no, lights, nl, g, rgba=None, s=sea, **bad), text="projectSteps")
     assert refused(call(objs, no, lights, nl, g, rgba=None, s=sea), text="all null")
-    assert refused(call(objs, no, lights, nl, g, s=sea), UNSUPPORTED, "TERRAIN / CLOUD / SEA")
+    assert refused(call(objs, no, lights, nl, g, s=sea), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED)
 
 
 def test_layers_capacity_loop_bounds_and_types_in_order():
     objs, no, lights, nl, g = _scene()
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_TERRAIN | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
+        assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
     for feat in (0, abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, abi.RM_FEAT_REFERENCE_DEFAULT):
         assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat), points=None), text=ARRAYS), feat
-    assert refused(call(objs, no, lights, nl, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
+    assert refused(call(objs, no, lights, nl, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
     lots = (abi.RmLight * (abi.RM_MAX_LIGHTS + 1))(*[h.make_light(abi.RM_LIGHT_POINT) for _ in range(abi.RM_MAX_LIGHTS + 1)])
     for outs in (dict(), dict(rgba=None, surface=FAKE), dict(rgba=None, ao=FAKE)):  # with and without the colour
-        assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, **outs), CAPACITY, "RM_MAX_OBJECTS"), outs
+        assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, **outs), "RM_MAX_OBJECTS", want=CAPACITY), outs
         assert refused(call(many, abi.RM_MAX_OBJECTS, lights, nl, g, points=None, **outs), text=ARRAYS), outs
         for field in ("maxSteps", "fractalIters", "mengerLevels"):
             assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(**{field: -1}), **outs), text="loop bound"), field
         # the layers come before the capacity, the capacity before the loop bounds, the loop bounds before the types
         assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(features=abi.RM_FEAT_CLOUD), **outs),
-                       UNSUPPORTED, "TERRAIN")
-        assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(maxSteps=-1), **outs), CAPACITY)
+                       "TERRAIN", want=UNSUPPORTED)
+        assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(maxSteps=-1), **outs), want=CAPACITY)
         objs[1].type = abi.RM_CUSTOM
         assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(maxSteps=-1), **outs), text="loop bound")
-        assert refused(call(objs, no, lights, nl, g, **outs), UNSUPPORTED, "object 1")
+        assert refused(call(objs, no, lights, nl, g, **outs), "object 1", want=UNSUPPORTED)
         assert "CUSTOM" in lib().rm_last_error().decode()
         objs[1].type = abi.RM_CUBE
     # what only the colour reads is only checked with it: the light table's size and types, numReflection
-    assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g), CAPACITY, "RM_MAX_LIGHTS")
+    assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g), "RM_MAX_LIGHTS", want=CAPACITY)
     assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g, rgba=None, surface=FAKE, points=None), text=ARRAYS)
     assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(numReflection=-1)), text="loop bound")
     lights[1].type = 7
-    assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "light 1")
+    assert refused(call(objs, no, lights, nl, g), "light 1", want=UNSUPPORTED)
     assert refused(call(objs, no, lights, nl, g, rgba=None, ao=FAKE, points=None), text=ARRAYS)
 
 
@@ -221,16 +197,16 @@ def test_samplers_are_asked_for_only_with_the_colour():
     objs, no, lights, nl, g = _scene()
     tex = abi.RmTexture(0x2000, 4, 4)
     night = abi.default_settings(features=abi.RM_FEAT_NIGHTSKY_BACKGROUND)
-    assert refused(call(objs, no, lights, nl, g, s=night), UNSUPPORTED, "noise")
+    assert refused(call(objs, no, lights, nl, g, s=night), "noise", want=UNSUPPORTED)
     assert refused(call(objs, no, lights, nl, g, s=night, rgba=None, surface=FAKE, points=None), text=ARRAYS)
     res = abi.RmResources()
     res.noise = tex
     assert refused(call(objs, no, lights, nl, g, s=night, res=res, points=None), text=ARRAYS)
     box = abi.default_settings(enableSkyBox=1)
-    assert refused(call(objs, no, lights, nl, g, s=box), UNSUPPORTED, "enableSkyBox")
+    assert refused(call(objs, no, lights, nl, g, s=box), "enableSkyBox", want=UNSUPPORTED)
     assert refused(call(objs, no, lights, nl, g, s=box, rgba=None, ao=FAKE, points=None), text=ARRAYS)
     objs[0].texLoc = 0
-    assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "texLoc")
+    assert refused(call(objs, no, lights, nl, g), "texLoc", want=UNSUPPORTED)
     assert refused(call(objs, no, lights, nl, g, rgba=None, surface=FAKE, points=None), text=ARRAYS)
     res = abi.RmResources()
     arr = (abi.RmTexture * 1)(tex)
@@ -238,9 +214,9 @@ def test_samplers_are_asked_for_only_with_the_colour():
     assert refused(call(objs, no, lights, nl, g, res=res, points=None), text=ARRAYS)
     objs[0].texLoc = -1
     res.numTextures = abi.RM_MAX_TEXTURES + 1
-    assert refused(call(objs, no, lights, nl, g, res=res), CAPACITY, "RM_MAX_TEXTURES")
+    assert refused(call(objs, no, lights, nl, g, res=res), "RM_MAX_TEXTURES", want=CAPACITY)
     scene = SB.area_light_scene(8, 8)
-    assert refused(call(*scene[1:6]), UNSUPPORTED, "LTC")
+    assert refused(call(*scene[1:6]), "LTC", want=UNSUPPORTED)
     assert refused(call(*scene[1:6], rgba=None, surface=FAKE, points=None), text=ARRAYS)
     res = abi.RmResources()
     res.ltc1, res.ltc2 = 0x3000, 0x4000
@@ -251,19 +227,17 @@ def test_the_five_arrays():
     objs, no, lights, nl, g = _scene()
     assert refused(call(objs, no, lights, nl, g, points=None), text=ARRAYS)
     for off in (4, 8, 12, 1):
-        bad = C.c_void_p(0x1000 + off)
+        bad = fake(0x1000 + off)
         for name in ("points", "view", "surface", "rgba"):
             assert refused(call(objs, no, lights, nl, g, **{name: bad}), text="16-byte aligned"), (name, off)
     for off in (1, 2, 3):
-        assert refused(call(objs, no, lights, nl, g, ao=C.c_void_p(0x1000 + off)), text="4-byte aligned"), off
+        assert refused(call(objs, no, lights, nl, g, ao=fake(0x1000 + off)), text="4-byte aligned"), off
     # the arrays come behind everything about the scene
     objs[0].type = abi.RM_CUSTOM
-    assert refused(call(objs, no, lights, nl, g, points=None), UNSUPPORTED, "object 0")
+    assert refused(call(objs, no, lights, nl, g, points=None), "object 0", want=UNSUPPORTED)
     objs[0].type = abi.RM_SPHERE
     # host memory is not device memory: the only check that asks the HIP runtime, and the last
-    host = np.zeros(100 * 8 + 8, dtype=np.float32)
-    hp = C.c_void_p((host.ctypes.data + 15) & ~15)
-    assert refused(call(objs, no, lights, nl, g, points=hp, rgba=hp), text="d_points")
+    assert refused(call(objs, no, lights, nl, g, points=HP, rgba=HP), text="d_points")
 
 
 # ---------------------------------------------------------------- rm_write_ply_ex

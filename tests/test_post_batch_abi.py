@@ -1,29 +1,19 @@
 """rm_post_process_batch / rm_frames_to_rgba8 without a GPU: the header declares them, the library exports them, and every argument
 error returns its status before the first HIP call; Renderer.post_process_batch / to_rgba8_batch / render_sequence check lengths,
 shapes and types in Python."""
-import ctypes as C
-import os
-import re
-
 import pytest
 
+import abi_helpers as ah
+from abi_helpers import FAKE
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call below fails its checks first
+from raymarcher_amd._lib import SIGNATURES
 
 
 def test_header_declares_and_library_exports_the_post_batch_entry_points():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    assert re.search(r"\bint\s+rm_post_process_batch\s*\(", body)
-    assert re.search(r"\bint\s+rm_frames_to_rgba8\s*\(", body)
+    assert ah.params("rm_post_process_batch") and ah.params("rm_frames_to_rgba8")
     assert "rm_post_process_batch" in SIGNATURES and "rm_frames_to_rgba8" in SIGNATURES
-    lib()
-    handle = C.CDLL(LIB_PATH)
-    assert hasattr(handle, "rm_post_process_batch") and hasattr(handle, "rm_frames_to_rgba8")
-    assert lib().rm_abi_version() == abi.RM_ABI_VERSION == 5
+    ah.assert_exported(["rm_post_process_batch", "rm_frames_to_rgba8"])
+    ah.assert_abi_version()
 
 
 def posts(*flag_sets, exposure=1.0):

@@ -3,42 +3,30 @@ version, the Python layer has its methods with their defaults, and every refusal
 status — with pointers that would fault if read — in the order the header states."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
+from abi_helpers import HEADER, HP, fake, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INVALID = abi.RM_ERR_INVALID_ARGUMENT
-FAKE = C.c_void_p(0x10000)  # aligned, never dereferenced: every call that gets it fails its checks first
-
-
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+FAKE = fake(0x10000)  # this module's arrays are 0x10000 apart: an alias or a misaligned one is told by its address
 
 
 def test_header_declares_and_library_exports_both_symbols():
-    assert _params("rm_rays_order") == ["const RmRay *d_rays", "int numRays", "int originBits", "int dirBits", "int32_t *d_order",
-                                        "RmRay *d_sorted", "uint64_t *d_keys", "void *stream"]
-    assert _params("rm_rays_restore") == ["const void *d_rows", "const int32_t *d_order", "int numRows", "int rowBytes", "void *d_out",
-                                          "void *stream"]
-    lib()
-    L = C.CDLL(LIB_PATH)
+    assert ah.params("rm_rays_order") == [
+        "const RmRay *d_rays", "int numRays", "int originBits", "int dirBits", "int32_t *d_order",
+        "RmRay *d_sorted", "uint64_t *d_keys", "void *stream"]
+    assert ah.params("rm_rays_restore") == [
+        "const void *d_rows", "const int32_t *d_order", "int numRows", "int rowBytes", "void *d_out",
+        "void *stream"]
+    ah.assert_exported(["rm_rays_order", "rm_rays_restore"])
     for name, n in (("rm_rays_order", 8), ("rm_rays_restore", 6)):
-        assert hasattr(L, name), f"the library does not export {name}"
         assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int and len(SIGNATURES[name][1]) == n
 
 
 def test_abi_version_stays_and_the_header_carries_the_definition():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert re.search(r"#define\s+RM_RAYS_ORDER_TILE\s+2048\b", HEADER) and abi.RM_RAYS_ORDER_TILE == 2048
     assert (abi.RM_RAYS_MAX_ORIGIN_BITS, abi.RM_RAYS_MAX_DIR_BITS) == (10, 11)
     words = {"rm_rays_order": ("s = (|dx| + |dy|) + |dz|", "sgn being −1 where the sign bit is set", "tMax and `reserved` are NOT read",
@@ -49,11 +37,7 @@ def test_abi_version_stays_and_the_header_carries_the_definition():
              "rm_rays_restore": ("d_out[d_order[k]] = d_rows[k]", "is skipped", "rowBytes other than 16 or 32", "d_out == d_rows",
                                  "before any HIP call")}
     for name, ws in words.items():
-        m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*(?:#define[^\n]*\n)*int " + name + r"\b", HEADER, flags=re.S)
-        assert m, f"no comment in front of {name}"
-        text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-        for w in ws:
-            assert w in text, f"the comment of {name} lacks: {w}"
+        ah.assert_comment_has(name, ws)
 
 
 def test_python_signatures_and_defaults():
@@ -72,16 +56,11 @@ def test_python_signatures_and_defaults():
     assert sig(Renderer.shade_rays) == ["self", "tables", "settings", "rays", "far", "bright", "out", "out_bright"]
 
 
-def refused(status, text):
-    msg = lib().rm_last_error().decode()
-    return status == INVALID and text in msg
-
-
-def order(rays=FAKE, n=100, ob=10, db=11, out=FAKE, srt=C.c_void_p(0x20000), keys=C.c_void_p(0x30000)):
+def order(rays=FAKE, n=100, ob=10, db=11, out=FAKE, srt=fake(0x20000), keys=fake(0x30000)):
     return lib().rm_rays_order(rays, n, ob, db, out, srt, keys, None)
 
 
-def restore(rows=FAKE, order_=C.c_void_p(0x20000), n=100, row_bytes=32, out=C.c_void_p(0x30000)):
+def restore(rows=FAKE, order_=fake(0x20000), n=100, row_bytes=32, out=fake(0x30000)):
     return lib().rm_rays_restore(rows, order_, n, row_bytes, out, None)
 
 
@@ -97,19 +76,16 @@ def test_order_refusals_in_order():
         assert refused(order(ob=ob, db=db, rays=None), "null d_rays or d_order"), (ob, db)
     assert refused(order(rays=None), "null d_rays or d_order")
     assert refused(order(out=None), "null d_rays or d_order")
-    assert refused(order(out=None, rays=C.c_void_p(0x10008)), "null d_rays or d_order")  # null before misaligned
-    for kw in (dict(rays=C.c_void_p(0x10008)), dict(rays=C.c_void_p(0x10004)), dict(srt=C.c_void_p(0x20008)), dict(keys=C.c_void_p(0x30004)),
-               dict(out=C.c_void_p(0x10002)), dict(out=C.c_void_p(0x10001))):
+    assert refused(order(out=None, rays=fake(0x10008)), "null d_rays or d_order")  # null before misaligned
+    for kw in (dict(rays=fake(0x10008)), dict(rays=fake(0x10004)), dict(srt=fake(0x20008)), dict(keys=fake(0x30004)),
+               dict(out=fake(0x10002)), dict(out=fake(0x10001))):
         assert refused(order(**kw), "misaligned"), kw
     assert refused(order(srt=FAKE), "d_sorted must not be d_rays")
-    assert refused(order(srt=FAKE, keys=C.c_void_p(0x30004)), "misaligned")            # alignment before the alias
+    assert refused(order(srt=FAKE, keys=fake(0x30004)), "misaligned")            # alignment before the alias
     # the optional outputs may be null, an 8-byte aligned d_keys and a 4-byte aligned d_order are in order: each of these gets
     # as far as the device-memory check of an array that is host memory
-    host = np.zeros(100 * 8 + 4, dtype=np.float32)
-    base = host.ctypes.data + (-host.ctypes.data) % 16
-    hp = C.c_void_p(base)
-    assert refused(order(rays=hp, srt=None, keys=None), "d_rays is not device-accessible")
-    assert refused(order(rays=hp, srt=None, keys=C.c_void_p(0x30008), out=C.c_void_p(0x10004)), "d_rays is not device-accessible")
+    assert refused(order(rays=HP, srt=None, keys=None), "d_rays is not device-accessible")
+    assert refused(order(rays=HP, srt=None, keys=fake(0x30008), out=fake(0x10004)), "d_rays is not device-accessible")
 
 
 def test_restore_refusals_in_order():
@@ -123,15 +99,13 @@ def test_restore_refusals_in_order():
     for kw in (dict(rows=None), dict(order_=None), dict(out=None)):
         assert refused(restore(**kw), "null d_rows, d_order or d_out"), kw
         assert refused(restore(row_bytes=16, **kw), "null d_rows, d_order or d_out"), kw
-    assert refused(restore(rows=None, out=C.c_void_p(0x30008)), "null d_rows")
-    for kw in (dict(rows=C.c_void_p(0x10008)), dict(out=C.c_void_p(0x30004)), dict(order_=C.c_void_p(0x20002))):
+    assert refused(restore(rows=None, out=fake(0x30008)), "null d_rows")
+    for kw in (dict(rows=fake(0x10008)), dict(out=fake(0x30004)), dict(order_=fake(0x20002))):
         assert refused(restore(**kw), "misaligned"), kw
     assert refused(restore(out=FAKE), "d_out must not be d_rows")
-    assert refused(restore(out=FAKE, order_=C.c_void_p(0x20001)), "misaligned")
-    host = np.zeros(100 * 8 + 4, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data + (-host.ctypes.data) % 16)
-    assert refused(restore(rows=hp), "d_rows is not device-accessible")
-    assert refused(restore(rows=hp, order_=C.c_void_p(0x20004), row_bytes=16), "d_rows is not device-accessible")
+    assert refused(restore(out=FAKE, order_=fake(0x20001)), "misaligned")
+    assert refused(restore(rows=HP), "d_rows is not device-accessible")
+    assert refused(restore(rows=HP, order_=fake(0x20004), row_bytes=16), "d_rows is not device-accessible")
 
 
 def test_empty_calls_read_and_write_nothing():

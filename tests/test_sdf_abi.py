@@ -3,53 +3,44 @@ ABI version, every refusal returns its status before the first HIP call — with
 header states, and rm_write_ply, a host function, writes what a few lines of Python read back."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import helpers as h
+import scene_builders as SB
 import sdf_helpers as V
+from abi_helpers import BAD_ORIGINS, BAD_STEPS, CAPACITY, FAKE, HEADER, HP, inf, nan, refused, vec3
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INVALID, CAPACITY, UNSUPPORTED, IO = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED, abi.RM_ERR_IO
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
-inf, nan = float("inf"), float("nan")
-
-
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
+UNSUPPORTED, IO = abi.RM_ERR_UNSUPPORTED, abi.RM_ERR_IO
 
 
 # ---------------------------------------------------------------- the ABI surface
 def test_header_declares_and_library_exports_the_three_symbols():
-    assert _params("rm_sdf_grid") == ["const RmObject *objs", "int numObjects", "const RmGlobals *g", "const RmSettings *s",
-                                      "const float origin[3]", "const float step[3]", "int nx", "int ny", "int nz", "float *d_dist",
-                                      "int32_t *d_objectId", "void *stream"]
-    assert _params("rm_sdf_mesh") == ["const float *d_dist", "const int32_t *d_objectId", "int nx", "int ny", "int nz",
-                                      "const float origin[3]", "const float step[3]", "float iso", "int maxVertices", "int maxQuads",
-                                      "float *d_vertices", "int32_t *d_vertexObject", "int32_t *d_quads", "uint32_t *d_counts",
-                                      "void *stream"]
-    assert _params("rm_write_ply") == ["const char *path", "const float *vertices4", "int numVertices", "const int32_t *quads4",
-                                       "int numQuads", "const uint8_t *rgb"]
-    lib()
-    L = C.CDLL(LIB_PATH)
+    assert ah.params("rm_sdf_grid") == [
+        "const RmObject *objs", "int numObjects", "const RmGlobals *g", "const RmSettings *s",
+        "const float origin[3]", "const float step[3]", "int nx", "int ny", "int nz", "float *d_dist",
+        "int32_t *d_objectId", "void *stream"]
+    assert ah.params("rm_sdf_mesh") == [
+        "const float *d_dist", "const int32_t *d_objectId", "int nx", "int ny", "int nz",
+        "const float origin[3]", "const float step[3]", "float iso", "int maxVertices", "int maxQuads",
+        "float *d_vertices", "int32_t *d_vertexObject", "int32_t *d_quads", "uint32_t *d_counts",
+        "void *stream"]
+    assert ah.params("rm_write_ply") == [
+        "const char *path", "const float *vertices4", "int numVertices", "const int32_t *quads4",
+        "int numQuads", "const uint8_t *rgb"]
+    ah.assert_exported(["rm_sdf_grid", "rm_sdf_mesh", "rm_write_ply"])
     for name in ("rm_sdf_grid", "rm_sdf_mesh", "rm_write_ply"):
-        assert hasattr(L, name), f"the library does not export {name}"
         assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int
     assert len(SIGNATURES["rm_sdf_grid"][1]) == 12 and len(SIGNATURES["rm_sdf_mesh"][1]) == 15 and len(SIGNATURES["rm_write_ply"][1]) == 6
 
 
 def test_abi_version_stays_and_the_header_carries_the_definitions():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert re.search(r"#define\s+RM_MAX_LATTICE_DIM\s+4096\b", HEADER) and abi.RM_MAX_LATTICE_DIM == 4096 and abi.RM_PATH_SDF_GRID == 16
     assert re.search(r"16 = a launch of rm_sdf_grid", HEADER), "rm_debug_last_path's comment does not document 16"
     for name, words in (("rm_sdf_grid", ("never fused", "frag:1406-1430", "rm_probe_sdscene", "a 64-bit index", "before any HIP call",
@@ -57,11 +48,7 @@ def test_abi_version_stays_and_the_header_carries_the_definitions():
                         ("rm_sdf_mesh", ("inside(v) = v < iso", "a NaN is outside", "t = 0.5f unless (t >= 0 && t <= 1)", "(c0, c3, c2, c1)",
                                          "first inside corner", "the counting call", "FULL number", "before any HIP call",
                                          "rm_set_workspace_limit", "rm_release_workspaces"))):
-        m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*(?:#define RM_MAX_LATTICE_DIM 4096\s*)?int " + name + r"\b", HEADER, flags=re.S)
-        assert m, f"no comment in front of {name}"
-        text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-        for w in words:
-            assert w in text, f"the comment of {name} lacks: {w}"
+        ah.assert_comment_has(name, words)
 
 
 def test_python_signatures():
@@ -103,37 +90,21 @@ def test_mesh_bounds_hold_the_surface_or_raise():
         mesh_bounds(SceneTables(abi.RmCamera(), None, 0, None, 0, h.make_globals()))
 
 
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
-
-
-def vec(*v):
-    return (C.c_float * 3)(*v)
-
-
 # ---------------------------------------------------------------- rm_sdf_grid's refusals, in the header's order
-def _scene():
-    objs, no = h.table([h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                        h.make_object(abi.RM_TORUS)])
-    return objs, no, h.make_globals()
-
-
 def grid(objs, no, g, s="default", origin=(0, 0, 0), step=(0.1, 0.1, 0.1), dims=(8, 8, 8), dist=FAKE, ids=FAKE):
     s = abi.default_settings() if s == "default" else s
     return lib().rm_sdf_grid(objs, no, C.byref(g) if g is not None else None, C.byref(s) if s is not None else None,
-                             vec(*origin) if origin is not None else None, vec(*step) if step is not None else None,
+                             vec3(origin), vec3(step),
                              dims[0], dims[1], dims[2], dist, ids, None)
 
 
-BAD_STEPS = ((nan, 1, 1), (1, inf, 1), (1, 1, 0.0), (-0.5, 1, 1), (1, -0.0, 1), (1, 1, -inf))
-BAD_ORIGINS = ((nan, 0, 0), (0, inf, 0), (0, 0, -inf))
+# a baked lattice may have a dimension of 1: these differ from the sampled lattices' shared table
 BAD_DIMS = ((0, 8, 8), (8, -1, 8), (8, 8, 0), (4097, 1, 1), (1, 4097, 1), (1, 1, 2 ** 31 - 1), (-2 ** 31, 8, 8))
 TOO_MANY = ((2048, 2048, 512), (4096, 4096, 128), (4096, 4096, 4096), (1291, 1291, 1291))  # 2^31 points and more
 
 
 def test_grid_pointers_and_lattice():
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     assert refused(grid(objs, no, None), text="null g, s, origin or step")
     assert refused(grid(objs, no, g, s=None), text="null g, s, origin or step")
     assert refused(grid(objs, no, g, origin=None), text="null g, s, origin or step")
@@ -158,39 +129,36 @@ def test_grid_pointers_and_lattice():
 
 
 def test_grid_unsupported_table_and_outputs():
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_SEA | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(grid(objs, no, g, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
+        assert refused(grid(objs, no, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
         # the lattice comes before the layers, the layers before the 2-D mode
         assert refused(grid(objs, no, g, s=abi.default_settings(features=feat), dims=(0, 1, 1)), text="lattice dimension"), feat
-        assert refused(grid(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN"), feat
-    assert refused(grid(objs, no, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
+        assert refused(grid(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), "TERRAIN", want=UNSUPPORTED), feat
+    assert refused(grid(objs, no, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
     many, nm = h.table([h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(grid(many, nm, g), CAPACITY, "RM_MAX_OBJECTS")
-    assert refused(grid(many, nm, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")  # the 2-D mode comes before the table
-    assert refused(grid(many, nm, g, dist=None), CAPACITY, "RM_MAX_OBJECTS")        # and the table before the output
+    assert refused(grid(many, nm, g), "RM_MAX_OBJECTS", want=CAPACITY)
+    assert refused(grid(many, nm, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)  # the 2-D mode comes before the table
+    assert refused(grid(many, nm, g, dist=None), "RM_MAX_OBJECTS", want=CAPACITY)        # and the table before the output
     assert refused(grid(many, abi.RM_MAX_OBJECTS, g, dist=None), text="null d_dist")
     for field in ("fractalIters", "mengerLevels", "maxSteps"):
         assert refused(grid(objs, no, g, s=abi.default_settings(**{field: -1})), text="loop bound"), field
     objs[1].type = abi.RM_CUSTOM
-    assert refused(grid(objs, no, g), UNSUPPORTED, "object 1") and "CUSTOM" in lib().rm_last_error().decode()
+    assert refused(grid(objs, no, g), "object 1", want=UNSUPPORTED) and "CUSTOM" in lib().rm_last_error().decode()
     objs[1].type = 99
-    assert refused(grid(objs, no, g, dist=None), UNSUPPORTED, "object 1")
+    assert refused(grid(objs, no, g, dist=None), "object 1", want=UNSUPPORTED)
     objs[1].type = abi.RM_CUBE
     assert refused(grid(objs, no, g, dist=None), text="null d_dist")
     assert refused(grid(None, 0, g, dist=None), text="null d_dist")  # an empty table needs no pointer
     # host memory is not device memory: the only check that asks the HIP runtime
-    host = np.zeros(8 * 8 * 8, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(grid(objs, no, g, dist=hp, ids=None), text="d_dist")
-    assert refused(grid(objs, no, g, dist=hp, ids=hp), text="is not device-accessible")
+    assert refused(grid(objs, no, g, dist=HP, ids=None), text="d_dist")
+    assert refused(grid(objs, no, g, dist=HP, ids=HP), text="is not device-accessible")
 
 
 # ---------------------------------------------------------------- rm_sdf_mesh's refusals, in the header's order
 def mesh(dims=(8, 8, 8), origin=(0, 0, 0), step=(0.1, 0.1, 0.1), iso=0.0, max_v=10, max_q=10, dist=FAKE, ids=FAKE, verts=FAKE, vobj=FAKE,
          quads=FAKE, counts=FAKE):
-    return lib().rm_sdf_mesh(dist, ids, dims[0], dims[1], dims[2], vec(*origin) if origin is not None else None,
-                             vec(*step) if step is not None else None, iso, max_v, max_q, verts, vobj, quads, counts, None)
+    return lib().rm_sdf_mesh(dist, ids, dims[0], dims[1], dims[2], vec3(origin), vec3(step), iso, max_v, max_q, verts, vobj, quads, counts, None)
 
 
 def test_mesh_refusals_in_order():
@@ -220,14 +188,12 @@ def test_mesh_refusals_in_order():
     assert refused(mesh(counts=None), text="null d_dist or d_counts")
     # the counting call takes null outputs, a capacity of 0 takes a null array, d_vertexObject and d_objectId may be null: each of
     # these gets as far as the device-memory check of an array that is host memory
-    host = np.zeros(8 * 8 * 8, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(mesh(max_v=0, max_q=0, verts=None, vobj=None, quads=None, ids=None, dist=hp), text="d_dist is not device-accessible")
-    assert refused(mesh(max_v=0, verts=None, vobj=None, ids=None, dist=hp), text="d_dist is not device-accessible")
-    assert refused(mesh(max_q=0, quads=None, dist=hp), text="d_dist is not device-accessible")
+    assert refused(mesh(max_v=0, max_q=0, verts=None, vobj=None, quads=None, ids=None, dist=HP), text="d_dist is not device-accessible")
+    assert refused(mesh(max_v=0, verts=None, vobj=None, ids=None, dist=HP), text="d_dist is not device-accessible")
+    assert refused(mesh(max_q=0, quads=None, dist=HP), text="d_dist is not device-accessible")
     # a lattice with a dimension of 1 is a lattice: it is checked like any other
     assert refused(mesh(dims=(1, 8, 8), dist=None), text="null d_dist or d_counts")
-    assert refused(mesh(dims=(8, 1, 8), dist=hp, max_v=0, max_q=0, verts=None, quads=None), text="d_dist is not device-accessible")
+    assert refused(mesh(dims=(8, 1, 8), dist=HP, max_v=0, max_q=0, verts=None, quads=None), text="d_dist is not device-accessible")
 
 
 # ---------------------------------------------------------------- rm_write_ply
@@ -273,8 +239,8 @@ def test_write_ply_refusals(tmp_path):
         q2[0, 2] = bad
         assert refused(_write(ok, v, q2), text="names a vertex outside"), bad
     assert not ok.exists(), "a refused call created the file"
-    assert refused(_write(tmp_path / "no_such_directory" / "m.ply", v, q), IO, "cannot open")
-    assert refused(_write(tmp_path, v, q), IO, "cannot open")  # a directory
+    assert refused(_write(tmp_path / "no_such_directory" / "m.ply", v, q), "cannot open", want=IO)
+    assert refused(_write(tmp_path, v, q), "cannot open", want=IO)  # a directory
     with pytest.raises(Exception):
         from raymarcher_amd import write_ply
         write_ply(ok, v, q, np.zeros((3, 3), np.uint8))

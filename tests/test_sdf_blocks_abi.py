@@ -3,28 +3,17 @@ them under the unchanged ABI version, the Python layer has its methods, and ever
 call — with pointers that would fault if read — in the order the header states."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
 import helpers as h
+import scene_builders as SB
+from abi_helpers import BAD_BLOCKS, BAD_ORIGINS, BAD_STEPS, BIG_BLOCKS, CAPACITY, FAKE, HEADER, HP, inf, nan, refused, vec3
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INVALID, CAPACITY, UNSUPPORTED = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
-inf, nan = float("inf"), float("nan")
+UNSUPPORTED = abi.RM_ERR_UNSUPPORTED
 NAMES = ("rm_sdf_blocks_select", "rm_sdf_grid_blocks", "rm_sdf_mesh_blocks")
-
-
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
 
 
 SCENE = ["const RmObject *objs", "int numObjects", "const RmGlobals *g", "const RmSettings *s", "const float origin[3]", "const float step[3]",
@@ -32,23 +21,21 @@ SCENE = ["const RmObject *objs", "int numObjects", "const RmGlobals *g", "const 
 
 
 def test_header_declares_and_library_exports_the_three_symbols():
-    assert _params("rm_sdf_blocks_select") == SCENE + ["float iso", "int maxBlocks", "int32_t *d_blocks", "uint32_t *d_count", "void *stream"]
-    assert _params("rm_sdf_grid_blocks") == SCENE + ["const int32_t *d_blocks", "int numBlocks", "float *d_dist", "int32_t *d_objectId",
+    assert ah.params("rm_sdf_blocks_select") == SCENE + ["float iso", "int maxBlocks", "int32_t *d_blocks", "uint32_t *d_count", "void *stream"]
+    assert ah.params("rm_sdf_grid_blocks") == SCENE + ["const int32_t *d_blocks", "int numBlocks", "float *d_dist", "int32_t *d_objectId",
                                                      "void *stream"]
-    assert _params("rm_sdf_mesh_blocks") == ["const float *d_dist", "const int32_t *d_objectId", "const int32_t *d_blocks", "int numBlocks",
-                                             "int mx", "int my", "int mz", "const float origin[3]", "const float step[3]", "float iso",
-                                             "int maxVertices", "int maxQuads", "float *d_vertices", "int32_t *d_vertexObject",
-                                             "int32_t *d_quads", "uint32_t *d_counts", "void *stream"]
-    lib()
-    L = C.CDLL(LIB_PATH)
+    assert ah.params("rm_sdf_mesh_blocks") == [
+        "const float *d_dist", "const int32_t *d_objectId", "const int32_t *d_blocks", "int numBlocks",
+        "int mx", "int my", "int mz", "const float origin[3]", "const float step[3]", "float iso",
+        "int maxVertices", "int maxQuads", "float *d_vertices", "int32_t *d_vertexObject",
+        "int32_t *d_quads", "uint32_t *d_counts", "void *stream"]
+    ah.assert_exported(NAMES)
     for name, n in zip(NAMES, (14, 14, 17)):
-        assert hasattr(L, name), f"the library does not export {name}"
         assert name in SIGNATURES and SIGNATURES[name][0] is C.c_int and len(SIGNATURES[name][1]) == n
 
 
 def test_abi_version_stays_and_the_header_carries_the_definitions():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert re.search(r"#define\s+RM_MAX_LATTICE_BLOCKS\s+512\b", HEADER) and abi.RM_MAX_LATTICE_BLOCKS == 512
     assert re.search(r"#define\s+RM_MAX_BLOCK_LIST\s+\(1 << 22\)", HEADER) and abi.RM_MAX_BLOCK_LIST == 1 << 22
     assert (abi.RM_PATH_SDF_BLOCKS_SELECT, abi.RM_PATH_SDF_GRID_BLOCKS) == (18, 19)
@@ -61,11 +48,7 @@ def test_abi_version_stays_and_the_header_carries_the_definitions():
              "rm_sdf_mesh_blocks": ("GLOBAL cell index", "(c·8 + b)·8 + a", "that cell's block owns the edge", "OPEN vertices",
                                     "stored vertex numbers stay below d_counts[0]", "before any HIP call", "88 B per list entry")}
     for name, ws in words.items():
-        m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int " + name + r"\b", HEADER, flags=re.S)
-        assert m, f"no comment in front of {name}"
-        text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-        for w in ws:
-            assert w in text, f"the comment of {name} lacks: {w}"
+        ah.assert_comment_has(name, ws)
     assert "of equal entries the first counts" in re.sub(r"\s*\n\s*\*\s?", " ", HEADER)
 
 
@@ -82,25 +65,10 @@ def test_python_signatures():
     assert sig(Renderer.bake_mesh_sparse) == sig(Renderer.bake_mesh)
 
 
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
-
-
-def vec(*v):
-    return (C.c_float * 3)(*v)
-
-
-def _scene():
-    objs, no = h.table([h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                        h.make_object(abi.RM_TORUS)])
-    return objs, no, h.make_globals()
-
-
 def _head(objs, no, g, s, origin, step, blocks):
     s = abi.default_settings() if s == "default" else s
     return (objs, no, C.byref(g) if g is not None else None, C.byref(s) if s is not None else None,
-            vec(*origin) if origin is not None else None, vec(*step) if step is not None else None, blocks[0], blocks[1], blocks[2])
+            vec3(origin), vec3(step), blocks[0], blocks[1], blocks[2])
 
 
 def select(objs, no, g, s="default", origin=(0, 0, 0), step=(0.1, 0.1, 0.1), blocks=(2, 2, 2), iso=0.0, max_blocks=8, out=FAKE, count=FAKE):
@@ -111,16 +79,10 @@ def grid(objs, no, g, s="default", origin=(0, 0, 0), step=(0.1, 0.1, 0.1), block
     return lib().rm_sdf_grid_blocks(*_head(objs, no, g, s, origin, step, blocks), bl, n, dist, ids, None)
 
 
-BAD_STEPS = ((nan, 1, 1), (1, inf, 1), (1, 1, 0.0), (-0.5, 1, 1), (1, -0.0, 1), (1, 1, -inf))
-BAD_ORIGINS = ((nan, 0, 0), (0, inf, 0), (0, 0, -inf))
-BAD_BLOCKS = ((0, 2, 2), (2, -1, 2), (2, 2, 0), (513, 1, 1), (1, 513, 1), (1, 1, 2 ** 31 - 1), (-2 ** 31, 2, 2))
-BIG_BLOCKS = ((512, 512, 512), (1, 1, 1), (512, 1, 1), (1, 1, 512))  # 4097³ points and more than INT_MAX of them: a lattice here
-
-
 def _shared_refusals(call, null_output):
     """What the two staged entry points refuse alike, in order; null_output: keyword arguments that get a call past everything but
     its outputs, and the text of that refusal."""
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     kw, text = null_output
     assert refused(call(objs, no, None), text="null g, s, origin or step")
     assert refused(call(objs, no, g, s=None), text="null g, s, origin or step")
@@ -141,21 +103,21 @@ def _shared_refusals(call, null_output):
     for b in BIG_BLOCKS:  # no INT_MAX rule: these get as far as the outputs
         assert refused(call(objs, no, g, blocks=b, **kw), text=text), b
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_SEA | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(call(objs, no, g, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
+        assert refused(call(objs, no, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
         assert refused(call(objs, no, g, s=abi.default_settings(features=feat), blocks=(0, 1, 1)), text="block dimension"), feat
-        assert refused(call(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN"), feat
-    assert refused(call(objs, no, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
+        assert refused(call(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), "TERRAIN", want=UNSUPPORTED), feat
+    assert refused(call(objs, no, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
     many, nm = h.table([h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(call(many, nm, g), CAPACITY, "RM_MAX_OBJECTS")
-    assert refused(call(many, nm, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")  # the 2-D mode comes before the table
-    assert refused(call(many, nm, g, **kw), CAPACITY, "RM_MAX_OBJECTS")              # and the table before the outputs
+    assert refused(call(many, nm, g), "RM_MAX_OBJECTS", want=CAPACITY)
+    assert refused(call(many, nm, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)  # the 2-D mode comes before the table
+    assert refused(call(many, nm, g, **kw), "RM_MAX_OBJECTS", want=CAPACITY)              # and the table before the outputs
     assert refused(call(many, abi.RM_MAX_OBJECTS, g, **kw), text=text)
     for field in ("fractalIters", "mengerLevels", "maxSteps"):
         assert refused(call(objs, no, g, s=abi.default_settings(**{field: -1})), text="loop bound"), field
     objs[1].type = abi.RM_CUSTOM
-    assert refused(call(objs, no, g), UNSUPPORTED, "object 1") and "CUSTOM" in lib().rm_last_error().decode()
+    assert refused(call(objs, no, g), "object 1", want=UNSUPPORTED) and "CUSTOM" in lib().rm_last_error().decode()
     objs[1].type = 99
-    assert refused(call(objs, no, g, **kw), UNSUPPORTED, "object 1")
+    assert refused(call(objs, no, g, **kw), "object 1", want=UNSUPPORTED)
     objs[1].type = abi.RM_CUBE
     assert refused(call(objs, no, g, **kw), text=text)
     assert refused(call(None, 0, g, **kw), text=text)  # an empty table needs no pointer
@@ -163,7 +125,7 @@ def _shared_refusals(call, null_output):
 
 def test_select_refusals_in_order():
     _shared_refusals(select, (dict(count=None), "null d_count"))
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     for iso in (nan, inf, -inf):
         assert refused(select(objs, no, g, iso=iso), text="iso must be finite"), iso
         assert refused(select(objs, no, g, iso=iso, blocks=(0, 1, 1)), text="block dimension"), iso  # the lattice comes before iso
@@ -172,19 +134,17 @@ def test_select_refusals_in_order():
     assert refused(select(objs, no, g, max_blocks=-2 ** 31, out=None), text="negative maxBlocks")
     # maxBlocks comes before the layers, the layers before the outputs
     assert refused(select(objs, no, g, max_blocks=-1, s=abi.default_settings(features=abi.RM_FEAT_SEA)), text="negative maxBlocks")
-    assert refused(select(objs, no, g, out=None, s=abi.default_settings(features=abi.RM_FEAT_SEA)), UNSUPPORTED, "TERRAIN / CLOUD / SEA")
+    assert refused(select(objs, no, g, out=None, s=abi.default_settings(features=abi.RM_FEAT_SEA)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED)
     assert refused(select(objs, no, g, out=None), text="null d_blocks with maxBlocks above 0")
     assert refused(select(objs, no, g, count=None), text="null d_count")
     # the counting call takes a null list: it gets as far as the device-memory check of a count that is host memory
-    host = np.zeros(64, dtype=np.int32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(select(objs, no, g, max_blocks=0, out=None, count=hp), text="d_count is not device-accessible")
-    assert refused(select(objs, no, g, out=hp, count=hp), text="d_blocks is not device-accessible")
+    assert refused(select(objs, no, g, max_blocks=0, out=None, count=HP), text="d_count is not device-accessible")
+    assert refused(select(objs, no, g, out=HP, count=HP), text="d_blocks is not device-accessible")
 
 
 def test_grid_blocks_refusals_in_order_and_the_empty_list():
     _shared_refusals(grid, (dict(dist=None), "null d_blocks or d_dist"))
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     for n in (-1, -2 ** 31, (1 << 22) + 1, 2 ** 31 - 1):
         assert refused(grid(objs, no, g, n=n), text="numBlocks must be 0 … RM_MAX_BLOCK_LIST"), n
         assert refused(grid(objs, no, g, n=n, blocks=(0, 1, 1)), text="block dimension"), n  # the lattice comes before numBlocks
@@ -196,16 +156,14 @@ def test_grid_blocks_refusals_in_order_and_the_empty_list():
     assert grid(objs, no, g, n=0, bl=None, dist=None, ids=None) == abi.RM_OK
     assert grid(objs, no, g, n=0) == abi.RM_OK
     assert refused(grid(objs, no, g, n=0, blocks=(0, 1, 1)), text="block dimension")
-    assert refused(grid(objs, no, h.make_globals(two_d=1), n=0), UNSUPPORTED, "isTwoD")
-    host = np.zeros(3 * 729, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(grid(objs, no, g, bl=hp, ids=None), text="d_blocks is not device-accessible")
+    assert refused(grid(objs, no, h.make_globals(two_d=1), n=0), "isTwoD", want=UNSUPPORTED)
+    assert refused(grid(objs, no, g, bl=HP, ids=None), text="d_blocks is not device-accessible")
 
 
 def mesh(blocks=(2, 2, 2), origin=(0, 0, 0), step=(0.1, 0.1, 0.1), iso=0.0, n=3, max_v=10, max_q=10, dist=FAKE, ids=FAKE, bl=FAKE, verts=FAKE,
          vobj=FAKE, quads=FAKE, counts=FAKE):
-    return lib().rm_sdf_mesh_blocks(dist, ids, bl, n, blocks[0], blocks[1], blocks[2], vec(*origin) if origin is not None else None,
-                                    vec(*step) if step is not None else None, iso, max_v, max_q, verts, vobj, quads, counts, None)
+    return lib().rm_sdf_mesh_blocks(dist, ids, bl, n, blocks[0], blocks[1], blocks[2], vec3(origin), vec3(step), iso, max_v, max_q, verts,
+                                    vobj, quads, counts, None)
 
 
 def test_mesh_blocks_refusals_in_order():
@@ -240,9 +198,7 @@ def test_mesh_blocks_refusals_in_order():
         assert refused(mesh(blocks=b, n=1 << 22, counts=None), text="null d_dist, d_blocks or d_counts"), b
     # the counting call takes null outputs, d_vertexObject and d_objectId may be null, an empty list needs neither d_dist nor
     # d_blocks: each of these gets as far as the device-memory check of an array that is host memory
-    host = np.zeros(3 * 729, dtype=np.float32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(mesh(max_v=0, max_q=0, verts=None, vobj=None, quads=None, ids=None, dist=hp), text="d_dist is not device-accessible")
-    assert refused(mesh(max_q=0, quads=None, dist=hp), text="d_dist is not device-accessible")
-    assert refused(mesh(n=0, dist=None, bl=None, ids=None, max_v=0, max_q=0, verts=None, vobj=None, quads=None, counts=hp),
+    assert refused(mesh(max_v=0, max_q=0, verts=None, vobj=None, quads=None, ids=None, dist=HP), text="d_dist is not device-accessible")
+    assert refused(mesh(max_q=0, quads=None, dist=HP), text="d_dist is not device-accessible")
+    assert refused(mesh(n=0, dist=None, bl=None, ids=None, max_v=0, max_q=0, verts=None, vobj=None, quads=None, counts=HP),
                    text="d_counts is not device-accessible")

@@ -3,58 +3,47 @@ header's comment carries the definition, the Python layer has its methods, and e
 HIP call — with pointers that would fault if read — in rm_sdf_blocks_select's order, the two constants between iso and maxBlocks."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
 import helpers as h
+import scene_builders as SB
+from abi_helpers import BAD_BLOCKS, BAD_ORIGINS, BAD_STEPS, BIG_BLOCKS, CAPACITY, FAKE, HEADER, HP, inf, nan, refused, vec3
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INVALID, CAPACITY, UNSUPPORTED = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED
-FAKE = C.c_void_p(0x1000)  # never dereferenced: every call that gets it fails its checks first
-inf, nan = float("inf"), float("nan")
+UNSUPPORTED = abi.RM_ERR_UNSUPPORTED
 NAME = "rm_sdf_blocks_select_pruned"
 
 
 def test_header_declares_and_library_exports_the_symbol():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + NAME + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {NAME}"
-    params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-    assert params == ["const RmObject *objs", "int numObjects", "const RmGlobals *g", "const RmSettings *s", "const float origin[3]",
-                      "const float step[3]", "int mx", "int my", "int mz", "float iso", "float lipschitzOut", "float lipschitzIn",
-                      "int maxBlocks", "int32_t *d_blocks", "uint32_t *d_count", "void *stream"]
+    body = ah.HEADER_CODE
+    assert ah.params(NAME) == [
+        "const RmObject *objs", "int numObjects", "const RmGlobals *g", "const RmSettings *s", "const float origin[3]",
+        "const float step[3]", "int mx", "int my", "int mz", "float iso", "float lipschitzOut", "float lipschitzIn",
+        "int maxBlocks", "int32_t *d_blocks", "uint32_t *d_count", "void *stream"]
     assert body.index("int rm_sdf_blocks_select(") < body.index("int " + NAME + "(") < body.index("int rm_sdf_grid_blocks(")
     assert "uint32_t *d_count /* 2 words */" in HEADER
-    lib()
-    assert hasattr(C.CDLL(LIB_PATH), NAME), f"the library does not export {NAME}"
+    ah.assert_exported([NAME])
     assert NAME in SIGNATURES and SIGNATURES[NAME][0] is C.c_int and len(SIGNATURES[NAME][1]) == 16
     floats = [n for n, ty in enumerate(SIGNATURES[NAME][1]) if ty is C.c_float]
     assert floats == [9, 10, 11]
 
 
 def test_abi_version_stays_and_the_header_carries_the_definition():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert abi.RM_PATH_SDF_BLOCKS_SELECT_PRUNED == 20
     assert re.search(r"19 = a launch of rm_sdf_grid_blocks,\s*\*?\s*20 = a launch of rm_sdf_blocks_select_pruned", HEADER)
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int " + NAME + r"\b", HEADER, flags=re.S)
-    assert m, f"no comment in front of {NAME}"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for w in ("lattice point (8i, 8j, 8k)", "h = 4 · sqrt((sx·sx + sy·sy) + sz·sz)", "correctly rounded", "computed on the host",
-              "bOut = lipschitzOut · h", "bIn = lipschitzIn · h", "a NaN bound (0 · inf) discards nothing", "d = c − iso", "farOut = d > bOut",
-              "farIn = d < −bIn", "a NaN c is neither", "DISCARDED iff farOut holds at all eight", "CANDIDATE", "(bk·my + bj)·mx + bi",
-              "FULL number", "the counting call", "d_count[1] receives the number of candidates, saturated at 2^32 − 1",
-              "sub-sequence of rm_sdf_blocks_select's list", "With both constants +INFINITY the two lists and d_count[0] are equal in every word",
-              "v(p) ≥ v(q) − lipschitzOut·|p − q|", "A true distance function honours this with 1", "lipschitzIn = +INFINITY",
-              "before any HIP call", "NaN or below 0", "+INFINITY and 0 are valid", "rm_debug_last_path() = 20", "counts as one launch",
-              "4 B per corner + 8 B per block", "at most 12 B per block", "rm_set_workspace_limit", "rm_release_workspaces",
-              "no host synchronisation", "does not depend on its wave", "length they read from device memory", "RM_ABI_VERSION"):
-        assert w in text, f"the comment of {NAME} lacks: {w}"
+    ah.assert_comment_has(NAME, (
+        "lattice point (8i, 8j, 8k)", "h = 4 · sqrt((sx·sx + sy·sy) + sz·sz)", "correctly rounded", "computed on the host",
+        "bOut = lipschitzOut · h", "bIn = lipschitzIn · h", "a NaN bound (0 · inf) discards nothing", "d = c − iso", "farOut = d > bOut",
+        "farIn = d < −bIn", "a NaN c is neither", "DISCARDED iff farOut holds at all eight", "CANDIDATE", "(bk·my + bj)·mx + bi",
+        "FULL number", "the counting call", "d_count[1] receives the number of candidates, saturated at 2^32 − 1",
+        "sub-sequence of rm_sdf_blocks_select's list", "With both constants +INFINITY the two lists and d_count[0] are equal in every word",
+        "v(p) ≥ v(q) − lipschitzOut·|p − q|", "A true distance function honours this with 1", "lipschitzIn = +INFINITY",
+        "before any HIP call", "NaN or below 0", "+INFINITY and 0 are valid", "rm_debug_last_path() = 20", "counts as one launch",
+        "4 B per corner + 8 B per block", "at most 12 B per block", "rm_set_workspace_limit", "rm_release_workspaces",
+        "no host synchronisation", "does not depend on its wave", "length they read from device memory", "RM_ABI_VERSION"))
 
 
 def test_python_signatures():
@@ -76,38 +65,18 @@ def test_python_signatures():
     assert sig(Renderer.scene_field_sparse) == ["self", "tables", "settings", "resolution", "iso", "bounds"]
 
 
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
-
-
-def vec(*v):
-    return (C.c_float * 3)(*v)
-
-
-def _scene():
-    objs, no = h.table([h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                        h.make_object(abi.RM_TORUS)])
-    return objs, no, h.make_globals()
-
-
 def pruned(objs, no, g, s="default", origin=(0, 0, 0), step=(0.1, 0.1, 0.1), blocks=(2, 2, 2), iso=0.0, l_out=1.0, l_in=inf, max_blocks=8,
            out=FAKE, count=FAKE):
     s = abi.default_settings() if s == "default" else s
     return lib().rm_sdf_blocks_select_pruned(objs, no, C.byref(g) if g is not None else None, C.byref(s) if s is not None else None,
-                                             vec(*origin) if origin is not None else None, vec(*step) if step is not None else None,
-                                             blocks[0], blocks[1], blocks[2], iso, l_out, l_in, max_blocks, out, count, None)
+                                             vec3(origin), vec3(step), blocks[0], blocks[1], blocks[2], iso, l_out, l_in, max_blocks, out, count, None)
 
 
-BAD_STEPS = ((nan, 1, 1), (1, inf, 1), (1, 1, 0.0), (-0.5, 1, 1), (1, -0.0, 1), (1, 1, -inf))
-BAD_ORIGINS = ((nan, 0, 0), (0, inf, 0), (0, 0, -inf))
-BAD_BLOCKS = ((0, 2, 2), (2, -1, 2), (2, 2, 0), (513, 1, 1), (1, 513, 1), (1, 1, 2 ** 31 - 1), (-2 ** 31, 2, 2))
-BIG_BLOCKS = ((512, 512, 512), (1, 1, 1), (512, 1, 1), (1, 1, 512))
 BAD_CONSTANTS = (nan, -0.5, -inf)
 
 
 def test_refusals_in_rm_sdf_blocks_selects_order():
-    objs, no, g = _scene()
+    objs, no, g = SB.three_primitives_table()
     assert refused(pruned(objs, no, None), text="null g, s, origin or step")
     assert refused(pruned(objs, no, g, s=None), text="null g, s, origin or step")
     assert refused(pruned(objs, no, g, origin=None), text="null g, s, origin or step")
@@ -145,25 +114,23 @@ def test_refusals_in_rm_sdf_blocks_selects_order():
     # maxBlocks comes before the layers, the layers before the 2-D mode, that before the table, the table before the outputs
     assert refused(pruned(objs, no, g, max_blocks=-1, s=abi.default_settings(features=abi.RM_FEAT_SEA)), text="negative maxBlocks")
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_SEA | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(pruned(objs, no, g, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
-        assert refused(pruned(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN"), feat
-        assert refused(pruned(objs, no, g, out=None, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
-    assert refused(pruned(objs, no, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
+        assert refused(pruned(objs, no, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
+        assert refused(pruned(objs, no, h.make_globals(two_d=1), s=abi.default_settings(features=feat)), "TERRAIN", want=UNSUPPORTED), feat
+        assert refused(pruned(objs, no, g, out=None, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
+    assert refused(pruned(objs, no, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
     many, nm = h.table([h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(pruned(many, nm, g), CAPACITY, "RM_MAX_OBJECTS")
-    assert refused(pruned(many, nm, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
-    assert refused(pruned(many, nm, g, count=None), CAPACITY, "RM_MAX_OBJECTS")
+    assert refused(pruned(many, nm, g), "RM_MAX_OBJECTS", want=CAPACITY)
+    assert refused(pruned(many, nm, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
+    assert refused(pruned(many, nm, g, count=None), "RM_MAX_OBJECTS", want=CAPACITY)
     assert refused(pruned(many, abi.RM_MAX_OBJECTS, g, count=None), text="null d_count")
     for field in ("fractalIters", "mengerLevels", "maxSteps"):
         assert refused(pruned(objs, no, g, s=abi.default_settings(**{field: -1})), text="loop bound"), field
     objs[1].type = abi.RM_CUSTOM
-    assert refused(pruned(objs, no, g), UNSUPPORTED, "object 1") and "CUSTOM" in lib().rm_last_error().decode()
+    assert refused(pruned(objs, no, g), "object 1", want=UNSUPPORTED) and "CUSTOM" in lib().rm_last_error().decode()
     objs[1].type = abi.RM_CUBE
     assert refused(pruned(None, 0, g, count=None), text="null d_count")  # an empty table needs no pointer
     assert refused(pruned(objs, no, g, out=None), text="null d_blocks with maxBlocks above 0")
     assert refused(pruned(objs, no, g, count=None), text="null d_count")
     # the counting call takes a null list: it gets as far as the device-memory check of a count that is host memory
-    host = np.zeros(64, dtype=np.int32)
-    hp = C.c_void_p(host.ctypes.data)
-    assert refused(pruned(objs, no, g, max_blocks=0, out=None, count=hp), text="d_count is not device-accessible")
-    assert refused(pruned(objs, no, g, out=hp, count=hp), text="d_blocks is not device-accessible")
+    assert refused(pruned(objs, no, g, max_blocks=0, out=None, count=HP), text="d_count is not device-accessible")
+    assert refused(pruned(objs, no, g, out=HP, count=HP), text="d_blocks is not device-accessible")

@@ -3,17 +3,14 @@ evaluator instantiations that production kernels compile, refusing everything el
 oracle's Mandelbulb against the binary64 arbiter, where the value is well conditioned and where binary32 overflows."""
 import ctypes as C
 import itertools
-import os
-import re
 
 import numpy as np
 
+import abi_helpers as ah
 import helpers as h
+from abi_helpers import FAKE
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
+from raymarcher_amd._lib import SIGNATURES
 
 # (bulbClass, count, trap, skip, track, one) of every production instantiation, from the call sites in rm_device.hip.h and
 # rm_wavefront.hip.h: march (TRAP = !SHADOW, SKIP = TRACK = CULL && !BULB && COUNT != 1, sdSceneOne on its fast path), getNormal
@@ -49,12 +46,10 @@ def call(objs, no, g, cls, count, trap, skip, track, one, pts=None, out=None, n=
 
 
 def test_header_declares_and_library_exports_the_variant_probe():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    assert re.search(r"\bint\s+rm_probe_sdscene_variant\s*\(", body)
-    assert re.search(r"\bint\s+rm_probe_sdscene\s*\(", body)  # the original probe stays
+    assert ah.params("rm_probe_sdscene_variant")
+    assert ah.params("rm_probe_sdscene")  # the original probe stays
     assert "rm_probe_sdscene_variant" in SIGNATURES
-    lib()
-    assert hasattr(C.CDLL(LIB_PATH), "rm_probe_sdscene_variant")
+    ah.assert_exported(["rm_probe_sdscene_variant"])
 
 
 def test_exactly_the_production_instantiations_are_accepted():
@@ -131,9 +126,8 @@ def test_scene_and_pointer_errors():
         == abi.RM_ERR_INVALID_ARGUMENT
     assert lib().rm_probe_sdscene_variant(objs, abi.RM_MAX_OBJECTS + 1, C.byref(g), C.byref(s), 0, 0, 1, 0, 0, -1, None, None,
                                           None, 1, None) == abi.RM_ERR_CAPACITY
-    fake = C.c_void_p(0x1000)  # never dereferenced: the calls below fail their checks first
-    assert call(objs, no, g, 0, 0, 1, 0, 0, -1, pts=fake, out=None) == abi.RM_ERR_INVALID_ARGUMENT
-    assert call(objs, no, g, 0, 0, 1, 0, 0, -1, pts=fake, out=fake, n=-1) == abi.RM_ERR_INVALID_ARGUMENT
+    assert call(objs, no, g, 0, 0, 1, 0, 0, -1, pts=FAKE, out=None) == abi.RM_ERR_INVALID_ARGUMENT
+    assert call(objs, no, g, 0, 0, 1, 0, 0, -1, pts=FAKE, out=FAKE, n=-1) == abi.RM_ERR_INVALID_ARGUMENT
     assert L.rm_last_error() == b"bad probe arguments"
 
 

@@ -3,28 +3,22 @@ carries the definition, and every argument error returns its status, in the docu
 pointers that would fault if read."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import numpy as np
-
+import abi_helpers as ah
 import helpers as h
 import scene_builders as SB
+from abi_helpers import CAPACITY, FAKE, HEADER, HP, INT_MAX, fake, refused
 from raymarcher_amd import abi, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
+from raymarcher_amd._lib import SIGNATURES
+from scene_builders import three_primitives_lit as _scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
-INVALID, CAPACITY, UNSUPPORTED = abi.RM_ERR_INVALID_ARGUMENT, abi.RM_ERR_CAPACITY, abi.RM_ERR_UNSUPPORTED
+UNSUPPORTED = abi.RM_ERR_UNSUPPORTED
 
 
 # ---------------------------------------------------------------- the symbol and the written definition
 def test_header_declares_and_library_exports_the_symbol():
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+rm_shade_rays\s*\(([^)]*)\)", body)
-    assert m, "include/raymarcher_amd.h does not declare rm_shade_rays"
-    assert [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")] == [
+    assert ah.params("rm_shade_rays") == [
         "const RmRay *d_rays", "int numRays", "float far", "const RmObject *objs", "int numObjects", "const RmLight *lights",
         "int numLights", "const RmGlobals *g", "const RmSettings *s", "const RmResources *res", "float *d_rgba", "float *d_bright",
         "void *stream"]
@@ -32,21 +26,17 @@ def test_header_declares_and_library_exports_the_symbol():
     assert SIGNATURES["rm_shade_rays"] == (C.c_int, [C.c_void_p, C.c_int, C.c_float, Ptr(abi.RmObject), C.c_int, Ptr(abi.RmLight), C.c_int,
                                                      Ptr(abi.RmGlobals), Ptr(abi.RmSettings), Ptr(abi.RmResources), C.c_void_p,
                                                      C.c_void_p, C.c_void_p])
-    lib()
-    assert hasattr(C.CDLL(LIB_PATH), "rm_shade_rays")
+    ah.assert_exported(["rm_shade_rays"])
     assert abi.RM_PATH_SHADE_RAYS == 13 and abi.RM_PATH_TRACE_RAYS == 12
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5 and re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
 
 
 def test_header_comment_carries_the_definition():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int rm_shade_rays\b", HEADER, flags=re.S)
-    assert m, "no comment in front of rm_shade_rays"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("NOT normalised", "assumes a unit rd", "frag:2405-2419", "frag:2443", "frag:2491-2524", "frag:2526-2570", "frag:2572",
-                  "frag:1938-1946", "render(ro, rd, OUTSIDE, far, bg)", "ONE value per call", "RmRay.tMax is NOT read",
-                  "(0, 0, 0, 0) in both outputs", "alpha 0 marks it", "evaluates nothing", "cannot refuse them",
-                  "does not depend on which other rays", "before any HIP call", "rm_debug_last_path() = 13", "symbol lookup"):
-        assert words in text, f"the comment of rm_shade_rays lacks: {words}"
+    ah.assert_comment_has("rm_shade_rays", (
+        "NOT normalised", "assumes a unit rd", "frag:2405-2419", "frag:2443", "frag:2491-2524", "frag:2526-2570", "frag:2572",
+        "frag:1938-1946", "render(ro, rd, OUTSIDE, far, bg)", "ONE value per call", "RmRay.tMax is NOT read",
+        "(0, 0, 0, 0) in both outputs", "alpha 0 marks it", "evaluates nothing", "cannot refuse them",
+        "does not depend on which other rays", "before any HIP call", "rm_debug_last_path() = 13", "symbol lookup"))
     assert re.search(r"13 = a launch of rm_shade_rays", HEADER), "rm_debug_last_path's comment does not document 13"
 
 
@@ -65,26 +55,13 @@ def test_python_signatures():
 
 
 # ---------------------------------------------------------------- refusals, all without a device
-FAKE = C.c_void_p(0x1000)  # 16-byte aligned and never dereferenced: every call that gets it fails its checks first
 DEFAULT = object()
-
-
-def _scene():
-    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
-    lights = (abi.RmLight * 2)(h.make_light(abi.RM_LIGHT_DIRECTIONAL, (1, 1, 1), (0, -1, 0)), h.make_light(abi.RM_LIGHT_POINT, pos=(1, 2, 3)))
-    return objs, 3, lights, 2, h.make_globals()
 
 
 def call(objs, no, lights, nl, g, s=DEFAULT, n=100, far=100.0, res=None, rays=FAKE, rgba=FAKE, bright=None):
     s = abi.default_settings() if s is DEFAULT else s
     return lib().rm_shade_rays(rays, n, far, objs, no, lights, nl, C.byref(g) if g is not None else None,
                                C.byref(s) if s is not None else None, C.byref(res) if res is not None else None, rgba, bright, None)
-
-
-def refused(status, want=INVALID, text=None):
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
 
 
 ARRAYS = "null d_rays or d_rgba"  # the first check behind the scene's: a call that gets this far passed everything before it
@@ -122,33 +99,33 @@ def test_far():
 def test_layers_capacity_loop_bounds_and_types_in_order():
     objs, no, lights, nl, g = _scene()
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_TERRAIN | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat)), UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
+        assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=UNSUPPORTED), feat
     for feat in (0, abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_DARK_BACKGROUND, abi.RM_FEAT_REFERENCE_DEFAULT):
         assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(features=feat), rgba=None), text=ARRAYS), feat
-    assert refused(call(objs, no, lights, nl, h.make_globals(two_d=1)), UNSUPPORTED, "isTwoD")
+    assert refused(call(objs, no, lights, nl, h.make_globals(two_d=1)), "isTwoD", want=UNSUPPORTED)
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g), CAPACITY, "RM_MAX_OBJECTS")
+    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g), "RM_MAX_OBJECTS", want=CAPACITY)
     assert refused(call(many, abi.RM_MAX_OBJECTS, lights, nl, g, rays=None), text=ARRAYS)
     lots = (abi.RmLight * (abi.RM_MAX_LIGHTS + 1))(*[h.make_light(abi.RM_LIGHT_POINT) for _ in range(abi.RM_MAX_LIGHTS + 1)])
-    assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g), CAPACITY, "RM_MAX_LIGHTS")
+    assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS + 1, g), "RM_MAX_LIGHTS", want=CAPACITY)
     assert refused(call(objs, no, lots, abi.RM_MAX_LIGHTS, g, rays=None), text=ARRAYS)
     for field in ("maxSteps", "fractalIters", "mengerLevels", "numReflection"):
         assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(**{field: -1})), text="loop bound"), field
     assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(maxSteps=0, numReflection=0), rays=None), text=ARRAYS)
     # the layers come before the capacity, the capacity before the loop bounds, the loop bounds before the types
-    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(features=abi.RM_FEAT_CLOUD)), UNSUPPORTED, "TERRAIN")
-    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(maxSteps=-1)), CAPACITY)
+    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(features=abi.RM_FEAT_CLOUD)), "TERRAIN", want=UNSUPPORTED)
+    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, lights, nl, g, s=abi.default_settings(maxSteps=-1)), want=CAPACITY)
     objs[1].type = abi.RM_CUSTOM
     assert refused(call(objs, no, lights, nl, g, s=abi.default_settings(maxSteps=-1)), text="loop bound")
-    assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "object 1")
+    assert refused(call(objs, no, lights, nl, g), "object 1", want=UNSUPPORTED)
     assert "CUSTOM" in lib().rm_last_error().decode()
     for ty in (99, -1):
         objs[1].type = abi.RM_CUBE
         objs[2].type = ty
-        assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "object 2"), ty
+        assert refused(call(objs, no, lights, nl, g), "object 2", want=UNSUPPORTED), ty
     objs[2].type = abi.RM_TORUS
     lights[1].type = 7
-    assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "light 1")
+    assert refused(call(objs, no, lights, nl, g), "light 1", want=UNSUPPORTED)
 
 
 def test_samplers_are_asked_for_as_by_rm_render_res():
@@ -157,38 +134,38 @@ def test_samplers_are_asked_for_as_by_rm_render_res():
     objs, no, lights, nl, g = _scene()
     tex = abi.RmTexture(0x2000, 4, 4)
     night = abi.default_settings(features=abi.RM_FEAT_NIGHTSKY_BACKGROUND)
-    assert refused(call(objs, no, lights, nl, g, s=night), UNSUPPORTED, "noise")
-    assert refused(call(objs, no, lights, nl, g, s=night, res=abi.RmResources()), UNSUPPORTED, "noise")
+    assert refused(call(objs, no, lights, nl, g, s=night), "noise", want=UNSUPPORTED)
+    assert refused(call(objs, no, lights, nl, g, s=night, res=abi.RmResources()), "noise", want=UNSUPPORTED)
     res = abi.RmResources()
     res.noise = tex
     assert refused(call(objs, no, lights, nl, g, s=night, res=res, rays=None), text=ARRAYS)
     box = abi.default_settings(enableSkyBox=1)
-    assert refused(call(objs, no, lights, nl, g, s=box), UNSUPPORTED, "enableSkyBox")
+    assert refused(call(objs, no, lights, nl, g, s=box), "enableSkyBox", want=UNSUPPORTED)
     res = abi.RmResources()
     for f in range(5):
         res.skybox[f] = tex
-    assert refused(call(objs, no, lights, nl, g, s=box, res=res), UNSUPPORTED, "enableSkyBox")
+    assert refused(call(objs, no, lights, nl, g, s=box, res=res), "enableSkyBox", want=UNSUPPORTED)
     res.skybox[5] = tex
     assert refused(call(objs, no, lights, nl, g, s=box, res=res, rays=None), text=ARRAYS)
     objs[0].texLoc = 0
-    assert refused(call(objs, no, lights, nl, g), UNSUPPORTED, "texLoc")
+    assert refused(call(objs, no, lights, nl, g), "texLoc", want=UNSUPPORTED)
     res = abi.RmResources()
     arr = (abi.RmTexture * 1)(tex)
     res.textures, res.numTextures = arr, 1
     assert refused(call(objs, no, lights, nl, g, res=res, rays=None), text=ARRAYS)
     objs[0].texLoc = 1
-    assert refused(call(objs, no, lights, nl, g, res=res), UNSUPPORTED, "texLoc")
+    assert refused(call(objs, no, lights, nl, g, res=res), "texLoc", want=UNSUPPORTED)
     objs[0].texLoc = -1
     objs[2].texLoc = 0  # a torus takes no texture
-    assert refused(call(objs, no, lights, nl, g, res=res), UNSUPPORTED, "textures are only defined")
+    assert refused(call(objs, no, lights, nl, g, res=res), "textures are only defined", want=UNSUPPORTED)
     objs[2].texLoc = -1
     res.numTextures = abi.RM_MAX_TEXTURES + 1
-    assert refused(call(objs, no, lights, nl, g, res=res), CAPACITY, "RM_MAX_TEXTURES")
+    assert refused(call(objs, no, lights, nl, g, res=res), "RM_MAX_TEXTURES", want=CAPACITY)
     scene = SB.area_light_scene(8, 8)
-    assert refused(call(*scene[1:6]), UNSUPPORTED, "LTC")
+    assert refused(call(*scene[1:6]), "LTC", want=UNSUPPORTED)
     res = abi.RmResources()
     res.ltc1 = 0x3000
-    assert refused(call(*scene[1:6], res=res), UNSUPPORTED, "LTC")
+    assert refused(call(*scene[1:6], res=res), "LTC", want=UNSUPPORTED)
     res.ltc2 = 0x4000
     assert refused(call(*scene[1:6], res=res, rgba=None), text=ARRAYS)
 
@@ -198,15 +175,13 @@ def test_the_three_arrays():
     assert refused(call(objs, no, lights, nl, g, rays=None), text=ARRAYS)
     assert refused(call(objs, no, lights, nl, g, rgba=None), text=ARRAYS)
     for off in (4, 8, 12, 1):
-        bad = C.c_void_p(0x1000 + off)
+        bad = fake(0x1000 + off)
         assert refused(call(objs, no, lights, nl, g, rays=bad), text="16-byte aligned"), off
         assert refused(call(objs, no, lights, nl, g, rgba=bad), text="16-byte aligned"), off
         assert refused(call(objs, no, lights, nl, g, bright=bad), text="16-byte aligned"), off
     # the arrays come behind everything about the scene
     objs[0].type = abi.RM_CUSTOM
-    assert refused(call(objs, no, lights, nl, g, rays=None), UNSUPPORTED, "object 0")
+    assert refused(call(objs, no, lights, nl, g, rays=None), "object 0", want=UNSUPPORTED)
     objs[0].type = abi.RM_SPHERE
     # host memory is not device memory: the only check that asks the HIP runtime, and the last
-    host = np.zeros(100 * 8 + 8, dtype=np.float32)
-    hp = C.c_void_p((host.ctypes.data + 15) & ~15)
-    assert refused(call(objs, no, lights, nl, g, rays=hp, rgba=hp), text="d_rays")
+    assert refused(call(objs, no, lights, nl, g, rays=HP, rgba=HP), text="d_rays")

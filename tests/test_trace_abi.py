@@ -4,47 +4,36 @@ fault if read — and rm_camera_rays, a host function, equals the specification'
 (tests/trace_spec/rm_trace_spec.c: the oracle's own rayPlanes, interpolateVarying and normalize3)."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_helpers as ah
 import helpers as h
 import scene_builders as SB
 import trace_helpers as T
+from abi_helpers import FAKE, HEADER, HP, INT_MAX, fake, refused
 from raymarcher_amd import abi, camera_rays, lib
-from raymarcher_amd._lib import LIB_PATH, SIGNATURES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "raymarcher_amd.h")).read()
-INT_MAX = 2 ** 31 - 1
+from raymarcher_amd._lib import SIGNATURES
+from scene_builders import three_primitives as _scene
 
 
 # ---------------------------------------------------------------- symbols, structs, the written definition
-def _params(name):
-    body = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", body)
-    assert m, f"include/raymarcher_amd.h does not declare {name}"
-    return [re.sub(r"\s+", " ", p.strip()) for p in m.group(1).split(",")]
-
-
 def test_header_declares_and_library_exports_both_symbols():
-    assert _params("rm_trace_rays") == ["const RmRay *d_rays", "int numRays", "const RmObject *objs", "int numObjects",
-                                        "const RmGlobals *g", "const RmSettings *s", "unsigned mode", "RmRayHit *d_hits", "void *stream"]
-    assert _params("rm_camera_rays") == ["const RmCamera *cam", "int W", "int H", "const int32_t *xy", "int n", "RmRay *out"]
+    assert ah.params("rm_trace_rays") == [
+        "const RmRay *d_rays", "int numRays", "const RmObject *objs", "int numObjects",
+        "const RmGlobals *g", "const RmSettings *s", "unsigned mode", "RmRayHit *d_hits", "void *stream"]
+    assert ah.params("rm_camera_rays") == ["const RmCamera *cam", "int W", "int H", "const int32_t *xy", "int n", "RmRay *out"]
     P = C.POINTER
     assert SIGNATURES["rm_trace_rays"] == (C.c_int, [C.c_void_p, C.c_int, P(abi.RmObject), C.c_int, P(abi.RmGlobals), P(abi.RmSettings),
                                                      C.c_uint, C.c_void_p, C.c_void_p])
     assert SIGNATURES["rm_camera_rays"] == (C.c_int, [P(abi.RmCamera), C.c_int, C.c_int, P(C.c_int32), C.c_int, C.c_void_p])
-    lib()
-    L = C.CDLL(LIB_PATH)
-    assert hasattr(L, "rm_trace_rays") and hasattr(L, "rm_camera_rays")
+    ah.assert_exported(["rm_trace_rays", "rm_camera_rays"])
 
 
 def test_abi_version_stays_and_the_structs_are_32_bytes():
-    assert abi.RM_ABI_VERSION == 5 and lib().rm_abi_version() == 5
-    assert re.search(r"#define\s+RM_ABI_VERSION\s+5\b", HEADER)
+    ah.assert_abi_version()
     assert lib().rm_abi_sizeof(11) == C.sizeof(abi.RmRay) == 32
     assert lib().rm_abi_sizeof(12) == C.sizeof(abi.RmRayHit) == 32
     assert lib().rm_abi_sizeof(99) == -1 and lib().rm_abi_sizeof(13) == -1
@@ -57,15 +46,12 @@ def test_abi_version_stays_and_the_structs_are_32_bytes():
 
 
 def test_header_comment_carries_the_definition():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*typedef struct RmRay\b", HEADER, flags=re.S)
-    assert m, "no comment in front of RmRay"
-    text = re.sub(r"\s*\n\s*\*\s?", " ", m.group(1))
-    for words in ("NOT normalised", "units of |dir|", "raymarch(origin, dir, tMax, OUTSIDE)", "frag:1453-1484", "frag:2318-2337",
-                  "frag:1436-1444", "frag:1679-1691", "frag:1703-1725", "softshadow(origin, dir, 0, tMax, 8)",
-                  "t = tMax as given", "not the march's ray depth", "penumbra factor", "objectId == −1 ? t : 0", "RM_RAY_INVALID, t = 0",
-                  "evaluates nothing", "cannot refuse them", "does not depend on which other rays", "before any HIP call",
-                  "rm_debug_last_path() = 12", "symbol lookup"):
-        assert words in text, f"the comment of rm_trace_rays lacks: {words}"
+    ah.assert_comment_has("RmRay", (
+        "NOT normalised", "units of |dir|", "raymarch(origin, dir, tMax, OUTSIDE)", "frag:1453-1484", "frag:2318-2337",
+        "frag:1436-1444", "frag:1679-1691", "frag:1703-1725", "softshadow(origin, dir, 0, tMax, 8)",
+        "t = tMax as given", "not the march's ray depth", "penumbra factor", "objectId == −1 ? t : 0", "RM_RAY_INVALID, t = 0",
+        "evaluates nothing", "cannot refuse them", "does not depend on which other rays", "before any HIP call",
+        "rm_debug_last_path() = 12", "symbol lookup"))
     assert re.search(r"12 = a launch of rm_trace_rays", HEADER), "rm_debug_last_path's comment does not document 12"
     assert re.search(r"11 RmRay, 12 RmRayHit", HEADER), "rm_abi_sizeof's comment does not list the two structs"
 
@@ -80,25 +66,12 @@ def test_python_signatures():
 
 
 # ---------------------------------------------------------------- refusals, all without a device
-FAKE = C.c_void_p(0x1000)  # 16-byte aligned and never dereferenced: every call that gets it fails its checks first
-
-
-def _scene():
-    objs = (abi.RmObject * 3)(h.make_object(abi.RM_SPHERE, model=h.translate(-1, 0, 0)), h.make_object(abi.RM_CUBE, model=h.translate(1, 0, 0)),
-                              h.make_object(abi.RM_TORUS, model=h.translate(0, 1, 0)))
-    return objs, 3, h.make_globals()
 
 
 def call(objs, no, g, s="default", n=100, mode=0, rays=FAKE, hits=FAKE):
     s = abi.default_settings() if s == "default" else s
     return lib().rm_trace_rays(rays, n, objs, no, C.byref(g) if g is not None else None, C.byref(s) if s is not None else None, mode,
                                hits, None)
-
-
-def refused(status, want=None, text=None):
-    want = abi.RM_ERR_INVALID_ARGUMENT if want is None else want
-    msg = lib().rm_last_error().decode()
-    return status == want and len(msg) > 0 and (text is None or text in msg)
 
 
 def test_counts_and_scene_pointers():
@@ -132,23 +105,23 @@ def test_mode_bits():
 def test_capacity_unsupported_and_loop_bounds():
     objs, no, g = _scene()
     many = (abi.RmObject * (abi.RM_MAX_OBJECTS + 1))(*[h.make_object(abi.RM_SPHERE) for _ in range(abi.RM_MAX_OBJECTS + 1)])
-    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, g), abi.RM_ERR_CAPACITY, "RM_MAX_OBJECTS")
+    assert refused(call(many, abi.RM_MAX_OBJECTS + 1, g), "RM_MAX_OBJECTS", want=abi.RM_ERR_CAPACITY)
     assert refused(call(many, abi.RM_MAX_OBJECTS, g, rays=None), text="null d_rays or d_hits")
     for feat in (abi.RM_FEAT_TERRAIN, abi.RM_FEAT_CLOUD, abi.RM_FEAT_SEA, abi.RM_FEAT_TERRAIN | abi.RM_FEAT_PERLIN_BUMP):
-        assert refused(call(objs, no, g, s=abi.default_settings(features=feat)), abi.RM_ERR_UNSUPPORTED, "TERRAIN / CLOUD / SEA"), feat
+        assert refused(call(objs, no, g, s=abi.default_settings(features=feat)), "TERRAIN / CLOUD / SEA", want=abi.RM_ERR_UNSUPPORTED), feat
     for feat in (0, abi.RM_FEAT_SKY_BACKGROUND, abi.RM_FEAT_NIGHTSKY_BACKGROUND, abi.RM_FEAT_REFERENCE_DEFAULT):
         assert refused(call(objs, no, g, s=abi.default_settings(features=feat), hits=None), text="null d_rays or d_hits"), feat
-    assert refused(call(objs, no, h.make_globals(two_d=1)), abi.RM_ERR_UNSUPPORTED, "isTwoD")
+    assert refused(call(objs, no, h.make_globals(two_d=1)), "isTwoD", want=abi.RM_ERR_UNSUPPORTED)
     for field in ("maxSteps", "fractalIters", "mengerLevels"):
         assert refused(call(objs, no, g, s=abi.default_settings(**{field: -1})), text="loop bound"), field
     assert refused(call(objs, no, g, s=abi.default_settings(maxSteps=0), rays=None), text="null d_rays or d_hits")
     objs[1].type = abi.RM_CUSTOM
-    assert refused(call(objs, no, g), abi.RM_ERR_UNSUPPORTED, "object 1")
+    assert refused(call(objs, no, g), "object 1", want=abi.RM_ERR_UNSUPPORTED)
     assert "CUSTOM" in lib().rm_last_error().decode()
     for ty in (99, -1):
         objs[1].type = abi.RM_CUBE
         objs[2].type = ty
-        assert refused(call(objs, no, g), abi.RM_ERR_UNSUPPORTED, "object 2"), ty
+        assert refused(call(objs, no, g), "object 2", want=abi.RM_ERR_UNSUPPORTED), ty
 
 
 def test_the_two_arrays():
@@ -157,13 +130,10 @@ def test_the_two_arrays():
     assert refused(call(objs, no, g, hits=None), text="null d_rays or d_hits")
     assert refused(call(None, 0, g, hits=None), text="null d_rays or d_hits")  # an empty table needs no pointer
     for off in (4, 8, 12, 1):
-        assert refused(call(objs, no, g, rays=C.c_void_p(0x1000 + off)), text="16-byte aligned"), off
-        assert refused(call(objs, no, g, hits=C.c_void_p(0x1000 + off)), text="16-byte aligned"), off
+        assert refused(call(objs, no, g, rays=fake(0x1000 + off)), text="16-byte aligned"), off
+        assert refused(call(objs, no, g, hits=fake(0x1000 + off)), text="16-byte aligned"), off
     # host memory is not device memory: each array is checked (the only check that asks the HIP runtime)
-    host = np.zeros(100 * 8 + 8, dtype=np.float32)
-    base = (host.ctypes.data + 15) & ~15
-    hp = C.c_void_p(base)
-    assert refused(call(objs, no, g, rays=hp, hits=hp), text="d_rays")
+    assert refused(call(objs, no, g, rays=HP, hits=HP), text="d_rays")
 
 
 # ---------------------------------------------------------------- rm_camera_rays against the specification
