@@ -1149,7 +1149,9 @@ int rm_render_clocked(const RmCamera *cam, const RmObject *objs, int numObjects,
                       unsigned long long *d_waveSpans);
 
 /* Average device time in ms of the `rm_render*` launches made on the CURRENT device since rm_set_timing(1), timed with
- * hipEvents on their own stream; rm_get_* reads and resets that device's records (the on/off switch is process-wide). */
+ * hipEvents on their own stream; rm_get_* reads and resets that device's records (the on/off switch is process-wide).
+ * rm_set_timing acts on the PROCESS: launches of every thread on every device are recorded while it is on, each in its device's
+ * list, and rm_get_timing returns the launches of all threads on the current device. */
 int rm_set_timing(int on);
 int rm_get_timing(double *avgKernelMs, int *launches);
 /* Same, split by role, both averaged over ALL the launches (total = stage 0 + stage 1): stage 1 = the render (the one-lane-per-pixel
@@ -1168,7 +1170,9 @@ int rm_get_stage_timing(double *avgTotalMs, double avgStageMs[4], int *launches)
  * bounce kernel.  A request that does not apply to the scene (5 with a Mandelbulb, samplers, layers or refraction, or on a
  * frame its 32-bit ray ids cannot cover) runs 1.  Both produce identical bits; the switch exists for A/B measurement and
  * tests.  (Paths 2-4, three multi-kernel pipelines of the single-Mandelbulb class, were measured slower than path 1 on every
- * frame incl. frames without tile-order history — profiles/r04_b_bulb_paths.md — and removed in round 4; the numbers are refused.) */
+ * frame incl. frames without tile-order history — profiles/r04_b_bulb_paths.md — and removed in round 4; the numbers are refused.)
+ * The switch acts on the PROCESS — every device, stream and thread reads it at its next launch: set it while no other thread is
+ * launching. */
 int rm_set_kernel_path(int path);
 /* Scratch memory the library owns.  Everything the schedules need beyond the caller's frame lives in grow-only buffers per
  * (device, stream): 8 B per tile for the tile-order feedback, the post passes' ping-pong images, the lists of rm_render_adaptive
@@ -1181,7 +1185,8 @@ int rm_set_kernel_path(int path);
  * an explicit rm_set_kernel_path(5) reports RM_ERR_DEVICE.  An allocation failure never leaves HIP's error state set.
  * rm_release_workspaces drains the current device and frees all of its buffers (freedBytes may be NULL); a render launch or
  * post pass that another thread is enqueuing on the device at the time finishes its enqueue first.  The next launch that
- * needs a buffer allocates it again, and the next frame on each stream runs in raster tile order. */
+ * needs a buffer allocates it again, and the next frame on each stream runs in raster tile order.  rm_set_workspace_limit acts
+ * on the PROCESS: one limit for every device, stream and thread. */
 int rm_set_workspace_limit(unsigned long long bytes);
 int rm_release_workspaces(unsigned long long *freedBytes);
 /* Tests: the schedule (numbering above; never 0) the most recent render launch on the current device ran, -1 on error; 6 = a
@@ -1190,18 +1195,21 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
  * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
  * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned (none of them is a value rm_set_kernel_path
- * takes). */
+ * takes).  The value belongs to the DEVICE, not to the calling thread or stream: it reports the device's most recent launch,
+ * whichever thread made it. */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the
  * heaviest tiles of a SETTLED picture of the plain table-walk class with two or more lights are rendered by numLights workgroups
  * each, one shadow march per pixel apiece, and finished — by whichever of them arrives last — from the stored results: the same
  * marches and the same sums in the same order, so the same pixels; it shortens the longest waves of latency-bound frames, C2 0.79 →
  * 0.51 ms.  Whether it pays is measured per picture.  RM_LIGHT_SPLIT=0 turns it off, =n makes the heaviest 1/n of the tiles the
- * candidates; default 256).  0: none; -1 on error. */
+ * candidates; default 256).  0: none; -1 on error.  Per DEVICE, as rm_debug_last_path: the device's most recent launch, whichever
+ * thread made it. */
 int rm_debug_last_split(void);
 /* Tests / experiments: the divisor above for the process — n >= 1 also splits WITHOUT the measurement that normally decides per
  * picture whether the split pays (settled frames 0-1 plain, 2-3 split, the better of the two from then on); 0 = off, -1 = back to
- * RM_LIGHT_SPLIT / the default, measured. */
+ * RM_LIGHT_SPLIT / the default, measured.  It acts on the PROCESS (every device, stream and thread): set it while no other thread
+ * is launching. */
 int rm_debug_set_light_split(int div);
 /* Launch order of a frame's tiles (workgroups).  Tile costs span three orders of magnitude and a single ray that never
  * converges is a sequential chain of ~1 ms, so a kernel whose heaviest tiles start late ends in a tail of a few lonely
@@ -1215,12 +1223,13 @@ int rm_debug_set_light_split(int div);
  * scenes with procedural layers or objects without a bound start new pictures in raster order.  mode 0: always raster order;
  * -1: back to the default / the RM_TILE_ORDER environment variable.  Applies to every launch of the one-lane-per-pixel kernel
  * with at least 2048 tiles (not to the 2-D Mandelbrot path or the wavefront pipeline, whose persistent waves balance
- * themselves). */
+ * themselves).  The mode acts on the PROCESS: every device, stream and thread reads it at its next launch. */
 int rm_set_tile_order(int mode);
 /* Shape of the pixel tile a wave renders: 8×8 by default; for table-walk, sampler and layer scenes the launcher measures, per
  * stream and picture, whether 4 wide × 16 tall tiles are faster (frames 0-1 and 4-5 of a picture run 8×8, frames 2-3 and 6-7 4×16,
  * the second of each pair timed with HIP events) and keeps the shape with the smaller best time from the ninth frame on.  The shape never changes a pixel.  Tests /
- * experiments: mode 0 = tune (default), 3 = always 8×8, 2 = always 4×16, -1 = back to the RM_TILE_SHAPE environment variable. */
+ * experiments: mode 0 = tune (default), 3 = always 8×8, 2 = always 4×16, -1 = back to the RM_TILE_SHAPE environment variable.
+ * The mode acts on the PROCESS: every device, stream and thread reads it at its next launch. */
 int rm_debug_set_tile_shape(int mode);
 /* Experiments: force a given launch order (d_order: a device permutation of 0..tileCount-1, or NULL) and / or collect the
  * tiles' costs (d_cost: tileCount device words, accumulated, or NULL) for subsequent launches on the current device. */

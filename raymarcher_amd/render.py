@@ -6,6 +6,7 @@ getGlobalData (src/raymarch/raymarchscene.h:12-90) and Realtime::rayMarch / save
 rm_render*, rm_frame_to_rgba8 and rm_write_png.
 """
 import ctypes as C
+import threading
 from dataclasses import dataclass
 
 from . import abi
@@ -458,6 +459,11 @@ class Renderer:
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         check(lib().rm_set_device(device))
+        # _upload's cache: id(host array) → (the array, its device copy).  Threads may share a Renderer (each on a stream of its own),
+        # so the dict exists before any of them runs and every look-up and insertion holds the lock: an entry, once made, keeps the
+        # device tensor that an enqueued launch reads alive.
+        self._tex_cache = {}
+        self._tex_lock = threading.Lock()
 
     def _out(self, a, shape, dtype, name="out"):
         """A fresh tensor of `shape` and `dtype` on this device, or the caller's `a` once it is checked to be exactly that (the
@@ -474,12 +480,11 @@ class Renderer:
 
     def _upload(self, a):
         """Host uint8 array → device tensor, cached per array object."""
-        if not hasattr(self, "_tex_cache"):
-            self._tex_cache = {}
         key = id(a)
-        if key not in self._tex_cache:
-            self._tex_cache[key] = (a, self.torch.from_numpy(a).contiguous().to(self.device))
-        return self._tex_cache[key][1]
+        with self._tex_lock:
+            if key not in self._tex_cache:
+                self._tex_cache[key] = (a, self.torch.from_numpy(a).contiguous().to(self.device))
+            return self._tex_cache[key][1]
 
     def _resources(self, tables):
         """RmResources with device pointers for everything `tables` carries; returns (struct, keep-alive list)."""
