@@ -1,6 +1,6 @@
 // rm_blocks_prune.h — the classification of rm_sdf_blocks_select_pruned (include/raymarcher_amd.h has the definition): the bounds
 // from the lattice step and the two constants, whether a corner value is far from the iso surface, and the eight-corner rule that
-// discards a block.  Plain C++ with no device built-in, so the kernel of rm_blocks_prune.hip and a host program
+// discards a block.  Plain C++ with no device built-in, so the kernel of rm_blocks.hip and a host program
 // (tests/sdf_prune_spec/rm_blocks_prune_cpu.cpp) run the very same code.  Every operation is one binary32 operation as written:
 // compile with -ffp-contract=off (the library's flags).
 #pragma once

@@ -19,7 +19,7 @@
 // 8·value / t: the step is NOT taken then, and the fine skip below runs as it is written.  The tests `t > tEnd` between the fine
 // skips only ever give the miss that the test behind the step gives: t does not decrease.  tests/test_field_handle_spec.py holds
 // all this against the fine march (RM_FIELD_COARSE=0) in every bit on rays built to tie and graze, with t above and below 0.
-//   Plain C++ with no device built-in, so the kernels of rm_field_handle.hip and a host program
+//   Plain C++ with no device built-in, so the handle kernels of rm_field.hip and a host program
 // (tests/field_handle_spec/rm_field_handle_cpu.cpp) run the very same code.  Compile with -ffp-contract=off.
 #pragma once
 #include "rm_field_march.h"

@@ -44,6 +44,24 @@ int lock_current_device(std::unique_lock<std::mutex> &lock);
 // synchronises `stream` (nothing else uses the old buffer) and reallocates.  Returns an rm_status.
 enum { kWsPost = 2, kWsTileOrder = 3, kWsWavefront = 4, kWsLightSplit = 5, kWsAdaptive = 6, kWsAdaptiveCounts = 7, kWsMesh = 8, kWsBlocks = 9, kWsRayOrder = 10 };
 int stream_workspace(int tag, hipStream_t stream, size_t need, void **out);
+// The layout of a workspace, written once: take<T>(count) hands out the next `count` elements, every buffer on a multiple of 256
+// bytes; bytes() is what has been taken.  Without a base it only measures (take returns null), so the size a caller asks
+// stream_workspace for and the pointers its kernels get come from the same lines.
+class Carve {
+ public:
+  explicit Carve(void *base = nullptr) : base_(static_cast<char *>(base)) {}
+  template <class T>
+  T *take(size_t count) {
+    const size_t at = used_;
+    used_ += (count * sizeof(T) + 255) & ~size_t(255);
+    return base_ ? reinterpret_cast<T *>(base_ + at) : nullptr;
+  }
+  size_t bytes() const { return used_; }
+
+ private:
+  char *base_;
+  size_t used_ = 0;
+};
 // The test-only probe of the scene evaluator (rm_probe.hip, rm_probe_sdscene_variant): whether a production kernel instantiates
 // this combination (no HIP call), and the launch of its probe kernel on a staged SceneBlock (device pointer `sb`).
 bool sdscene_variant_exists(int bulbClass, int count, int trap, int skip, int track, bool one);
@@ -113,44 +131,7 @@ int launch_shade_layers_kernel(const void *sb, bool tex, bool sec, const void *d
                                float *d_bright, hipStream_t stream);
 int launch_trace_layers_kernel(const void *sb, int bulbClass, bool noNormal, const void *d_rays, int numRays, int imageWidth,
                                void *d_hits, hipStream_t stream);
-// The lattice kernels (rm_volume.hip, rm_sdf_grid and rm_sdf_mesh; a translation unit of its own for the same reason).
-// check_lattice: the rules both entry points have for origin, step and the dimensions, in the header's order, no HIP call.
-// launch_sdf_grid_kernel: sdf_grid_kernel<bulbClass> over the ONE staged SceneBlock `sb`, one lane per lattice point, a wave per
-// brick — nx·ny·nz values into d_dist and, when d_objectId is not null, as many object indices.  rm_sdf_mesh is whole in rm_volume.hip.
-int check_lattice(const float *origin, const float *step, int nx, int ny, int nz);
-int launch_sdf_grid_kernel(const void *sb, int bulbClass, const float origin[3], const float step[3], int nx, int ny, int nz,
-                           float *d_dist, int32_t *d_objectId, hipStream_t stream);
-// The block-sparse lattice kernels (rm_blocks.hip, rm_sdf_blocks_select, rm_sdf_grid_blocks and rm_sdf_mesh_blocks; a translation
-// unit of its own for the same reason).  check_block_lattice: the rules the three entry points have for origin, step and the block
-// dimensions, no HIP call.  launch_blocks_select_kernels: blocks_eval_kernel<bulbClass, select> over the ONE staged SceneBlock `sb`,
-// a workgroup per block of the virtual lattice, then the compaction of the flags into d_blocks and d_count; `workspace` holds
-// blocks_select_workspace bytes.  launch_blocks_grid_kernels: the block map of the list, then blocks_eval_kernel<bulbClass, grid>, a
-// workgroup per entry — 729 values per entry that is not void into d_dist and, when d_objectId is not null, as many object indices;
-// `workspace` holds blocks_map_workspace bytes.  rm_sdf_mesh_blocks is whole in rm_blocks.hip.
-int check_block_lattice(const float *origin, const float *step, int mx, int my, int mz);
-size_t blocks_select_workspace(int mx, int my, int mz);
-size_t blocks_map_workspace(int mx, int my, int mz);
-int launch_blocks_select_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz, float iso,
-                                 int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace, hipStream_t stream);
-int launch_blocks_grid_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz,
-                               const int32_t *d_blocks, int numBlocks, float *d_dist, int32_t *d_objectId, void *workspace, hipStream_t stream);
-// What rm_blocks.hip shares with rm_blocks_prune.hip (rm_sdf_blocks_select_pruned; a translation unit of its own for the same
-// reason).  The lattice as the evaluation kernels take it.  The compaction of one flag per block in linear order: the flags are
-// dealt in shares of kShare to workgroups of one wave; enqueue_flags_count counts each share into off[share], scans the
-// flag_shares(numFlags) counts into exclusive offsets in place, stores the total in off[shares] and, saturated at 2^32 − 1, in
-// *d_count; enqueue_flags_emit stores the rows (bi, bj, bk, 0) of the set flags numbered below maxBlocks.
-// launch_blocks_prune_kernels: the corner lattice, the classification, the candidates' exact evaluation and the compaction of the
-// active flags into d_blocks and d_count[0], the candidates' number into d_count[1]; `workspace` holds blocks_prune_workspace bytes.
-struct BlockLattice { float ox, oy, oz, sx, sy, sz; int mx, my, mz; };
-constexpr int kShareRounds = 16, kShare = 64 * kShareRounds;
-inline size_t flag_shares(size_t numFlags) { return (numFlags + kShare - 1) / kShare; }
-void enqueue_flags_count(const uint32_t *flags, size_t numFlags, unsigned long long *off, uint32_t *d_count, hipStream_t stream);
-void enqueue_flags_emit(const uint32_t *flags, size_t numFlags, int mx, int my, const unsigned long long *off, int maxBlocks, int32_t *d_blocks,
-                        hipStream_t stream);
-size_t blocks_prune_workspace(int mx, int my, int mz);
-int launch_blocks_prune_kernels(const void *sb, int bulbClass, const float origin[3], const float step[3], int mx, int my, int mz, float iso,
-                                float lipschitzOut, float lipschitzIn, int maxBlocks, int32_t *d_blocks, uint32_t *d_count, void *workspace,
-                                hipStream_t stream);
+// The lattice family — rm_sdf_grid, rm_sdf_mesh, the block-sparse forms, the lattice queries — declares itself in rm_lattice.h.
 // The points kernels (rm_points.hip, rm_shade_points; a translation unit of its own for the same reason): the launch of
 // shade_points_kernel<bulbClass, tex> over the ONE staged SceneBlock `sb`, one lane per point — numPoints float4 from d_points and,
 // when d_view is not null, from d_view; into whichever of d_surface (numPoints RmSurfacePoint), d_ao (a float each) and d_rgba (a

@@ -335,39 +335,29 @@ int refuse_two_d(const RmGlobals *g, const char *text) {
 
 namespace {
 
-// Carve the wavefront pipeline's records for `cap` hit slots and `nl` lights out of the stream's workspace.
-constexpr int kWfBuffers = 13;
-size_t wavefront_sizes(size_t cap, int nl, size_t sizes[kWfBuffers]) {
-  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const size_t nlq = (size_t)(nl > 0 ? nl : 1);
-  const size_t sz[kWfBuffers] = {align(WF_STRIDE * (kWfMaxBounces + 2) * 4), align(cap * 16), align(cap * 16), align(cap * 16), align(cap * 16),
-                                 align(cap * 16), align(cap * 16), align(cap * 16), align(cap * nlq * 4), align(cap * 8), align(cap * 16),
-                                 align(cap * 16), align(cap * 8)};
-  size_t total = 0;
-  for (int i = 0; i < kWfBuffers; i++) { sizes[i] = sz[i]; total += sz[i]; }
-  return total;
-}
-size_t wavefront_bytes(size_t cap, int nl) { size_t sizes[kWfBuffers]; return wavefront_sizes(cap, nl, sizes); }
-int wavefront_workspace(size_t cap, int nl, hipStream_t stream, WfWs *ws) {
-  size_t sizes[kWfBuffers];
-  const size_t total = wavefront_sizes(cap, nl, sizes);
-  void *mem = nullptr;
-  if (int st = stream_workspace(kWsWavefront, stream, total, &mem)) return st;
-  char *q = static_cast<char *>(mem);
-  int k = 0;
-  auto take = [&]() { char *r = q; q += sizes[k++]; return r; };
-  ws->counters = reinterpret_cast<uint32_t *>(take());
-  ws->rayO[0] = reinterpret_cast<float4 *>(take()); ws->rayO[1] = reinterpret_cast<float4 *>(take());
-  ws->rayD[0] = reinterpret_cast<float4 *>(take()); ws->rayD[1] = reinterpret_cast<float4 *>(take());
-  ws->hit = reinterpret_cast<int4 *>(take());
-  ws->surfP = reinterpret_cast<float4 *>(take());
-  ws->surfN = reinterpret_cast<float4 *>(take());
-  ws->shadow = reinterpret_cast<float *>(take());
-  ws->pathPix = reinterpret_cast<int2 *>(take());
-  ws->pathA = reinterpret_cast<float4 *>(take());
-  ws->pathB = reinterpret_cast<float4 *>(take());
-  ws->pathC = reinterpret_cast<float2 *>(take());
+// The wavefront pipeline's records for `cap` hit slots and `nl` lights, laid out once: into ws from the workspace at mem, or
+// measured where mem is null.
+size_t wavefront_layout(size_t cap, int nl, void *mem, WfWs *ws) {
+  Carve c(mem);
+  ws->counters = c.take<uint32_t>(WF_STRIDE * (kWfMaxBounces + 2));
+  ws->rayO[0] = c.take<float4>(cap); ws->rayO[1] = c.take<float4>(cap);
+  ws->rayD[0] = c.take<float4>(cap); ws->rayD[1] = c.take<float4>(cap);
+  ws->hit = c.take<int4>(cap);
+  ws->surfP = c.take<float4>(cap);
+  ws->surfN = c.take<float4>(cap);
+  ws->shadow = c.take<float>(cap * (size_t)(nl > 0 ? nl : 1));
+  ws->pathPix = c.take<int2>(cap);
+  ws->pathA = c.take<float4>(cap);
+  ws->pathB = c.take<float4>(cap);
+  ws->pathC = c.take<float2>(cap);
   ws->cap = (uint32_t)cap;
+  return c.bytes();
+}
+size_t wavefront_bytes(size_t cap, int nl) { WfWs unused; return wavefront_layout(cap, nl, nullptr, &unused); }
+int wavefront_workspace(size_t cap, int nl, hipStream_t stream, WfWs *ws) {
+  void *mem = nullptr;
+  if (int st = stream_workspace(kWsWavefront, stream, wavefront_bytes(cap, nl), &mem)) return st;
+  wavefront_layout(cap, nl, mem, ws);
   return RM_OK;
 }
 

@@ -1,7 +1,6 @@
 // rm_order.hip — rm_rays_order and rm_rays_restore (gfx950 only): the coherence ordering of an RmRay array and its inverse.
 // include/raymarcher_amd.h has the definitions, rm_ray_key.h the key.  Everything of the two entry points is here, as
-// rm_sdf_mesh_blocks is in rm_blocks.hip.  A translation unit of its own, so that adding it leaves the code objects of the existing
-// kernels as they were.
+// rm_sdf_mesh_blocks is in rm_blocks.hip.
 //   1. order_bounds_kernel: lo and hi of the five coordinates over a workgroup's rays — lanes, then the wave (shuffles), then LDS —
 //      one partial per workgroup; order_bounds_final_kernel merges the partials.  Minima and maxima are exact, so a store-and-merge
 //      gives the bits of any other order; no float atomic.
@@ -21,6 +20,7 @@
 #include <string>
 
 #include "../../include/raymarcher_amd.h"
+#include "rm_compact.hip.h"
 #include "rm_internal.h"
 #include "rm_ray_key.h"
 
@@ -155,7 +155,6 @@ RO_DEV unsigned long long digit_peers(unsigned d, bool live) {
   }
   return m;
 }
-RO_DEV unsigned lanes_below(unsigned long long ballot, unsigned lane) { return (unsigned)__popcll(ballot & ((1ull << lane) - 1ull)); }
 
 // hist[d·numTiles + tile] = the tile's keys with digit d
 __global__ __launch_bounds__(kSortLanes) void order_hist_kernel(SortBuffers s, unsigned n, int pass, const unsigned long long *__restrict__ orAnd,
@@ -180,32 +179,18 @@ __global__ __launch_bounds__(kSortLanes) void order_hist_kernel(SortBuffers s, u
   hist[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = count[threadIdx.x];
 }
 
-// Workgroup d turns digit d's numTiles counts into exclusive offsets in place (blocks_scan_kernel's pattern) and stores their sum.
+// Workgroup d turns digit d's numTiles counts into exclusive offsets in place and stores their sum.
 __global__ __launch_bounds__(1024) void order_scan_kernel(uint32_t *__restrict__ hist, unsigned numTiles, int pass,
                                                           const unsigned long long *__restrict__ orAnd, uint32_t *__restrict__ totals) {
-  __shared__ unsigned waveSum[16];
+  __shared__ uint32_t waveSum[16];
   if (pass_info(orAnd, pass).skipped) return;
   uint32_t *mine = hist + (size_t)blockIdx.x * (size_t)numTiles;
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  unsigned carry = 0;  // the same in every lane
+  uint32_t carry = 0;  // the same in every lane
   for (unsigned base = 0; base < numTiles; base += 1024u) {
     const unsigned i = base + threadIdx.x;
-    const unsigned v = i < numTiles ? mine[i] : 0u;
-    unsigned sum = v;  // inclusive within the wave
-    for (unsigned d = 1; d < 64u; d <<= 1) {
-      const unsigned t = __shfl_up(sum, d);
-      if (lane >= d) sum += t;
-    }
-    if (lane == 63u) waveSum[wave] = sum;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-    for (unsigned w = 0; w < 16u; w++) {
-      if (w < wave) before += waveSum[w];
-      all += waveSum[w];
-    }
-    if (i < numTiles) mine[i] = carry + before + sum - v;
-    carry += all;
-    __syncthreads();
+    const ScanRound<uint32_t> r = scan_round_1024(i < numTiles ? mine[i] : 0u, waveSum);
+    if (i < numTiles) mine[i] = carry + r.before;
+    carry += r.all;
   }
   if (threadIdx.x == 0u) totals[blockIdx.x] = carry;
 }
@@ -327,7 +312,24 @@ __global__ __launch_bounds__(256) void order_restore_kernel(const uint4 *__restr
   out[(size_t)to * parts + part] = rows[g];
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// The workspace of a call: 24 B per ray — two key buffers, two index buffers —, the histograms (1 KB per tile), the digits' totals,
+// the bounds' partials, then 256 B of head: the bounds and, 64 B in, the keys' OR and AND.  Measured where mem is null.
+struct OrderWs { SortBuffers sb; uint32_t *hist, *totals; float *partials, *bounds; unsigned long long *orAnd; size_t bytes; };
+static OrderWs order_workspace(size_t n, size_t numTiles, void *mem) {
+  Carve c(mem);
+  OrderWs w;
+  w.sb.keys[0] = c.take<unsigned long long>(n);
+  w.sb.keys[1] = c.take<unsigned long long>(n);
+  w.sb.idx[0] = c.take<uint32_t>(n);
+  w.sb.idx[1] = c.take<uint32_t>(n);
+  w.hist = c.take<uint32_t>(256 * numTiles);
+  w.totals = c.take<uint32_t>(256);
+  w.partials = c.take<float>((size_t)kBoundsGroups * 2 * rk::kCoords);
+  w.bounds = c.take<float>(64);
+  w.orAnd = mem ? reinterpret_cast<unsigned long long *>(w.bounds + 16) : nullptr;
+  w.bytes = c.bytes();
+  return w;
+}
 static bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace rm
@@ -351,39 +353,25 @@ extern "C" int rm_rays_order(const RmRay *d_rays, int numRays, int originBits, i
   const size_t groups = (n + 255) / 256;
   const unsigned boundsGroups = (unsigned)(groups < (size_t)kBoundsGroups ? groups : (size_t)kBoundsGroups);
   const unsigned keyGroups = (unsigned)(groups < (size_t)kKeyGroups ? groups : (size_t)kKeyGroups);
-  // 24 B per ray — two key buffers, two index buffers —, the histograms (1 KB per tile), the digits' totals, the bounds' partials,
-  // then the bounds and the keys' OR and AND
-  const size_t keyBytes = align256(n * sizeof(unsigned long long)), idxBytes = align256(n * sizeof(uint32_t)),
-               histBytes = align256(256 * numTiles * sizeof(uint32_t)), totalBytes = align256(256 * sizeof(uint32_t)),
-               partialBytes = align256((size_t)kBoundsGroups * 2 * rk::kCoords * sizeof(float)), headBytes = 256;
   // the workspace is in use until the last launch is enqueued: the device's launcher lock keeps rm_release_workspaces away
   std::unique_lock<std::mutex> lock;
   if (int st = lock_current_device(lock)) return st;
   void *mem = nullptr;
-  if (int st = stream_workspace(kWsRayOrder, hs, 2 * keyBytes + 2 * idxBytes + histBytes + totalBytes + partialBytes + headBytes, &mem)) return st;
-  char *at = static_cast<char *>(mem);
-  auto take = [&at](size_t bytes) { char *p = at; at += bytes; return p; };
-  SortBuffers sb;
-  sb.keys[0] = reinterpret_cast<unsigned long long *>(take(keyBytes));
-  sb.keys[1] = reinterpret_cast<unsigned long long *>(take(keyBytes));
-  sb.idx[0] = reinterpret_cast<uint32_t *>(take(idxBytes));
-  sb.idx[1] = reinterpret_cast<uint32_t *>(take(idxBytes));
-  uint32_t *hist = reinterpret_cast<uint32_t *>(take(histBytes)), *totals = reinterpret_cast<uint32_t *>(take(totalBytes));
-  float *partials = reinterpret_cast<float *>(take(partialBytes)), *bounds = reinterpret_cast<float *>(take(headBytes));
-  unsigned long long *orAnd = reinterpret_cast<unsigned long long *>(bounds + 16);
+  if (int st = stream_workspace(kWsRayOrder, hs, order_workspace(n, numTiles, nullptr).bytes, &mem)) return st;
+  const OrderWs ws = order_workspace(n, numTiles, mem);
   const float4 *rays = reinterpret_cast<const float4 *>(d_rays);
 
-  hipLaunchKernelGGL(order_bounds_kernel, dim3(boundsGroups), dim3(256), 0, hs, rays, (unsigned)n, partials);
-  hipLaunchKernelGGL(order_bounds_final_kernel, dim3(1), dim3(256), 0, hs, partials, boundsGroups, bounds, orAnd);
-  hipLaunchKernelGGL(order_keys_kernel, dim3(keyGroups), dim3(256), 0, hs, rays, (unsigned)n, originBits, dirBits, bounds, sb.keys[0], sb.idx[0],
-                     reinterpret_cast<unsigned long long *>(d_keys), orAnd);
+  hipLaunchKernelGGL(order_bounds_kernel, dim3(boundsGroups), dim3(256), 0, hs, rays, (unsigned)n, ws.partials);
+  hipLaunchKernelGGL(order_bounds_final_kernel, dim3(1), dim3(256), 0, hs, ws.partials, boundsGroups, ws.bounds, ws.orAnd);
+  hipLaunchKernelGGL(order_keys_kernel, dim3(keyGroups), dim3(256), 0, hs, rays, (unsigned)n, originBits, dirBits, ws.bounds, ws.sb.keys[0], ws.sb.idx[0],
+                     reinterpret_cast<unsigned long long *>(d_keys), ws.orAnd);
   const int numPasses = (rk::key_bits(originBits, dirBits) + 7) / 8;  // at most 7
   for (int pass = 0; pass < numPasses; pass++) {
-    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)numTiles), dim3(kSortLanes), 0, hs, sb, (unsigned)n, pass, orAnd, hist);
-    hipLaunchKernelGGL(order_scan_kernel, dim3(256), dim3(1024), 0, hs, hist, (unsigned)numTiles, pass, orAnd, totals);
-    hipLaunchKernelGGL(order_scatter_kernel, dim3((unsigned)numTiles), dim3(kSortLanes), 0, hs, sb, (unsigned)n, pass, orAnd, hist, totals);
+    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)numTiles), dim3(kSortLanes), 0, hs, ws.sb, (unsigned)n, pass, ws.orAnd, ws.hist);
+    hipLaunchKernelGGL(order_scan_kernel, dim3(256), dim3(1024), 0, hs, ws.hist, (unsigned)numTiles, pass, ws.orAnd, ws.totals);
+    hipLaunchKernelGGL(order_scatter_kernel, dim3((unsigned)numTiles), dim3(kSortLanes), 0, hs, ws.sb, (unsigned)n, pass, ws.orAnd, ws.hist, ws.totals);
   }
-  hipLaunchKernelGGL(order_emit_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, hs, sb, (unsigned)n, numPasses, orAnd, rays, d_order,
+  hipLaunchKernelGGL(order_emit_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, hs, ws.sb, (unsigned)n, numPasses, ws.orAnd, rays, d_order,
                      reinterpret_cast<float4 *>(d_sorted));
   HIP_OK(hipGetLastError());
   return RM_OK;

@@ -2,8 +2,8 @@
 // probes.  Each checks its arguments, stages one scene block and launches one kernel of another unit through the launcher's
 // stage_block_launch (rm_launch.h), which also records the path and the timing: nothing here reads or writes a tuner, the tile
 // order or the wavefront state, and nothing here sees the launcher's slots, rings or device state.  Host code only: the kernels
-// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_layers.hip, rm_points.hip, rm_volume.hip, rm_blocks.hip,
-// rm_blocks_prune.hip and rm_probe.hip (declared in rm_internal.h), the scene prep that needs no GPU in rm_frame.cpp.
+// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_layers.hip, rm_points.hip, rm_volume.hip, rm_blocks.hip
+// and rm_probe.hip (declared in rm_internal.h, the lattice family's in rm_lattice.h), the scene prep that needs no GPU in rm_frame.cpp.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -11,6 +11,7 @@
 
 #include "rm_internal.h"
 #include "rm_frame.h"
+#include "rm_lattice.h"
 #include "rm_launch.h"
 
 namespace rm {
@@ -236,7 +237,7 @@ int launch_sdf_grid(const RmObject *objs, int numObjects, const RmGlobals *g, co
 // launch_sdf_grid's staging behind the stream's workspace (kWsBlocks; BlockCall::workspaceBytes), which stage_block_launch takes
 // under the device's lock as launch_adaptive takes its own.  rm_sdf_blocks_select: one launch of blocks_eval_kernel (rm_blocks.hip)
 // over every block of the lattice, which keeps a flag per block, and the compaction of the flags, path 18;
-// rm_sdf_blocks_select_pruned: the same flags from the kernels of rm_blocks_prune.hip, which evaluate only the blocks near the
+// rm_sdf_blocks_select_pruned: the same flags from the pruning kernels of rm_blocks.hip, which evaluate only the blocks near the
 // surface, path 20.  rm_sdf_grid_blocks: the block map of the list (void entries), then one launch of blocks_eval_kernel over the
 // list's entries, path 19.
 struct BlocksCall {
@@ -261,7 +262,7 @@ int check_blocks_head(const BlocksCall &c) {
   return check_block_lattice(c.origin, c.step, c.mx, c.my, c.mz);
 }
 // lipschitz: null for rm_sdf_blocks_select; (lipschitzOut, lipschitzIn) for rm_sdf_blocks_select_pruned, which has the same checks
-// with its own between iso and maxBlocks, the same staging, the kernels of rm_blocks_prune.hip and path 20.
+// with its own between iso and maxBlocks, the same staging, the pruning kernels of rm_blocks.hip and path 20.
 int launch_sdf_blocks_select(const BlocksCall &c, float iso, const float *lipschitz, int maxBlocks, int32_t *d_blocks, uint32_t *d_count) {
   int st = check_blocks_head(c);
   if (st != RM_OK) return st;

@@ -1,16 +1,15 @@
 // rm_volume.hip — where the surface is (gfx950 only): the kernel of rm_sdf_grid, sdScene on a dense lattice, and the kernels and the
 // entry point of rm_sdf_mesh, a quad mesh from any lattice of floats by naive surface nets.  include/raymarcher_amd.h has both
 // definitions.  rm_sdf_grid's argument checks and staging are launch_sdf_grid in rm_queries.hip; everything of rm_sdf_mesh is
-// here, as the post passes are in rm_post.hip.  A translation unit of its own, so that adding it leaves the code objects of the
-// existing kernels as they were.
+// here, as the post passes are in rm_post.hip.  rm_lattice.h has the lattice rules, rm_compact.hip.h the scan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <string>
 
+#include "rm_compact.hip.h"
 #include "rm_device.hip.h"
-#include "rm_internal.h"
+#include "rm_lattice.h"
 #include "rm_surface_nets.h"
 
 namespace rm {
@@ -69,20 +68,6 @@ int launch_sdf_grid_kernel(const void *sbv, int bulbClass, const float origin[3]
   return RM_OK;
 }
 
-// The lattice rules that rm_sdf_grid and rm_sdf_mesh share, in the header's order.  No HIP call.
-int check_lattice(const float *origin, const float *step, int nx, int ny, int nz) {
-  auto bad = [](const char *msg) { set_error(msg); return (int)RM_ERR_INVALID_ARGUMENT; };
-  if (!origin || !step) return bad("null origin or step");
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(origin[a])) return bad("origin must be finite");
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(step[a]) || !(step[a] > 0.0f)) return bad("step must be finite and greater than 0 on every axis");
-  if (nx < 1 || ny < 1 || nz < 1 || nx > RM_MAX_LATTICE_DIM || ny > RM_MAX_LATTICE_DIM || nz > RM_MAX_LATTICE_DIM)
-    return bad("every lattice dimension must be 1 … RM_MAX_LATTICE_DIM (4096)");
-  if ((long long)nx * ny * nz > INT_MAX) return bad("more than INT_MAX lattice points");
-  return RM_OK;
-}
-
 // ---- rm_sdf_mesh ---------------------------------------------------------------------------------------------------------------
 // Lattice points in their linear order q = (k·ny + j)·nx + i are dealt to workgroups of ONE wave, kMeshShare = 1024 consecutive
 // points each (16 rounds of 64: a round reads 64 consecutive floats per corner).  Point q stands for two things: the cell whose
@@ -126,7 +111,6 @@ RM_DEV PointClass classify_point(const Lattice &L, unsigned q) {
     c.quad[a] = sn::edge_interior(a, c.i, c.j, c.k, L.nx, L.ny, L.nz) && (((c.mask >> (1 << a)) & 1u) != 0u) != p;
   return c;
 }
-RM_DEV unsigned below(unsigned long long ballot, unsigned lane) { return (unsigned)__popcll(ballot & ((1ull << lane) - 1ull)); }
 
 __global__ __launch_bounds__(64) void mesh_count_kernel(Lattice L, unsigned numPoints, uint32_t *__restrict__ vOff,
                                                         unsigned long long *__restrict__ qOff) {
@@ -150,35 +134,24 @@ __global__ __launch_bounds__(64) void mesh_count_kernel(Lattice L, unsigned numP
 
 __global__ __launch_bounds__(1024) void mesh_scan_kernel(uint32_t *__restrict__ vOff, unsigned long long *__restrict__ qOff, unsigned n,
                                                          uint32_t *__restrict__ counts) {
-  __shared__ unsigned long long waveV[16], waveQ[16];
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  unsigned long long carryV = 0, carryQ = 0;  // the same in every lane
+  __shared__ uint32_t waveV[16];
+  __shared__ unsigned long long waveQ[16];
+  uint32_t carryV = 0;  // the same in every lane; at most the number of cells, below 2^31
+  unsigned long long carryQ = 0;
   for (unsigned base = 0; base < n; base += 1024u) {
     const unsigned i = base + threadIdx.x;
-    const unsigned long long v = i < n ? vOff[i] : 0ull, q = i < n ? qOff[i] : 0ull;
-    unsigned long long sv = v, sq = q;  // inclusive within the wave
-    for (unsigned d = 1; d < 64u; d <<= 1) {
-      const unsigned long long tv = __shfl_up(sv, d), tq = __shfl_up(sq, d);
-      if (lane >= d) { sv += tv; sq += tq; }
-    }
-    if (lane == 63u) { waveV[wave] = sv; waveQ[wave] = sq; }
-    __syncthreads();
-    unsigned long long beforeV = 0, beforeQ = 0, allV = 0, allQ = 0;
-    for (unsigned w = 0; w < 16u; w++) {
-      if (w < wave) { beforeV += waveV[w]; beforeQ += waveQ[w]; }
-      allV += waveV[w];
-      allQ += waveQ[w];
-    }
+    ScanRound<uint32_t> v;
+    ScanRound<unsigned long long> q;
+    scan_round_1024(i < n ? vOff[i] : 0u, waveV, v, i < n ? qOff[i] : 0ull, waveQ, q);
     if (i < n) {
-      vOff[i] = (uint32_t)(carryV + beforeV + sv - v);  // at most the number of cells, below 2^31
-      qOff[i] = carryQ + beforeQ + sq - q;
+      vOff[i] = carryV + v.before;
+      qOff[i] = carryQ + q.before;
     }
-    carryV += allV;
-    carryQ += allQ;
-    __syncthreads();
+    carryV += v.all;
+    carryQ += q.all;
   }
   if (threadIdx.x == 0) {
-    counts[0] = (uint32_t)carryV;
+    counts[0] = carryV;
     counts[1] = carryQ > 0xffffffffull ? 0xffffffffu : (uint32_t)carryQ;
   }
 }
@@ -199,7 +172,7 @@ __global__ __launch_bounds__(64) void mesh_vertices_kernel(Lattice L, const int3
     }
     const unsigned long long ballot = __ballot(act);
     if (act) {
-      const unsigned number = base + below(ballot, threadIdx.x);
+      const unsigned number = base + lanes_below(ballot, threadIdx.x);
       cellVertex[((size_t)c.k * (size_t)(L.ny - 1) + (size_t)c.j) * (size_t)(L.nx - 1) + (size_t)c.i] = (int32_t)number;
       if (number < (unsigned)maxVertices) {
         float local[3];
@@ -234,7 +207,7 @@ __global__ __launch_bounds__(64) void mesh_quads_kernel(Lattice L, unsigned numP
     if (q < numPoints) c = classify_point(L, q);
     const unsigned long long b0 = __ballot(c.quad[0]), b1 = __ballot(c.quad[1]), b2 = __ballot(c.quad[2]);
     // the quads of the points before this one in the round, then this point's own, in axis order
-    unsigned long long number = base + below(b0, threadIdx.x) + below(b1, threadIdx.x) + below(b2, threadIdx.x);
+    unsigned long long number = base + lanes_below(b0, threadIdx.x) + lanes_below(b1, threadIdx.x) + lanes_below(b2, threadIdx.x);
 #pragma unroll
     for (int a = 0; a < 3; a++) {
       if (!c.quad[a]) continue;
@@ -251,6 +224,13 @@ __global__ __launch_bounds__(64) void mesh_quads_kernel(Lattice L, unsigned numP
     }
     base += (unsigned long long)(__popcll(b0) + __popcll(b1) + __popcll(b2));
   }
+}
+
+// the workspace of a call: a vertex number per cell, the shares' quad and vertex offsets; measured where mem is null
+struct MeshWs { int32_t *cellVertex; unsigned long long *qOff; uint32_t *vOff; size_t bytes; };
+static MeshWs mesh_workspace(size_t cells, size_t shares, void *mem) {
+  Carve c(mem);  // a braced list is evaluated left to right: the members' order is the layout
+  return MeshWs{c.take<int32_t>(cells), c.take<unsigned long long>(shares), c.take<uint32_t>(shares), c.bytes()};
 }
 
 }  // namespace rm
@@ -276,25 +256,20 @@ extern "C" int rm_sdf_mesh(const float *d_dist, const int32_t *d_objectId, int n
   }
   const unsigned numPoints = (unsigned)((long long)nx * ny * nz), shares = (numPoints + kMeshShare - 1u) / kMeshShare;
   const size_t cells = (size_t)(nx - 1) * (size_t)(ny - 1) * (size_t)(nz - 1);
-  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const size_t mapBytes = align(cells * sizeof(int32_t)), qBytes = align((size_t)shares * sizeof(unsigned long long)),
-               vBytes = align((size_t)shares * sizeof(uint32_t));
   // the workspace is in use until the last launch is enqueued: the device's launcher lock keeps rm_release_workspaces away
   std::unique_lock<std::mutex> lock;
   if (int st = lock_current_device(lock)) return st;
   void *mem = nullptr;
-  if (int st = stream_workspace(kWsMesh, hs, mapBytes + qBytes + vBytes, &mem)) return st;
-  int32_t *cellVertex = static_cast<int32_t *>(mem);
-  unsigned long long *qOff = reinterpret_cast<unsigned long long *>(static_cast<char *>(mem) + mapBytes);
-  uint32_t *vOff = reinterpret_cast<uint32_t *>(static_cast<char *>(mem) + mapBytes + qBytes);
+  if (int st = stream_workspace(kWsMesh, hs, mesh_workspace(cells, shares, nullptr).bytes, &mem)) return st;
+  const MeshWs ws = mesh_workspace(cells, shares, mem);
   const Lattice L{d_dist, nx, ny, nz, iso};
-  hipLaunchKernelGGL(mesh_count_kernel, dim3(shares), dim3(64), 0, hs, L, numPoints, vOff, qOff);
-  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(1024), 0, hs, vOff, qOff, shares, d_counts);
+  hipLaunchKernelGGL(mesh_count_kernel, dim3(shares), dim3(64), 0, hs, L, numPoints, ws.vOff, ws.qOff);
+  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(1024), 0, hs, ws.vOff, ws.qOff, shares, d_counts);
   if (maxVertices > 0 || maxQuads > 0)
     hipLaunchKernelGGL(mesh_vertices_kernel, dim3(shares), dim3(64), 0, hs, L, d_objectId, numPoints, origin[0], origin[1], origin[2],
-                       step[0], step[1], step[2], vOff, maxVertices, d_vertices, d_vertexObject, cellVertex);
+                       step[0], step[1], step[2], ws.vOff, maxVertices, d_vertices, d_vertexObject, ws.cellVertex);
   if (maxQuads > 0)
-    hipLaunchKernelGGL(mesh_quads_kernel, dim3(shares), dim3(64), 0, hs, L, numPoints, qOff, maxQuads, cellVertex,
+    hipLaunchKernelGGL(mesh_quads_kernel, dim3(shares), dim3(64), 0, hs, L, numPoints, ws.qOff, maxQuads, ws.cellVertex,
                        d_quads);
   HIP_OK(hipGetLastError());
   return RM_OK;

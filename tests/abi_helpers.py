@@ -105,7 +105,7 @@ def vec3(v):
     return (C.c_float * 3)(*v) if v is not None else None
 
 
-# ---------------------------------------------------------------- the lattice arguments that rm_field_check.h refuses
+# ---------------------------------------------------------------- the lattice arguments that rm_lattice.h refuses
 inf, nan = float("inf"), float("nan")
 BAD_STEPS = ((nan, 1, 1), (1, inf, 1), (1, 1, 0.0), (-0.5, 1, 1), (1, -0.0, 1), (1, 1, -inf))
 BAD_ORIGINS = ((nan, 0, 0), (0, inf, 0), (0, 0, -inf))

@@ -1,4 +1,4 @@
-// rm_field_trace on the CPU, serially, through the very function the kernels of rm_field_handle.hip call
+// rm_field_trace on the CPU, serially, through the very function the handle kernels of rm_field.hip call
 // (raymarcher_amd/csrc/rm_field_skip.h).  A stand-alone program, so that it can run under the host sanitizers.  The block map and the
 // coarse level are built here by a plain loop over the list.
 //   rm_field_handle_cpu <query file> <result file>

@@ -151,6 +151,22 @@ def test_mesh_of_oracle_lattices_equals_the_spec(renderer, name, dims, iso):
         assert (dist < iso).sum() > 100, "the lattice holds too few points inside the bulb"
 
 
+def test_mesh_of_more_than_1024_shares_carries_the_scan_into_its_second_round(renderer):
+    """mesh_scan_kernel scans 1024 shares per round and carries both totals into the next.  128 × 128 × 72 points are 1152 shares of
+    1024: a sphere of radius 0.55 around the middle of the box has active cells on both sides of share 1024, so the vertices and
+    quads numbered behind it are right only with the carry."""
+    nx, ny, nz = 128, 128, 72
+    origin, step = np.array([-1.0, -1.0, -0.5], np.float32), np.array([2 / 127, 2 / 127, 1 / 71], np.float32)
+    x, y, z = (origin[a] + np.arange(n, dtype=np.float32) * step[a] for a, n in enumerate((nx, ny, nz)))
+    dist = np.sqrt(z[:, None, None] ** 2 + y[None, :, None] ** 2 + x[None, None, :] ** 2) - np.float32(0.55)
+    assert dist.dtype == np.float32 and dist.shape == (nz, ny, nx) and dist.size == 1152 * 1024
+    ids = (np.arange(dist.size, dtype=np.int32) % 7).reshape(dist.shape)
+    want = assert_mesh(renderer, dist, ids, origin, step, 0.0, "128 × 128 × 72 sphere")
+    assert (len(want["vertices"]), len(want["quads"])) == (22976, 22856)
+    share = ((want["cells"][:, 2] * ny + want["cells"][:, 1]) * nx + want["cells"][:, 0]) // 1024
+    assert ((share < 1024).sum(), (share >= 1024).sum()) == (20736, 2240), "active cells on both sides of the scan's second round"
+
+
 @pytest.mark.parametrize("name", sorted(V.handmade()))
 def test_mesh_of_handmade_lattices_equals_the_spec(renderer, name):
     dist, ids, origin, step, iso = V.handmade()[name]
