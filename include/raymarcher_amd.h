@@ -981,6 +981,62 @@ int  rm_field_trace(const RmField *field, const RmRay *d_rays, int numRays, floa
                     unsigned mode /* RM_TRACE_CLOSEST, | RM_TRACE_NO_NORMAL, or RM_TRACE_OCCLUSION */, RmRayHit *d_hits, void *stream);
 
 /*
+ * rm_field_ambient — hemisphere occlusion and the bent normal at POINTS of a baked lattice, one launch: numDirs rays per point from a
+ * table of directions, each marched by rm_field_trace's own march, summed inside the kernel by a fixed binary32 tree.  No device
+ * memory proportional to numPoints·numDirs exists at any time: the caller who composes the same from rm_field_trace writes 32 B per
+ * ray and reads 32 B per ray back.  rm_hemisphere_directions fills a table on the host.
+ * d_points: numPoints float4 in device memory (w is not read); d_normals: as many float4 (w is not read) or NULL, the lattice's own
+ * gradient then; d_dirs: numSets·numDirs float4 in device memory, (x, y, z) in the point's frame with z along its normal and w the
+ * ray's weight; point i uses set i mod numSets.  d_out: numPoints RmAmbient.  Asynchronous on `stream`.
+ * Definition for point i, bit for bit: every operation below is ONE binary32 operation, unfused, in the order written, division and
+ * sqrt correctly rounded (rm_field_ambient.h is this text in C++).  p = points[i].xyz.  The record starts as zeros.
+ * a. A non-finite component of p: hits = RM_RAY_INVALID, the rest zeros.
+ * b. The normal n.  With d_normals: normals[i].xyz as given — unit length is the caller's duty —; a non-finite component or all three
+ *    zero: hits = RM_RAY_INVALID.  Without: s = rm_field_sample's record at p; RM_FIELD_OUTSIDE or RM_FIELD_UNLISTED there goes to hits;
+ *    otherwise len = sqrt((gx·gx + gy·gy) + gz·gz) and n = g / len, component by component; len zero or not finite: hits =
+ *    RM_RAY_INVALID.  In every refused case the rest of the record stays zero, `normal` included.
+ * c. The frame (Duff et al. 2017, "Building an orthonormal basis, revisited"): s = copysign(1, n.z); a = −1 / (s + n.z); b = (n.x·n.y)·a;
+ *    T = (1 + (s·(n.x·n.x))·a, s·b, (−s)·n.x); B = (b, s + (n.y·n.y)·a, −n.y).  No direction is singular: n.z = −1 gives a = 0.5.
+ * d. For k = 0 … numDirs − 1: e = dirs[(i mod numSets)·numDirs + k]; d[c] = (e.x·T[c] + e.y·B[c]) + e.z·n[c]; o[c] = p[c] + n[c]·bias;
+ *    h = rm_field_trace's march of the ray (o, tMax = maxDistance, d) with iso and maxSteps — RM_AMBIENT_SOFT: its RM_TRACE_OCCLUSION
+ *    march; RM_AMBIENT_HARD: its RM_TRACE_NO_NORMAL march.  v = 0 if h.objectId != −1 (a hit, an invalid ray); on a miss SOFT has v =
+ *    h.t > 0 ? h.t : 0 — the penumbra factor starts at 1 and only falls, so v lies in [0, 1] on a finite lattice and no infinity or
+ *    NaN enters a sum — and HARD has v = 1.  A hit (objectId neither −1 nor RM_RAY_INVALID) adds 1 to hits.  c = e.w·v, and leaf k =
+ *    (c·d.x, c·d.y, c·d.z, c).
+ * e. The four components are summed over the leaves by the pairwise tree, level by level: s[j] = s[2j] + s[2j + 1], numDirs a power
+ *    of two.  bent = the first three sums, not normalised; visibility = the fourth; normal = the n used; hits = the count.
+ * f. The contract covers finite tables and lattices.  A non-finite d_dirs entry may put a NaN into the sums; its sign and payload
+ *    are not specified.
+ * bias moves the origins off the surface and must exceed iso by a margin: at p + bias·n the field is about bias, and a first sample
+ * below iso is a hit at t = 0.  With rm_hemisphere_directions' table, visibility is the cosine-weighted open fraction of the
+ * hemisphere within maxDistance.
+ * rm_hemisphere_directions(numDirs, numSets, out4), host only: for set s and index k, in double and then rounded to float, u = (k +
+ * 0.5) / numDirs, r = sqrt(u), z = sqrt(1 − u), φ = 2π·frac(k·0.6180339887498949 + s·0.7548776662466927), entry (r cos φ, r sin φ, z,
+ * 1 / numDirs): a cosine-weighted spiral, one rotation per set.  It refuses numDirs and numSets as below, then a null out4.
+ * rm_field_ambient refuses, in this order, RM_ERR_INVALID_ARGUMENT: a null or bad handle; a negative numPoints; numDirs not a power of
+ * two in 1 … RM_MAX_AMBIENT_DIRS; numSets below 1 or numSets·numDirs above RM_MAX_AMBIENT_TABLE; bias, maxDistance or iso not finite or
+ * maxDistance below 0; maxSteps outside 0 … RM_MAX_FIELD_STEPS; mode bits other than RM_AMBIENT_HARD.  Then numPoints == 0: RM_OK,
+ * nothing read or written.  Then a null d_points, d_dirs or d_out; a misaligned one (16 bytes), d_normals included when it is given;
+ * — from here on with HIP calls — another device current than the handle's; an array that is not device memory.
+ * Schedule: ONE launch, 256-lane workgroups, (point, direction) pairs flattened over lanes so that lane mod numDirs is the direction:
+ * up to 64 directions a wave holds 64 / numDirs points and folds each segment by log2(numDirs) xor-shuffle levels; 128 and 256 are 2
+ * or 4 passes of 64 by one wave, folded by the same tree.  binary32 addition is commutative in every bit, so the butterfly has the
+ * tree's words.  The table, at most 16 KB, is staged into LDS once per workgroup; a record is two 16-byte stores.  Not a render
+ * launch: rm_debug_last_path() keeps its value.  Added without a change of RM_ABI_VERSION: bindings detect it by symbol lookup.
+ */
+typedef struct RmAmbient { float bent[3]; float visibility; float normal[3]; int32_t hits; } RmAmbient;   /* 32 bytes */
+#define RM_AMBIENT_SOFT 0u      /* every ray is rm_field_trace's RM_TRACE_OCCLUSION march */
+#define RM_AMBIENT_HARD 1u      /* every ray is its RM_TRACE_NO_NORMAL march: visible or not */
+#define RM_MAX_AMBIENT_DIRS 256
+#define RM_MAX_AMBIENT_TABLE 1024   /* numSets * numDirs */
+int rm_hemisphere_directions(int numDirs, int numSets, float *out4 /* host, numSets*numDirs float4 */);
+int rm_field_ambient(const RmField *field, const float *d_points /* float4 each, w not read */,
+                     const float *d_normals /* float4 each, w not read; may be NULL */, int numPoints,
+                     const float *d_dirs /* float4 each: local x, y, z, weight */, int numDirs, int numSets,
+                     float bias, float maxDistance, float iso, int maxSteps, unsigned mode,
+                     RmAmbient *d_out, void *stream);
+
+/*
  * rm_shade_points — what the renderer thinks of POINTS the caller already has: the scene's distance and object at each point, its
  * normal, its ambient occlusion and its shaded colour, with the point optionally projected onto the iso-surface first (no reference
  * counterpart: the shader reaches a surface point only at the end of a ray of its own).  The points counterpart of rm_trace_rays /

@@ -84,6 +84,9 @@ SIGNATURES = {
     "rm_field_destroy": (None, [C.c_void_p]),
     "rm_field_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rm_field_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
+    "rm_hemisphere_directions": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "rm_field_ambient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                   C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "rm_points_settings_default": (None, [_P(abi.RmPointsSettings)]),
     "rm_shade_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(abi.RmPointsSettings), _P(abi.RmObject), C.c_int, _P(abi.RmLight),
                                   C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p,

@@ -148,6 +148,15 @@ class RmFieldSample(C.Structure):
 RM_FIELD_OUTSIDE, RM_FIELD_UNLISTED = -5, -6  # RmFieldSample.objectId of a point outside the lattice's box / in an unlisted block
 RM_MAX_FIELD_STEPS = 65536  # march steps of one rm_sdf_trace / rm_sdf_trace_blocks call
 RM_FIELD_PENUMBRA_K = 8.0  # the k of the penumbra tracker of rm_field_trace's RM_TRACE_OCCLUSION
+
+
+class RmAmbient(C.Structure):
+    _fields_ = [("bent", f32 * 3), ("visibility", f32), ("normal", f32 * 3), ("hits", i32)]
+
+
+RM_AMBIENT_SOFT, RM_AMBIENT_HARD = 0, 1  # mode of rm_field_ambient: the penumbra factor of every ray, or visible or not
+RM_MAX_AMBIENT_DIRS = 256  # directions per point of one rm_field_ambient call, a power of two
+RM_MAX_AMBIENT_TABLE = 1024  # numSets * numDirs of its table
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

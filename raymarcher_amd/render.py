@@ -389,19 +389,32 @@ def write_ply_ex(path, vertices, quads, colours=None, normals=None):
     return path
 
 
+def hemisphere_directions(num_dirs, num_sets=1):
+    """rm_hemisphere_directions: the table LatticeField.ambient builds for an int `directions` → float32 (num_sets·num_dirs, 4)
+    numpy array of (x, y, z, weight) rows in a point's frame, z along its normal: a cosine-weighted spiral of num_dirs unit
+    directions (a power of two, at most abi.RM_MAX_AMBIENT_DIRS) with weight 1 / num_dirs, turned by another angle in each set."""
+    import numpy as np
+    table = np.zeros((max(int(num_sets), 0) * max(int(num_dirs), 0), 4), dtype=np.float32)
+    check(lib().rm_hemisphere_directions(int(num_dirs), int(num_sets), C.c_void_p(table.ctypes.data)))
+    return table
+
+
 class LatticeField:
     """An RmField handle (Renderer.lattice_field, lattice_field_blocks, scene_field): one lattice queried again and again.  It keeps
     references to the tensors the handle borrows.  A context manager; close() is idempotent, and the handle is destroyed on garbage
     collection at the latest.  Synchronise the streams that still run its queries before closing it."""
 
-    def __init__(self, renderer, handle, borrowed):
-        self._r, self._h, self._borrowed = renderer, handle, borrowed
+    def __init__(self, renderer, handle, borrowed, box=None):
+        """box: (origin, step, cells per axis) of the lattice, which ambient's defaults are taken from."""
+        self._r, self._h, self._borrowed, self._box = renderer, handle, borrowed, box
+        self._tables = {}  # ambient's tables on the device, per (dirs, sets)
 
     def close(self):
         h, self._h = self._h, None
         if h:
             lib().rm_field_destroy(h)
         self._borrowed = None
+        self._tables = {}
 
     def __enter__(self):
         return self
@@ -445,6 +458,58 @@ class LatticeField:
         check(lib().rm_field_trace(h, C.c_void_p(rays.data_ptr()) if n else None, n, float(iso), int(max_steps), bits,
                                    C.c_void_p(hits.data_ptr()) if n else None, r._stream()))
         return hits[:, 0:3], hits[:, 3], hits[:, 4:7], hits[:, 7].view(t.int32)
+
+    def ambient(self, points, normals=None, directions=16, sets=1, max_distance=None, bias=None, iso=0.001, max_steps=64, soft=True, out=None):
+        """rm_field_ambient: hemisphere occlusion and the bent normal at points of the lattice, `directions` rays per point marched
+        and summed in ONE launch, with no per-ray memory → (bent, visibility, normal, hits): float32 (n, 3), (n), (n, 3) and int32
+        (n), views of ONE float32 (n, 8) device tensor of RmAmbient rows (`out`, if given).  points as sample takes them; normals:
+        the same shapes, unit vectors, or None for the lattice's own normalised gradient.  directions: an int, a power of two up to
+        abi.RM_MAX_AMBIENT_DIRS — hemisphere_directions(directions, sets), built once per (directions, sets) and kept on the handle
+        — or a ready float32 (sets·dirs, 4) table of (x, y, z, weight) rows in the point's frame, z along the normal; point i uses
+        set i mod sets.  soft: every ray contributes its penumbra factor (trace's "occlusion" march); otherwise 1 or 0.  visibility
+        is the weighted sum over the rays, with the built table the cosine-weighted open fraction of the hemisphere; bent is the
+        same sum of the directions, not normalised; hits counts the rays that hit, or is abi.RM_RAY_INVALID, abi.RM_FIELD_OUTSIDE or
+        abi.RM_FIELD_UNLISTED beside zeros for a point that has no normal.  max_distance (None: the diagonal of the lattice's box)
+        is every ray's tMax.  bias (None: twice the largest lattice step) moves the ray origins along the normal and must exceed
+        iso: at p + bias·n the field is about bias, and a ray whose first sample lies below iso is a hit at once.  The definition,
+        bit for bit, is in include/raymarcher_amd.h."""
+        r, h = self._r, self._handle()
+        t = r.torch
+        pts = r._points(points, "points")
+        n = pts.shape[0]
+        nrm = None if normals is None else r._points(normals, "normals")
+        if nrm is not None and nrm.shape[0] != n:
+            raise ValueError("one normal per point")
+        sets = int(sets)
+        if isinstance(directions, int):
+            dirs = int(directions)
+            key = (dirs, sets)
+            if key not in self._tables:
+                self._tables[key] = t.from_numpy(hemisphere_directions(dirs, sets)).to(r.device)
+            table = self._tables[key]
+        else:
+            table = directions if t.is_tensor(directions) else t.from_numpy(_np_f32(directions))
+            if table.dim() != 2 or table.shape[1] != 4 or table.dtype != t.float32 or sets < 1 or table.shape[0] % sets != 0:
+                raise ValueError("directions must be an int or a float32 table of shape (sets * dirs, 4)")
+            table = table.to(r.device).contiguous()
+            dirs = table.shape[0] // sets
+        if (bias is None or max_distance is None) and self._box is None:
+            raise ValueError("this LatticeField does not know its lattice: give bias and max_distance")
+        if bias is None:
+            bias = 2.0 * max(float(v) for v in self._box[1])
+        if max_distance is None:
+            max_distance = sum((float(v) * c) ** 2 for v, c in zip(self._box[1], self._box[2])) ** 0.5
+        rec = r._out(out, (n, 8), t.float32)
+        check(lib().rm_field_ambient(h, C.c_void_p(pts.data_ptr()) if n else None, C.c_void_p(nrm.data_ptr()) if nrm is not None and n else None, n,
+                                     C.c_void_p(table.data_ptr()) if table.numel() else None, dirs, sets, float(bias), float(max_distance),
+                                     float(iso), int(max_steps), abi.RM_AMBIENT_SOFT if soft else abi.RM_AMBIENT_HARD,
+                                     C.c_void_p(rec.data_ptr()) if n else None, r._stream()))
+        return rec[:, 0:3], rec[:, 3], rec[:, 4:7], rec[:, 7].view(t.int32)
+
+
+def _np_f32(a):
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 class Renderer:
@@ -1074,6 +1139,24 @@ class Renderer:
         return self._bake(tables, settings, self._scene_mesh_sparse(tables, settings, resolution, iso, bounds, (outside, inside)), iso, project,
                           ao, colour)
 
+    def bake_mesh_pruned_ambient(self, tables, settings, resolution, ambient=16, iso=0.001, bounds=None, project=2, ao=True, colour=True,
+                                 outside=4.0, inside=None):
+        """bake_mesh_pruned with a LatticeField.ambient pass of `ambient` hemisphere directions over it: the field is baked again with
+        scene_field_pruned at the same resolution, the projected vertices and their normals go through ambient(directions=ambient),
+        and the 8-bit colours are multiplied by its visibility (rounded to nearest) → bake_mesh_pruned's tuple with those colours.
+        ambient=None, or colour=False, is bake_mesh_pruned as it is."""
+        baked = self.bake_mesh_pruned(tables, settings, resolution, iso, bounds, project, ao, colour, outside, inside)
+        if ambient is None or baked[5] is None:
+            return baked
+        t = self.torch
+        verts, quads, object_id, normal, aos, rgb = baked
+        dist, obj, bl, blocks, origin, step = self.scene_field_pruned(tables, settings, resolution, iso, bounds, outside, inside)
+        with self.lattice_field_blocks(dist, bl, blocks, origin, step, obj) as field:
+            visibility = field.ambient(verts, normal, directions=int(ambient), iso=iso)[1]
+            shaded = t.clamp(t.round(rgb.to(t.float32) * visibility.clamp(0.0, 1.0)[:, None]), 0.0, 255.0).to(t.uint8)
+            t.cuda.current_stream(self.device).synchronize()  # the handle is destroyed on the way out
+        return verts, quads, object_id, normal, aos, shaded
+
     # ---- lattice queries: a baked lattice read back at points and marched by rays (include/raymarcher_amd.h) ----
     def _lattice(self, grid, ids, shape_text, shape_ok):
         t = self.torch
@@ -1189,7 +1272,7 @@ class Renderer:
         nz, ny, nx = grid.shape
         h = C.c_void_p()
         check(lib().rm_field_create(gp, ip, nx, ny, nz, _vec3(origin, "origin"), _vec3(step, "step"), C.byref(h)))
-        return LatticeField(self, h, (grid, ids))
+        return LatticeField(self, h, (grid, ids), (tuple(origin), tuple(step), (nx - 1, ny - 1, nz - 1)))
 
     def lattice_field_blocks(self, grid_blocks, block_list, blocks, origin, step, ids=None):
         """rm_field_create_blocks: a handle on a block-sparse lattice → LatticeField.  grid_blocks, block_list, blocks and ids as
@@ -1202,7 +1285,7 @@ class Renderer:
         h = C.c_void_p()
         check(lib().rm_field_create_blocks(gp, ip, C.c_void_p(bl.data_ptr()) if nb else None, nb, mx, my, mz, _vec3(origin, "origin"),
                                            _vec3(step, "step"), self._stream(), C.byref(h)))
-        return LatticeField(self, h, (grid_blocks, ids))
+        return LatticeField(self, h, (grid_blocks, ids), (tuple(origin), tuple(step), (8 * mx, 8 * my, 8 * mz)))
 
     def scene_field(self, tables, settings, resolution, iso=0.001, bounds=None):
         """scene_field_sparse's lattice behind a handle → LatticeField: the scene's distance field baked where its surface is, ready
