@@ -533,6 +533,67 @@ int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageW
                          const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s,
                          const RmResources *res /* may be NULL */, float *d_rgba, float *d_bright /* may be NULL */, void *stream);
 /*
+ * rm_light_probes — SH9 radiance probes, shaded and reduced in ONE launch: numDirs rays from each of numProbes positions along the
+ * rows of a direction table, each shaded by rm_shade_rays' own code, its colour and hit flag multiplied into the row's nine basis
+ * values and summed per probe inside the kernel by a fixed binary32 tree.  For a grid of irradiance probes that lights moving objects
+ * in a static scene.  No device memory proportional to numProbes·numDirs exists at any time: the caller who composes the same from
+ * rm_shade_rays writes 32 B per ray, reads 16 B per ray back and projects them in passes of their own, for 160 B per probe.
+ * rm_sphere_directions fills a table on the host.
+ * d_positions: numProbes float4 in device memory (w is not read); d_dirs: numSets·numDirs RmProbeDir in device memory; d_out:
+ * numProbes RmLightProbe in device memory (all three 16-byte aligned); the tables, g, s and res (may be NULL) are host memory, copied
+ * before return.  Asynchronous on `stream`.
+ * Definition, bit for bit.  Probe i uses rows (i mod numSets)·numDirs + k, for k = 0 … numDirs − 1; numDirs is a power of two in
+ * 1 … RM_MAX_PROBE_DIRS.  For row e: let (c, hit) belong to the ray origin = position_i, dir = e.dir (used as given, NOT normalised),
+ * with the call's `far`: c is the r, g, b that rm_shade_rays stores for that ray, and hit is whether main's primary march found a
+ * surface — observable as rm_trace_rays(RM_TRACE_CLOSEST | RM_TRACE_NO_NORMAL) with tMax = far giving objectId >= 0.  A row whose dir
+ * is invalid by rm_shade_rays' rule (a non-finite component, or all three zero) gives c = 0, hit = false, and evaluates nothing.  Let
+ * h = hit ? 1.0f : 0.0f.  The leaf of row k is leaf[j] = (e.basis[j]·c.r, e.basis[j]·c.g, e.basis[j]·c.b, e.basis[j]·h) for j = 0 … 8,
+ * each ONE binary32 multiplication, unfused.  sh[j] is the pairwise tree over the leaf index, level by level: s[m] = s[2m] + s[2m + 1],
+ * which is rm_field_ambient's tree.  hits is the number of rays with hit.  The record's `reserved` is stored as zeros.
+ * A probe with a non-finite position stores hits = RM_RAY_INVALID and zeros in every other word, and evaluates nothing.  Positions and
+ * rows are device data: the host cannot refuse them.  `reserved` and `pad` of a row are not read.  The result of a probe does not
+ * depend on which other probes share its call.  The contract covers finite tables: a non-finite basis value may put a NaN into the
+ * sums; its sign and payload are not specified.
+ * The w channel is the projection of "something is there within far": 1 − that is the probe's directional sky visibility.
+ * rm_sphere_directions(numDirs, numSets, out), host only (no HIP call): for set s and index k, in binary64 and then rounded once to
+ * binary32, z = 1 − (2k + 1) / numDirs, r = sqrt(1 − z²), φ = 2π·frac(k·0.6180339887498949 + s·0.7548776662466927), dir = (r cos φ,
+ * r sin φ, z) — spherical Fibonacci points, one rotation about z per set — and basis[j] = (4π / numDirs)·Y_j(dir), evaluated on the
+ * binary64 direction and rounded once: the Monte-Carlo weight of a uniform direction times the nine real spherical harmonics of
+ * bands 0 to 2 in the usual order,
+ *   Y0 = sqrt(1/4π);  Y1 = sqrt(3/4π)·y;  Y2 = sqrt(3/4π)·z;  Y3 = sqrt(3/4π)·x;  Y4 = sqrt(15/4π)·x·y;  Y5 = sqrt(15/4π)·y·z;
+ *   Y6 = sqrt(5/16π)·(3z² − 1);  Y7 = sqrt(15/4π)·x·z;  Y8 = sqrt(15/16π)·(x² − y²).
+ * reserved and pad are written as zeros.  With that table sh[j].rgb are the probe's radiance coefficients and Σ_j A_j·sh[j]·Y_j(n), A =
+ * π, 2π/3, π/4 per band, its irradiance (Ramamoorthi & Hanrahan 2001).  A caller may pass any table of their own — an ambient cube,
+ * fewer bands, importance-weighted directions: the kernel only multiplies and adds.  It refuses numDirs and numSets as below, then a
+ * null out.
+ * rm_light_probes refuses, in this order and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: numProbes < 0; numDirs
+ * not a power of two in 1 … RM_MAX_PROBE_DIRS; numSets below 1 or numSets·numDirs above RM_MAX_PROBE_TABLE.  Then numProbes == 0:
+ * RM_OK, nothing read or written.  Then RM_ERR_INVALID_ARGUMENT: numProbes·numDirs above INT_MAX; null g or s, a null table with a
+ * positive count or a negative count; far NaN, negative or infinite; RM_ERR_UNSUPPORTED: RM_FEAT_TERRAIN, RM_FEAT_CLOUD or
+ * RM_FEAT_SEA (rays through the layers are not defined here), g->isTwoD; then rm_render_res's checks of the scene with its statuses,
+ * as rm_shade_rays has them; RM_ERR_INVALID_ARGUMENT: a null or misaligned d_positions, d_dirs or d_out (16 bytes); an array or a
+ * sampler's pixels that are not device memory.
+ * Schedule: ONE launch of the probe kernel of the scene's class (the twelve classes of the render kernels; rm_debug_last_path() = 21,
+ * rm_debug_last_split() = 0), 256-lane workgroups, (probe, row) pairs flattened over lanes so that lane mod numDirs is the row: up to
+ * 64 directions a wave holds 64 / numDirs probes and folds each segment by log2(numDirs) xor-shuffle levels over the 36 words of the
+ * leaf; more are numDirs / 64 passes of 64 by one wave on one probe, whose sums join in leaf order with one pending sum per level.
+ * binary32 addition is commutative in every bit, so the butterfly has the tree's words.  A lane reads its own 64-byte row; a record
+ * is ten 16-byte stores.  One slot of the batch ring of scene blocks; no tuner, tile-order or workspace state is read or changed, and
+ * nothing is allocated.  With rm_set_timing(1) it counts as one launch, all stage 1.  The rays of a wave share an origin or
+ * neighbouring ones and go every way: a wave costs what its longest ray costs.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmProbeDir   { float dir[3]; float reserved; float basis[9]; float pad[3]; } RmProbeDir;   /* 64 bytes */
+typedef struct RmLightProbe { float sh[9][4]; int32_t hits; int32_t reserved[3]; } RmLightProbe;           /* 160 bytes */
+#define RM_MAX_PROBE_DIRS  1024
+#define RM_MAX_PROBE_TABLE 4096   /* numSets * numDirs */
+int rm_sphere_directions(int numDirs, int numSets, RmProbeDir *out /* host */);
+int rm_light_probes(const float *d_positions /* float4 each, w not read */, int numProbes,
+                    const RmProbeDir *d_dirs, int numDirs, int numSets, float far,
+                    const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                    const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */,
+                    RmLightProbe *d_out, void *stream);
+/*
  * rm_trace_rays_layers — rm_trace_rays THROUGH terrain and sea: the closest VISIBLE SURFACE along each ray, by the rules main
  * applies to its own rays.  For keeping a fly-through camera above the terrain, and for picking on a landscape.  The arguments are
  * rm_trace_rays' with imageWidth (as above, >= 1 in every call) behind numRays.
@@ -1250,8 +1311,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
  * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
- * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned (none of them is a value rm_set_kernel_path
- * takes).  The value belongs to the DEVICE, not to the calling thread or stream: it reports the device's most recent launch,
+ * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned, 21 = a launch of rm_light_probes (none of them is a
+ * value rm_set_kernel_path takes).  The value belongs to the DEVICE, not to the calling thread or stream: it reports the device's most recent launch,
  * whichever thread made it. */
 int rm_debug_last_path(void);
 /* Tests: how many tiles the most recent render launch on the current device rendered one light per workgroup ("light split": the

@@ -157,6 +157,17 @@ class RmAmbient(C.Structure):
 RM_AMBIENT_SOFT, RM_AMBIENT_HARD = 0, 1  # mode of rm_field_ambient: the penumbra factor of every ray, or visible or not
 RM_MAX_AMBIENT_DIRS = 256  # directions per point of one rm_field_ambient call, a power of two
 RM_MAX_AMBIENT_TABLE = 1024  # numSets * numDirs of its table
+class RmProbeDir(C.Structure):
+    _fields_ = [("dir", f32 * 3), ("reserved", f32), ("basis", f32 * 9), ("pad", f32 * 3)]
+
+
+class RmLightProbe(C.Structure):
+    _fields_ = [("sh", (f32 * 4) * 9), ("hits", i32), ("reserved", i32 * 3)]
+
+
+RM_MAX_PROBE_DIRS = 1024  # directions per probe of one rm_light_probes call, a power of two
+RM_MAX_PROBE_TABLE = 4096  # numSets * numDirs of its table
+RM_PATH_LIGHT_PROBES = 21  # rm_debug_last_path() behind a launch of rm_light_probes
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

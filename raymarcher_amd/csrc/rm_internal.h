@@ -123,6 +123,11 @@ int launch_trace_kernel(const void *sb, int bulbClass, bool occlusion, bool noNo
 // numRays float4 of colour into d_rgba and, when d_bright is not null, of bright values into d_bright.
 int launch_shade_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const void *d_rays, int numRays, float *d_rgba,
                         float *d_bright, hipStream_t stream);
+// The light-probe kernels (rm_light_probes.hip, rm_light_probes; a translation unit of its own for the same reason): the launch of
+// light_probes_kernel<bulbClass, env, tex, sec, numDirs above 64> over the ONE staged SceneBlock `sb`, (probe, row) pairs flattened
+// over lanes — numProbes float4 from d_positions, numSets·numDirs RmProbeDir from d_dirs, numProbes RmLightProbe into d_out.
+int launch_probes_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const float *d_positions, int numProbes,
+                         const void *d_dirs, int numDirs, int numSets, void *d_out, hipStream_t stream);
 // The layer kernels (rm_layers.hip, rm_shade_rays_layers and rm_trace_rays_layers; a translation unit of its own for the same
 // reason), for the calls that have a layer bit — a call without one goes to the two launches above.  shade_rays_layers_kernel<tex,
 // sec> (the env class; imageWidth feeds the sea normal's epsilon) and trace_layers_kernel<bulbClass> (closest mode only) over the
@@ -186,7 +191,7 @@ constexpr int render_waves(int bulb, bool env, bool tex, bool sec) {
 // Julia seed, or the plain form that SceneBlock::bulbPlain describes.
 constexpr int kBulbGeneral = 1, kBulbPlain = 2;
 // The production kernel classes: the twelve <BULB, ENV, TEX, SEC> that render_kernel, render_ss_kernel, adaptive_refine_kernel,
-// render_acc_kernel, render_anim_kernel and shade_rays_kernel are instantiated with.  Layers and samplers (env, tex: the table walk,
+// render_acc_kernel, render_anim_kernel, shade_rays_kernel and light_probes_kernel are instantiated with.  Layers and samplers (env, tex: the table walk,
 // whatever the table holds) first, then the bulb class, then the plain table walk, each with main's secondary rays compiled in
 // only where they can fire (sec).
 template <int BULB, bool ENV, bool TEX, bool SEC>

@@ -2,11 +2,12 @@
 // probes.  Each checks its arguments, stages one scene block and launches one kernel of another unit through the launcher's
 // stage_block_launch (rm_launch.h), which also records the path and the timing: nothing here reads or writes a tuner, the tile
 // order or the wavefront state, and nothing here sees the launcher's slots, rings or device state.  Host code only: the kernels
-// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_layers.hip, rm_points.hip, rm_volume.hip, rm_blocks.hip
-// and rm_probe.hip (declared in rm_internal.h, the lattice family's in rm_lattice.h), the scene prep that needs no GPU in rm_frame.cpp.
+// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_light_probes.hip, rm_layers.hip, rm_points.hip,
+// rm_volume.hip, rm_blocks.hip and rm_probe.hip (declared in rm_internal.h, the lattice family's in rm_lattice.h), the scene prep that needs no GPU in rm_frame.cpp.
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cmath>
 #include <cstdint>
 
 #include "rm_internal.h"
@@ -136,6 +137,70 @@ int launch_shade(const ShadeCall &c) {
     if (c.layers && (c.s->features & (RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA)))
       return launch_shade_layers_kernel(sb, fc.textured, fc.secondary, c.d_rays, c.numRays, c.imageWidth, c.d_rgba, c.d_bright, c.stream);
     return launch_shade_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, c.d_rgba, c.d_bright, c.stream);
+  });
+}
+
+// ---- light probes: rays from a position and a table row, shaded and summed (rm_light_probes) -------------------------------------
+// rm_light_probes (the header has the definition): rm_shade_rays for the rays of numProbes positions times the numDirs rows of a
+// direction table, each colour and hit flag multiplied into its row's nine basis values and summed per probe inside the kernel.
+// ProbesCall stands beside ShadeCall; its checks run in check_shade's order with its words where they overlap, every one but the
+// last ahead of the first HIP call: numProbes (negative), the table's shape (numDirs, then numSets), numProbes == 0 (RM_OK), the
+// rays of the call beyond INT_MAX, the scene pointers and counts, far, the layers and the 2-D mode, validate_scene, the arrays
+// (null, alignment of the float4 accesses), and whether they, and the resources' pixels, are device memory.
+// Staging is launch_shade's: stage_block_launch, one block, the caller's lights and resources and a camera that is zeros but for
+// initialFar = far; the class is the frame's.  Then ONE launch of light_probes_kernel (rm_light_probes.hip), path 21: no tuner,
+// tile-order or workspace state is read or changed and nothing is allocated.
+struct ProbesCall {
+  const float *d_positions; int numProbes; const RmProbeDir *d_dirs; int numDirs, numSets; float far;
+  const RmObject *objs; int numObjects; const RmLight *lights; int numLights;
+  const RmGlobals *g; const RmSettings *s; const RmResources &res;
+  RmLightProbe *d_out; hipStream_t stream;
+};
+// What rm_light_probes and rm_sphere_directions refuse about the table's shape; no HIP call.
+int check_probe_table(int numDirs, int numSets) {
+  if (numDirs < 1 || numDirs > RM_MAX_PROBE_DIRS || (numDirs & (numDirs - 1)) != 0) {
+    set_error("numDirs must be a power of two, 1 … RM_MAX_PROBE_DIRS (1024)");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (numSets < 1 || (long long)numSets * numDirs > RM_MAX_PROBE_TABLE) {
+    set_error("numSets must be at least 1 and numSets * numDirs at most RM_MAX_PROBE_TABLE (4096)");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  return RM_OK;
+}
+int check_probes(const ProbesCall &c, const RmCamera &cam) {
+  if (c.numProbes < 0) { set_error("negative numProbes"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = check_probe_table(c.numDirs, c.numSets);
+  if (st != RM_OK || c.numProbes == 0) return st;
+  if ((long long)c.numProbes * c.numDirs > INT_MAX) { set_error("numProbes * numDirs exceeds INT_MAX rays"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.numLights > 0 && !c.lights) || c.numObjects < 0 || c.numLights < 0) {
+    set_error("null scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (!(c.far >= 0.0f) || c.far == __builtin_inff()) { set_error("far must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
+  st = refuse_layers(c.s, "rm_light_probes shades rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
+  if ((st = validate_scene(&cam, c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, c.res)) != RM_OK) return st;
+  if (!c.d_positions || !c.d_dirs || !c.d_out) { set_error("null d_positions, d_dirs or d_out"); return RM_ERR_INVALID_ARGUMENT; }
+  if (((uintptr_t)c.d_positions | (uintptr_t)c.d_dirs | (uintptr_t)c.d_out) & 15u) {
+    set_error("d_positions, d_dirs and d_out must be 16-byte aligned");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if ((st = require_device_pointers({{"d_positions", c.d_positions}, {"d_dirs", c.d_dirs}, {"d_out", c.d_out}})) != RM_OK) return st;
+  return check_device_pointers(c.res, nullptr, nullptr);
+}
+int launch_probes(const ProbesCall &c) {
+  RmCamera cam{};
+  cam.initialFar = c.far;
+  int st = check_probes(c, cam);
+  if (st != RM_OK || c.numProbes == 0) return st;
+  const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
+  const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  BlockCall b{c.objs, c.numObjects, c.g, c.s, c.stream, 21};
+  b.cam = &cam; b.lights = c.lights; b.numLights = c.numLights; b.res = &c.res;
+  return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
+    return launch_probes_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_positions, c.numProbes, c.d_dirs, c.numDirs,
+                                c.numSets, c.d_out, c.stream);
   });
 }
 
@@ -336,6 +401,35 @@ int rm_shade_rays_layers(const RmRay *d_rays, int numRays, float far, int imageW
 int rm_trace_rays_layers(const RmRay *d_rays, int numRays, int imageWidth, const RmObject *objs, int numObjects, const RmGlobals *g,
                          const RmSettings *s, unsigned mode, RmRayHit *d_hits, void *stream) {
   return launch_trace(TraceCall{d_rays, numRays, objs, numObjects, g, s, mode, d_hits, static_cast<hipStream_t>(stream), true, imageWidth});
+}
+
+int rm_light_probes(const float *d_positions, int numProbes, const RmProbeDir *d_dirs, int numDirs, int numSets, float far,
+                    const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g, const RmSettings *s,
+                    const RmResources *res, RmLightProbe *d_out, void *stream) {
+  return launch_probes(ProbesCall{d_positions, numProbes, d_dirs, numDirs, numSets, far, objs, numObjects, lights, numLights, g, s,
+                                  res ? *res : kNoResources, d_out, static_cast<hipStream_t>(stream)});
+}
+
+// rm_sphere_directions (the header has the definition): host only, binary64 rounded once.  Spherical Fibonacci points and, per
+// point, 4π / numDirs times the nine real spherical harmonics of bands 0 to 2.
+int rm_sphere_directions(int numDirs, int numSets, RmProbeDir *out) {
+  if (int st = check_probe_table(numDirs, numSets)) return st;
+  if (!out) { set_error("null out"); return RM_ERR_INVALID_ARGUMENT; }
+  const double K = (double)numDirs, pi = 3.14159265358979323846, twoPi = 2.0 * pi, w = 4.0 * pi / K;
+  const double c0 = std::sqrt(1.0 / (4.0 * pi)), c1 = std::sqrt(3.0 / (4.0 * pi)), c2 = std::sqrt(15.0 / (4.0 * pi)),
+               c20 = std::sqrt(5.0 / (16.0 * pi)), c22 = std::sqrt(15.0 / (16.0 * pi));
+  for (int s = 0; s < numSets; s++)
+    for (int k = 0; k < numDirs; k++) {
+      const double z = 1.0 - (2.0 * (double)k + 1.0) / K, r = std::sqrt(1.0 - z * z);
+      const double turn = (double)k * 0.6180339887498949 + (double)s * 0.7548776662466927, phi = twoPi * (turn - std::floor(turn));
+      const double x = r * std::cos(phi), y = r * std::sin(phi);
+      const double Y[9] = {c0, c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z), c20 * (3.0 * (z * z) - 1.0), c2 * (x * z), c22 * (x * x - y * y)};
+      RmProbeDir &e = out[(size_t)s * (size_t)numDirs + (size_t)k];
+      e.dir[0] = (float)x, e.dir[1] = (float)y, e.dir[2] = (float)z, e.reserved = 0.0f;
+      for (int j = 0; j < 9; j++) e.basis[j] = (float)(w * Y[j]);
+      e.pad[0] = e.pad[1] = e.pad[2] = 0.0f;
+    }
+  return RM_OK;
 }
 
 void rm_points_settings_default(RmPointsSettings *ps) {

@@ -399,6 +399,36 @@ def hemisphere_directions(num_dirs, num_sets=1):
     return table
 
 
+def sphere_directions(num_dirs, num_sets=1):
+    """rm_sphere_directions: the table Renderer.light_probes builds for an int `directions` → float32 (num_sets·num_dirs, 16) numpy
+    array of RmProbeDir rows (dir.xyz, 0, the nine basis values, 0, 0, 0): num_dirs spherical Fibonacci directions (a power of two,
+    at most abi.RM_MAX_PROBE_DIRS), turned about z by another angle in each set, and per direction 4π / num_dirs times the nine real
+    spherical harmonics of bands 0 to 2 there."""
+    import numpy as np
+    table = np.zeros((max(int(num_sets), 0) * max(int(num_dirs), 0), 16), dtype=np.float32)
+    check(lib().rm_sphere_directions(int(num_dirs), int(num_sets), C.c_void_p(table.ctypes.data)))
+    return table
+
+
+def sh_irradiance(sh, normals):
+    """The irradiance that SH9 radiance coefficients give a surface with unit normal n: the clamped-cosine convolution
+    E(n) = Σ_j A_band(j)·sh_j·Y_j(n) with A = π, 2π/3, π/4 for bands 0, 1, 2 (Ramamoorthi & Hanrahan 2001).  sh: (..., 9, c) —
+    light_probes' `sh`, whose fourth channel convolves like the others —, normals: (..., 3), broadcast against sh's leading
+    dimensions → (..., c).  Torch tensors or NumPy arrays, in their own precision; plain array arithmetic, not bit-defined."""
+    import math
+    x, y, z = normals[..., 0], normals[..., 1], normals[..., 2]
+    c1, c2 = math.sqrt(3.0 / (4.0 * math.pi)), math.sqrt(15.0 / (4.0 * math.pi))
+    a0, a1, a2 = math.pi, 2.0 * math.pi / 3.0, math.pi / 4.0
+    weights = (a0 * math.sqrt(1.0 / (4.0 * math.pi)) * (x * 0 + 1), a1 * c1 * y, a1 * c1 * z, a1 * c1 * x, a2 * c2 * (x * y), a2 * c2 * (y * z),
+               a2 * math.sqrt(5.0 / (16.0 * math.pi)) * (3.0 * (z * z) - 1.0), a2 * c2 * (x * z),
+               a2 * math.sqrt(15.0 / (16.0 * math.pi)) * (x * x - y * y))
+    total = None
+    for j, w in enumerate(weights):
+        term = sh[..., j, :] * w[..., None]
+        total = term if total is None else total + term
+    return total
+
+
 class LatticeField:
     """An RmField handle (Renderer.lattice_field, lattice_field_blocks, scene_field): one lattice queried again and again.  It keeps
     references to the tensors the handle borrows.  A context manager; close() is idempotent, and the handle is destroyed on garbage
@@ -529,6 +559,7 @@ class Renderer:
         # device tensor that an enqueued launch reads alive.
         self._tex_cache = {}
         self._tex_lock = threading.Lock()
+        self._probe_tables = {}  # light_probes' tables on the device, per (directions, sets); under the same lock
 
     def _out(self, a, shape, dtype, name="out"):
         """A fresh tensor of `shape` and `dtype` on this device, or the caller's `a` once it is checked to be exactly that (the
@@ -771,6 +802,41 @@ class Renderer:
                                   C.byref(res), C.c_void_p(out.data_ptr()), C.c_void_p(br.data_ptr()) if bright else None,
                                   self._stream()))
         return (out, br) if bright else out
+
+    def light_probes(self, tables, settings, positions, directions=256, sets=1, far=None, table=None, out=None):
+        """rm_light_probes: SH9 radiance probes at `positions`, `directions` rays each shaded as shade_rays shades them and summed per
+        probe in ONE launch → (sh, hits): float32 (n, 9, 4) and int32 (n), views of ONE float32 (n, 40) device tensor of RmLightProbe
+        rows (`out`, if given).  positions: (n, 3) or (n, 4) float32, a numpy array, which is uploaded, or a tensor.  The table is
+        sphere_directions(directions, sets) — directions a power of two, at most abi.RM_MAX_PROBE_DIRS; probe i uses set i mod sets —
+        built once per (directions, sets) and kept on the renderer, or the caller's `table`: float32 (sets·directions, 16) rows of
+        RmProbeDir, numpy or a tensor on this device, any basis values (an ambient cube, fewer bands, importance weights).  far: the
+        one march limit of the call, None = tables.camera.initialFar.  sh[:, j, 0:3] are the radiance coefficients with
+        sphere_directions' table (sh_irradiance turns them into irradiance), sh[:, j, 3] the same projection of "the ray hit
+        something"; hits: the rays that hit, abi.RM_RAY_INVALID for a probe with a non-finite position (zeros in sh).  Terrain,
+        clouds and sea are refused.  The definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        dirs, sets = int(directions), int(sets)
+        pts = self._points(positions, "positions")
+        n = pts.shape[0]
+        if table is None:
+            key = (dirs, sets)
+            with self._tex_lock:
+                if key not in self._probe_tables:
+                    self._probe_tables[key] = t.from_numpy(sphere_directions(dirs, sets)).to(self.device)
+                table = self._probe_tables[key]
+        else:
+            if not t.is_tensor(table):
+                table = t.from_numpy(_np_f32(table)).to(self.device)
+            if (table.dim() != 2 or tuple(table.shape) != (sets * dirs, 16) or table.dtype != t.float32 or not table.is_contiguous()
+                    or table.device != self.device):
+                raise ValueError(f"table must be a contiguous float32 tensor of shape (sets * directions, 16) on {self.device}")
+        rec = self._out(out, (n, 40), t.float32)
+        res, _keep = self._resources(tables)
+        check(lib().rm_light_probes(C.c_void_p(pts.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr()), dirs, sets,
+                                    tables.camera.initialFar if far is None else far, tables.objects, tables.num_objects, tables.lights,
+                                    tables.num_lights, C.byref(tables.globals_), C.byref(settings), C.byref(res),
+                                    C.c_void_p(rec.data_ptr()) if n else None, self._stream()))
+        return rec[:, 0:36].view(n, 9, 4), rec[:, 36].view(t.int32)
 
     def render_panorama(self, tables, settings, W, H, position, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), far=None):
         """A W×H equirectangular panorama of the scene from `position` → float32 (H, W, 4), row 0 = bottom: panorama_rays shaded
