@@ -594,6 +594,63 @@ int rm_light_probes(const float *d_positions /* float4 each, w not read */, int 
                     const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */,
                     RmLightProbe *d_out, void *stream);
 /*
+ * rm_light_grid_irradiance — light at POINTS from a grid of rm_light_probes' SH9 records, ONE launch: the query half of the probes.
+ * Per point the eight probes around it are blended trilinearly, probes inside geometry (hits < 0) are left out, DDGI's backface
+ * term (Majercik et al. 2019) keeps light from behind the surface away, and each probe's radiance is convolved with the clamped
+ * cosine lobe of the point's normal (Ramamoorthi & Hanrahan 2001).  For the hit points of a G-buffer, mesh vertices and particles.
+ * No memory proportional to numPoints exists but the result: the caller who composes the same in array arithmetic gathers eight
+ * probes per point, 1152 B, and blends in passes of their own.
+ * d_probes: dims[0]·dims[1]·dims[2] RmLightProbe in device memory, exactly as rm_light_probes stores them, consumed where they lie:
+ * the probe at (i, j, k) is at index i + dims[0]·(j + dims[1]·k) and its world position is origin_a + (float)index_a·step_a,
+ * unfused.  Byte offsets are 64-bit.  d_points, d_normals: numPoints float4 each in device memory (w is not read); d_out: numPoints
+ * RmGridLight in device memory (all four 16-byte aligned); dims, origin and step are host memory, copied before return.
+ * Asynchronous on `stream`.
+ * Definition, bit for bit.  Every operation is ONE binary32 operation as written, unfused; division and sqrt are the correctly
+ * rounded ones (rm_light_grid.h is this text in C++).  Per point p with normal n:
+ *  1. p or n with a non-finite component, or n all zeros: the record is probes = RM_RAY_INVALID and zeros elsewhere, and nothing is
+ *     evaluated.  n is used as given, NOT normalised (rm_light_probes' rule for its directions).
+ *  2. Per axis a: u_a = (p_a − origin_a) / step_a, clamped to [0, dims_a − 1]: a u_a not greater than 0 becomes +0, a u_a above
+ *     dims_a − 1 becomes dims_a − 1, an infinite u_a clamps like any other — a point outside the box takes the border's light, it is
+ *     not refused.  cell_a = min((int)floor(u_a), dims_a − 2), f_a = u_a − (float)cell_a.
+ *  3. Corner c = cx + 2·cy + 4·cz is probe cell + (cx, cy, cz); its trilinear weight is t_c = (wx·wy)·wz with w_a = c_a ? f_a : 1 − f_a.
+ *  4. A corner probe is valid iff its hits >= 0.  Of an invalid probe only hits is read: its sh words may hold anything, NaNs
+ *     included, and never reach a sum.
+ *  5. With RM_LIGHT_GRID_FACING, per valid corner: d = probePosition − p per component, len = sqrt((dx·dx + dy·dy) + dz·dz);
+ *     len == 0 gives face = 1, otherwise cosv = ((dx·nx + dy·ny) + dz·nz) / len, b = (cosv + 1)·0.5, face = b·b + 0.2.  Without the
+ *     flag face = 1 and none of this is evaluated.  w_c = t_c·face for a valid probe and +0 for an invalid one.
+ *  6. W = ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).  probes = the number of valid corners with w_c > 0.  probes == 0: the
+ *     record is probes = 0, weight = W and zeros in e, and no sh word is read.
+ *  7. The cosine-lobe weights of n, once per point, from constants evaluated in binary64 and rounded once to binary32,
+ *     K0 = π·sqrt(1/4π), K1 = (2π/3)·sqrt(3/4π), K2 = (π/4)·sqrt(15/4π), K6 = (π/4)·sqrt(5/16π), K8 = (π/4)·sqrt(15/16π):
+ *     k0 = K0; k1 = K1·y; k2 = K1·z; k3 = K1·x; k4 = K2·(x·y); k5 = K2·(y·z); k6 = K6·(3·(z·z) − 1); k7 = K2·(x·z);
+ *     k8 = K8·(x·x − y·y), with (x, y, z) = n — rm_sphere_directions' order of Y0 … Y8.
+ *  8. Per valid corner and channel ch = 0 … 3: E_c[ch] = k0·sh[0][ch], then E_c[ch] = E_c[ch] + k_j·sh[j][ch] for j = 1 … 8 in
+ *     order.  e[ch] = T(w_c·E_c[ch]) / W, T the three-level tree of step 6 over the corners; an invalid corner's leaf is +0, a
+ *     valid corner of weight zero has the leaf 0·E_c[ch].  e is not clamped: SH ringing may make it negative.  e[3] is the same
+ *     convolution of "something is there within far", so 1 − e[3]/π is the cosine-weighted sky visibility at the point.
+ *  9. weight = W; reserved is stored as zeros.
+ * A point's record does not depend on which points share its call.  The contract covers finite probe records: a non-finite
+ * coefficient of a valid probe, or a point so far off that step 5 overflows, may put a NaN into the sums; its sign and payload are
+ * not specified.
+ * rm_light_grid_irradiance refuses, in this order and all but the last before any HIP call: RM_ERR_INVALID_ARGUMENT: numPoints < 0;
+ * null dims, origin or step; a dimension below 2 or above RM_MAX_LIGHT_GRID_DIM; dims[0]·dims[1]·dims[2] above
+ * RM_MAX_LIGHT_GRID_PROBES; a non-finite origin component; a step component that is not finite or not greater than 0; flag bits
+ * other than RM_LIGHT_GRID_FACING.  Then numPoints == 0: RM_OK, nothing read or written.  Then RM_ERR_INVALID_ARGUMENT: a null or
+ * misaligned d_probes, d_points, d_normals or d_out (16 bytes); last, an array that is not device memory.
+ * Schedule: ONE launch, one lane per point, 256-lane workgroups.  A lane reads its two 16-byte inputs, the hits word of each of its
+ * eight corners, then the nine float4 of every valid corner, keeps four sums per corner and stores the record as two 16-byte
+ * stores.  This is not a render launch: like the field queries, rm_debug_last_path() keeps its value, rm_set_timing does not time
+ * it, no scene block, tuner or workspace state is touched, and nothing is allocated.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+typedef struct RmGridLight { float e[4]; float weight; int32_t probes; int32_t reserved[2]; } RmGridLight;   /* 32 bytes */
+#define RM_LIGHT_GRID_FACING 1u
+#define RM_MAX_LIGHT_GRID_DIM    1024
+#define RM_MAX_LIGHT_GRID_PROBES (1 << 24)
+int rm_light_grid_irradiance(const RmLightProbe *d_probes, const int dims[3], const float origin[3], const float step[3],
+                             const float *d_points /* float4 each, w not read */, const float *d_normals /* float4 each, w not read */,
+                             int numPoints, uint32_t flags, RmGridLight *d_out, void *stream);
+/*
  * rm_trace_rays_layers — rm_trace_rays THROUGH terrain and sea: the closest VISIBLE SURFACE along each ray, by the rules main
  * applies to its own rays.  For keeping a fly-through camera above the terrain, and for picking on a landscape.  The arguments are
  * rm_trace_rays' with imageWidth (as above, >= 1 in every call) behind numRays.

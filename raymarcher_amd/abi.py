@@ -168,6 +168,15 @@ class RmLightProbe(C.Structure):
 RM_MAX_PROBE_DIRS = 1024  # directions per probe of one rm_light_probes call, a power of two
 RM_MAX_PROBE_TABLE = 4096  # numSets * numDirs of its table
 RM_PATH_LIGHT_PROBES = 21  # rm_debug_last_path() behind a launch of rm_light_probes
+
+
+class RmGridLight(C.Structure):
+    _fields_ = [("e", f32 * 4), ("weight", f32), ("probes", i32), ("reserved", i32 * 2)]
+
+
+RM_LIGHT_GRID_FACING = 1  # flag of rm_light_grid_irradiance: DDGI's backface term on every corner's weight
+RM_MAX_LIGHT_GRID_DIM = 1024  # probes per axis of the grid of one rm_light_grid_irradiance call, at least 2
+RM_MAX_LIGHT_GRID_PROBES = 1 << 24  # and probes of the whole grid
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

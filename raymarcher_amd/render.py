@@ -542,6 +542,81 @@ def _np_f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _grid_dims(dims):
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 2:
+        raise ValueError("a light grid has at least 2 probes along every axis")
+    return nx, ny, nz
+
+
+def light_grid_positions(origin, step, dims):
+    """The world positions of a light grid's probes → float32 (nx·ny·nz, 4) numpy array, w = 0, x fastest: probe (i, j, k) is row
+    i + nx·(j + ny·k) at origin + (i, j, k)·step, each coordinate one float32 multiplication and one float32 addition — the formula
+    of rm_light_grid_irradiance (include/raymarcher_amd.h), so probes baked at these positions are where the lookup thinks they are."""
+    import numpy as np
+    nx, ny, nz = _grid_dims(dims)
+    o, s = np.asarray(origin, dtype=np.float32).reshape(3), np.asarray(step, dtype=np.float32).reshape(3)
+    axes = [o[a] + np.arange(n, dtype=np.float32) * s[a] for a, n in enumerate((nx, ny, nz))]
+    out = np.zeros((nz, ny, nx, 4), dtype=np.float32)
+    out[..., 0], out[..., 1], out[..., 2] = axes[0][None, None, :], axes[1][None, :, None], axes[2][:, None, None]
+    return out.reshape(nx * ny * nz, 4)
+
+
+class LightGrid:
+    """A grid of SH9 radiance probes and the box it spans (Renderer.light_grid bakes one; LightGrid(renderer, probes, origin, step,
+    dims) wraps a caller's own records): `probes` is the float32 (nx·ny·nz, 40) tensor of RmLightProbe rows as light_probes stores
+    them, probe (i, j, k) at row i + nx·(j + ny·k) and at origin + (i, j, k)·step (light_grid_positions).  A probe whose hits is
+    negative (abi.RM_RAY_INVALID) is left out of every lookup.  A numpy array is uploaded, a tensor on the renderer's device is kept
+    as it is."""
+
+    def __init__(self, renderer, probes, origin, step, dims):
+        import numpy as np
+        t = renderer.torch
+        self.dims = _grid_dims(dims)
+        if not t.is_tensor(probes):
+            probes = t.from_numpy(_np_f32(probes)).to(renderer.device)
+        count = self.dims[0] * self.dims[1] * self.dims[2]
+        if (tuple(probes.shape) != (count, 40) or probes.dtype != t.float32 or not probes.is_contiguous() or probes.device != renderer.device):
+            raise ValueError(f"probes must be a contiguous float32 tensor of shape ({count}, 40) on {renderer.device}")
+        self._r, self.probes = renderer, probes
+        self.origin, self.step = np.asarray(origin, dtype=np.float32).reshape(3).copy(), np.asarray(step, dtype=np.float32).reshape(3).copy()
+
+    def irradiance(self, points, normals, facing=True, out=None):
+        """rm_light_grid_irradiance: the grid's light at `points` on surfaces with `normals`, ONE launch → (e, weight, probes): float32
+        (n, 4), float32 (n) and int32 (n), views of ONE float32 (n, 8) device tensor of RmGridLight rows (`out`, if given).  points,
+        normals: (n, 3) or (n, 4) float32, numpy arrays, which are uploaded, or tensors, used in place; normals are used as given
+        (unit vectors are meant).  e[:, 0:3] is the irradiance — the eight probes around the point blended trilinearly, invalid probes
+        left out, each convolved with the normal's cosine lobe; times albedo / π it is the diffuse light a surface sends on — and
+        1 − e[:, 3] / π the cosine-weighted sky visibility.  facing: DDGI's backface term, which takes weight from probes behind the
+        surface.  weight: the sum of the eight weights; probes: how many corners took part, 0 (zeros in e) where none did,
+        abi.RM_RAY_INVALID for a non-finite point or a non-finite or zero normal.  A point outside the box takes the border's light.
+        The definition, bit for bit, is in include/raymarcher_amd.h."""
+        r = self._r
+        t = r.torch
+        pts, nrm = r._points(points, "points"), r._points(normals, "normals")
+        n = pts.shape[0]
+        if nrm.shape[0] != n:
+            raise ValueError("one normal per point")
+        rec = r._out(out, (n, 8), t.float32)
+        check(lib().rm_light_grid_irradiance(C.c_void_p(self.probes.data_ptr()), (C.c_int * 3)(*self.dims), _vec3(self.origin, "origin"),
+                                             _vec3(self.step, "step"), C.c_void_p(pts.data_ptr()) if n else None,
+                                             C.c_void_p(nrm.data_ptr()) if n else None, n, abi.RM_LIGHT_GRID_FACING if facing else 0,
+                                             C.c_void_p(rec.data_ptr()) if n else None, r._stream()))
+        return rec[:, 0:4], rec[:, 4], rec[:, 5].view(t.int32)
+
+    def light_gbuffer(self, normal_depth, position, facing=True):
+        """irradiance at the primary hits of render_gbuffer(position=True): normal_depth and position, float32 (N, H, W, 4) as it
+        returns them, used in place → float32 (N, H, W, 4), e per pixel (a view of the (N·H·W, 8) result).  A miss has a zero normal,
+        which makes it an invalid point: zeros."""
+        t = self._r.torch
+        if (normal_depth.dim() != 4 or normal_depth.shape[3] != 4 or tuple(position.shape) != tuple(normal_depth.shape)
+                or normal_depth.dtype != t.float32 or position.dtype != t.float32):
+            raise ValueError("normal_depth and position must be float32 tensors of the same shape (N, H, W, 4)")
+        N, H, W, _ = normal_depth.shape
+        e, _, _ = self.irradiance(position.reshape(-1, 4), normal_depth.reshape(-1, 4), facing=facing)
+        return e.view(N, H, W, 4)
+
+
 class Renderer:
     """Launches the HIP raymarch on one GPU; outputs are torch tensors on that device."""
 
@@ -837,6 +912,48 @@ class Renderer:
                                     tables.num_lights, C.byref(tables.globals_), C.byref(settings), C.byref(res),
                                     C.c_void_p(rec.data_ptr()) if n else None, self._stream()))
         return rec[:, 0:36].view(n, 9, 4), rec[:, 36].view(t.int32)
+
+    def light_grid(self, tables, settings, dims, bounds=None, directions=256, sets=1, far=None, mask_inside=0.0):
+        """A LightGrid of dims = (nx, ny, nz) probes over `bounds` — (lo, hi), or None for mesh_bounds(tables) —, the first probe at
+        lo and the last at hi: ONE light_probes call at light_grid_positions(origin, step, dims) with `directions`, `sets` and `far` as
+        light_probes takes them.  mask_inside (None: no masking): one sdf_grid call on the same origin, step and dims, and every probe
+        whose scene distance is below it gets hits = abi.RM_RAY_INVALID, so that LightGrid.irradiance leaves it out — 0.0 masks the
+        probes inside geometry, whose rays see the inside of a surface."""
+        import numpy as np
+        t = self.torch
+        nx, ny, nz = _grid_dims(dims)
+        lo, hi = mesh_bounds(tables) if bounds is None else bounds
+        lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+        if not np.isfinite(hi - lo).all() or not (hi > lo).all():
+            raise ValueError("bounds must be (lo, hi) with three finite components each and lo < hi")
+        origin, step = lo.astype(np.float32), ((hi - lo) / (np.array([nx, ny, nz]) - 1)).astype(np.float32)
+        rec = t.empty((nx * ny * nz, 40), dtype=t.float32, device=self.device)
+        _, hits = self.light_probes(tables, settings, light_grid_positions(origin, step, (nx, ny, nz)), directions=directions, sets=sets,
+                                    far=far, out=rec)
+        if mask_inside is not None:
+            dist = self.sdf_grid(tables, settings, origin, step, (nx, ny, nz))
+            hits[dist.reshape(-1) < float(mask_inside)] = abi.RM_RAY_INVALID
+        return LightGrid(self, rec, origin, step, (nx, ny, nz))
+
+    def render_indirect(self, tables, settings, W, H, grid, cameras=None, strength=1.0):
+        """render_batch's frames plus one bounce of diffuse light from a LightGrid → float32 (N, H, W, 4): on every pixel whose
+        primary ray hits an object, strength · kd · cDiffuse[object_id] · e.rgb / π is added to the colour, e = grid.light_gbuffer
+        of one render_gbuffer(position=True) through the same cameras (None: the scene's own, N = 1).  Plain torch arithmetic around
+        the three launches, NOT bit-defined.  The albedo is the object's cDiffuse alone: textures and the fractals' trap colours are
+        not part of it, and reflections and refractions get no indirect light."""
+        import math
+        t = self.torch
+        cams = [tables.camera] if cameras is None else cameras
+        frames = self.render_batch(tables, settings, W, H, cams)
+        if tables.num_objects == 0:
+            return frames
+        nd, ids, pos = self.render_gbuffer(tables, settings, W, H, cams, position=True)
+        e = grid.light_gbuffer(nd, pos)
+        albedo = t.tensor([list(tables.objects[i].cDiffuse) for i in range(tables.num_objects)], dtype=t.float32, device=self.device)
+        hit = ids >= 0
+        bounce = albedo[ids.clamp(min=0).long()] * e[..., 0:3] * (float(strength) * float(tables.globals_.kd) / math.pi)
+        frames[..., 0:3] += t.where(hit[..., None], bounce, t.zeros_like(bounce))
+        return frames
 
     def render_panorama(self, tables, settings, W, H, position, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), far=None):
         """A W×H equirectangular panorama of the scene from `position` → float32 (H, W, 4), row 0 = bottom: panorama_rays shaded
