@@ -651,6 +651,81 @@ int rm_light_grid_irradiance(const RmLightProbe *d_probes, const int dims[3], co
                              const float *d_points /* float4 each, w not read */, const float *d_normals /* float4 each, w not read */,
                              int numPoints, uint32_t flags, RmGridLight *d_out, void *stream);
 /*
+ * rm_light_probes_depth, rm_probe_depth_weights, rm_light_grid_irradiance_visible — a visibility term per probe, so that a light
+ * grid does not leak through walls: DDGI's depth moments (Majercik et al. 2019).  A trilinear blend takes light from probes on the
+ * far side of an occluder, and RM_LIGHT_GRID_FACING only removes probes behind the SURFACE.  Per probe an 8×8 octahedral map holds
+ * the mean distance to the scene and the mean squared distance per direction; the lookup weighs every corner by a Chebyshev bound
+ * of the chance that the point is seen from the probe.
+ *
+ * The map.  Texel x = tx + 8·ty (tx, ty = 0 … 7) has the centre direction c_x = octDecode(((tx + 0.5)/8)·2 − 1, ((ty + 0.5)/8)·2 − 1),
+ * octDecode(u, v) = normalize(X, Y, Z) with Z = 1 − |u| − |v| and (X, Y) = (u, v) for Z >= 0, ((1 − |v|)·sign(u), (1 − |u|)·sign(v))
+ * for Z < 0, sign(±0) = +1: the unit octahedron |x| + |y| + |z| = 1 unfolded onto [−1, 1]², upper half in the inner diamond.
+ *
+ * rm_probe_depth_weights(dirs, numDirs, numSets, sharpness, out), host only (no HIP call): out is numSets·numDirs rows of
+ * RM_PROBE_DEPTH_TEXELS floats, row s·numDirs + k the weights of table row k of set s on the 64 texels.  In binary64 from the
+ * binary32 dir: d = dir/|dir| with |dir| = sqrt((x·x + y·y) + z·z), dot = (c_x.x·d.x + c_x.y·d.y) + c_x.z·d.z, raw = pow(max(0, dot),
+ * sharpness) (pow(0, 0) = 1), sum = Σ raw over the set's rows in ascending k, out = raw/sum rounded ONCE to binary32.  A texel whose
+ * sum is 0 (few directions, a high sharpness) gives the row with the largest dot weight 1 and the others +0, ties to the lowest k:
+ * no texel is ever empty.  A row whose dir is invalid by rm_shade_rays' rule gets +0 on every texel and takes no part in sums or
+ * ties.  It refuses numDirs and numSets as rm_sphere_directions does, then a null dirs or out, then a sharpness that is not finite
+ * or is below 0.
+ *
+ * rm_light_probes_depth — the bake, ONE launch.  d_positions, d_dirs, numDirs, numSets: as rm_light_probes takes them, the same
+ * table (the basis of a row is not read); d_weights: numSets·numDirs rows of 64 floats in device memory, 16-byte aligned —
+ * rm_probe_depth_weights' or the caller's own; d_out: numProbes RmProbeDepth in device memory, 16-byte aligned.  Lights and
+ * resources are no arguments: a march reads no material.  Asynchronous on `stream`.
+ * Definition, bit for bit.  Probe i uses rows (i mod numSets)·numDirs + k, for k = 0 … numDirs − 1.  r_k is the t that
+ * rm_trace_rays(RM_TRACE_CLOSEST | RM_TRACE_NO_NORMAL) stores for the ray origin = position_i, dir = row.dir (used as given),
+ * tMax = maxDistance: the hit's t, or maxDistance on a miss.  A row whose dir is invalid gives r_k = +0 and evaluates nothing.  Per
+ * texel x: moments[x][0] = T_k(w[k][x]·r_k) and moments[x][1] = T_k(w[k][x]·(r_k·r_k)), every product ONE binary32 multiplication,
+ * unfused, T the pairwise tree of rm_light_probes over k, level by level: s[m] = s[2m] + s[2m + 1].  A probe with a non-finite
+ * position stores 512 bytes of zeros and evaluates nothing.  A probe's record does not depend on which probes share its call.  The
+ * contract covers finite weights: a non-finite one may put a NaN into the sums; its sign and payload are not specified.
+ * It refuses in rm_light_probes' order with maxDistance in the place of far, all but the last before any HIP call:
+ * RM_ERR_INVALID_ARGUMENT: numProbes < 0; numDirs not a power of two in 1 … RM_MAX_PROBE_DIRS; numSets below 1 or numSets·numDirs
+ * above RM_MAX_PROBE_TABLE.  Then numProbes == 0: RM_OK.  Then RM_ERR_INVALID_ARGUMENT: numProbes·numDirs above INT_MAX; null g or s,
+ * a null table with a positive count or a negative count; maxDistance NaN, infinite or not greater than 0; RM_ERR_UNSUPPORTED:
+ * RM_FEAT_TERRAIN, RM_FEAT_CLOUD or RM_FEAT_SEA, g->isTwoD; then rm_trace_rays' checks of the object table;
+ * RM_ERR_INVALID_ARGUMENT: a null or misaligned d_positions, d_dirs, d_weights or d_out (16 bytes); an array that is not device memory.
+ * Schedule: ONE launch of the depth kernel of the table's march class (the table walk, the general Mandelbulb, its plain form;
+ * rm_debug_last_path() = 22, rm_debug_last_split() = 0), 256-lane workgroups.  The march is rm_light_probes' flattening: lane mod
+ * numDirs is the row, 64 / numDirs probes per wave up to 64 directions, passes of 64 above.  Then the wave leaves its 64 (r, r·r) in
+ * LDS and lane x becomes texel x: it reads row k's weights — one 256-byte line per row for the wave —, forms the two leaves and folds
+ * the leaves of the pass in tree order by itself; a serial walk adds the same operands in the same pairs as the tree, so it has
+ * the tree's words.  The passes of a probe join with one pending pair per level and lane.  A record is 512 contiguous bytes of one
+ * wave.  One slot of the batch ring of scene blocks; no tuner, tile-order or workspace state is read or changed, nothing is allocated.
+ *
+ * rm_light_grid_irradiance_visible — the lookup, ONE launch, one lane per point: rm_light_grid_irradiance's arguments with d_depth —
+ * the grid's RmProbeDepth records, index as d_probes — behind d_probes and normalBias behind flags.  Its steps 1 to 9 with one step
+ * between 5 and 6; binary32, unfused, division and sqrt correctly rounded (rm_light_grid.h is this text in C++).
+ *  5a. Once per point q = p + normalBias·n per component, one multiplication and one addition.  Per valid corner: v = q −
+ *      probePosition per component, r = sqrt((vx·vx + vy·vy) + vz·vz).  r == 0 gives vis = 1 and no depth word is read.  Otherwise
+ *      l1 = (|vx| + |vy|) + |vz|, (ox, oy) = (vx/l1, vy/l1), and for vz < 0 the fold (ox, oy) = ((1 − |oy|)·sign(ox), (1 − |ox|)·sign(oy))
+ *      of the unfolded pair, sign(±0) = +1.  Per axis u_a = o_a·4 + 3.5 clamped to [0, 7] (a u_a not greater than 0 becomes +0),
+ *      i_a = min((int)floor(u_a), 6), f_a = u_a − (float)i_a.  With a, b, c, d the texels (ix, iy), (ix + 1, iy), (ix, iy + 1),
+ *      (ix + 1, iy + 1): m = (a·(1 − fx) + b·fx)·(1 − fy) + (c·(1 − fx) + d·fx)·fy on moments[·][0], m2 the same on moments[·][1].
+ *      The blend clamps at the map's edge: the octahedral wrap is NOT followed, directions near the z = 0 seam blend with the edge
+ *      texel alone.  r <= m gives vis = 1.  Otherwise var = |m2 − m·m|, dd = r − m, den = var + dd·dd, c = var/den (1 for den == 0),
+ *      vis = max((c·c)·c, RM_LIGHT_GRID_VIS_FLOOR).  w_c = (t_c·face)·vis.  Of an invalid probe neither sh nor depth words are read.
+ * Depth records whose every mean is at least every r give vis = 1 exactly, and x·1.0f is x: the record then equals
+ * rm_light_grid_irradiance's IN EVERY WORD.  The floor keeps a point that no probe sees lit by all of them rather than black.
+ * It refuses as rm_light_grid_irradiance does, a non-finite normalBias behind the step, d_depth beside d_probes.  Not a render
+ * launch: rm_debug_last_path() keeps its value, no scene block, tuner or workspace state is touched, nothing is allocated.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_PROBE_DEPTH_TEXELS 64
+typedef struct RmProbeDepth { float moments[64][2]; } RmProbeDepth;   /* 512 bytes: mean, mean of squares per texel */
+#define RM_LIGHT_GRID_VIS_FLOOR 1.0e-6f
+int rm_probe_depth_weights(const RmProbeDir *dirs /* host */, int numDirs, int numSets, float sharpness, float *out /* host */);
+int rm_light_probes_depth(const float *d_positions /* float4 each, w not read */, int numProbes, const RmProbeDir *d_dirs,
+                          const float *d_weights, int numDirs, int numSets, float maxDistance,
+                          const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                          RmProbeDepth *d_out, void *stream);
+int rm_light_grid_irradiance_visible(const RmLightProbe *d_probes, const RmProbeDepth *d_depth, const int dims[3],
+                                     const float origin[3], const float step[3],
+                                     const float *d_points /* float4 each, w not read */, const float *d_normals /* float4 each, w not read */,
+                                     int numPoints, uint32_t flags, float normalBias, RmGridLight *d_out, void *stream);
+/*
  * rm_trace_rays_layers — rm_trace_rays THROUGH terrain and sea: the closest VISIBLE SURFACE along each ray, by the rules main
  * applies to its own rays.  For keeping a fly-through camera above the terrain, and for picking on a landscape.  The arguments are
  * rm_trace_rays' with imageWidth (as above, >= 1 in every call) behind numRays.
@@ -1368,7 +1443,7 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
  * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
- * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned, 21 = a launch of rm_light_probes (none of them is a
+ * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned, 21 = a launch of rm_light_probes, 22 = a launch of rm_light_probes_depth (none of them is a
  * value rm_set_kernel_path takes).  The value belongs to the DEVICE, not to the calling thread or stream: it reports the device's most recent launch,
  * whichever thread made it. */
 int rm_debug_last_path(void);

@@ -5,5 +5,5 @@ streams / torch.distributed.  The renderer itself is raymarcher_amd/lib/librayma
 """
 from . import abi  # noqa: F401
 from ._lib import LIB_PATH, RaymarcherError, lib  # noqa: F401
-from .render import (LatticeField, LightGrid, Renderer, Scene, SceneTables, camera_rays, hemisphere_directions, light_grid_positions, mesh_bounds, panorama_rays,  # noqa: F401
+from .render import (LatticeField, LightGrid, Renderer, Scene, SceneTables, camera_rays, hemisphere_directions, light_grid_positions, mesh_bounds, panorama_rays, probe_depth_weights,  # noqa: F401
                      sh_irradiance, sphere_directions, tile_order, translated_objects, write_ply, write_ply_ex)

@@ -92,6 +92,11 @@ SIGNATURES = {
                                   C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p]),
     "rm_light_grid_irradiance": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rm_probe_depth_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "rm_light_probes_depth": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, _P(abi.RmObject), C.c_int,
+                                        _P(abi.RmGlobals), _P(abi.RmSettings), C.c_void_p, C.c_void_p]),
+    "rm_light_grid_irradiance_visible": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int), _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
     "rm_points_settings_default": (None, [_P(abi.RmPointsSettings)]),
     "rm_shade_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(abi.RmPointsSettings), _P(abi.RmObject), C.c_int, _P(abi.RmLight),
                                   C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p,

@@ -177,6 +177,15 @@ class RmGridLight(C.Structure):
 RM_LIGHT_GRID_FACING = 1  # flag of rm_light_grid_irradiance: DDGI's backface term on every corner's weight
 RM_MAX_LIGHT_GRID_DIM = 1024  # probes per axis of the grid of one rm_light_grid_irradiance call, at least 2
 RM_MAX_LIGHT_GRID_PROBES = 1 << 24  # and probes of the whole grid
+
+
+class RmProbeDepth(C.Structure):
+    _fields_ = [("moments", (f32 * 2) * 64)]
+
+
+RM_PROBE_DEPTH_TEXELS = 64  # texels of an RmProbeDepth, an 8×8 octahedral map: tx + 8·ty
+RM_LIGHT_GRID_VIS_FLOOR = 1.0e-6  # the least visibility rm_light_grid_irradiance_visible gives a corner that does not see the point
+RM_PATH_LIGHT_PROBES_DEPTH = 22  # rm_debug_last_path() behind a launch of rm_light_probes_depth
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

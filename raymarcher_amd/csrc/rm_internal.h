@@ -128,6 +128,12 @@ int launch_shade_kernel(const void *sb, int bulbClass, bool env, bool tex, bool 
 // over lanes — numProbes float4 from d_positions, numSets·numDirs RmProbeDir from d_dirs, numProbes RmLightProbe into d_out.
 int launch_probes_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const float *d_positions, int numProbes,
                          const void *d_dirs, int numDirs, int numSets, void *d_out, hipStream_t stream);
+// The probe-depth kernels (rm_light_depth.hip, rm_light_probes_depth; a translation unit of its own for the same reason): the launch
+// of light_depth_kernel<bulbClass, numDirs from 64 on> over the ONE staged SceneBlock `sb`, light_probes_kernel's flattening for the
+// march and a lane per texel behind it — numProbes float4 from d_positions, numSets·numDirs RmProbeDir from d_dirs and as many rows
+// of 64 floats from d_weights, numProbes RmProbeDepth into d_out.
+int launch_probes_depth_kernel(const void *sb, int bulbClass, const float *d_positions, int numProbes, const void *d_dirs,
+                               const float *d_weights, int numDirs, int numSets, float maxDistance, void *d_out, hipStream_t stream);
 // The layer kernels (rm_layers.hip, rm_shade_rays_layers and rm_trace_rays_layers; a translation unit of its own for the same
 // reason), for the calls that have a layer bit — a call without one goes to the two launches above.  shade_rays_layers_kernel<tex,
 // sec> (the env class; imageWidth feeds the sea normal's epsilon) and trace_layers_kernel<bulbClass> (closest mode only) over the

@@ -2,13 +2,14 @@
 // probes.  Each checks its arguments, stages one scene block and launches one kernel of another unit through the launcher's
 // stage_block_launch (rm_launch.h), which also records the path and the timing: nothing here reads or writes a tuner, the tile
 // order or the wavefront state, and nothing here sees the launcher's slots, rings or device state.  Host code only: the kernels
-// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_light_probes.hip, rm_layers.hip, rm_points.hip,
+// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_light_probes.hip, rm_light_depth.hip, rm_layers.hip, rm_points.hip,
 // rm_volume.hip, rm_blocks.hip and rm_probe.hip (declared in rm_internal.h, the lattice family's in rm_lattice.h), the scene prep that needs no GPU in rm_frame.cpp.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "rm_internal.h"
 #include "rm_frame.h"
@@ -201,6 +202,55 @@ int launch_probes(const ProbesCall &c) {
   return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
     return launch_probes_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_positions, c.numProbes, c.d_dirs, c.numDirs,
                                 c.numSets, c.d_out, c.stream);
+  });
+}
+
+// ---- probe depth: rays from a position and a table row, marched and summed into 64 texels (rm_light_probes_depth) ------------------
+// rm_light_probes_depth (the header has the definition): rm_trace_rays' closest hit for the rays of numProbes positions times the
+// numDirs rows of rm_light_probes' direction table, each distance and its square multiplied into the row's 64 texel weights and
+// summed per probe and texel inside the kernel.  Its checks run in check_probes' order with maxDistance in the place of far and
+// d_weights beside d_dirs; a march reads no material, so the scene is checked and staged as launch_trace's (check_object_table, a
+// zeroed camera, no lights, no resources, the table's march class).  Then ONE launch of light_depth_kernel (rm_light_depth.hip),
+// path 22: no tuner, tile-order or workspace state is read or changed and nothing is allocated.
+struct ProbesDepthCall {
+  const float *d_positions; int numProbes; const RmProbeDir *d_dirs; const float *d_weights; int numDirs, numSets; float maxDistance;
+  const RmObject *objs; int numObjects; const RmGlobals *g; const RmSettings *s;
+  RmProbeDepth *d_out; hipStream_t stream;
+};
+int check_probes_depth(const ProbesDepthCall &c) {
+  if (c.numProbes < 0) { set_error("negative numProbes"); return RM_ERR_INVALID_ARGUMENT; }
+  int st = check_probe_table(c.numDirs, c.numSets);
+  if (st != RM_OK || c.numProbes == 0) return st;
+  if ((long long)c.numProbes * c.numDirs > INT_MAX) { set_error("numProbes * numDirs exceeds INT_MAX rays"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || c.numObjects < 0) {
+    set_error("null scene pointer or negative count");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (!(c.maxDistance > 0.0f) || c.maxDistance == __builtin_inff()) {
+    set_error("maxDistance must be finite and greater than 0");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  st = refuse_layers(c.s, "rm_light_probes_depth marches rays against the object table: rays through TERRAIN / CLOUD / SEA are not defined");
+  if (st != RM_OK || (st = refuse_two_d(c.g, "the 2-D mode (isTwoD) marches no ray")) != RM_OK) return st;
+  if ((st = check_object_table(c.objs, c.numObjects, c.s)) != RM_OK) return st;
+  if (!c.d_positions || !c.d_dirs || !c.d_weights || !c.d_out) {
+    set_error("null d_positions, d_dirs, d_weights or d_out");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if (((uintptr_t)c.d_positions | (uintptr_t)c.d_dirs | (uintptr_t)c.d_weights | (uintptr_t)c.d_out) & 15u) {
+    set_error("d_positions, d_dirs, d_weights and d_out must be 16-byte aligned");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  return require_device_pointers({{"d_positions", c.d_positions}, {"d_dirs", c.d_dirs}, {"d_weights", c.d_weights}, {"d_out", c.d_out}});
+}
+int launch_probes_depth(const ProbesDepthCall &c) {
+  int st = check_probes_depth(c);
+  if (st != RM_OK || c.numProbes == 0) return st;
+  const int bulbClass = table_bulb_class(c.objs, c.numObjects, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  BlockCall b{c.objs, c.numObjects, c.g, c.s, c.stream, 22};
+  return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
+    return launch_probes_depth_kernel(sb, bulbClass, c.d_positions, c.numProbes, c.d_dirs, c.d_weights, c.numDirs, c.numSets, c.maxDistance,
+                                      c.d_out, c.stream);
   });
 }
 
@@ -429,6 +479,65 @@ int rm_sphere_directions(int numDirs, int numSets, RmProbeDir *out) {
       for (int j = 0; j < 9; j++) e.basis[j] = (float)(w * Y[j]);
       e.pad[0] = e.pad[1] = e.pad[2] = 0.0f;
     }
+  return RM_OK;
+}
+
+int rm_light_probes_depth(const float *d_positions, int numProbes, const RmProbeDir *d_dirs, const float *d_weights, int numDirs,
+                          int numSets, float maxDistance, const RmObject *objs, int numObjects, const RmGlobals *g, const RmSettings *s,
+                          RmProbeDepth *d_out, void *stream) {
+  return launch_probes_depth(ProbesDepthCall{d_positions, numProbes, d_dirs, d_weights, numDirs, numSets, maxDistance, objs, numObjects, g, s,
+                                             d_out, static_cast<hipStream_t>(stream)});
+}
+
+// rm_probe_depth_weights (the header has the definition): host only, binary64 rounded once.  Per set and texel the rows' lobes
+// max(0, cos)^sharpness around the texel's centre direction, normalised over the set's valid rows; a texel that no lobe reaches
+// goes to the nearest row whole.
+int rm_probe_depth_weights(const RmProbeDir *dirs, int numDirs, int numSets, float sharpness, float *out) {
+  if (int st = check_probe_table(numDirs, numSets)) return st;
+  if (!dirs || !out) { set_error("null dirs or out"); return RM_ERR_INVALID_ARGUMENT; }
+  if (!std::isfinite(sharpness) || sharpness < 0.0f) { set_error("sharpness must be finite and not negative"); return RM_ERR_INVALID_ARGUMENT; }
+  double centre[RM_PROBE_DEPTH_TEXELS][3];
+  for (int x = 0; x < RM_PROBE_DEPTH_TEXELS; x++) {
+    const double u = (((double)(x % 8) + 0.5) / 8.0) * 2.0 - 1.0, v = (((double)(x / 8) + 0.5) / 8.0) * 2.0 - 1.0;
+    const double z = 1.0 - std::fabs(u) - std::fabs(v);
+    double cx = u, cy = v;
+    if (z < 0.0) cx = (1.0 - std::fabs(v)) * (u >= 0.0 ? 1.0 : -1.0), cy = (1.0 - std::fabs(u)) * (v >= 0.0 ? 1.0 : -1.0);
+    const double len = std::sqrt(cx * cx + cy * cy + z * z);
+    centre[x][0] = cx / len, centre[x][1] = cy / len, centre[x][2] = z / len;
+  }
+  std::vector<double> dots((size_t)numDirs * RM_PROBE_DEPTH_TEXELS);
+  std::vector<char> valid((size_t)numDirs);
+  for (int s = 0; s < numSets; s++) {
+    const RmProbeDir *rows = dirs + (size_t)s * (size_t)numDirs;
+    float *w = out + (size_t)s * (size_t)numDirs * RM_PROBE_DEPTH_TEXELS;
+    for (int k = 0; k < numDirs; k++) {
+      const float *d = rows[k].dir;
+      valid[k] = std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]) && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f);
+      if (!valid[k]) continue;
+      const double dx = d[0], dy = d[1], dz = d[2], len = std::sqrt(dx * dx + dy * dy + dz * dz);
+      for (int x = 0; x < RM_PROBE_DEPTH_TEXELS; x++)
+        dots[(size_t)k * RM_PROBE_DEPTH_TEXELS + x] = centre[x][0] * (dx / len) + centre[x][1] * (dy / len) + centre[x][2] * (dz / len);
+    }
+    for (int x = 0; x < RM_PROBE_DEPTH_TEXELS; x++) {
+      double sum = 0.0, best = -__builtin_inf();
+      int nearest = -1;
+      for (int k = 0; k < numDirs; k++) {
+        if (!valid[k]) continue;
+        const double dot = dots[(size_t)k * RM_PROBE_DEPTH_TEXELS + x];
+        sum += std::pow(dot > 0.0 ? dot : 0.0, (double)sharpness);
+        if (dot > best) best = dot, nearest = k;
+      }
+      for (int k = 0; k < numDirs; k++) {
+        float &o = w[(size_t)k * RM_PROBE_DEPTH_TEXELS + x];
+        if (!valid[k]) o = 0.0f;
+        else if (sum == 0.0) o = k == nearest ? 1.0f : 0.0f;
+        else {
+          const double dot = dots[(size_t)k * RM_PROBE_DEPTH_TEXELS + x];
+          o = (float)(std::pow(dot > 0.0 ? dot : 0.0, (double)sharpness) / sum);
+        }
+      }
+    }
+  }
   return RM_OK;
 }
 

@@ -410,6 +410,22 @@ def sphere_directions(num_dirs, num_sets=1):
     return table
 
 
+def probe_depth_weights(table, sets=1, sharpness=50.0):
+    """rm_probe_depth_weights: the texel weights Renderer.light_probes_depth builds for a direction table → float32
+    (sets·directions, 64) numpy array: row k's share of each texel of the 8×8 octahedral depth map, max(0, cos)^sharpness around the
+    texel's centre direction, normalised per texel over the rows of the set.  table: float32 (sets·directions, 16) rows of
+    RmProbeDir (sphere_directions' or the caller's own; the basis is not read).  A texel that no lobe reaches goes to the nearest
+    row whole; the definition is in include/raymarcher_amd.h."""
+    import numpy as np
+    table = _np_f32(table)
+    sets = int(sets)
+    if table.ndim != 2 or table.shape[1] != 16 or sets < 1 or table.shape[0] % sets:
+        raise ValueError("table must be float32 (sets * directions, 16) rows of RmProbeDir")
+    out = np.zeros((table.shape[0], abi.RM_PROBE_DEPTH_TEXELS), dtype=np.float32)
+    check(lib().rm_probe_depth_weights(C.c_void_p(table.ctypes.data), table.shape[0] // sets, sets, float(sharpness), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def sh_irradiance(sh, normals):
     """The irradiance that SH9 radiance coefficients give a surface with unit normal n: the clamped-cosine convolution
     E(n) = Σ_j A_band(j)·sh_j·Y_j(n) with A = π, 2π/3, π/4 for bands 0, 1, 2 (Ramamoorthi & Hanrahan 2001).  sh: (..., 9, c) —
@@ -567,7 +583,8 @@ class LightGrid:
     dims) wraps a caller's own records): `probes` is the float32 (nx·ny·nz, 40) tensor of RmLightProbe rows as light_probes stores
     them, probe (i, j, k) at row i + nx·(j + ny·k) and at origin + (i, j, k)·step (light_grid_positions).  A probe whose hits is
     negative (abi.RM_RAY_INVALID) is left out of every lookup.  A numpy array is uploaded, a tensor on the renderer's device is kept
-    as it is."""
+    as it is.  `depth` is None, or — Renderer.light_grid_visible bakes them, set_depth attaches a caller's own — the probes' depth
+    moments, with which every lookup weighs a probe by whether it sees the point."""
 
     def __init__(self, renderer, probes, origin, step, dims):
         import numpy as np
@@ -578,8 +595,23 @@ class LightGrid:
         count = self.dims[0] * self.dims[1] * self.dims[2]
         if (tuple(probes.shape) != (count, 40) or probes.dtype != t.float32 or not probes.is_contiguous() or probes.device != renderer.device):
             raise ValueError(f"probes must be a contiguous float32 tensor of shape ({count}, 40) on {renderer.device}")
-        self._r, self.probes = renderer, probes
+        self._r, self.probes, self.depth, self.normal_bias = renderer, probes, None, None
         self.origin, self.step = np.asarray(origin, dtype=np.float32).reshape(3).copy(), np.asarray(step, dtype=np.float32).reshape(3).copy()
+
+    def set_depth(self, depth, normal_bias=None):
+        """Attaches (None: removes) the probes' depth moments → self: float32 (nx·ny·nz, 64, 2), RmProbeDepth rows as
+        Renderer.light_probes_depth stores them, probe order as `probes`; a numpy array is uploaded, a tensor on the renderer's
+        device is kept as it is.  From then on irradiance, light_gbuffer and Renderer.render_indirect take the visible lookup.
+        normal_bias: the default bias of those lookups, None = 0.25 × the smallest step."""
+        t = self._r.torch
+        if depth is not None:
+            if not t.is_tensor(depth):
+                depth = t.from_numpy(_np_f32(depth)).to(self._r.device)
+            count = self.dims[0] * self.dims[1] * self.dims[2]
+            if (tuple(depth.shape) != (count, 64, 2) or depth.dtype != t.float32 or not depth.is_contiguous() or depth.device != self._r.device):
+                raise ValueError(f"depth must be a contiguous float32 tensor of shape ({count}, 64, 2) on {self._r.device}")
+        self.depth, self.normal_bias = depth, normal_bias
+        return self
 
     def irradiance(self, points, normals, facing=True, out=None):
         """rm_light_grid_irradiance: the grid's light at `points` on surfaces with `normals`, ONE launch → (e, weight, probes): float32
@@ -590,14 +622,34 @@ class LightGrid:
         1 − e[:, 3] / π the cosine-weighted sky visibility.  facing: DDGI's backface term, which takes weight from probes behind the
         surface.  weight: the sum of the eight weights; probes: how many corners took part, 0 (zeros in e) where none did,
         abi.RM_RAY_INVALID for a non-finite point or a non-finite or zero normal.  A point outside the box takes the border's light.
+        A grid that has depth records takes irradiance_visible's lookup with its defaults; one without gives what it always gave.
         The definition, bit for bit, is in include/raymarcher_amd.h."""
+        return self.irradiance_visible(points, normals, facing=facing, out=out)
+
+    def irradiance_visible(self, points, normals, facing=True, out=None, visible=None, normal_bias=None):
+        """irradiance with the choice of the lookup.  visible: True — rm_light_grid_irradiance_visible, which also weighs every probe
+        by the Chebyshev visibility of the point q = p + normal_bias·n in the probe's depth map, so that light does not leak through
+        walls (the grid must have depth records) —, False — rm_light_grid_irradiance —, None — whichever the grid has records for.
+        normal_bias: None = the grid's normal_bias, and 0.25 × the smallest step where that is None too.  The definition, bit for
+        bit, is in include/raymarcher_amd.h."""
         r = self._r
         t = r.torch
         pts, nrm = r._points(points, "points"), r._points(normals, "normals")
         n = pts.shape[0]
         if nrm.shape[0] != n:
             raise ValueError("one normal per point")
+        visible = self.depth is not None if visible is None else bool(visible)
+        if visible and self.depth is None:
+            raise ValueError("visible=True needs a grid with depth records (Renderer.light_grid_visible, LightGrid.set_depth)")
         rec = r._out(out, (n, 8), t.float32)
+        if visible:
+            bias = self.normal_bias if normal_bias is None else normal_bias
+            bias = 0.25 * float(self.step.min()) if bias is None else float(bias)
+            check(lib().rm_light_grid_irradiance_visible(
+                C.c_void_p(self.probes.data_ptr()), C.c_void_p(self.depth.data_ptr()), (C.c_int * 3)(*self.dims), _vec3(self.origin, "origin"),
+                _vec3(self.step, "step"), C.c_void_p(pts.data_ptr()) if n else None, C.c_void_p(nrm.data_ptr()) if n else None, n,
+                abi.RM_LIGHT_GRID_FACING if facing else 0, bias, C.c_void_p(rec.data_ptr()) if n else None, r._stream()))
+            return rec[:, 0:4], rec[:, 4], rec[:, 5].view(t.int32)
         check(lib().rm_light_grid_irradiance(C.c_void_p(self.probes.data_ptr()), (C.c_int * 3)(*self.dims), _vec3(self.origin, "origin"),
                                              _vec3(self.step, "step"), C.c_void_p(pts.data_ptr()) if n else None,
                                              C.c_void_p(nrm.data_ptr()) if n else None, n, abi.RM_LIGHT_GRID_FACING if facing else 0,
@@ -607,13 +659,18 @@ class LightGrid:
     def light_gbuffer(self, normal_depth, position, facing=True):
         """irradiance at the primary hits of render_gbuffer(position=True): normal_depth and position, float32 (N, H, W, 4) as it
         returns them, used in place → float32 (N, H, W, 4), e per pixel (a view of the (N·H·W, 8) result).  A miss has a zero normal,
-        which makes it an invalid point: zeros."""
+        which makes it an invalid point: zeros.  Follows the grid as irradiance does."""
+        return self.light_gbuffer_visible(normal_depth, position, facing=facing)
+
+    def light_gbuffer_visible(self, normal_depth, position, facing=True, visible=None, normal_bias=None):
+        """light_gbuffer with irradiance_visible's `visible` and `normal_bias`."""
         t = self._r.torch
         if (normal_depth.dim() != 4 or normal_depth.shape[3] != 4 or tuple(position.shape) != tuple(normal_depth.shape)
                 or normal_depth.dtype != t.float32 or position.dtype != t.float32):
             raise ValueError("normal_depth and position must be float32 tensors of the same shape (N, H, W, 4)")
         N, H, W, _ = normal_depth.shape
-        e, _, _ = self.irradiance(position.reshape(-1, 4), normal_depth.reshape(-1, 4), facing=facing)
+        e, _, _ = self.irradiance_visible(position.reshape(-1, 4), normal_depth.reshape(-1, 4), facing=facing, visible=visible,
+                                          normal_bias=normal_bias)
         return e.view(N, H, W, 4)
 
 
@@ -635,6 +692,7 @@ class Renderer:
         self._tex_cache = {}
         self._tex_lock = threading.Lock()
         self._probe_tables = {}  # light_probes' tables on the device, per (directions, sets); under the same lock
+        self._depth_weights = {}  # light_probes_depth's weights of those tables, per (directions, sets, sharpness); under the same lock
 
     def _out(self, a, shape, dtype, name="out"):
         """A fresh tensor of `shape` and `dtype` on this device, or the caller's `a` once it is checked to be exactly that (the
@@ -893,18 +951,7 @@ class Renderer:
         dirs, sets = int(directions), int(sets)
         pts = self._points(positions, "positions")
         n = pts.shape[0]
-        if table is None:
-            key = (dirs, sets)
-            with self._tex_lock:
-                if key not in self._probe_tables:
-                    self._probe_tables[key] = t.from_numpy(sphere_directions(dirs, sets)).to(self.device)
-                table = self._probe_tables[key]
-        else:
-            if not t.is_tensor(table):
-                table = t.from_numpy(_np_f32(table)).to(self.device)
-            if (table.dim() != 2 or tuple(table.shape) != (sets * dirs, 16) or table.dtype != t.float32 or not table.is_contiguous()
-                    or table.device != self.device):
-                raise ValueError(f"table must be a contiguous float32 tensor of shape (sets * directions, 16) on {self.device}")
+        table = self._probe_table(dirs, sets, table)
         rec = self._out(out, (n, 40), t.float32)
         res, _keep = self._resources(tables)
         check(lib().rm_light_probes(C.c_void_p(pts.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr()), dirs, sets,
@@ -913,12 +960,82 @@ class Renderer:
                                     C.c_void_p(rec.data_ptr()) if n else None, self._stream()))
         return rec[:, 0:36].view(n, 9, 4), rec[:, 36].view(t.int32)
 
+    def _probe_table(self, dirs, sets, table):
+        """light_probes' table on this device: sphere_directions(dirs, sets), built once per (dirs, sets) and kept, or the caller's
+        `table` once it is checked."""
+        t = self.torch
+        if table is None:
+            key = (dirs, sets)
+            with self._tex_lock:
+                if key not in self._probe_tables:
+                    self._probe_tables[key] = t.from_numpy(sphere_directions(dirs, sets)).to(self.device)
+                return self._probe_tables[key]
+        if not t.is_tensor(table):
+            table = t.from_numpy(_np_f32(table)).to(self.device)
+        if (table.dim() != 2 or tuple(table.shape) != (sets * dirs, 16) or table.dtype != t.float32 or not table.is_contiguous()
+                or table.device != self.device):
+            raise ValueError(f"table must be a contiguous float32 tensor of shape (sets * directions, 16) on {self.device}")
+        return table
+
+    def light_probes_depth(self, tables, settings, positions, directions=256, sets=1, max_distance=None, table=None, weights=None,
+                           sharpness=50.0, out=None):
+        """rm_light_probes_depth: the depth moments of probes at `positions`, `directions` rays each marched as trace_rays marches
+        them and summed per probe and texel in ONE launch → float32 (n, 64, 2) device tensor of RmProbeDepth rows (`out`, if
+        given): per texel of an 8×8 octahedral map the weighted mean of the distance to the scene and of its square, which
+        LightGrid.irradiance turns into a visibility term.  positions, directions, sets, table: as light_probes takes them — one
+        table serves both bakes.  max_distance: where a ray that hits nothing is taken to end, None = tables.camera.initialFar; keep
+        it near the probe spacing, since a mean over a lobe that mixes a wall with a far miss says little.  weights: None =
+        probe_depth_weights(table, sets, sharpness) — built once per (directions, sets, sharpness) and kept on the renderer for the
+        renderer's own tables; for a caller's `table` EVERY call copies the table to the host (which waits for the device), builds
+        the weights there and uploads them, so build them once yourself and pass them — or float32 (sets·directions, 64), numpy or
+        a tensor on this device.  A probe with a non-finite position stores zeros.  Terrain, clouds
+        and sea are refused.  The definition is in include/raymarcher_amd.h."""
+        t = self.torch
+        dirs, sets = int(directions), int(sets)
+        pts = self._points(positions, "positions")
+        n = pts.shape[0]
+        own_table = table is None
+        table = self._probe_table(dirs, sets, table)
+        if weights is None:
+            key = (dirs, sets, float(sharpness))
+            with self._tex_lock:
+                weights = self._depth_weights.get(key) if own_table else None
+            if weights is None:
+                weights = t.from_numpy(probe_depth_weights(table.cpu().numpy(), sets, sharpness)).to(self.device)
+                if own_table:
+                    with self._tex_lock:
+                        weights = self._depth_weights.setdefault(key, weights)
+        else:
+            if not t.is_tensor(weights):
+                weights = t.from_numpy(_np_f32(weights)).to(self.device)
+            if (tuple(weights.shape) != (sets * dirs, 64) or weights.dtype != t.float32 or not weights.is_contiguous()
+                    or weights.device != self.device):
+                raise ValueError(f"weights must be a contiguous float32 tensor of shape (sets * directions, 64) on {self.device}")
+        rec = self._out(out, (n, 64, 2), t.float32)
+        check(lib().rm_light_probes_depth(C.c_void_p(pts.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr()),
+                                          C.c_void_p(weights.data_ptr()), dirs, sets,
+                                          tables.camera.initialFar if max_distance is None else max_distance, tables.objects,
+                                          tables.num_objects, C.byref(tables.globals_), C.byref(settings),
+                                          C.c_void_p(rec.data_ptr()) if n else None, self._stream()))
+        return rec
+
     def light_grid(self, tables, settings, dims, bounds=None, directions=256, sets=1, far=None, mask_inside=0.0):
         """A LightGrid of dims = (nx, ny, nz) probes over `bounds` — (lo, hi), or None for mesh_bounds(tables) —, the first probe at
         lo and the last at hi: ONE light_probes call at light_grid_positions(origin, step, dims) with `directions`, `sets` and `far` as
         light_probes takes them.  mask_inside (None: no masking): one sdf_grid call on the same origin, step and dims, and every probe
         whose scene distance is below it gets hits = abi.RM_RAY_INVALID, so that LightGrid.irradiance leaves it out — 0.0 masks the
         probes inside geometry, whose rays see the inside of a surface."""
+        return self._light_grid(tables, settings, dims, bounds, directions, sets, far, mask_inside, False)
+
+    def light_grid_visible(self, tables, settings, dims, bounds=None, directions=256, sets=1, far=None, mask_inside=0.0, visibility=True,
+                           sharpness=50.0):
+        """light_grid, and with visibility ONE light_probes_depth call more at the same positions with the same table, the weights
+        of probe_depth_weights(table, sets, sharpness) and max_distance = 1.5 × the length of `step`: the grid then carries depth
+        records and its lookups weigh every probe by whether it sees the point, so that a lit room does not bleed through a wall
+        into the dark room next to it."""
+        return self._light_grid(tables, settings, dims, bounds, directions, sets, far, mask_inside, bool(visibility), sharpness)
+
+    def _light_grid(self, tables, settings, dims, bounds, directions, sets, far, mask_inside, visibility, sharpness=50.0):
         import numpy as np
         t = self.torch
         nx, ny, nz = _grid_dims(dims)
@@ -928,17 +1045,22 @@ class Renderer:
             raise ValueError("bounds must be (lo, hi) with three finite components each and lo < hi")
         origin, step = lo.astype(np.float32), ((hi - lo) / (np.array([nx, ny, nz]) - 1)).astype(np.float32)
         rec = t.empty((nx * ny * nz, 40), dtype=t.float32, device=self.device)
-        _, hits = self.light_probes(tables, settings, light_grid_positions(origin, step, (nx, ny, nz)), directions=directions, sets=sets,
-                                    far=far, out=rec)
+        positions = self._points(light_grid_positions(origin, step, (nx, ny, nz)), "positions")
+        _, hits = self.light_probes(tables, settings, positions, directions=directions, sets=sets, far=far, out=rec)
         if mask_inside is not None:
             dist = self.sdf_grid(tables, settings, origin, step, (nx, ny, nz))
             hits[dist.reshape(-1) < float(mask_inside)] = abi.RM_RAY_INVALID
-        return LightGrid(self, rec, origin, step, (nx, ny, nz))
+        grid = LightGrid(self, rec, origin, step, (nx, ny, nz))
+        if visibility:
+            grid.set_depth(self.light_probes_depth(tables, settings, positions, directions=directions, sets=sets, sharpness=sharpness,
+                                                   max_distance=1.5 * float(np.linalg.norm(step.astype(np.float64)))))
+        return grid
 
     def render_indirect(self, tables, settings, W, H, grid, cameras=None, strength=1.0):
         """render_batch's frames plus one bounce of diffuse light from a LightGrid → float32 (N, H, W, 4): on every pixel whose
         primary ray hits an object, strength · kd · cDiffuse[object_id] · e.rgb / π is added to the colour, e = grid.light_gbuffer
-        of one render_gbuffer(position=True) through the same cameras (None: the scene's own, N = 1).  Plain torch arithmetic around
+        of one render_gbuffer(position=True) through the same cameras (None: the scene's own, N = 1) — with the visibility term where
+        the grid has depth records (light_grid_visible), without it where not.  Plain torch arithmetic around
         the three launches, NOT bit-defined.  The albedo is the object's cDiffuse alone: textures and the fractals' trap colours are
         not part of it, and reflections and refractions get no indirect light."""
         import math
