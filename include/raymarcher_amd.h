@@ -726,6 +726,71 @@ int rm_light_grid_irradiance_visible(const RmLightProbe *d_probes, const RmProbe
                                      const float *d_points /* float4 each, w not read */, const float *d_normals /* float4 each, w not read */,
                                      int numPoints, uint32_t flags, float normalBias, RmGridLight *d_out, void *stream);
 /*
+ * rm_shade_rays_indirect, rm_light_probes_indirect — the diffuse term of a light grid at the hit of a shaded ray, computed inside
+ * the shading kernel: what a multi-bounce bake feeds back (DDGI: each probe ray adds albedo · E_grid(hit, normal) / π at its hit) and
+ * what a frame lit by a grid adds per pixel.  Inside the kernel the hit point, the bumped normal, getDiffuse's texture blend and the
+ * march's orbit trap all exist; no other entry hands out the last two.
+ *
+ * The grid is ONE host struct, RmLightGridRef, copied before the call returns: d_probes and dims, origin, step as
+ * rm_light_grid_irradiance takes them; d_depth the grid's RmProbeDepth records or NULL; flags and normalBias as
+ * rm_light_grid_irradiance_visible takes them (normalBias is not read by the lookup without d_depth, but is checked); strength.
+ *
+ * The term, bit for bit, for a ray (ro, rd).  Every operation is ONE binary32 operation as written, unfused (rm_indirect.h is the
+ * arithmetic behind the hit in C++).
+ *   colour is what rm_shade_rays stores for the ray, in every word.
+ *   (n, t, p, obj) is what rm_trace_rays(RM_TRACE_CLOSEST) stores for the same ray with tMax = far.
+ *   NO TERM — colour's words are stored unchanged and no addition is performed, not even of +0 — where the ray is invalid (zeros, as
+ *   rm_shade_rays), where the primary march misses, where the hit object isEmissive, and where probes <= 0 in the grid record below.
+ *   Otherwise e is RmGridLight.e of the record that rm_light_grid_irradiance_visible stores at (p, n) with flags and normalBias
+ *   where d_depth is not NULL, rm_light_grid_irradiance's where it is NULL, word for word;
+ *     ec[ch] = e[ch] > 0 ? e[ch] : +0          (ringing of the clamped-cosine lobe, −0 and NaN become +0)
+ *     k      = strength · RM_INV_PI            (one multiplication, on the host)
+ *     dif    = getDiffuse at p for the hit object, the value render() puts into mat.dif: kd·cDiffuse, or its blend with the texture
+ *     x[ch]  = (dif[ch] · ec[ch]) · k
+ *   and the palette multiplies the term as it multiplies Phong: Mandelbulb ind = c · (x · 8) with
+ *   c = bulbTrapColor(trap.y, trap.z, trap.w); Menger sponge ind = c · x with the cosine palette of trap.z; every other type ind = x.
+ *   trap is the primary march's; in a table with a fractal behind the hit one, UB3's rule (the trap of the last fractal evaluated)
+ *   holds here as in render().
+ *     out.rgb = colour.rgb + ind, one addition per channel; alpha is colour's.
+ * The term lights the PRIMARY HIT ONLY: reflection and refraction bounces get none, and ambient occlusion does not multiply it.
+ * There is no bright output.  The result of a ray does not depend on the rays it shares a call with.
+ *
+ * rm_shade_rays_indirect — ONE launch, one lane per ray: rm_shade_rays' arguments without d_bright, `grid` behind res; rm_shade_rays'
+ * classes and staging (rm_debug_last_path() = 23, rm_debug_last_split() = 0).  It refuses in this order, all but the last before any
+ * HIP call: rm_shade_rays' own refusals up to and with the alignment of d_rays and d_rgba (numRays == 0 is RM_OK there); then
+ * RM_ERR_INVALID_ARGUMENT: a null grid; a dimension below 2 or above RM_MAX_LIGHT_GRID_DIM; more than RM_MAX_LIGHT_GRID_PROBES probes;
+ * a non-finite origin component; a step component that is not finite or not greater than 0; a non-finite normalBias; flag bits other
+ * than RM_LIGHT_GRID_FACING; a null d_probes (d_depth may be NULL); a misaligned d_probes or d_depth (16 bytes); a non-finite
+ * strength; last, an array that is not device memory (d_rays, the resources' pixels and d_rgba, d_probes, d_depth).  RM_FEAT_TERRAIN,
+ * RM_FEAT_CLOUD and RM_FEAT_SEA are RM_ERR_UNSUPPORTED, as for rm_shade_rays.
+ *
+ * rm_light_probes_indirect — ONE launch: rm_light_probes with every ray's colour replaced by out.rgb above; the hit flag, the leaves,
+ * the tree, the flattening and the multi-pass fold are unchanged, so a record equals rm_shade_rays_indirect on the numProbes·numDirs
+ * rays through rm_light_probes' tree in every word (rm_debug_last_path() = 24).  rm_light_probes' arguments with `grid` behind res.
+ * It refuses rm_light_probes' own up to and with the alignment of its arrays (numProbes == 0 is RM_OK there), then the grid and the
+ * strength as above, then RM_ERR_INVALID_ARGUMENT: [d_out, d_out + numProbes·160) overlaps the grid's probe records — a bake must
+ * not read the grid it writes; ping-pong two buffers —, last the device-memory checks.
+ * Schedule: shade_rays_kernel's and light_probes_kernel's, with the grid (64 bytes) by value in the kernel's arguments.  Behind its
+ * primary hit a lane reads its cell's eight hits words, the nine float4 of every valid corner and, with d_depth, four texels of each.
+ * One slot of the batch ring of scene blocks; no tuner, tile-order or workspace state is read or changed, nothing is allocated.
+ * Added without a change of RM_ABI_VERSION (new symbols and nothing else): bindings detect them by symbol lookup.
+ */
+#define RM_INV_PI ((float)0.31830988618379067)   /* 1/π in binary64, rounded once to binary32 */
+typedef struct RmLightGridRef {
+  const RmLightProbe *d_probes; const RmProbeDepth *d_depth /* may be NULL */;
+  int dims[3]; float origin[3]; float step[3];
+  float strength; uint32_t flags; float normalBias;
+} RmLightGridRef;   /* 64 bytes */
+int rm_shade_rays_indirect(const RmRay *d_rays, int numRays, float far,
+                           const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                           const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */,
+                           const RmLightGridRef *grid, float *d_rgba, void *stream);
+int rm_light_probes_indirect(const float *d_positions /* float4 each, w not read */, int numProbes,
+                             const RmProbeDir *d_dirs, int numDirs, int numSets, float far,
+                             const RmObject *objs, int numObjects, const RmLight *lights, int numLights,
+                             const RmGlobals *g, const RmSettings *s, const RmResources *res /* may be NULL */,
+                             const RmLightGridRef *grid, RmLightProbe *d_out, void *stream);
+/*
  * rm_trace_rays_layers — rm_trace_rays THROUGH terrain and sea: the closest VISIBLE SURFACE along each ray, by the rules main
  * applies to its own rays.  For keeping a fly-through camera above the terrain, and for picking on a landscape.  The arguments are
  * rm_trace_rays' with imageWidth (as above, >= 1 in every call) behind numRays.
@@ -1443,7 +1508,8 @@ int rm_release_workspaces(unsigned long long *freedBytes);
  * with ss > 1, 8 = a call of rm_render_adaptive, 9 = a launch of rm_render_accumulated, 10 = a launch of rm_render_animated, 11 = a launch
  * of rm_render_gbuffer, 12 = a launch of rm_trace_rays, 13 = a launch of rm_shade_rays, 14 = a launch of rm_shade_rays_layers, 15 = a
  * launch of rm_trace_rays_layers, 16 = a launch of rm_sdf_grid, 17 = a launch of rm_shade_points, 18 = a launch of rm_sdf_blocks_select,
- * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned, 21 = a launch of rm_light_probes, 22 = a launch of rm_light_probes_depth (none of them is a
+ * 19 = a launch of rm_sdf_grid_blocks, 20 = a launch of rm_sdf_blocks_select_pruned, 21 = a launch of rm_light_probes, 22 = a launch of rm_light_probes_depth,
+ * 23 = a launch of rm_shade_rays_indirect, 24 = a launch of rm_light_probes_indirect (none of them is a
  * value rm_set_kernel_path takes).  The value belongs to the DEVICE, not to the calling thread or stream: it reports the device's most recent launch,
  * whichever thread made it. */
 int rm_debug_last_path(void);

@@ -97,6 +97,11 @@ SIGNATURES = {
                                         _P(abi.RmGlobals), _P(abi.RmSettings), C.c_void_p, C.c_void_p]),
     "rm_light_grid_irradiance_visible": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int), _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+    "rm_shade_rays_indirect": (C.c_int, [C.c_void_p, C.c_int, C.c_float, _P(abi.RmObject), C.c_int, _P(abi.RmLight), C.c_int, _P(abi.RmGlobals),
+                                         _P(abi.RmSettings), _P(abi.RmResources), _P(abi.RmLightGridRef), C.c_void_p, C.c_void_p]),
+    "rm_light_probes_indirect": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, _P(abi.RmObject), C.c_int,
+                                           _P(abi.RmLight), C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources),
+                                           _P(abi.RmLightGridRef), C.c_void_p, C.c_void_p]),
     "rm_points_settings_default": (None, [_P(abi.RmPointsSettings)]),
     "rm_shade_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(abi.RmPointsSettings), _P(abi.RmObject), C.c_int, _P(abi.RmLight),
                                   C.c_int, _P(abi.RmGlobals), _P(abi.RmSettings), _P(abi.RmResources), C.c_void_p, C.c_void_p,

@@ -186,6 +186,15 @@ class RmProbeDepth(C.Structure):
 RM_PROBE_DEPTH_TEXELS = 64  # texels of an RmProbeDepth, an 8×8 octahedral map: tx + 8·ty
 RM_LIGHT_GRID_VIS_FLOOR = 1.0e-6  # the least visibility rm_light_grid_irradiance_visible gives a corner that does not see the point
 RM_PATH_LIGHT_PROBES_DEPTH = 22  # rm_debug_last_path() behind a launch of rm_light_probes_depth
+
+
+class RmLightGridRef(C.Structure):
+    _fields_ = [("d_probes", C.c_void_p), ("d_depth", C.c_void_p), ("dims", i32 * 3), ("origin", f32 * 3), ("step", f32 * 3),
+                ("strength", f32), ("flags", C.c_uint32), ("normalBias", f32)]
+
+
+RM_INV_PI = 0.3183098733425140380859375  # float32(1/π): k = strength · RM_INV_PI of rm_shade_rays_indirect's term
+RM_PATH_SHADE_RAYS_INDIRECT, RM_PATH_LIGHT_PROBES_INDIRECT = 23, 24  # rm_debug_last_path() behind rm_shade_rays_indirect / rm_light_probes_indirect
 RM_PATH_SHADE_POINTS = 17  # rm_debug_last_path() behind a launch of rm_shade_points
 RM_MAX_PROJECT_STEPS = 16  # projection steps of one rm_shade_points call
 

@@ -134,6 +134,16 @@ int launch_probes_kernel(const void *sb, int bulbClass, bool env, bool tex, bool
 // of 64 floats from d_weights, numProbes RmProbeDepth into d_out.
 int launch_probes_depth_kernel(const void *sb, int bulbClass, const float *d_positions, int numProbes, const void *d_dirs,
                                const float *d_weights, int numDirs, int numSets, float maxDistance, void *d_out, hipStream_t stream);
+// The kernels that read a light grid at the primary hit (rm_shade_indirect.hip, rm_shade_rays_indirect; rm_light_probes_indirect.hip,
+// rm_light_probes_indirect; translation units of their own for the same reason): launch_shade_kernel's and launch_probes_kernel's
+// launches with the grid of the call — an RmLightGridRef's fields, checked, with k = strength · RM_INV_PI — by value in the kernel's
+// arguments.  There is no bright output.
+struct IndirectGridArgs { const void *d_probes, *d_depth; int dims[3]; float origin[3], step[3]; float k; unsigned flags; float normalBias; };
+int launch_shade_indirect_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const void *d_rays, int numRays,
+                                 const IndirectGridArgs &grid, float *d_rgba, hipStream_t stream);
+int launch_probes_indirect_kernel(const void *sb, int bulbClass, bool env, bool tex, bool sec, const float *d_positions, int numProbes,
+                                  const void *d_dirs, int numDirs, int numSets, const IndirectGridArgs &grid, void *d_out,
+                                  hipStream_t stream);
 // The layer kernels (rm_layers.hip, rm_shade_rays_layers and rm_trace_rays_layers; a translation unit of its own for the same
 // reason), for the calls that have a layer bit — a call without one goes to the two launches above.  shade_rays_layers_kernel<tex,
 // sec> (the env class; imageWidth feeds the sea normal's epsilon) and trace_layers_kernel<bulbClass> (closest mode only) over the

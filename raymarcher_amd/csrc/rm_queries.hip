@@ -2,7 +2,7 @@
 // probes.  Each checks its arguments, stages one scene block and launches one kernel of another unit through the launcher's
 // stage_block_launch (rm_launch.h), which also records the path and the timing: nothing here reads or writes a tuner, the tile
 // order or the wavefront state, and nothing here sees the launcher's slots, rings or device state.  Host code only: the kernels
-// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_light_probes.hip, rm_light_depth.hip, rm_layers.hip, rm_points.hip,
+// and the functions that launch them are in rm_trace.hip, rm_shade.hip, rm_shade_indirect.hip, rm_light_probes.hip, rm_light_probes_indirect.hip, rm_light_depth.hip, rm_layers.hip, rm_points.hip,
 // rm_volume.hip, rm_blocks.hip and rm_probe.hip (declared in rm_internal.h, the lattice family's in rm_lattice.h), the scene prep that needs no GPU in rm_frame.cpp.
 #include <hip/hip_runtime.h>
 
@@ -103,7 +103,7 @@ struct ShadeCall {
   float *d_rgba, *d_bright; hipStream_t stream;
   bool layers = false; int imageWidth = 1;  // rm_shade_rays_layers: the layers are shaded, not refused
 };
-int check_shade(const ShadeCall &c, const RmCamera &cam) {
+int check_shade_args(const ShadeCall &c, const RmCamera &cam) {  // every check ahead of the first HIP call
   if (c.numRays < 0) { set_error("negative numRays"); return RM_ERR_INVALID_ARGUMENT; }
   if (c.numRays == 0) return RM_OK;
   if (!c.g || !c.s || (c.numObjects > 0 && !c.objs) || (c.numLights > 0 && !c.lights) || c.numObjects < 0 || c.numLights < 0) {
@@ -121,8 +121,15 @@ int check_shade(const ShadeCall &c, const RmCamera &cam) {
     set_error("d_rays, d_rgba and d_bright must be 16-byte aligned");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  if ((st = require_device_pointers({{"d_rays", c.d_rays}})) != RM_OK) return st;
+  return RM_OK;
+}
+int check_shade_device(const ShadeCall &c) {
+  if (int st = require_device_pointers({{"d_rays", c.d_rays}})) return st;
   return check_device_pointers(c.res, c.d_rgba, c.d_bright);
+}
+int check_shade(const ShadeCall &c, const RmCamera &cam) {
+  const int st = check_shade_args(c, cam);
+  return (st != RM_OK || c.numRays == 0) ? st : check_shade_device(c);
 }
 int launch_shade(const ShadeCall &c) {
   RmCamera cam{};
@@ -169,7 +176,7 @@ int check_probe_table(int numDirs, int numSets) {
   }
   return RM_OK;
 }
-int check_probes(const ProbesCall &c, const RmCamera &cam) {
+int check_probes_args(const ProbesCall &c, const RmCamera &cam) {  // every check ahead of the first HIP call
   if (c.numProbes < 0) { set_error("negative numProbes"); return RM_ERR_INVALID_ARGUMENT; }
   int st = check_probe_table(c.numDirs, c.numSets);
   if (st != RM_OK || c.numProbes == 0) return st;
@@ -187,8 +194,15 @@ int check_probes(const ProbesCall &c, const RmCamera &cam) {
     set_error("d_positions, d_dirs and d_out must be 16-byte aligned");
     return RM_ERR_INVALID_ARGUMENT;
   }
-  if ((st = require_device_pointers({{"d_positions", c.d_positions}, {"d_dirs", c.d_dirs}, {"d_out", c.d_out}})) != RM_OK) return st;
+  return RM_OK;
+}
+int check_probes_device(const ProbesCall &c) {
+  if (int st = require_device_pointers({{"d_positions", c.d_positions}, {"d_dirs", c.d_dirs}, {"d_out", c.d_out}})) return st;
   return check_device_pointers(c.res, nullptr, nullptr);
+}
+int check_probes(const ProbesCall &c, const RmCamera &cam) {
+  const int st = check_probes_args(c, cam);
+  return (st != RM_OK || c.numProbes == 0) ? st : check_probes_device(c);
 }
 int launch_probes(const ProbesCall &c) {
   RmCamera cam{};
@@ -202,6 +216,81 @@ int launch_probes(const ProbesCall &c) {
   return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
     return launch_probes_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_positions, c.numProbes, c.d_dirs, c.numDirs,
                                 c.numSets, c.d_out, c.stream);
+  });
+}
+
+// ---- the grid's diffuse term at the hit of a shaded ray (rm_shade_rays_indirect, rm_light_probes_indirect) -------------------------
+// Both (the header has the definition) are launch_shade / launch_probes with a light grid in the kernel's arguments and no bright
+// output.  The checks: check_shade_args / check_probes_args (the call's own, all ahead of the first HIP call; a call of no ray or
+// no probe is RM_OK there), then check_grid_ref — rm_light_grid_irradiance_visible's order with d_depth == NULL allowed, then the
+// strength —, for the bake the overlap of d_out with the grid's probe records, and last the device-memory checks of the call and
+// of the grid.  Staging and class are launch_shade's; ONE launch of shade_rays_indirect_kernel (rm_shade_indirect.hip), path 23, or
+// of light_probes_indirect_kernel (rm_light_probes_indirect.hip), path 24.
+int check_grid_ref(const RmLightGridRef *gr) {
+  using fchk::bad;
+  if (!gr) return bad("null grid");
+  for (int a = 0; a < 3; a++)
+    if (gr->dims[a] < 2 || gr->dims[a] > RM_MAX_LIGHT_GRID_DIM) return bad("grid dimension must be 2 … RM_MAX_LIGHT_GRID_DIM (1024)");
+  if ((long long)gr->dims[0] * gr->dims[1] * gr->dims[2] > RM_MAX_LIGHT_GRID_PROBES) return bad("more than RM_MAX_LIGHT_GRID_PROBES (2^24) probes");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(gr->origin[a])) return bad("origin must be finite");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(gr->step[a]) || !(gr->step[a] > 0.0f)) return bad("step must be finite and greater than 0");
+  if (!std::isfinite(gr->normalBias)) return bad("normalBias must be finite");
+  if (gr->flags & ~RM_LIGHT_GRID_FACING) return bad("flag bits other than RM_LIGHT_GRID_FACING");
+  if (!gr->d_probes) return bad("null d_probes in the grid");
+  if (((uintptr_t)gr->d_probes | (uintptr_t)gr->d_depth) & 15u) return bad("the grid's d_probes and d_depth must be 16-byte aligned");
+  if (!std::isfinite(gr->strength)) return bad("strength must be finite");
+  return RM_OK;
+}
+int check_grid_device(const RmLightGridRef &gr) { return require_device_pointers({{"grid.d_probes", gr.d_probes}, {"grid.d_depth", gr.d_depth}}); }
+// The checked grid as the kernels take it; k = strength · RM_INV_PI, the ONE multiplication of the definition.
+IndirectGridArgs grid_args(const RmLightGridRef &gr) {
+  IndirectGridArgs a{gr.d_probes, gr.d_depth, {gr.dims[0], gr.dims[1], gr.dims[2]}, {gr.origin[0], gr.origin[1], gr.origin[2]},
+                     {gr.step[0], gr.step[1], gr.step[2]}, 0.0f, gr.flags, gr.normalBias};
+  volatile float k = gr.strength * RM_INV_PI;  // volatile: rounded to binary32 here, whatever the host's evaluation method
+  a.k = k;
+  return a;
+}
+int launch_shade_indirect(const ShadeCall &c, const RmLightGridRef *gridRef) {
+  RmCamera cam{};
+  cam.initialFar = c.far;
+  int st = check_shade_args(c, cam);
+  if (st != RM_OK || c.numRays == 0) return st;
+  if ((st = check_grid_ref(gridRef)) != RM_OK) return st;
+  const RmLightGridRef gr = *gridRef;  // the caller's struct is read once
+  if ((st = check_shade_device(c)) != RM_OK || (st = check_grid_device(gr)) != RM_OK) return st;
+  const IndirectGridArgs ga = grid_args(gr);
+  const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
+  const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  BlockCall b{c.objs, c.numObjects, c.g, c.s, c.stream, 23};
+  b.cam = &cam; b.lights = c.lights; b.numLights = c.numLights; b.res = &c.res;
+  return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
+    return launch_shade_indirect_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_rays, c.numRays, ga, c.d_rgba, c.stream);
+  });
+}
+int launch_probes_indirect(const ProbesCall &c, const RmLightGridRef *gridRef) {
+  RmCamera cam{};
+  cam.initialFar = c.far;
+  int st = check_probes_args(c, cam);
+  if (st != RM_OK || c.numProbes == 0) return st;
+  if ((st = check_grid_ref(gridRef)) != RM_OK) return st;
+  const RmLightGridRef gr = *gridRef;
+  const uintptr_t o0 = (uintptr_t)c.d_out, o1 = o0 + (uintptr_t)c.numProbes * sizeof(RmLightProbe);
+  const uintptr_t g0 = (uintptr_t)gr.d_probes, g1 = g0 + (uintptr_t)gr.dims[0] * gr.dims[1] * gr.dims[2] * sizeof(RmLightProbe);
+  if (o0 < g1 && g0 < o1) {
+    set_error("d_out overlaps the grid's probe records: a bake must not read the grid it writes");
+    return RM_ERR_INVALID_ARGUMENT;
+  }
+  if ((st = check_probes_device(c)) != RM_OK || (st = check_grid_device(gr)) != RM_OK) return st;
+  const IndirectGridArgs ga = grid_args(gr);
+  const FrameClass fc = classify_frame(c.objs, c.numObjects, c.lights, c.numLights, c.g, c.s, 0);
+  const int bulbClass = bulb_class(fc, bulb_plain(c.objs, c.numObjects, c.g) != 0);
+  BlockCall b{c.objs, c.numObjects, c.g, c.s, c.stream, 24};
+  b.cam = &cam; b.lights = c.lights; b.numLights = c.numLights; b.res = &c.res;
+  return stage_block_launch(b, [&](const SceneBlock *sb, const SceneBlock *, void *) {
+    return launch_probes_indirect_kernel(sb, bulbClass, fc.envFeatures, fc.textured, fc.secondary, c.d_positions, c.numProbes, c.d_dirs,
+                                         c.numDirs, c.numSets, ga, c.d_out, c.stream);
   });
 }
 
@@ -458,6 +547,20 @@ int rm_light_probes(const float *d_positions, int numProbes, const RmProbeDir *d
                     const RmResources *res, RmLightProbe *d_out, void *stream) {
   return launch_probes(ProbesCall{d_positions, numProbes, d_dirs, numDirs, numSets, far, objs, numObjects, lights, numLights, g, s,
                                   res ? *res : kNoResources, d_out, static_cast<hipStream_t>(stream)});
+}
+
+int rm_shade_rays_indirect(const RmRay *d_rays, int numRays, float far, const RmObject *objs, int numObjects, const RmLight *lights,
+                           int numLights, const RmGlobals *g, const RmSettings *s, const RmResources *res, const RmLightGridRef *grid,
+                           float *d_rgba, void *stream) {
+  return launch_shade_indirect(ShadeCall{d_rays, numRays, far, objs, numObjects, lights, numLights, g, s, res ? *res : kNoResources, d_rgba,
+                                         nullptr, static_cast<hipStream_t>(stream)}, grid);
+}
+
+int rm_light_probes_indirect(const float *d_positions, int numProbes, const RmProbeDir *d_dirs, int numDirs, int numSets, float far,
+                             const RmObject *objs, int numObjects, const RmLight *lights, int numLights, const RmGlobals *g,
+                             const RmSettings *s, const RmResources *res, const RmLightGridRef *grid, RmLightProbe *d_out, void *stream) {
+  return launch_probes_indirect(ProbesCall{d_positions, numProbes, d_dirs, numDirs, numSets, far, objs, numObjects, lights, numLights, g, s,
+                                           res ? *res : kNoResources, d_out, static_cast<hipStream_t>(stream)}, grid);
 }
 
 // rm_sphere_directions (the header has the definition): host only, binary64 rounded once.  Spherical Fibonacci points and, per

@@ -656,6 +656,19 @@ class LightGrid:
                                              C.c_void_p(rec.data_ptr()) if n else None, r._stream()))
         return rec[:, 0:4], rec[:, 4], rec[:, 5].view(t.int32)
 
+    def ref(self, strength=1.0, facing=True, visible=None, normal_bias=None):
+        """The grid as rm_shade_rays_indirect and rm_light_probes_indirect take it → abi.RmLightGridRef (it holds device pointers
+        of this grid's tensors: keep the grid alive while a call that was given it runs).  facing, visible and normal_bias are
+        irradiance_visible's: visible=None takes the depth records where the grid has them."""
+        visible = self.depth is not None if visible is None else bool(visible)
+        if visible and self.depth is None:
+            raise ValueError("visible=True needs a grid with depth records (Renderer.light_grid_visible, LightGrid.set_depth)")
+        bias = self.normal_bias if normal_bias is None else normal_bias
+        bias = 0.25 * float(self.step.min()) if bias is None else float(bias)
+        return abi.RmLightGridRef(self.probes.data_ptr(), self.depth.data_ptr() if visible else None, (C.c_int32 * 3)(*self.dims),
+                                  (C.c_float * 3)(*self.origin), (C.c_float * 3)(*self.step), float(strength),
+                                  abi.RM_LIGHT_GRID_FACING if facing else 0, bias)
+
     def light_gbuffer(self, normal_depth, position, facing=True):
         """irradiance at the primary hits of render_gbuffer(position=True): normal_depth and position, float32 (N, H, W, 4) as it
         returns them, used in place → float32 (N, H, W, 4), e per pixel (a view of the (N·H·W, 8) result).  A miss has a zero normal,
@@ -1076,6 +1089,83 @@ class Renderer:
         bounce = albedo[ids.clamp(min=0).long()] * e[..., 0:3] * (float(strength) * float(tables.globals_.kd) / math.pi)
         frames[..., 0:3] += t.where(hit[..., None], bounce, t.zeros_like(bounce))
         return frames
+
+    def shade_rays_indirect(self, tables, settings, rays, grid, far=None, strength=1.0, facing=True, visible=None, normal_bias=None,
+                            out=None):
+        """rm_shade_rays_indirect: shade_rays' colour with the diffuse light of `grid` (a LightGrid) added at every ray's primary hit,
+        one lane per ray in ONE launch → float32 (n, 4).  rays and far: as shade_rays takes them.  At a hit the kernel looks the
+        grid up at the hit point and the bumped normal — LightGrid.irradiance_visible's lookup with `facing`, `visible` and
+        `normal_bias` —, clamps the irradiance at zero and adds strength · dif · e / π, dif the hit's diffuse colour WITH its
+        texture, times the trap palette on the Mandelbulb and the Menger sponge.  Misses, emissive hits, invalid rays and hits that
+        no probe reaches keep shade_rays' words; reflection and refraction bounces get no indirect light; there is no bright
+        output.  Terrain, clouds and sea are refused.  The definition, bit for bit, is in include/raymarcher_amd.h."""
+        t = self.torch
+        rays = self._rays(rays)
+        n = rays.shape[0]
+        out = self._out(out, (n, 4), t.float32)
+        res, _keep = self._resources(tables)
+        ref = grid.ref(strength, facing, visible, normal_bias)
+        check(lib().rm_shade_rays_indirect(C.c_void_p(rays.data_ptr()), n, tables.camera.initialFar if far is None else far, tables.objects,
+                                           tables.num_objects, tables.lights, tables.num_lights, C.byref(tables.globals_),
+                                           C.byref(settings), C.byref(res), C.byref(ref), C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def light_probes_indirect(self, tables, settings, positions, grid, directions=256, sets=1, far=None, table=None, strength=1.0,
+                              facing=True, visible=None, normal_bias=None, out=None):
+        """rm_light_probes_indirect: light_probes with every ray shaded as shade_rays_indirect shades it — the probes of the next
+        bounce, from the grid of the bounce before, in ONE launch → (sh, hits) as light_probes.  positions, directions, sets, far,
+        table: light_probes'; grid, strength, facing, visible, normal_bias: shade_rays_indirect's.  `out` must not be the grid's own
+        records: the call is refused, ping-pong two buffers (light_grid_bounces does).  The definition is in
+        include/raymarcher_amd.h."""
+        t = self.torch
+        dirs, sets = int(directions), int(sets)
+        pts = self._points(positions, "positions")
+        n = pts.shape[0]
+        table = self._probe_table(dirs, sets, table)
+        rec = self._out(out, (n, 40), t.float32)
+        res, _keep = self._resources(tables)
+        ref = grid.ref(strength, facing, visible, normal_bias)
+        check(lib().rm_light_probes_indirect(C.c_void_p(pts.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr()), dirs, sets,
+                                             tables.camera.initialFar if far is None else far, tables.objects, tables.num_objects,
+                                             tables.lights, tables.num_lights, C.byref(tables.globals_), C.byref(settings), C.byref(res),
+                                             C.byref(ref), C.c_void_p(rec.data_ptr()) if n else None, self._stream()))
+        return rec[:, 0:36].view(n, 9, 4), rec[:, 36].view(t.int32)
+
+    def light_grid_bounces(self, tables, settings, dims, bounces=2, bounds=None, directions=256, sets=1, far=None, mask_inside=0.0,
+                           visibility=True, strength=1.0):
+        """A LightGrid that holds `bounces` further bounces of diffuse light: one light_grid / light_grid_visible bake (direct
+        light at the probe rays' hits), then `bounces` calls of light_probes_indirect at the same positions, each reading the
+        grid of the call before it and writing the other of two record buffers.  The depth records and the inside mask are made
+        once, by the first bake, and carried along.  → the last LightGrid; bounces=0 is light_grid_visible's."""
+        t = self.torch
+        grid = self._light_grid(tables, settings, dims, bounds, directions, sets, far, mask_inside, bool(visibility))
+        if int(bounces) <= 0:
+            return grid
+        positions = self._points(light_grid_positions(grid.origin, grid.step, grid.dims), "positions")
+        masked = grid.probes[:, 36].view(t.int32) < 0
+        spare = t.empty_like(grid.probes)
+        for _ in range(int(bounces)):
+            _, hits = self.light_probes_indirect(tables, settings, positions, grid, directions=directions, sets=sets, far=far,
+                                                 strength=strength, out=spare)
+            hits[masked] = abi.RM_RAY_INVALID
+            nxt = LightGrid(self, spare, grid.origin, grid.step, grid.dims).set_depth(grid.depth, grid.normal_bias)
+            grid, spare = nxt, grid.probes
+        return grid
+
+    def render_lit(self, tables, settings, W, H, grid, cameras=None, strength=1.0):
+        """Frames lit by a LightGrid, bit-defined → float32 (N, H, W, 4), row 0 = bottom: camera_rays of every camera (None: the
+        scene's own, N = 1) in tile_order through shade_rays_indirect — ONE launch per frame — and scattered back to their pixels
+        on the device.  The successor of render_indirect: the albedo has the texture and the fractals' palette, and every word
+        is defined by include/raymarcher_amd.h."""
+        t = self.torch
+        cams = [tables.camera] if cameras is None else cameras
+        order = tile_order(W, H)
+        where = t.from_numpy(order).to(self.device)
+        out = t.empty((len(cams), H * W, 4), dtype=t.float32, device=self.device)
+        for f, cam in enumerate(cams):
+            out[f][where] = self.shade_rays_indirect(tables, settings, camera_rays(cam, W, H)[order], grid, far=cam.initialFar,
+                                                     strength=strength)
+        return out.view(len(cams), H, W, 4)
 
     def render_panorama(self, tables, settings, W, H, position, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), far=None):
         """A W×H equirectangular panorama of the scene from `position` → float32 (H, W, 4), row 0 = bottom: panorama_rays shaded
