@@ -2,16 +2,17 @@
 // streams or devices may be issued concurrently from different host threads; calls on ONE stream must come from one thread at a
 // time".  A stand-alone host over the C ABI, the HIP runtime and std::thread — no Python, whose threads contend only by accident.
 //
-//   gpu_threads <case> <scenes dir> <out dir>        cases: frames entries field release counted timing
+//   gpu_threads <case> <scenes dir> <out dir>        cases: frames entries field release counted timing light lattice
 //
-// A case is a set of FAMILIES, one per thread: a fixed sequence of ABI calls ("steps") over a set of output buffers, repeated for a
-// number of rounds, every round into buffers of its own.  The serial pass makes every step alone, on the default stream, and
+// A case is a set of FAMILIES, one per thread: a fixed sequence of ABI calls ("steps") over a set of output buffers, repeated for
+// a number of rounds, every round into buffers of its own.  The serial pass makes every step alone, on the default stream, and
 // keeps each buffer's bytes; it also dumps the whole frames it produced to <out dir> (NAME.scene: the tables, NAME.rgba: the
-// pixels), which the Python test holds to the oracle.  Then every thread creates its own non-blocking stream, waits at one
-// barrier and makes its calls in a tight loop, with steady_clock stamps around each.  After the join and a device synchronise
-// every buffer is read back: its guard bands (a poison word before and behind the payload) must be intact and its payload must
-// equal the serial bytes.  `overlap` is the share of calls whose interval intersects a call of another thread (the wait for the
-// device lock is inside the interval).  Process-wide switches are set once, before the barrier.
+// pixels), which the Python test holds to the oracle; the cases light and lattice dump their inputs and every serial record
+// (NAME.bin, the tables as NAME.tables), which the test holds to each entry's definition.  Then every thread creates its own non-
+// blocking stream, waits at one barrier and makes its calls in a tight loop, with steady_clock stamps around each.  After the
+// join and a device synchronise every buffer is read back: its guard bands (a poison word before and behind the payload) must be
+// intact and its payload must equal the serial bytes.  `overlap` is the share of calls whose interval intersects a call of
+// another thread (the wait for the device lock is inside the interval).  Process-wide switches are set once, before the barrier.
 // One JSON line on stdout: {"case", "ok", "threads", "calls", "overlap", "first_mismatch", "wall_ms"}; exit status 0 iff ok, 3 where a
 // HIP call failed or the library reported RM_ERR_DEVICE, 1 for any other mismatch.
 #include <hip/hip_runtime_api.h>
@@ -213,11 +214,33 @@ static bool menger_scene(const std::string &scenes, int W, int H, SceneData *out
   return true;
 }
 
-// the dump the Python test holds to the oracle: the tables as the ABI structs' bytes, then the pixels
-static bool dump_frame(const std::string &name, const SceneData &sc, const Bytes &rgba, const std::vector<uint8_t> *noise) {
+// terrain, sea, clouds and the sky over a sphere: the layer kernels and the noise texture
+static bool layers_scene(int W, int H, float iTime, SceneData *land) {
+  land->objs = {primitive(RM_SPHERE, 0.0f, 701.0f, -4.0f, 2.0f, 0.8f, 0.3f, 0.2f)};
+  land->objs[0].cReflective[0] = land->objs[0].cReflective[1] = land->objs[0].cReflective[2] = 0.6f;
+  land->lights = {directional(1.0f, 1.0f, 1.0f, -0.4f, -1.0f, -0.3f)};
+  land->g = plain_globals();
+  land->g.iTime = iTime;
+  rm_settings_default(&land->s);
+  land->s.features = RM_FEAT_SKY_BACKGROUND | RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA | RM_FEAT_PERLIN_BUMP;
+  land->s.enableReflection = 1;
+  land->W = W; land->H = H;
+  const RmCameraData cd = camera_data(0.0f, 700.0f, 6.0f, 0.0f, -0.2f, -1.0f, 0.87f);
+  if (rm_camera_build(&cd, land->W, land->H, 0.1f, 100.0f, nullptr, nullptr, &land->cam) != RM_OK) { mismatch(std::string("rm_camera_build: ") + rm_last_error()); return false; }
+  return true;
+}
+static void noise_texture(std::vector<uint8_t> *noise) {
+  noise->resize(256 * 256 * 4);
+  uint32_t lcg = 12345u;
+  for (size_t i = 0; i < noise->size(); i++) { lcg = lcg * 1664525u + 1013904223u; (*noise)[i] = (i % 4 == 3) ? 255 : (uint8_t)(lcg >> 24); }
+}
+
+// the dump the Python test holds to the oracle: the tables as the ABI structs' bytes, then the pixels.  `ext`: ".scene" for a frame
+// that the test renders with the oracle as it is; another extension where the tables are the input of records checked otherwise
+static bool dump_frame(const std::string &name, const SceneData &sc, const Bytes &rgba, const std::vector<uint8_t> *noise, const char *ext = ".scene") {
   const std::string base = g_outDir + "/" + g_case + "_" + name;
-  FILE *f = std::fopen((base + ".scene").c_str(), "wb");
-  if (!f) { mismatch("cannot write " + base + ".scene"); return false; }
+  FILE *f = std::fopen((base + ext).c_str(), "wb");
+  if (!f) { mismatch("cannot write " + base + ext); return false; }
   const int32_t head[6] = {sc.W, sc.H, sc.no(), sc.nl(), noise ? 1 : 0, 0};
   std::fwrite(head, sizeof(head), 1, f);
   std::fwrite(&sc.cam, sizeof(sc.cam), 1, f);
@@ -237,6 +260,23 @@ static bool dump_frame(const std::string &name, const SceneData &sc, const Bytes
     std::fclose(f);
   }
   return true;
+}
+// raw bytes of an input or of a serial record, for the Python test: <out dir>/<case>_NAME.bin
+static bool dump_bytes(const std::string &name, const void *p, size_t n) {
+  const std::string path = g_outDir + "/" + g_case + "_" + name + ".bin";
+  FILE *f = std::fopen(path.c_str(), "wb");
+  if (!f) { mismatch("cannot write " + path); return false; }
+  const bool ok = std::fwrite(p, 1, n, f) == n;
+  std::fclose(f);
+  if (!ok) mismatch("short write of " + path);
+  return ok;
+}
+template <class T>
+static bool dump_vector(const std::string &name, const std::vector<T> &v) { return dump_bytes(name, v.data(), v.size() * sizeof(T)); }
+static bool dump_device(const std::string &name, const void *d, size_t n) {
+  Bytes b(n);
+  HIP_TRY(hipMemcpy(b.data(), d, n, hipMemcpyDeviceToHost));
+  return dump_bytes(name, b.data(), n);
 }
 
 // ---------------------------------------------------------------------------------------------------- families
@@ -421,6 +461,66 @@ static Family render_family(const std::string &name, const SceneData *sc, int ro
   return f;
 }
 
+// every buffer of a variant's serial pass as <case>_NAME_v<variant>_b<buffer>.bin
+static std::function<bool(int, const std::vector<Bytes> &)> dump_buffers(const std::string &name) {
+  return [name](int v, const std::vector<Bytes> &e) {
+    for (size_t b = 0; b < e.size(); b++)
+      if (!dump_vector(name + "_v" + std::to_string(v) + "_b" + std::to_string(b), e[b])) return false;
+    return true;
+  };
+}
+
+// "The tables, g, s … are host memory, copied before return": the host arguments of a step of the light case live in a scratch copy
+// that the calling thread owns.  The thread fills it before the call and overwrites it with 0xFF bytes as soon as the call has
+// returned — in the serial pass and on the threads alike —, so a library that read one of them later would read a table of NaNs.
+struct HostArgs {
+  std::vector<RmObject> objs;
+  std::vector<RmLight> lights;
+  RmGlobals g;
+  RmSettings s;
+  int dims[3];
+  float origin[3], step[3];
+  RmLightGridRef grid;
+  int no() const { return (int)objs.size(); }
+  int nl() const { return (int)lights.size(); }
+  void spoil() {
+    std::memset(static_cast<void *>(objs.data()), 0xFF, objs.size() * sizeof(RmObject));
+    std::memset(static_cast<void *>(lights.data()), 0xFF, lights.size() * sizeof(RmLight));
+    std::memset(static_cast<void *>(&g), 0xFF, sizeof(g));
+    std::memset(static_cast<void *>(&s), 0xFF, sizeof(s));
+    std::memset(dims, 0xFF, sizeof(dims));
+    std::memset(origin, 0xFF, sizeof(origin));
+    std::memset(step, 0xFF, sizeof(step));
+    std::memset(static_cast<void *>(&grid), 0xFF, sizeof(grid));
+  }
+};
+// the light case's probe grid: 5×4×3 probes over the box of the driver's points
+static const int kGridDims[3] = {5, 4, 3};
+static const float kGridOrigin[3] = {-2.75f, -2.25f, -2.25f}, kGridStep[3] = {1.375f, 1.5f, 2.25f};
+static const float kLightFar = 100.0f, kDepthDistance = 8.0f, kNormalBias = 0.1f, kStrength = 0.8f;
+// the lattice case's rm_field_ambient: origins a third of a step off the surface, rays as long as the lattice is deep
+static const float kAmbBias = 0.1f, kAmbDistance = 2.0f;
+static HostArgs &host_args(const SceneData &sc, const RmLightProbe *probes, const RmProbeDepth *depth, uint32_t flags) {
+  thread_local HostArgs a;
+  a.objs = sc.objs;
+  a.lights = sc.lights;
+  a.g = sc.g;
+  a.s = sc.s;
+  std::memcpy(a.dims, kGridDims, sizeof(a.dims));
+  std::memcpy(a.origin, kGridOrigin, sizeof(a.origin));
+  std::memcpy(a.step, kGridStep, sizeof(a.step));
+  std::memset(&a.grid, 0, sizeof(a.grid));
+  a.grid.d_probes = probes;
+  a.grid.d_depth = depth;
+  std::memcpy(a.grid.dims, kGridDims, sizeof(a.grid.dims));
+  std::memcpy(a.grid.origin, kGridOrigin, sizeof(a.grid.origin));
+  std::memcpy(a.grid.step, kGridStep, sizeof(a.grid.step));
+  a.grid.strength = kStrength;
+  a.grid.flags = flags;
+  a.grid.normalBias = kNormalBias;
+  return a;
+}
+
 int main(int argc, char **argv) {
   if (argc < 4) { std::fprintf(stderr, "usage: gpu_threads <case> <scenes dir> <out dir>\n"); return 2; }
   g_case = argv[1];
@@ -441,21 +541,9 @@ int main(int argc, char **argv) {
     lit.s.enableAmbientOcclusion = 1;
     lit.s.enableReflection = 0;
     lit.s.numReflection = 8;
-    // terrain, sea, clouds and the sky over a sphere: the layer kernels and the noise texture
-    land.objs = {primitive(RM_SPHERE, 0.0f, 701.0f, -4.0f, 2.0f, 0.8f, 0.3f, 0.2f)};
-    land.objs[0].cReflective[0] = land.objs[0].cReflective[1] = land.objs[0].cReflective[2] = 0.6f;
-    land.lights = {directional(1.0f, 1.0f, 1.0f, -0.4f, -1.0f, -0.3f)};
-    land.g = plain_globals();
-    land.g.iTime = 0.7f;
-    rm_settings_default(&land.s);
-    land.s.features = RM_FEAT_SKY_BACKGROUND | RM_FEAT_TERRAIN | RM_FEAT_CLOUD | RM_FEAT_SEA | RM_FEAT_PERLIN_BUMP;
-    land.s.enableReflection = 1;
-    land.W = 72; land.H = 40;
-    const RmCameraData cd = camera_data(0.0f, 700.0f, 6.0f, 0.0f, -0.2f, -1.0f, 0.87f);
-    if (rm_camera_build(&cd, land.W, land.H, 0.1f, 100.0f, nullptr, nullptr, &land.cam) != RM_OK) return give_up(std::string("rm_camera_build: ") + rm_last_error());
-    static std::vector<uint8_t> noise(256 * 256 * 4);
-    uint32_t lcg = 12345u;
-    for (size_t i = 0; i < noise.size(); i++) { lcg = lcg * 1664525u + 1013904223u; noise[i] = (i % 4 == 3) ? 255 : (uint8_t)(lcg >> 24); }
+    if (!layers_scene(72, 40, 0.7f, &land)) return finish(0, 0, 0.0, 0.0);
+    static std::vector<uint8_t> noise;
+    noise_texture(&noise);
     uint8_t *dNoise = nullptr;
     if (!upload(noise, &dNoise)) return finish(0, 0, 0.0, 0.0);
     static RmResources res;
@@ -559,6 +647,21 @@ int main(int argc, char **argv) {
   }
   static float *dPoints = nullptr;
   if (!upload(hostPoints, &dPoints)) return finish(0, 0, 0.0, 0.0);
+  // 4096 unit normals, uniform over the sphere (light and lattice)
+  static std::vector<float> hostNormals((size_t)nRays * 4);
+  {
+    uint32_t lcg = 4242u;
+    const auto rnd = [&lcg] { lcg = lcg * 1664525u + 1013904223u; return (float)(lcg >> 8) * (1.0f / 16777216.0f); };
+    for (int i = 0; i < nRays; i++) {
+      const float z = 2.0f * rnd() - 1.0f, phi = 6.2831853f * rnd(), r = std::sqrt(std::fmax(0.0f, 1.0f - z * z));
+      float n[3] = {r * std::cos(phi), r * std::sin(phi), z};
+      const float len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+      for (int a = 0; a < 3; a++) hostNormals[(size_t)i * 4 + a] = n[a] / len;
+      hostNormals[(size_t)i * 4 + 3] = 0.0f;
+    }
+  }
+  static float *dNormals = nullptr;
+  if (!upload(hostNormals, &dNormals)) return finish(0, 0, 0.0, 0.0);
   // the 17×13×9 lattice and the 2×2×1 blocks (17×17×9 points) over the primitives
   static const float lo[3] = {-2.5f, -2.0f, -2.0f}, step[3] = {0.3125f, 1.0f / 3.0f, 0.5f};
   static const float blo[3] = {-2.5f, -2.5f, -2.0f}, bstep[3] = {0.3125f, 0.3125f, 0.5f};
@@ -698,7 +801,7 @@ int main(int argc, char **argv) {
   }
 
   // ================================================================================================ field
-  if (g_case == "field") {
+  if (g_case == "field" || g_case == "lattice") {
     // one dense and one block handle over the primitives' lattices, built here, on the main thread
     static float *dDist = nullptr, *dBDist = nullptr;
     static int32_t *dIds = nullptr, *dBIds = nullptr, *dBlocks = nullptr;
@@ -718,7 +821,59 @@ int main(int argc, char **argv) {
         rm_field_create_blocks(dBDist, dBIds, dBlocks, (int)listed, mx, my, mz, blo, bstep, nullptr, &blocks) != RM_OK || hipDeviceSynchronize() != hipSuccess)
       return give_up(std::string("rm_field_create: ") + rm_last_error());
     std::vector<Family> fams;
-    for (int t = 0; t < 4; t++) {
+    if (g_case == "lattice") {
+      // rm_field_ambient on both handles and the handle-free lattice entries, four threads with the same family.  The block entries
+      // take two lists in turn, the full one and the one without its last block, back to back on the thread's stream: the block
+      // map in the stream's workspace is rebuilt behind a query that still reads the previous one.
+      if (listed < 2) return give_up("the block list has " + std::to_string(listed) + " entries: the case needs two lists");
+      const int nAmb = 256, full = (int)listed, shorter = (int)listed - 1;
+      static std::vector<float> hemi64((size_t)3 * 64 * 4), hemi256((size_t)256 * 4);
+      static float *dHemi64 = nullptr, *dHemi256 = nullptr, *dVirtual = nullptr;
+      static int32_t *dVirtualIds = nullptr;
+      if (rm_hemisphere_directions(64, 3, hemi64.data()) != RM_OK || rm_hemisphere_directions(256, 1, hemi256.data()) != RM_OK)
+        return give_up(std::string("rm_hemisphere_directions: ") + rm_last_error());
+      if (!upload(hemi64, &dHemi64) || !upload(hemi256, &dHemi256)) return finish(0, 0, 0.0, 0.0);
+      // the blocks' virtual lattice as a dense one: what the Python test hands to the definition of the block entries
+      const int vx = 8 * mx + 1, vy = 8 * my + 1, vz = 8 * mz + 1, vPoints = vx * vy * vz;
+      if (hipMalloc(reinterpret_cast<void **>(&dVirtual), (size_t)vPoints * 4) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&dVirtualIds), (size_t)vPoints * 4) != hipSuccess)
+        return give_up("hipMalloc of the virtual lattice failed");
+      if (rm_sdf_grid(prim.objs.data(), prim.no(), &prim.g, &prim.s, blo, bstep, vx, vy, vz, dVirtual, dVirtualIds, nullptr) != RM_OK || hipDeviceSynchronize() != hipSuccess)
+        return give_up(std::string("the virtual lattice: ") + rm_last_error());
+      const int32_t head[8] = {nRays, nAmb, full, shorter, nx, ny, nz, maxBlocks};
+      const float params[14] = {lo[0], lo[1], lo[2], step[0], step[1], step[2], blo[0], blo[1], blo[2], bstep[0], bstep[1], bstep[2], kAmbBias, kAmbDistance};
+      if (!dump_bytes("head", head, sizeof(head)) || !dump_bytes("params", params, sizeof(params)) || !dump_vector("points", hostPoints) || !dump_vector("normals", hostNormals) || !dump_vector("rays", hostRays[0]) ||
+          !dump_vector("hemi64", hemi64) || !dump_vector("hemi256", hemi256) || !dump_device("dense", dDist, (size_t)points * 4) ||
+          !dump_device("dense_ids", dIds, (size_t)points * 4) || !dump_device("virtual", dVirtual, (size_t)vPoints * 4) ||
+          !dump_device("virtual_ids", dVirtualIds, (size_t)vPoints * 4) || !dump_device("blocks", dBlocks, (size_t)full * 16))
+        return finish(0, 0, 0.0, 0.0);
+      for (int t = 0; t < 4; t++) {
+        Family f;
+        f.name = "lattice";
+        f.rounds = 5;
+        const size_t rec = (size_t)nRays * 32, amb = (size_t)nAmb * 32;
+        f.bufBytes = {amb, amb, amb, amb, rec, rec, rec, rec, rec, rec, (size_t)maxBlocks * 16, 2 * sizeof(uint32_t)};
+        const auto ambient = [=](RmField **h, bool soft, int b) {
+          return Step{soft ? "rm_field_ambient soft" : "rm_field_ambient hard", [=](const Ctx &c) {
+            return soft ? rm_field_ambient(*h, dPoints, dNormals, nAmb, dHemi64, 64, 3, kAmbBias, kAmbDistance, 0.0f, 64, RM_AMBIENT_SOFT, static_cast<RmAmbient *>(c.buf[b]), S(c))
+                        : rm_field_ambient(*h, dPoints, nullptr, nAmb, dHemi256, 256, 1, kAmbBias, kAmbDistance, 0.0f, 64, RM_AMBIENT_HARD, static_cast<RmAmbient *>(c.buf[b]), S(c)); }, nullptr}; };
+        const auto sampleBlocks = [=](int count, int b) {
+          return Step{"rm_sdf_sample_blocks", [=](const Ctx &c) {
+            return rm_sdf_sample_blocks(dPoints, nRays, dBDist, dBIds, dBlocks, count, mx, my, mz, blo, bstep, static_cast<RmFieldSample *>(c.buf[b]), S(c)); }, nullptr}; };
+        const auto traceBlocks = [=](int count, int b) {
+          return Step{"rm_sdf_trace_blocks", [=](const Ctx &c) {
+            return rm_sdf_trace_blocks(dRays[0], nRays, dBDist, dBIds, dBlocks, count, mx, my, mz, blo, bstep, 0.0f, 128, 0u, static_cast<RmRayHit *>(c.buf[b]), S(c)); }, nullptr}; };
+        f.steps = {ambient(&dense, true, 0), ambient(&blocks, true, 1), ambient(&dense, false, 2), ambient(&blocks, false, 3),
+                   Step{"rm_sdf_sample", [=](const Ctx &c) { return rm_sdf_sample(dPoints, nRays, dDist, dIds, nx, ny, nz, lo, step, static_cast<RmFieldSample *>(c.buf[4]), S(c)); }, nullptr},
+                   Step{"rm_sdf_trace", [=](const Ctx &c) { return rm_sdf_trace(dRays[0], nRays, dDist, dIds, nx, ny, nz, lo, step, 0.0f, 128, 0u, static_cast<RmRayHit *>(c.buf[5]), S(c)); }, nullptr},
+                   sampleBlocks(full, 6), sampleBlocks(shorter, 7), traceBlocks(full, 8), traceBlocks(shorter, 9),
+                   Step{"rm_sdf_blocks_select_pruned", [=](const Ctx &c) {
+                     return rm_sdf_blocks_select_pruned(prim.objs.data(), prim.no(), &prim.g, &prim.s, blo, bstep, mx, my, mz, 0.0f, 1.0f, 1.0f, maxBlocks, static_cast<int32_t *>(c.buf[10]),
+                                                        static_cast<uint32_t *>(c.buf[11]), S(c)); }, nullptr}};
+        if (t == 0) f.dump = dump_buffers("lattice");
+        fams.push_back(f);
+      }
+    }
+    for (int t = 0; t < 4 && g_case == "field"; t++) {
       Family f;
       f.name = "queries";
       f.rounds = 5;
@@ -734,6 +889,183 @@ int main(int argc, char **argv) {
     rm_field_destroy(dense);
     rm_field_destroy(blocks);
     return rc;
+  }
+
+  // ================================================================================================ light
+  if (g_case == "light") {
+    const int nProbes = kGridDims[0] * kGridDims[1] * kGridDims[2];
+    // read-only inputs, built here on the main thread: the grid's positions, the two direction tables, the depth weights
+    static std::vector<float> gridPos((size_t)nProbes * 4);
+    for (int k = 0; k < kGridDims[2]; k++)
+      for (int j = 0; j < kGridDims[1]; j++)
+        for (int i = 0; i < kGridDims[0]; i++) {
+          float *p = &gridPos[(size_t)(i + kGridDims[0] * (j + kGridDims[1] * k)) * 4];
+          p[0] = kGridOrigin[0] + (float)i * kGridStep[0]; p[1] = kGridOrigin[1] + (float)j * kGridStep[1]; p[2] = kGridOrigin[2] + (float)k * kGridStep[2];
+          p[3] = 1.0f;
+        }
+    static std::vector<RmProbeDir> dirs64(3 * 64), dirs128(128);
+    static std::vector<float> weights64((size_t)3 * 64 * RM_PROBE_DEPTH_TEXELS);
+    if (rm_sphere_directions(64, 3, dirs64.data()) != RM_OK || rm_sphere_directions(128, 1, dirs128.data()) != RM_OK ||
+        rm_probe_depth_weights(dirs64.data(), 64, 3, 50.0f, weights64.data()) != RM_OK)
+      return give_up(std::string("direction tables: ") + rm_last_error());
+    static float *dPos = nullptr, *dWeights = nullptr;
+    static RmProbeDir *dDirs64 = nullptr, *dDirs128 = nullptr;
+    if (!upload(gridPos, &dPos) || !upload(dirs64, &dDirs64) || !upload(dirs128, &dDirs128) || !upload(weights64, &dWeights)) return finish(0, 0, 0.0, 0.0);
+    // per scene the shared grid, baked at K = 64, and its depth records
+    static RmLightProbe *dGrid[2] = {nullptr, nullptr};
+    static RmProbeDepth *dDepth[2] = {nullptr, nullptr};
+    for (int v = 0; v < 2; v++) {
+      const SceneData &s = *two[v];
+      if (hipMalloc(reinterpret_cast<void **>(&dGrid[v]), (size_t)nProbes * sizeof(RmLightProbe)) != hipSuccess ||
+          hipMalloc(reinterpret_cast<void **>(&dDepth[v]), (size_t)nProbes * sizeof(RmProbeDepth)) != hipSuccess)
+        return give_up("hipMalloc of the shared grid failed");
+      if (rm_light_probes(dPos, nProbes, dDirs64, 64, 3, kLightFar, s.objs.data(), s.no(), s.lights.data(), s.nl(), &s.g, &s.s, nullptr, dGrid[v], nullptr) != RM_OK ||
+          rm_light_probes_depth(dPos, nProbes, dDirs64, dWeights, 64, 3, kDepthDistance, s.objs.data(), s.no(), &s.g, &s.s, dDepth[v], nullptr) != RM_OK ||
+          hipDeviceSynchronize() != hipSuccess)
+        return give_up(std::string("the shared grid: ") + rm_last_error());
+    }
+    // the layer families' table (terrain + sea under the sky, two times of day), its rays and the noise texture
+    static SceneData land[2];
+    static std::vector<uint8_t> noise;
+    static std::vector<RmRay> landRays((size_t)nRays);
+    static RmRay *dLandRays = nullptr;
+    static RmResources res;
+    noise_texture(&noise);
+    uint8_t *dNoise = nullptr;
+    if (!layers_scene(64, 64, 0.7f, &land[0]) || !layers_scene(64, 64, 1.9f, &land[1]) || !upload(noise, &dNoise)) return finish(0, 0, 0.0, 0.0);
+    if (rm_camera_rays(&land[0].cam, 64, 64, nullptr, nRays, landRays.data()) != RM_OK) return give_up(std::string("rm_camera_rays: ") + rm_last_error());
+    if (!upload(landRays, &dLandRays)) return finish(0, 0, 0.0, 0.0);
+    std::memset(&res, 0, sizeof(res));
+    res.noise.pixels = dNoise; res.noise.width = 256; res.noise.height = 256;
+    // the inputs, for the Python test that holds the serial records to each entry's definition
+    const int32_t head[4] = {nRays, nProbes, kGridDims[0] | kGridDims[1] << 8 | kGridDims[2] << 16, 0};
+    const float params[10] = {kGridOrigin[0], kGridOrigin[1], kGridOrigin[2], kGridStep[0], kGridStep[1], kGridStep[2], kLightFar, kDepthDistance, kNormalBias, kStrength};
+    bool dumped = dump_bytes("head", head, sizeof(head)) && dump_bytes("params", params, sizeof(params)) && dump_vector("positions", gridPos) &&
+                  dump_vector("dirs64", dirs64) && dump_vector("dirs128", dirs128) && dump_vector("weights64", weights64) && dump_vector("points", hostPoints) &&
+                  dump_vector("normals", hostNormals);
+    for (int v = 0; v < 2 && dumped; v++)
+      dumped = dump_vector("rays_v" + std::to_string(v), hostRays[v]) && dump_device("grid_v" + std::to_string(v), dGrid[v], (size_t)nProbes * sizeof(RmLightProbe)) &&
+               dump_device("depth_v" + std::to_string(v), dDepth[v], (size_t)nProbes * sizeof(RmProbeDepth)) &&
+               dump_frame("scene_v" + std::to_string(v), *two[v], Bytes(), nullptr, ".tables");
+    if (!dumped) return finish(0, 0, 0.0, 0.0);
+
+    const size_t probeBytes = (size_t)nProbes * sizeof(RmLightProbe), depthBytes = (size_t)nProbes * sizeof(RmProbeDepth), lightBytes = (size_t)nRays * sizeof(RmGridLight);
+    const auto done = [](HostArgs &a, int rc) { a.spoil(); return rc; };  // the call has returned: its host arguments are overwritten
+    const auto probes = [=](RmProbeDir **dirs, int K, int sets, int b) {
+      return Step{"rm_light_probes", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant & 1], nullptr, nullptr, 0);
+        return done(a, rm_light_probes(dPos, nProbes, *dirs, K, sets, kLightFar, a.objs.data(), a.no(), a.lights.data(), a.nl(), &a.g, &a.s, nullptr, static_cast<RmLightProbe *>(c.buf[b]), S(c))); }, nullptr}; };
+    std::vector<Family> fams;
+    {
+      Family f; f.name = "probes_64"; f.rounds = 8; f.variants = 2; f.bufBytes = {probeBytes};
+      f.steps = {probes(&dDirs64, 64, 3, 0)};
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      Family f; f.name = "probes_128"; f.rounds = 8; f.variants = 2; f.bufBytes = {probeBytes};
+      f.steps = {probes(&dDirs128, 128, 1, 0)};
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      // the lookup reads the round's own depth records, behind their bake on the same stream with no synchronise between the two
+      Family f; f.name = "depth"; f.rounds = 8; f.variants = 2; f.bufBytes = {depthBytes, lightBytes};
+      f.steps.push_back({"rm_light_probes_depth", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant], nullptr, nullptr, 0);
+        return done(a, rm_light_probes_depth(dPos, nProbes, dDirs64, dWeights, 64, 3, kDepthDistance, a.objs.data(), a.no(), &a.g, &a.s, static_cast<RmProbeDepth *>(c.buf[0]), S(c))); }, nullptr});
+      f.steps.push_back({"rm_light_grid_irradiance_visible", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant], nullptr, nullptr, 0);
+        return done(a, rm_light_grid_irradiance_visible(dGrid[c.variant], static_cast<RmProbeDepth *>(c.buf[0]), a.dims, a.origin, a.step, dPoints, dNormals, nRays, RM_LIGHT_GRID_FACING, kNormalBias,
+                                                        static_cast<RmGridLight *>(c.buf[1]), S(c))); }, nullptr});
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      Family f; f.name = "lookups"; f.rounds = 8; f.variants = 2; f.bufBytes = {lightBytes, lightBytes, lightBytes};
+      const auto plain = [=](uint32_t flags, int b) {
+        return Step{"rm_light_grid_irradiance", [=](const Ctx &c) {
+          HostArgs &a = host_args(*two[c.variant], nullptr, nullptr, 0);
+          return done(a, rm_light_grid_irradiance(dGrid[c.variant], a.dims, a.origin, a.step, dPoints, dNormals, nRays, flags, static_cast<RmGridLight *>(c.buf[b]), S(c))); }, nullptr}; };
+      f.steps = {plain(RM_LIGHT_GRID_FACING, 0), plain(0u, 1)};
+      f.steps.push_back({"rm_light_grid_irradiance_visible", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant], nullptr, nullptr, 0);
+        return done(a, rm_light_grid_irradiance_visible(dGrid[c.variant], dDepth[c.variant], a.dims, a.origin, a.step, dPoints, dNormals, nRays, RM_LIGHT_GRID_FACING, kNormalBias,
+                                                        static_cast<RmGridLight *>(c.buf[2]), S(c))); }, nullptr});
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      // variant: bit 0 the scene, bit 1 whether the grid comes with its depth records — one round in two of each scene
+      Family f; f.name = "indirect"; f.rounds = 8; f.variants = 4; f.bufBytes = {(size_t)nRays * 16, probeBytes};
+      f.steps.push_back({"rm_shade_rays_indirect", [=](const Ctx &c) {
+        const int v = c.variant & 1;
+        HostArgs &a = host_args(*two[v], dGrid[v], (c.variant & 2) ? dDepth[v] : nullptr, RM_LIGHT_GRID_FACING);
+        return done(a, rm_shade_rays_indirect(dRays[v], nRays, kLightFar, a.objs.data(), a.no(), a.lights.data(), a.nl(), &a.g, &a.s, nullptr, &a.grid, F(c, 0), S(c))); }, nullptr});
+      f.steps.push_back({"rm_light_probes_indirect", [=](const Ctx &c) {
+        const int v = c.variant & 1;
+        HostArgs &a = host_args(*two[v], dGrid[v], (c.variant & 2) ? dDepth[v] : nullptr, RM_LIGHT_GRID_FACING);
+        return done(a, rm_light_probes_indirect(dPos, nProbes, dDirs64, 64, 3, kLightFar, a.objs.data(), a.no(), a.lights.data(), a.nl(), &a.g, &a.s, nullptr, &a.grid,
+                                                static_cast<RmLightProbe *>(c.buf[1]), S(c))); }, nullptr});
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      // three staged blocks on one stream with two device-side dependencies and no synchronise: a bake, a second bounce that reads
+      // it through an RmLightGridRef, rays lit by the second bounce
+      Family f; f.name = "bounce_chain"; f.rounds = 8; f.variants = 2; f.bufBytes = {probeBytes, probeBytes, (size_t)nRays * 16};
+      f.steps = {probes(&dDirs64, 64, 3, 0)};
+      f.steps.push_back({"rm_light_probes_indirect", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant], static_cast<RmLightProbe *>(c.buf[0]), nullptr, RM_LIGHT_GRID_FACING);
+        return done(a, rm_light_probes_indirect(dPos, nProbes, dDirs64, 64, 3, kLightFar, a.objs.data(), a.no(), a.lights.data(), a.nl(), &a.g, &a.s, nullptr, &a.grid,
+                                                static_cast<RmLightProbe *>(c.buf[1]), S(c))); }, nullptr});
+      f.steps.push_back({"rm_shade_rays_indirect", [=](const Ctx &c) {
+        HostArgs &a = host_args(*two[c.variant], static_cast<RmLightProbe *>(c.buf[1]), nullptr, RM_LIGHT_GRID_FACING);
+        return done(a, rm_shade_rays_indirect(dRays[c.variant], nRays, kLightFar, a.objs.data(), a.no(), a.lights.data(), a.nl(), &a.g, &a.s, nullptr, &a.grid, F(c, 2), S(c))); }, nullptr});
+      f.dump = dump_buffers(f.name);
+      fams.push_back(f);
+    }
+    {
+      Family f; f.name = "layers"; f.rounds = 8; f.variants = 2; f.bufBytes = {(size_t)nRays * 16, (size_t)nRays * 16, (size_t)nRays * 32};
+      f.steps.push_back({"rm_shade_rays_layers", [=](const Ctx &c) { const SceneData &s = land[c.variant];
+        return rm_shade_rays_layers(dLandRays, nRays, kLightFar, 64, s.objs.data(), s.no(), s.lights.data(), s.nl(), &s.g, &s.s, &res, F(c, 0), F(c, 1), S(c)); }, nullptr});
+      f.steps.push_back({"rm_trace_rays_layers", [=](const Ctx &c) { const SceneData &s = land[c.variant];
+        return rm_trace_rays_layers(dLandRays, nRays, 64, s.objs.data(), s.no(), &s.g, &s.s, RM_TRACE_CLOSEST, static_cast<RmRayHit *>(c.buf[2]), S(c)); }, nullptr});
+      fams.push_back(f);
+    }
+    {
+      // the single-frame ring and the tuner beside the batch ring: the frame as rm_render_res and rm_render_ex give it, then as the
+      // two shards of a row-tile partition, de-interleaved, converted to 8 bits both ways round, and one post pass of a batch.
+      // Buffers: 0 frame, 1 frame and 2 bright of rm_render_ex, 3 the two shards' slots, 4 the de-interleaved frame, 5 the slots
+      // in 8 bits, 6 their de-interleaved frame, 7 buffer 4 in 8 bits, 8 the post pass.  The serial frame is dumped for the oracle.
+      const int tileRows = 8, slotRows = rm_gather_slot_rows(bulb.H, tileRows, 2);
+      if (slotRows < rm_shard_rows(bulb.H, tileRows, 0, 2) || slotRows < rm_shard_rows(bulb.H, tileRows, 1, 2) || slotRows > bulb.H)
+        return give_up("rm_gather_slot_rows: " + std::to_string(slotRows) + " rows");
+      const size_t slotFloats = (size_t)slotRows * bulb.W * 4, px = (size_t)bulb.W * bulb.H;
+      Family f = render_family("render", &bulb, 4, nullptr, 0, false, 1, nullptr);
+      f.bufBytes = {px * 16, px * 16, px * 16, 2 * slotFloats * 4, px * 16, 2 * slotFloats, px * 4, px * 4, px * 16};
+      f.steps.push_back({"rm_render_ex", [](const Ctx &c) {
+        return rm_render_ex(&bulb.cam, bulb.objs.data(), bulb.no(), bulb.lights.data(), bulb.nl(), &bulb.g, &bulb.s, nullptr, 0, bulb.W, bulb.H, 0, bulb.H, F(c, 1), F(c, 2), S(c)); }, nullptr});
+      f.steps.push_back({"rm_render_tiles", [=](const Ctx &c) {
+        return rm_render_tiles(&bulb.cam, bulb.objs.data(), bulb.no(), bulb.lights.data(), bulb.nl(), &bulb.g, &bulb.s, bulb.W, bulb.H, tileRows, 0, 2, F(c, 3), nullptr, S(c)); }, nullptr});
+      f.steps.push_back({"rm_render_tiles_res", [=](const Ctx &c) {
+        return rm_render_tiles_res(&bulb.cam, bulb.objs.data(), bulb.no(), bulb.lights.data(), bulb.nl(), &bulb.g, &bulb.s, nullptr, bulb.W, bulb.H, tileRows, 1, 2, F(c, 3) + slotFloats,
+                                   nullptr, S(c)); }, nullptr});
+      f.steps.push_back({"rm_deinterleave", [=](const Ctx &c) { return rm_deinterleave(F(c, 3), F(c, 4), bulb.W, bulb.H, tileRows, 2, slotRows, S(c)); }, nullptr});
+      f.steps.push_back({"rm_tiles_to_rgba8", [=](const Ctx &c) { return rm_tiles_to_rgba8(F(c, 3), static_cast<uint8_t *>(c.buf[5]), bulb.W, 2 * slotRows, S(c)); }, nullptr});
+      f.steps.push_back({"rm_deinterleave_rgba8", [=](const Ctx &c) {
+        return rm_deinterleave_rgba8(static_cast<uint8_t *>(c.buf[5]), static_cast<uint8_t *>(c.buf[6]), bulb.W, bulb.H, tileRows, 2, slotRows, 1, S(c)); }, nullptr});
+      f.steps.push_back({"rm_frame_to_rgba8", [](const Ctx &c) { return rm_frame_to_rgba8(F(c, 4), static_cast<uint8_t *>(c.buf[7]), bulb.W, bulb.H, S(c)); }, nullptr});
+      f.steps.push_back({"rm_post_process_batch", [](const Ctx &c) {
+        RmPostSettings ps;
+        std::memset(&ps, 0, sizeof(ps));
+        ps.enableBloom = ps.enableHDR = ps.enableFXAA = 1;
+        ps.exposure = 0.8f;
+        return rm_post_process_batch(F(c, 1), F(c, 2), F(c, 8), bulb.W, bulb.H, 1, &ps, 1, S(c)); }, nullptr});
+      f.dump = [](int v, const std::vector<Bytes> &e) { return dump_frame("render", bulb, e[0], nullptr, ".tables") && dump_buffers("render")(v, e); };
+      fams.push_back(f);
+    }
+    return run_case(fams, nullptr, nullptr);
   }
 
   // ================================================================================================ release

@@ -13,6 +13,8 @@ import light_depth_helpers as MD
 import light_depth_spec as D
 import light_grid_helpers as MG
 import light_grid_spec as G
+import shade_helpers as S
+from raymarcher_amd import abi
 
 f32 = np.float32
 CPU_SRC = os.path.join(h.ROOT, "tests", "light_bounce_spec", "rm_light_bounce_cpu.cpp")
@@ -73,3 +75,61 @@ def ray_inputs(name, n):
         has_term[rng.choice(np.arange(1, n - 1), n // 8, replace=False)] = 0
         palette[0:3] = (B.PLAIN, B.BULB, B.SPONGE)
     return colour, dif, c, palette, has_term
+
+
+# ---------------------------------------------------------------- shade_rays_indirect through the shipped entries
+def object_fields(scene):
+    _, objs, no = scene[:3]
+    m = max(no, 1)
+    return {"cDiffuse": np.array([list(objs[i].cDiffuse) for i in range(m)], f32), "type": np.array([objs[i].type for i in range(m)]),
+            "isEmissive": np.array([objs[i].isEmissive for i in range(m)]), "texLoc": np.array([objs[i].texLoc for i in range(m)]),
+            "repeatU": np.array([objs[i].repeatU for i in range(m)], np.float64), "repeatV": np.array([objs[i].repeatV for i in range(m)], np.float64),
+            "blend": np.array([objs[i].blend for i in range(m)], np.float64),
+            "invModel": np.array([np.array(list(objs[i].invModel), np.float64).reshape(4, 4).T for i in range(m)])}
+
+
+def palette_tables(scene, s, res):
+    """The copy of the tables whose shade_rays colour is the palette factor alone: no lights, ka = 1, cAmbient = 1, AO, reflection
+    and refraction off — Phong is (1·1)·1 = 1 exactly, so the colour of a hit is 8c on the bulb, c on the sponge, 1 elsewhere."""
+    cam, objs, no, _, _, g = scene[:6]
+    o = (abi.RmObject * max(no, 1))(*[abi.RmObject.from_buffer_copy(bytes(objs[i])) for i in range(no)])
+    for i in range(no):
+        for k in range(3):
+            o[i].cAmbient[k] = 1.0
+    g2 = abi.RmGlobals.from_buffer_copy(bytes(g))
+    g2.ka = 1.0
+    s2 = abi.RmSettings.from_buffer_copy(bytes(s))
+    s2.enableAmbientOcclusion = s2.enableReflection = s2.enableRefraction = 0
+    return S.tables_of((cam, o, no, None, 0, g2), res), s2
+
+
+def composed_indirect(renderer, scene, s, res, rays, grid, facing, bias, strength, far):
+    """shade_rays_indirect through the shipped entries — shade_rays, trace_rays with tMax = far, the grid's lookup, a second
+    shade_rays call for the palette factor and the NumPy term — → (want (n, 4), on (n): the rays with a term, textured (n): the
+    hits of textured objects, whose dif the composition does not have bit for bit, parts: what went into it).  scene, s, res: a
+    case of shade_helpers.CASES or any other tables; grid: a LightGrid."""
+    t = S.tables_of(scene, res)
+    rays = np.array(rays)
+    n = len(rays)
+    colour = renderer.shade_rays(t, s, rays, far=far).cpu().numpy()
+    probe = rays.copy()
+    probe[:, 3] = f32(far)
+    normal, _, point, obj = (a.cpu().numpy() for a in renderer.trace_rays(t, s, probe))
+    o = object_fields(scene)
+    k = np.maximum(obj, 0)
+    has_term = (obj >= 0) & (o["isEmissive"][k] == 0)
+    p4, n4 = np.zeros((n, 4), f32), np.zeros((n, 4), f32)
+    p4[:, 0:3], n4[:, 0:3] = point, normal
+    e, _, probes = grid.irradiance_visible(p4, n4, facing=facing, visible=grid.depth is not None, normal_bias=bias)
+    e, probes = e.cpu().numpy(), probes.cpu().numpy()
+    tp, sp = palette_tables(scene, s, res)
+    pal = renderer.shade_rays(tp, sp, rays, far=far).cpu().numpy()[:, 0:3]
+    kind = np.where(o["type"][k] == abi.RM_MANDELBULB, B.BULB, np.where(o["type"][k] == abi.RM_MENGERSPONGE, B.SPONGE, B.PLAIN))
+    plain = has_term & (kind == B.PLAIN)
+    assert (pal[plain] == f32(1)).all(), "the palette call's colour is exactly 1 on a hit of anything but the two fractals"
+    c = np.where((kind == B.BULB)[:, None], pal * f32(0.125), pal).astype(f32)  # 8c → c, exact
+    dif = (f32(scene[5].kd) * o["cDiffuse"][k]).astype(f32)
+    want = B.term(colour, has_term, probes, e, dif, B.scale_of(strength), kind, c)
+    on = has_term & (probes > 0)
+    textured = on & (o["texLoc"][k] != -1)
+    return want, on, textured, dict(colour=colour, obj=obj, point=point, e=e, probes=probes, kind=kind, c=c, o=o, k=k)
